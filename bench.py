@@ -5,18 +5,23 @@ A "step" = one full pass of trgt_locus_batch over one batch of synthetic loci pe
 resident pre-filter + back-tracing ends-free WFA for the misses) -> length / cluster genotyping -> consensus BiWFA where
 needed -> motif-HMM labelling (MS / MC / AP).
 
-  python bench.py [--gpus 1] [--steps 100] [--warmup 3] [--config 2|3|4|5] [--loci N]
+  python bench.py [--gpus 1] [--steps 100] [--warmup 3] [--config 2|3|4|5] [--loci N] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps `value` is measured on, writes their outputs (--dump-outputs) and prints the
+result line.  --full adds everything else: the one-context loops and per-kernel times (roofline), the streaming figures, the CPU
+baseline and its parity sample, the N > 1 digest check, the side file, and at --config 0 the legs of configs 3 / 4 / 5 and the
+end-to-end leg.
 
 --config picks the BASELINE.json workload: 2 = configs[1] (10k single-motif STR loci, the configuration the metric is quoted on),
 3 = configs[2] (70 loci of the pathogenic catalog, alleles to 10 kb), 4 = configs[3] catalog mix (10k loci per GPU per step),
 5 = configs[4] (compound / N motifs through the cluster genotyper).
 
 `value` is measured with read and flank bytes resident in HBM before the timed region (only offsets / spans / alleles cross PCIe
-inside it); `value_streaming` is the same batches with the reads starting in pinned HOST memory, uploaded inside every call.
+inside it); `value_streaming` (--full) is the same batches with the reads starting in pinned HOST memory, uploaded inside every call.
 Loci shard embarrassingly: rank r generates and processes loci [r*L, (r+1)*L) (weak scaling, no collective on the data path);
-value = loci of all ranks * steps / max-over-ranks time.  At N > 1 every rank also recomputes its right neighbour's shard
+value = loci of all ranks * steps / max-over-ranks time.  With --full at N > 1 every rank also recomputes its right neighbour's shard
 (untimed) and the digests must agree: N-GPU output == 1-GPU output, byte for byte.
 """
 import argparse
@@ -165,7 +170,7 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 4, 5], help="BASELINE workload; 0 (default) = config 2 (the one the metric is quoted on) followed, at N = 1, by short legs of configs 3, 4 and 5 reported under \"configs\" in the same JSON line")
+    ap.add_argument("--config", type=int, default=0, choices=[0, 2, 3, 4, 5], help="BASELINE workload; 0 (default) = config 2 (the one the metric is quoted on) followed, with --full at N = 1, by short legs of configs 3, 4 and 5 reported under \"configs\" in the same JSON line")
     ap.add_argument("--loci", type=int, default=0, help="loci per GPU per step (default: by config)")
     ap.add_argument("--host-threads", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -176,9 +181,14 @@ def parse_args():
     ap.add_argument("--e2e-read-len", type=int, default=6000)
     ap.add_argument("--leg-steps", type=int, default=20, help="timed steps of each of the config 3 / 4 / 5 legs")
     ap.add_argument("--ws-limit-gb", type=float, default=0.0, help="workspace limit per context in GB (trgt_hip_set_workspace_limit; 0 = by config: the library's 32 GB, 8 GB for config 3)")
-    ap.add_argument("--detail", default="", help="where the full record goes (default: bench_detail.json next to bench.py, and gpurun_out/ when it exists); stdout carries the compact contract line only")
+    ap.add_argument("--detail", default="", help="with --full: where the full record goes (default: bench_detail.json next to bench.py); stdout carries the compact contract line only")
     ap.add_argument("--contexts", type=int, default=0, help="contexts per GPU (trgt_hip_pool / trgt_locus_batch_many): worker threads, one context each, draining the queue of steps, so that the tail of one step (results back, host-path loci, HMM) overlaps the flank location of the next ones; 0 = by config (4; 6 for configs 3 and 5); 1 = the blocking call only")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last of them returned on rank 0 (the per-locus results locus_result() reads) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="everything besides `value`: one-context loops, per-kernel times and roofline, streaming, CPU baseline and parity, N > 1 digest check, side file, and at --config 0 the legs and the end-to-end leg")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -210,7 +220,7 @@ def main():
         for k, v in plan_host(world, max(1, args.contexts), os.cpu_count() or 8, cpu_quota())[1].items():
             os.environ.setdefault(k, v)
     env = dict(torch=torch, dist=dist, rank=rank, local_rank=local_rank, world=world)
-    legs = args.config == 0 and not args.no_legs and world == 1
+    legs = args.full and args.config == 0 and not args.no_legs and world == 1
     first = argparse.Namespace(**vars(args))
     first.config = args.config or 2
     res = run_one(first, env)
@@ -221,16 +231,17 @@ def main():
         for cfg in (3, 4, 5):
             a = argparse.Namespace(**vars(args))
             a.config, a.steps, a.warmup, a.no_streaming, a.loci, a.contexts, a.ws_limit_gb = cfg, args.leg_steps, min(args.warmup, 2), True, 0, 0, 0.0
+            a.dump_outputs = ""
             t0 = time.perf_counter()
             r = run_one(a, env, cpu_seconds=6.0, all_cores=False)
             r["leg_wall_s"] = round(time.perf_counter() - t0, 1)
             res["configs"][str(cfg)] = r
-    if world == 1 and not args.no_e2e and args.config == 0:
+    if args.full and world == 1 and not args.no_e2e and args.config == 0:
         res["e2e"] = run_e2e(args, env)
     if rank == 0:
         # The full record (per-config detail, prose, every side figure) goes to a side file; stdout carries ONE compact contract line
         # (the single line had grown past what the driver keeps, and the round went unparsed).
-        detail_path = write_detail(res, args.detail)
+        detail_path = write_detail(res, args.detail) if args.full else None
         line = compact_line(res, detail_path)
         print(line)
         sys.stdout.flush()
@@ -271,7 +282,8 @@ def compact_line(res, detail_path=None):
         cfg["workload"] = _short(cfg["workload"], 200)
     out["config"] = cfg
     roof = _pick(res.get("roofline", {}), ROOFLINE_KEYS)
-    out["roofline"] = roof
+    if roof:  # (a plain run has none: the per-kernel times are --full)
+        out["roofline"] = roof
     if res.get("cpu_baseline"):
         cb = _pick(res["cpu_baseline"], CPU_KEYS)
         cb["sample"] = _short(cb.get("sample", ""), 120)
@@ -323,6 +335,52 @@ def write_detail(res, path=None):
         except OSError:
             pass
     return written
+
+
+DUMP_LIMIT = 64 << 20   # bytes of --dump-outputs
+
+
+def _ragged(off, n):
+    """Indexes of the slices [off[i], off[i] + n[i]), concatenated."""
+    off, n = np.asarray(off, np.int64), np.asarray(n, np.int64)
+    ends = np.cumsum(n)
+    return np.repeat(off - (ends - n), n) + np.arange(int(ends[-1]) if len(n) else 0)
+
+
+def output_arrays(batch, out, loci):
+    """What locus_result() hands a caller for the given loci of a finished batch, packed per field in locus order: float64, the
+    allele bytes float32.  Only what the library defines is read (present alleles, their spans and counts, the kept reads' classes)."""
+    loci = np.asarray(loci, np.int64)
+    n_al = out.n_alleles[loci].astype(np.int64)
+    s = (2 * np.repeat(loci, n_al) + _ragged(np.zeros(len(loci)), n_al))   # allele slots 2l + a, a < n_alleles[l]
+    lrb = np.asarray(batch["locus_read_begin"], np.int64)
+    r = _ragged(lrb[loci], lrb[loci + 1] - lrb[loci])
+    rank = out.read_rank[r]
+    f8 = lambda a: np.asarray(a, np.float64)
+    return {
+        "loci": f8(loci), "n_alleles": f8(n_al),
+        "allele_len": f8(out.allele_len[s]), "allele_seq": np.asarray(out.allele_blob[_ragged(out.allele_off[s], out.allele_len[s])], np.float32),
+        "allele_ci": f8(out.ci.reshape(-1, 2)[s]), "allele_num_spanning": f8(out.num_spanning[s]), "allele_purity": f8(out.purity[s]),
+        "allele_n_spans": f8(out.n_spans[s]), "allele_spans": f8(out.spans3.reshape(-1, 3)[_ragged(out.span_off[s], out.n_spans[s])]),
+        "allele_motif_counts": f8(out.motif_counts[_ragged(out.count_off[s], out.n_motifs[s // 2])]),
+        "read_rank": f8(rank), "read_span_start": f8(out.span_start[r]), "read_span_end": f8(out.span_end[r]),
+        "read_classification": f8(np.where(rank >= 0, out.classification[r], -1)),
+    }
+
+
+def dump_outputs(path, batch, out, limit=DUMP_LIMIT):
+    """--dump-outputs: output_arrays() of every locus as path/<name>.npy; above `limit` bytes, of a fixed seeded sample of loci
+    (halved until it fits)."""
+    n = int(batch["n_loci"])
+    loci = np.arange(n)
+    arrs = output_arrays(batch, out, loci)
+    while sum(a.nbytes for a in arrs.values()) > limit and len(loci) > 1:
+        loci = np.sort(np.random.default_rng(20250509).choice(n, len(loci) // 2, replace=False))
+        arrs = output_arrays(batch, out, loci)
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return arrs
 
 
 def run_e2e(args, env):
@@ -607,49 +665,46 @@ def run_one(args, env, cpu_seconds=20.0, all_cores=True):
             dist.barrier()
         torch.cuda.synchronize()
 
-    step()  # setup: primes the library's device-buffer pool and code objects (part of the untimed set-up, like the H2D upload)
-    ctx.timing_enable(True)  # per-kernel HIP events (roofline).  The HIP runtime spends a one-off ~9 ms in the second call after the
-    step()                   # first timing event is recorded on a stream (measured: tools/step_times.py timing), so two more
-    step()                   # set-up calls run with the events on before the warm-up proper
-    for _ in range(args.warmup):
-        step()
-    ctx.timing_reset()
     import gc
+    if args.full:
+        step()  # setup: primes the library's device-buffer pool and code objects (part of the untimed set-up, like the H2D upload)
+        ctx.timing_enable(True)  # per-kernel HIP events (roofline).  The HIP runtime spends a one-off ~9 ms in the second call after the
+        step()                   # first timing event is recorded on a stream (measured: tools/step_times.py timing), so two more
+        step()                   # set-up calls run with the events on before the warm-up proper
+        for _ in range(args.warmup):
+            step()
+        ctx.timing_reset()
     gc.collect()
     gc.disable()  # a generation-2 collection of the driver script's own objects showed up as a 30-40 ms pause in one call out of ~400
-    # ---- K steps on ONE context (the blocking call, batch after batch) ...
-    fence()
-    t0 = time.perf_counter()
-    marks = [t0]
-    for _ in range(args.steps):
-        step()
-        marks.append(time.perf_counter())  # (a call is synchronous: no extra synchronisation is added inside the timed region)
-    fence()
-    dt_single = time.perf_counter() - t0
     names = {k: n for n, k in (("flank_scan", 0), ("wfa_consensus", 1), ("hmm_viterbi", 2), ("wfa_flank", 3), ("wfa_flank_rest", 4), ("wfa_filter", 5), ("flank_window", 6))}
-    kt = {names[k]: ctx.timing_get(k) for k in names}
-    ctx.timing_enable(False)
-    dt_single_instrumented = dt_single
-    # ... and the same loop once more WITHOUT the timing events: recorded on the side streams of the HMM launches they keep launches
-    # that would run next to each other from overlapping (config 3: 43 against 30 ms per call), so the one-context figure that is
-    # reported is this one; the loop above is only where the per-kernel times (roofline) come from
-    n_plain = max(4, min(args.steps, 50))
-    step(); step()
-    fence()
-    t0 = time.perf_counter()
-    for _ in range(n_plain):
-        step()
-    fence()
-    dt_single = (time.perf_counter() - t0) * args.steps / n_plain
-    dt = dt_single
-    # ---- ... and through `contexts` worker threads, one context each, all on this rank's GPU, draining a queue of the same K steps:
-    #      a call's host-bound tail (results back, the few loci of the host path, HMM collection) and the kernels of its last stage
-    #      overlap the flank location of the next calls.  This is `value`; the per-kernel times below are then those of this region,
-    #      summed over the contexts.
-    # ---- ... and through `contexts` contexts on this rank's GPU behind one queue (trgt_hip_pool / trgt_locus_batch_many: one worker
+    if args.full:
+        # ---- K steps on ONE context (the blocking call, batch after batch) ...
+        fence()
+        t0 = time.perf_counter()
+        marks = [t0]
+        for _ in range(args.steps):
+            step()
+            marks.append(time.perf_counter())  # (a call is synchronous: no extra synchronisation is added inside the timed region)
+        fence()
+        dt_single = time.perf_counter() - t0
+        kt = {names[k]: ctx.timing_get(k) for k in names}
+        ctx.timing_enable(False)
+        dt_single_instrumented = dt_single
+        # ... and the same loop once more WITHOUT the timing events: recorded on the side streams of the HMM launches they keep launches
+        # that would run next to each other from overlapping (config 3: 43 against 30 ms per call), so the one-context figure that is
+        # reported is this one; the loop above is only where the per-kernel times (roofline) come from
+        n_plain = max(4, min(args.steps, 50))
+        step(); step()
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(n_plain):
+            step()
+        fence()
+        dt_single = (time.perf_counter() - t0) * args.steps / n_plain
+    # ---- `value`: through `contexts` contexts on this rank's GPU behind one queue (trgt_hip_pool / trgt_locus_batch_many: one worker
     #      thread per context inside the library), draining the same K steps: a call's tail (results back, the few loci of the host
-    #      path, HMM collection) and the kernels of its last stage overlap the flank location of the next calls.  This is `value`; the
-    #      per-kernel times below are then those of this region, summed over the contexts.
+    #      path, HMM collection) and the kernels of its last stage overlap the flank location of the next calls.  With --full the
+    #      per-kernel times below are then those of this region, summed over the contexts.  One context: K blocking calls.
     pool, kt_pool, cpus_busy = None, None, None
     if args.contexts > 1:
         pool = _lib.Pool([local_rank] * args.contexts)
@@ -659,11 +714,13 @@ def run_one(args, env, cpu_seconds=20.0, all_cores=True):
         outs_w = [locus.BatchOutputs(batch) for _ in range(args.contexts)]
         many = lambda n: locus.run_many(pool, [batch] * n, params, outs_w, flank_dev=flank_dev, reads_dev=reads_dev, out_per_context=True)
         # set-up of every context (buffer pools, code objects, first touch of its workspaces): at least 3 batches per context and 0.6 s
-        # (a fresh context runs at half speed for its first few hundred milliseconds on the host-heavy configs)
+        # (a fresh context runs at half speed for its first few hundred milliseconds on the host-heavy configs), then the warm-up steps
         t_w = time.perf_counter()
         many(3 * args.contexts)
         while time.perf_counter() - t_w < 0.6:
             many(2 * args.contexts)
+        if args.warmup > 0:
+            many(args.warmup)
         fence()
         import resource
         ru0 = resource.getrusage(resource.RUSAGE_SELF)
@@ -673,6 +730,22 @@ def run_one(args, env, cpu_seconds=20.0, all_cores=True):
         dt = time.perf_counter() - t0
         ru1 = resource.getrusage(resource.RUSAGE_SELF)
         cpus_busy = (ru1.ru_utime - ru0.ru_utime + ru1.ru_stime - ru0.ru_stime) / max(dt, 1e-9)  # host CPUs this rank kept busy while `value` was measured
+        last = outs_w[ran[-1]]  # (the context that ran the last step runs nothing after it)
+    else:
+        if not args.full:  # (--full warmed this context up above)
+            step()
+            for _ in range(args.warmup):
+                step()
+        fence()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        fence()
+        dt = time.perf_counter() - t0
+        last = out
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, batch, last)
+    if args.full and pool is not None:
         # per-kernel times of the same region, from a shorter instrumented pass
         for c in pool.contexts:
             c.timing_enable(True)
@@ -688,14 +761,15 @@ def run_one(args, env, cpu_seconds=20.0, all_cores=True):
         for c in pool.contexts:
             c.timing_enable(False)
     gc.enable()
-    step_ms = sorted(1e3 * (b - a) for a, b in zip(marks, marks[1:]))
     dt = shard.max_over_ranks(dt, dist if world > 1 else None, device="cuda")
-    dt_single = shard.max_over_ranks(dt_single, dist if world > 1 else None, device="cuda")
+    if args.full:
+        step_ms = sorted(1e3 * (b - a) for a, b in zip(marks, marks[1:]))
+        dt_single = shard.max_over_ranks(dt_single, dist if world > 1 else None, device="cuda")
 
     # ---- the same batches with the reads starting in pinned host memory, through the pipelined entry points: the upload of batch
     #      k + 1 (trgt_locus_batch_submit, copy stream) runs next to the kernels of batch k (trgt_locus_batch_wait)
     dt_stream = dt_stream_single = dt_stream4 = dt_stream4_single = None
-    if not args.no_streaming:
+    if args.full and not args.no_streaming:
         pins = [torch.from_numpy(batch["read_blob"]).pin_memory() for _ in range(2)]
         outs_s = [locus.BatchOutputs(batch) for _ in range(2)]
         n_s = max(4, min(args.steps, 40))
@@ -779,7 +853,7 @@ def run_one(args, env, cpu_seconds=20.0, all_cores=True):
 
     # ---- N > 1: every rank recomputes its right neighbour's shard; the digests must agree (N-GPU output == 1-GPU output)
     digest_check = None
-    if world > 1:
+    if args.full and world > 1:
         mine = shard.result_digest(out, n_loci)
         nb = (rank + 1) % world
         nbatch = make_batch(args.config, n_loci, nb * n_loci)
@@ -796,6 +870,18 @@ def run_one(args, env, cpu_seconds=20.0, all_cores=True):
         pool.close()
     res = None
     if rank == 0:
+        res = {
+            "metric": "loci/s", "value": round(world * n_loci * args.steps / dt, 1), "unit": "loci/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8+u8 packed (WFA pre-filter), u16 (WFA back-trace), f64 (HMM)",
+            "data": "synthetic",
+            "config": {"workload": WORKLOAD[args.config] % n_loci, "baseline_config": args.config,
+                       "steps_replay_one_batch": True,
+                       "loci_per_gpu": n_loci, "reads_per_locus": 30, "parallelism": "loci sharded across %d GPU(s), no collective" % world,
+                       "host_threads_per_context": host_threads, "contexts_per_gpu": args.contexts, "host_cores": cores, "host_cpu_quota": cpu_quota(),
+                       "host_threads_all_ranks": host_threads * args.contexts * world, "gpu_waits": ("poll, spin %s us, nap %s us" % (os.environ.get("TRGT_POLL_SPIN_US", "2000"), os.environ.get("TRGT_POLL_NAP_US", "20"))) if os.environ.get("TRGT_POLL_WAIT", "0") not in ("", "0") else "hipEventSynchronize (spins)", "host_cpus_busy_per_rank": round(cpus_busy, 2) if cpus_busy is not None else None, "workspace_limit_gb_per_context": args.ws_limit_gb or 32.0},
+        }
+    if rank == 0 and args.full:
         # wfa_filter: register-resident pre-filter over the alignments of reads too short to span their locus (>90 % of the wavefront
         # offsets); wfa_flank: the back-tracing kernel over the alignments the filter keeps; wfa_flank_rest: the other flank alignments
         # (on seeded windows, then the few that need the whole read); flank_scan: exact-match scan + segment search for the windows
@@ -857,27 +943,14 @@ def run_one(args, env, cpu_seconds=20.0, all_cores=True):
         valu_issue_frac = round(valu_insts * 4.0 / (num_cus * 4 * avg_ms * 1e-3 * CLOCK_GHZ * 1e9), 4) if valu_insts and avg_ms > 0 else None
         valu_peak = num_cus * VALU_LANES_PER_CU * CLOCK_GHZ * 1e9   # 32-bit integer lane-operations per second
         cells_per_s = cells / max(ms, 1e-9) * 1e3
-        res = {
-            "metric": "loci/s", "value": round(world * n_loci * args.steps / dt, 1), "unit": "loci/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 3),
+        res.update({
             "ms_per_step_single_context_min_median_max": [round(step_ms[0], 2), round(step_ms[len(step_ms) // 2], 2), round(step_ms[-1], 2)],  # rank 0
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8+u8 packed (WFA pre-filter), u16 (WFA back-trace), f64 (HMM)",
-            "data": "synthetic",
             "value_is": "HBM-resident, the K steps REPLAY ONE BATCH (the contexts of the pool read the same blob: the L2 / MALL see it more than once; nothing in the step is HBM-bound, and no result is kept between steps): read and flank bytes are in HBM before the timed region; value_streaming: every batch's reads start in pinned host memory and cross PCIe inside the timed region -- through the same worker contexts, each uploading its batch and then computing on it (single context: uploaded by trgt_locus_batch_submit next to the compute of the batch before, trgt_locus_batch_wait); value_streaming_bam4: the same with the reads as BAM 4-bit codes (TRGT_READS_BAM4), expanded in HBM",
             "value_streaming": round(world * n_loci / dt_stream, 1) if dt_stream else None,
             "value_streaming_single_context": round(world * n_loci / dt_stream_single, 1) if dt_stream else None,
             "value_streaming_bam4": round(world * n_loci / dt_stream4, 1) if dt_stream4 else None,
             "value_streaming_bam4_single_context": round(world * n_loci / dt_stream4_single, 1) if dt_stream4 else None,
             "value_single_context": round(world * n_loci * args.steps / dt_single, 1), "ms_per_step_single_context": round(1e3 * dt_single / args.steps, 3), "ms_per_step_single_context_with_timing_events": round(1e3 * dt_single_instrumented / args.steps, 3),
-            "config": {"workload": WORKLOAD[args.config] % n_loci, "baseline_config": args.config,
-                       # (the figures next to `value` that a reader of the parsed line needs: SURVEY 8(d)'s "first H2D to last D2H" rates and the blocking call)
-                       "value_streaming": round(world * n_loci / dt_stream, 1) if dt_stream else None,
-                       "value_streaming_bam4": round(world * n_loci / dt_stream4, 1) if dt_stream4 else None,
-                       "value_single_context": round(world * n_loci * args.steps / dt_single, 1), "ms_per_step_single_context": round(1e3 * dt_single / args.steps, 3),
-                       "steps_replay_one_batch": True,
-                       "loci_per_gpu": n_loci, "reads_per_locus": 30, "parallelism": "loci sharded across %d GPU(s), no collective" % world,
-                       "host_threads_per_context": host_threads, "contexts_per_gpu": args.contexts, "host_cores": cores, "host_cpu_quota": cpu_quota(),
-                       "host_threads_all_ranks": host_threads * args.contexts * world, "gpu_waits": ("poll, spin %s us, nap %s us" % (os.environ.get("TRGT_POLL_SPIN_US", "2000"), os.environ.get("TRGT_POLL_NAP_US", "20"))) if os.environ.get("TRGT_POLL_WAIT", "0") not in ("", "0") else "hipEventSynchronize (spins)", "host_cpus_busy_per_rank": round(cpus_busy, 2) if cpus_busy is not None else None, "workspace_limit_gb_per_context": args.ws_limit_gb or 32.0},
             "roofline": {"bound": "hbm", "kernel": dom, "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
                          # what the HBM counters saw (profiles/traffic.json: FETCH_SIZE + WRITE_SIZE per launch) as a fraction of peak: the utilisation proper
@@ -913,7 +986,11 @@ def run_one(args, env, cpu_seconds=20.0, all_cores=True):
             "work_per_step": {"flank_wfa_jobs": int(stats[0]), "flank_wfa_jobs_expensive": int(stats[14]), "filter_kept": int(stats[16]),
                               "filter_offsets": int(stats[17]), "consensus_jobs": int(stats[1]), "edit_distance_jobs": int(stats[15]),
                               "spanning_reads": int(stats[2]), "hmm_jobs": int(stats[3])},
-        }
+        })
+        # (the figures next to `value` that a reader of the parsed line needs: SURVEY 8(d)'s "first H2D to last D2H" rates and the blocking call)
+        res["config"].update({"value_streaming": round(world * n_loci / dt_stream, 1) if dt_stream else None,
+                              "value_streaming_bam4": round(world * n_loci / dt_stream4, 1) if dt_stream4 else None,
+                              "value_single_context": round(world * n_loci * args.steps / dt_single, 1), "ms_per_step_single_context": round(1e3 * dt_single / args.steps, 3)})
         if digest_check:
             res["multi_gpu_digest_check"] = digest_check
         if not args.no_cpu_baseline and world == 1:  # the CPU baseline is timed at N = 1 only

@@ -76,3 +76,49 @@ def test_contract_line_without_legs_or_baseline():
     full["multi_gpu_digest_check"] = {"ranks": 2, "shards_recomputed_on_another_gpu": 2, "digest_mismatches": 0}
     d = json.loads(bench.compact_line(full))
     assert d["multi_gpu_digest_check"]["digest_mismatches"] == 0 and "configs" not in d and d["config"]["loci_per_gpu"] == 10000
+
+
+def test_dumped_outputs_are_what_locus_result_returns(tmp_path):
+    # --dump-outputs: the arrays hold, locus by locus, what locus_result() gives a caller; above the size limit, a seeded sample of loci
+    import numpy as np
+    from trgt_amd import locus, synth
+    bench = _bench()
+    b = synth.generate(40, first_locus=7)
+    nl, nr = int(b["n_loci"]), int(b["n_reads"])
+    out = locus.BatchOutputs(b)
+    rng = np.random.default_rng(1)
+    for a, lo, hi in ((out.n_alleles, 0, 3), (out.allele_blob, 65, 91), (out.n_spans, 0, 4), (out.spans3, 0, 1000), (out.motif_counts, 0, 9),
+                      (out.ci, 0, 300), (out.num_spanning, 0, 30), (out.read_rank, -1, 30), (out.classification, 0, 4), (out.span_start, 0, 500),
+                      (out.span_end, 500, 1000)):
+        a[:] = rng.integers(lo, hi, a.size)
+    out.allele_len[:] = rng.integers(0, 9, 2 * nl)
+    out.purity[:] = rng.random(2 * nl)
+    d = bench.dump_outputs(str(tmp_path / "all"), b, out)
+    for k, v in d.items():
+        f = np.load(tmp_path / "all" / (k + ".npy"))
+        assert f.dtype in (np.float32, np.float64) and np.array_equal(f, v), k
+    assert sorted(os.listdir(tmp_path / "all")) == sorted(k + ".npy" for k in d)
+    al = sp = mc = s = rd = 0
+    for l in range(nl):
+        got = locus.locus_result(b, out, l)
+        assert d["loci"][l] == l and d["n_alleles"][l] == len(got.genotype)
+        for a in got.genotype:
+            n, ns, nc = len(a.seq), len(a.annotation.labels or []), len(a.annotation.motif_counts)
+            assert d["allele_len"][s] == n and bytes(d["allele_seq"][al:al + n].astype(np.uint8)) == a.seq
+            assert tuple(d["allele_ci"][s]) == a.ci and d["allele_num_spanning"][s] == a.num_spanning and d["allele_purity"][s] == a.annotation.purity
+            assert d["allele_n_spans"][s] == ns and [tuple(x) for x in d["allele_spans"][sp:sp + ns]] == [(x.motif_index, x.start, x.end) for x in a.annotation.labels or []]
+            assert list(d["allele_motif_counts"][mc:mc + nc]) == a.annotation.motif_counts
+            al, sp, mc, s = al + n, sp + ns, mc + nc, s + 1
+        k = int(b["locus_read_begin"][l + 1]) - int(b["locus_read_begin"][l])
+        rank = d["read_rank"][rd:rd + k]
+        kept = np.argsort(np.where(rank >= 0, rank, 1 << 30), kind="stable")[:int((rank >= 0).sum())]
+        assert list(kept) == got.reads and list(d["read_classification"][rd:rd + k][kept]) == got.classification
+        assert list(zip(d["read_span_start"][rd:rd + k][kept], d["read_span_end"][rd:rd + k][kept])) == got.tr_spans
+        rd += k
+    assert (al, sp, mc, s, rd) == (d["allele_seq"].size, len(d["allele_spans"]), d["allele_motif_counts"].size, d["allele_len"].size, nr)
+    # the size limit: a seeded sample of loci, the same in every run
+    small = sum(a.nbytes for a in d.values()) // 3
+    s1 = bench.dump_outputs(str(tmp_path / "s1"), b, out, limit=small)
+    s2 = bench.dump_outputs(str(tmp_path / "s2"), b, out, limit=small)
+    assert sum(a.nbytes for a in s1.values()) <= small and 0 < len(s1["loci"]) < nl
+    assert all(np.array_equal(s1[k], s2[k]) for k in s1)

@@ -18,7 +18,7 @@ def test_two_ranks_print_one_line_and_agree_on_each_others_shards():
     env = dict(os.environ, TRGT_BENCH_ONE_GPU="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1", "--contexts", "2",
-           "--loci", "1500", "--no-cpu-baseline", "--no-streaming"]
+           "--loci", "1500", "--no-cpu-baseline", "--no-streaming", "--full"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/e2e_in_bench; mkdir -p $O; cd $R
 i=0
 for flags in "--no-cpu-baseline --no-streaming --no-legs" "--no-streaming --no-legs" "--no-cpu-baseline --no-legs" "--no-cpu-baseline --no-streaming" ""; do
   i=$((i+1))
-  python bench.py --steps 20 --warmup 3 $flags --detail $O/d$i.json > $O/l$i.json 2> $O/e$i.log
+  python bench.py --full --steps 20 --warmup 3 $flags --detail $O/d$i.json > $O/l$i.json 2> $O/e$i.log
   python - $O/d$i.json "$flags" <<'PY'
 import json, sys
 e = json.load(open(sys.argv[1]))["e2e"]

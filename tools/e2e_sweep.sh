@@ -4,7 +4,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${1:-e2e_sweep}; mkdir -p $O; cd $R
 for cw in ${2:-3:0 3:16 5:12 5:16}; do
   c=${cw%%:*}; w=${cw##*:}
-  BENCH_INGEST_CALLERS=$c BENCH_INFLATE_WAVES=$w python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-streaming --no-legs --detail $O/detail_${c}_${w}.json > $O/line_${c}_$w.json 2> $O/err_${c}_$w.log
+  BENCH_INGEST_CALLERS=$c BENCH_INFLATE_WAVES=$w python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-streaming --no-legs --detail $O/detail_${c}_${w}.json > $O/line_${c}_$w.json 2> $O/err_${c}_$w.log
   python - $O/detail_${c}_${w}.json $c $w <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -3,5 +3,5 @@
 CFG=${1:-2}
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/oc; rm -rf $O; mkdir -p $O; cd $R
-rocprofv3 --kernel-trace --stats -d $O/kt -o b -- python bench.py --config $CFG --steps 20 --warmup 2 --contexts 1 --no-streaming --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+rocprofv3 --kernel-trace --stats -d $O/kt -o b -- python bench.py --full --config $CFG --steps 20 --warmup 2 --contexts 1 --no-streaming --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 python tools/rocprof_summary.py $(find $O/kt -name "*.db" | head -1) | head -16 | cut -c1-60,92-150
