@@ -437,6 +437,20 @@ const char* trgt_writer_last_error(const trgt_writer* w);
 /* ABI 10: BGZF blocks of the spanning BAM so far: out[0] deflated on the device (deflate_device), [1] declined by it (zlib took them), [2] by
  * zlib because no device was named or a flush held fewer than 16 full blocks.  A device deflate that FAILS fails trgt_writer_write. */
 void trgt_writer_device_stats(const trgt_writer* w, int64_t out[3]);
+/* The spanning-BAM records assembled on the GPU (additive to ABI 11): BamWriter::write (src/trgt/writers/write_bam.rs:72-144) with
+ * HiFiRead::clip_bases (src/trgt/reads/clip_bases.rs:9-120) as kernels over the per-read arrays trgt_ingest_params.ingest_device left in HBM,
+ * cut into BGZF blocks, checksummed and -- with deflate_device -- deflated there: only compressed payloads, CRCs and the tail of the stream
+ * (less than one block) come back; without deflate_device the assembled bytes come back once and zlib deflates them.  The VCF and the BAM
+ * are the files the writer writes without it, byte for byte.
+ * device >= 0: GPU ordinal (the one deflate_device names, when that is set); call after trgt_writer_open and before the first
+ * trgt_writer_write.  -1 = off (what open leaves).  No GPU, a bad ordinal, a writer without a BAM path: a TRGT_ERR_* and a message in
+ * trgt_writer_last_error (no silent host-only run).  A batch is assembled on the device when read_blob_dev != NULL and read_blob_device ==
+ * device; any other batch, and a batch in which the kernels flag a record (a CIGAR shorter than its read, more than 65535 operations, a
+ * contig missing from the header, results outside the read), is formatted by the host code as a whole -- which reports what it reports. */
+int trgt_writer_set_records_device(trgt_writer* w, int32_t device);
+/* out[0] batches whose records were assembled on the device, [1] batches formatted by the host, [2] the reason of the last such batch
+ * (1 no device arrays on that GPU, 2 a record the kernels flagged), [3] records assembled on the device, [4] their bytes */
+void trgt_writer_records_stats(const trgt_writer* w, int64_t out[5]);
 
 /* ------------------------------------------------- per-read helpers of the ingestion / writer steps, exported on their own
  * (host code; the functions trgt_ingest_* and trgt_writer_* use internally -- a host that keeps its own BAM reader can call them, and the

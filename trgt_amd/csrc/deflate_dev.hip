@@ -161,17 +161,20 @@ __global__ void __launch_bounds__(64) deflate_blocks_kernel(const uint8_t* __res
 
 }  // namespace defl
 
-int deflate_blocks_device(trgt_hip_ctx* c, int64_t n, const uint8_t* src, uint64_t src_bytes, const defl::BlockDesc* descs, uint8_t* dst, uint64_t dst_bytes, uint32_t* dst_len) {
+// src_on_device: `src` is memory of c's GPU already (64 bytes of slack behind src_bytes, every write to it finished): nothing goes up but the table
+int deflate_blocks_device(trgt_hip_ctx* c, int64_t n, const uint8_t* src, uint64_t src_bytes, const defl::BlockDesc* descs, uint8_t* dst, uint64_t dst_bytes, uint32_t* dst_len,
+                          bool src_on_device = false) {
   if (n <= 0) return TRGT_OK;
   TRGT_HIP_TRY(c, hipSetDevice(c->device));
   void *d_src = nullptr, *d_desc = nullptr, *d_dst = nullptr, *d_len = nullptr, *d_counter = nullptr, *d_scratch = nullptr;
   int rc;
   const unsigned grid = (unsigned)std::min<int64_t>(n, (int64_t)c->num_cus * 4);
-  if ((rc = dev_get(c, S_INF_SRC, (size_t)src_bytes + 64, &d_src)) || (rc = dev_get(c, S_INF_DESC, (size_t)n * sizeof(defl::BlockDesc), &d_desc)) ||
+  if ((rc = src_on_device ? TRGT_OK : dev_get(c, S_INF_SRC, (size_t)src_bytes + 64, &d_src)) || (rc = dev_get(c, S_INF_DESC, (size_t)n * sizeof(defl::BlockDesc), &d_desc)) ||
       (rc = dev_get(c, S_INF_DST, (size_t)dst_bytes + 64, &d_dst)) || (rc = dev_get(c, S_INF_STATUS, (size_t)n * 4 + 16, &d_len)) ||
       (rc = dev_get(c, S_INF_COUNTER, 16, &d_counter)) || (rc = dev_get(c, S_DEFL_SCRATCH, (size_t)grid * 64 * defl::WORDS_MAX * 4, &d_scratch)))
     return rc;
-  TRGT_HIP_TRY(c, hipMemcpyAsync(d_src, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
+  if (src_on_device) d_src = const_cast<uint8_t*>(src);
+  else TRGT_HIP_TRY(c, hipMemcpyAsync(d_src, src, (size_t)src_bytes, hipMemcpyHostToDevice, c->stream));
   TRGT_HIP_TRY(c, hipMemcpyAsync(d_desc, descs, (size_t)n * sizeof(defl::BlockDesc), hipMemcpyHostToDevice, c->stream));
   TRGT_HIP_TRY(c, hipMemsetAsync(d_counter, 0, 16, c->stream));
   hipLaunchKernelGGL(defl::deflate_blocks_kernel, dim3(grid), dim3(64), 0, c->stream, (const uint8_t*)d_src, (const defl::BlockDesc*)d_desc, (uint32_t)n, (uint8_t*)d_dst,
@@ -191,6 +194,15 @@ int deflate_blocks_device(trgt_hip_ctx* c, int64_t n, const uint8_t* src, uint64
   else if (widest > 0) TRGT_HIP_TRY(c, hipMemcpyAsync(dst, d_dst, (size_t)dst_bytes, hipMemcpyDeviceToHost, c->stream));
   TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
   return TRGT_OK;
+}
+
+
+// the writer's blocks when its records were assembled on the device (bam_records_dev.hip): n blocks of 0xFF00 bytes laid end to end at d_src
+// (memory of c's GPU), block k deflated into dst + k * slot (room for `cap` bytes each), its length into dst_len[k] (0: declined)
+int deflate_device_blocks_ff00(trgt_hip_ctx* c, int64_t n, const uint8_t* d_src, uint8_t* dst, uint64_t slot, uint32_t cap, uint32_t* dst_len) {
+  std::vector<defl::BlockDesc> d((size_t)n);
+  for (int64_t k = 0; k < n; ++k) d[(size_t)k] = defl::BlockDesc{(uint64_t)k * 0xFF00ull, (uint64_t)k * slot, 0xFF00u, cap};
+  return deflate_blocks_device(c, n, d_src, (uint64_t)n * 0xFF00ull, d.data(), dst, (uint64_t)(n - 1) * slot + cap + 8, dst_len, true);
 }
 
 }  // namespace trgt

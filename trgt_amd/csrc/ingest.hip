@@ -741,6 +741,18 @@ struct BatchStore {  // owner of the arrays a trgt_ingest_batch points to
   trgt_ingest_batch pub;
 };
 
+// (for the writers, trgt_amd/csrc/writers.hip: the device slab behind a device-ingested batch and its pinned mirror -- the per-read array at
+// host address a lies at dev + (a - pin) in HBM of GPU *device)
+namespace trgt {
+bool ingest_batch_slab(const trgt_ingest_batch* b, const void** dev, const void** pin, size_t* bytes, int* device) {
+  if (!b || !b->owner || !b->read_blob_dev) return false;
+  const BatchStore* S = reinterpret_cast<const BatchStore*>(b->owner);
+  if (&S->pub != b || !S->slab.dev || !S->slab.pin) return false;
+  *dev = S->slab.dev; *pin = S->slab.pin; *bytes = S->slab.cap; *device = S->slab.device;
+  return true;
+}
+}  // namespace trgt
+
 extern "C" {
 
 const char* trgt_ingest_last_error(const trgt_ingest* h) { return h ? h->err.c_str() : "null handle"; }

@@ -113,16 +113,17 @@ __device__ __forceinline__ uint32_t gf2_apply(const uint32_t* m, uint32_t v) {
 // One wave per block: lane l takes the 1024 bytes that end 1024 * l bytes before the block's end (the first, shorter slice falls to the
 // highest lane at work and starts from the CRC's initial register), then the lanes' remainders are combined pairwise: a remainder that
 // 1024 * 2^j more bytes follow is multiplied by x^(8 * 1024 * 2^j) mod P (a 32 x 32 bit matrix).  status[b]: 1 stays 1 when the CRC
-// matches, becomes 2 when it does not; 0 (declined by the inflate kernel) is left alone.
+// matches, becomes 2 when it does not; 0 (declined by the inflate kernel) is left alone.  With `out` (the writer: bam_records_dev.hip) nothing
+// is compared: out[b] gets the block's CRC-32.
 __global__ void __launch_bounds__(64) crc32_blocks_kernel(const uint8_t* __restrict__ data, const infl::BlockDesc* __restrict__ blocks, const uint32_t* __restrict__ want,
-                                                          uint32_t n_blocks, const CrcTables* __restrict__ tab, uint8_t* __restrict__ status) {
+                                                          uint32_t n_blocks, const CrcTables* __restrict__ tab, uint8_t* __restrict__ status, uint32_t* __restrict__ out) {
   __shared__ CrcTables sh;
   const int lane = lane_id();
   for (int i = lane; i < (int)(sizeof(CrcTables) / 4); i += 64) ((uint32_t*)&sh)[i] = ((const uint32_t*)tab)[i];
   __syncthreads();
   const uint32_t b = blockIdx.x;
   if (b >= n_blocks) return;
-  if (status[b] != 1) return;
+  if (!out && status[b] != 1) return;
   const infl::BlockDesc bd = blocks[b];
   const uint8_t* p0 = data + bd.dst_off;
   const uint32_t len = bd.dst_len;
@@ -144,7 +145,7 @@ __global__ void __launch_bounds__(64) crc32_blocks_kernel(const uint8_t* __restr
     const uint32_t up = (uint32_t)__shfl((int)r, (lane + (1 << j)) & 63);
     if ((lane & ((2 << j) - 1)) == 0) r ^= gf2_apply(sh.shift[j], up);
   }
-  if (lane == 0 && (r ^ 0xFFFFFFFFu) != want[b]) status[b] = 2;
+  if (lane == 0) { if (out) out[b] = r ^ 0xFFFFFFFFu; else if ((r ^ 0xFFFFFFFFu) != want[b]) status[b] = 2; }
 }
 
 // ------------------------------------------------------------------------------------------------ the reservoir's random stream
@@ -710,6 +711,14 @@ void make_crc_tables(CrcTables& T) {
 }
 }  // namespace
 
+// the same kernel for the writer's blocks (bam_records_dev.hip): CRC-32 of n blocks of d_data into d_out; d_tab holds crc32_tables_bytes()
+// bytes filled by crc32_tables_make
+size_t crc32_tables_bytes() { return sizeof(CrcTables); }
+void crc32_tables_make(void* host) { make_crc_tables(*(CrcTables*)host); }
+void crc32_blocks_launch(void* hip_stream, const uint8_t* d_data, const infl::BlockDesc* d_blocks, uint32_t n, const void* d_tab, uint32_t* d_out) {
+  if (n) hipLaunchKernelGGL(crc32_blocks_kernel, dim3(n), dim3(64), 0, (hipStream_t)hip_stream, d_data, d_blocks, (const uint32_t*)nullptr, n, (const CrcTables*)d_tab, (uint8_t*)nullptr, d_out);
+}
+
 class Slot {
  public:
   int device = -1;
@@ -804,7 +813,7 @@ int slot_run(Slot* s, const RunIn& in, SlabPool& pool, RunOut& out, std::string&
   trgt::inflate_launch((void*)st, (const uint8_t*)s->d_src.p, (const infl::BlockDesc*)s->d_blocks.p, nb, (uint8_t*)s->d_infl.p, (uint8_t*)s->d_status.p, (unsigned*)s->d_counter.p,
                        (unsigned)cus * waves_per_cu);
   if (nb) hipLaunchKernelGGL(crc32_blocks_kernel, dim3(nb), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const infl::BlockDesc*)s->d_blocks.p, (const uint32_t*)s->d_crc.p, nb,
-                             (const CrcTables*)s->d_tab.p, (uint8_t*)s->d_status.p);
+                             (const CrcTables*)s->d_tab.p, (uint8_t*)s->d_status.p, (uint32_t*)nullptr);
   ING_TRY(hipGetLastError());
   ING_TRY(hipMemcpyAsync(h_status, s->d_status.p, nb, hipMemcpyDeviceToHost, st));
   ING_TRY(slot_wait(s));

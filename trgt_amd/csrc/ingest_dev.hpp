@@ -10,7 +10,12 @@
 
 #include "inflate_dev.hpp"
 
+struct trgt_ingest_batch;
+
 namespace trgt {
+// ingest.hip: the slab of a device-ingested batch (false: the batch has none)
+bool ingest_batch_slab(const trgt_ingest_batch* b, const void** dev, const void** pin, size_t* bytes, int* device);
+
 namespace ingd {
 
 // One fetch of extract_reads: the window of a locus and its chunks of the .bai as positions in the inflated bytes of the call
@@ -68,6 +73,13 @@ void slot_destroy(Slot* s);
 uint8_t* slot_src(Slot* s, size_t bytes, std::string& err);   // pinned staging for the compressed bytes of a call (valid until the next call)
 // 0 ok (out.fallback says whether the results are usable), < 0 TRGT_ERR_*
 int slot_run(Slot* s, const RunIn& in, SlabPool& pool, RunOut& out, std::string& err);
+
+
+// crc32_blocks_kernel for another stage's blocks (the writer's BGZF blocks, bam_records_dev.hip): d_out[b] = CRC-32 of d_data[dst_off .. + dst_len)
+// of block b (src_off / src_len unused; 3 bytes of slack behind the data).  d_tab: crc32_tables_bytes() device bytes, a copy of crc32_tables_make's.
+size_t crc32_tables_bytes();
+void crc32_tables_make(void* host);
+void crc32_blocks_launch(void* hip_stream, const uint8_t* d_data, const infl::BlockDesc* d_blocks, uint32_t n, const void* d_tab, uint32_t* d_out);
 
 }  // namespace ingd
 }  // namespace trgt

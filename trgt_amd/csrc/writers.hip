@@ -6,6 +6,7 @@
 // Input: a batch of the native ingestion (trgt_ingest_batch: catalog fields, clipped reads with their HiFiRead fields) and the result
 // arrays trgt_locus_batch filled for it.  The reference writes through htslib; here VCF lines are formatted directly (BGZF-compressed when
 // the path ends in .gz -- the reference's bcf::Writer compresses) and BAM records are encoded and BGZF-compressed with zlib.
+// trgt_writer_set_records_device: the records of a device-ingested batch are assembled by bam_records_dev.hip's kernels instead (same bytes).
 #include <zlib.h>
 
 #include <algorithm>
@@ -20,7 +21,9 @@
 #include <thread>
 #include <vector>
 
+#include "bam_records_dev.hpp"
 #include "crc32_fast.hpp"
+#include "ingest_dev.hpp"
 #include "../../include/trgt_hip.h"
 
 extern "C" {
@@ -54,19 +57,20 @@ struct BgzfOut {  // a file, plain or as a series of BGZF blocks (cut every 0xFF
   }
   bool block(const uint8_t* d, size_t n) { std::vector<uint8_t> out; return deflate_block(d, n, out, level) && std::fwrite(out.data(), 1, out.size(), f) == out.size(); }
   // a BGZF block around a payload that is deflated already (trgt_deflate_blocks): header, payload, CRC-32 and size of the data
-  static void frame_block(const uint8_t* d, size_t n, const uint8_t* payload, size_t clen, std::vector<uint8_t>& out) {
+  static void frame_block(const uint8_t* d, size_t n, const uint8_t* payload, size_t clen, std::vector<uint8_t>& out) { frame_block(n ? trgt::crc32_fast(d, n) : 0u, n, payload, clen, out); }
+  static void frame_block(uint32_t crc, size_t n, const uint8_t* payload, size_t clen, std::vector<uint8_t>& out) {
     const size_t total = 18 + clen + 8;
     out.resize(total);
     static const uint8_t head[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
     std::memcpy(out.data(), head, 16);
     out[16] = (uint8_t)((total - 1) & 0xFF); out[17] = (uint8_t)((total - 1) >> 8);
     std::memcpy(out.data() + 18, payload, clen);
-    const uint32_t crc = n ? trgt::crc32_fast(d, n) : 0u;
     for (int i = 0; i < 4; ++i) { out[18 + clen + i] = (uint8_t)(crc >> (8 * i)); out[22 + clen + i] = (uint8_t)((uint32_t)n >> (8 * i)); }
   }
   trgt_hip_ctx* dev = nullptr;   // trgt_writer_params.deflate_device: the full blocks of a flush are deflated on this context's GPU
   std::string dev_err;           // a device deflate that FAILED fails the write (no silent host-only run, like ingest_device); this says why
-  int64_t n_dev = 0, n_declined = 0, n_host = 0;  // blocks the device deflated / declined (zlib took them) / zlib deflated because the flush was too small or no device was named
+  std::atomic<int64_t> n_dev{0}, n_declined{0}, n_host{0};  // (read by trgt_writer_device_stats while the write-behind thread may run) blocks the device deflated / declined (zlib took them) / zlib deflated because the flush was too small or no device was named
+  std::atomic<int64_t> link_up{0}, link_down{0};  // bytes the BAM's blocks moved to / from the device so far (TRGT_WRITER_TRACE)
   std::vector<uint8_t> dev_out; std::vector<uint64_t> dev_soff, dev_doff; std::vector<uint32_t> dev_slen, dev_cap, dev_len;
   // the full blocks of buf: deflated by `threads` workers (a block is independent of its neighbours) -- or on the GPU in one go, the
   // workers then only frame them (CRC-32) and deflate what the device declined -- written in order
@@ -83,7 +87,9 @@ struct BgzfOut {  // a file, plain or as a series of BGZF blocks (cut every 0xFF
       const int rc = trgt_deflate_blocks(dev, (int64_t)nb, buf.data(), dev_soff.data(), dev_slen.data(), dev_out.data(), dev_doff.data(), dev_cap.data(), dev_len.data());
       if (rc != TRGT_OK) { dev_err = std::string("deflate_device: ") + trgt_hip_last_error(dev); return false; }
       on_dev = true;
-      for (size_t k = 0; k < nb; ++k) { if (dev_len[k] > 0 && dev_len[k] + 26u <= 0x10000u) ++n_dev; else ++n_declined; }
+      uint32_t widest = 0;
+      for (size_t k = 0; k < nb; ++k) { if (dev_len[k] > 0 && dev_len[k] + 26u <= 0x10000u) ++n_dev; else ++n_declined; widest = std::max(widest, dev_len[k]); }
+      link_up += (int64_t)(nb * 0xFF00 + nb * 24); link_down += (int64_t)(nb * 4 + nb * (((size_t)widest + 3) & ~(size_t)3));
     } else n_host += (int64_t)nb;
     auto work = [&]() {
       try {
@@ -180,8 +186,12 @@ struct trgt_writer {
   // caller formats the next batch; one batch in flight; what that thread reports is returned by the next write or by the close
   bool write_behind = false;
   std::thread bg; int bg_rc = TRGT_OK; std::string bg_err;
+  // trgt_writer_set_records_device: the records of the batches that carry device arrays on GPU rec_device are assembled there
+  trgt::brec::Engine* rec = nullptr; int32_t rec_device = -1, dev_ordinal = -1;
+  std::atomic<int64_t> rec_stats[5] = {{0}, {0}, {0}, {0}, {0}};
+  bool wrote = false;
   int bg_wait() { if (bg.joinable()) bg.join(); if (bg_rc != TRGT_OK && !bg_err.empty()) { err = bg_err; bg_err.clear(); } const int rc = bg_rc; bg_rc = TRGT_OK; return rc; }
-  ~trgt_writer() { if (bg.joinable()) bg.join(); if (dev) trgt_hip_destroy(dev); }
+  ~trgt_writer() { if (bg.joinable()) bg.join(); if (rec) trgt::brec::engine_destroy(rec); if (dev) trgt_hip_destroy(dev); }
 };
 
 extern "C" {
@@ -189,7 +199,27 @@ extern "C" {
 const char* trgt_writer_last_error(const trgt_writer* w) { return w ? w->err.c_str() : "null handle"; }
 // ABI 10: BGZF blocks of the spanning BAM so far -- out[0] deflated on the device, [1] declined by it (zlib took them), [2] deflated by zlib
 // because no device was named or the flush held fewer than 16 full blocks
-void trgt_writer_device_stats(const trgt_writer* w, int64_t out[3]) { if (w && out) { out[0] = w->bam.n_dev; out[1] = w->bam.n_declined; out[2] = w->bam.n_host; } }
+void trgt_writer_device_stats(const trgt_writer* w, int64_t out[3]) { if (w && out) { out[0] = w->bam.n_dev.load(); out[1] = w->bam.n_declined.load(); out[2] = w->bam.n_host.load(); } }
+// the records of device-ingested batches assembled on GPU `device` (bam_records_dev.hip); see include/trgt_hip.h
+int trgt_writer_set_records_device(trgt_writer* w, int32_t device) {
+  if (!w) return TRGT_ERR_INVALID;
+  try {
+    auto bad = [&](int rc, const std::string& m) { w->err = m; return rc; };
+    if (w->wrote) return bad(TRGT_ERR_INVALID, "trgt_writer_set_records_device: called after the first trgt_writer_write");
+    if (device < 0) { if (w->rec) { trgt::brec::engine_destroy(w->rec); w->rec = nullptr; } w->rec_device = -1; return TRGT_OK; }
+    if (!w->has_bam) return bad(TRGT_ERR_INVALID, "trgt_writer_set_records_device: records_device " + std::to_string(device) + " on a writer without a spanning BAM");
+    if (w->dev && w->dev_ordinal != device)
+      return bad(TRGT_ERR_INVALID, "trgt_writer_set_records_device: records_device " + std::to_string(device) + " and deflate_device " + std::to_string(w->dev_ordinal) + " must name the same GPU");
+    std::string e;
+    int n = 0;
+    trgt::brec::Engine* eng = trgt::brec::engine_create(device, e, &n);
+    if (!eng) return bad(n <= 0 ? TRGT_ERR_NO_DEVICE : TRGT_ERR_INVALID, "trgt_writer_set_records_device: " + e);
+    if (w->rec) trgt::brec::engine_destroy(w->rec);
+    w->rec = eng; w->rec_device = device;
+    return TRGT_OK;
+  } catch (const std::exception& e) { w->err = std::string("trgt_writer_set_records_device: ") + e.what(); return TRGT_ERR_NOMEM; }
+}
+void trgt_writer_records_stats(const trgt_writer* w, int64_t out[5]) { if (w && out) for (int i = 0; i < 5; ++i) out[i] = w->rec_stats[i].load(); }
 
 void trgt_writer_default_params(trgt_writer_params* p) {
   if (!p) return;
@@ -208,7 +238,7 @@ static int writer_open_impl(const trgt_ingest* src, const trgt_writer_params* p,
   w->bam.level = std::min(9, std::max(0, p->bam_compress_level));
   if (p->deflate_device >= 0 && bam_path) {  // the spanning BAM's blocks on the GPU (the VCF stays with zlib: it is small)
     if (trgt_hip_create(p->deflate_device, &w->dev) != TRGT_OK) { const std::string m = w->dev ? trgt_hip_last_error(w->dev) : "no such device"; if (w->dev) { trgt_hip_destroy(w->dev); w->dev = nullptr; } return bad("deflate_device: " + m); }
-    w->bam.dev = w->dev;
+    w->bam.dev = w->dev; w->dev_ordinal = p->deflate_device;
   }
   const std::string prog = p->program ? p->program : "trgt", ver = p->version ? p->version : "", cl = p->command_line ? p->command_line : "";
   w->sample = p->sample_name ? p->sample_name : "sample";
@@ -259,6 +289,8 @@ static int writer_write_impl(trgt_writer* w, const trgt_ingest_batch* b, const t
   if (!o->n_alleles || !o->allele_blob || !o->allele_off || !o->allele_len || !o->ci || !o->num_spanning || !o->classification || !o->read_rank ||
       !o->span_start || !o->span_end || !o->spans3 || !o->span_off || !o->n_spans || !o->motif_counts || !o->count_off || !o->purity)
     return bad("trgt_writer_write: incomplete result arrays");
+  w->wrote = true;
+  bool host_records = true;  // false: the records of this batch are assembled on the device (records_device), format_locus gives the VCF line only
   // One locus: its VCF line and its spanning-BAM records, appended to the caller's buffers (loci are independent: a batch is formatted
   // by w->threads workers over contiguous ranges of loci, and the pieces are written in locus order).
   auto format_locus = [&](int64_t l, std::string& lines, std::vector<uint8_t>& recs, std::vector<uint8_t>& rec, std::string& err) -> bool {
@@ -361,7 +393,7 @@ static int writer_write_impl(trgt_writer* w, const trgt_ingest_batch* b, const t
     }
     lines += line;
     // ---- spanning reads (write_bam.rs:72-144)
-    if (!w->has_bam) return true;
+    if (!w->has_bam || !host_records) return true;
     int tid = -1;
     for (size_t i = 0; i < w->contigs.size(); ++i) if (w->contigs[i] == contig) { tid = (int)i; break; }
     if (tid < 0) return bad("contig " + contig + " is not in the BAM header");
@@ -415,7 +447,7 @@ static int writer_write_impl(trgt_writer* w, const trgt_ingest_batch* b, const t
   const int64_t nl = b->n_loci;
   static const bool trace = std::getenv("TRGT_WRITER_TRACE") != nullptr;  // phase times on stderr
   auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
+  double t0 = now();
   const int nt = (int)std::max<int64_t>(1, std::min<int64_t>(w->threads, nl / 16));
   std::vector<std::string> lines((size_t)nt), errs((size_t)nt);
   std::vector<std::vector<uint8_t>> recs((size_t)nt);
@@ -425,12 +457,113 @@ static int writer_write_impl(trgt_writer* w, const trgt_ingest_batch* b, const t
       for (int64_t l = nl * t / nt; l < nl * (t + 1) / nt; ++l) if (!format_locus(l, lines[(size_t)t], recs[(size_t)t], rec, errs[(size_t)t])) return;
     } catch (const std::exception& e) { errs[(size_t)t] = std::string("trgt_writer_write: ") + e.what(); }
   };
-  if (nt <= 1) work(0);
-  else { std::vector<std::thread> th; for (int t = 0; t < nt; ++t) th.emplace_back(work, t); for (auto& t : th) t.join(); }
+  auto format_all = [&]() {
+    for (int t = 0; t < nt; ++t) { lines[(size_t)t].clear(); errs[(size_t)t].clear(); recs[(size_t)t].clear(); }
+    if (nt <= 1) work(0);
+    else { std::vector<std::thread> th; for (int t = 0; t < nt; ++t) th.emplace_back(work, t); for (auto& t : th) t.join(); }
+  };
+  // ---- records_device: the records of a batch whose per-read arrays lie in HBM of that GPU are assembled there (bam_records_dev.hip); any
+  // other batch, and a batch the kernels flag, goes through the host code below and is counted with its reason
+  int host_reason = 0;
+  if (w->rec && w->has_bam) {
+    namespace br = trgt::brec;
+    const void *sd = nullptr, *sp = nullptr; size_t sbytes = 0; int sdev = -1;
+    br::BatchDev D;
+    bool mapped = b->read_blob_dev != nullptr && b->read_blob_device == w->rec_device && trgt::ingest_batch_slab(b, &sd, &sp, &sbytes, &sdev) && sdev == w->rec_device;
+    auto at = [&](const void* host, auto** out) {  // the device address of an array of the pinned mirror
+      const uintptr_t h = (uintptr_t)host, p0 = (uintptr_t)sp;
+      if (!host || h < p0 || h >= p0 + sbytes) { mapped = false; return; }
+      *out = reinterpret_cast<std::remove_reference_t<decltype(*out)>>((uintptr_t)sd + (h - p0));
+    };
+    if (mapped) {
+      D.n_reads = b->n_reads;
+      at(b->read_off, &D.read_off); at(b->read_len, &D.read_len); at(b->read_blob, &D.reads); at(b->qual_blob, &D.quals); at(b->name_blob, &D.names); at(b->name_off, &D.name_off);
+      at(b->read_qual, &D.rq); at(b->is_reverse, &D.is_reverse); at(b->mapq, &D.mapq); at(b->hp_tag, &D.hp); at(b->start_offset, &D.start_offset); at(b->end_offset, &D.end_offset);
+      at(b->mismatch_offsets, &D.snp); at(b->mismatch_off, &D.snp_off); at(b->meth, &D.meth); at(b->meth_off, &D.meth_off); at(b->has_meth, &D.has_meth); at(b->cigar, &D.cig);
+      at(b->cigar_off, &D.cig_off); at(b->cigar_ref_pos, &D.cig_ref_pos);
+    }
+    if (!mapped) host_reason = 1;
+    else {
+      host_records = false;
+      format_all();  // the VCF lines (host: small, and AM needs the results' doubles)
+      bool vcf_ok = true;
+      for (int t = 0; t < nt; ++t) if (!errs[(size_t)t].empty()) vcf_ok = false;
+      // the kept reads in record order (the `kept` vector of format_locus) with their results; per locus the contig's tid and the id text
+      std::vector<br::RecIn> rin; std::vector<br::LocusIn> lin((size_t)nl); std::string ids;
+      for (int64_t l = 0; vcf_ok && l < nl; ++l) {
+        const char* cn = b->contig_blob + b->contig_off[l]; const size_t cl = (size_t)(b->contig_off[l + 1] - b->contig_off[l]);
+        int tid = -1;
+        for (size_t i = 0; i < w->contigs.size(); ++i) if (w->contigs[i].size() == cl && std::memcmp(w->contigs[i].data(), cn, cl) == 0) { tid = (int)i; break; }
+        if (tid < 0) { vcf_ok = false; break; }  // (the host path reports it)
+        lin[(size_t)l] = br::LocusIn{tid, (uint32_t)ids.size(), (uint32_t)(b->id_off[l + 1] - b->id_off[l])};
+        ids.append(b->id_blob + b->id_off[l], b->id_off[l + 1] - b->id_off[l]);
+        const uint64_t r0 = b->locus_read_begin[l], r1 = b->locus_read_begin[l + 1];
+        if (r1 > (uint64_t)b->n_reads || r0 > r1) { vcf_ok = false; break; }
+        std::vector<uint64_t> kept;
+        for (uint64_t r = r0; r < r1; ++r) if (o->read_rank[r] >= 0) { if ((size_t)o->read_rank[r] >= kept.size()) kept.resize((size_t)o->read_rank[r] + 1, r0); kept[(size_t)o->read_rank[r]] = r; }
+        for (uint64_t r : kept) rin.push_back(br::RecIn{(uint32_t)r, (uint32_t)l, o->span_start[r], o->span_end[r], (int32_t)o->classification[r]});
+      }
+      if (!vcf_ok) host_reason = 2;
+      else {
+        const double t1 = now();
+        if (w->write_behind) { if (const int prc = w->bg_wait()) return prc; }  // (the tail of the stream is the flush's before this one)
+        br::Assembled A; std::string e;
+        if (const int arc = br::assemble(w->rec, D, rin.data(), rin.size(), lin.data(), lin.size(), ids.data(), ids.size(), (uint32_t)w->flank_len, w->keep_unmapped, w->bam.buf.data(),
+                                         w->bam.buf.size(), A, e)) { w->err = "trgt_writer_write: " + e; return arc; }
+        if (A.flags) host_reason = 2;
+        else {
+          const double t2 = now();
+          ++w->rec_stats[0]; w->rec_stats[3] += (int64_t)A.n_records; w->rec_stats[4] += (int64_t)A.rec_bytes;
+          w->bam.link_up += (int64_t)A.h2d_bytes;
+          size_t vcf_bytes = 0; for (int t = 0; t < nt; ++t) vcf_bytes += lines[(size_t)t].size();
+          // CRC-32, deflate, what comes back, the files: nothing of the batch or of the results is referenced from here on
+          auto flush_dev = [t0, t1, t2, now, nl, nt, vcf_bytes, A](trgt_writer* ww, std::vector<std::string>& ln, std::string& msg) -> int {
+            for (auto& s : ln) if (!s.empty() && !ww->vcf.append(s.data(), s.size())) { msg = "cannot write the VCF"; return TRGT_ERR_INVALID; }
+            if (!ww->vcf.flush()) { msg = "cannot write the VCF"; return TRGT_ERR_INVALID; }
+            BgzfOut& bo = ww->bam;
+            br::Finished Fi; std::string e2;
+            if (const int frc = br::finish(ww->rec, bo.dev, 16, Fi, e2)) { msg = e2; return frc; }
+            bo.link_down += (int64_t)Fi.d2h_bytes;
+            if (!Fi.deflated) {  // zlib: the stream is the buffer (what it held is the stream's head)
+              bo.buf.assign(Fi.raw, Fi.raw + Fi.raw_bytes);
+              if (!bo.flush()) { msg = bo.dev_err.empty() ? "cannot write the BAM" : bo.dev_err; return TRGT_ERR_INVALID; }
+            } else {
+              bo.link_up += (int64_t)(Fi.n_blocks * 24);
+              std::vector<uint8_t> out;
+              for (uint64_t k = 0; k < Fi.n_blocks; ++k) {
+                const bool took = Fi.len[k] > 0 && Fi.len[k] + 26u <= 0x10000u;
+                if (took) { ++bo.n_dev; BgzfOut::frame_block(Fi.crc[k], 0xFF00, Fi.payload + k * 0x10000, Fi.len[k], out); }
+                else { ++bo.n_declined; if (!BgzfOut::deflate_block(Fi.raw + Fi.raw_at[k], 0xFF00, out, bo.level)) { msg = "cannot write the BAM"; return TRGT_ERR_INVALID; } }
+                if (std::fwrite(out.data(), 1, out.size(), bo.f) != out.size()) { msg = "cannot write the BAM"; return TRGT_ERR_INVALID; }
+              }
+              bo.buf.assign(Fi.tail, Fi.tail + Fi.tail_bytes);
+            }
+            if (trace) std::fprintf(stderr, "[writer] %lld loci, %d threads: formatting %.1f ms (%zu B of VCF; %llu B of BAM records in %llu records on the device: %.1f ms of it), deflate + write %.1f ms, link %lld B up / %lld B down so far\n",
+                                    (long long)nl, nt, t2 - t0, vcf_bytes, (unsigned long long)A.rec_bytes, (unsigned long long)A.n_records, t2 - t1, now() - t2, (long long)bo.link_up.load(), (long long)bo.link_down.load());
+            return TRGT_OK;
+          };
+          if (w->write_behind) {
+            auto ln = std::make_shared<std::vector<std::string>>(std::move(lines));
+            w->bg = std::thread([w, ln, flush_dev]() {
+              try { std::string msg; w->bg_rc = flush_dev(w, *ln, msg); if (w->bg_rc != TRGT_OK) w->bg_err = msg; }
+              catch (const std::exception& e) { w->bg_rc = TRGT_ERR_NOMEM; w->bg_err = std::string("trgt_writer_write: ") + e.what(); }
+            });
+            return TRGT_OK;
+          }
+          std::string msg;
+          if (const int frc = flush_dev(w, lines, msg)) { w->err = msg; return frc; }
+          return TRGT_OK;
+        }
+      }
+    }
+    host_records = true; t0 = now();
+    ++w->rec_stats[1]; w->rec_stats[2] = host_reason;
+  }
+  format_all();
   const double t1 = now();
   size_t vcf_bytes = 0, bam_bytes = 0;
   for (int t = 0; t < nt; ++t) { vcf_bytes += lines[(size_t)t].size(); bam_bytes += recs[(size_t)t].size(); }
-  struct Tr { bool on; double t0, t1; int64_t nl; int nt; size_t v, b; decltype(now)& now; ~Tr() { if (on) std::fprintf(stderr, "[writer] %lld loci, %d threads: formatting %.1f ms (%zu B of VCF, %zu B of BAM records), deflate + write %.1f ms\n", (long long)nl, nt, t1 - t0, v, b, now() - t1); } } tr{trace, t0, t1, nl, nt, vcf_bytes, bam_bytes, now};
+  struct Tr { bool on; double t0, t1; int64_t nl; int nt; size_t v, b; decltype(now)& now; BgzfOut& bo; ~Tr() { if (on) std::fprintf(stderr, "[writer] %lld loci, %d threads: formatting %.1f ms (%zu B of VCF, %zu B of BAM records), deflate + write %.1f ms, link %lld B up / %lld B down so far\n", (long long)nl, nt, t1 - t0, v, b, now() - t1, (long long)bo.link_up.load(), (long long)bo.link_down.load()); } } tr{trace, t0, t1, nl, nt, vcf_bytes, bam_bytes, now, w->bam};
   // what precedes the first failing locus is written, as a serial writer would have; msg: what went wrong (empty: nothing)
   auto flush_pieces = [](trgt_writer* ww, std::vector<std::string>& ln, std::vector<std::vector<uint8_t>>& rc, std::vector<std::string>& er, std::string& msg) -> int {
     for (size_t t = 0; t < ln.size(); ++t) {

@@ -17,7 +17,7 @@ class WriterParams(C.Structure):
 
 class Writer:
     def __init__(self, reader, vcf_path, bam_path=None, output_flank_len=50, sample_name="sample", program="trgt", version="3.0.0",
-                 command_line="", keep_unmapped_flag=1, threads=0, bam_compress_level=6, deflate_device=-1, write_behind=0):
+                 command_line="", keep_unmapped_flag=1, threads=0, bam_compress_level=6, deflate_device=-1, write_behind=0, records_device=-1):
         L = _lib.lib()
         L.trgt_writer_open.argtypes = [C.c_void_p, C.POINTER(WriterParams), C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
         L.trgt_writer_write.argtypes = [C.c_void_p, C.POINTER(IngestBatch), C.c_void_p]
@@ -35,6 +35,14 @@ class Writer:
                 L.trgt_writer_close(self.handle)
                 self.handle = C.c_void_p()
             raise _lib.TrgtHipError("trgt_writer_open: %s" % msg)
+        if records_device >= 0:  # the spanning-BAM records of device-ingested batches are assembled on that GPU (same files)
+            L.trgt_writer_set_records_device.argtypes = [C.c_void_p, C.c_int32]
+            rc = L.trgt_writer_set_records_device(self.handle, int(records_device))
+            if rc != 0:
+                msg = L.trgt_writer_last_error(self.handle).decode()
+                L.trgt_writer_close(self.handle)
+                self.handle = C.c_void_p()
+                raise _lib.TrgtHipError("trgt_writer_set_records_device: %s" % msg)
 
     def write(self, batch, outputs):
         """batch: a dict of ingest.Reader.batch(..., keep_native=True); outputs: the locus.BatchOutputs trgt_locus_batch filled for it"""
@@ -50,6 +58,15 @@ class Writer:
         self._L.trgt_writer_device_stats.restype = None
         self._L.trgt_writer_device_stats(self.handle, v)
         return dict(device=int(v[0]), declined=int(v[1]), host=int(v[2]))
+
+    def records_stats(self):
+        """trgt_writer_records_stats: batches whose spanning-BAM records were assembled on the device / formatted by the host, the reason of
+        the last host-formatted one (1 no device arrays on that GPU, 2 a record the kernels flagged), records and bytes assembled on the device."""
+        v = (C.c_int64 * 5)()
+        self._L.trgt_writer_records_stats.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        self._L.trgt_writer_records_stats.restype = None
+        self._L.trgt_writer_records_stats(self.handle, v)
+        return dict(device_batches=int(v[0]), host_batches=int(v[1]), host_reason=int(v[2]), records=int(v[3]), bytes=int(v[4]))
 
     def close(self):
         if self.handle:
