@@ -166,7 +166,7 @@ def main():
                 n_filt += 1
                 continue
             reads.append(r)
-        assert len(reads) < 3 * MAX_DEPTH, "reservoir sampling would kick in; not restated here"
+        assert len(reads) < 3 * MAX_DEPTH, "reservoir sampling would kick in: tests/pyreads.py restates its random stream (block function pinned by published vectors, the rest cross-checked but not pinned by rand), this generator does not"
         region = (start - 2 * FLANK_LEN, end + 2 * FLANK_LEN)
         clipped = [s for s in (clip_to_region(r, region) for r in reads) if s is not None]
         out.append(dict(id=fields["ID"], motifs=fields["MOTIFS"].split(","), struc=fields["STRUC"], contig=contig,

@@ -8,8 +8,15 @@ Reference (PacificBiosciences/trgt v3.0.0):
 
 Plain Python over zlib (BGZF is a multi-member gzip stream): the reference does this through htslib, which is I/O plumbing outside
 the hot path; nothing here touches the GPU.  Not mirrored: methylation tags (MM/ML), SNV mismatch offsets, HP tags -- the locus path
-behind them (get_meth, genotype_flank) is out of scope, so reads carry bases and the rq tag only; reservoir sampling of
-loci deeper than 3 x max_depth (tr.rs:311-335) needs Rust's StdRng stream and raises NotImplementedError.
+behind them (get_meth, genotype_flank) is out of scope, so reads carry bases and the rq tag only.
+
+Reservoir sampling of loci deeper than 3 x max_depth (tr.rs:311-335) draws from rand 0.9's StdRng::seed_from_u64(42).  Its stream is
+restated below in plain Python integers from the published algorithms (ChaCha: Bernstein 2008 / RFC 8439 2.1-2.3; PCG32 XSH-RR: O'Neill
+2014; Canon's range sampling as rand 0.9 documents it), on its own and not from trgt_amd/csrc/ingest.hip, so that it can stand as a
+third party between the host's StdRng and the kernel's DevRng.  What that gives: chacha_block is PINNED by published vectors
+(tests/golden/chacha_vectors.json); the seed expansion, the order the words are read in and the range sampling agree across three
+separately written implementations -- second draw, 64-bit ranges and the straddling next_u64 included -- but are not pinned by any
+value that rand itself produced (none can be made where this was written).
 """
 import gzip
 import struct
@@ -128,12 +135,122 @@ def read_bam(path) -> List[BamRecord]:
     return out
 
 
-def extract_reads(locus: Locus, records: List[BamRecord], flank_len=250, min_read_qual=0.98, max_depth=250):
-    """tr.rs:262-361: records overlapping region +- flank_len, in file order; returns (records, number dropped for quality)"""
+# ---- rand 0.9: StdRng::seed_from_u64(seed).random_range(0..n), from the published algorithms --------------------------------------------
+_M32, _M64 = (1 << 32) - 1, (1 << 64) - 1
+_CONSTANTS = struct.unpack("<4I", b"expand 32-byte k")
+_COLUMNS = ((0, 4, 8, 12), (1, 5, 9, 13), (2, 6, 10, 14), (3, 7, 11, 15))
+_DIAGONALS = ((0, 5, 10, 15), (1, 6, 11, 12), (2, 7, 8, 13), (3, 4, 9, 14))
+
+
+def _quarter_round(s, a, b, c, d):
+    """RFC 8439 2.1: a += b; d ^= a; d <<<= 16;  c += d; b ^= c; b <<<= 12;  a += b; d ^= a; d <<<= 8;  c += d; b ^= c; b <<<= 7"""
+    for x, y, z, left in ((a, b, d, 16), (c, d, b, 12), (a, b, d, 8), (c, d, b, 7)):
+        s[x] = (s[x] + s[y]) & _M32
+        v = s[z] ^ s[x]
+        s[z] = ((v << left) | (v >> (32 - left))) & _M32
+
+
+def chacha_block(key_words, counter64, stream64, rounds):
+    """One 16-word ChaCha block.  State: the four constants, the eight key words, then 128 bits that Bernstein's ChaCha (and rand_chacha)
+    read as a 64-bit block counter (words 12-13) and a 64-bit stream id (14-15), RFC 8439 as a 32-bit counter and a 96-bit nonce.
+    `rounds` / 2 double rounds (a column round, a diagonal round), then the input state is added word by word."""
+    assert len(key_words) == 8 and rounds % 2 == 0
+    start = list(_CONSTANTS) + [k & _M32 for k in key_words] + [counter64 & _M32, (counter64 >> 32) & _M32, stream64 & _M32, (stream64 >> 32) & _M32]
+    s = list(start)
+    for _ in range(rounds // 2):
+        for q in _COLUMNS:
+            _quarter_round(s, *q)
+        for q in _DIAGONALS:
+            _quarter_round(s, *q)
+    return [(x + y) & _M32 for x, y in zip(s, start)]
+
+
+def seed_from_u64(state):
+    """rand_core's SeedableRng::seed_from_u64 for a 32-byte seed: eight outputs of PCG32 (XSH-RR 64/32; the state advances BEFORE each
+    output), each written little-endian -- read back as little-endian key words they are the outputs themselves"""
+    words = []
+    for _ in range(8):
+        state = (state * 6364136223846793005 + 11634580027462260723) & _M64
+        xorshifted = (((state >> 18) ^ state) >> 27) & _M32
+        rot = state >> 59
+        words.append(((xorshifted >> rot) | (xorshifted << (32 - rot))) & _M32 if rot else xorshifted)
+    return words
+
+
+class StdRng:
+    """rand 0.9's StdRng: ChaCha with 12 rounds behind rand_core's BlockRng -- a buffer of 64 words (four consecutive blocks per refill),
+    read in order; it starts empty.  The counters (`refills`, `u64_cases`, `second_draws`, `carries`) let a test assert that its inputs
+    reached a branch."""
+
+    def __init__(self, seed=42, key=None, rounds=12, counter=0, stream=0):
+        self.key = list(key) if key is not None else seed_from_u64(seed)
+        self.rounds, self.counter, self.stream = rounds, counter, stream
+        self.results, self.index = [0] * 64, 64
+        self.refills, self.u64_cases, self.second_draws, self.carries = 0, [0, 0, 0], 0, 0
+
+    def _generate(self):
+        self.results = [w for b in range(4) for w in chacha_block(self.key, (self.counter + b) & _M64, self.stream, self.rounds)]
+        self.counter = (self.counter + 4) & _M64
+        self.refills += 1
+
+    def next_u32(self):
+        if self.index >= 64:
+            self._generate()
+            self.index = 0
+        self.index += 1
+        return self.results[self.index - 1]
+
+    def next_u64(self):
+        """BlockRng::next_u64: two words, the first one the low half -- [0] both still in the buffer; [1] the buffer is used up: refill,
+        words 0 and 1; [2] one word left: it is the low half, the high half is word 0 of the refilled buffer, and reading goes on at 1"""
+        i = self.index
+        if i < 63:
+            self.u64_cases[0] += 1
+            self.index = i + 2
+            return (self.results[i + 1] << 32) | self.results[i]
+        if i >= 64:
+            self.u64_cases[1] += 1
+            self._generate()
+            self.index = 2
+            return (self.results[1] << 32) | self.results[0]
+        self.u64_cases[2] += 1
+        low = self.results[63]
+        self._generate()
+        self.index = 1
+        return (self.results[0] << 32) | low
+
+    def random_range(self, n):
+        """rng.random_range(0..n) for usize on a 64-bit target (n >= 1).  The half-open range is sampled as the inclusive 0 ..= n - 1;
+        when that upper bound fits in u32 the sample type is u32, else u64.  Canon's method: one widening multiplication of a random
+        word by the span; only if the low half of the product exceeds -span (in the sample type) a second word is drawn, and the high half
+        of ITS product is added to that low half -- a carry out of the addition bumps the result.  A span that wraps to 0 is the whole
+        type: the random word itself."""
+        high = n - 1
+        bits, draw = (32, self.next_u32) if high <= _M32 else (64, self.next_u64)
+        mask = (1 << bits) - 1
+        span = (high + 1) & mask
+        if span == 0:
+            return draw()
+        product = draw() * span
+        result, low = product >> bits, product & mask
+        if low > ((-span) & mask):
+            self.second_draws += 1
+            if low + ((draw() * span) >> bits) > mask:
+                self.carries += 1
+                result += 1
+        return result
+
+
+def extract_reads_seen(locus: Locus, records: List[BamRecord], flank_len=250, min_read_qual=0.98, max_depth=250):
+    """tr.rs:262-361: records overlapping region +- flank_len, in file order.  The first 3 * max_depth that pass the filters fill the
+    reservoir; every further one draws j = random_range(0..reads so far) from StdRng::seed_from_u64(42) and replaces slot j when
+    j < 3 * max_depth (secondary / supplementary / low-rq records draw nothing).  A record with the unmapped bit set that the fetch returns
+    counts like any other (clip_to_region drops it later).  Returns (records in slot order, number dropped for quality, reads seen)."""
     lo, hi = max(0, locus.start - flank_len), locus.end + flank_len
-    reads, n_filt = [], 0
+    reservoir = 3 * max_depth
+    reads, n_filt, n_reads, rng = [], 0, 0, None
     for r in records:
-        if r.contig != locus.contig or (r.flag & 0x4):
+        if r.contig != locus.contig:
             continue
         ref_end = r.pos + sum(n for c, n in r.cigar if c in REF_CONSUMING)
         if ref_end <= lo or hi <= r.pos:
@@ -143,10 +260,21 @@ def extract_reads(locus: Locus, records: List[BamRecord], flank_len=250, min_rea
         if (r.rq if r.rq is not None else 1.0) < min_read_qual:
             n_filt += 1
             continue
-        reads.append(r)
-    if len(reads) >= 3 * max_depth:
-        raise NotImplementedError("reservoir sampling of deep loci (tr.rs:311-335) is not mirrored")
-    return reads, n_filt
+        if n_reads < reservoir:
+            reads.append(r)
+        else:
+            if rng is None:
+                rng = StdRng(42)
+            j = rng.random_range(n_reads)
+            if j < reservoir:
+                reads[j] = r
+        n_reads += 1
+    return reads, n_filt, n_reads
+
+
+def extract_reads(locus: Locus, records: List[BamRecord], flank_len=250, min_read_qual=0.98, max_depth=250):
+    """extract_reads_seen without the count: (records, number dropped for quality)"""
+    return extract_reads_seen(locus, records, flank_len, min_read_qual, max_depth)[:2]
 
 
 def clip_cigar(ref_pos0, ops, region):
@@ -177,7 +305,9 @@ def clip_cigar(ref_pos0, ops, region):
 
 
 def clip_to_region(rec: BamRecord, region) -> Optional[bytes]:
-    """HiFiRead::clip_to_region (clip_region.rs:19-76), bases only"""
+    """HiFiRead::clip_to_region (clip_region.rs:19-76), bases only (a record with the unmapped bit carries no alignment: no read)"""
+    if rec.flag & 0x4:
+        return None
     r = clip_cigar(rec.pos, rec.cigar, region)
     if r is None:
         return None

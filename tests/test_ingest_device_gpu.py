@@ -120,6 +120,109 @@ def test_a_locus_deeper_than_the_reservoir_is_down_sampled_like_the_host_path(tm
         assert int(host["n_reads_seen"][1]) == 201 and int(host["locus_read_begin"][2] - host["locus_read_begin"][1]) <= 3 * depth
 
 
+# ---- the reservoir's random stream and deep loci: device = host = the Python mirror (the lists and files of tests/test_reservoir_stream.py) ----
+def test_block_function_of_the_kernels_generator_matches_the_published_vectors():
+    # DevRng::block through the developer build's one-wave kernel, key given directly; the kernel type has no stream id: the vectors with stream 0
+    from test_reservoir_stream import VECTORS, _vector_words, native_draws, vector_args
+    done = []
+    for v in VECTORS:
+        a = vector_args(v)
+        if a["stream"] == 0:
+            want = _vector_words(v)
+            assert native_draws([0] * 16, device=0, **a)[:len(want)] == want, v["name"]
+            done.append(v["rounds"])
+    assert sorted(done) == [8, 12, 20]
+
+
+def test_raw_words_of_the_kernels_generator_against_the_mirror():
+    from test_reservoir_stream import SEEDS, mirror_draws, native_draws
+    for seed in SEEDS:
+        want, m = mirror_draws([0] * 1500, seed=seed)
+        assert m.refills == 24
+        assert native_draws([0] * 1500, seed=seed, device=0) == want, seed
+
+
+def test_range_draws_of_the_kernels_generator_against_the_mirror():
+    # every list of the host test whose ranges fit the kernel's 32-bit type; the mirror's counters say that the second draw (and its carry)
+    # was met a thousand times in the lists made for it
+    from test_reservoir_stream import check_mirror_met, mirror_draws, native_draws, range_lists
+    ran = []
+    for label, ns, want_met in range_lists():
+        if max(ns) > 0xFFFFFFFF:
+            continue
+        want, m = mirror_draws(ns, seed=42)
+        check_mirror_met(label, ns, want_met, m)
+        got = native_draws(ns, seed=42, device=0)
+        assert got == want, (label, next(i for i in range(len(ns)) if got[i] != want[i]))
+        ran.append(want_met)
+    assert ran.count("often") == 3 and ran.count("never") >= 6 and len(ran) >= 13
+
+
+def _deep_three_ways(label, files, kw, monkeypatch):
+    """host = mirror, then device = host array by array, with the inflate kernel's own loop and with the compiler's; no call may go back to
+    the host path (the comparison would be the host's with itself), and FB_RESERVOIR (3) is a reason the device never gives"""
+    from trgt_amd import ingest
+    from test_reservoir_stream import assert_batch_is_the_mirrors, mirror_expectation
+    bam, fa, bed = files
+    exp = mirror_expectation(bam, fa, bed, **kw)
+    rd = ingest.Reader(bam, fa)
+    host = rd.batch(bed, **kw)
+    assert_batch_is_the_mirrors(host, exp, label)
+    for compiler_loop in (False, True):
+        if compiler_loop:
+            monkeypatch.setenv("TRGT_INFLATE_COMPILER_LOOP", "1")
+        else:
+            monkeypatch.delenv("TRGT_INFLATE_COMPILER_LOOP", raising=False)
+        before = rd.device_stats()
+        dev = rd.batch(bed, ingest_device=0, **kw)
+        st = rd.device_stats()
+        assert st["calls"] == before["calls"] + 1 and st["fallbacks"] == 0 and st["last_reason"] == 0 and st["last_reason"] != 3, (label, st)
+        _same_batches(host, dev)
+        assert_batch_is_the_mirrors(dev, exp, label)
+    monkeypatch.delenv("TRGT_INFLATE_COMPILER_LOOP", raising=False)
+    rd.close()
+    return exp
+
+
+@pytest.mark.parametrize("d", [1, 10, 250])
+def test_reservoir_device_host_and_mirror(tmp_path, monkeypatch, d):
+    from test_reservoir_stream import single_locus_cases
+    for label, files, kw, depth in single_locus_cases(tmp_path, d):
+        exp = _deep_three_ways(label, files, kw, monkeypatch)
+        assert exp[0]["n_seen"] == depth and len(exp[0]["names"]) == min(depth, 3 * d), label
+
+
+def test_reservoir_of_several_loci_device_host_and_mirror(tmp_path, monkeypatch):
+    from test_reservoir_stream import multi_locus_cases
+    for label, files, kw in multi_locus_cases(tmp_path):
+        exp = _deep_three_ways(label, files, kw, monkeypatch)
+        assert sum(e["n_seen"] > 3 * kw.get("max_depth", 250) for e in exp) >= 1, label
+
+
+def test_reservoir_at_every_place_of_a_tile_device_host_and_mirror(tmp_path, monkeypatch):
+    # the first read beyond the reservoir at lane 0 / 63 / 30 of walk_kernel's 64-record tile, tiles in which every lane draws behind a tile
+    # that ends with exactly `reservoir` reads, reservoirs of 60 / 63 / 66
+    from test_reservoir_stream import tile_cases
+    n = 0
+    for label, files, kw in tile_cases(tmp_path):
+        exp = _deep_three_ways(label, files, kw, monkeypatch)
+        assert exp[0]["n_seen"] > 3 * kw["max_depth"], label
+        n += 1
+    assert n == 10
+
+
+def test_reservoir_across_chunks_and_blocks_and_in_many_workgroups(tmp_path, monkeypatch):
+    from test_reservoir_stream import chunked_case, chunks_and_blocks, many_loci_case
+    label, files, kw = chunked_case(tmp_path)
+    n_chunks, n_blocks = chunks_and_blocks(files[0], 16684 - 250, 16714 + 250)
+    assert n_chunks >= 30 and n_blocks >= 30, (n_chunks, n_blocks)  # (ChunkDesc after ChunkDesc, records across BGZF blocks)
+    exp = _deep_three_ways(label, files, kw, monkeypatch)
+    assert exp[0]["n_seen"] > 300 and any(n.startswith("A") for n in exp[0]["names"]) and any(n.startswith("C") for n in exp[0]["names"])
+    label, files, kw = many_loci_case(tmp_path)
+    exp = _deep_three_ways(label, files, kw, monkeypatch)
+    assert len(exp) == 70 and all(e["n_seen"] > 3 for e in exp)
+
+
 def test_a_block_with_a_wrong_crc_is_refused(tmp_path):
     from trgt_amd import _lib, ingest, synth_bam
     ds = synth_bam.write_dataset(str(tmp_path / "ds"), n_loci=12, read_len=2000)

@@ -3,7 +3,10 @@ written by tests/bamtools.py -- reads with random CIGARs (M = X I D S N H P runs
 supplementary / unmapped flags, rq values either side of the filter, HP tags, MM / ML tags of several shapes (C+m with and without '?',
 numeric codes, two codes, other bases, deltas that run off the read, too few ML values), read lengths from 30 bases to several kb, loci
 with no read and loci deeper than the reservoir, several contigs, catalog windows cut by flank_len 20 .. 250 -- every array of the two
-batches compared.  Usage: python tests/tools/ingest_fuzz.py [n_files] [seed]"""
+batches compared.  Deep loci come in the shapes of tests/test_reservoir_stream.py (max_depth 1 / 10 / 21 / 250 with 3 x max_depth - 1, + 0,
++ 1, + 63, + 64, + 65 and about 10 x max_depth reads that pass the filters, other records between them), and the Python mirror
+tests/pyreads.py is the third party: names in slot order, clipped bases, rq, reads seen and reads filtered of every locus, against the host
+batch (which the device batch has to equal).  Usage: python tests/tools/ingest_fuzz.py [n_files] [seed]"""
 import os
 import sys
 import tempfile
@@ -15,13 +18,16 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 from bamtools import write_bam, write_fasta  # noqa: E402
 from trgt_amd import ingest  # noqa: E402
+from test_reservoir_stream import assert_batch_is_the_mirrors, mirror_expectation  # noqa: E402
 
 
 def comp(s):
     return s.translate(str.maketrans("ACGT", "TGCA"))[::-1]
 
 
-def one_file(rng, d, tag):
+def one_file(rng, d, tag, shapes=None):
+    """shapes: None -- the files as they always were (tests/test_writer_records_device_gpu.py takes them); a dict -- deep loci come in the
+    shapes of tests/test_reservoir_stream.py, and shapes["max_depth"] is the max_depth to read the file with"""
     glen = int(rng.integers(6000, 30000))
     contigs = [("chr1", "".join(rng.choice(list("ACGT"), glen))), ("chr2", "".join(rng.choice(list("ACGT"), 4000)))]
     fa = os.path.join(d, tag + ".fa")
@@ -42,10 +48,20 @@ def one_file(rng, d, tag):
         f.write("chr2\t1000\t1030\tID=other;MOTIFS=A;STRUC=(A)n\n")
     recs = []
     deep = int(rng.integers(0, len(loci))) if rng.random() < 0.3 else -1
+    # max_depth the file is read with; the deep loci (one or two, the second next to the first: overlapping windows) get a number of
+    # passing reads at one of the edges of its reservoir, as short reads (the file stays small)
+    depth, edge, shaped = 0, 0, False
+    if shapes is not None:
+        depth = int(rng.choice([10, 250])) if rng.random() < 0.5 else int(rng.choice([1, 10, 21, 250]))
+        edge = int(rng.choice([-1, 0, 1, 63, 64, 65, 7 * depth]))
+        shaped = deep >= 0 and rng.random() < 0.7
+        shapes["max_depth"] = depth
     for li, (a, b) in enumerate(loci):
-        n_reads = int(rng.integers(0, 40)) if li != deep else int(rng.integers(100, 200))
+        is_deep = li == deep or (shaped and li == deep + 1 and rng.random() < 0.5)
+        n_reads = int(rng.integers(0, 40)) if not is_deep else (int(rng.integers(100, 200)) if not shaped else int((3 * depth + edge) * 1.1))
+        n_plain = 3 * depth + edge if is_deep and shaped else 0   # of them: reads that pass every filter
         for r in range(n_reads):
-            span = int(rng.integers(30, 4000))
+            span = int(rng.integers(30, 4000)) if not (is_deep and shaped) else int(rng.integers(100, 300))
             pos = max(0, a - int(rng.integers(0, span)))
             ops, ref, left = [], pos, span
             if rng.random() < 0.3:
@@ -77,6 +93,10 @@ def one_file(rng, d, tag):
             tags = {}
             if rng.random() < 0.9:
                 tags["rq"] = ("f", float(rng.choice([0.999, 0.99, 0.95, 0.5])))
+            if r < n_plain:  # (their places among the others: the sort by position below)
+                flag, tags = int(rng.choice([0, 16])), ({"rq": ("f", 0.999)} if rng.random() < 0.9 else {})
+            elif n_plain:
+                flag, tags = int(rng.choice([0, 256, 2048])), {"rq": ("f", 0.5)}
             if rng.random() < 0.4:
                 tags["HP"] = ("C", int(rng.integers(0, 3)))
             shape = int(rng.integers(0, 9))
@@ -122,13 +142,21 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
     rng = np.random.default_rng(seed)
-    bad = reads = fell = 0
+    bad = reads = fell = deep_loci = bad_mirror = 0
     with tempfile.TemporaryDirectory() as d:
         for i in range(n):
-            bam, fa, bed, flank, nrec = one_file(rng, d, "f%d" % i)
+            shapes = {}
+            bam, fa, bed, flank, nrec = one_file(rng, d, "f%d" % i, shapes)
+            depth = shapes["max_depth"]
             rd = ingest.Reader(bam, fa)
-            kw = dict(flank_len=flank, max_depth=int(rng.choice([10, 250])), min_read_qual=float(rng.choice([0.98, 0.9, 0.0])), keep_bam4=int(rng.integers(0, 2)))
+            kw = dict(flank_len=flank, max_depth=depth, min_read_qual=float(rng.choice([0.98, 0.9, 0.0])), keep_bam4=int(rng.integers(0, 2)))
             host = rd.batch(bed, **kw)
+            deep_loci += int((host["n_reads_seen"] > 3 * depth).sum())
+            try:  # the third party: tests/pyreads.py against the host batch
+                assert_batch_is_the_mirrors(host, mirror_expectation(bam, fa, bed, flank_len=flank, min_read_qual=kw["min_read_qual"], max_depth=depth), "file %d" % i)
+            except AssertionError as e:
+                bad_mirror += 1
+                print("MIRROR MISMATCH file %d (seed %d): %s; kw %r" % (i, seed, str(e).splitlines()[0] if str(e) else "?", kw), flush=True)
             dev = rd.batch(bed, ingest_device=0, **kw)
             st = rd.device_stats()
             fell += st["fallbacks"]
@@ -144,8 +172,9 @@ def main():
             rd.close()
             for p in (bam, bam + ".bai", fa, fa + ".fai", bed):
                 os.remove(p)
-    print("RESULT ingest_fuzz: %d files, %d clipped reads, %d calls fell back to the host path, %d mismatches" % (n, reads, fell, bad))
-    sys.exit(1 if bad else 0)
+    print("RESULT ingest_fuzz: %d files, %d clipped reads, %d loci deeper than the reservoir, %d calls fell back to the host path, %d mismatches device / host, %d mismatches host / mirror"
+          % (n, reads, deep_loci, fell, bad, bad_mirror))
+    sys.exit(1 if bad or bad_mirror else 0)
 
 
 main()

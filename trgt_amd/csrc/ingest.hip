@@ -491,9 +491,14 @@ bool clip_to_region(const Read& in, int64_t rs, int64_t re, Read& out) {
 // The reservoir of extract_reads (tr.rs:311-335) draws from rand 0.9's StdRng = ChaCha12 seeded through rand_core's seed_from_u64
 // (a PCG32 stream fills the 32-byte key).  rand is not vendored in the reference tree: the stream below restates its published
 // algorithms (ChaCha block function, 64-word buffer read in order, Canon's widening-multiply range sampling for 32-bit and 64-bit
-// ranges) -- parity UNPINNED (no fixture in the reference reaches this path).
+// ranges).  What holds it (tests/test_reservoir_stream.py, through trgt_dev_rng_draws of the developer build): the block function is
+// PINNED by published ChaCha vectors (tests/golden/chacha_vectors.json, 20 and 12 rounds through refill()); the seed expansion, the
+// order the buffer is read in and the range sampling agree with DevRng (ingest_dev.hip) and with the separately written Python
+// restatement in tests/pyreads.py, draw by draw -- the second draw of the sampler, the 64-bit range and the next_u64 that straddles a
+// refill included -- but no value produced by rand itself is available, so those three stay parity UNPINNED.
+// `rounds` is a parameter for the sake of the published vectors only: every caller of the product leaves it at StdRng's 12.
 struct StdRng {
-  uint32_t key[8]; uint64_t counter = 0; uint32_t buf[64]; int at = 64;
+  uint32_t key[8]; uint64_t counter = 0, stream = 0; uint32_t buf[64]; int at = 64;
   explicit StdRng(uint64_t state) {
     const uint64_t MUL = 6364136223846793005ull, INC = 11634580027462260723ull;
     for (int i = 0; i < 8; ++i) {
@@ -503,39 +508,42 @@ struct StdRng {
     }
   }
   static inline uint32_t rotl(uint32_t v, int n) { return (v << n) | (v >> (32 - n)); }
-  void refill() {
+  void refill(int rounds = 12) {
     for (int b = 0; b < 4; ++b) {
       uint32_t s[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7],
-                        (uint32_t)counter, (uint32_t)(counter >> 32), 0u, 0u};
+                        (uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
       uint32_t x[16];
       std::memcpy(x, s, sizeof x);
       auto qr = [&](int a, int bb, int c, int d) {
         x[a] += x[bb]; x[d] = rotl(x[d] ^ x[a], 16); x[c] += x[d]; x[bb] = rotl(x[bb] ^ x[c], 12);
         x[a] += x[bb]; x[d] = rotl(x[d] ^ x[a], 8); x[c] += x[d]; x[bb] = rotl(x[bb] ^ x[c], 7);
       };
-      for (int r = 0; r < 6; ++r) { qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15); qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14); }
+      for (int r = 0; r < rounds / 2; ++r) { qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15); qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14); }
       for (int i = 0; i < 16; ++i) buf[16 * b + i] = x[i] + s[i];
       ++counter;
     }
     at = 0;
   }
-  uint32_t next_u32() { if (at >= 64) refill(); return buf[at++]; }
-  uint64_t next_u64() {
+  uint32_t next_u32(int rounds = 12) { if (at >= 64) refill(rounds); return buf[at++]; }
+  uint64_t next_u64(int rounds = 12) {
     if (at < 63) { const uint64_t lo = buf[at], hi = buf[at + 1]; at += 2; return (hi << 32) | lo; }
-    if (at >= 64) { refill(); const uint64_t lo = buf[0], hi = buf[1]; at = 2; return (hi << 32) | lo; }
-    const uint64_t lo = buf[63]; refill(); const uint64_t hi = buf[0]; at = 1; return (hi << 32) | lo;
+    if (at >= 64) { refill(rounds); const uint64_t lo = buf[0], hi = buf[1]; at = 2; return (hi << 32) | lo; }
+    const uint64_t lo = buf[63]; refill(rounds); const uint64_t hi = buf[0]; at = 1; return (hi << 32) | lo;
   }
-  uint64_t range(uint64_t n) {  // 0 .. n (exclusive), n >= 1
-    if (n <= 0xFFFFFFFFull) {
+  uint64_t range(uint64_t n, int rounds = 12) {  // 0 .. n (exclusive), n >= 1
+    // random_range(0..n) samples the inclusive range 0 ..= n - 1, and usize on a 64-bit target takes the 32-bit sampler whenever that
+    // INCLUSIVE bound fits in u32: n = 2^32 is still a 32-bit draw, its range wraps to 0 ("the whole of u32") and is one raw word
+    if (n - 1 <= 0xFFFFFFFFull) {
       const uint32_t r = (uint32_t)n;
-      uint64_t m = (uint64_t)next_u32() * r;
+      if (r == 0) return next_u32(rounds);
+      uint64_t m = (uint64_t)next_u32(rounds) * r;
       uint32_t hi = (uint32_t)(m >> 32); const uint32_t lo = (uint32_t)m;
-      if (lo > (uint32_t)(0u - r)) { const uint32_t hi2 = (uint32_t)(((uint64_t)next_u32() * r) >> 32); if ((uint64_t)lo + hi2 > 0xFFFFFFFFull) ++hi; }
+      if (lo > (uint32_t)(0u - r)) { const uint32_t hi2 = (uint32_t)(((uint64_t)next_u32(rounds) * r) >> 32); if ((uint64_t)lo + hi2 > 0xFFFFFFFFull) ++hi; }
       return hi;
     }
-    const unsigned __int128 m = (unsigned __int128)next_u64() * n;
+    const unsigned __int128 m = (unsigned __int128)next_u64(rounds) * n;
     uint64_t hi = (uint64_t)(m >> 64); const uint64_t lo = (uint64_t)m;
-    if (lo > 0ull - n) { const uint64_t hi2 = (uint64_t)(((unsigned __int128)next_u64() * n) >> 64); if (lo + hi2 < lo) ++hi; }
+    if (lo > 0ull - n) { const uint64_t hi2 = (uint64_t)(((unsigned __int128)next_u64(rounds) * n) >> 64); if (lo + hi2 < lo) ++hi; }
     return hi;
   }
 };
@@ -811,6 +819,30 @@ void trgt_ingest_device_stats(const trgt_ingest* h, int64_t out[5]) {
   if (!h || !out) return;
   out[0] = h->dev_calls.load(); out[1] = h->dev_fallbacks.load(); out[2] = h->dev_last_reason.load(); out[3] = h->dev_blocks.load(); out[4] = h->dev_blocks_host.load();
 }
+
+#ifdef TRGT_DEV_BUILD
+// Developer build only (not in include/trgt_hip.h; tests/test_reservoir_stream.py, tests/test_ingest_device_gpu.py): `count` draws, in
+// order, of the reservoir's generator -- device < 0: StdRng above on the host; >= 0: DevRng of ingest_dev.hip in a one-wave kernel on that
+// GPU.  key == nullptr: the key is expanded from `seed` as seed_from_u64 does; else the eight words are the key (the published ChaCha
+// vectors).  counter / stream: state words 12-13 / 14-15 of the first block.  Draw k: kind[k] == 1 (kind may be nullptr) -> raw next_u64;
+// else n[k] == 0 -> raw next_u32, n[k] >= 1 -> range(n[k]).  The device type has 32-bit ranges, stream 0 and no next_u64: anything else
+// is refused (TRGT_ERR_INVALID).
+int trgt_dev_rng_draws(int32_t device, uint64_t seed, const uint32_t* key, uint64_t counter, uint64_t stream, int32_t rounds, int64_t count,
+                       const uint64_t* n, const uint8_t* kind, uint64_t* out) {
+  if (count < 0 || (count && (!n || !out)) || rounds < 2 || (rounds & 1)) return TRGT_ERR_INVALID;
+  if (device >= 0) {
+    if (stream != 0) return TRGT_ERR_INVALID;
+    for (int64_t k = 0; k < count; ++k) if ((kind && kind[k]) || n[k] > 0xFFFFFFFFull) return TRGT_ERR_INVALID;
+    std::string err;
+    return trgt::ingd::dev_rng_draws(device, seed, key, counter, rounds, count, n, out, err);
+  }
+  StdRng rng(seed);
+  if (key) std::memcpy(rng.key, key, sizeof rng.key);
+  rng.counter = counter; rng.stream = stream;
+  for (int64_t k = 0; k < count; ++k) out[k] = kind && kind[k] ? rng.next_u64(rounds) : n[k] ? rng.range(n[k], rounds) : (uint64_t)rng.next_u32(rounds);
+  return TRGT_OK;
+}
+#endif
 
 void trgt_ingest_default_params(trgt_ingest_params* p) {
   if (!p) return;

@@ -152,7 +152,10 @@ __global__ void __launch_bounds__(64) crc32_blocks_kernel(const uint8_t* __restr
 // extract_reads (tr.rs:311-335) keeps 3 * max_depth reads; every further read replaces a random one of them with probability
 // reservoir / (n + 1), drawn from rand 0.9's StdRng::seed_from_u64(42): ChaCha12 keyed by a PCG32 stream over the seed, its 32-bit words
 // read in order, ranges by Canon's widening multiplication.  The restatement of ingest.hip's StdRng for one lane (the words of the
-// 64-word buffer there are four consecutive blocks: the same stream block by block); unpinned like the host's (no fixture reaches it).
+// 64-word buffer there are four consecutive blocks: the same stream block by block).  Held like the host's: the block function by
+// published ChaCha vectors, seed expansion / word order / range sampling (its second draw included) draw by draw against StdRng and
+// the Python restatement of tests/pyreads.py, through rng_draws_kernel of the developer build -- those three are not pinned by values
+// of rand's own.  `rounds` is a parameter for the published vectors only; walk_kernel leaves it at 12.
 struct DevRng {
   uint32_t key[8]; uint32_t buf[16]; uint32_t at; uint64_t counter;
   __device__ void seed(uint64_t state) {
@@ -164,7 +167,7 @@ struct DevRng {
     }
     at = 16; counter = 0;
   }
-  __device__ void block() {
+  __device__ void block(int rounds = 12) {
     const uint32_t s0[16] = {0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u, key[0], key[1], key[2], key[3], key[4], key[5], key[6], key[7],
                              (uint32_t)counter, (uint32_t)(counter >> 32), 0u, 0u};
     uint32_t x[16];
@@ -174,18 +177,31 @@ struct DevRng {
       x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 16); x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 12);
       x[a] += x[b]; x[d] = rotl(x[d] ^ x[a], 8); x[c] += x[d]; x[b] = rotl(x[b] ^ x[c], 7);
     };
-    for (int r = 0; r < 6; ++r) { qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15); qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14); }
+    for (int r = 0; r < rounds / 2; ++r) { qr(0, 4, 8, 12); qr(1, 5, 9, 13); qr(2, 6, 10, 14); qr(3, 7, 11, 15); qr(0, 5, 10, 15); qr(1, 6, 11, 12); qr(2, 7, 8, 13); qr(3, 4, 9, 14); }
     for (int i = 0; i < 16; ++i) buf[i] = x[i] + s0[i];
     ++counter; at = 0;
   }
-  __device__ uint32_t next_u32() { if (at >= 16) block(); return buf[at++]; }
-  __device__ uint32_t range(uint32_t n) {  // 0 .. n (exclusive), n >= 1
-    const uint64_t m = (uint64_t)next_u32() * n;
+  __device__ uint32_t next_u32(int rounds = 12) { if (at >= 16) block(rounds); return buf[at++]; }
+  __device__ uint32_t range(uint32_t n, int rounds = 12) {  // 0 .. n (exclusive), n >= 1
+    const uint64_t m = (uint64_t)next_u32(rounds) * n;
     uint32_t hi = (uint32_t)(m >> 32); const uint32_t lo = (uint32_t)m;
-    if (lo > (uint32_t)(0u - n)) { const uint32_t hi2 = (uint32_t)(((uint64_t)next_u32() * n) >> 32); if ((uint64_t)lo + hi2 > 0xFFFFFFFFull) ++hi; }
+    if (lo > (uint32_t)(0u - n)) { const uint32_t hi2 = (uint32_t)(((uint64_t)next_u32(rounds) * n) >> 32); if ((uint64_t)lo + hi2 > 0xFFFFFFFFull) ++hi; }
     return hi;
   }
 };
+
+#ifdef TRGT_DEV_BUILD
+// developer build only: the draws of DevRng on their own (lane 0 of one wave, the generator in LDS as walk_kernel keeps it)
+__global__ void __launch_bounds__(64) rng_draws_kernel(uint64_t seed, const uint32_t* __restrict__ key, uint64_t counter, int rounds, int64_t count,
+                                                       const uint64_t* __restrict__ n, uint64_t* __restrict__ out) {
+  __shared__ DevRng rng;
+  if (blockIdx.x != 0 || lane_id() != 0) return;
+  rng.seed(seed);
+  if (key) for (int i = 0; i < 8; ++i) rng.key[i] = key[i];
+  rng.counter = counter;
+  for (int64_t k = 0; k < count; ++k) out[k] = n[k] ? (uint64_t)rng.range((uint32_t)n[k], rounds) : (uint64_t)rng.next_u32(rounds);
+}
+#endif
 
 // ------------------------------------------------------------------------------------------------ the record walk of a locus
 struct WalkOut { uint32_t n_kept, n_filt, status, pad; };
@@ -916,6 +932,26 @@ int slot_run(Slot* s, const RunIn& in, SlabPool& pool, RunOut& out, std::string&
   out.ms_upload = t4 - t3; out.ms_inflate = t1 - t0; out.ms_walk = t2 - t1; out.ms_reads = t3 - t2; out.ms_download = t5 - t4;
   return TRGT_OK;
 }
+
+#ifdef TRGT_DEV_BUILD
+int dev_rng_draws(int device, uint64_t seed, const uint32_t* key, uint64_t counter, int rounds, int64_t count, const uint64_t* n, uint64_t* out, std::string& err) {
+  int n_dev = 0;
+  if (hipGetDeviceCount(&n_dev) != hipSuccess || device < 0 || device >= n_dev) { (void)hipGetLastError(); err = "dev_rng_draws: no such GPU"; return TRGT_ERR_NO_DEVICE; }
+  if (count <= 0) return TRGT_OK;
+  ING_TRY(hipSetDevice(device));
+  DevBuf d_n, d_out, d_key;
+  struct Free { DevBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } fr{d_n, d_out, d_key};
+  ING_NEED(d_n, (size_t)count * 8); ING_NEED(d_out, (size_t)count * 8); ING_NEED(d_key, 32);
+  ING_TRY(hipMemcpy(d_n.p, n, (size_t)count * 8, hipMemcpyHostToDevice));
+  if (key) ING_TRY(hipMemcpy(d_key.p, key, 32, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(rng_draws_kernel, dim3(1), dim3(64), 0, (hipStream_t)nullptr, seed, key ? (const uint32_t*)d_key.p : (const uint32_t*)nullptr, counter, rounds, count,
+                     (const uint64_t*)d_n.p, (uint64_t*)d_out.p);
+  ING_TRY(hipGetLastError());
+  ING_TRY(hipDeviceSynchronize());
+  ING_TRY(hipMemcpy(out, d_out.p, (size_t)count * 8, hipMemcpyDeviceToHost));
+  return TRGT_OK;
+}
+#endif
 
 }  // namespace ingd
 }  // namespace trgt

@@ -64,7 +64,7 @@ struct RunIn {
 };
 // Why a call went back to the host path (RunOut::fallback)
 enum : int { FB_NONE = 0, FB_BLOCK = 1 /* a block the device could not inflate or whose CRC-32 / ISIZE does not match */, FB_WALK = 2 /* a record the walk refuses */,
-             FB_RESERVOIR = 3 /* (unused since the reservoir's random stream runs in walk_kernel) */, FB_METH = 4 /* MM / ML beyond the kernel's LDS caps */ };
+             FB_RESERVOIR = 3 /* (never set since the reservoir's random stream runs in walk_kernel; the value stays for the layout of the stats, and tests/test_ingest_device_gpu.py asserts that deep loci do not report it) */, FB_METH = 4 /* MM / ML beyond the kernel's LDS caps */ };
 struct RunOut { int fallback = FB_NONE; Slab slab; HostOut out; double ms_upload = 0, ms_inflate = 0, ms_walk = 0, ms_reads = 0, ms_download = 0; uint64_t blocks_host_inflated = 0; };
 
 class Slot;
@@ -80,6 +80,12 @@ int slot_run(Slot* s, const RunIn& in, SlabPool& pool, RunOut& out, std::string&
 size_t crc32_tables_bytes();
 void crc32_tables_make(void* host);
 void crc32_blocks_launch(void* hip_stream, const uint8_t* d_data, const infl::BlockDesc* d_blocks, uint32_t n, const void* d_tab, uint32_t* d_out);
+
+#ifdef TRGT_DEV_BUILD
+// developer build only (trgt_dev_rng_draws, ingest.hip): `count` draws of walk_kernel's DevRng by one wave of GPU `device` -- n[k] == 0: raw
+// next_u32, else range(n[k]) with n[k] < 2^32; key == nullptr: expanded from `seed`
+int dev_rng_draws(int device, uint64_t seed, const uint32_t* key, uint64_t counter, int rounds, int64_t count, const uint64_t* n, uint64_t* out, std::string& err);
+#endif
 
 }  // namespace ingd
 }  // namespace trgt
