@@ -190,6 +190,10 @@ int trgt_flank_filter_batch(trgt_hip_ctx* ctx, const trgt_span_params* p, int64_
  *               (filter_impure_trs, tr.rs:400-452, needs nothing else)
  *   motif_counts  MC per motif at motif_counts[count_off[j] .. + #motifs of the set]
  *   purity      AP (NaN for an empty allele); edit_dist / max_dist: the integers calc_purity divides
+ * Limits (the same for the motif sets of trgt_locus_batch): a set's model has 7 + sum(3 * len(motif) + 1) states; sets of up to
+ * 4096 states (1362 motif bases in total) and 253 motifs are labelled.  A larger set makes the call return TRGT_ERR_UNSUPPORTED --
+ * the message names the set and the limit -- before any output is written; a batch whose back-pointer workspace (one byte per
+ * state and base, states rounded up to 16) exceeds the workspace limit returns TRGT_ERR_NOMEM.
  */
 int trgt_hmm_batch(trgt_hip_ctx* ctx, int32_t n_sets, const uint8_t* motif_blob, const uint32_t* motif_off,
                    const uint32_t* set_motif_begin,

@@ -1289,6 +1289,7 @@ __global__ void hmm_viterbi_kernel(const HmmJobDev* __restrict__ jobs, const Hmm
 }
 
 #include "hmm_ppl.hpp"
+#include "hmm_big.hpp"
 
 // ---- trace-back of LONG alleles on many waves (DESIGN_HISTORY 7.3: "block-wise composed trace-back").  The chase of the back-pointers
 // is a serial chain of dependent look-ups -- a third of a long allele's time on one lane.  Here the columns are cut into chunks of
@@ -1738,13 +1739,17 @@ __global__ void __launch_bounds__(1024) hmm_resolve_kernel(const HmmResolveArgs 
 // class -- twenty dependent rounds of probes on one CU -- between the genotyper and the HMM of every call).  First launch: verdict per
 // candidate, counts per (class, length bin) through one atomic per wave and key; second launch: every workgroup scans the 8 x 64 counts
 // itself (longest bin first within a class) and reserves the places of its candidates, again one atomic per wave and key.
+constexpr int HMM_SLOT_CLASSES = 9;         // launch classes of the locus path: 0 .. 7 as in hmm_set_class, 8 = the large models (hmm_viterbi_big_kernel)
+constexpr int HMM_PPL_CLASSES = 8;          // classes 0 .. 7 can hold sets with a position-per-lane fill (ppl::PplSegs has a segment for each); the large models behind them cannot
+static_assert(HMM_SLOT_CLASSES == HMM_PPL_CLASSES + 1, "the class of the large models follows the classes of hmm_viterbi_kernel");
+constexpr int HMM_RESOLVE_KEYS = 64 * HMM_SLOT_CLASSES;  // (class, length bin) counters
 struct HmmResolveAllArgs {
   const HmmJobDev* cand; uint32_t n;        // all candidates, classes back to back
-  uint32_t class_begin[9];                  // class k = candidates [class_begin[k], class_begin[k + 1])
+  uint32_t class_begin[HMM_SLOT_CLASSES + 1];  // class k = candidates [class_begin[k], class_begin[k + 1])
   const uint8_t* skip_locus; const int32_t* n_alleles; const uint32_t* allele_len;
   HmmJobDev* jobs; uint32_t* n_jobs;        // job list of class k at jobs + class_begin[k], its length at n_jobs[k]
   uint32_t* n_spans; double* purity;
-  uint32_t* verdict; uint32_t* hist; uint32_t* taken;  // [n], [512], [512] (hist and taken cleared by the caller)
+  uint32_t* verdict; uint32_t* hist; uint32_t* taken;  // [n], [HMM_RESOLVE_KEYS], [HMM_RESOLVE_KEYS] (hist and taken cleared by the caller)
   uint32_t len_shift;
   const uint8_t* seq_blob; uint8_t* dup;   // dup [n] (optional): 1 = the second allele of a locus equals the first -- no job, its results are copied (hmm_dup_copy_kernel)
 };
@@ -1762,7 +1767,7 @@ __device__ __forceinline__ void hmm_wave_keys(bool on, uint32_t key, int lane, u
 __device__ __forceinline__ uint32_t hmm_class_of(const HmmResolveAllArgs& a, uint32_t i) {
   uint32_t k = 0;
 #pragma unroll
-  for (int c = 1; c < 8; ++c) k += i >= a.class_begin[c] ? 1u : 0u;
+  for (int c = 1; c < HMM_SLOT_CLASSES; ++c) k += i >= a.class_begin[c] ? 1u : 0u;
   return k;
 }
 __global__ void __launch_bounds__(256) hmm_resolve_count_kernel(const HmmResolveAllArgs a) {
@@ -1800,10 +1805,10 @@ __global__ void __launch_bounds__(256) hmm_resolve_count_kernel(const HmmResolve
   if (v && rank == 0u) atomicAdd(&a.hist[key], count);
 }
 __global__ void __launch_bounds__(256) hmm_resolve_scatter_kernel(const HmmResolveAllArgs a) {
-  __shared__ uint32_t base[512];
-  for (uint32_t t = threadIdx.x; t < 512; t += 256) base[t] = a.hist[t];
+  __shared__ uint32_t base[HMM_RESOLVE_KEYS];
+  for (uint32_t t = threadIdx.x; t < (uint32_t)HMM_RESOLVE_KEYS; t += 256) base[t] = a.hist[t];
   __syncthreads();
-  if (threadIdx.x < 8) {  // exclusive scan of a class's bins, bin 0 (the longest alleles) first
+  if (threadIdx.x < (uint32_t)HMM_SLOT_CLASSES) {  // exclusive scan of a class's bins, bin 0 (the longest alleles) first
     uint32_t run = 0;
     for (int b = 0; b < 64; ++b) { const uint32_t h = base[threadIdx.x * 64 + b]; base[threadIdx.x * 64 + b] = run; run += h; }
     if (blockIdx.x == 0) a.n_jobs[threadIdx.x] = run;
@@ -1890,6 +1895,27 @@ static size_t hmm_lds_bytes(uint32_t S, uint32_t nb) {
 }
 
 
+// Launch class of a motif set: 0 = at most 32 states (two alleles per wave of hmm_viterbi_kernel), w = 1 .. max_waves: its workgroup
+// of w waves (a thread per lane), above that HMM_CLASS_BIG: hmm_viterbi_big_kernel (hmm_big.hpp; the lanes tiled over 1 024 threads).
+// trgt_hmm_batch launches hmm_viterbi_kernel with up to 16 waves, the locus path (hmm_enqueue_slots) with up to 7.
+constexpr uint32_t HMM_BATCH_MAX_WAVES = 16, HMM_SLOT_MAX_WAVES = 7, HMM_CLASS_BIG = 17;
+static inline uint32_t hmm_set_class(const HmmSetDev& sd, uint32_t max_waves) {
+  if (sd.S <= 32) return 0u;
+  const uint32_t w = (std::max(sd.S, sd.n_lanes) + 63) / 64;
+  return w <= max_waves ? w : HMM_CLASS_BIG;
+}
+// One class of large models behind the resolved job list [jobs, jobs + nj) (n_jobs_dev: its length on the device, or null)
+static int hmm_launch_big(trgt_hip_ctx* c, hipStream_t ls, uint32_t maxS, uint32_t maxnb, uint32_t nj, const HmmJobDev* d_jobs, const HmmSetDev* d_sets, const uint8_t* d_model,
+                          const uint8_t* d_seq, uint8_t* d_bp, uint32_t* d_visits, uint16_t* path, uint32_t* plen, int32_t* spans, uint32_t* nsp, uint32_t* cnt, double* pur,
+                          int32_t* edit, int32_t* maxd, const uint32_t* n_jobs_dev) {
+  const size_t lds = hmm_big_lds(maxS, maxnb).total;
+  if (lds > 160 * 1024) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: LDS need %zu B", lds);
+  if (lds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)hmm_viterbi_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(hmm_viterbi_big_kernel, dim3(nj), dim3(HMM_BIG_THREADS), lds, ls, d_jobs, d_sets, d_model, d_seq, d_bp, d_visits, path, plen, spans, nsp, cnt, pur, edit, maxd, nj, n_jobs_dev);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  return TRGT_OK;
+}
+
 // The position-per-lane fill (hmm_ppl.hpp) of one class's job list, in front of the class's trace-back launch on the same stream: one
 // launch per group width the class's sets need (lanes_mask: bit 0 = 8 lanes, 1 = 16, 2 = 32, 3 = 64); a launch walks the whole list
 // and takes the jobs of its width (groups of other widths idle: a wave without a job of its own returns at once).
@@ -1964,7 +1990,7 @@ int hmm_build_models(int32_t n_sets, const uint8_t* motif_blob, const uint32_t* 
         if (set_err[s]) continue;
         if (motifs.empty()) { set_err[s] = 2; continue; }
         build_set(motifs, blobs[s], sets[s]);
-        if (sets[s].S > 1024) set_err[s] = 3;
+        if (sets[s].S > HMM_BIG_MAX_STATES || sets[s].n_lanes > HMM_BIG_MAX_STATES) set_err[s] = 3;
         else if (sets[s].n_blocks > 254) set_err[s] = 4;
       }
     };
@@ -1981,7 +2007,7 @@ int hmm_build_models(int32_t n_sets, const uint8_t* motif_blob, const uint32_t* 
     for (int s = 0; s < n_sets; ++s) {
       if (set_err[s] == 1) { snprintf(msg, sizeof msg, "trgt_hmm_batch: empty motif in set %d", s); out.err = msg; return out.rc = TRGT_ERR_INVALID; }
       if (set_err[s] == 2) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has no motif", s); out.err = msg; return out.rc = TRGT_ERR_INVALID; }
-      if (set_err[s] == 3) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has %u HMM states (kernel limit 1024)", s, sets[s].S); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
+      if (set_err[s] == 3) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has %u HMM states on %u lanes (kernel limit %u)", s, sets[s].S, sets[s].n_lanes, HMM_BIG_MAX_STATES); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
       if (set_err[s] == 4) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has too many motifs", s); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
       total += blobs[s].size();
     }
@@ -2041,7 +2067,7 @@ int hmm_models_on_device(trgt_hip_ctx* c, int32_t n_sets, const uint8_t* motif_b
     }
     HmmSetDev& d = sets[(size_t)s];
     const uint64_t bytes = layout_set(mlens.data(), (uint32_t)mlens.size(), d, blocks, perm);
-    if (d.S > 1024) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has %u HMM states (kernel limit 1024)", s, d.S); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
+    if (d.S > HMM_BIG_MAX_STATES || d.n_lanes > HMM_BIG_MAX_STATES) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has %u HMM states on %u lanes (kernel limit %u)", s, d.S, d.n_lanes, HMM_BIG_MAX_STATES); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
     d.off_inlp += pos; d.off_em += pos; d.off_inst += pos; d.off_block += pos; d.off_nin += pos; d.off_level += pos;
     d.off_flags += pos; d.off_blocks += pos; d.off_motifs += pos; d.off_perm += pos;
     pos += bytes;
@@ -2193,7 +2219,7 @@ int trgt::hmm_enqueue(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets,
   jobs.resize((size_t)n_jobs);
   uint64_t bp_total = 0, visit_total = 0, seq_total = 0, span_total = 0, count_total = 0, path_total = 0;
   int64_t cells = 0;
-  auto set_class_of = [&](const HmmSetDev& sd_) { return sd_.S <= 32 ? 0u : (std::max(sd_.S, sd_.n_lanes) + 63) / 64; };
+  auto set_class_of = [&](const HmmSetDev& sd_) { return hmm_set_class(sd_, HMM_BATCH_MAX_WAVES); };
   uint64_t class_jobs[32] = {};
   for (int64_t j = 0; j < n_jobs; ++j) {
     if ((int32_t)job_set[j] >= n_sets) return fail(c, TRGT_ERR_INVALID, "trgt_hmm_batch: job %lld bad set", (long long)j);
@@ -2213,7 +2239,7 @@ int trgt::hmm_enqueue(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets,
     // bp_off = 16; no row of any job may ever start below 16 (tests/test_hmm_gpu.py compares both fills on long alleles)
     jd.bp_off = bp_total + 16; bp_total += 16 + align_up(spad * ((uint64_t)seq_len[j] + 2), 16);
     jd.visit_off = visit_total; visit_total += 3ull * ((uint64_t)seq_len[j] + 2);
-    { const uint64_t mw = c->knobs.hmm_no_long_tb ? 0 : hmm_map_words(sd.S, seq_len[j], hmm_long_min(class_jobs[std::min<uint32_t>(set_class_of(sd), 31u)])); jd.map_off = mw ? visit_total + 4 : 0; visit_total += mw ? mw + 4 : 0; }
+    { const uint64_t mw = c->knobs.hmm_no_long_tb || set_class_of(sd) == HMM_CLASS_BIG ? 0 : hmm_map_words(sd.S, seq_len[j], hmm_long_min(class_jobs[std::min<uint32_t>(set_class_of(sd), 31u)])); jd.map_off = mw ? visit_total + 4 : 0; visit_total += mw ? mw + 4 : 0; }
     seq_total = std::max<uint64_t>(seq_total, seq_off[j] + seq_len[j]);
     if (spans3) span_total = std::max<uint64_t>(span_total, span_off[j] + seq_len[j] + 1);
     count_total = std::max<uint64_t>(count_total, count_off[j] + (sd.n_blocks - 1));
@@ -2223,7 +2249,7 @@ int trgt::hmm_enqueue(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets,
   }
   if (bp_total > c->ws_limit) return fail(c, TRGT_ERR_NOMEM, "trgt_hmm_batch: back-pointer workspace %llu B exceeds limit", (unsigned long long)bp_total);
   // class 0: at most 32 states (two alleles per wave); else the number of waves per allele
-  auto job_class = [&](const HmmJobDev& j) { const HmmSetDev& sd_ = sets[j.set]; return sd_.S <= 32 ? 0u : (std::max(sd_.S, sd_.n_lanes) + 63) / 64; };
+  auto job_class = [&](const HmmJobDev& j) { return hmm_set_class(sets[j.set], HMM_BATCH_MAX_WAVES); };
   {  // (usually one class: skip the sort then)
     bool mixed = false;
     const uint32_t c0 = job_class(jobs[0]);
@@ -2328,7 +2354,8 @@ int trgt::hmm_enqueue(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets,
     }
     if (c->knobs.hmm_no_ppl) ppl_mask = 0;
     const bool half = cls == 0;  // two alleles per wave
-    const size_t lds_job = (hmm_lds_bytes(maxS, maxnb) + 15) & ~(size_t)15;
+    const bool big = cls == HMM_CLASS_BIG;  // (hmm_viterbi_big_kernel: no position-per-lane fill, its own trace-back for every length)
+    const size_t lds_job = big ? 0 : (hmm_lds_bytes(maxS, maxnb) + 15) & ~(size_t)15;
     const size_t lds = half ? 2 * lds_job : lds_job;
     if (lds > 160 * 1024) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: LDS need %zu B", lds);
     const bool regs = !c->knobs.hmm_lds_fill;  // one-wave classes keep the score columns in registers (TRGT_HMM_LDS_FILL=1: in LDS like the others)
@@ -2347,6 +2374,13 @@ int trgt::hmm_enqueue(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets,
     ++n_class;
     KTimer t(c, TRGT_K_HMM, ls);
     const uint32_t nj = (uint32_t)(e - i);
+    if (big) {
+      if ((rc = hmm_launch_big(c, ls, maxS, maxnb, nj, (const HmmJobDev*)d_jobs + i, (const HmmSetDev*)d_sets, (const uint8_t*)d_model, d_seq, (uint8_t*)d_bp, (uint32_t*)d_visits,
+                               o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev, nullptr))) return rc;
+      t.stop(i == 0 ? cells : 0);
+      i = e;
+      continue;
+    }
     const dim3 grid(half ? (nj + 1) / 2 : nj), block(half ? 64 : 64 * cls);
 #define TRGT_HMM_LAUNCH(SB, OW)                                                                                                    \
     hipLaunchKernelGGL((hmm_viterbi_kernel<SB, OW>), grid, block, lds, ls, (const HmmJobDev*)d_jobs + i, (const HmmSetDev*)d_sets,   \
@@ -2411,18 +2445,17 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
   const std::vector<HmmSetDev>& sets = mp->sets;
   std::unique_ptr<HmmPending> P(new HmmPending());
   P->n_jobs = n_slots; P->spans3 = spans3; P->span_off = span_off; P->set = buffer_set; P->stream = c->stream;
-  auto set_class = [&](const HmmSetDev& sd) { return sd.S <= 32 ? 0u : (std::max(sd.S, sd.n_lanes) + 63) / 64; };
+  constexpr int NC = HMM_SLOT_CLASSES, BIG = HMM_SLOT_CLASSES - 1;  // (the classes of hmm_viterbi_kernel keep their numbers and launch shapes)
+  auto set_class = [&](const HmmSetDev& sd) { const uint32_t k = hmm_set_class(sd, HMM_SLOT_MAX_WAVES); return k == HMM_CLASS_BIG ? (uint32_t)BIG : k; };
   // candidates by class (a counting sort: loci keep their order inside a class)
-  uint32_t class_n[8] = {0, 0, 0, 0, 0, 0, 0, 0}, class_begin[9];
+  uint32_t class_n[NC] = {}, class_begin[NC + 1];
   for (int64_t l = 0; l < nl; ++l) {
     if (in.host_skip && in.host_skip[l]) continue;
-    const uint32_t k = set_class(sets[(size_t)l]);
-    if (k >= 8) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: a model of %u states", sets[(size_t)l].S);
-    class_n[k] += 2;
+    class_n[set_class(sets[(size_t)l])] += 2;
   }
   class_begin[0] = 0;
-  for (int k = 0; k < 8; ++k) class_begin[k + 1] = class_begin[k] + class_n[k];
-  const uint32_t n_cand = class_begin[8];
+  for (int k = 0; k < NC; ++k) class_begin[k + 1] = class_begin[k] + class_n[k];
+  const uint32_t n_cand = class_begin[NC];
   P->slot_nm.assign((size_t)n_slots, 0); P->slot_cnt_off.assign(count_off, count_off + n_slots);
   P->tight_off.assign(span_off, span_off + n_slots);
   P->spans_on_host = spans3 != nullptr;
@@ -2441,8 +2474,8 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
   HmmJobDev* cand = (HmmJobDev*)h_cand;
   uint64_t bp_total = 0, visit_total = 0;
   {
-    uint32_t at[8];
-    for (int k = 0; k < 8; ++k) at[k] = class_begin[k];
+    uint32_t at[NC];
+    for (int k = 0; k < NC; ++k) at[k] = class_begin[k];
     for (int64_t l = 0; l < nl; ++l) {
       if (in.host_skip && in.host_skip[l]) continue;
       const HmmSetDev& sd = sets[(size_t)l];
@@ -2455,7 +2488,7 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
         jd.seq_off = in.seq_off[sl]; jd.path_off = 0; jd.span_off = span_off[sl]; jd.count_off = count_off[sl];
         jd.bp_off = bp_total + 16; bp_total += 16 + align_up(spad * ((uint64_t)in.cap[l] + 2), 16);  // room for the longest allele the locus can have (+ the dump slot of hmm_fill_ppl_kernel)
         jd.visit_off = visit_total; visit_total += 3ull * ((uint64_t)in.cap[l] + 2);
-        { const uint64_t mw = c->knobs.hmm_no_long_tb ? 0 : hmm_map_words(sd.S, in.cap[l], hmm_long_min(class_n[k])); jd.map_off = mw ? visit_total + 4 : 0; visit_total += mw ? mw + 4 : 0; }
+        { const uint64_t mw = c->knobs.hmm_no_long_tb || k == (uint32_t)BIG ? 0 : hmm_map_words(sd.S, in.cap[l], hmm_long_min(class_n[k])); jd.map_off = mw ? visit_total + 4 : 0; visit_total += mw ? mw + 4 : 0; }
       }
     }
   }
@@ -2463,17 +2496,18 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
   if (bp_total > c->ws_limit) return fail(c, TRGT_ERR_NOMEM, "trgt_hmm_batch: back-pointer workspace %llu B exceeds limit", (unsigned long long)bp_total);
   void *d_jobs = nullptr, *d_bp = nullptr, *d_visits = nullptr;
   const size_t jobs_bytes = (size_t)n_cand * sizeof(HmmJobDev);
-  // (S_HMM_JOBS: candidates | job lists | 8 counts | 512 + 512 resolve counters | verdicts)
-  if ((rc = dev_get(c, S_HMM_JOBS + so, 2 * jobs_bytes + 64 + 4096 + 4 * (size_t)n_cand + (size_t)n_cand + 16, &d_jobs)) || (rc = dev_get(c, S_HMM_BP + so, (size_t)bp_total, &d_bp)) ||
+  // (S_HMM_JOBS: candidates | job lists | counts per class (16 words) | 2 x HMM_RESOLVE_KEYS resolve counters | verdicts)
+  constexpr size_t count_bytes = 64 + 8 * (size_t)HMM_RESOLVE_KEYS;
+  if ((rc = dev_get(c, S_HMM_JOBS + so, 2 * jobs_bytes + count_bytes + 4 * (size_t)n_cand + (size_t)n_cand + 16, &d_jobs)) || (rc = dev_get(c, S_HMM_BP + so, (size_t)bp_total, &d_bp)) ||
       (rc = dev_get(c, S_HMM_VISITS + so, (size_t)visit_total * 4, &d_visits)))
     return rc;
   HmmJobDev* const d_cand = (HmmJobDev*)d_jobs;
   void* d_pack_tabs = nullptr;
   HmmJobDev* const d_list = d_cand + n_cand;
-  // counts | histogram | places taken (64 + 4096 bytes, cleared): a piece of the call's zero arena when there is one
-  void* const z_count = zero_take(c, 64 + 4096);
+  // counts | histogram | places taken (cleared): a piece of the call's zero arena when there is one
+  void* const z_count = zero_take(c, count_bytes);
   uint32_t* const d_count = z_count ? (uint32_t*)z_count : (uint32_t*)((uint8_t*)d_jobs + 2 * jobs_bytes);
-  uint32_t* const d_verdict = (uint32_t*)((uint8_t*)d_jobs + 2 * jobs_bytes + 64 + 4096);
+  uint32_t* const d_verdict = (uint32_t*)((uint8_t*)d_jobs + 2 * jobs_bytes + count_bytes);
   {  // on the copy stream: a copy queued on the batch's stream would sit in the copy engine's queue until the genotyper in front of it
      // has run, and hold up every copy issued after it (the next batch's reads)
     hipStream_t us = c->stream_copy ? c->stream_copy : c->stream;
@@ -2505,7 +2539,7 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
   else TRGT_HIP_TRY(c, hipMemsetAsync(o_nsp.dev, 0, (size_t)n_slots * 4, c->stream));
   const uint8_t* d_dup = nullptr;
   if (c->knobs.hmm_resolve_one_wg) {
-    for (int k = 0; k < 8; ++k) {
+    for (int k = 0; k < NC; ++k) {
       if (!class_n[k]) continue;
       HmmResolveArgs ra{d_cand + class_begin[k], class_n[k], in.d_skip, in.d_n_alleles, in.d_allele_len, d_list + class_begin[k], d_count + k, o_nsp.dev, o_pur.dev, len_shift};
       hipLaunchKernelGGL(hmm_resolve_kernel, dim3(1), dim3(1024), 0, c->stream, ra);
@@ -2513,14 +2547,13 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
   } else {
     HmmResolveAllArgs ra;
     ra.cand = d_cand; ra.n = (uint32_t)n_cand;
-    for (int k = 0; k < 8; ++k) ra.class_begin[k] = (uint32_t)class_begin[k];
-    ra.class_begin[8] = (uint32_t)n_cand;
+    for (int k = 0; k <= NC; ++k) ra.class_begin[k] = (uint32_t)class_begin[k];
     ra.skip_locus = in.d_skip; ra.n_alleles = in.d_n_alleles; ra.allele_len = in.d_allele_len;
     ra.jobs = d_list; ra.n_jobs = d_count; ra.n_spans = o_nsp.dev; ra.purity = o_pur.dev;
-    ra.hist = d_count + 16; ra.taken = ra.hist + 512; ra.verdict = d_verdict; ra.len_shift = len_shift;
+    ra.hist = d_count + 16; ra.taken = ra.hist + HMM_RESOLVE_KEYS; ra.verdict = d_verdict; ra.len_shift = len_shift;
     ra.seq_blob = in.seq_blob_dev; ra.dup = c->knobs.hmm_no_dedupe ? nullptr : reinterpret_cast<uint8_t*>(ra.verdict + n_cand);
     d_dup = ra.dup;
-    if (!z_count) TRGT_HIP_TRY(c, hipMemsetAsync(d_count, 0, 64 + 4096, c->stream));
+    if (!z_count) TRGT_HIP_TRY(c, hipMemsetAsync(d_count, 0, count_bytes, c->stream));
     const dim3 rg((unsigned)((n_cand + 255) / 256));
     hipLaunchKernelGGL(hmm_resolve_count_kernel, rg, dim3(256), 0, c->stream, ra);
     hipLaunchKernelGGL(hmm_resolve_scatter_kernel, rg, dim3(256), 0, c->stream, ra);
@@ -2532,23 +2565,24 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
   //      each of up to four classes -- the stage had more streams than HIP has hardware queues, and what shares a queue runs one after
   //      the other: in a cfg4 trace the second 64-lane fill began 0.7 ms after the stage did (1.47 ms for the stage; 0.57 + 0.3 are its
   //      longest fill and trace-back).  TRGT_HMM_PPL_PER_CLASS=1: as before.
-  unsigned class_ppl_mask[8] = {0, 0, 0, 0, 0, 0, 0, 0}, all_ppl_mask = 0;
+  unsigned class_ppl_mask[HMM_PPL_CLASSES] = {}, all_ppl_mask = 0;
   if (!c->knobs.hmm_no_ppl)
-    for (uint32_t k = 0; k < 8; ++k) {
+    for (uint32_t k = 0; k < (uint32_t)HMM_PPL_CLASSES; ++k) {
       for (uint32_t i = class_begin[k]; i < class_begin[k + 1]; i += 2) class_ppl_mask[k] |= hmm_ppl_bit(sets[cand[i].set]);
       all_ppl_mask |= class_ppl_mask[k];
     }
   const bool ppl_merged = all_ppl_mask != 0 && !c->knobs.hmm_ppl_per_class;
   if (ppl_merged) {
     ppl::PplSegs segs{};
-    for (int k = 0; k <= 8; ++k) segs.begin[k] = k < 8 ? (uint32_t)class_begin[k] : (uint32_t)n_cand;
-    segs.n_seg = 8; segs.counts = (const uint32_t*)d_count;
+    static_assert(sizeof(segs.begin) / sizeof(segs.begin[0]) == HMM_PPL_CLASSES + 1, "a segment per class that can have such a fill");
+    for (int k = 0; k <= HMM_PPL_CLASSES; ++k) segs.begin[k] = (uint32_t)class_begin[k];  // (the large models behind them have no such fill)
+    segs.n_seg = HMM_PPL_CLASSES; segs.counts = (const uint32_t*)d_count;
     // a width's launch spans the classes that hold sets of that width, not the whole list: a workgroup that finds no job of its width
     // ends at once, but 17 000 of them in front of 3 000 that work made the 64-lane launch of cfg4 0.73 ms instead of 0.54
     for (int w = 0; w < 4; ++w) {
       segs.first_slot[w] = segs.end_slot[w] = 0;
       bool any = false;
-      for (int k = 0; k < 8; ++k)
+      for (int k = 0; k < HMM_PPL_CLASSES; ++k)
         if (class_ppl_mask[k] & (1u << w)) { if (!any) segs.first_slot[w] = segs.begin[k]; segs.end_slot[w] = segs.begin[k + 1]; any = true; }
     }
     KTimer tf(c, TRGT_K_HMM, c->stream);
@@ -2560,13 +2594,14 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
   TRGT_HIP_TRY(c, hipEventRecord(c->hmm_fork[buffer_set ? 1 : 0], c->stream));  // (behind the resolve kernel and the merged fills, in front of the first class launch)
   int n_class = 0;
   unsigned side_used = 0;
-  for (uint32_t k = 0; k < 8; ++k) {
+  for (uint32_t k = 0; k < (uint32_t)NC; ++k) {
     if (!class_n[k]) continue;
     uint32_t maxS = 0, maxnb = 0;
     for (uint32_t i = class_begin[k]; i < class_begin[k + 1]; i += 2) { const HmmSetDev& sd = sets[cand[i].set]; maxS = std::max(maxS, sd.S); maxnb = std::max(maxnb, sd.n_blocks); }
-    const unsigned ppl_mask = class_ppl_mask[k];
+    const bool big = k == (uint32_t)BIG;
+    const unsigned ppl_mask = big ? 0u : class_ppl_mask[k];
     const bool half = k == 0;
-    const size_t lds_job = (hmm_lds_bytes(maxS, maxnb) + 15) & ~(size_t)15;
+    const size_t lds_job = big ? 0 : (hmm_lds_bytes(maxS, maxnb) + 15) & ~(size_t)15;
     const size_t lds = half ? 2 * lds_job : lds_job;
     if (lds > 160 * 1024) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: LDS need %zu B", lds);
     const bool regs = !c->knobs.hmm_lds_fill;  // one-wave classes keep the score columns in registers (TRGT_HMM_LDS_FILL=1: in LDS like the others)
@@ -2585,6 +2620,12 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
     ++n_class;
     KTimer t(c, TRGT_K_HMM, ls);
     const uint32_t nj = class_n[k];
+    if (big) {
+      if ((rc = hmm_launch_big(c, ls, maxS, maxnb, nj, (const HmmJobDev*)d_list + class_begin[k], (const HmmSetDev*)mp->d_sets, (const uint8_t*)mp->d_blob, in.seq_blob_dev, (uint8_t*)d_bp,
+                               (uint32_t*)d_visits, o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev, (const uint32_t*)(d_count + k)))) return rc;
+      t.stop(0);
+      continue;
+    }
     const dim3 grid(half ? (nj + 1) / 2 : nj), block(half ? 64 : 64 * k);
 #define TRGT_HMM_LAUNCH(SB, OW)                                                                                                    \
     hipLaunchKernelGGL((hmm_viterbi_kernel<SB, OW>), grid, block, lds, ls, (const HmmJobDev*)d_list + class_begin[k], (const HmmSetDev*)mp->d_sets, \

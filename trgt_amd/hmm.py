@@ -64,6 +64,9 @@ def collapse_labels(spans):  # utils.rs:11-27
     return out
 
 
+MAX_STATES = 4096  # largest model the library labels (include/trgt_hip.h, trgt_hmm_batch); a larger set is TRGT_ERR_UNSUPPORTED
+
+
 def num_states(motifs):  # builder.rs:6
     return 7 + sum(3 * len(m) + 1 for m in motifs)
 
