@@ -3,13 +3,18 @@
 paths, spans, motif counts, edit / max distances and the bits of the f64 purity of every job.  A developer tool (the GPU suite keeps
 small batches of the same shapes: tests/test_hmm_gpu.py).
 
-    python tests/tools/hmm_fuzz.py [sets_per_round=2000] [rounds=10] [seed=1]
+    python tests/tools/hmm_fuzz.py [sets_per_round=2000] [rounds=10] [seed=1] [--pyhmm[=CELLS]]
+
+--pyhmm also holds the GPU's output to tests/pyhmm.py, the restatement written from the reference alone (bit for bit, plus the exact
+optimality of paths within its budget): the round's jobs in their order until their states x columns add up to CELLS (default 20 M,
+about a minute of Python per round).  Only rounds that ask for state paths.
 """
 import os
 import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(1, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from trgt_amd import hmm as H
 from oracle import binding as oracle
@@ -71,7 +76,37 @@ def compare(batch, got, ref, n_jobs, want_path):
     return None
 
 
+def compare_pyhmm(sets, jobs, got, budget):
+    """the first jobs of the round (states x columns within `budget`) as a batch of their own slice of `got`, against pyhmm"""
+    import hmm_cases as HC
+    import pyhmm
+    models, refs, cells = {}, [], 0
+    for s, a in jobs:
+        cells += H.num_states(sets[s]) * (len(a) + 2)
+        if cells > budget:
+            break
+        if s not in models:
+            models[s] = pyhmm.build(pyhmm.clean_motifs(sets[s]))
+        r = pyhmm.annotate(models[s], len(sets[s]), a)
+        r["model"], r["optimum"] = models[s], None
+        if r["seq"] and models[s].n * (len(r["seq"]) + 2) <= HC.EXACT_BUDGET:
+            r["optimum"] = pyhmm.label(models[s], r["seq"], "exact").score
+        refs.append(r)
+    try:
+        HC.check_batch(H.pack_hmm_batch(sets, jobs), got, refs, "pyhmm")  # (offsets of a prefix of the jobs are those of the whole batch)
+    except AssertionError as e:
+        return "pyhmm %s" % (e,), len(refs)
+    return None, len(refs)
+
+
 def main():
+    flags = [a for a in sys.argv[1:] if a.startswith("--")]
+    sys.argv = [a for a in sys.argv if not a.startswith("--")]
+    py_budget = 0
+    for f in flags:
+        if f.split("=")[0] != "--pyhmm":
+            sys.exit("unknown option %s" % f)
+        py_budget = int(float(f.split("=")[1])) if "=" in f else 20_000_000
     n_sets = int(sys.argv[1]) if len(sys.argv) > 1 else 2000
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 10
     seed = int(sys.argv[3]) if len(sys.argv) > 3 else 1
@@ -113,6 +148,9 @@ def main():
         ref = oracle.hmm_batch(batch, n_threads=threads, want_path=want_path)
         tc = time.perf_counter() - t0
         why = compare(batch, got, ref, len(jobs), want_path)
+        if why is None and py_budget and want_path:
+            why, n_py = compare_pyhmm(sets, jobs, got, py_budget)
+            print("[hmm fuzz]          %d jobs held to pyhmm" % n_py, flush=True)
         bad += why is not None
         jobs_total += len(jobs)
         print("[hmm fuzz] round %2d %-14s sets %5d jobs %6d paths %-3s gpu %.2fs oracle %.1fs  %s" % (r, kind, n_sets, len(jobs), "yes" if want_path else "no", tg, tc, "OK" if why is None else "MISMATCH: " + why), flush=True)
