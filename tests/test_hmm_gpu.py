@@ -19,9 +19,9 @@ def hmm():
     return H
 
 
-def _same(oracle, H, motif_sets, jobs, want_path=True):
+def _same(oracle, H, motif_sets, jobs, want_path=True, ctx=None):
     batch = H.pack_hmm_batch(motif_sets, jobs)
-    got = H.hmm_batch(batch, want_path=want_path)
+    got = H.hmm_batch(batch, ctx=ctx, want_path=want_path)
     ref = oracle.hmm_batch(batch, n_threads=4, want_path=want_path)
     assert np.array_equal(got["n_spans"], ref["n_spans"])
     assert np.array_equal(got["path_len"], ref["path_len"])
@@ -162,6 +162,33 @@ def test_long_alleles_parallel_traceback(oracle, hmm):
         for j in range(len(jobs)):  # (behind a job's path the buffer holds what the reversal left there)
             po, pl = int(batch["path_off"][j]), int(a["path_len"][j])
             assert np.array_equal(a["path"][po:po + pl], b["path"][po:po + pl]), (env, j)
+
+
+def test_every_launch_class_in_one_call(oracle, hmm):
+    # one set per launch class of trgt_hmm_batch -- two alleles per wave, one / two / four / six / eight waves, the large models --
+    # in ONE call: seven classes through the one class launcher, more than the three side streams of a buffer set, so their rotation
+    # wraps.  Every set has a short allele and one of 600 bases: a class of at most 256 jobs sends alleles of 512 columns and more to
+    # hmm_traceback_long_kernel, so every class but the large one also launches the long trace-back behind its fill, on its side
+    # stream -- in three phases by default, in one launch with TRGT_HMM_LONG_WGS=1.
+    from trgt_amd import _lib
+    rng = np.random.default_rng(1045)
+    sets = [[rand_dna(rng, 3)], [rand_dna(rng, 10)], [rand_dna(rng, 30), rand_dna(rng, 3)], [rand_dna(rng, 40), rand_dna(rng, 40)],
+            [rand_dna(rng, 60), rand_dna(rng, 60), rand_dna(rng, 3)], [rand_dna(rng, 150)], [rand_dna(rng, 340), b"CAG", b"AT"]]
+    assert [hmm.num_states(s) for s in sets] == [17, 38, 108, 249, 379, 458, 1045]
+    jobs = []
+    for s, motifs in enumerate(sets):
+        jobs.append((s, repeat_allele(rng, motifs, 40, err=0.02)))
+        jobs.append((s, repeat_allele(rng, motifs, 600, err=0.02)))
+    assert all(len(a) + 2 >= 512 for _, a in jobs[1::2])
+    jobs = [jobs[int(i)] for i in rng.permutation(len(jobs))]
+    for want_path in (True, False):
+        _same(oracle, hmm, sets, jobs, want_path=want_path)
+    ctx = _lib.context_with_env(TRGT_HMM_LONG_WGS=1)
+    try:
+        for want_path in (True, False):
+            _same(oracle, hmm, sets, jobs, want_path=want_path, ctx=ctx)
+    finally:
+        ctx.close()
 
 
 def test_register_fill_variants_agree(oracle, hmm):

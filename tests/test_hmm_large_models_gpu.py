@@ -81,6 +81,24 @@ def test_hmm_batch_sizes_around_the_old_limits(oracle, hmm):
     _same(oracle, hmm, sets, jobs)
 
 
+def test_large_model_visit_records_and_dropped_copies(oracle, hmm):
+    # the branches of the shared step decoder behind hmm_viterbi_big_kernel: 200 visits of a 3-base motif are more than the
+    # HMM_VIS_LDS = 64 records kept in LDS plus one staged chunk of 85 read back from the workspace (records in LDS, in the
+    # workspace, and a second chunk of the read-back); the mutated allele has copies that remove_imperfect_motifs drops
+    rng = np.random.default_rng(340)
+    sets = [[rand_dna(rng, 340), b"CAG", b"AT"]]
+    assert hmm.num_states(sets[0]) == 1045  # past the 1 024 states of hmm_viterbi_kernel
+    clean = b"CAG" * 200
+    jobs = [(0, clean), (0, mutate(rng, clean, 0.01, 0.005, 0.005))]
+    batch = hmm.pack_hmm_batch(sets, jobs)
+    ref = oracle.hmm_batch(batch, n_threads=2)
+    co = batch["count_off"]
+    assert int(ref["counts"][int(co[0]):int(co[0]) + 3].sum()) >= 150 and int(ref["n_spans"][0]) >= 1
+    assert int(ref["n_spans"][1]) >= 2
+    for want_path in (True, False):
+        _same(oracle, hmm, sets, jobs, want_path=want_path)
+
+
 def test_locus_batch_large_motif_sets(oracle):
     from trgt_amd import locus
     rng = np.random.default_rng(4096)

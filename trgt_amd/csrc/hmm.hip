@@ -457,6 +457,8 @@ __device__ __forceinline__ uint32_t hmm_pred_entry(uint32_t pr, int S, int nb, c
   return pr | ((uint32_t)(g_flags[pr] & 1) << 15) | (hmm_bp_loc((int)pr, nb, (int)g_block[pr], g_blocks) << 16);
 }
 
+#include "hmm_traceback.hpp"
+
 // ONE_WAVE (models of at most 64 states: one state per lane of ONE wave, or two alleles of at most 32 states in its halves): the score
 // columns of the fill live in REGISTERS -- a state's predecessors are fetched from their lanes (ds_bpermute: one LDS-crossbar round per
 // pass, nothing written) instead of through two LDS arrays (a write, a fence and a read per pass), and what the run-end lane worked out
@@ -505,8 +507,6 @@ __global__ void hmm_viterbi_kernel(const HmmJobDev* __restrict__ jobs, const Hmm
   }
   // ---- LDS carve-up (all dynamic, 16-byte aligned pieces; no static LDS in front of it)
   int* tb = reinterpret_cast<int*>(lds);  // traceback state shared between the walker and the stagers
-  int &tb_state = tb[0], &tb_idx = tb[1], &tb_done = tb[2], &tb_npath = tb[3], &tb_nvisit = tb[4], &tb_edit = tb[5],
-      &tb_ref = tb[6], &tb_next = tb[7], &tb_vb1 = tb[8];
   uint32_t* l_inst = reinterpret_cast<uint32_t*>(lds + 64);           // [S][4] hmm_pred_entry (predecessor b of state s at 4 s + b: 16 bytes per state, one read)
   double* sc0 = reinterpret_cast<double*>(l_inst + 4 * S);
   double* sc1 = sc0 + S;
@@ -1101,190 +1101,29 @@ __global__ void hmm_viterbi_kernel(const HmmJobDev* __restrict__ jobs, const Hmm
     if (tid == 0) long_list[1 + atomicAdd(long_list, 1u)] = jidx;
     return;
   }
-  if (tid == 0) {
-    tb_state = S - 1; tb_idx = L - 1; tb_done = 0; tb_npath = 0; tb_nvisit = 0; tb_edit = 0; tb_ref = 0; tb_next = -1; tb_vb1 = 0;
-  }
+  if (tid == 0) hmm_trace_init(tb, S, L);
   hmm_sync_mem(sync_n);  // the back-pointer columns written by all waves are read back from here on
 
-  // ---- traceback (hmm_model.rs:125-142) fused with get_events/calc_purity (events.rs:17-86, purity.rs:6-41)
-  //      and motif-visit collection (operations.rs:26-40); back-pointer columns are staged through LDS.
-  //      Thread 0 only CHASES the back-pointers (state, column -> predecessor: two LDS round trips and a dozen instructions per step)
-  //      and notes the states it passes, HMM_REC at a time; what each step means -- its events, its part of the edit count, the motif
-  //      visit it closes -- is then worked out for all noted steps at once, one lane per step.  (Everything in one loop on one lane was
-  //      90 instructions per step: 750 cycles, a third of the kernel.)  What a step needs from its neighbours is little: the state
-  //      walked just before it (the implied leading deletions of a block start) and the column of the last block end before it (the
-  //      bases of the visit a block start closes): a lane shift and a ballot.
+  // ---- traceback, fused with the events, the purity counts and the motif-visit collection (hmm_traceback.hpp).
   // rows of the back-pointer workspace: one byte per state (this kernel's own fill, the round-5 layout of the position-per-lane fill) or
   // one byte per lane of the job's group (hmm_fill_ppl_kernel<G, true>)
   const bool packed = ppl_filled && ppl_packed && set.ppl_lanes != 0u;
   const int rstride = packed ? hmm_ppl_group(set.ppl_lanes) : Spad;
   const int cols_per_chunk = packed ? hmm_stage_bytes(Spad) / rstride - 2 : max(1, hmm_stage_bytes(Spad) / Spad);
-  int& tb_loc = tb[11];  // hmm_bp_loc of tb_state
-  if (tid == 0) tb_loc = 0;  // (the end state: a constant 0)
+  if (tid == 0) tb[TB_LOC] = 0;  // (the end state: a constant 0)
   uint16_t* pbuf = path ? path + job.path_off : nullptr;
   uint32_t* const g_vis = visit_ws + job.visit_off;  // visits HMM_VIS_LDS, HMM_VIS_LDS + 1, ... at their own index
   const int pcap = (int)job.path_cap;
   constexpr int HMM_REC = SUB == 32 ? 32 : 64;  // steps per round: the lanes of the job's first wave
-  int &tb_nrec = tb[9], &tb_more = tb[10];      // steps noted in this round; 1: the chunk has more, 0: it is exhausted, 2: the walk is over
-  const int hwlane = (int)(threadIdx.x & 63u);
-  const unsigned long long gmask = SUB == 32 ? (0xFFFFFFFFull << (hwlane & 32)) : ~0ull;  // the lanes of my job in this wave
-  const unsigned long long below = gmask & ((1ull << hwlane) - 1ull);
-  while (true) {
-    if (tb_done) break;
-    const int c1 = tb_idx + 1, c0 = packed ? (max(0, c1 - cols_per_chunk) & ~1) : max(0, c1 - cols_per_chunk);  // (rows of 8 bytes: an even column starts a 16-byte piece)
-    {
-      const uint4* src = reinterpret_cast<const uint4*>(bp + (size_t)c0 * rstride);
-      uint4* dst = reinterpret_cast<uint4*>(l_stage);
-      const int n16 = ((c1 - c0) * rstride + 15) / 16;
-      for (int i = tid; i < n16; i += nthr) dst[i] = src[i];
-      // ... and the symbol codes of the same columns, plus those a motif copy starting in the last of them reaches into
-      win0 = c0;
-      for (int k = tid; k < c1 - c0 + HMM_CODE_PAD && c0 + k < L; k += nthr) l_seq[k] = (uint8_t)hmm_code(seq, c0 + k, L);
-    }
-    hmm_sync(sync_n);
-    for (;;) {
-      if (tid == 0) {  // ---- the chase
-        int state = tb_state, idx = tb_idx, n = 0;
-        int row = (idx - c0) * rstride;  // offset of column idx in the staged chunk
-        int emits = (int)((l_info[state] >> 3) & 1u);
-        uint32_t loc = (uint32_t)tb_loc;
-        while (state != 0 && idx >= c0 && n < HMM_REC) {
-          l_rec[2 * n] = (uint32_t)state; l_rec[2 * n + 1] = (uint32_t)idx; ++n;
-          const uint4 pred4 = *reinterpret_cast<const uint4*>(l_inst + 4 * state);  // all four predecessors: no second round trip behind b
-          int b;
-          if (packed) {
-            b = (int)hmm_bp_unpack(l_stage[row + (int)(loc & 63u)], loc);
-            if (state == S - 2) b = (int)hmm_bp_run_end(*reinterpret_cast<const uint32_t*>(l_stage + row));
-          } else b = l_stage[row + state];
-          uint32_t pe = (b & 2) ? ((b & 1) ? pred4.w : pred4.z) : ((b & 1) ? pred4.y : pred4.x);  // predecessor | its "emits" bit << 15 | its hmm_bp_loc << 16
-          if (state == S - 2) { const uint32_t be_ = l_blocks[1 * nb + b]; pe = be_ | ((uint32_t)(l_flags[be_] & 1) << 15) | (hmm_bp_loc_block_end(b, nb, l_blocks) << 16); }  // the run end: from a block end
-          if (emits) { --idx; row -= rstride; }
-          emits = (int)((pe >> 15) & 1u);
-          state = (int)(pe & 0x7FFFu);
-          loc = pe >> 16;
-        }
-        tb_state = state; tb_idx = idx; tb_nrec = n; tb_loc = (int)loc;
-        tb_more = state == 0 ? 2 : (idx >= c0 ? 1 : 0);
-      }
-      hmm_sync(sync_n);
-      const int more = tb_more;  // (read before the next barrier: thread 0 writes it again right behind that one)
-      if (tid < HMM_REC) {  // ---- what the noted steps mean (events.rs:17-86, purity.rs:6-41, operations.rs:26-57), one lane per step
-        const int n = tb_nrec, np0 = tb_npath, nv0 = tb_nvisit, nxt0 = tb_next, vb0 = tb_vb1;
-        const bool valid = tid < n;
-        const int state = valid ? (int)l_rec[2 * tid] : 0, idx = valid ? (int)l_rec[2 * tid + 1] : 0;
-        const uint32_t inf = valid ? l_info[state] : 0u;
-        const int kind = (int)(inf & 7u), blk = (int)((inf >> 8) & 0xFFu), expected = (int)((inf >> 16) & 0xFFu);
-        if (valid && pbuf && np0 + tid < pcap) pbuf[pcap - 1 - (np0 + tid)] = (uint16_t)state;
-        // the state walked just before this one (the step before: the lane before)
-        const int up = __shfl_up(state, 1);
-        const int nxt = tid == 0 ? nxt0 : up;
-        // MotifStart (1) adds the implied leading deletions, Skip (3) / Mismatch / Ins (5) / Del (6) are edits, Skip / Match-state /
-        // Del consume a reference base
-        const int qbase = valid ? hmm_code_char(code_at(idx)) : 0;
-        const int dels = kind == 1 ? nxt - state - 1 : 0;
-        const int mism = kind == 4 && !(qbase == expected || expected == 'N');  // events.rs:66-73
-        int edit = valid ? dels + (kind == 3) + mism + (kind == 5) + (kind == 6) : 0;
-        int ref = valid ? dels + (kind == 3) + (kind == 4) + (kind == 6) : 0;
-        // the last block end (2) walked before this step: the bases of the visit a block start (1) closes are query[idx .. vb1)
-        const unsigned long long ends = __ballot(valid && kind == 2) & gmask, starts = __ballot(valid && kind == 1) & gmask;
-        const unsigned long long ends_below = ends & below;
-        const int src_end = ends_below ? 63 - (int)__builtin_clzll(ends_below) : hwlane;
-        const int idx_end = __shfl(idx, src_end);
-        const int vb1 = ends_below ? idx_end : vb0;
-        if (valid && kind == 1) {  // a motif visit
-          // remove_imperfect_motifs(.., 6) (operations.rs:45-57): only copies of STR motifs can be dropped -- short ones, and ones
-          // whose bases differ from the motif (its bases are columns idx + 1 .. idx + mlen: in the window)
-          uint32_t drop = 0;
-          const int mlen = (int)l_blocks[2 * nb + blk];
-          if (blk != nb - 1 && mlen <= 6) {
-            if (vb1 - idx < mlen) drop = 1;
-            else {
-              const uint8_t* mot = motif_bytes + l_blocks[3 * nb + blk];
-              for (int j = 0; j < mlen; ++j) {
-                const int obs = hmm_code_char(code_at(idx + j + 1));
-                if (mot[j] != 'N' && obs != mot[j]) drop = 1;
-              }
-            }
-          }
-          const int nv = nv0 + (int)__builtin_popcountll(starts & below);
-          uint32_t* vrec = nv < HMM_VIS_LDS ? l_vis + 3 * nv : g_vis + 3 * (size_t)nv;
-          vrec[0] = (uint32_t)blk | (drop << 15); vrec[1] = (uint32_t)idx; vrec[2] = (uint32_t)vb1;
-        }
-        // sums over the round (butterfly inside the job's lanes)
-#pragma unroll
-        for (int o = HMM_REC / 2; o >= 1; o >>= 1) { edit += __shfl_xor(edit, o); ref += __shfl_xor(ref, o); }
-        const int src_last_end = ends ? 63 - (int)__builtin_clzll(ends) : hwlane;
-        const int idx_last_end = __shfl(idx, src_last_end);
-        const int last_state = __shfl(state, (hwlane & ~(HMM_REC - 1)) + max(n - 1, 0));
-        if (tid == 0) {
-          int np = np0 + n;
-          if (more == 2) { if (pbuf && np < pcap) pbuf[pcap - 1 - np] = 0; ++np; tb_done = 1; }
-          tb_npath = np; tb_nvisit = nv0 + (int)__builtin_popcountll(starts); tb_edit += edit; tb_ref += ref;
-          if (n > 0) tb_next = last_state;
-          if (ends) tb_vb1 = idx_last_end;
-        }
-      }
-      hmm_sync(sync_n);
-      if (more != 1) break;
-    }
-  }
-  const int np = tb_npath;
+  const unsigned long long gmask = SUB == 32 ? (0xFFFFFFFFull << (threadIdx.x & 32u)) : ~0ull;  // the lanes of my job in this wave
+  const HmmSyncN sync{sync_n};
+  const HmmTraceLds tl{tb, l_inst, l_info, l_blocks, l_flags, l_stage, l_seq, l_mot, l_vis, l_cnt, l_rec};
+  hmm_trace_rounds<HMM_REC, true>(sync, tid, nthr, tl, packed, rstride, cols_per_chunk, S, nb, L, seq, bp, g_vis, pbuf, pcap, gmask);
+  const int np = tb[TB_NPATH];
   HP_MARK(2);
-  // ---- state path: shift the reversed tail to the front (forward order)
-  if (pbuf) {
-    const int n = min(np, pcap), shift = pcap - n;
-    hmm_sync_mem(sync_n);  // (the path was written by thread 0)
-    for (int base = 0; base < n; base += nthr) {
-      const int f = base + tid;
-      uint16_t v = 0;
-      if (f < n) v = pbuf[shift + f];
-      hmm_sync_mem(sync_n);
-      if (f < n) pbuf[f] = v;
-      hmm_sync_mem(sync_n);
-    }
-  }
-  // ---- decode (thread 0): purity, label_motifs over the kept copies, skip filter, counts, collapse.  Visits were recorded back to
-  //      front: the last ones recorded (the first of the allele) sit in global memory and come through LDS in chunks.
-  int ns = 0, cum = 0, last_motif = -1, last_end = -1;
-  int32_t* const sp = spans3 + 3 * job.span_off;
-  auto take_visit = [&](const uint32_t* vrec) {
-    const int blk = (int)(vrec[0] & 0x7FFFu), b0 = (int)vrec[1], b1 = (int)vrec[2];
-    const bool keep = (vrec[0] >> 15) == 0;
-    const int cnt = b1 - b0;
-    const int start = cum, end = cum + cnt;
-    cum = end;
-    const int motif = keep ? blk : nb - 1;
-    if (motif < n_motifs) {
-      l_cnt[motif] += 1;
-      if (ns > 0 && last_motif == motif && last_end == start) { sp[3 * (ns - 1) + 2] = end; }
-      else { sp[3 * ns + 0] = motif; sp[3 * ns + 1] = start; sp[3 * ns + 2] = end; ++ns; last_motif = motif; }
-      last_end = end;
-    }
-  };
-  if (tid == 0) {
-    if (path_len) path_len[job.job_index] = (uint32_t)np;
-    const int edit = tb_edit, mx = max(tb_ref, qlen);
-    purity[job.job_index] = ((double)mx - (double)edit) / (double)mx;
-    if (edit_out) edit_out[job.job_index] = edit;
-    if (maxd_out) maxd_out[job.job_index] = mx;
-  }
-  int v = tb_nvisit - 1;
-  constexpr int VIS_CHUNK = HMM_STAGE_BYTES / 12;
-  uint32_t* const l_vchunk = reinterpret_cast<uint32_t*>(l_stage);  // (the staging window of the back-pointers is free now)
-  while (v >= HMM_VIS_LDS) {
-    const int n = min(v - HMM_VIS_LDS + 1, VIS_CHUNK), v0 = v - n + 1;
-    hmm_sync_mem(sync_n);  // (the visits were written by thread 0; the chunk before has been consumed)
-    for (int k = tid; k < 3 * n; k += nthr) l_vchunk[k] = g_vis[3 * (size_t)v0 + k];
-    hmm_sync(sync_n);
-    if (tid == 0) for (int k = n - 1; k >= 0; --k) take_visit(l_vchunk + 3 * k);
-    v -= n;
-  }
-  if (tid == 0) {
-    for (; v >= 0; --v) take_visit(l_vis + 3 * v);
-    n_spans[job.job_index] = (uint32_t)ns;
-  }
-  hmm_sync(sync_n);
-  for (int m = tid; m < n_motifs; m += nthr) counts[job.count_off + m] = l_cnt[m];
+  hmm_path_to_front(sync, tid, nthr, pbuf, np, pcap);
+  if (tid == 0) hmm_store_purity(job.job_index, np, tb[TB_EDIT], tb[TB_REF], qlen, path_len, purity, edit_out, maxd_out);
+  hmm_decode_visits(sync, tid, nthr, tl, nb, g_vis, spans3 + 3 * job.span_off, n_spans + job.job_index, counts + job.count_off);
   HP_MARK(3);
 }
 
@@ -1475,7 +1314,6 @@ __global__ void __launch_bounds__(HMM_LONG_THREADS) hmm_traceback_long_kernel(
     uint16_t* pbuf = path ? path + job.path_off : nullptr;
     const int pcap = (int)job.path_cap;
     auto code_at = [&](int i) -> int { return hmm_code(seq, i, L); };
-    const unsigned long long below = (1ull << lane) - 1ull;
     int edit_acc = 0, ref_acc = 0;
     for (int j = wave + NW * part; j < n_chunks; j += NW * G) {
       const HmmChunkRec cr = g_crec[j];
@@ -1502,49 +1340,12 @@ __global__ void __launch_bounds__(HMM_LONG_THREADS) hmm_traceback_long_kernel(
             loc = pe >> 16;
           }
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-          {  // ---- what the noted steps mean, one lane per step (events.rs:17-86, purity.rs:6-41, operations.rs:26-57)
-            const bool valid = lane < n;
-            const int st = valid ? (int)l_rec[2 * lane] : 0, ix = valid ? (int)l_rec[2 * lane + 1] : 0;
-            const uint32_t inf = valid ? l_info[st] : 0u;
-            const int kind = (int)(inf & 7u), blk = (int)((inf >> 8) & 0xFFu), expected = (int)((inf >> 16) & 0xFFu);
-            if (valid && pbuf && np_c + lane < pcap) pbuf[pcap - 1 - (np_c + lane)] = (uint16_t)st;
-            const int up = __shfl_up(st, 1);
-            const int nxt = lane == 0 ? nxt_c : up;
-            const int qbase = valid ? hmm_code_char(code_at(ix)) : 0;
-            const int dels = kind == 1 ? nxt - st - 1 : 0;
-            const int mism = kind == 4 && !(qbase == expected || expected == 'N');
-            int edit = valid ? dels + (kind == 3) + mism + (kind == 5) + (kind == 6) : 0;
-            int ref = valid ? dels + (kind == 3) + (kind == 4) + (kind == 6) : 0;
-            const unsigned long long ends = __ballot(valid && kind == 2), starts = __ballot(valid && kind == 1);
-            const unsigned long long ends_below = ends & below;
-            const int src_end = ends_below ? 63 - (int)__builtin_clzll(ends_below) : lane;
-            const int idx_end = __shfl(ix, src_end);
-            const int vb1 = ends_below ? idx_end : vb_c;
-            if (valid && kind == 1) {
-              uint32_t drop = 0;
-              const int mlen = (int)l_blocks[2 * nb + blk];
-              if (blk != nb - 1 && mlen <= 6) {
-                if (vb1 - ix < mlen) drop = 1;
-                else {
-                  const uint8_t* mot = l_mot + l_blocks[3 * nb + blk];
-                  for (int jj = 0; jj < mlen; ++jj) {
-                    const int obs = hmm_code_char(code_at(ix + jj + 1));
-                    if (mot[jj] != 'N' && obs != mot[jj]) drop = 1;
-                  }
-                }
-              }
-              const int nv = nv_c + (int)__builtin_popcountll(starts & below);
-              uint32_t* vrec = g_vis + 3 * (size_t)nv;
-              vrec[0] = (uint32_t)blk | (drop << 15); vrec[1] = (uint32_t)ix; vrec[2] = (uint32_t)vb1;
-            }
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) { edit += __shfl_xor(edit, o); ref += __shfl_xor(ref, o); }
-            const int src_last_end = ends ? 63 - (int)__builtin_clzll(ends) : lane;
-            const int idx_last_end = __shfl(ix, src_last_end);
-            const int last_state = __shfl(st, max(n - 1, 0));
-            np_c += n; nv_c += (int)__builtin_popcountll(starts); edit_acc += edit; ref_acc += ref;
-            if (n > 0) nxt_c = last_state;
-            if (ends) vb_c = idx_last_end;
+          {  // ---- what the noted steps mean, one lane per step; the visits always go to the job's workspace
+            const HmmStepSums r = hmm_decode_steps<64>(lane, n, HmmStepCarry{np_c, nv_c, nxt_c, vb_c}, ~0ull, l_rec, l_info, l_blocks, nb, l_mot, pbuf, pcap, code_at,
+                                                       [&](int nv) -> uint32_t* { return g_vis + 3 * (size_t)nv; });
+            np_c += n; nv_c += r.n_starts; edit_acc += r.edit; ref_acc += r.ref;
+            if (n > 0) nxt_c = r.last_state;
+            if (r.any_end) vb_c = r.idx_last_end;
           }
           __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         }
@@ -1574,25 +1375,8 @@ __global__ void __launch_bounds__(HMM_LONG_THREADS) hmm_traceback_long_kernel(
     int np = tot[2];
     if (tid == 0 && pbuf && np < pcap) pbuf[pcap - 1 - np] = 0;
     ++np;
-    if (pbuf) {
-      const int n = min(np, pcap), shift = pcap - n;
-      __syncthreads();
-      for (int base = 0; base < n; base += HMM_LONG_THREADS) {
-        const int f = base + tid;
-        uint16_t v = 0;
-        if (f < n) v = pbuf[shift + f];
-        __syncthreads();
-        if (f < n) pbuf[f] = v;
-        __syncthreads();
-      }
-    }
-    if (tid == 0) {
-      if (path_len) path_len[job.job_index] = (uint32_t)np;
-      const int edit = tot[0], mx = max(tot[1], qlen);
-      purity[job.job_index] = ((double)mx - (double)edit) / (double)mx;
-      if (edit_out) edit_out[job.job_index] = edit;
-      if (maxd_out) maxd_out[job.job_index] = mx;
-    }
+    hmm_path_to_front(HmmSyncBlock{}, tid, HMM_LONG_THREADS, pbuf, np, pcap);
+    if (tid == 0) hmm_store_purity(job.job_index, np, tot[0], tot[1], qlen, path_len, purity, edit_out, maxd_out);
     // label_motifs over the kept copies, skip filter, counts, collapse (hmm_model.rs:158-200, operations.rs:6-80, utils.rs:3-27), all threads:
     // the visits were recorded back to front, one lane takes one visit; base ranges by a prefix sum of the copy lengths, "the kept
     // visit before me" by a look-back (a span goes on when that one has my motif and ends where I start), span numbers by a prefix
@@ -1887,8 +1671,6 @@ static size_t hmm_long_lds_bytes(uint32_t S, uint32_t nb) {
 }
 static size_t hmm_lds_bytes(uint32_t S, uint32_t nb) {
   size_t o = 64 + (((size_t)HMM_LDS_PER_STATE * S + 15) & ~(size_t)15) + (((size_t)16 * nb + 15) & ~(size_t)15) + (size_t)hmm_stage_bytes((int)((S + 15) & ~15u));
-  const size_t spad = (S + 15) & ~15u;
-  (void)spad;
   o += HMM_CODE_WINDOW + HMM_CODE_PAD + (((size_t)S / 3 + 15) & ~(size_t)15) + 12 * (size_t)HMM_VIS_LDS + 4 * (size_t)nb;
   o += 8 + 8 * 64;  // the steps of a trace-back round (l_rec)
   return o + 64;
@@ -1965,6 +1747,137 @@ static int hmm_launch_ppl(trgt_hip_ctx* c, int bset, int class_slot, hipStream_t
 }
 static inline ppl::PplSegs hmm_ppl_one_segment(uint32_t nj, const uint32_t* n_jobs_dev) { ppl::PplSegs g{}; g.begin[1] = nj; g.n_seg = 1; g.counts = n_jobs_dev; for (int w = 0; w < 4; ++w) { g.first_slot[w] = 0; g.end_slot[w] = nj; } return g; }
 static inline unsigned hmm_ppl_bit(const HmmSetDev& sd) { const int g = ppl::lanes_for(sd.ppl_lanes); return g == 8 ? 1u : g == 16 ? 2u : g == 32 ? 4u : g == 64 ? 8u : 0u; }
+
+// ---- the launches of one class (jobs of one workgroup size), for a host-built job list (hmm_enqueue) and a device-resolved one
+//      (hmm_enqueue_slots) alike.
+// The buffers every kernel of a batch gets:
+struct HmmLaunchBufs {
+  const HmmSetDev* sets; const uint8_t* model; const uint8_t* seq; uint8_t* bp; uint32_t* visits;
+  uint16_t* path; uint32_t* plen; int32_t* spans; uint32_t* nsp; uint32_t* cnt; double* pur; int32_t* edit; int32_t* maxd;
+};
+struct HmmClassLaunch {
+  uint32_t cls;                // hmm_set_class of the class's sets (HMM_CLASS_BIG: hmm_viterbi_big_kernel)
+  int ordinal;                 // how many classes of this batch were launched before (0: on the batch's stream, else on a side stream)
+  int buffer_set;
+  const HmmJobDev* jobs;       // the class's jobs (device) ...
+  uint32_t nj;                 // ... how many there are (a device-resolved list: at most) ...
+  const uint32_t* n_jobs_dev;  // ... and, for a device-resolved list, where the device counted them (else null)
+  uint32_t maxS, maxnb;        // largest model of the class
+  uint64_t max_len;            // longest allele the class can have
+  unsigned ppl_mask;           // group widths of the class's position-per-lane fills (hmm_ppl_bit)
+  bool ppl_launched;           // those fills were launched in front, merged over all classes
+  size_t first_job, n_listed;  // where the class's jobs begin in the batch's list, and that list's length (S_HMM_LONG fallback, below)
+  int64_t cells;               // for the timer
+  unsigned* side_used;         // the batch's side streams in use so far (hmm_join_classes)
+  HmmLaunchBufs b;
+};
+constexpr size_t HMM_LONG_PIECE_PAD = 16;
+
+// The `lds_per_job` word of hmm_viterbi_kernel, as its first lines decode it:
+//   bits  0-22  LDS bytes of one job (a multiple of 16)
+//   bit   23    the position-per-lane fill wrote rows of one byte per lane (hmm_fill_ppl_kernel<G, true>), not one per state
+//   bits 24-29  columns from which an allele goes to hmm_traceback_long_kernel, / 256 (0: HMM_LONG_MIN)
+//   bit   30    the back-pointers of sets with ppl_lanes are there already (hmm_fill_ppl_kernel ran in front)
+//   bit   31    TRGT_HMM_FOUR_ROUNDS
+static uint32_t hmm_viterbi_flags(const trgt_hip_ctx* c, size_t lds_job, unsigned ppl_mask, uint32_t long_min) {
+  return (uint32_t)lds_job | (c->knobs.hmm_four_rounds ? 0x80000000u : 0u) | (ppl_mask ? 0x40000000u : 0u) | (ppl_mask && !c->knobs.hmm_ppl_wide ? 0x00800000u : 0u) | ((long_min / 256u) << 24);
+}
+// The four instantiations of hmm_viterbi_kernel: two alleles per wave or one, score columns in registers (one-wave classes) or in LDS
+struct HmmViterbiFn {
+  const void* fn;
+  void (*launch)(dim3 grid, dim3 block, size_t lds, hipStream_t ls, const HmmClassLaunch& a, uint32_t flags, uint32_t* d_long);
+};
+template <int SUB, bool ONE_WAVE>
+static void hmm_launch_viterbi(dim3 grid, dim3 block, size_t lds, hipStream_t ls, const HmmClassLaunch& a, uint32_t flags, uint32_t* d_long) {
+  hipLaunchKernelGGL((hmm_viterbi_kernel<SUB, ONE_WAVE>), grid, block, lds, ls, a.jobs, a.b.sets, a.b.model, a.b.seq, a.b.bp, a.b.visits, a.b.path, a.b.plen, a.b.spans,
+                     a.b.nsp, a.b.cnt, a.b.pur, a.b.edit, a.b.maxd, a.nj, flags, a.n_jobs_dev, d_long);
+}
+template <int SUB, bool ONE_WAVE>
+static HmmViterbiFn hmm_viterbi_fn() { return {(const void*)hmm_viterbi_kernel<SUB, ONE_WAVE>, hmm_launch_viterbi<SUB, ONE_WAVE>}; }
+
+// The classes of a batch run next to each other: the first on the batch's stream, the others on side streams forked off it (three per
+// buffer set, in rotation) and joined back into it.  A class is bounded by its longest allele: one behind the other they add up their tails.
+static int hmm_fork_record(trgt_hip_ctx* c, int buffer_set) {  // where the side streams fork off: in front of the first class's launch
+  hipEvent_t& ev = c->hmm_fork[buffer_set ? 1 : 0];
+  if (!ev) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  TRGT_HIP_TRY(c, hipEventRecord(ev, c->stream));
+  return TRGT_OK;
+}
+static int hmm_class_stream(trgt_hip_ctx* c, int buffer_set, int ordinal, unsigned& side_used, hipStream_t* ls) {
+  *ls = c->stream;
+  if (ordinal == 0) return TRGT_OK;
+  const int sidx = (ordinal - 1) % 3 + (buffer_set ? 3 : 0);
+  if (!c->hmm_side[sidx]) TRGT_HIP_TRY(c, trgt::make_side_stream(c, &c->hmm_side[sidx]));
+  if (!c->hmm_join[sidx]) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->hmm_join[sidx], hipEventDisableTiming));
+  *ls = c->hmm_side[sidx];
+  TRGT_HIP_TRY(c, hipStreamWaitEvent(*ls, c->hmm_fork[buffer_set ? 1 : 0], 0));
+  side_used |= 1u << sidx;
+  return TRGT_OK;
+}
+static int hmm_join_classes(trgt_hip_ctx* c, unsigned side_used) {
+  for (int sidx = 0; sidx < 6; ++sidx)
+    if (side_used & (1u << sidx)) {
+      TRGT_HIP_TRY(c, hipEventRecord(c->hmm_join[sidx], c->hmm_side[sidx]));
+      TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->hmm_join[sidx], 0));
+    }
+  return TRGT_OK;
+}
+
+static int hmm_launch_class(trgt_hip_ctx* c, const HmmClassLaunch& a) {
+  int rc;
+  const bool half = a.cls == 0;             // two alleles per wave
+  const bool big = a.cls == HMM_CLASS_BIG;  // (hmm_viterbi_big_kernel: no position-per-lane fill, its own trace-back for every length)
+  const size_t lds_job = big ? 0 : (hmm_lds_bytes(a.maxS, a.maxnb) + 15) & ~(size_t)15;
+  const size_t lds = half ? 2 * lds_job : lds_job;
+  if (lds > 160 * 1024) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: LDS need %zu B", lds);
+  const bool regs = !c->knobs.hmm_lds_fill;  // one-wave classes keep the score columns in registers (TRGT_HMM_LDS_FILL=1: in LDS like the others)
+  const HmmViterbiFn k = half ? (regs ? hmm_viterbi_fn<32, true>() : hmm_viterbi_fn<32, false>())
+                              : (regs && a.cls == 1 ? hmm_viterbi_fn<64, true>() : hmm_viterbi_fn<64, false>());
+  if (lds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipStream_t ls;
+  if ((rc = hmm_class_stream(c, a.buffer_set, a.ordinal, *a.side_used, &ls))) return rc;
+  KTimer t(c, TRGT_K_HMM, ls);
+  const HmmLaunchBufs& b = a.b;
+  if (big) {
+    if ((rc = hmm_launch_big(c, ls, a.maxS, a.maxnb, a.nj, a.jobs, b.sets, b.model, b.seq, b.bp, b.visits, b.path, b.plen, b.spans, b.nsp, b.cnt, b.pur, b.edit, b.maxd, a.n_jobs_dev))) return rc;
+    t.stop(a.cells);
+    return TRGT_OK;
+  }
+  // (the class's list of long alleles: filled by the fill kernel, worked off by the trace-back kernel right behind it)
+  uint32_t* d_long_cls = nullptr;
+  const uint32_t long_min_cls = hmm_long_min(a.nj);
+  if (!c->knobs.hmm_no_long_tb && a.max_len + 2 >= (uint64_t)long_min_cls) {
+    if (void* z = zero_take(c, ((size_t)a.nj + 16) * 4)) d_long_cls = (uint32_t*)z;  // [count | job indices] of this class, the count cleared
+    else {
+      // no zero arena: S_HMM_LONG, n_listed + HMM_LONG_PIECE_PAD * (HMM_CLASS_BIG + 1) words.  The class with `ordinal` classes in
+      // front of it, whose jobs are [first_job, first_job + nj) of the batch's list, has the nj + HMM_LONG_PIECE_PAD words from
+      // first_job + HMM_LONG_PIECE_PAD * ordinal on: the pieces follow each other without overlap, whatever the classes' sizes.
+      void* dl = nullptr;
+      const int so = a.buffer_set ? (int)S_HMM_B_BASE - (int)S_HMM_SEQ : 0;
+      if ((rc = dev_get(c, S_HMM_LONG + so, (a.n_listed + HMM_LONG_PIECE_PAD * (HMM_CLASS_BIG + 1)) * 4, &dl))) return rc;
+      d_long_cls = (uint32_t*)dl + a.first_job + HMM_LONG_PIECE_PAD * (size_t)a.ordinal;
+      TRGT_HIP_TRY(c, hipMemsetAsync(d_long_cls, 0, 4, ls));
+    }
+  }
+  if (a.ppl_mask && !a.ppl_launched &&
+      (rc = hmm_launch_ppl(c, a.buffer_set ? 1 : 0, a.ordinal & 3, ls, a.ppl_mask, a.jobs, b.sets, b.model, b.seq, b.bp, hmm_ppl_one_segment(a.nj, a.n_jobs_dev)))) return rc;
+  k.launch(dim3(half ? (a.nj + 1) / 2 : a.nj), dim3(half ? 64 : 64 * a.cls), lds, ls, a, hmm_viterbi_flags(c, lds_job, a.ppl_mask, long_min_cls), d_long_cls);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  if (d_long_cls) {
+    const size_t llds = hmm_long_lds_bytes(a.maxS, a.maxnb);
+    if (llds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)hmm_traceback_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds));
+    const int G = c->knobs.hmm_long_wgs;  // workgroups per long allele (1: one launch, the whole trace-back by one workgroup; else the phases 1 / 2 / 3)
+    for (int ph = G > 1 ? 1 : 0; ph <= (G > 1 ? 3 : 0); ++ph) {
+      const int g = ph == 1 || ph == 3 ? G : 1;
+      hipLaunchKernelGGL(hmm_traceback_long_kernel, dim3((unsigned)std::min<uint32_t>(a.nj, 64u) * (unsigned)g), dim3(HMM_LONG_THREADS), llds, ls, a.jobs, b.sets, b.model, b.seq,
+                         (const uint8_t*)b.bp, b.visits, b.path, b.plen, b.spans, b.nsp, b.cnt, b.pur, b.edit, b.maxd, (const uint32_t*)d_long_cls,
+                         ph | (a.ppl_mask && !c->knobs.hmm_ppl_wide ? 0x100 : 0), g);  // (bit 8: rows of one byte per lane, as bit 23 above)
+    }
+    TRGT_HIP_TRY(c, hipGetLastError());
+  }
+  t.stop(a.cells);
+  return TRGT_OK;
+}
 
 // All motif-set models of a batch (host side).  Thread-safe: touches no ctx state.
 int hmm_build_models(int32_t n_sets, const uint8_t* motif_blob, const uint32_t* motif_off, const uint32_t* set_motif_begin, HmmModels& out) {
@@ -2226,7 +2139,6 @@ int trgt::hmm_enqueue(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets,
     class_jobs[std::min<uint32_t>(set_class_of(sets[job_set[j]]), 31u)] += 1;
   }
   for (int64_t j = 0; j < n_jobs; ++j) {
-    if ((int32_t)job_set[j] >= n_sets) return fail(c, TRGT_ERR_INVALID, "trgt_hmm_batch: job %lld bad set", (long long)j);
     const HmmSetDev& sd = sets[job_set[j]];
     HmmJobDev& jd = jobs[(size_t)j];
     jd.set = job_set[j]; jd.seq_len = seq_len[j]; jd.job_index = (uint32_t)j;
@@ -2338,90 +2250,28 @@ int trgt::hmm_enqueue(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets,
   //      the classes run next to each other (a class is bounded by its longest allele: one behind the other they add up their tails)
   // the fork event sits behind the uploads and IN FRONT of the first launch: recorded behind it (as it was until the cfg3 trace showed
   // it), every other class waited for the first class to finish -- 17.6 + 15.2 ms instead of 17.6 for the 10-kb alleles of cfg3
-  if (!c->hmm_fork[buffer_set ? 1 : 0]) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->hmm_fork[buffer_set ? 1 : 0], hipEventDisableTiming));
-  TRGT_HIP_TRY(c, hipEventRecord(c->hmm_fork[buffer_set ? 1 : 0], c->stream));
-  size_t i = 0;
-  int n_class = 0;
+  if ((rc = hmm_fork_record(c, buffer_set))) return rc;
+  HmmClassLaunch cl{};
+  cl.buffer_set = buffer_set; cl.n_listed = jobs.size();
+  cl.b = HmmLaunchBufs{(const HmmSetDev*)d_sets, (const uint8_t*)d_model, d_seq, (uint8_t*)d_bp, (uint32_t*)d_visits,
+                       o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev};
   unsigned side_used = 0;
-  while (i < jobs.size()) {
-    const uint32_t jc = job_class(jobs[i]), cls = jc;
-    size_t e = i;
-    uint32_t maxS = 0, maxnb = 0, maxq = 0;
-    unsigned ppl_mask = 0;
-    while (e < jobs.size() && job_class(jobs[e]) == jc) {
-      maxS = std::max(maxS, sets[jobs[e].set].S); maxnb = std::max(maxnb, sets[jobs[e].set].n_blocks); maxq = std::max(maxq, jobs[e].seq_len);
-      ppl_mask |= hmm_ppl_bit(sets[jobs[e].set]); ++e;
+  cl.side_used = &side_used;
+  for (size_t i = 0, e; i < jobs.size(); i = e, ++cl.ordinal) {
+    cl.cls = job_class(jobs[i]);
+    uint32_t maxq = 0;
+    cl.maxS = cl.maxnb = 0; cl.ppl_mask = 0;
+    for (e = i; e < jobs.size() && job_class(jobs[e]) == cl.cls; ++e) {
+      const HmmSetDev& sd = sets[jobs[e].set];
+      cl.maxS = std::max(cl.maxS, sd.S); cl.maxnb = std::max(cl.maxnb, sd.n_blocks); maxq = std::max(maxq, jobs[e].seq_len);
+      cl.ppl_mask |= hmm_ppl_bit(sd);
     }
-    if (c->knobs.hmm_no_ppl) ppl_mask = 0;
-    const bool half = cls == 0;  // two alleles per wave
-    const bool big = cls == HMM_CLASS_BIG;  // (hmm_viterbi_big_kernel: no position-per-lane fill, its own trace-back for every length)
-    const size_t lds_job = big ? 0 : (hmm_lds_bytes(maxS, maxnb) + 15) & ~(size_t)15;
-    const size_t lds = half ? 2 * lds_job : lds_job;
-    if (lds > 160 * 1024) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: LDS need %zu B", lds);
-    const bool regs = !c->knobs.hmm_lds_fill;  // one-wave classes keep the score columns in registers (TRGT_HMM_LDS_FILL=1: in LDS like the others)
-    const void* kfn = half ? (regs ? (const void*)hmm_viterbi_kernel<32, true> : (const void*)hmm_viterbi_kernel<32, false>)
-                           : (regs && cls == 1 ? (const void*)hmm_viterbi_kernel<64, true> : (const void*)hmm_viterbi_kernel<64, false>);
-    if (lds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipStream_t ls = c->stream;
-    if (n_class > 0) {
-      const int sidx = (n_class - 1) % 3 + (buffer_set ? 3 : 0);
-      if (!c->hmm_side[sidx]) TRGT_HIP_TRY(c, trgt::make_side_stream(c, &c->hmm_side[sidx]));
-      if (!c->hmm_join[sidx]) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->hmm_join[sidx], hipEventDisableTiming));
-      ls = c->hmm_side[sidx];
-      TRGT_HIP_TRY(c, hipStreamWaitEvent(ls, c->hmm_fork[buffer_set ? 1 : 0], 0));
-      side_used |= 1u << sidx;
-    }
-    ++n_class;
-    KTimer t(c, TRGT_K_HMM, ls);
-    const uint32_t nj = (uint32_t)(e - i);
-    if (big) {
-      if ((rc = hmm_launch_big(c, ls, maxS, maxnb, nj, (const HmmJobDev*)d_jobs + i, (const HmmSetDev*)d_sets, (const uint8_t*)d_model, d_seq, (uint8_t*)d_bp, (uint32_t*)d_visits,
-                               o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev, nullptr))) return rc;
-      t.stop(i == 0 ? cells : 0);
-      i = e;
-      continue;
-    }
-    const dim3 grid(half ? (nj + 1) / 2 : nj), block(half ? 64 : 64 * cls);
-#define TRGT_HMM_LAUNCH(SB, OW)                                                                                                    \
-    hipLaunchKernelGGL((hmm_viterbi_kernel<SB, OW>), grid, block, lds, ls, (const HmmJobDev*)d_jobs + i, (const HmmSetDev*)d_sets,   \
-                       (const uint8_t*)d_model, d_seq, (uint8_t*)d_bp, (uint32_t*)d_visits, o_path.dev, o_plen.dev, o_spans.dev, \
-                       o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev, nj, (uint32_t)lds_job | (c->knobs.hmm_four_rounds ? 0x80000000u : 0u) | (ppl_mask ? 0x40000000u : 0u) | (ppl_mask && !c->knobs.hmm_ppl_wide ? 0x00800000u : 0u) | ((long_min_cls / 256u) << 24), (const uint32_t*)nullptr, d_long_cls)
-    // (the class's list of long alleles: filled by the fill kernel, worked off by the trace-back kernel right behind it)
-    uint32_t* d_long_cls = nullptr;
-    const uint32_t long_min_cls = hmm_long_min(e - i);
-    if (!c->knobs.hmm_no_long_tb && (uint64_t)maxq + 2 >= (uint64_t)long_min_cls) {
-      if (void* z = zero_take(c, ((size_t)nj + 16) * 4)) d_long_cls = (uint32_t*)z;  // [count | job indices] of this class, the count cleared
-      else {
-        void* dl = nullptr;
-        if ((rc = dev_get(c, S_HMM_LONG + so, 8 * ((size_t)jobs.size() + 16) * 4, &dl))) return rc;
-        d_long_cls = (uint32_t*)dl + (size_t)n_class * 0 + (i + 8 * (size_t)(n_class - 1));
-        TRGT_HIP_TRY(c, hipMemsetAsync(d_long_cls, 0, 4, ls));
-      }
-    }
-    if (ppl_mask && (rc = hmm_launch_ppl(c, buffer_set ? 1 : 0, (n_class - 1) & 3, ls, ppl_mask, (const HmmJobDev*)d_jobs + i, (const HmmSetDev*)d_sets, (const uint8_t*)d_model, d_seq, (uint8_t*)d_bp, hmm_ppl_one_segment(nj, nullptr)))) return rc;
-    if (half) { if (regs) TRGT_HMM_LAUNCH(32, true); else TRGT_HMM_LAUNCH(32, false); }
-    else if (regs && cls == 1) TRGT_HMM_LAUNCH(64, true);
-    else TRGT_HMM_LAUNCH(64, false);
-#undef TRGT_HMM_LAUNCH
-    TRGT_HIP_TRY(c, hipGetLastError());
-    if (d_long_cls) {
-      const size_t llds = hmm_long_lds_bytes(maxS, maxnb);
-      if (llds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)hmm_traceback_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds));
-      const int G = c->knobs.hmm_long_wgs;  // workgroups per long allele (1: one launch, the whole trace-back by one workgroup)
-      for (int ph = G > 1 ? 1 : 0; ph <= (G > 1 ? 3 : 0); ++ph)
-        hipLaunchKernelGGL(hmm_traceback_long_kernel, dim3((unsigned)std::min<uint32_t>(nj, 64u) * (unsigned)(ph == 1 || ph == 3 ? G : 1)), dim3(HMM_LONG_THREADS), llds, ls, (const HmmJobDev*)d_jobs + i, (const HmmSetDev*)d_sets,
-                           (const uint8_t*)d_model, d_seq, (const uint8_t*)d_bp, (uint32_t*)d_visits, o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev,
-                           o_edit.dev, o_maxd.dev, (const uint32_t*)d_long_cls, ph | (ppl_mask && !c->knobs.hmm_ppl_wide ? 0x100 : 0), ph == 1 || ph == 3 ? G : 1);
-      TRGT_HIP_TRY(c, hipGetLastError());
-    }
-    t.stop(i == 0 ? cells : 0);
-    i = e;
+    if (c->knobs.hmm_no_ppl) cl.ppl_mask = 0;
+    cl.jobs = (const HmmJobDev*)d_jobs + i; cl.nj = (uint32_t)(e - i); cl.first_job = i; cl.max_len = maxq;
+    cl.cells = i == 0 ? cells : 0;
+    if ((rc = hmm_launch_class(c, cl))) return rc;
   }
-  for (int sidx = 0; sidx < 6; ++sidx)
-    if (side_used & (1u << sidx)) {
-      TRGT_HIP_TRY(c, hipEventRecord(c->hmm_join[sidx], c->hmm_side[sidx]));
-      TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->hmm_join[sidx], 0));
-    }
+  if ((rc = hmm_join_classes(c, side_used))) return rc;
   if (P->spans_on_host && (rc = pack_behind_kernels(c, P.get(), d_pack_tabs, n_jobs, d_bp, bp_total, o_spans.dev, o_nsp.dev, so))) return rc;
   *out_pending = P.release();
   return TRGT_OK;
@@ -2590,83 +2440,28 @@ int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots
     TRGT_HIP_TRY(c, hipGetLastError());
     tf.stop(0);
   }
-  if (!c->hmm_fork[buffer_set ? 1 : 0]) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->hmm_fork[buffer_set ? 1 : 0], hipEventDisableTiming));
-  TRGT_HIP_TRY(c, hipEventRecord(c->hmm_fork[buffer_set ? 1 : 0], c->stream));  // (behind the resolve kernel and the merged fills, in front of the first class launch)
-  int n_class = 0;
+  if ((rc = hmm_fork_record(c, buffer_set))) return rc;  // (behind the resolve kernel and the merged fills, in front of the first class launch)
+  HmmClassLaunch cl{};
+  cl.buffer_set = buffer_set; cl.n_listed = n_cand; cl.ppl_launched = ppl_merged;
+  cl.b = HmmLaunchBufs{(const HmmSetDev*)mp->d_sets, (const uint8_t*)mp->d_blob, in.seq_blob_dev, (uint8_t*)d_bp, (uint32_t*)d_visits,
+                       o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev};
   unsigned side_used = 0;
+  cl.side_used = &side_used;
   for (uint32_t k = 0; k < (uint32_t)NC; ++k) {
     if (!class_n[k]) continue;
-    uint32_t maxS = 0, maxnb = 0;
-    for (uint32_t i = class_begin[k]; i < class_begin[k + 1]; i += 2) { const HmmSetDev& sd = sets[cand[i].set]; maxS = std::max(maxS, sd.S); maxnb = std::max(maxnb, sd.n_blocks); }
-    const bool big = k == (uint32_t)BIG;
-    const unsigned ppl_mask = big ? 0u : class_ppl_mask[k];
-    const bool half = k == 0;
-    const size_t lds_job = big ? 0 : (hmm_lds_bytes(maxS, maxnb) + 15) & ~(size_t)15;
-    const size_t lds = half ? 2 * lds_job : lds_job;
-    if (lds > 160 * 1024) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: LDS need %zu B", lds);
-    const bool regs = !c->knobs.hmm_lds_fill;  // one-wave classes keep the score columns in registers (TRGT_HMM_LDS_FILL=1: in LDS like the others)
-    const void* kfn = half ? (regs ? (const void*)hmm_viterbi_kernel<32, true> : (const void*)hmm_viterbi_kernel<32, false>)
-                           : (regs && k == 1 ? (const void*)hmm_viterbi_kernel<64, true> : (const void*)hmm_viterbi_kernel<64, false>);
-    if (lds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipStream_t ls = c->stream;
-    if (n_class > 0) {
-      const int sidx = (n_class - 1) % 3 + (buffer_set ? 3 : 0);
-      if (!c->hmm_side[sidx]) TRGT_HIP_TRY(c, trgt::make_side_stream(c, &c->hmm_side[sidx]));
-      if (!c->hmm_join[sidx]) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->hmm_join[sidx], hipEventDisableTiming));
-      ls = c->hmm_side[sidx];
-      TRGT_HIP_TRY(c, hipStreamWaitEvent(ls, c->hmm_fork[buffer_set ? 1 : 0], 0));
-      side_used |= 1u << sidx;
-    }
-    ++n_class;
-    KTimer t(c, TRGT_K_HMM, ls);
-    const uint32_t nj = class_n[k];
-    if (big) {
-      if ((rc = hmm_launch_big(c, ls, maxS, maxnb, nj, (const HmmJobDev*)d_list + class_begin[k], (const HmmSetDev*)mp->d_sets, (const uint8_t*)mp->d_blob, in.seq_blob_dev, (uint8_t*)d_bp,
-                               (uint32_t*)d_visits, o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev, (const uint32_t*)(d_count + k)))) return rc;
-      t.stop(0);
-      continue;
-    }
-    const dim3 grid(half ? (nj + 1) / 2 : nj), block(half ? 64 : 64 * k);
-#define TRGT_HMM_LAUNCH(SB, OW)                                                                                                    \
-    hipLaunchKernelGGL((hmm_viterbi_kernel<SB, OW>), grid, block, lds, ls, (const HmmJobDev*)d_list + class_begin[k], (const HmmSetDev*)mp->d_sets, \
-                       (const uint8_t*)mp->d_blob, in.seq_blob_dev, (uint8_t*)d_bp, (uint32_t*)d_visits, o_path.dev, o_plen.dev, o_spans.dev, \
-                       o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev, nj, (uint32_t)lds_job | (c->knobs.hmm_four_rounds ? 0x80000000u : 0u) | (ppl_mask ? 0x40000000u : 0u) | (ppl_mask && !c->knobs.hmm_ppl_wide ? 0x00800000u : 0u) | ((long_min_cls / 256u) << 24), (const uint32_t*)(d_count + k), d_long_cls)
-    uint32_t* d_long_cls = nullptr;
     uint32_t max_cap_cls = 0;
-    for (uint32_t i = class_begin[k]; i < class_begin[k + 1]; i += 2) max_cap_cls = std::max(max_cap_cls, in.cap[cand[i].set]);
-    const uint32_t long_min_cls = hmm_long_min(class_n[k]);
-    if (!c->knobs.hmm_no_long_tb && (uint64_t)max_cap_cls + 2 >= (uint64_t)long_min_cls) {
-      if (void* z = zero_take(c, ((size_t)nj + 16) * 4)) d_long_cls = (uint32_t*)z;  // [count | job indices] of this class, the count cleared
-      else {
-        void* dl = nullptr;
-        if ((rc = dev_get(c, S_HMM_LONG + so, ((size_t)n_cand + 8 * 16) * 4, &dl))) return rc;
-        d_long_cls = (uint32_t*)dl + class_begin[k] + 8 * k;
-        TRGT_HIP_TRY(c, hipMemsetAsync(d_long_cls, 0, 4, ls));
-      }
+    cl.maxS = cl.maxnb = 0;
+    for (uint32_t i = class_begin[k]; i < class_begin[k + 1]; i += 2) {
+      const HmmSetDev& sd = sets[cand[i].set];
+      cl.maxS = std::max(cl.maxS, sd.S); cl.maxnb = std::max(cl.maxnb, sd.n_blocks); max_cap_cls = std::max(max_cap_cls, in.cap[cand[i].set]);
     }
-    if (ppl_mask && !ppl_merged && (rc = hmm_launch_ppl(c, buffer_set ? 1 : 0, (n_class - 1) & 3, ls, ppl_mask, (const HmmJobDev*)d_list + class_begin[k], (const HmmSetDev*)mp->d_sets, (const uint8_t*)mp->d_blob, in.seq_blob_dev, (uint8_t*)d_bp, hmm_ppl_one_segment(nj, (const uint32_t*)(d_count + k))))) return rc;
-    if (half) { if (regs) TRGT_HMM_LAUNCH(32, true); else TRGT_HMM_LAUNCH(32, false); }
-    else if (regs && k == 1) TRGT_HMM_LAUNCH(64, true);
-    else TRGT_HMM_LAUNCH(64, false);
-#undef TRGT_HMM_LAUNCH
-    TRGT_HIP_TRY(c, hipGetLastError());
-    if (d_long_cls) {
-      const size_t llds = hmm_long_lds_bytes(maxS, maxnb);
-      if (llds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)hmm_traceback_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds));
-      const int G = c->knobs.hmm_long_wgs;
-      for (int ph = G > 1 ? 1 : 0; ph <= (G > 1 ? 3 : 0); ++ph)
-        hipLaunchKernelGGL(hmm_traceback_long_kernel, dim3((unsigned)std::min<uint32_t>(nj, 64u) * (unsigned)(ph == 1 || ph == 3 ? G : 1)), dim3(HMM_LONG_THREADS), llds, ls, (const HmmJobDev*)d_list + class_begin[k], (const HmmSetDev*)mp->d_sets,
-                           (const uint8_t*)mp->d_blob, in.seq_blob_dev, (const uint8_t*)d_bp, (uint32_t*)d_visits, o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev,
-                           o_edit.dev, o_maxd.dev, (const uint32_t*)d_long_cls, ph | (ppl_mask && !c->knobs.hmm_ppl_wide ? 0x100 : 0), ph == 1 || ph == 3 ? G : 1);
-      TRGT_HIP_TRY(c, hipGetLastError());
-    }
-    t.stop(0);
+    cl.cls = k == (uint32_t)BIG ? HMM_CLASS_BIG : k;
+    cl.ppl_mask = k < (uint32_t)HMM_PPL_CLASSES ? class_ppl_mask[k] : 0u;
+    cl.jobs = (const HmmJobDev*)d_list + class_begin[k]; cl.nj = class_n[k]; cl.n_jobs_dev = d_count + k; cl.first_job = class_begin[k]; cl.max_len = max_cap_cls;
+    if ((rc = hmm_launch_class(c, cl))) return rc;  // (cells: counted when the genotyper's results are known, hmm_slots_resolved)
+    ++cl.ordinal;
   }
-  for (int sidx = 0; sidx < 6; ++sidx)
-    if (side_used & (1u << sidx)) {
-      TRGT_HIP_TRY(c, hipEventRecord(c->hmm_join[sidx], c->hmm_side[sidx]));
-      TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->hmm_join[sidx], 0));
-    }
+  if ((rc = hmm_join_classes(c, side_used))) return rc;
   if (d_dup) {  // homozygous loci: the second allele's results are the first one's
     hipLaunchKernelGGL(hmm_dup_copy_kernel, dim3((unsigned)((n_cand + 255) / 256)), dim3(256), 0, c->stream, (const HmmJobDev*)d_cand, (uint32_t)n_cand, d_dup, (const HmmSetDev*)mp->d_sets,
                        o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev);

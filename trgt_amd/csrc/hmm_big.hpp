@@ -13,7 +13,7 @@
 // passes chains | run end + run start | block starts (any topological order gives the same values, hmm_model.rs:206-240).
 //
 // Trace-back: the serial chase of hmm_viterbi_kernel (thread 0 follows the back-pointers through LDS-staged columns, the lanes of the
-// first wave decode the noted steps) for alleles of ANY length.  The chunk-map kernel (hmm_traceback_long_kernel) walks every chunk
+// first wave decode the noted steps) for alleles of ANY length -- shared code, not a copy: hmm_traceback.hpp, with this kernel's barriers.  The chunk-map kernel (hmm_traceback_long_kernel) walks every chunk
 // from every entry state, S * columns step-lanes and 12 S bytes of map per chunk, and its LDS plan (21 B per state + staging + maps)
 // does not fit 4 096 states; the serial chase is exact and its measured share of such a job is in DESIGN.md 5.
 // The predecessor entries of the chase (16 B per state) take the place of the score columns once the fill is through.
@@ -76,8 +76,7 @@ __global__ void __launch_bounds__(HMM_BIG_THREADS) hmm_viterbi_big_kernel(
   }
   const HmmBigLds lay = hmm_big_lds((uint32_t)S, (uint32_t)nb);
   int* tb = reinterpret_cast<int*>(lds_big);
-  int &tb_state = tb[0], &tb_idx = tb[1], &tb_done = tb[2], &tb_npath = tb[3], &tb_nvisit = tb[4], &tb_edit = tb[5],
-      &tb_ref = tb[6], &tb_next = tb[7], &tb_vb1 = tb[8], &tb_nrec = tb[9], &tb_more = tb[10], &l_bp_rs = tb[12];
+  int& l_bp_rs = tb[12];  // (behind the words TB_* of the trace-back)
   double* sc0 = reinterpret_cast<double*>(lds_big + lay.sc);
   double* sc1 = sc0 + S;
   uint32_t* l_inst = reinterpret_cast<uint32_t*>(lds_big + lay.sc);  // (behind the fill)
@@ -169,7 +168,7 @@ __global__ void __launch_bounds__(HMM_BIG_THREADS) hmm_viterbi_big_kernel(
   uint8_t* __restrict__ bp = bp_ws + job.bp_off;
   int win0 = 0;
   auto code_at = [&](int i) -> int { return (int)l_seq[i - win0]; };
-  auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };  // (not vmcnt: the back-pointer stores are read again behind a full barrier only)
+  const HmmSyncBlock sync;  // (sync.lds(): not vmcnt -- the back-pointer stores are read again behind a full barrier only)
   __syncthreads();
   HP_MARK(0);
 
@@ -181,10 +180,10 @@ __global__ void __launch_bounds__(HMM_BIG_THREADS) hmm_viterbi_big_kernel(
     uint8_t* __restrict__ bp_col = bp;
     for (int i = 0; i < L; ++i) {
       if ((i % HMM_CODE_WINDOW) == 0) {  // next window of symbol codes (one column more than the window: the look-ahead below)
-        lds_barrier();
+        sync.lds();
         win0 = i;
         for (int k = tid; k < HMM_CODE_WINDOW + 1 && i + k < L; k += nthr) l_seq[k] = (uint8_t)hmm_code(seq, i + k, L);
-        lds_barrier();
+        sync.lds();
         const int sym = code_at(i);
 #pragma unroll
         for (int j = 0; j < K; ++j) em_next[j] = t_emit[j] ? g_em[(size_t)sym * S + t_st[j]] : NINF;
@@ -217,7 +216,7 @@ __global__ void __launch_bounds__(HMM_BIG_THREADS) hmm_viterbi_big_kernel(
           cur[t_st[j]] = best[j];
         }
       }
-      lds_barrier();
+      sync.lds();
       // -- the chains d0 <- d1 <- ... <- block end of all motif blocks: what the other predecessors give, then the walk across the
       //    lanes of a wave (see hmm_viterbi_kernel).  Round r makes the states r waves behind the first lane of their chain final;
       //    a wave runs the rounds in which some lane of it becomes final (a state that is final already is recomputed from the
@@ -260,9 +259,9 @@ __global__ void __launch_bounds__(HMM_BIG_THREADS) hmm_viterbi_big_kernel(
           if (t_chain[j]) cur[t_st[j]] = val;
           best[j] = val; bpi[j] = bb;
         }
-        if (r + 1 < chain_rounds) lds_barrier();
+        if (r + 1 < chain_rounds) sync.lds();
       }
-      lds_barrier();
+      sync.lds();
       // -- run end: the block ends in block order; then the run start {start state, run end}
 #pragma unroll
       for (int j = 0; j < K; ++j) {
@@ -281,7 +280,7 @@ __global__ void __launch_bounds__(HMM_BIG_THREADS) hmm_viterbi_big_kernel(
           cur[1] = br; l_bp_rs = pr;
         }
       }
-      lds_barrier();
+      sync.lds();
       // -- block starts: {run start, own block end}
 #pragma unroll
       for (int j = 0; j < K; ++j) {
@@ -294,7 +293,7 @@ __global__ void __launch_bounds__(HMM_BIG_THREADS) hmm_viterbi_big_kernel(
           cur[t_st[j]] = best[j];
         }
       }
-      lds_barrier();
+      sync.lds();
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         if (t_act[j]) {
@@ -310,171 +309,20 @@ __global__ void __launch_bounds__(HMM_BIG_THREADS) hmm_viterbi_big_kernel(
   HP_MARK(1);
   // (bit 15 of a predecessor entry: that state emits a base -- the trace-back then knows it on arrival, without a look-up of its own)
   for (int i = tid; i < 4 * S; i += nthr) l_inst[4 * (i % S) + i / S] = hmm_pred_entry(g_inst[i], S, nb, g_flags, g_block, g_blocks);
-  if (tid == 0) {
-    tb_state = S - 1; tb_idx = L - 1; tb_done = 0; tb_npath = 0; tb_nvisit = 0; tb_edit = 0; tb_ref = 0; tb_next = -1; tb_vb1 = 0;
-  }
+  if (tid == 0) hmm_trace_init(tb, S, L);
   __syncthreads();
 
-  // ---- traceback (hmm_model.rs:125-142) fused with get_events/calc_purity (events.rs:17-86, purity.rs:6-41) and motif-visit
-  //      collection (operations.rs:26-40): the round loop of hmm_viterbi_kernel (rows of one byte per state), thread 0 chases,
-  //      the lanes of wave 0 decode HMM_REC noted steps at a time
-  const int rstride = Spad;
-  const int cols_per_chunk = HMM_BIG_STAGE_COLS;
+  // ---- traceback: the serial chase of hmm_viterbi_kernel (hmm_traceback.hpp) over rows of one byte per state, thread 0 chases, the
+  //      lanes of wave 0 decode 64 noted steps at a time
   uint16_t* pbuf = path ? path + job.path_off : nullptr;
   uint32_t* const g_vis = visit_ws + job.visit_off;  // visits HMM_VIS_LDS, HMM_VIS_LDS + 1, ... at their own index
   const int pcap = (int)job.path_cap;
-  constexpr int HMM_REC = 64;
-  const int hwlane = tid & 63;
-  const unsigned long long below = (1ull << hwlane) - 1ull;
-  while (true) {
-    if (tb_done) break;
-    const int c1 = tb_idx + 1, c0 = max(0, c1 - cols_per_chunk);
-    {
-      const uint4* src = reinterpret_cast<const uint4*>(bp + (size_t)c0 * rstride);
-      uint4* dst = reinterpret_cast<uint4*>(l_stage);
-      const int n16 = ((c1 - c0) * rstride + 15) / 16;
-      for (int i = tid; i < n16; i += nthr) dst[i] = src[i];
-      // ... and the symbol codes of the same columns, plus those a motif copy starting in the last of them reaches into
-      win0 = c0;
-      for (int k = tid; k < c1 - c0 + HMM_CODE_PAD && c0 + k < L; k += nthr) l_seq[k] = (uint8_t)hmm_code(seq, c0 + k, L);
-    }
-    lds_barrier();
-    for (;;) {
-      if (tid == 0) {  // ---- the chase
-        int state = tb_state, idx = tb_idx, n = 0;
-        int row = (idx - c0) * rstride;  // offset of column idx in the staged chunk
-        int emits = (int)((l_info[state] >> 3) & 1u);
-        while (state != 0 && idx >= c0 && n < HMM_REC) {
-          l_rec[2 * n] = (uint32_t)state; l_rec[2 * n + 1] = (uint32_t)idx; ++n;
-          const uint4 pred4 = *reinterpret_cast<const uint4*>(l_inst + 4 * state);  // all four predecessors: no second round trip behind b
-          const int b = l_stage[row + state];
-          uint32_t pe = (b & 2) ? ((b & 1) ? pred4.w : pred4.z) : ((b & 1) ? pred4.y : pred4.x);  // predecessor | its "emits" bit << 15
-          if (state == S - 2) { const uint32_t be_ = l_blocks[1 * nb + (b < nb ? b : 0)]; pe = be_ | ((uint32_t)(l_flags[be_] & 1) << 15); }  // the run end: from a block end
-          if (emits) { --idx; row -= rstride; }
-          emits = (int)((pe >> 15) & 1u);
-          state = (int)(pe & 0x7FFFu);
-        }
-        tb_state = state; tb_idx = idx; tb_nrec = n;
-        tb_more = state == 0 ? 2 : (idx >= c0 ? 1 : 0);
-      }
-      lds_barrier();
-      const int more = tb_more;  // (read before the next barrier: thread 0 writes it again right behind that one)
-      if (tid < HMM_REC) {  // ---- what the noted steps mean (events.rs:17-86, purity.rs:6-41, operations.rs:26-57), one lane per step
-        const int n = tb_nrec, np0 = tb_npath, nv0 = tb_nvisit, nxt0 = tb_next, vb0 = tb_vb1;
-        const bool valid = tid < n;
-        const int state = valid ? (int)l_rec[2 * tid] : 0, idx = valid ? (int)l_rec[2 * tid + 1] : 0;
-        const uint32_t inf = valid ? l_info[state] : 0u;
-        const int kind = (int)(inf & 7u), blk = (int)((inf >> 8) & 0xFFu), expected = (int)((inf >> 16) & 0xFFu);
-        if (valid && pbuf && np0 + tid < pcap) pbuf[pcap - 1 - (np0 + tid)] = (uint16_t)state;
-        // the state walked just before this one (the step before: the lane before)
-        const int up = __shfl_up(state, 1);
-        const int nxt = tid == 0 ? nxt0 : up;
-        // MotifStart (1) adds the implied leading deletions, Skip (3) / Mismatch / Ins (5) / Del (6) are edits, Skip / Match-state /
-        // Del consume a reference base
-        const int qbase = valid ? hmm_code_char(code_at(idx)) : 0;
-        const int dels = kind == 1 ? nxt - state - 1 : 0;
-        const int mism = kind == 4 && !(qbase == expected || expected == 'N');  // events.rs:66-73
-        int edit = valid ? dels + (kind == 3) + mism + (kind == 5) + (kind == 6) : 0;
-        int ref = valid ? dels + (kind == 3) + (kind == 4) + (kind == 6) : 0;
-        // the last block end (2) walked before this step: the bases of the visit a block start (1) closes are query[idx .. vb1)
-        const unsigned long long ends = __ballot(valid && kind == 2), starts = __ballot(valid && kind == 1);
-        const unsigned long long ends_below = ends & below;
-        const int src_end = ends_below ? 63 - (int)__builtin_clzll(ends_below) : hwlane;
-        const int idx_end = __shfl(idx, src_end);
-        const int vb1 = ends_below ? idx_end : vb0;
-        if (valid && kind == 1) {  // a motif visit
-          // remove_imperfect_motifs(.., 6) (operations.rs:45-57): only copies of STR motifs can be dropped -- short ones, and ones
-          // whose bases differ from the motif (its bases are columns idx + 1 .. idx + mlen: in the window)
-          uint32_t drop = 0;
-          const int mlen = (int)l_blocks[2 * nb + blk];
-          if (blk != nb - 1 && mlen <= 6) {
-            if (vb1 - idx < mlen) drop = 1;
-            else {
-              const uint8_t* mot = l_mot + l_blocks[3 * nb + blk];
-              for (int jj = 0; jj < mlen; ++jj) {
-                const int obs = hmm_code_char(code_at(idx + jj + 1));
-                if (mot[jj] != 'N' && obs != mot[jj]) drop = 1;
-              }
-            }
-          }
-          const int nv = nv0 + (int)__builtin_popcountll(starts & below);
-          uint32_t* vrec = nv < HMM_VIS_LDS ? l_vis + 3 * nv : g_vis + 3 * (size_t)nv;
-          vrec[0] = (uint32_t)blk | (drop << 15); vrec[1] = (uint32_t)idx; vrec[2] = (uint32_t)vb1;
-        }
-        // sums over the round (butterfly inside the wave)
-#pragma unroll
-        for (int o = HMM_REC / 2; o >= 1; o >>= 1) { edit += __shfl_xor(edit, o); ref += __shfl_xor(ref, o); }
-        const int src_last_end = ends ? 63 - (int)__builtin_clzll(ends) : hwlane;
-        const int idx_last_end = __shfl(idx, src_last_end);
-        const int last_state = __shfl(state, max(n - 1, 0));
-        if (tid == 0) {
-          int np = np0 + n;
-          if (more == 2) { if (pbuf && np < pcap) pbuf[pcap - 1 - np] = 0; ++np; tb_done = 1; }
-          tb_npath = np; tb_nvisit = nv0 + (int)__builtin_popcountll(starts); tb_edit += edit; tb_ref += ref;
-          if (n > 0) tb_next = last_state;
-          if (ends) tb_vb1 = idx_last_end;
-        }
-      }
-      lds_barrier();
-      if (more != 1) break;
-    }
-  }
-  const int np = tb_npath;
+  const HmmTraceLds tl{tb, l_inst, l_info, l_blocks, l_flags, l_stage, l_seq, l_mot, l_vis, l_cnt, l_rec};
+  hmm_trace_rounds<64, false>(sync, tid, nthr, tl, false, Spad, HMM_BIG_STAGE_COLS, S, nb, L, seq, bp, g_vis, pbuf, pcap, ~0ull);
+  const int np = tb[TB_NPATH];
   HP_MARK(2);
-  // ---- state path: shift the reversed tail to the front (forward order)
-  if (pbuf) {
-    const int n = min(np, pcap), shift = pcap - n;
-    __syncthreads();  // (the path was written by wave 0)
-    for (int base = 0; base < n; base += nthr) {
-      const int f = base + tid;
-      uint16_t v = 0;
-      if (f < n) v = pbuf[shift + f];
-      __syncthreads();
-      if (f < n) pbuf[f] = v;
-      __syncthreads();
-    }
-  }
-  // ---- decode (thread 0): purity, label_motifs over the kept copies, skip filter, counts, collapse.  Visits were recorded back to
-  //      front: the last ones recorded (the first of the allele) sit in global memory and come through LDS in chunks.
-  int ns = 0, cum = 0, last_motif = -1, last_end = -1;
-  int32_t* const sp = spans3 + 3 * job.span_off;
-  auto take_visit = [&](const uint32_t* vrec) {
-    const int blk = (int)(vrec[0] & 0x7FFFu), b0 = (int)vrec[1], b1 = (int)vrec[2];
-    const bool keep = (vrec[0] >> 15) == 0;
-    const int cnt = b1 - b0;
-    const int start = cum, end = cum + cnt;
-    cum = end;
-    const int motif = keep ? blk : nb - 1;
-    if (motif < n_motifs) {
-      l_cnt[motif] += 1;
-      if (ns > 0 && last_motif == motif && last_end == start) { sp[3 * (ns - 1) + 2] = end; }
-      else { sp[3 * ns + 0] = motif; sp[3 * ns + 1] = start; sp[3 * ns + 2] = end; ++ns; last_motif = motif; }
-      last_end = end;
-    }
-  };
-  if (tid == 0) {
-    if (path_len) path_len[job.job_index] = (uint32_t)np;
-    const int edit = tb_edit, mx = max(tb_ref, qlen);
-    purity[job.job_index] = ((double)mx - (double)edit) / (double)mx;
-    if (edit_out) edit_out[job.job_index] = edit;
-    if (maxd_out) maxd_out[job.job_index] = mx;
-  }
-  int v = tb_nvisit - 1;
-  constexpr int VIS_CHUNK = HMM_STAGE_BYTES / 12;
-  uint32_t* const l_vchunk = reinterpret_cast<uint32_t*>(l_stage);  // (the staging window of the back-pointers is free now)
-  while (v >= HMM_VIS_LDS) {
-    const int n = min(v - HMM_VIS_LDS + 1, VIS_CHUNK), v0 = v - n + 1;
-    __syncthreads();  // (the visits were written by wave 0; the chunk before has been consumed)
-    for (int k = tid; k < 3 * n; k += nthr) l_vchunk[k] = g_vis[3 * (size_t)v0 + k];
-    lds_barrier();
-    if (tid == 0) for (int k = n - 1; k >= 0; --k) take_visit(l_vchunk + 3 * k);
-    v -= n;
-  }
-  if (tid == 0) {
-    for (; v >= 0; --v) take_visit(l_vis + 3 * v);
-    n_spans[job.job_index] = (uint32_t)ns;
-  }
-  lds_barrier();
-  for (int m = tid; m < n_motifs; m += nthr) counts[job.count_off + m] = l_cnt[m];
+  hmm_path_to_front(sync, tid, nthr, pbuf, np, pcap);
+  if (tid == 0) hmm_store_purity(job.job_index, np, tb[TB_EDIT], tb[TB_REF], qlen, path_len, purity, edit_out, maxd_out);
+  hmm_decode_visits(sync, tid, nthr, tl, nb, g_vis, spans3 + 3 * job.span_off, n_spans + job.job_index, counts + job.count_off);
   HP_MARK(3);
 }
