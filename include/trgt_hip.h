@@ -218,7 +218,8 @@ typedef struct trgt_locus_params {
   int32_t mism, gapo, gape;  /* 2,5,1 */
   int32_t host_threads;      /* threads for the host glue between GPU stages (0 = hardware concurrency) */
   double min_read_qual;      /* Params::min_read_qual (tr.rs:19, --min-read-quality, default 0.98): below MIN_RQ_FOR_PURITY = 0.9
-                                the purity filter filter_impure_trs runs on the spanning reads (tr.rs:37-50) */
+                                the purity filter filter_impure_trs runs on the spanning reads (tr.rs:37-50) -- on the device, in front
+                                of the device-side genotypers, which stay in use: the value does not move a call to the host path */
 } trgt_locus_params;
 /* flank_len 250, min_flank_id_frac 0.7, max_depth 250, scoring 2,5,1, host_threads 0, min_read_qual 0.98 (cli.rs:271-344) */
 void trgt_locus_default_params(trgt_locus_params* p);

@@ -86,6 +86,7 @@ struct trgt_knobs {
   bool hmm_lds_fill = false;  // TRGT_HMM_LDS_FILL: one-wave motif sets fill their Viterbi columns through LDS like the larger ones (not in registers)
   int cluster_arena_kb = 0;  // TRGT_CLUSTER_ARENA_KB: developer switch -- the CIGAR / result / scratch arenas of the device-side cluster genotyper capped at this many KB (loci that find no room take the host path: the mixed case of the tests)
   bool host_cluster = false; // TRGT_HOST_CLUSTER: Genotyper::Cluster loci take the host path (linkage, groups and round sequencing on host threads, locus_cluster.hpp)
+  bool host_purity = false;  // TRGT_HOST_PURITY (DEV): calls with filter_impure_trs on (min_read_qual < 0.9) send every locus down the host path, as until the filter ran on the device (locus_purity.hpp)
   bool host_repair = false;  // TRGT_HOST_REPAIR: loci whose pick lacks majority support go back to the host (no device-side consensus repair)
   bool split_hmm = false;    // TRGT_SPLIT_HMM: the HMM of the loci the genotyper settles next to the device-side repair of the others, a second batch behind it
   int repair_blocks = 2048;  // TRGT_REPAIR_BLOCKS: workgroups (and workspaces) of the alignment kernel of the device-side repair
@@ -259,11 +260,12 @@ enum Slot {
   S_INF_SRC, S_INF_DESC, S_INF_DST, S_INF_STATUS, S_INF_COUNTER,  // device-side BGZF inflate (inflate_dev.hip)
   S_ZERO_ARENA,  // trgt::zero_begin / zero_take
   S_DEFL_SCRATCH,  // device-side BGZF deflate (deflate_dev.hip): the lanes' bit strings
+  S_PUR_SLAB, S_PUR_CNT, S_PUR_RQ,  // filter_impure_trs on the device (locus_purity.hpp): selected lists, purities; motif counts of its HMM batch
   S_COUNT
 };
 // pinned host buffer slots
 enum PinSlot { P_SPAN_S = 0, P_SPAN_E, P_HIT_L, P_HIT_R, P_CELLS, P_HMM_SEQ, P_HMM_SEQ_B, P_HMM_JOBS, P_HMM_JOBS_B, P_SEG0, P_SEG_META, P_GT_NEED, P_GT_NAL, P_GT_ALEN, P_GT_CI, P_GT_NSP, P_GT_CLS,
-               P_GT_RANK, P_GT_NSPAN, P_GT_TOFF, P_GT_PACKED, P_HMM_BUILD, P_COUNT };
+               P_GT_RANK, P_GT_NSPAN, P_GT_TOFF, P_GT_PACKED, P_HMM_BUILD, P_PUR_JOBS, P_COUNT };
 
 inline int dev_get(trgt_hip_ctx* c, int slot, size_t bytes, void** out) {
   if ((int)c->pool.size() < S_COUNT) c->pool.resize(S_COUNT);

@@ -31,6 +31,7 @@
 #include "hmm_host.hpp"
 #include "host_pool.hpp"
 #include "locus_gt.hpp"
+#include "locus_purity.hpp"
 #include "locus_cluster_dev.hpp"
 #include "wfa_host.hpp"
 
@@ -584,8 +585,10 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   }
   int threads = p->host_threads > 0 ? p->host_threads : (int)std::max(1u, std::thread::hardware_concurrency());
   // a few microseconds of work per locus: more threads only add wake-up cost.  The device genotyper leaves the
-  // host little to do (4 threads measure the same as 32, and large pools produce the occasional late wake-up)
-  threads = std::min(threads, !c->knobs.host_genotyper && p->min_read_qual >= 0.9 ? 8 : 32);
+  // host little to do (4 threads measure the same as 32, and large pools produce the occasional late wake-up).  That holds with
+  // filter_impure_trs on as well since the filter runs on the device (locus_purity.hpp): the host then sees the same few handed-back loci
+  // as in a call without the filter, so the cap no longer looks at min_read_qual -- only the all-host routes keep the large pool
+  threads = std::min(threads, !c->knobs.host_genotyper && !(p->min_read_qual < 0.9 && c->knobs.host_purity) ? 8 : 32);
   HostPool* pool = host_pool(c, threads);
   const int64_t t0 = now_ns();
   c->tl_t0 = t0;
@@ -603,6 +606,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     for (int64_t s = 0; s < 2 * nl; ++s) { out->n_spans[s] = 0; out->purity[s] = std::nan(""); }
   };
   if (nr == 0) { init_outputs(); return TRGT_OK; }
+  bool outputs_ready = false;  // (a call that waits for its purity jobs initialises the outputs during that wait)
   if (!c->stream2) TRGT_HIP_TRY(c, trgt::make_stream(c, &c->stream2));
   // The motif-HMM tables depend only on the catalog: build them on a host thread while the GPU locates flanks.
   // They are uploaded from the same thread (second stream), so stage C finds them in HBM.
@@ -652,10 +656,13 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   c->dbg_ns[0] = now_ns() - t0;  // set-up: thread pool, model thread, piece / read-locus tables
   TL("set-up");
   const bool reads_on_device = is_device_ptr(in->read_blob);
-  // filter_impure_trs (tr.rs:37-50) sits between get_spanning_reads and the genotyper: with it on, every locus takes the host path
+  // filter_impure_trs (tr.rs:37-50) sits between get_spanning_reads and the genotyper.  With it on, the selection, the purity batch and
+  // the filter run on the device in front of the genotyper chains (locus_purity.hpp), which then load the filtered lists instead of
+  // selecting the reads themselves; the loci they hand back are filtered by the host path below, like every locus under TRGT_HOST_PURITY
   const bool impure_filter = p->min_read_qual < 0.9;
   // (host reads are uploaded for the flank scan anyway: the device genotyper then works on that copy just as well)
-  const bool dev_gt = !c->knobs.host_genotyper && !impure_filter;
+  const bool dev_gt = !c->knobs.host_genotyper && !(impure_filter && c->knobs.host_purity);
+  const bool presel = dev_gt && impure_filter;
   auto is_cluster = [&](int64_t l) { return in->genotyper && in->genotyper[l] == 1; };
   // genotype_flank (tr.rs:69-75) can only change a genotype when reads carry haplotype tags or mismatch offsets
   const bool flank_on = in->hp_tag != nullptr || (in->mismatch_offsets != nullptr && in->mismatch_off != nullptr);
@@ -706,6 +713,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     const uint32_t* tr_len = nullptr; const uint64_t* al_off = nullptr; const uint32_t* al_cap = nullptr; const uint8_t* geno = nullptr;
     void *need = nullptr, *nal = nullptr, *blob = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr,
          *toff = nullptr, *packed = nullptr;
+    const double* rq = nullptr;
   } g;
   std::vector<uint32_t> cl_list; std::vector<uint64_t> cl_moff;
   uint64_t cl_pairs = 0, cl_reads = 0; uint32_t cl_max_nr = 0;
@@ -716,6 +724,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         (rc = dev_in(c, S_GT_TR, in->tr_blob, (size_t)tr_total, &g.tr, &ub)) || (rc = dev_in(c, S_GT_TROFF, in->tr_off, (size_t)nl, &g.tr_off, &ub)) ||
         (rc = dev_in(c, S_GT_TRLEN, in->tr_len, (size_t)nl, &g.tr_len, &ub)) || (rc = dev_in(c, S_GT_ALOFF, out->allele_off, 2 * (size_t)nl, &g.al_off, &ub)) ||
         (rc = dev_in(c, S_GT_ALCAP, out->allele_cap, (size_t)nl, &g.al_cap, &ub)) || (in->genotyper && (rc = dev_in(c, S_GT_GENO, in->genotyper, (size_t)nl, &g.geno, &ub))) ||
+        (presel && in->read_qual && (rc = dev_in(c, S_PUR_RQ, in->read_qual, (size_t)nr, &g.rq, &ub))) ||
         (rc = dev_get(c, S_GT_BLOB, (size_t)allele_total + 16, &g.blob)) || (rc = dev_get(c, S_GT_PACKED, (size_t)allele_total + 16, &g.packed)))
       return rc;
     // Genotyper::Cluster loci stay on the device too (locus_cluster_dev.hpp) unless TRGT_HOST_CLUSTER / TRGT_SPLIT_HMM say otherwise: the
@@ -832,7 +841,69 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       if (!z_rpc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, rp.counts, (uint32_t)gt::RC_WORDS);
     }
     const bool small_gt = max_locus_reads <= 64;
-    if (small_gt) hipLaunchKernelGGL((gt::locus_genotype_kernel<64, 8 * 1024>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
+    if (presel) {
+      // ---- filter_impure_trs in front of the genotypers (locus_purity.hpp): selection, purity jobs, HMM batch, filter.  The job list is
+      //      resolved by the host from the select kernel's compact output in pinned memory -- one wait for the spans (which the call
+      //      waits for anyway, later) and one for the purity batch; the purities stay in HBM, indexed by job, and the filter kernel
+      //      finds them through the job index of every selected slot
+      ga.sel_read = ga.sel_start = ga.sel_len = ga.n_sel = nullptr;
+      size_t pt = 0;
+      auto padd = [&](size_t bytes) { const size_t o = pt; pt += (bytes + 255) & ~(size_t)255; return o; };
+      const size_t po_read = padd((size_t)nr * 4), po_start = padd((size_t)nr * 4), po_len = padd((size_t)nr * 4), po_job = padd((size_t)nr * 4), po_n = padd((size_t)nl * 4),
+                   po_pur = padd((size_t)nr * 8), po_nsp = padd((size_t)nr * 4), po_cnt = padd(64);
+      void *d_ps = nullptr, *h_pj = nullptr;
+      if ((rc = dev_get(c, S_PUR_SLAB, pt, &d_ps)) || (rc = pin_get(c, P_PUR_JOBS, 64 + (size_t)nr * sizeof(pur::PurityJob), &h_pj))) return rc;
+      auto psl = [&](size_t o) { return (void*)((uint8_t*)d_ps + o); };
+      pur::PurityArgs pa;
+      std::memset(&pa, 0, sizeof pa);
+      pa.read_qual = g.rq; pa.skip_cluster = cl_list.empty() ? 1 : 0;
+      pa.sel_read = (uint32_t*)psl(po_read); pa.sel_start = (uint32_t*)psl(po_start); pa.sel_len = (uint32_t*)psl(po_len); pa.sel_job = (uint32_t*)psl(po_job);
+      pa.n_sel = (uint32_t*)psl(po_n); pa.purity = (const double*)psl(po_pur);
+      pa.jobs = (pur::PurityJob*)((uint8_t*)h_pj + 64); pa.cap_jobs = (uint32_t)nr;
+      void* const z_cnt = zero_take(c, 64);  // (cleared with the call's zero arena; else by the kernel below)
+      pa.counter = z_cnt ? (uint32_t*)z_cnt : (uint32_t*)psl(po_cnt);
+      if (!z_cnt) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, pa.counter, 1u);
+      const dim3 pgrid((unsigned)nl);
+      if (small_gt) hipLaunchKernelGGL((pur::purity_select_kernel<64>), pgrid, dim3(64), 0, c->stream, ga, pa);
+      else hipLaunchKernelGGL((pur::purity_select_kernel<gt::GT_MAX_READS>), pgrid, dim3(64), 0, c->stream, ga, pa);
+      TRGT_HIP_TRY(c, hipGetLastError());
+      *(uint32_t*)h_pj = 0;
+      { const int d2h_rc = trgt::d2h(c, h_pj, pa.counter, 4, c->stream); if (d2h_rc) return d2h_rc; }
+      tl_mark(c, "purity selection enqueued");
+      init_outputs(); outputs_ready = true;  // host-only work: done while the GPU locates the flanks
+      const int64_t tw_p = now_ns();
+      TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
+      tA += now_ns() - tw_p;
+      TL("purity jobs listed");
+      const int64_t n_pj = (int64_t)std::min<uint32_t>(*(const uint32_t*)h_pj, pa.cap_jobs);
+      if (n_pj > 0) {
+        const pur::PurityJob* pj = pa.jobs;
+        std::vector<uint32_t> pj_set((size_t)n_pj), pj_len((size_t)n_pj); std::vector<uint64_t> pj_off((size_t)n_pj), pj_cnt_off((size_t)n_pj);
+        uint64_t cnt_total = 0;
+        for (int64_t j = 0; j < n_pj; ++j) {
+          if ((int64_t)pj[j].locus >= nl) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: purity job %lld names locus %u", (long long)j, pj[j].locus);
+          pj_set[(size_t)j] = pj[j].locus; pj_off[(size_t)j] = pj[j].seq_off; pj_len[(size_t)j] = pj[j].seq_len;
+          pj_cnt_off[(size_t)j] = cnt_total; cnt_total += in->set_motif_begin[pj[j].locus + 1] - in->set_motif_begin[pj[j].locus];
+        }
+        void* d_pcnt = nullptr;
+        if ((rc = dev_get(c, S_PUR_CNT, ((size_t)cnt_total + 1) * 4, &d_pcnt))) return rc;
+        const int64_t tc0 = now_ns();
+        // (device pointers for every result: nothing is copied back, the call returns when the kernels are through)
+        rc = hmm_batch_impl(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, n_pj, pj_set.data(), d_reads, pj_off.data(), pj_len.data(),
+                            nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t*)psl(po_nsp), (uint32_t*)d_pcnt, pj_cnt_off.data(), (double*)psl(po_pur), nullptr, nullptr);
+        if (rc) return rc;
+        tC += now_ns() - tc0;
+        stat_hmm_jobs += n_pj;
+        TL("purity batch done");
+      }
+      if (small_gt) hipLaunchKernelGGL((pur::purity_filter_kernel<64>), pgrid, dim3(64), 0, c->stream, ga, pa);
+      else hipLaunchKernelGGL((pur::purity_filter_kernel<gt::GT_MAX_READS>), pgrid, dim3(64), 0, c->stream, ga, pa);
+      TRGT_HIP_TRY(c, hipGetLastError());
+      ga.sel_read = pa.sel_read; ga.sel_start = pa.sel_start; ga.sel_len = pa.sel_len; ga.n_sel = pa.n_sel;
+      if (small_gt) hipLaunchKernelGGL((gt::locus_genotype_kernel<64, 8 * 1024, true>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
+      else hipLaunchKernelGGL((gt::locus_genotype_kernel<gt::GT_MAX_READS, gt::GT_SEG_LDS, true>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
+    }
+    else if (small_gt) hipLaunchKernelGGL((gt::locus_genotype_kernel<64, 8 * 1024>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
     else hipLaunchKernelGGL((gt::locus_genotype_kernel<gt::GT_MAX_READS, gt::GT_SEG_LDS>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
     TRGT_HIP_TRY(c, hipGetLastError());
     tl_mark(c, "genotyper launched");
@@ -903,7 +974,11 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)rp.cap_groups), dim3(vote::VOTE_THREADS), 0, c->stream, va);
       const gt::FinishArgs fa{(const uint8_t*)d_vout, (const uint32_t*)d_vlen};
       const dim3 fgrid((unsigned)nl);
-      if (small_gt) hipLaunchKernelGGL((gt::repair_finish_kernel<64>), fgrid, dim3(64), 0, c->stream, ga, fa);
+      if (presel) {
+        if (small_gt) hipLaunchKernelGGL((gt::repair_finish_kernel<64, true>), fgrid, dim3(64), 0, c->stream, ga, fa);
+        else hipLaunchKernelGGL((gt::repair_finish_kernel<gt::GT_MAX_READS, true>), fgrid, dim3(64), 0, c->stream, ga, fa);
+      }
+      else if (small_gt) hipLaunchKernelGGL((gt::repair_finish_kernel<64>), fgrid, dim3(64), 0, c->stream, ga, fa);
       else hipLaunchKernelGGL((gt::repair_finish_kernel<gt::GT_MAX_READS>), fgrid, dim3(64), 0, c->stream, ga, fa);
       TRGT_HIP_TRY(c, hipGetLastError());
       if ((rc = dbg_sync("vote + finish"))) return rc;
@@ -955,7 +1030,12 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       ca.vote_out = (const uint8_t*)d_vout; ca.vote_len = (const uint32_t*)d_vlen;
       if (!z_clc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, ca.counts, (uint32_t)cl::CC_WORDS);
       const dim3 cgrid(n_cl);
-      if (big) hipLaunchKernelGGL((cl::cluster_front_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
+      // (with filter_impure_trs on: the instantiations that load the filtered lists, like the length genotyper's)
+      if (presel) {
+        if (big) hipLaunchKernelGGL((cl::cluster_front_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
+        else hipLaunchKernelGGL((cl::cluster_front_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
+      }
+      else if (big) hipLaunchKernelGGL((cl::cluster_front_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
       else hipLaunchKernelGGL((cl::cluster_front_kernel<64>), cgrid, dim3(64), 0, c->stream, ca);
       TRGT_HIP_TRY(c, hipGetLastError());
       const int64_t wg_bound = (int64_t)std::max(64, 2 * c->knobs.repair_blocks);
@@ -989,16 +1069,28 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         return TRGT_OK;
       };
       if ((rc = ed_launch(ca.ed_jobs, cl_pairs, ca.counts + cl::CC_ED, d_reads, ca.escore))) return rc;
-      if (big) hipLaunchKernelGGL((cl::cluster_ward_kernel<gt::GT_MAX_READS, false>), cgrid, dim3(64), 0, c->stream, ca);
+      if (presel) {
+        if (big) hipLaunchKernelGGL((cl::cluster_ward_kernel<gt::GT_MAX_READS, false, true>), cgrid, dim3(64), 0, c->stream, ca);
+        else hipLaunchKernelGGL((cl::cluster_ward_kernel<64, true, true>), cgrid, dim3(64), 0, c->stream, ca);
+      }
+      else if (big) hipLaunchKernelGGL((cl::cluster_ward_kernel<gt::GT_MAX_READS, false>), cgrid, dim3(64), 0, c->stream, ca);
       else hipLaunchKernelGGL((cl::cluster_ward_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
       TRGT_HIP_TRY(c, hipGetLastError());
       if ((rc = cons_launch(0, ca.counts + cl::CC_J1, 0, ca.counts + cl::CC_G1))) return rc;
-      if (big) hipLaunchKernelGGL((cl::cluster_round2_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
+      if (presel) {
+        if (big) hipLaunchKernelGGL((cl::cluster_round2_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
+        else hipLaunchKernelGGL((cl::cluster_round2_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
+      }
+      else if (big) hipLaunchKernelGGL((cl::cluster_round2_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
       else hipLaunchKernelGGL((cl::cluster_round2_kernel<64>), cgrid, dim3(64), 0, c->stream, ca);
       TRGT_HIP_TRY(c, hipGetLastError());
       if ((rc = cons_launch(ca.cap_j, ca.counts + cl::CC_J2, ca.cap_g, ca.counts + cl::CC_G2))) return rc;
       if ((rc = ed_launch(ca.ed2_jobs, 2 * cl_reads, ca.counts + cl::CC_ED2, (const uint8_t*)d_vout, ca.escore2))) return rc;
-      if (big) hipLaunchKernelGGL((cl::cluster_finish_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
+      if (presel) {
+        if (big) hipLaunchKernelGGL((cl::cluster_finish_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
+        else hipLaunchKernelGGL((cl::cluster_finish_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
+      }
+      else if (big) hipLaunchKernelGGL((cl::cluster_finish_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
       else hipLaunchKernelGGL((cl::cluster_finish_kernel<64>), cgrid, dim3(64), 0, c->stream, ca);
       TRGT_HIP_TRY(c, hipGetLastError());
       tl_mark(c, "cluster chain enqueued");
@@ -1017,7 +1109,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   TRGT_HIP_TRY(c, hipEventRecord(evA, c->stream));
   c->dbg_ns[2] = now_ns() - t0;  // + stage A enqueued
   TL("stage A enqueued");
-  init_outputs();  // host-only work: done while the GPU is already busy
+  if (!outputs_ready) init_outputs();  // host-only work: done while the GPU is already busy
   const int64_t tw_a = now_ns();  // from here on the host waits for stage A (the table upload below sits behind it in the copy queue)
   if (use_slots && !hmm_pending && !hmm_pendingB) {  // one HMM batch behind the genotyper and the repair (need_host is final by then)
     hs.d_skip = (const uint8_t*)g.need;
@@ -1035,7 +1127,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         fprintf(stderr, "\n"); }
       if (ea != hipSuccess) return trgt::fail(c, TRGT_ERR_HIP, "trgt::event_wait(evA) failed: %s", hipGetErrorString(ea)); }
     if (stage_a_token.owns_lock()) stage_a_token.unlock();
-    tA = now_ns() - tw_a;
+    tA += now_ns() - tw_a;
   TL("evA");
   }
   int64_t th_begin = now_ns();
@@ -1099,6 +1191,43 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     }
     TL("hmm1 job lists");
   }
+  // the two device-resolved HMM batches: the first one's counts / purities arrive as whole arrays ("no allele" in every slot that was not
+  // its job), so it is collected first and the second one's are merged in slot by slot
+  auto collect_ab = [&]() -> int {
+    if (!hmm_pendingB) return TRGT_OK;  // (a single batch is collected where it always was, below)
+    const int64_t tc0 = now_ns();
+    if (hmm_pending) {
+      HmmPending* pend = hmm_pending; hmm_pending = nullptr;
+      if (int r = hmm_collect(c, pend)) return r;
+      const uint8_t* need = (const uint8_t*)gh.need;
+      for (int64_t l = 0; l < nl; ++l) if (need[l]) { out->n_spans[2 * l] = out->n_spans[2 * l + 1] = 0; out->purity[2 * l] = out->purity[2 * l + 1] = std::nan(""); }
+      TL("hmm1 collected");
+    }
+    {
+      HmmPending* pend = hmm_pendingB; hmm_pendingB = nullptr;
+      if (int r = hmm_collect(c, pend)) return r;
+      const uint8_t* skip_b = (const uint8_t*)hsl(o_skipb); const int32_t* nal = (const int32_t*)gh.nal;
+      for (int64_t l = 0; l < nl; ++l)
+        if (!skip_b[l]) for (int a = 0; a < nal[l]; ++a) { out->n_spans[2 * l + a] = nsB[(size_t)(2 * l + a)]; out->purity[2 * l + a] = puB[(size_t)(2 * l + a)]; }
+      TL("hmm1b collected");
+    }
+    tC += now_ns() - tc0;
+    return TRGT_OK;
+  };
+  auto collect_hmm1 = [&]() -> int {  // stage C results of the device-genotyped loci (one batch)
+    if (!hmm_pending) return TRGT_OK;
+    const int64_t tc0 = now_ns();
+    HmmPending* pend = hmm_pending; hmm_pending = nullptr;
+    if (int r = hmm_collect(c, pend)) return r;
+    TL("hmm1 collected");
+    if (use_slots) {  // (the whole arrays came back: the slots of the loci that took the host path hold "no allele" until stage C of those)
+      const uint8_t* need = (const uint8_t*)gh.need;
+      for (int64_t l = 0; l < nl; ++l) if (need[l]) { out->n_spans[2 * l] = out->n_spans[2 * l + 1] = 0; out->purity[2 * l] = out->purity[2 * l + 1] = std::nan(""); }
+    }
+    for (size_t j = 0; j < slot.size(); ++j) { out->n_spans[slot[j]] = nsp[j]; out->purity[slot[j]] = pur[j]; }
+    tC += now_ns() - tc0;
+    return TRGT_OK;
+  };
   std::vector<LocusWork> work((size_t)nR);
   struct K { uint32_t read, s, e; };
   std::vector<uint64_t> sel_begin((size_t)nR + 1, 0);
@@ -1154,6 +1283,8 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         pj_begin[(size_t)li + 1] = pj_set.size();
       }
       if (!pj_set.empty()) {
+        // (the device-resolved stage-C batches of this call hold the HMM buffer sets: they are collected before this batch takes one)
+        if ((rc = collect_ab()) || (rc = collect_hmm1())) return rc;
         pj_nsp.resize(pj_set.size()); pj_pur.resize(pj_set.size());
         std::vector<uint32_t> pj_counts((size_t)cnt_total + 1);
         rc = hmm_batch_impl(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, (int64_t)pj_set.size(), pj_set.data(),
@@ -1226,29 +1357,6 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   // publishing of spans and device-genotyper results: host work of ~1.2 ms that needs the GPU only to start the HMM batch.  It runs
   // while the consensus alignments of the host-path loci are on the GPU (wfa_batch_impl calls it between launch and wait), or
   // right here when there are none.
-  // the two device-resolved HMM batches: the first one's counts / purities arrive as whole arrays ("no allele" in every slot that was not
-  // its job), so it is collected first and the second one's are merged in slot by slot
-  auto collect_ab = [&]() -> int {
-    if (!hmm_pendingB) return TRGT_OK;  // (a single batch is collected where it always was, below)
-    const int64_t tc0 = now_ns();
-    if (hmm_pending) {
-      HmmPending* pend = hmm_pending; hmm_pending = nullptr;
-      if (int r = hmm_collect(c, pend)) return r;
-      const uint8_t* need = (const uint8_t*)gh.need;
-      for (int64_t l = 0; l < nl; ++l) if (need[l]) { out->n_spans[2 * l] = out->n_spans[2 * l + 1] = 0; out->purity[2 * l] = out->purity[2 * l + 1] = std::nan(""); }
-      TL("hmm1 collected");
-    }
-    {
-      HmmPending* pend = hmm_pendingB; hmm_pendingB = nullptr;
-      if (int r = hmm_collect(c, pend)) return r;
-      const uint8_t* skip_b = (const uint8_t*)hsl(o_skipb); const int32_t* nal = (const int32_t*)gh.nal;
-      for (int64_t l = 0; l < nl; ++l)
-        if (!skip_b[l]) for (int a = 0; a < nal[l]; ++a) { out->n_spans[2 * l + a] = nsB[(size_t)(2 * l + a)]; out->purity[2 * l + a] = puB[(size_t)(2 * l + a)]; }
-      TL("hmm1b collected");
-    }
-    tC += now_ns() - tc0;
-    return TRGT_OK;
-  };
   bool published = false;
   auto hmm1_enqueue = [&]() -> int {
   if (dev_gt && !use_slots) {
@@ -1565,19 +1673,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   // ---------------- stage C results of the device-genotyped loci
   TL("hmm2 enqueued");
   if ((rc = collect_ab())) return rc;
-  if (hmm_pending) {
-    const int64_t tc0 = now_ns();
-    HmmPending* pend = hmm_pending; hmm_pending = nullptr;
-    rc = hmm_collect(c, pend);
-    if (rc) return rc;
-    TL("hmm1 collected");
-    if (use_slots) {  // (the whole arrays came back: the slots of the loci that took the host path hold "no allele" until stage C of those)
-      const uint8_t* need = (const uint8_t*)gh.need;
-      for (int64_t l = 0; l < nl; ++l) if (need[l]) { out->n_spans[2 * l] = out->n_spans[2 * l + 1] = 0; out->purity[2 * l] = out->purity[2 * l + 1] = std::nan(""); }
-    }
-    for (size_t j = 0; j < slot.size(); ++j) { out->n_spans[slot[j]] = nsp[j]; out->purity[slot[j]] = pur[j]; }
-    tC += now_ns() - tc0;
-  }
+  if ((rc = collect_hmm1())) return rc;
   if (hmm_pending2) {
     const int64_t tc0 = now_ns();
     HmmPending* pend = hmm_pending2; hmm_pending2 = nullptr;

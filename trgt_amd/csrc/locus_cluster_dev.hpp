@@ -78,7 +78,7 @@ __device__ __forceinline__ int wave_min_i32(int v) {
 __device__ __forceinline__ unsigned long long lanes_below(int lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
 
 // ---- 1. spanning reads, pair list
-template <int MAXR>
+template <int MAXR, bool PRESEL = false>
 __global__ void __launch_bounds__(64) cluster_front_kernel(const ClArgs a) {
   __shared__ ClFront<MAXR> sh;
   __shared__ uint32_t s_base;
@@ -98,7 +98,7 @@ __global__ void __launch_bounds__(64) cluster_front_kernel(const ClArgs a) {
     return;
   }
   if (lane == 0) sh.n = 0;
-  gt::gt_front<MAXR>(sh, a.g, r0, nr, lane);
+  gt::gt_selected<MAXR, PRESEL>(sh, a.g, l, r0, nr, lane);
   const int n = sh.n;
   rec.n = n; rec.state = n > 0 ? 1 : 0;
   if (lane == 0) a.rec[k] = rec;
@@ -181,7 +181,7 @@ __device__ __forceinline__ int central_read_wave(const double* D, uint32_t n, co
   return gm[m < 0 ? 0 : m];
 }
 
-template <int MAXR, bool LDS_MAT>
+template <int MAXR, bool LDS_MAT, bool PRESEL = false>
 __global__ void __launch_bounds__(64) cluster_ward_kernel(const ClArgs a) {
   __shared__ ClWard<MAXR, LDS_MAT> sh;
   constexpr int T = MAXR / 64;
@@ -194,7 +194,7 @@ __global__ void __launch_bounds__(64) cluster_ward_kernel(const ClArgs a) {
   const uint64_t r0 = a.g.locus_read_begin[l];
   const int nr = (int)(a.g.locus_read_begin[l + 1] - r0);
   if (lane == 0) sh.f.n = 0;
-  gt::gt_front<MAXR>(sh.f, a.g, r0, nr, lane);
+  gt::gt_selected<MAXR, PRESEL>(sh.f, a.g, l, r0, nr, lane);
   const int n = sh.f.n;
   const uint32_t un = (uint32_t)n;
   const int ploidy = a.g.ploidy[l] == 1 ? 1 : 2;
@@ -428,7 +428,7 @@ __global__ void __launch_bounds__(64) cluster_ward_kernel(const ClArgs a) {
 }
 
 // ---- 3. behind the first consensus round: the homozygous redo, or the dropped reads against both alleles
-template <int MAXR>
+template <int MAXR, bool PRESEL = false>
 __global__ void __launch_bounds__(64) cluster_round2_kernel(const ClArgs a) {
   __shared__ ClFront<MAXR> sh;
   __shared__ int s_ok; __shared__ uint32_t s_g0, s_j0; __shared__ unsigned long long s_c0, s_o0, s_s0;
@@ -444,7 +444,7 @@ __global__ void __launch_bounds__(64) cluster_round2_kernel(const ClArgs a) {
   const uint64_t r0 = a.g.locus_read_begin[l];
   const int nr = (int)(a.g.locus_read_begin[l + 1] - r0);
   if (lane == 0) sh.n = 0;
-  gt::gt_front<MAXR>(sh, a.g, r0, nr, lane);
+  gt::gt_selected<MAXR, PRESEL>(sh, a.g, l, r0, nr, lane);
   const int n = sh.n;
   const uint32_t l1 = a.vote_len[rec.grp[0]], l2 = a.vote_len[rec.grp[1]];
   const uint32_t c1 = (uint32_t)rec.gsize[0], c2 = (uint32_t)rec.gsize[1];
@@ -538,7 +538,7 @@ __global__ void __launch_bounds__(64) cluster_round2_kernel(const ClArgs a) {
 }
 
 // ---- 4. genotype, classifications, allele order (:143-151, :99-115, :62-73), reference allele first (tr.rs:95-101), outputs
-template <int MAXR>
+template <int MAXR, bool PRESEL = false>
 __global__ void __launch_bounds__(64) cluster_finish_kernel(const ClArgs a) {
   __shared__ ClFront<MAXR> sh;
   __shared__ int8_t s_cls[MAXR];
@@ -554,7 +554,7 @@ __global__ void __launch_bounds__(64) cluster_finish_kernel(const ClArgs a) {
   const uint64_t r0 = a.g.locus_read_begin[l];
   const int nr = (int)(a.g.locus_read_begin[l + 1] - r0);
   if (lane == 0) sh.n = 0;
-  gt::gt_front<MAXR>(sh, a.g, r0, nr, lane);
+  gt::gt_selected<MAXR, PRESEL>(sh, a.g, l, r0, nr, lane);
   const int n = sh.n;
   const int ploidy = a.g.ploidy[l] == 1 ? 1 : 2;
   const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0}; uint32_t civ[4] = {0, 0, 0, 0};

@@ -55,6 +55,9 @@ struct GtArgs {
   uint8_t* skip_b;   // [n_loci] 0 for the loci repair_finish_kernel completed (their HMM batch runs behind it), else 1
   int32_t finish_clears_need;  // 1: repair_finish_kernel also sets need_host = 0 (nothing reads it concurrently: one HMM batch behind the repair)
   RepairBufs rp;
+  // calls with filter_impure_trs on (locus_purity.hpp), read by the PRESEL instantiations only: the kept reads of locus l, already selected,
+  // ordered and filtered, in slots [locus_read_begin[l], + n_sel[l]) -- read (index inside the locus), span start, span length
+  const uint32_t *sel_read, *sel_start, *sel_len, *n_sel;
 };
 
 template <int MAXR, int SEG>
@@ -194,7 +197,22 @@ __device__ __forceinline__ void gt_front(SH& sh, const GtArgs& a, uint64_t r0, i
   }
 }
 
-template <int MAXR, int SEG>
+// The kept reads of a locus for every kernel behind the selection: gt_front, or -- PRESEL, the instantiations launched when
+// filter_impure_trs is on -- the list purity_select_kernel and purity_filter_kernel (locus_purity.hpp) left in global memory.  Either
+// way sh.n kept reads sit in sh.s_read / s_start / s_len in LocusResult.reads order and sh.r_off holds the blob offsets of all reads.
+template <int MAXR, bool PRESEL, class SH>
+__device__ __forceinline__ void gt_selected(SH& sh, const GtArgs& a, int64_t l, uint64_t r0, int nr, int lane) {
+  if constexpr (!PRESEL) gt_front<MAXR>(sh, a, r0, nr, lane);
+  else {
+    const int n = min((int)a.n_sel[l], nr);
+    for (int i = lane; i < nr; i += 64) sh.r_off[i] = a.read_off[r0 + i];
+    for (int i = lane; i < n; i += 64) { sh.s_read[i] = a.sel_read[r0 + i]; sh.s_start[i] = a.sel_start[r0 + i]; sh.s_len[i] = a.sel_len[r0 + i]; }
+    if (lane == 0) sh.n = n;
+    __syncthreads();
+  }
+}
+
+template <int MAXR, int SEG, bool PRESEL = false>
 __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgs a) {  // exactly one wave per locus: the lane-0 sections and the ballots rely on it
   __shared__ GtShared<MAXR, SEG> sh;
   const int64_t l = blockIdx.x;
@@ -215,7 +233,7 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgs a) {  /
     if (lane == 0 && (nr > MAXR || cluster) && a.ploidy[l] != 0 && nr != 0) a.need_host[l] = 1;
     return;
   }
-  gt_front<MAXR>(sh, a, r0, nr, lane);
+  gt_selected<MAXR, PRESEL>(sh, a, l, r0, nr, lane);
   const uint32_t refn = a.tr_len[l];
   const uint64_t refo = a.tr_off[l];
   int n = sh.n;
@@ -525,7 +543,7 @@ __device__ __forceinline__ bool wave_equal(const uint8_t* __restrict__ p, uint32
   for (uint32_t i = threadIdx.x & 63; i < n; i += 64) diff = diff || p[i] != q[i];
   return __ballot(diff) == 0ull;
 }
-template <int MAXR>
+template <int MAXR, bool PRESEL = false>
 __global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgs a, const FinishArgs f) {
   __shared__ FinShared<MAXR> sh;
   const RepairBufs& rp = a.rp;
@@ -535,7 +553,7 @@ __global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgs a, const
   const uint64_t r0 = a.locus_read_begin[l];
   const int nr = (int)(a.locus_read_begin[l + 1] - r0);
   if (lane == 0) sh.n = 0;
-  gt_front<MAXR>(sh, a, r0, nr, lane);
+  gt_selected<MAXR, PRESEL>(sh, a, l, r0, nr, lane);
   const int n = sh.n;
   const RepairPend pd = rp.pend[l];
   const int ploidy = a.ploidy[l] == 1 ? 1 : 2;
