@@ -79,6 +79,14 @@ const char* trgt_hip_last_error(const trgt_hip_ctx* ctx); /* ctx may be NULL: la
 int trgt_hip_set_stream(trgt_hip_ctx* ctx, void* hip_stream);
 /* Upper bound (bytes) for the per-call device workspace (wavefront history, back-pointers). 0 = default (32 GiB). */
 int trgt_hip_set_workspace_limit(trgt_hip_ctx* ctx, uint64_t bytes);
+/* Genotyper::Cluster (genotype_cluster.rs:58-152) on the device for deep loci.  By default the device chain takes cluster loci of at
+ * most 256 candidate reads and deeper ones are genotyped on host threads.  A context set to max_reads > 256 also keeps cluster loci
+ * with 256 < reads <= max_reads on the device (one workgroup per locus, locus_cluster_deep.hpp), as far as they fit the call's budget
+ * -- an eighth of the workspace limit, at most 2 GiB; a locus without room takes the host path and is counted in stats[23].  Results
+ * are the same either way.  trgt_hip_cluster_max_reads_limit: the compiled ceiling (2048), no GPU needed.  max_reads outside
+ * [256, limit]: TRGT_ERR_INVALID, the setting stays.  The contexts of a pool are set one by one through trgt_hip_pool_context. */
+int32_t trgt_hip_cluster_max_reads_limit(void);
+int trgt_hip_set_cluster_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
 
 /* ---- kernel timing (HIP events on the ctx stream, for bench.py's roofline) ---- */
 #define TRGT_K_FLANK_SCAN 0   /* exact flank search (+ the segment search for the seeded windows of the fallback alignments) */

@@ -104,6 +104,7 @@ struct trgt_hip_ctx {
   bool in_pool = false;     // created by trgt_hip_pool_create
   std::string err;
   uint64_t ws_limit = 32ull << 30;
+  int32_t cluster_max_reads = 256;  // trgt_hip_set_cluster_max_reads: deepest Genotyper::Cluster locus the device chains take (256 = the one-wave chain only)
   int num_cus = 256;
   // cached device buffers, indexed by slot
   struct Buf { void* p = nullptr; size_t cap = 0; };
@@ -261,6 +262,8 @@ enum Slot {
   S_ZERO_ARENA,  // trgt::zero_begin / zero_take
   S_DEFL_SCRATCH,  // device-side BGZF deflate (deflate_dev.hip): the lanes' bit strings
   S_PUR_SLAB, S_PUR_CNT, S_PUR_RQ,  // filter_impure_trs on the device (locus_purity.hpp): selected lists, purities; motif counts of its HMM batch
+  S_CLD_LIST, S_CLD_LAST = S_CLD_LIST + (S_CL_VSCR - S_CL_LIST),  // the deep list of the cluster genotyper (locus_cluster_deep.hpp): a second set of the S_CL_ slots
+  S_CLD_SEL,  // ... and its selected lists and merge records (one slab)
   S_COUNT
 };
 // pinned host buffer slots

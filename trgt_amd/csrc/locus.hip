@@ -33,6 +33,7 @@
 #include "locus_gt.hpp"
 #include "locus_purity.hpp"
 #include "locus_cluster_dev.hpp"
+#include "locus_cluster_deep.hpp"
 #include "wfa_host.hpp"
 
 namespace trgt {
@@ -410,12 +411,13 @@ HostPool* host_pool(trgt_hip_ctx* c, int threads) {
 // Exclusive prefix over the allele lengths (one workgroup) and the packing of the alleles into one dense buffer for the D2H copy
 // (... and, riding along: the count blocks of the device-side repair and of the cluster genotyper copied into the result slab -- null
 //  source: zeros -- which were a D2D copy or a fill each)
-struct CountCopy { const uint32_t* src1; uint32_t* dst1; uint32_t n1; const uint32_t* src2; uint32_t* dst2; uint32_t n2; };
+struct CountCopy { const uint32_t* src1; uint32_t* dst1; uint32_t n1; const uint32_t* src2; uint32_t* dst2; uint32_t n2; const uint32_t* src3; uint32_t* dst3; uint32_t n3; };
 __global__ void __launch_bounds__(1024) allele_prefix_kernel(const uint32_t* __restrict__ len, uint64_t* __restrict__ off, int64_t n, const CountCopy cc) {
   __shared__ uint64_t part[1024];
   const int t = threadIdx.x;
   if ((uint32_t)t < cc.n1) cc.dst1[t] = cc.src1 ? __hip_atomic_load(cc.src1 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   if ((uint32_t)t < cc.n2) cc.dst2[t] = cc.src2 ? __hip_atomic_load(cc.src2 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  if ((uint32_t)t < cc.n3) cc.dst3[t] = cc.src3 ? __hip_atomic_load(cc.src3 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   const int64_t per = (n + 1023) / 1024, b = t * per, e = b + per < n ? b + per : n;
   uint64_t sum = 0;
   for (int64_t i = b; i < e; ++i) sum += len[i];
@@ -694,12 +696,12 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     size_t add(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
   } slab;
   const size_t o_ss = slab.add((size_t)nr * 4), o_se = slab.add((size_t)nr * 4), o_hl = slab.add((size_t)nr), o_hr = slab.add((size_t)nr);
-  size_t o_need = 0, o_nal = 0, o_alen = 0, o_ci = 0, o_nsp = 0, o_cls = 0, o_rank = 0, o_nspan = 0, o_toff = 0, o_flip = 0, o_gsz = 0, o_rpc = 0, o_skipb = 0, o_clc = 0;
+  size_t o_need = 0, o_nal = 0, o_alen = 0, o_ci = 0, o_nsp = 0, o_cls = 0, o_rank = 0, o_nspan = 0, o_toff = 0, o_flip = 0, o_gsz = 0, o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0;
   if (dev_gt) {
     o_need = slab.add((size_t)nl); o_nal = slab.add((size_t)nl * 4); o_alen = slab.add(2 * (size_t)nl * 4); o_ci = slab.add(4 * (size_t)nl * 4);
     o_nsp = slab.add(2 * (size_t)nl * 4); o_cls = slab.add((size_t)nr * 4); o_rank = slab.add((size_t)nr * 4); o_nspan = slab.add((size_t)nl * 4);
     o_toff = slab.add((2 * (size_t)nl + 1) * 8); o_flip = slab.add((size_t)nl);
-    o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4);
+    o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
   }
   void *d_slab = nullptr, *h_slab = nullptr;
   if ((rc = dev_get(c, S_LOCUS_4, slab.total, &d_slab)) || (rc = pin_get(c, P_SPAN_S, slab.total, &h_slab))) return rc;
@@ -715,9 +717,11 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
          *toff = nullptr, *packed = nullptr;
     const double* rq = nullptr;
   } g;
-  std::vector<uint32_t> cl_list; std::vector<uint64_t> cl_moff;
-  uint64_t cl_pairs = 0, cl_reads = 0; uint32_t cl_max_nr = 0;
-  const uint32_t* d_cl_list = nullptr; const uint64_t* d_cl_moff = nullptr;
+  // the cluster loci of the call: [0] the shallow list (at most GT_MAX_READS reads: the one-wave chain), [1] the deep list (beyond that,
+  // up to the context's cluster_max_reads: locus_cluster_deep.hpp), each with its own pair slots, job lists, arenas and counters
+  struct ClPlan { std::vector<uint32_t> list; std::vector<uint64_t> moff; uint64_t pairs = 0, reads = 0; uint32_t max_nr = 0; const uint32_t* d_list = nullptr; const uint64_t* d_moff = nullptr; } clp[2];
+  std::vector<uint32_t>& cl_list = clp[0].list; std::vector<uint32_t>& cld_list = clp[1].list;
+  uint32_t cld_no_room = 0;  // deep loci inside the envelope that found no room in the call's budget (host path, stats[23])
   struct GtHost { void *need = nullptr, *nal = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr, *toff = nullptr, *packed = nullptr; } gh;
   if (dev_gt) {
     if ((rc = dev_in(c, S_GT_LRB, in->locus_read_begin, (size_t)nl + 1, &g.lrb, &ub)) || (rc = dev_in(c, S_GT_PLOIDY, in->ploidy, (size_t)nl, &g.ploidy, &ub)) ||
@@ -730,16 +734,33 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     // Genotyper::Cluster loci stay on the device too (locus_cluster_dev.hpp) unless TRGT_HOST_CLUSTER / TRGT_SPLIT_HMM say otherwise: the
     // list of them and the first pair slot of each (condensed distance matrix, sized for all reads of the locus)
     if (in->genotyper && !c->knobs.host_cluster && !c->knobs.split_hmm) {
+      // budget of the deep list: an eighth of the context's workspace limit, at most 2 GB (64 loci of 600 reads take 0.7 GB, one of 2 048
+      // reads 0.13 GB); TRGT_CLUSTER_ARENA_KB, the developer switch that shrinks the arenas, shrinks it to 64 times that many KB
+      const uint64_t cl_deep_pair_bytes = sizeof(JobDev) + 4 + 8;
+      uint64_t cl_deep_budget = std::min<uint64_t>(c->ws_limit / 8, 2ull << 30);
+      if (c->knobs.cluster_arena_kb > 0) cl_deep_budget = std::min<uint64_t>(cl_deep_budget, (uint64_t)c->knobs.cluster_arena_kb << 16);
       for (int64_t l = 0; l < nl; ++l) {
         if (in->genotyper[l] != 1 || in->ploidy[l] == 0) continue;
         const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
-        if (n == 0 || n > (uint64_t)gt::GT_MAX_READS) continue;
-        cl_list.push_back((uint32_t)l); cl_moff.push_back(cl_pairs);
-        cl_pairs += n * (n - 1) / 2; cl_reads += n; cl_max_nr = std::max(cl_max_nr, (uint32_t)n);
+        if (n == 0) continue;
+        if (n > (uint64_t)gt::GT_MAX_READS) {
+          // the deep list: admitted in catalog order while the pair slots (32-bit output indices) and the call's budget last -- per pair an
+          // edit-distance job, a score and a matrix entry; the per-read lists are sized by the batch.  No room: the host path, as before.
+          if (n > (uint64_t)c->cluster_max_reads) continue;
+          const uint64_t np = n * (n - 1) / 2;
+          if (clp[1].pairs + np > 0x7FFFFFF0ull || (clp[1].pairs + np) * cl_deep_pair_bytes > cl_deep_budget) { ++cld_no_room; continue; }
+          clp[1].list.push_back((uint32_t)l); clp[1].moff.push_back(clp[1].pairs);
+          clp[1].pairs += np; clp[1].reads += n; clp[1].max_nr = std::max(clp[1].max_nr, (uint32_t)n);
+          continue;
+        }
+        clp[0].list.push_back((uint32_t)l); clp[0].moff.push_back(clp[0].pairs);
+        clp[0].pairs += n * (n - 1) / 2; clp[0].reads += n; clp[0].max_nr = std::max(clp[0].max_nr, (uint32_t)n);
       }
-      if (cl_pairs > 0x7FFFFFF0ull) { cl_list.clear(); cl_moff.clear(); }  // (pair slots are 32-bit output indices: the host path takes such a batch)
-      if (!cl_list.empty() && ((rc = dev_in(c, S_CL_LIST, cl_list.data(), cl_list.size(), &d_cl_list, &ub)) || (rc = dev_in(c, S_CL_MOFF, cl_moff.data(), cl_moff.size(), &d_cl_moff, &ub))))
-        return rc;
+      if (clp[0].pairs > 0x7FFFFFF0ull) { clp[0].list.clear(); clp[0].moff.clear(); }  // (pair slots are 32-bit output indices: the host path takes such a batch)
+      for (int d = 0; d < 2; ++d)
+        if (!clp[d].list.empty() && ((rc = dev_in(c, d ? S_CLD_LIST : S_CL_LIST, clp[d].list.data(), clp[d].list.size(), &clp[d].d_list, &ub)) ||
+                                     (rc = dev_in(c, S_CL_MOFF + (d ? (int)S_CLD_LIST - (int)S_CL_LIST : 0), clp[d].moff.data(), clp[d].moff.size(), &clp[d].d_moff, &ub))))
+          return rc;
     }
     g.need = dsl(o_need); g.nal = dsl(o_nal); g.alen = dsl(o_alen); g.ci = dsl(o_ci); g.nsp = dsl(o_nsp); g.cls = dsl(o_cls); g.rank = dsl(o_rank);
     g.nspan = dsl(o_nspan); g.toff = dsl(o_toff);
@@ -797,7 +818,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   if (use_slots) {
     hs.n_loci = nl; hs.cap = out->allele_cap; hs.seq_off = out->allele_off; hs.seq_blob_dev = (const uint8_t*)g.blob;
     hs.d_n_alleles = (const int32_t*)g.nal; hs.d_allele_len = (const uint32_t*)g.alen;
-    if (in->genotyper && cl_list.empty()) { slot_skip.assign(in->genotyper, in->genotyper + nl); for (auto& v : slot_skip) v = v == 1; hs.host_skip = slot_skip.data(); }
+    if (in->genotyper && cl_list.empty() && cld_list.empty()) { slot_skip.assign(in->genotyper, in->genotyper + nl); for (auto& v : slot_skip) v = v == 1; hs.host_skip = slot_skip.data(); }
   }
   if (dev_gt) {
     gt::GtArgs ga;
@@ -816,7 +837,23 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     std::memset(&rp, 0, sizeof rp);
     void *d_vout = nullptr, *d_vlen = nullptr, *d_vscr = nullptr, *d_rcig = nullptr, *d_rclen = nullptr;
     const bool dev_repair = !c->knobs.host_repair;
-    const uint32_t* cl_counts_dev = nullptr;  // count block of the device-side cluster genotyper, when it runs
+    const uint32_t* cl_counts_dev[2] = {nullptr, nullptr};  // count blocks of the device-side cluster genotyper (shallow, deep list), when it runs
+    // the deep list's selection: its lists and merge records are per read of the batch, like ClArgs::cls (one slab); with the purity
+    // filter on, its select / filter kernels run next to the shallow ones below and share their purity batch
+    cld::DeepArgs da;
+    std::memset(&da, 0, sizeof da);
+    if (!cld_list.empty()) {
+      size_t dt = 0;
+      auto dadd = [&](size_t bytes) { const size_t o = dt; dt += (bytes + 255) & ~(size_t)255; return o; };
+      const size_t do_read = dadd((size_t)nr * 4), do_start = dadd((size_t)nr * 4), do_len = dadd((size_t)nr * 4), do_job = dadd((size_t)nr * 4), do_n = dadd(cld_list.size() * 4),
+                   do_ma = dadd((size_t)nr * 2), do_mb = dadd((size_t)nr * 2), do_md = dadd((size_t)nr * 8);
+      void* d_ds = nullptr;
+      if ((rc = dev_get(c, S_CLD_SEL, dt, &d_ds))) return rc;
+      auto dsl2 = [&](size_t o) { return (void*)((uint8_t*)d_ds + o); };
+      da.sel_read = (uint32_t*)dsl2(do_read); da.sel_start = (uint32_t*)dsl2(do_start); da.sel_len = (uint32_t*)dsl2(do_len); da.sel_job = (uint32_t*)dsl2(do_job);
+      da.n_sel = (uint32_t*)dsl2(do_n); da.mg_a = (uint16_t*)dsl2(do_ma); da.mg_b = (uint16_t*)dsl2(do_mb); da.mg_d = (double*)dsl2(do_md);
+      da.c.list = clp[1].d_list; da.c.n_list = (uint32_t)cld_list.size();
+    }
     if (dev_repair) {
       void* const z_rpc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
       if (z_rpc) rp.counts = (uint32_t*)z_rpc;
@@ -866,6 +903,10 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       const dim3 pgrid((unsigned)nl);
       if (small_gt) hipLaunchKernelGGL((pur::purity_select_kernel<64>), pgrid, dim3(64), 0, c->stream, ga, pa);
       else hipLaunchKernelGGL((pur::purity_select_kernel<gt::GT_MAX_READS>), pgrid, dim3(64), 0, c->stream, ga, pa);
+      if (!cld_list.empty()) {  // (behind the shallow selection: it leaves the deep loci alone, and both append to one job list)
+        da.c.g = ga; da.purity_on = 1; da.read_qual = pa.read_qual; da.pj_counter = pa.counter; da.pj = pa.jobs; da.pj_cap = pa.cap_jobs; da.purity = pa.purity;
+        hipLaunchKernelGGL(cld::deep_select_kernel, dim3(da.c.n_list), dim3(cld::DW), 0, c->stream, da);
+      }
       TRGT_HIP_TRY(c, hipGetLastError());
       *(uint32_t*)h_pj = 0;
       { const int d2h_rc = trgt::d2h(c, h_pj, pa.counter, 4, c->stream); if (d2h_rc) return d2h_rc; }
@@ -898,6 +939,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       }
       if (small_gt) hipLaunchKernelGGL((pur::purity_filter_kernel<64>), pgrid, dim3(64), 0, c->stream, ga, pa);
       else hipLaunchKernelGGL((pur::purity_filter_kernel<gt::GT_MAX_READS>), pgrid, dim3(64), 0, c->stream, ga, pa);
+      if (!cld_list.empty()) hipLaunchKernelGGL(cld::deep_filter_kernel, dim3(da.c.n_list), dim3(cld::DW), 0, c->stream, da);
       TRGT_HIP_TRY(c, hipGetLastError());
       ga.sel_read = pa.sel_read; ga.sel_start = pa.sel_start; ga.sel_len = pa.sel_len; ga.n_sel = pa.n_sel;
       if (small_gt) hipLaunchKernelGGL((gt::locus_genotype_kernel<64, 8 * 1024, true>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
@@ -994,15 +1036,18 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_rp, 0));
       }
     }
-    if (!cl_list.empty()) {
+    for (int deep = 0; deep < 2; ++deep) {
+      if (clp[deep].list.empty()) continue;
+      const uint64_t cl_pairs = clp[deep].pairs, cl_reads = clp[deep].reads;
+      const int so = deep ? (int)S_CLD_LIST - (int)S_CL_LIST : 0;  // the deep list's buffers: the same slots, second set
       // ---- Genotyper::Cluster on the device (locus_cluster_dev.hpp): pair list -> edit distances -> linkage / groups / backbones ->
       //      consensus round -> redo or dropped reads -> second round + edit distances -> genotype.  Four alignment launches and two
       //      votes, most of them over empty lists after the first round; nothing waits for the host.
-      const uint32_t n_cl = (uint32_t)cl_list.size();
+      const uint32_t n_cl = (uint32_t)clp[deep].list.size();
       const uint32_t max_seg = max_read_len > 2u * (uint32_t)F ? max_read_len - 2u * (uint32_t)F : 1u;
       cl::ClArgs ca;
       std::memset(&ca, 0, sizeof ca);
-      ca.g = ga; ca.list = d_cl_list; ca.n_list = n_cl; ca.mat_off = d_cl_moff;
+      ca.g = ga; ca.list = clp[deep].d_list; ca.n_list = n_cl; ca.mat_off = clp[deep].d_moff;
       ca.flags = (c->knobs.sens_ward_ties ? 1u : 0u) | (c->knobs.sens_lw_order ? 2u : 0u);
       ca.cap_j = (uint32_t)cl_reads; ca.cap_g = 2 * n_cl; ca.vote_lds_pos = (uint32_t)vote::VOTE_LDS_POS;
       // arenas for two consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
@@ -1013,16 +1058,16 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         const uint64_t kb = (uint64_t)c->knobs.cluster_arena_kb;
         ca.cap_cigar = std::min<uint64_t>(ca.cap_cigar, kb * 256); ca.cap_out = std::min<uint64_t>(ca.cap_out, kb * 1024); ca.cap_scratch = std::min<uint64_t>(ca.cap_scratch, kb * 256);
       }
-      const bool big = cl_max_nr > 64;
+      const bool big = clp[deep].max_nr > 64;
       void *d_cnt = nullptr, *d_rec = nullptr, *d_cls = nullptr, *d_es = nullptr, *d_gm = nullptr, *d_edj = nullptr, *d_j = nullptr, *d_g = nullptr, *d_ed2 = nullptr, *d_es2 = nullptr,
            *d_cig = nullptr, *d_clen = nullptr, *d_vout = nullptr, *d_vlen = nullptr, *d_vscr = nullptr;
-      if ((rc = dev_get(c, S_CL_COUNTS, 256, &d_cnt)) || (rc = dev_get(c, S_CL_REC, (size_t)n_cl * sizeof(cl::ClRec), &d_rec)) || (rc = dev_get(c, S_CL_CLS, (size_t)nr + 16, &d_cls)) ||
-          (rc = dev_get(c, S_CL_ESCORE, (size_t)cl_pairs * 4 + 16, &d_es)) || (big && (rc = dev_get(c, S_CL_GMAT, (size_t)cl_pairs * 8 + 16, &d_gm))) ||
-          (rc = dev_get(c, S_CL_EDJOBS, (size_t)cl_pairs * sizeof(JobDev) + 16, &d_edj)) || (rc = dev_get(c, S_CL_JOBS, 2 * (size_t)ca.cap_j * sizeof(JobDev), &d_j)) ||
-          (rc = dev_get(c, S_CL_GROUPS, 2 * (size_t)ca.cap_g * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, S_CL_ED2JOBS, 2 * (size_t)cl_reads * sizeof(JobDev), &d_ed2)) ||
-          (rc = dev_get(c, S_CL_ESCORE2, 2 * (size_t)nr * 4 + 16, &d_es2)) || (rc = dev_get(c, S_CL_CIGAR, (size_t)ca.cap_cigar * 4, &d_cig)) ||
-          (rc = dev_get(c, S_CL_CLEN, 2 * (size_t)ca.cap_j * 4, &d_clen)) || (rc = dev_get(c, S_CL_VOUT, (size_t)ca.cap_out + 16, &d_vout)) ||
-          (rc = dev_get(c, S_CL_VLEN, 2 * (size_t)ca.cap_g * 4, &d_vlen)) || (rc = dev_get(c, S_CL_VSCR, (size_t)ca.cap_scratch * 4 + 16, &d_vscr)))
+      if ((rc = dev_get(c, S_CL_COUNTS + so, 256, &d_cnt)) || (rc = dev_get(c, S_CL_REC + so, (size_t)n_cl * sizeof(cl::ClRec), &d_rec)) || (rc = dev_get(c, S_CL_CLS + so, (size_t)nr + 16, &d_cls)) ||
+          (rc = dev_get(c, S_CL_ESCORE + so, (size_t)cl_pairs * 4 + 16, &d_es)) || (big && (rc = dev_get(c, S_CL_GMAT + so, (size_t)cl_pairs * 8 + 16, &d_gm))) ||
+          (rc = dev_get(c, S_CL_EDJOBS + so, (size_t)cl_pairs * sizeof(JobDev) + 16, &d_edj)) || (rc = dev_get(c, S_CL_JOBS + so, 2 * (size_t)ca.cap_j * sizeof(JobDev), &d_j)) ||
+          (rc = dev_get(c, S_CL_GROUPS + so, 2 * (size_t)ca.cap_g * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, S_CL_ED2JOBS + so, 2 * (size_t)cl_reads * sizeof(JobDev), &d_ed2)) ||
+          (rc = dev_get(c, S_CL_ESCORE2 + so, 2 * (size_t)nr * 4 + 16, &d_es2)) || (rc = dev_get(c, S_CL_CIGAR + so, (size_t)ca.cap_cigar * 4, &d_cig)) ||
+          (rc = dev_get(c, S_CL_CLEN + so, 2 * (size_t)ca.cap_j * 4, &d_clen)) || (rc = dev_get(c, S_CL_VOUT + so, (size_t)ca.cap_out + 16, &d_vout)) ||
+          (rc = dev_get(c, S_CL_VLEN + so, 2 * (size_t)ca.cap_g * 4, &d_vlen)) || (rc = dev_get(c, S_CL_VSCR + so, (size_t)ca.cap_scratch * 4 + 16, &d_vscr)))
         return rc;
       void* const z_clc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
       ca.counts = z_clc ? (uint32_t*)z_clc : (uint32_t*)d_cnt; ca.rec = (cl::ClRec*)d_rec; ca.cls = (int8_t*)d_cls; ca.escore = (int32_t*)d_es; ca.gmat = (double*)d_gm;
@@ -1031,7 +1076,12 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       if (!z_clc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, ca.counts, (uint32_t)cl::CC_WORDS);
       const dim3 cgrid(n_cl);
       // (with filter_impure_trs on: the instantiations that load the filtered lists, like the length genotyper's)
-      if (presel) {
+      if (deep) {  // (one workgroup per locus; the selection ran above when the purity filter is on)
+        da.c = ca;
+        if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+        hipLaunchKernelGGL(cld::deep_front_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+      }
+      else if (presel) {
         if (big) hipLaunchKernelGGL((cl::cluster_front_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
         else hipLaunchKernelGGL((cl::cluster_front_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
       }
@@ -1069,7 +1119,11 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         return TRGT_OK;
       };
       if ((rc = ed_launch(ca.ed_jobs, cl_pairs, ca.counts + cl::CC_ED, d_reads, ca.escore))) return rc;
-      if (presel) {
+      if (deep) {
+        hipLaunchKernelGGL(cld::deep_linkage_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+        hipLaunchKernelGGL(cld::deep_groups_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+      }
+      else if (presel) {
         if (big) hipLaunchKernelGGL((cl::cluster_ward_kernel<gt::GT_MAX_READS, false, true>), cgrid, dim3(64), 0, c->stream, ca);
         else hipLaunchKernelGGL((cl::cluster_ward_kernel<64, true, true>), cgrid, dim3(64), 0, c->stream, ca);
       }
@@ -1077,7 +1131,8 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       else hipLaunchKernelGGL((cl::cluster_ward_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
       TRGT_HIP_TRY(c, hipGetLastError());
       if ((rc = cons_launch(0, ca.counts + cl::CC_J1, 0, ca.counts + cl::CC_G1))) return rc;
-      if (presel) {
+      if (deep) hipLaunchKernelGGL(cld::deep_round2_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+      else if (presel) {
         if (big) hipLaunchKernelGGL((cl::cluster_round2_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
         else hipLaunchKernelGGL((cl::cluster_round2_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
       }
@@ -1086,18 +1141,19 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       TRGT_HIP_TRY(c, hipGetLastError());
       if ((rc = cons_launch(ca.cap_j, ca.counts + cl::CC_J2, ca.cap_g, ca.counts + cl::CC_G2))) return rc;
       if ((rc = ed_launch(ca.ed2_jobs, 2 * cl_reads, ca.counts + cl::CC_ED2, (const uint8_t*)d_vout, ca.escore2))) return rc;
-      if (presel) {
+      if (deep) hipLaunchKernelGGL(cld::deep_finish_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+      else if (presel) {
         if (big) hipLaunchKernelGGL((cl::cluster_finish_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
         else hipLaunchKernelGGL((cl::cluster_finish_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
       }
       else if (big) hipLaunchKernelGGL((cl::cluster_finish_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
       else hipLaunchKernelGGL((cl::cluster_finish_kernel<64>), cgrid, dim3(64), 0, c->stream, ca);
       TRGT_HIP_TRY(c, hipGetLastError());
-      tl_mark(c, "cluster chain enqueued");
-      cl_counts_dev = ca.counts;
+      tl_mark(c, deep ? "deep cluster chain enqueued" : "cluster chain enqueued");
+      cl_counts_dev[deep] = ca.counts;
     }
     // (the count blocks come back with the slab)
-    const CountCopy cc{dev_repair ? rp.counts : nullptr, (uint32_t*)dsl(o_rpc), (uint32_t)gt::RC_WORDS, cl_counts_dev, (uint32_t*)dsl(o_clc), (uint32_t)cl::CC_WORDS};
+    const CountCopy cc{dev_repair ? rp.counts : nullptr, (uint32_t*)dsl(o_rpc), (uint32_t)gt::RC_WORDS, cl_counts_dev[0], (uint32_t*)dsl(o_clc), (uint32_t)cl::CC_WORDS, cl_counts_dev[1], (uint32_t*)dsl(o_cldc), (uint32_t)cl::CC_WORDS};
     hipLaunchKernelGGL(allele_prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)g.alen, (uint64_t*)g.toff, (int64_t)(2 * nl), cc);
     hipLaunchKernelGGL(allele_pack_kernel, dim3((unsigned)((2 * nl + 3) / 4)), dim3(256), 0, c->stream, (const uint8_t*)g.blob, g.al_off,
                        (const uint32_t*)g.alen, (const uint64_t*)g.toff, (uint8_t*)g.packed, (int64_t)(2 * nl));
@@ -1139,7 +1195,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     const uint8_t* skip_b = (const uint8_t*)hsl(o_skipb);
     if (hmm_pendingB) need_a.assign(need, need + nl);
     for (int64_t l = 0; l < nl; ++l) if (need[l] == 2) need[l] = skip_b[l] ? 1 : 0;  // repaired on the device, or back to the host path after all
-    if (in->genotyper && cl_list.empty()) for (int64_t l = 0; l < nl; ++l) if (in->genotyper[l] == 1) need[l] = 1;  // Genotyper::Cluster: host-driven rounds (else: genotyped by the device chain, need_host = 0)
+    if (in->genotyper && cl_list.empty() && cld_list.empty()) for (int64_t l = 0; l < nl; ++l) if (in->genotyper[l] == 1) need[l] = 1;  // Genotyper::Cluster: host-driven rounds (else: genotyped by the device chain, need_host = 0)
     if (flank_on) {
       // device-genotyped loci whose two alleles are at most 10 bases apart and whose reads DO split by haplotype tag or flank SNVs
       // take the host path, where the genotype is replaced (genotype_flank below); the split only needs the per-read fields
@@ -1156,10 +1212,10 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     for (int64_t l = 0; l < nl; ++l) if (need[l]) R.push_back(l);
     // an alignment job of a device-built list that the generic kernel refused (longer than the workspace planned from the batch's maxima)
     // left INT32_MIN / an empty CIGAR behind: nothing downstream may use that -- the call fails (never seen in the sweeps)
-    if (const uint32_t refused = ((const uint32_t*)hsl(o_rpc))[gt::RC_REFUSED] + ((const uint32_t*)hsl(o_clc))[cl::CC_REFUSED])
+    if (const uint32_t refused = ((const uint32_t*)hsl(o_rpc))[gt::RC_REFUSED] + ((const uint32_t*)hsl(o_clc))[cl::CC_REFUSED] + ((const uint32_t*)hsl(o_cldc))[cl::CC_REFUSED])
       return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_locus_batch: %u alignment job(s) of the device-side genotyper chains exceed the planned workspace", refused);
     stat_cons_jobs += (int64_t)((const uint32_t*)hsl(o_rpc))[gt::RC_JOBS];  // consensus alignments of the device-side repair
-    { const uint32_t* cc = (const uint32_t*)hsl(o_clc);  // ... and of the device-side cluster genotyper, with its edit distances
+    for (const size_t o_cc : {o_clc, o_cldc}) { const uint32_t* cc = (const uint32_t*)hsl(o_cc);  // ... and of the device-side cluster genotyper (both lists), with its edit distances
       stat_cons_jobs += (int64_t)cc[cl::CC_J1] + (int64_t)cc[cl::CC_J2]; stat_ed_jobs += (int64_t)cc[cl::CC_ED] + (int64_t)cc[cl::CC_ED2]; }
   }
   else { R.resize((size_t)nl); for (int64_t l = 0; l < nl; ++l) R[(size_t)l] = l; }
@@ -1694,7 +1750,8 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     for (int i = 18; i < 24; ++i) s[i] = 0;
     s[21] = (int64_t)((uint64_t*)h_cells)[2];  // light fallback alignments settled by the substitution shortcut of the window search
     if (dev_gt) { const uint32_t* rc_ = (const uint32_t*)hsl(o_rpc); s[18] = rc_[gt::RC_LOCI]; s[19] = rc_[gt::RC_FAILED]; s[20] = rc_[gt::RC_JOBS];  // device-side consensus repair: loci, loci without room, alignments
-      const uint32_t* cc = (const uint32_t*)hsl(o_clc); s[22] = cc[cl::CC_DONE]; s[23] = cc[cl::CC_FAILED]; }  // device-side cluster genotyper: loci genotyped, loci handed to the host path
+      const uint32_t* cc = (const uint32_t*)hsl(o_clc); const uint32_t* cd = (const uint32_t*)hsl(o_cldc);
+      s[22] = (int64_t)cc[cl::CC_DONE] + cd[cl::CC_DONE]; s[23] = (int64_t)cc[cl::CC_FAILED] + cd[cl::CC_FAILED] + cld_no_room; }  // device-side cluster genotyper: loci genotyped, loci handed to the host path
   }
   return TRGT_OK;
 }
@@ -1704,6 +1761,16 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   try { return (call); }                                                                           \
   catch (const std::bad_alloc&) { return trgt::fail((ctx), TRGT_ERR_NOMEM, "out of host memory"); } \
   catch (const std::exception& e) { return trgt::fail((ctx), TRGT_ERR_INVALID, "unexpected exception: %s", e.what()); }
+
+// ---- the deep instantiation of the device-side cluster genotyper is opt-in per context (include/trgt_hip.h)
+extern "C" int32_t trgt_hip_cluster_max_reads_limit(void) { return cld::CL_DEEP_MAX_READS; }
+extern "C" int trgt_hip_set_cluster_max_reads(trgt_hip_ctx* c, int32_t max_reads) {
+  if (!c) return TRGT_ERR_INVALID;
+  if (max_reads < gt::GT_MAX_READS || max_reads > cld::CL_DEEP_MAX_READS)
+    return fail(c, TRGT_ERR_INVALID, "trgt_hip_set_cluster_max_reads: %d is outside [%d, %d]", (int)max_reads, gt::GT_MAX_READS, cld::CL_DEEP_MAX_READS);
+  c->cluster_max_reads = max_reads;
+  return TRGT_OK;
+}
 
 extern "C" int trgt_locus_batch(trgt_hip_ctx* c, const trgt_locus_params* p, const trgt_locus_batch_in* in, trgt_locus_batch_out* out) {
   TRGT_ABI_GUARD(c, locus_batch_run(c, p, in, out, nullptr, nullptr, nullptr));
