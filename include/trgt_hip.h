@@ -87,6 +87,19 @@ int trgt_hip_set_workspace_limit(trgt_hip_ctx* ctx, uint64_t bytes);
  * [256, limit]: TRGT_ERR_INVALID, the setting stays.  The contexts of a pool are set one by one through trgt_hip_pool_context. */
 int32_t trgt_hip_cluster_max_reads_limit(void);
 int trgt_hip_set_cluster_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
+/* Genotyper::Size (genotype_size.rs:6-64, diploid.rs:5-103, haploid.rs:3-30, consensus.rs:113-154; the reference's default genotyper)
+ * on the device for deep loci.  By default the device genotyper takes size loci of at most 256 candidate reads and deeper ones -- with
+ * the reference's default --max-depth 250 the reservoir hands over up to 750 -- go through the host path.  A context set to
+ * max_reads > 256 also keeps size loci with 256 < reads <= max_reads on the device (one workgroup per locus, locus_gt_deep.hpp); a locus
+ * whose pick lacks majority support joins the call's device-side consensus repair, and one that finds no room there, has a segment
+ * beyond the repair's longest or an allele beyond allele_cap takes the host path.  Results are the same either way.
+ * trgt_hip_size_max_reads_limit: the compiled ceiling (2048), no GPU needed.  max_reads outside [256, limit]: TRGT_ERR_INVALID, the
+ * setting stays.  trgt_hip_size_deep_stats: of the context's last trgt_locus_batch -- out[0] deep size loci genotyped on the device,
+ * out[1] those among them that went through the repair, out[2] deep size loci inside the setting that were handed to the host path,
+ * out[3] reserved (0).  The contexts of a pool are set and asked one by one through trgt_hip_pool_context. */
+int32_t trgt_hip_size_max_reads_limit(void);
+int trgt_hip_set_size_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
+int trgt_hip_size_deep_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
 
 /* ---- kernel timing (HIP events on the ctx stream, for bench.py's roofline) ---- */
 #define TRGT_K_FLANK_SCAN 0   /* exact flank search (+ the segment search for the seeded windows of the fallback alignments) */

@@ -72,7 +72,7 @@ class LocusBatchOut(C.Structure):
 EXPORTS = [
     "trgt_inflate_raw", "trgt_inflate_blocks", "trgt_deflate_blocks",
     "trgt_hip_abi_version", "trgt_hip_create", "trgt_hip_destroy", "trgt_hip_last_error", "trgt_hip_set_stream",
-    "trgt_hip_set_workspace_limit", "trgt_hip_cluster_max_reads_limit", "trgt_hip_set_cluster_max_reads", "trgt_hip_timing_enable", "trgt_hip_timing_reset", "trgt_hip_timing_get",
+    "trgt_hip_set_workspace_limit", "trgt_hip_cluster_max_reads_limit", "trgt_hip_set_cluster_max_reads", "trgt_hip_size_max_reads_limit", "trgt_hip_set_size_max_reads", "trgt_hip_size_deep_stats", "trgt_hip_timing_enable", "trgt_hip_timing_reset", "trgt_hip_timing_get",
     "trgt_wfa_default_params", "trgt_wfa_batch", "trgt_flank_filter_batch", "trgt_find_spans_batch", "trgt_hmm_batch", "trgt_hmm_path_capacity", "trgt_hmm_models_check",
     "trgt_locus_batch", "trgt_locus_batch_submit", "trgt_locus_batch_wait", "trgt_locus_default_params", "trgt_reads_pack_bam4",
     "trgt_hip_pool_create", "trgt_hip_pool_destroy", "trgt_hip_pool_size", "trgt_hip_pool_context", "trgt_hip_pool_last_error", "trgt_locus_batch_many",
@@ -123,6 +123,10 @@ def lib():
         L.trgt_hip_cluster_max_reads_limit.argtypes = []
         L.trgt_hip_cluster_max_reads_limit.restype = C.c_int32
         L.trgt_hip_set_cluster_max_reads.argtypes = [_VP, C.c_int32]
+        L.trgt_hip_size_max_reads_limit.argtypes = []
+        L.trgt_hip_size_max_reads_limit.restype = C.c_int32
+        L.trgt_hip_set_size_max_reads.argtypes = [_VP, C.c_int32]
+        L.trgt_hip_size_deep_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_timing_enable.argtypes = [_VP, C.c_int]
         L.trgt_hip_timing_reset.argtypes = [_VP]
         L.trgt_hip_timing_get.argtypes = [_VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -177,6 +181,18 @@ class Context:
         one-wave chain only; up to cluster_max_reads_limit(): the deep chain as well).  Every later call on this context uses it."""
         self.check(lib().trgt_hip_set_cluster_max_reads(self.handle, int(n)))
 
+    def set_size_max_reads(self, n):
+        """trgt_hip_set_size_max_reads: Genotyper::Size loci of up to n candidate reads stay on the device (256, the default: the one-wave
+        genotyper only; up to size_max_reads_limit(): the workgroup-wide one as well).  Every later call on this context uses it."""
+        self.check(lib().trgt_hip_set_size_max_reads(self.handle, int(n)))
+
+    def size_deep_stats(self):
+        """trgt_hip_size_deep_stats of the context's last trgt_locus_batch: (deep size loci genotyped on the device, those among them that
+        went through the consensus repair, deep size loci inside the setting handed to the host path, 0)."""
+        out = (C.c_int64 * 4)()
+        self.check(lib().trgt_hip_size_deep_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def timing_enable(self, on=True):
         self.check(lib().trgt_hip_timing_enable(self.handle, int(on)))
 
@@ -203,7 +219,7 @@ class Context:
 class Pool:
     """trgt_hip_pool: several contexts (devices[i] = ordinal of context i, ordinals may repeat) behind one queue of batches."""
 
-    def __init__(self, devices, cluster_max_reads=None):
+    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None):
         L = lib()
         L.trgt_hip_pool_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
         L.trgt_hip_pool_destroy.argtypes = [C.c_void_p]
@@ -230,6 +246,9 @@ class Pool:
         if cluster_max_reads is not None:  # (a setting of the contexts: each of the pool's gets it)
             for c in self.contexts:
                 c.set_cluster_max_reads(cluster_max_reads)
+        if size_max_reads is not None:
+            for c in self.contexts:
+                c.set_size_max_reads(size_max_reads)
 
     def run_many(self, params_struct, cins, couts, out_per_context=False):
         """cins / couts: lists of LocusBatchIn / LocusBatchOut structures (couts: one per batch, or one per context)"""
@@ -310,6 +329,11 @@ def context_with_env(device=0, **env):
 def cluster_max_reads_limit():
     """trgt_hip_cluster_max_reads_limit: the deepest cluster locus the device chains can be set to take (no GPU needed)."""
     return int(lib().trgt_hip_cluster_max_reads_limit())
+
+
+def size_max_reads_limit():
+    """trgt_hip_size_max_reads_limit: the deepest size locus the device genotypers can be set to take (no GPU needed)."""
+    return int(lib().trgt_hip_size_max_reads_limit())
 
 
 def context(device=0):

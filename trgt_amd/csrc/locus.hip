@@ -34,6 +34,7 @@
 #include "locus_purity.hpp"
 #include "locus_cluster_dev.hpp"
 #include "locus_cluster_deep.hpp"
+#include "locus_gt_deep.hpp"
 #include "wfa_host.hpp"
 
 namespace trgt {
@@ -544,6 +545,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   if (!p || !in || !out) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: null argument");
   const int64_t nl = in->n_loci;
   if (nl < 0) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: negative n_loci");
+  for (int64_t& v : c->size_deep_stats) v = 0;
   if (nl == 0) return TRGT_OK;
   if (!in->flank_blob || !in->lf_off || !in->lf_len || !in->rf_off || !in->rf_len || !in->tr_blob || !in->tr_off || !in->tr_len ||
       !in->motif_blob || !in->motif_off || !in->set_motif_begin || !in->ploidy || !in->locus_read_begin || !in->read_blob ||
@@ -722,6 +724,8 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   struct ClPlan { std::vector<uint32_t> list; std::vector<uint64_t> moff; uint64_t pairs = 0, reads = 0; uint32_t max_nr = 0; const uint32_t* d_list = nullptr; const uint64_t* d_moff = nullptr; } clp[2];
   std::vector<uint32_t>& cl_list = clp[0].list; std::vector<uint32_t>& cld_list = clp[1].list;
   uint32_t cld_no_room = 0;  // deep loci inside the envelope that found no room in the call's budget (host path, stats[23])
+  // the deep size list: Genotyper::Size loci beyond GT_MAX_READS reads, up to the context's size_max_reads (locus_gt_deep.hpp)
+  std::vector<uint32_t> gsd_list; const uint32_t* d_gsd_list = nullptr;
   struct GtHost { void *need = nullptr, *nal = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr, *toff = nullptr, *packed = nullptr; } gh;
   if (dev_gt) {
     if ((rc = dev_in(c, S_GT_LRB, in->locus_read_begin, (size_t)nl + 1, &g.lrb, &ub)) || (rc = dev_in(c, S_GT_PLOIDY, in->ploidy, (size_t)nl, &g.ploidy, &ub)) ||
@@ -761,6 +765,15 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         if (!clp[d].list.empty() && ((rc = dev_in(c, d ? S_CLD_LIST : S_CL_LIST, clp[d].list.data(), clp[d].list.size(), &clp[d].d_list, &ub)) ||
                                      (rc = dev_in(c, S_CL_MOFF + (d ? (int)S_CLD_LIST - (int)S_CL_LIST : 0), clp[d].moff.data(), clp[d].moff.size(), &clp[d].d_moff, &ub))))
           return rc;
+    }
+    // (not under TRGT_SPLIT_HMM: its first HMM batch reads need_host right behind the one-wave genotyper, before the deep kernels have spoken)
+    if (c->size_max_reads > gt::GT_MAX_READS && !c->knobs.split_hmm) {
+      for (int64_t l = 0; l < nl; ++l) {
+        if (is_cluster(l) || in->ploidy[l] == 0) continue;
+        const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
+        if (n > (uint64_t)gt::GT_MAX_READS && n <= (uint64_t)c->size_max_reads) gsd_list.push_back((uint32_t)l);
+      }
+      if (!gsd_list.empty() && (rc = dev_in(c, S_GSD_LIST, gsd_list.data(), gsd_list.size(), &d_gsd_list, &ub))) return rc;
     }
     g.need = dsl(o_need); g.nal = dsl(o_nal); g.alen = dsl(o_alen); g.ci = dsl(o_ci); g.nsp = dsl(o_nsp); g.cls = dsl(o_cls); g.rank = dsl(o_rank);
     g.nspan = dsl(o_nspan); g.toff = dsl(o_toff);
@@ -840,12 +853,12 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     const uint32_t* cl_counts_dev[2] = {nullptr, nullptr};  // count blocks of the device-side cluster genotyper (shallow, deep list), when it runs
     // the deep list's selection: its lists and merge records are per read of the batch, like ClArgs::cls (one slab); with the purity
     // filter on, its select / filter kernels run next to the shallow ones below and share their purity batch
-    cld::DeepArgs da;
-    std::memset(&da, 0, sizeof da);
-    if (!cld_list.empty()) {
+    cld::DeepArgs da, ds;  // (ds: the deep size list -- the same per-read lists, the loci of the two lists being different ones; its own counts)
+    std::memset(&da, 0, sizeof da); std::memset(&ds, 0, sizeof ds);
+    if (!cld_list.empty() || !gsd_list.empty()) {
       size_t dt = 0;
       auto dadd = [&](size_t bytes) { const size_t o = dt; dt += (bytes + 255) & ~(size_t)255; return o; };
-      const size_t do_read = dadd((size_t)nr * 4), do_start = dadd((size_t)nr * 4), do_len = dadd((size_t)nr * 4), do_job = dadd((size_t)nr * 4), do_n = dadd(cld_list.size() * 4),
+      const size_t do_read = dadd((size_t)nr * 4), do_start = dadd((size_t)nr * 4), do_len = dadd((size_t)nr * 4), do_job = dadd((size_t)nr * 4), do_n = dadd(cld_list.size() * 4), do_n2 = dadd(gsd_list.size() * 4),
                    do_ma = dadd((size_t)nr * 2), do_mb = dadd((size_t)nr * 2), do_md = dadd((size_t)nr * 8);
       void* d_ds = nullptr;
       if ((rc = dev_get(c, S_CLD_SEL, dt, &d_ds))) return rc;
@@ -853,6 +866,8 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       da.sel_read = (uint32_t*)dsl2(do_read); da.sel_start = (uint32_t*)dsl2(do_start); da.sel_len = (uint32_t*)dsl2(do_len); da.sel_job = (uint32_t*)dsl2(do_job);
       da.n_sel = (uint32_t*)dsl2(do_n); da.mg_a = (uint16_t*)dsl2(do_ma); da.mg_b = (uint16_t*)dsl2(do_mb); da.mg_d = (double*)dsl2(do_md);
       da.c.list = clp[1].d_list; da.c.n_list = (uint32_t)cld_list.size();
+      ds.sel_read = da.sel_read; ds.sel_start = da.sel_start; ds.sel_len = da.sel_len; ds.sel_job = da.sel_job; ds.n_sel = (uint32_t*)dsl2(do_n2);
+      ds.c.list = d_gsd_list; ds.c.n_list = (uint32_t)gsd_list.size();
     }
     if (dev_repair) {
       void* const z_rpc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
@@ -907,6 +922,10 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         da.c.g = ga; da.purity_on = 1; da.read_qual = pa.read_qual; da.pj_counter = pa.counter; da.pj = pa.jobs; da.pj_cap = pa.cap_jobs; da.purity = pa.purity;
         hipLaunchKernelGGL(cld::deep_select_kernel, dim3(da.c.n_list), dim3(cld::DW), 0, c->stream, da);
       }
+      if (!gsd_list.empty()) {  // (the deep size list likewise)
+        ds.c.g = ga; ds.purity_on = 1; ds.read_qual = pa.read_qual; ds.pj_counter = pa.counter; ds.pj = pa.jobs; ds.pj_cap = pa.cap_jobs; ds.purity = pa.purity;
+        hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
+      }
       TRGT_HIP_TRY(c, hipGetLastError());
       *(uint32_t*)h_pj = 0;
       { const int d2h_rc = trgt::d2h(c, h_pj, pa.counter, 4, c->stream); if (d2h_rc) return d2h_rc; }
@@ -940,6 +959,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       if (small_gt) hipLaunchKernelGGL((pur::purity_filter_kernel<64>), pgrid, dim3(64), 0, c->stream, ga, pa);
       else hipLaunchKernelGGL((pur::purity_filter_kernel<gt::GT_MAX_READS>), pgrid, dim3(64), 0, c->stream, ga, pa);
       if (!cld_list.empty()) hipLaunchKernelGGL(cld::deep_filter_kernel, dim3(da.c.n_list), dim3(cld::DW), 0, c->stream, da);
+      if (!gsd_list.empty()) hipLaunchKernelGGL(cld::deep_filter_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
       TRGT_HIP_TRY(c, hipGetLastError());
       ga.sel_read = pa.sel_read; ga.sel_start = pa.sel_start; ga.sel_len = pa.sel_len; ga.n_sel = pa.n_sel;
       if (small_gt) hipLaunchKernelGGL((gt::locus_genotype_kernel<64, 8 * 1024, true>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
@@ -947,6 +967,13 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     }
     else if (small_gt) hipLaunchKernelGGL((gt::locus_genotype_kernel<64, 8 * 1024>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
     else hipLaunchKernelGGL((gt::locus_genotype_kernel<gt::GT_MAX_READS, gt::GT_SEG_LDS>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
+    if (!gsd_list.empty()) {
+      // ---- the deep size list, behind the one-wave genotyper (which marked these loci need_host = 1): selection unless it ran in front
+      //      of the purity batch, then the workgroup-wide genotyper; its loci without majority support join the repair chain below
+      ds.c.g = ga;
+      if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
+      hipLaunchKernelGGL(gtd::deep_size_genotype_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
+    }
     TRGT_HIP_TRY(c, hipGetLastError());
     tl_mark(c, "genotyper launched");
     // Two ways to order the HMM of the settled loci and the repair of the others: one HMM batch behind the repair (default), or -- split_hmm,
@@ -1022,6 +1049,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       }
       else if (small_gt) hipLaunchKernelGGL((gt::repair_finish_kernel<64>), fgrid, dim3(64), 0, c->stream, ga, fa);
       else hipLaunchKernelGGL((gt::repair_finish_kernel<gt::GT_MAX_READS>), fgrid, dim3(64), 0, c->stream, ga, fa);
+      if (!gsd_list.empty()) { ds.c.g = ga; hipLaunchKernelGGL(gtd::deep_size_finish_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds, fa); }
       TRGT_HIP_TRY(c, hipGetLastError());
       if ((rc = dbg_sync("vote + finish"))) return rc;
       tl_mark(c, "repair chain enqueued");
@@ -1194,6 +1222,11 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     uint8_t* need = (uint8_t*)gh.need;
     const uint8_t* skip_b = (const uint8_t*)hsl(o_skipb);
     if (hmm_pendingB) need_a.assign(need, need + nl);
+    for (const uint32_t l : gsd_list) {  // trgt_hip_size_deep_stats (skip_b is 0 only where a finish kernel completed a locus)
+      const bool on_device = need[l] == 0 || (need[l] == 2 && !skip_b[l]);
+      if (on_device) { c->size_deep_stats[0] += 1; if (!skip_b[l]) c->size_deep_stats[1] += 1; }
+      else c->size_deep_stats[2] += 1;
+    }
     for (int64_t l = 0; l < nl; ++l) if (need[l] == 2) need[l] = skip_b[l] ? 1 : 0;  // repaired on the device, or back to the host path after all
     if (in->genotyper && cl_list.empty() && cld_list.empty()) for (int64_t l = 0; l < nl; ++l) if (in->genotyper[l] == 1) need[l] = 1;  // Genotyper::Cluster: host-driven rounds (else: genotyped by the device chain, need_host = 0)
     if (flank_on) {
@@ -1769,6 +1802,21 @@ extern "C" int trgt_hip_set_cluster_max_reads(trgt_hip_ctx* c, int32_t max_reads
   if (max_reads < gt::GT_MAX_READS || max_reads > cld::CL_DEEP_MAX_READS)
     return fail(c, TRGT_ERR_INVALID, "trgt_hip_set_cluster_max_reads: %d is outside [%d, %d]", (int)max_reads, gt::GT_MAX_READS, cld::CL_DEEP_MAX_READS);
   c->cluster_max_reads = max_reads;
+  return TRGT_OK;
+}
+
+// ---- ... and so is the deep instantiation of the size genotyper (locus_gt_deep.hpp)
+extern "C" int32_t trgt_hip_size_max_reads_limit(void) { return gtd::GT_DEEP_MAX_READS; }
+extern "C" int trgt_hip_set_size_max_reads(trgt_hip_ctx* c, int32_t max_reads) {
+  if (!c) return TRGT_ERR_INVALID;
+  if (max_reads < gt::GT_MAX_READS || max_reads > gtd::GT_DEEP_MAX_READS)
+    return fail(c, TRGT_ERR_INVALID, "trgt_hip_set_size_max_reads: %d is outside [%d, %d]", (int)max_reads, gt::GT_MAX_READS, gtd::GT_DEEP_MAX_READS);
+  c->size_max_reads = max_reads;
+  return TRGT_OK;
+}
+extern "C" int trgt_hip_size_deep_stats(const trgt_hip_ctx* c, int64_t out[4]) {
+  if (!c || !out) return TRGT_ERR_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = c->size_deep_stats[i];
   return TRGT_OK;
 }
 

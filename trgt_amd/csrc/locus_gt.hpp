@@ -4,10 +4,12 @@
 //   (haploid.rs:3-30), consensus::get_consensus (consensus.rs:113-154), the read classification (genotype_size.rs:42-61)
 //   and "reference allele first" (tr.rs:95-101).
 // One wavefront per locus; everything the decisions depend on (span lengths, the repeat segments themselves) is staged in
-// LDS.  A locus is handed back to the host path (need_host = 1) when it is out of this kernel's envelope: more than
-// GT_MAX_READS reads, more than GT_SEG_LDS segment bytes, or an allele without majority support, which needs the consensus
-// alignments of stage B (repair_consensus, consensus.rs:5-111).  The arithmetic (f64 penalties, tie-breaks) is written
-// operation for operation like the host version in locus.hip, which the oracle pins.
+// LDS (segments beyond GT_SEG_LDS bytes are compared where they lie, in the read blob).  A locus of more than GT_MAX_READS reads is out of
+// this kernel's envelope and leaves it with need_host = 1: on a context that opted in (trgt_hip_set_size_max_reads) the workgroup-wide
+// kernels of locus_gt_deep.hpp then take it, up to 2 048 reads, and overwrite that mark; otherwise, and beyond that, the host path of
+// locus.hip.  A locus whose pick lacks majority support waits (need_host = 2) for the consensus alignments of stage B
+// (repair_consensus, consensus.rs:5-111) and repair_finish_kernel below, or goes to the host path when that chain has no room for it.
+// The arithmetic (f64 penalties, tie-breaks) is written operation for operation like the host version in locus.hip, which the oracle pins.
 #pragma once
 #include "common.hpp"
 #include "wfa_host.hpp"
@@ -552,6 +554,7 @@ __global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgs a, const
   const int lane = threadIdx.x;
   const uint64_t r0 = a.locus_read_begin[l];
   const int nr = (int)(a.locus_read_begin[l + 1] - r0);
+  if (nr > MAXR) return;  // a locus of the deep size list (locus_gt_deep.hpp): deep_size_finish_kernel's
   if (lane == 0) sh.n = 0;
   gt_selected<MAXR, PRESEL>(sh, a, l, r0, nr, lane);
   const int n = sh.n;

@@ -1,0 +1,434 @@
+// trgt_amd/csrc/locus_gt_deep.hpp -- the deep instantiation of the device-side size genotyper: Genotyper::Size loci with more than
+// gt::GT_MAX_READS (256) candidate reads, up to GT_DEEP_MAX_READS, for the contexts that opted in (trgt_hip_set_size_max_reads).  The
+// reference's default --max-depth is 250 and its reservoir keeps 3 x max_depth reads, so an ordinary run over deep or targeted data hands
+// analyze_tr loci of 257 to 750 reads; without this chain every one of them takes the host path of locus.hip.
+//
+// Same decisions as locus_gt.hpp (genotype_size.rs:6-64, diploid.rs:5-103, haploid.rs:3-30, consensus.rs:113-154, tr.rs:95-101), restated
+// for one WORKGROUP of cld::DW threads per locus of the deep size list instead of one wave:
+//   cld::deep_select_kernel / cld::deep_filter_kernel   the kept reads, in global lists (shared with the deep cluster chain)
+//   deep_size_genotype_kernel   length histogram, diploid / haploid candidates, collapse, intervals, sequence histogram, picks, split();
+//                               a locus with majority support is classified and written out, the others write vote groups, alignment jobs
+//                               and a RepairPend into the call's RepairBufs (the repair chain of locus.hip is the same for both depths)
+//   deep_size_finish_kernel     behind the vote: classification against the repaired alleles, reference allele first, outputs
+// The sequential scans of the one-wave kernel (histogram insertion, binary-insertion sort, lane-0 loops) are rank sorts and workgroup
+// reductions here.  Ties as in locus_cluster_deep.hpp: every "first / last in index order" of a sequential scan is a lexicographic
+// (value, index) reduction.  The f64 penalties are those of locus_gt.hpp: one thread sums one candidate in ascending histogram order.
+// Segments are compared where they lie in the read blob; per-read state that no single thread walks stays in the global lists.
+#pragma once
+#include "locus_cluster_deep.hpp"
+#include "locus_gt.hpp"
+
+namespace trgt {
+namespace gtd {
+
+constexpr int GT_DEEP_MAX_READS = cld::CL_DEEP_MAX_READS;  // one ceiling: the two selection kernels serve both deep lists
+constexpr int MAXR = GT_DEEP_MAX_READS;
+using cld::DeepArgs; using cld::DT; using cld::DW; using cld::DWAVES; using cld::Red;
+using gt::adiff_u;
+
+// exclusive prefix sum of x over the workgroup in thread order, and the total
+__device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t x, uint32_t& total, Red& r) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  uint32_t inc = x;
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+  if (lane == 63) r.u[wave] = inc;
+  __syncthreads();
+  uint32_t before = 0; total = 0;
+  for (int w = 0; w < DWAVES; ++w) { const uint32_t cw = r.u[w]; before += w < wave ? cw : 0u; total += cw; }
+  __syncthreads();
+  return before + inc - x;
+}
+__device__ __forceinline__ uint32_t block_min_u32(uint32_t x, Red& r) {
+  for (int o = 32; o > 0; o >>= 1) { const uint32_t t = __shfl_xor(x, o); x = t < x ? t : x; }
+  if ((threadIdx.x & 63) == 0) r.u[threadIdx.x >> 6] = x;
+  __syncthreads();
+  uint32_t m = r.u[0];
+  for (int w = 1; w < DWAVES; ++w) m = r.u[w] < m ? r.u[w] : m;
+  __syncthreads();
+  return m;
+}
+__device__ __forceinline__ uint32_t block_max_u32(uint32_t x, Red& r) { return ~block_min_u32(~x, r); }
+
+// cmp_seg of locus.hip (memcmp over the common prefix, then the shorter one first) by ONE thread, on byte strings anywhere in global memory
+__device__ __forceinline__ int cmp_seg_thread(const uint8_t* __restrict__ a, uint32_t na, const uint8_t* __restrict__ b, uint32_t nb) {
+  const uint32_t m = na < nb ? na : nb;
+  uint32_t i = 0;
+  for (; i + 8 <= m; i += 8) {
+    uint64_t x, y;
+    __builtin_memcpy(&x, a + i, 8); __builtin_memcpy(&y, b + i, 8);
+    if (x != y) return __builtin_bswap64(x) < __builtin_bswap64(y) ? -1 : 1;  // byte order is memory order
+  }
+  for (; i < m; ++i) if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+  return na < nb ? -1 : (na > nb ? 1 : 0);
+}
+
+// ---- classification of the kept reads (genotype_size.rs:42-61), reference allele first (tr.rs:95-101) and the outputs of a locus, by the
+// workgroup.  ap / aln / civ / gsz are indexed by allele as genotyped; n_al: alleles the reads are classified against.  The tie-breaker
+// starts at 1 and flips at every tie, so the k-th tied read (k from 0) gets k & 1: a prefix count over the kept reads.  false: an allele
+// exceeds allele_cap (the host path reports the error), nothing was written.
+__device__ __forceinline__ bool deep_size_write(const DeepArgs& a, int64_t l, uint64_t r0, int n, int n_gt, int n_al, const uint8_t* const ap[2],
+                                                const uint32_t aln[2], const int32_t civ[4], const uint32_t gsz[2], Red& red) {
+  const gt::GtArgs& g = a.c.g;
+  const int tid = threadIdx.x;
+  const uint8_t* ref = g.tr_blob + g.tr_off[l]; const uint32_t refn = g.tr_len[l];
+  int flip = 0;  // (wave_equal: every wave compares the whole strings, all reach the same answer)
+  if (n_gt != 1 && !gt::wave_equal(ap[0], aln[0], ref, refn) && gt::wave_equal(ap[1], aln[1], ref, refn)) flip = 1;
+  // (constant indices throughout, selections instead of indexed loads: the small per-allele arrays stay in registers)
+  if (aln[0] > g.allele_cap[l] || (n_gt == 2 && aln[1] > g.allele_cap[l])) return false;
+  uint32_t ties = 0, h1 = 0;
+  for (int base = 0; base < n; base += DW) {
+    const int i = base + tid;
+    const bool valid = i < n;
+    uint32_t d1 = 0, d2 = 0;
+    if (valid && n_al == 2) { const uint32_t ln = a.sel_len[r0 + i]; d1 = adiff_u(ln, aln[0]); d2 = adiff_u(ln, aln[1]); }
+    const bool tie = valid && n_al == 2 && d1 == d2;
+    uint32_t total;
+    const uint32_t pos = ties + cld::block_rank(tie, total, red);
+    if (valid) {
+      const int cc = n_al == 2 ? (d1 < d2 ? 0 : (d1 > d2 ? 1 : (int)(pos & 1u))) : 0;
+      h1 += (uint32_t)cc;
+      const uint32_t rd = a.sel_read[r0 + i];
+      g.classification[r0 + rd] = flip ? 1 - cc : cc;
+      g.read_rank[r0 + rd] = i;
+    }
+    ties += total;
+  }
+  h1 = cld::block_sum_u32(h1, red);
+  const int hap0 = n - (int)h1, hap1 = (int)h1;
+#pragma unroll
+  for (int oi = 0; oi < 2; ++oi) {
+    if (oi >= n_gt) break;
+    const bool second = (oi == 1) != (flip != 0);  // the allele written in place oi: order = {1, 0} when flipped
+    const uint8_t* src = second ? ap[1] : ap[0]; const uint32_t len = second ? aln[1] : aln[0];
+    uint8_t* dst = g.allele_blob + g.allele_off[2 * l + oi];
+    for (uint32_t b = tid; b < len; b += DW) dst[b] = src[b];
+    if (tid == 0) {
+      g.allele_len[2 * l + oi] = len;
+      g.ci[4 * l + 2 * oi] = second ? civ[2] : civ[0]; g.ci[4 * l + 2 * oi + 1] = second ? civ[3] : civ[1];
+      g.num_spanning[2 * l + oi] = second ? hap1 : hap0;
+      if (g.gt_size) g.gt_size[2 * l + oi] = (int32_t)(second ? gsz[1] : gsz[0]);
+    }
+  }
+  if (tid == 0) { g.n_alleles[l] = n_gt; g.n_spanning_reads[l] = (uint32_t)n; g.flipped[l] = (uint8_t)flip; }
+  return true;
+}
+
+struct DeepSize {
+  uint32_t ln[MAXR]; uint64_t off[MAXR];  // kept reads in LocusResult.reads order: span length, blob offset of the repeat segment
+  uint32_t ulen[MAXR], ucnt[MAXR];        // unique lengths ascending, multiplicities
+  uint32_t tmp[MAXR];                     // the sorted lengths; later per kept read: multiplicity of its sequence, bit 31 = an earlier read has it too
+  uint16_t ord[MAXR];                     // first read of every length in the sorted list; later the kept reads in byte-lexicographic order (stable)
+  uint16_t u_rep[MAXR], u_cnt[MAXR];      // unique sequences in that order: representative (the earliest read), multiplicity
+  Red red;
+  int rp_ok; uint32_t rp_g0, rp_j0; unsigned long long rp_c0, rp_o0, rp_s0;
+};
+static_assert(sizeof(DeepSize) <= 64 * 1024, "static LDS of the deep size genotyper");
+
+__global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgs a) {
+  __shared__ DeepSize sh;
+  const uint32_t k = blockIdx.x;
+  if (k >= a.c.n_list) return;
+  const gt::GtArgs& g = a.c.g;
+  const int64_t l = a.c.list[k];
+  const int tid = threadIdx.x;
+  const uint64_t r0 = g.locus_read_begin[l];
+  const int nr = (int)(g.locus_read_begin[l + 1] - r0);
+  if (g.ploidy[l] == 0 || nr == 0 || nr > MAXR) return;  // (never on the list: what the one-wave kernel said stands)
+  const int n = min((int)a.n_sel[k], nr);
+  if (n == 0) { if (tid == 0) g.need_host[l] = 0; return; }  // no spanning read: the empty result stands
+  for (int i = tid; i < n; i += DW) { sh.ln[i] = a.sel_len[r0 + i]; sh.off[i] = cld::seg_off(a, r0, i); }
+  __syncthreads();
+  // ---- unique lengths / counts ascending: rank sort of the lengths (thread t owns elements t, t + DW, ...), run boundaries, run lengths
+  for (int i = tid; i < n; i += DW) {
+    const uint32_t li = sh.ln[i];
+    int rk = 0;
+    for (int j = 0; j < n; ++j) { const uint32_t lj = sh.ln[j]; rk += (lj < li) || (lj == li && j < i); }
+    sh.tmp[rk] = li;
+  }
+  __syncthreads();
+  int u = 0;
+  for (int base = 0; base < n; base += DW) {
+    const int p = base + tid;
+    const bool first = p < n && (p == 0 || sh.tmp[p - 1] != sh.tmp[p]);
+    uint32_t total;
+    const uint32_t q = (uint32_t)u + cld::block_rank(first, total, sh.red);
+    if (first) { sh.ulen[q] = sh.tmp[p]; sh.ord[q] = (uint16_t)p; }
+    u += (int)total;
+  }
+  __syncthreads();
+  for (int q = tid; q < u; q += DW) sh.ucnt[q] = (uint32_t)(q + 1 < u ? (int)sh.ord[q + 1] : n) - (uint32_t)sh.ord[q];
+  __syncthreads();
+  const int ploidy = g.ploidy[l] == 1 ? 1 : 2;
+  constexpr int NONE = 0x7FFFFFFF;
+  // ---- diploid::genotype / haploid::genotype: candidates spread over the workgroup, each summed by one thread in ascending histogram
+  //      order; the first minimum in candidate order wins
+  double best_pen = __builtin_huge_val(); int best_p = NONE;
+  if (ploidy == 2) {
+    const int P = u * (u + 1) / 2;
+    int si = 0, row0 = 0;  // row si of the candidate triangle starts at candidate row0 and has u - si entries
+    for (int p = tid; p < P; p += DW) {
+      while (p >= row0 + (u - si)) { row0 += u - si; ++si; }
+      const int li = si + (p - row0);
+      const uint32_t sa = sh.ulen[si], la = sh.ulen[li];
+      const double max_frac = adiff_u(sa, la) <= 100 ? 0.25 : 0.05;
+      double pen = 0.0;
+      for (int i = 0; i < u; ++i) {
+        const uint32_t ui = sh.ulen[i];
+        const uint32_t st = ui != sa ? 10 + 2 * adiff_u(sa, ui) : 0, lt = ui != la ? 10 + 2 * adiff_u(la, ui) : 0;
+        const double term = (double)(st < lt ? st : lt) + max_frac * (double)(st > lt ? st : lt);
+        pen += term * (double)sh.ucnt[i];
+      }
+      if (best_p == NONE || pen < best_pen) { best_pen = pen; best_p = p; }
+    }
+  } else {
+    for (int c = tid; c < u; c += DW) {
+      const uint32_t uc = sh.ulen[c];
+      double pen = 0.0;
+      for (int i = 0; i < u; ++i) {
+        const double term = sh.ulen[i] != uc ? 10.0 + 2.0 * (double)adiff_u(uc, sh.ulen[i]) : 0.0;
+        pen += term * (double)sh.ucnt[i];
+      }
+      if (best_p == NONE || pen < best_pen) { best_pen = pen; best_p = c; }
+    }
+  }
+  cld::block_min_vi(best_pen, best_p, sh.red);
+  uint32_t size[2] = {0, 0}; int32_t civ[4] = {0, 0, 0, 0};
+  int n_gt;
+  if (ploidy == 2) {
+    int si = 0, row0 = 0;
+    while (best_p >= row0 + (u - si)) { row0 += u - si; ++si; }
+    const int li = si + (best_p - row0);
+    const uint32_t bs = sh.ulen[si], bl = sh.ulen[li];
+    uint32_t short_size = bs < bl ? bs : bl, long_size = bs > bl ? bs : bl;
+    if (short_size != long_size && u >= 2) {  // (uniform: every thread holds the same sizes)
+      // the most frequent length, the first among equals (stable descending sort); the coverage is the number of kept reads
+      double tv = 0.0; int top = NONE;
+      for (int i = tid; i < u; i += DW) { const double v = -(double)sh.ucnt[i]; if (top == NONE || v < tv) { tv = v; top = i; } }
+      cld::block_min_vi(tv, top, sh.red);
+      const double top_frac = (double)sh.ucnt[top] / (double)(uint64_t)n;
+      const uint32_t range = sh.ulen[u - 1] - sh.ulen[0];
+      if (top_frac > 0.60 && range <= 6) short_size = long_size = sh.ulen[top];
+    }
+    n_gt = 2; size[0] = short_size; size[1] = long_size;
+    uint32_t lo0 = short_size, hi0 = short_size, lo1 = long_size, hi1 = long_size;
+    for (int i = tid; i < u; i += DW) {
+      const uint32_t s = sh.ulen[i];
+      if (adiff_u(s, short_size) <= adiff_u(s, long_size)) { lo0 = lo0 < s ? lo0 : s; hi0 = hi0 > s ? hi0 : s; }
+      else { lo1 = lo1 < s ? lo1 : s; hi1 = hi1 > s ? hi1 : s; }
+    }
+    civ[0] = (int32_t)block_min_u32(lo0, sh.red); civ[1] = (int32_t)block_max_u32(hi0, sh.red);
+    civ[2] = (int32_t)block_min_u32(lo1, sh.red); civ[3] = (int32_t)block_max_u32(hi1, sh.red);
+  } else {
+    n_gt = 1; size[0] = sh.ulen[best_p];
+    civ[0] = (int32_t)sh.ulen[0]; civ[1] = (int32_t)sh.ulen[u - 1];
+  }
+  // ---- get_seq_hist: the kept reads in byte-lexicographic order of their segments, equal ones in read order (rank = #{smaller} +
+  //      #{equal and earlier}); the first read of a run of equal segments represents it, as the insertion of the one-wave kernel does
+  for (int i = tid; i < n; i += DW) {
+    const uint8_t* pi = g.reads + sh.off[i]; const uint32_t li = sh.ln[i];
+    uint32_t r = 0, eq = 1, dup = 0;
+    for (int j = 0; j < n; ++j) {
+      if (j == i) continue;
+      const int c = cmp_seg_thread(g.reads + sh.off[j], sh.ln[j], pi, li);
+      r += (c < 0) || (c == 0 && j < i);
+      eq += c == 0; dup |= (c == 0 && j < i);
+    }
+    sh.ord[r] = (uint16_t)i; sh.tmp[i] = eq | (dup << 31);
+  }
+  __syncthreads();
+  int nu = 0;
+  for (int base = 0; base < n; base += DW) {
+    const int r = base + tid;
+    const int i = r < n ? sh.ord[r] : 0;
+    const bool first = r < n && !(sh.tmp[i] >> 31);
+    uint32_t total;
+    const uint32_t q = (uint32_t)nu + cld::block_rank(first, total, sh.red);
+    if (first) { sh.u_rep[q] = (uint16_t)i; sh.u_cnt[q] = (uint16_t)(sh.tmp[i] & 0x7FFFFFFFu); }
+    nu += (int)total;
+  }
+  __syncthreads();
+  auto ulen_of = [&](int q) { return sh.ln[sh.u_rep[q]]; };
+  // get_closest_len: the first length in sequence order at the smallest distance
+  auto closest = [&](uint32_t target) {
+    double bv = __builtin_huge_val(); int bq = NONE;
+    for (int q = tid; q < nu; q += DW) { const double d = (double)adiff_u(ulen_of(q), target); if (d < bv) { bv = d; bq = q; } }
+    cld::block_min_vi(bv, bq, sh.red);
+    return ulen_of(bq == NONE ? 0 : bq);  // (nu >= 1: some thread has a value)
+  };
+  // get_most_frequent_seq: max_by_key takes the LAST maximum in sequence order: the largest (count, index) pair
+  auto most_frequent = [&](uint32_t len) {
+    double bv = __builtin_huge_val(); int bi = NONE;
+    for (int q = tid; q < nu; q += DW) if (ulen_of(q) == len) { const double v = -(double)sh.u_cnt[q]; if (v <= bv) { bv = v; bi = -q; } }
+    cld::block_min_vi(bv, bi, sh.red);
+    return bi == NONE ? 0 : -bi;  // (len is the length of some unique sequence: some thread has a value)
+  };
+  int pick[2] = {most_frequent(closest(size[0])), -1};
+  int n_pick = 1;
+  if (n_gt != 1 && size[0] != size[1]) { pick[1] = most_frequent(closest(size[1])); n_pick = 2; }
+  auto in_group = [&](int q, int al) {
+    if (n_gt == 1) return true;
+    const uint32_t d1 = adiff_u(ulen_of(q), size[0]), d2 = adiff_u(ulen_of(q), size[1]);
+    return al == 0 ? d1 <= d2 : d2 < d1;
+  };
+  bool majority = true, lacks[2] = {false, false};
+#pragma unroll
+  for (int al = 0; al < 2; ++al) {  // split(): majority support of the pick inside its group, else stage B is needed
+    if (al >= n_pick) break;
+    uint32_t cov = 0;
+    for (int q = tid; q < nu; q += DW) if (in_group(q, al)) cov += sh.u_cnt[q];
+    const uint64_t coverage = cld::block_sum_u32(cov, sh.red), ref_count = in_group(pick[al], al) ? sh.u_cnt[pick[al]] : 0u;
+    if (!(2 * ref_count >= coverage)) { majority = false; lacks[al] = true; }
+  }
+  if (majority) {
+    const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
+#pragma unroll
+    for (int al = 0; al < 2; ++al) { if (al >= n_pick) break; const int rep = sh.u_rep[pick[al]]; ap[al] = g.reads + sh.off[rep]; aln[al] = sh.ln[rep]; }
+    int n_al = n_pick;
+    if (ploidy == 2 && n_al == 1) { ap[1] = ap[0]; aln[1] = aln[0]; n_al = 2; }
+    // (a pick with majority support has the genotype's size)
+    const bool ok = deep_size_write(a, l, r0, n, n_gt, n_al, ap, aln, civ, aln, sh.red);
+    if (tid == 0) g.need_host[l] = ok ? 0 : 1;
+    return;
+  }
+  // ---- stage B on the device: one vote group per allele without majority support, one alignment job per unique sequence of its group
+  //      against the pick, in sequence order; the reservations are those of the one-wave kernel, in its order
+  const gt::RepairBufs& rp = g.rp;
+  bool can = rp.counts != nullptr;
+  uint32_t nm[2] = {0, 0}, mbytes[2] = {0, 0}; unsigned long long cig[2] = {0, 0};
+  if (can) {
+#pragma unroll
+    for (int al = 0; al < 2; ++al) {
+      if (al >= n_pick || !lacks[al]) continue;
+      const uint32_t bb = ulen_of(pick[al]);
+      uint32_t cnt = 0, bytes = 0, over = bb > rp.max_seg;
+      for (int q = tid; q < nu; q += DW) {
+        if (!in_group(q, al)) continue;
+        const uint32_t ln = ulen_of(q);
+        over += ln > rp.max_seg; cnt += 1; bytes += ln;
+      }
+      nm[al] = cld::block_sum_u32(cnt, sh.red); mbytes[al] = cld::block_sum_u32(bytes, sh.red);
+      if (cld::block_sum_u32(over, sh.red)) can = false;
+      cig[al] = (unsigned long long)nm[al] * ((unsigned long long)bb + 1) + mbytes[al];
+    }
+  }
+  unsigned long long out_need[2] = {0, 0}, scr_need[2] = {0, 0};
+  uint32_t out_cap[2] = {0, 0};
+  if (can) {
+#pragma unroll
+    for (int al = 0; al < 2; ++al) {
+      if (al >= n_pick || !lacks[al]) continue;
+      const uint32_t bb = ulen_of(pick[al]);
+      // at most one base per backbone position plus the insertions taken, each of which is a piece of some member
+      out_cap[al] = (uint32_t)(bb + mbytes[al] + 16);
+      out_need[al] = ((unsigned long long)out_cap[al] + 15ull) & ~15ull;
+      scr_need[al] = (bb + 1 <= rp.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)bb + 1)) + 3ull * nm[al];
+    }
+    if (tid == 0) {  // cigar words, result bytes and vote scratch first: a failed reservation must not leave holes in the job list
+      const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
+      int ok = 1;
+      unsigned long long c0 = 0, o0 = 0, s0 = 0;
+      c0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_CIGAR), cn);
+      if (c0 + cn > rp.cap_cigar) ok = 0;
+      if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_OUT), on); if (o0 + on > rp.cap_out) ok = 0; }
+      if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_SCRATCH), sn); if (s0 + sn > rp.cap_scratch) ok = 0; }
+      if (ok) {
+        sh.rp_j0 = atomicAdd(rp.counts + gt::RC_JOBS, nm[0] + nm[1]);
+        sh.rp_g0 = atomicAdd(rp.counts + gt::RC_GROUPS, (uint32_t)lacks[0] + (uint32_t)lacks[1]);
+        rp.loci[atomicAdd(rp.counts + gt::RC_LOCI, 1u)] = (uint32_t)l;
+        if (sh.rp_j0 + nm[0] + nm[1] > rp.cap_jobs || sh.rp_g0 + 2 > rp.cap_groups) ok = 0;  // (cannot happen: the caps are the read and locus counts)
+      } else atomicAdd(rp.counts + gt::RC_FAILED, 1u);
+      sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
+    }
+    __syncthreads();
+    can = sh.rp_ok != 0;
+  }
+  if (!can) { if (tid == 0) g.need_host[l] = 1; return; }  // no room, a segment beyond max_seg, no device-side repair: the host path
+  uint32_t gi = sh.rp_g0, j = sh.rp_j0;
+  unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
+  gt::RepairPend pd;
+  pd.n_gt = n_gt; pd.n_pick = n_pick; pd.size[0] = size[0]; pd.size[1] = size[1];
+  for (int q = 0; q < 4; ++q) pd.civ[q] = civ[q];
+  pd.rep[0] = pd.rep[1] = -1; pd.grp[0] = pd.grp[1] = -1;
+#pragma unroll
+  for (int al = 0; al < 2; ++al) {
+    if (al >= n_pick) break;
+    const int rep = sh.u_rep[pick[al]];
+    pd.rep[al] = rep;
+    if (!lacks[al]) continue;
+    const unsigned long long bb_off = sh.off[rep];
+    const uint32_t bb = sh.ln[rep];
+    if (tid == 0) {
+      gt::RGroup G;
+      G.job_first = j; G.n_members = nm[al]; G.bb_len = bb; G.out_cap = out_cap[al];
+      G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
+      rp.groups[gi] = G;
+    }
+    pd.grp[al] = (int32_t)gi;
+    // job k of the group is its k-th member in sequence order; its CIGAR slot starts behind those of the members before it
+    uint32_t k0 = 0; unsigned long long b0 = 0;
+    for (int base = 0; base < nu; base += DW) {
+      const int q = base + tid;
+      const bool in = q < nu && in_group(q, al);
+      const int rq = in ? sh.u_rep[q] : 0;
+      const uint32_t ln = in ? sh.ln[rq] : 0u;
+      uint32_t tk, tb;
+      const uint32_t kk = k0 + cld::block_rank(in, tk, sh.red);
+      const unsigned long long before = b0 + block_excl_scan_u32(ln, tb, sh.red);
+      if (in) {
+        JobDev jd;
+        jd.pat_off = bb_off; jd.pat_len = bb;
+        jd.txt_off = sh.off[rq]; jd.txt_len = ln;
+        jd.cigar_off = co + (unsigned long long)kk * ((unsigned long long)bb + 1) + before; jd.ops_off = 0; jd.out_index = j + kk; jd.pad = 0;
+        rp.jobs[j + kk] = jd;
+      }
+      k0 += tk; b0 += tb;
+    }
+    co += cig[al]; j += nm[al]; oo += out_need[al]; so += scr_need[al]; ++gi;
+  }
+  if (tid == 0) { rp.pend[l] = pd; g.need_host[l] = 2; }  // the locus waits for deep_size_finish_kernel
+}
+
+// ---- behind the consensus alignments and the column voting: the rest of genotype_size::genotype for the loci of the deep size list that
+// wait for a repair (need_host = 2; they are in rp.loci too, where repair_finish_kernel passes them over by their read count).  A locus
+// whose repaired allele does not fit (vote overflow, allele_cap) goes to the host path after all.
+__global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgs a, const gt::FinishArgs f) {
+  __shared__ Red red;
+  const uint32_t k = blockIdx.x;
+  if (k >= a.c.n_list) return;
+  const gt::GtArgs& g = a.c.g;
+  const gt::RepairBufs& rp = g.rp;
+  const int64_t l = a.c.list[k];
+  const int tid = threadIdx.x;
+  const bool waits = g.need_host[l] == 2;
+  __syncthreads();  // (every thread has read the flag before thread 0 rewrites it below)
+  if (!waits) return;
+  const uint64_t r0 = g.locus_read_begin[l];
+  const int nr = (int)(g.locus_read_begin[l + 1] - r0);
+  const int n = min((int)a.n_sel[k], min(nr, MAXR));
+  const gt::RepairPend pd = rp.pend[l];
+  const int ploidy = g.ploidy[l] == 1 ? 1 : 2;
+  // the alleles: the repaired sequence of a group, or the pick that had majority support
+  const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
+  bool fail = n == 0;
+#pragma unroll
+  for (int al = 0; al < 2; ++al) {
+    if (al >= pd.n_pick || fail) break;
+    if (pd.grp[al] >= 0) {
+      const uint32_t len = f.vote_len[pd.grp[al]];
+      if (len == 0xFFFFFFFFu) { fail = true; break; }
+      ap[al] = f.vote_out + rp.groups[pd.grp[al]].out_off; aln[al] = len;
+    } else {
+      const int rep = pd.rep[al];
+      ap[al] = g.reads + cld::seg_off(a, r0, rep); aln[al] = a.sel_len[r0 + rep];
+    }
+  }
+  int n_al = pd.n_pick;
+  if (!fail && ploidy == 2 && n_al == 1) { ap[1] = ap[0]; aln[1] = aln[0]; n_al = 2; }
+  if (!fail) fail = !deep_size_write(a, l, r0, n, pd.n_gt, n_al, ap, aln, pd.civ, pd.size, red);
+  if (fail) { if (tid == 0) g.need_host[l] = 1; return; }
+  // (need_host stays 2 unless one HMM batch runs behind the repair: see repair_finish_kernel)
+  if (tid == 0) { g.skip_b[l] = 0; if (g.finish_clears_need) g.need_host[l] = 0; }
+}
+
+}  // namespace gtd
+}  // namespace trgt
