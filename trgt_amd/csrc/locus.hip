@@ -26,6 +26,7 @@
 #include <cstddef>
 #include <cstdlib>
 #include <functional>
+#include <optional>
 #include <thread>
 
 #include "hmm_host.hpp"
@@ -537,16 +538,158 @@ __global__ void __launch_bounds__(256) expand_bam4_kernel(const uint8_t* __restr
   }
 }
 
-// staged_reads / staged_flank: device copies of in->read_blob / in->flank_blob made ahead of time by trgt_locus_batch_submit (the
-// caller's pointers stay what the host glue reads); `ready`: the event behind those copies.
-static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const trgt_locus_batch_in* in, trgt_locus_batch_out* out,
-                           const uint8_t* staged_reads, const uint8_t* staged_flank, hipEvent_t ready) {
-  if (!c) return TRGT_ERR_INVALID;
-  if (!p || !in || !out) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: null argument");
-  const int64_t nl = in->n_loci;
+namespace {
+
+// ---- the one place that picks a kernel instantiation.  The one-wave kernels (one wavefront per locus) come in two sizes -- loci of at
+// most 64 reads, loci of up to GT_MAX_READS -- and, where they load the spanning reads, in a PRESEL form that takes the lists the purity
+// filter left instead of selecting the reads itself.  A family is the table k[big][presel] of its instantiations; the caller gives the
+// grid and the stream.
+template <typename... A> struct OneWave {
+  void (*k[2][2])(A...);
+  void launch(bool big, bool presel, dim3 grid, hipStream_t s, A... a) const { hipLaunchKernelGGL(k[big][presel], grid, dim3(64), 0, s, a...); }
+};
+constexpr int GT_BIG = gt::GT_MAX_READS;
+// (the two purity kernels run with the filter on only: one instantiation per size)
+const OneWave<gt::GtArgs, pur::PurityArgs> k_purity_select{{{pur::purity_select_kernel<64>, pur::purity_select_kernel<64>}, {pur::purity_select_kernel<GT_BIG>, pur::purity_select_kernel<GT_BIG>}}};
+const OneWave<gt::GtArgs, pur::PurityArgs> k_purity_filter{{{pur::purity_filter_kernel<64>, pur::purity_filter_kernel<64>}, {pur::purity_filter_kernel<GT_BIG>, pur::purity_filter_kernel<GT_BIG>}}};
+const OneWave<gt::GtArgs> k_genotype{{{gt::locus_genotype_kernel<64, 8 * 1024>, gt::locus_genotype_kernel<64, 8 * 1024, true>},
+                                      {gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS>, gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS, true>}}};
+const OneWave<gt::GtArgs, gt::FinishArgs> k_repair_finish{{{gt::repair_finish_kernel<64>, gt::repair_finish_kernel<64, true>}, {gt::repair_finish_kernel<GT_BIG>, gt::repair_finish_kernel<GT_BIG, true>}}};
+const OneWave<cl::ClArgs> k_cluster_front{{{cl::cluster_front_kernel<64>, cl::cluster_front_kernel<64, true>}, {cl::cluster_front_kernel<GT_BIG>, cl::cluster_front_kernel<GT_BIG, true>}}};
+// (the ward kernel's second argument is LDS_MAT: the distance matrix of a small locus fits the LDS -- it follows the size, not the filter)
+const OneWave<cl::ClArgs> k_cluster_ward{{{cl::cluster_ward_kernel<64, true>, cl::cluster_ward_kernel<64, true, true>}, {cl::cluster_ward_kernel<GT_BIG, false>, cl::cluster_ward_kernel<GT_BIG, false, true>}}};
+const OneWave<cl::ClArgs> k_cluster_round2{{{cl::cluster_round2_kernel<64>, cl::cluster_round2_kernel<64, true>}, {cl::cluster_round2_kernel<GT_BIG>, cl::cluster_round2_kernel<GT_BIG, true>}}};
+const OneWave<cl::ClArgs> k_cluster_finish{{{cl::cluster_finish_kernel<64>, cl::cluster_finish_kernel<64, true>}, {cl::cluster_finish_kernel<GT_BIG>, cl::cluster_finish_kernel<GT_BIG, true>}}};
+
+// the deep cluster list's buffers: the same slots as the shallow list's, second set
+inline int cl_slot(bool deep, int s) { return s + (deep ? (int)S_CLD_LIST - (int)S_CL_LIST : 0); }
+
+// A slab of pieces aligned to 256 bytes: add() hands back the offset of the next piece, d() / h() its address in the device / pinned copy
+struct Slab {
+  size_t total = 0; void *dev = nullptr, *host = nullptr;
+  size_t add(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
+  void* d(size_t o) const { return (uint8_t*)dev + o; }
+  void* h(size_t o) const { return (uint8_t*)host + o; }
+};
+
+// Puts the context's two streams back as they were when it was made: stages swap them, or put a side stream in their place, for the calls
+// they make meanwhile
+struct StreamGuard {
+  trgt_hip_ctx* c; hipStream_t s, s2;
+  explicit StreamGuard(trgt_hip_ctx* c_) : c(c_), s(c_->stream), s2(c_->stream2) {}
+  ~StreamGuard() { c->stream = s; c->stream2 = s2; }
+};
+
+// words of the pinned block P_CELLS (uint64_t each), and of trgt_hip_ctx::dbg_ns, the host-side phase timers (out->stats[9..13] are
+// DN_SETUP, DN_TABLES, DN_STAGE_A, DN_SELECT, DN_SPARE)
+enum CellWord { HC_FLANK_ALL = 0, HC_FLANK_FIRST = 1, HC_LIGHT_SHORTCUT = 2, HC_FILTER_OFFSETS = 4, HC_FILTER_KEPT = 5, HC_DEV_WFA = 6 };
+enum DbgNs { DN_SETUP = 0, DN_TABLES = 1, DN_STAGE_A = 2, DN_SELECT = 4, DN_SPARE = 5, DN_FRONT = 6, DN_BACK = 7 };
+
+// The state of one trgt_locus_batch call.  locus_batch_run (below) runs the stages in order; what a stage leaves for a later one is a
+// member, and every early return leaves through the destructor.
+struct LocusCall {
+  // device genotyper: inputs it needs beyond stage A's, and its outputs (device + pinned mirrors)
+  struct GtDev {
+    const uint64_t* lrb = nullptr; const uint8_t* ploidy = nullptr; const uint8_t* tr = nullptr; const uint64_t* tr_off = nullptr;
+    const uint32_t* tr_len = nullptr; const uint64_t* al_off = nullptr; const uint32_t* al_cap = nullptr; const uint8_t* geno = nullptr;
+    void *need = nullptr, *nal = nullptr, *blob = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr,
+         *toff = nullptr, *packed = nullptr;
+    const double* rq = nullptr;
+  };
+  struct GtHost { void *need = nullptr, *nal = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr, *toff = nullptr, *packed = nullptr; };
+  struct ClPlan { std::vector<uint32_t> list; std::vector<uint64_t> moff; uint64_t pairs = 0, reads = 0; uint32_t max_nr = 0; const uint32_t* d_list = nullptr; const uint64_t* d_moff = nullptr; };
+  struct RepairDev { void *vout = nullptr, *vlen = nullptr, *vscr = nullptr, *cig = nullptr, *clen = nullptr; };  // vote outputs and CIGARs of the device-side repair
+  struct K { uint32_t read, s, e; };  // a kept spanning read of a host-path locus
+  struct FlankRes { bool on = false; std::string repaired[2]; Seg al[2]; uint32_t ci[4] = {0, 0, 0, 0}; std::vector<int8_t> assignment; int rep_group[2] = {-1, -1}; };
+
+  // ---- arguments (staged_reads / staged_flank / ready: see locus_batch_run), sizes, modes
+  trgt_hip_ctx* const c; const trgt_locus_params* const p; const trgt_locus_batch_in* in; trgt_locus_batch_out* const out;
+  const uint8_t *staged_reads, *staged_flank; const hipEvent_t ready;
+  const int64_t nl; int64_t nr = 0; int F = 0;
+  bool done = false;  // nothing left to do (a call without loci or without reads)
+  trgt_locus_batch_in in_expanded; std::vector<uint64_t> expanded_off;  // TRGT_READS_BAM4: the batch with its reads expanded in HBM
+  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
+  FlankMeta flank_meta{};
+  // ---- clean-up state (see the destructor)
+  bool zeroed = false;
+  HmmPending *hmm_pending = nullptr, *hmm_pending2 = nullptr, *hmm_pendingB = nullptr;
+  hipEvent_t evA = nullptr;
+  std::unique_lock<std::mutex> stage_a_token;
+  std::optional<StreamGuard> host_streams;  // the host path's swap of the two streams
+  // ---- host tables and batch maxima
+  HostPool* pool = nullptr;
+  std::vector<uint64_t> piece_off; std::vector<uint32_t> read_locus, heavy_len;
+  uint64_t flank_total = 0, read_total = 0, tr_total = 0, allele_total = 0, max_locus_reads = 0; uint32_t max_read_len = 0, heavy_tlen_max = 0;
+  // ---- device and pinned memory: stage A's inputs and outputs, the result slab and the offsets of its pieces
+  UploadBatch ub;
+  const uint8_t *d_flank = nullptr, *d_reads = nullptr; const uint64_t *d_piece = nullptr, *d_roff = nullptr; const uint32_t *d_rlen = nullptr, *d_rloc = nullptr, *d_heavy = nullptr;
+  void *d_ss = nullptr, *d_se = nullptr, *d_hl = nullptr, *d_hr = nullptr, *h_ss = nullptr, *h_se = nullptr, *h_hl = nullptr, *h_hr = nullptr, *h_cells = nullptr;
+  Slab slab;
+  size_t o_ss = 0, o_se = 0, o_hl = 0, o_hr = 0, o_need = 0, o_nal = 0, o_alen = 0, o_ci = 0, o_nsp = 0, o_cls = 0, o_rank = 0, o_nspan = 0, o_toff = 0, o_flip = 0, o_gsz = 0,
+         o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0;
+  GtDev g; GtHost gh;
+  // ---- the device chains.  The cluster loci of the call: [0] the shallow list (at most GT_MAX_READS reads: the one-wave chain), [1] the
+  // deep list (beyond that, up to the context's cluster_max_reads: locus_cluster_deep.hpp), each with its own pair slots, job lists, arenas
+  // and counters
+  ClPlan clp[2];
+  std::vector<uint32_t>& cl_list = clp[0].list; std::vector<uint32_t>& cld_list = clp[1].list;
+  uint32_t cld_no_room = 0;  // deep loci inside the envelope that found no room in the call's budget (host path, stats[23])
+  // the deep size list: Genotyper::Size loci beyond GT_MAX_READS reads, up to the context's size_max_reads (locus_gt_deep.hpp)
+  std::vector<uint32_t> gsd_list; const uint32_t* d_gsd_list = nullptr;
+  gt::GtArgs ga; RepairDev rb;
+  const uint32_t* cl_counts_dev[2] = {nullptr, nullptr};  // count blocks of the device-side cluster genotyper (shallow, deep list), when it runs
+  cld::DeepArgs da, ds;  // (ds: the deep size list -- the same per-read lists, the loci of the two lists being different ones; its own counts)
+  // ---- stage C.  The motif-HMM tables depend only on the catalog: built on the device, behind stage A's launches
+  HmmModels models; HmmSlots hs;
+  hipStream_t upload_stream = nullptr;
+  std::vector<uint8_t> slot_skip;
+  std::vector<uint32_t> nsB; std::vector<double> puB;  // n_spans / purity of the second batch (merged into the outputs slot by slot)
+  std::vector<uint32_t> job_set, seq_len, nsp; std::vector<uint64_t> seq_off, span_off, count_off; std::vector<int64_t> slot; std::vector<double> pur;  // host-built lists of the device-genotyped loci
+  std::vector<uint32_t> js2, sl2, ns2; std::vector<uint64_t> so2, spo2, co2; std::vector<double> pu2; std::vector<int64_t> slot2;  // stage C, host-path loci
+  bool outputs_ready = false;  // (a call that waits for its purity jobs initialises the outputs during that wait)
+  bool published = false, hmm1_done = false;
+  // ---- the host path: its loci R, their kept reads, the flat segment arrays, the genotypers' work
+  std::vector<int64_t> R; int64_t nR = 0;
+  std::vector<uint8_t> need_a;  // need_host as the first HMM batch saw it (2 = waiting for the device-side repair: not its job)
+  const int32_t *sp_s = nullptr, *sp_e = nullptr;
+  std::vector<LocusWork> work; std::vector<uint64_t> sel_begin; std::vector<K> sel; std::vector<uint32_t> n_sel; std::vector<Scratch> scratch;
+  std::vector<uint64_t> seg_src, seg_dst; std::vector<uint32_t> seg_len, seg_read; std::vector<const uint8_t*> seg_ptr;
+  uint64_t n_seg = 0, seg_bytes = 0; void* h_seg = nullptr;
+  std::vector<ClusterLocus> cl_loci; std::vector<std::vector<Seg>> cl_trs; std::vector<FlankRes> fres;
+  // ---- clocks and counters of out->stats
+  bool tl_on = false;
+  int64_t t0 = 0, tA = 0, tB = 0, tC = 0, tHost = 0, tw_a = 0, th_begin = 0, th0 = 0;
+  int64_t stat_flank_jobs = 0, stat_flank_heavy = 0, stat_cons_jobs = 0, stat_spanning = 0, stat_hmm_jobs = 0, stat_ed_jobs = 0;
+
+  LocusCall(trgt_hip_ctx* c_, const trgt_locus_params* p_, const trgt_locus_batch_in* in_, trgt_locus_batch_out* out_, const uint8_t* staged_reads_,
+            const uint8_t* staged_flank_, hipEvent_t ready_)
+      : c(c_), p(p_), in(in_), out(out_), staged_reads(staged_reads_), staged_flank(staged_flank_), ready(ready_), nl(in_->n_loci),
+        stage_a_token(g_stage_a_mutex[(size_t)c_->device % 16], std::defer_lock), ub(c_, c_->stream) {}
+  ~LocusCall() {  // streams back in place, stage-A token, event, pending HMM batches, zero arena
+    host_streams.reset();
+    if (stage_a_token.owns_lock()) stage_a_token.unlock();
+    if (evA) (void)hipEventDestroy(evA);
+    for (HmmPending* q : {hmm_pendingB, hmm_pending2, hmm_pending}) if (q) hmm_pending_free(q);
+    if (zeroed) trgt::zero_end(c);
+  }
+
+  bool is_cluster(int64_t l) const { return in->genotyper && in->genotyper[l] == 1; }
+  uint64_t& cell(int w) { return ((uint64_t*)h_cells)[w]; }
+  void tl(const char* name) const { if (tl_on) fprintf(stderr, "[tl] %-28s %7.2f ms  ctx=%p\n", name, (double)(now_ns() - t0) / 1e6, (void*)c); }
+
+  // the stages, in the order locus_batch_run calls them
+  int check_args(), host_tables(), upload_tables(), plan_device_lists(), flush_uploads(), locate_flanks();
+  int repair_buffers(), purity_chain(), size_genotyper(), repair_chain(), cluster_chain(int deep), enqueue_results();
+  int wait_stage_a(), gather_host_segments(), host_front(), host_flank(), host_back(), host_stage_c(), collect_all();
+  void stage_c_job_lists(), select_host_reads();
+  // ... and what several of them call
+  void init_outputs();
+  int collect_ab(), collect_hmm1(), hmm1_enqueue(), hmm1_once(), publish();
+};
+int LocusCall::check_args() {
   if (nl < 0) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: negative n_loci");
   for (int64_t& v : c->size_deep_stats) v = 0;
-  if (nl == 0) return TRGT_OK;
+  if (nl == 0) { done = true; return TRGT_OK; }
   if (!in->flank_blob || !in->lf_off || !in->lf_len || !in->rf_off || !in->rf_len || !in->tr_blob || !in->tr_off || !in->tr_len ||
       !in->motif_blob || !in->motif_off || !in->set_motif_begin || !in->ploidy || !in->locus_read_begin || !in->read_blob ||
       !in->read_off || !in->read_len || !out->span_start || !out->span_end || !out->n_alleles || !out->allele_blob ||
@@ -554,16 +697,14 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       !out->read_rank || !out->spans3 || !out->span_off || !out->n_spans || !out->motif_counts || !out->count_off || !out->purity)
     return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: null field");
   TRGT_HIP_TRY(c, hipSetDevice(c->device));
-  struct ZeroGuard { trgt_hip_ctx* c; ~ZeroGuard() { trgt::zero_end(c); } } zero_guard{c};
+  zeroed = true;  // (from here on the destructor ends what zero_begin began, also where zero_begin itself fails)
   { const int zrc = trgt::zero_begin(c); if (zrc) return zrc; }  // (on the call's stream, in front of everything: every other stream forks off behind it)
-  const int F = p->flank_len;
+  F = p->flank_len;
   if (F <= 0) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: flank_len must be positive");
-  const int64_t nr = (int64_t)in->locus_read_begin[nl];
+  nr = (int64_t)in->locus_read_begin[nl];
   if (2 * nr > 0xFFFFFFF0ll) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_locus_batch: too many reads in one call");
   // reads handed over as BAM 4-bit codes: expanded in HBM, and from here on the batch is one with its reads on the device (the host
   // glue of the later stages fetches the few read segments it needs from there, as it does for a caller's device blob)
-  trgt_locus_batch_in in_expanded;
-  std::vector<uint64_t> expanded_off;
   if (in->read_encoding != TRGT_READS_ASCII && in->read_encoding != TRGT_READS_BAM4) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: read_encoding %d", in->read_encoding);
   if (in->read_encoding == TRGT_READS_BAM4 && nr > 0) {
     uint64_t packed_total = 0;
@@ -587,47 +728,33 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     in = &in_expanded;
     staged_reads = nullptr;
   }
+  return TRGT_OK;
+}
+void LocusCall::init_outputs() {
+  for (int64_t l = 0; l < nl; ++l) {
+    out->n_alleles[l] = 0; out->allele_len[2 * l] = out->allele_len[2 * l + 1] = 0; out->num_spanning[2 * l] = out->num_spanning[2 * l + 1] = 0;
+    if (out->gt_size) out->gt_size[2 * l] = out->gt_size[2 * l + 1] = 0;
+    if (out->flipped) out->flipped[l] = 0;
+  }
+  for (int64_t r = 0; r < nr; ++r) { out->classification[r] = -1; out->read_rank[r] = -1; out->span_start[r] = out->span_end[r] = -1; }
+  for (int64_t s = 0; s < 2 * nl; ++s) { out->n_spans[s] = 0; out->purity[s] = std::nan(""); }
+}
+// Thread pool, clock, and the host tables of stage A with the batch's maxima (a call without reads ends here)
+int LocusCall::host_tables() {
   int threads = p->host_threads > 0 ? p->host_threads : (int)std::max(1u, std::thread::hardware_concurrency());
   // a few microseconds of work per locus: more threads only add wake-up cost.  The device genotyper leaves the
   // host little to do (4 threads measure the same as 32, and large pools produce the occasional late wake-up).  That holds with
   // filter_impure_trs on as well since the filter runs on the device (locus_purity.hpp): the host then sees the same few handed-back loci
   // as in a call without the filter, so the cap no longer looks at min_read_qual -- only the all-host routes keep the large pool
   threads = std::min(threads, !c->knobs.host_genotyper && !(p->min_read_qual < 0.9 && c->knobs.host_purity) ? 8 : 32);
-  HostPool* pool = host_pool(c, threads);
-  const int64_t t0 = now_ns();
+  pool = host_pool(c, threads);
+  t0 = now_ns();
   c->tl_t0 = t0;
-  const bool tl_on = c->knobs.timeline;
-#define TL(name) do { if (tl_on) fprintf(stderr, "[tl] %-28s %7.2f ms  ctx=%p\n", name, (double)(now_ns() - t0) / 1e6, (void*)c); } while (0)
-  int64_t tA = 0, tB = 0, tC = 0, tHost = 0;
-  int64_t stat_flank_jobs = 0, stat_flank_heavy = 0, stat_cons_jobs = 0, stat_spanning = 0, stat_hmm_jobs = 0, stat_ed_jobs = 0;
-  auto init_outputs = [&]() {
-    for (int64_t l = 0; l < nl; ++l) {
-      out->n_alleles[l] = 0; out->allele_len[2 * l] = out->allele_len[2 * l + 1] = 0; out->num_spanning[2 * l] = out->num_spanning[2 * l + 1] = 0;
-      if (out->gt_size) out->gt_size[2 * l] = out->gt_size[2 * l + 1] = 0;
-      if (out->flipped) out->flipped[l] = 0;
-    }
-    for (int64_t r = 0; r < nr; ++r) { out->classification[r] = -1; out->read_rank[r] = -1; out->span_start[r] = out->span_end[r] = -1; }
-    for (int64_t s = 0; s < 2 * nl; ++s) { out->n_spans[s] = 0; out->purity[s] = std::nan(""); }
-  };
-  if (nr == 0) { init_outputs(); return TRGT_OK; }
-  bool outputs_ready = false;  // (a call that waits for its purity jobs initialises the outputs during that wait)
+  tl_on = c->knobs.timeline;
+  if (nr == 0) { init_outputs(); done = true; return TRGT_OK; }
   if (!c->stream2) TRGT_HIP_TRY(c, trgt::make_stream(c, &c->stream2));
-  // The motif-HMM tables depend only on the catalog: build them on a host thread while the GPU locates flanks.
-  // They are uploaded from the same thread (second stream), so stage C finds them in HBM.
-  // (the thread touches nothing of the context: its result and error live in `models`; the upload happens on this thread, below,
-  //  once stage A is on the GPU)
-  HmmModels models;  // the motif-HMM tables depend only on the catalog: built on the device, behind stage A's launches (below)
-  const hipStream_t upload_stream = c->stream2;  // (the "second stream" of this call, whichever of the two is current later on)
-  HmmPending *hmm_pending = nullptr, *hmm_pending2 = nullptr, *hmm_pendingB = nullptr;
-  struct PendGuard { HmmPending*& p; ~PendGuard() { if (p) hmm_pending_free(p); } } pend_guard{hmm_pending}, pend_guard2{hmm_pending2}, pend_guardB{hmm_pendingB};
-  std::vector<uint32_t> js2, sl2, ns2; std::vector<uint64_t> so2, spo2, co2; std::vector<double> pu2; std::vector<int64_t> slot2;  // stage C, host-path loci
-
-  // ---------------- stage A: flank location on the GPU (span_locater.rs:32-68), enqueued without host waits
-  std::vector<uint64_t> piece_off(2 * (size_t)nl);
-  std::vector<uint32_t> read_locus((size_t)nr), heavy_len((size_t)nl);
-  uint64_t flank_total = 0, read_total = 0, tr_total = 0, allele_total = 0;
-  uint32_t max_read_len = 0, heavy_tlen_max = 0;
-  uint64_t max_locus_reads = 0;
+  upload_stream = c->stream2;  // (the "second stream" of this call, whichever of the two is current later on)
+  piece_off.resize(2 * (size_t)nl); read_locus.resize((size_t)nr); heavy_len.resize((size_t)nl);
   {
     struct alignas(64) Acc { uint64_t flank = 0, read = 0, tr = 0, allele = 0, reads = 0; uint32_t max_len = 0, heavy = 0; };  // one cache line per worker
     std::vector<Acc> acc((size_t)pool->size());
@@ -657,33 +784,30 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       max_locus_reads = std::max(max_locus_reads, a.reads);
     }
   }
-  c->dbg_ns[0] = now_ns() - t0;  // set-up: thread pool, model thread, piece / read-locus tables
-  TL("set-up");
-  const bool reads_on_device = is_device_ptr(in->read_blob);
+  c->dbg_ns[DN_SETUP] = now_ns() - t0;  // set-up: thread pool, piece / read-locus tables
+  tl("set-up");
+  return TRGT_OK;
+}
+// The call's modes; stage A's inputs and the device genotyper's on their way up (one batch, flushed by flush_uploads); the result slab
+int LocusCall::upload_tables() {
+  reads_on_device = is_device_ptr(in->read_blob);
   // filter_impure_trs (tr.rs:37-50) sits between get_spanning_reads and the genotyper.  With it on, the selection, the purity batch and
   // the filter run on the device in front of the genotyper chains (locus_purity.hpp), which then load the filtered lists instead of
   // selecting the reads themselves; the loci they hand back are filtered by the host path below, like every locus under TRGT_HOST_PURITY
-  const bool impure_filter = p->min_read_qual < 0.9;
+  impure_filter = p->min_read_qual < 0.9;
   // (host reads are uploaded for the flank scan anyway: the device genotyper then works on that copy just as well)
-  const bool dev_gt = !c->knobs.host_genotyper && !(impure_filter && c->knobs.host_purity);
-  const bool presel = dev_gt && impure_filter;
-  auto is_cluster = [&](int64_t l) { return in->genotyper && in->genotyper[l] == 1; };
+  dev_gt = !c->knobs.host_genotyper && !(impure_filter && c->knobs.host_purity);
+  presel = dev_gt && impure_filter;
   // genotype_flank (tr.rs:69-75) can only change a genotype when reads carry haplotype tags or mismatch offsets
-  const bool flank_on = in->hp_tag != nullptr || (in->mismatch_offsets != nullptr && in->mismatch_off != nullptr);
-  const FlankMeta flank_meta{in->hp_tag, in->start_offset, in->end_offset, in->mismatch_offsets, in->mismatch_off};
+  flank_on = in->hp_tag != nullptr || (in->mismatch_offsets != nullptr && in->mismatch_off != nullptr);
+  flank_meta = FlankMeta{in->hp_tag, in->start_offset, in->end_offset, in->mismatch_offsets, in->mismatch_off};
   int rc;
-  const uint8_t *d_flank = nullptr, *d_reads = nullptr;
-  const uint64_t *d_piece = nullptr, *d_roff = nullptr;
-  const uint32_t *d_rlen = nullptr, *d_rloc = nullptr, *d_heavy = nullptr;
-  void *d_ss = nullptr, *d_se = nullptr, *d_hl = nullptr, *d_hr = nullptr;
-  void *h_ss = nullptr, *h_se = nullptr, *h_hl = nullptr, *h_hr = nullptr, *h_cells = nullptr;
   if (ready) TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, ready, 0));
   if (staged_flank) d_flank = staged_flank;
   else if ((rc = dev_in(c, S_FS_FLANK, in->flank_blob, (size_t)flank_total, &d_flank))) return rc;
   if (staged_reads) d_reads = staged_reads;
   else if ((rc = dev_in(c, S_FS_READS, in->read_blob, (size_t)read_total, &d_reads))) return rc;
   // the offset tables of stage A and of the device genotyper go up as ONE dispatch (a dozen separate ones were 0.35 ms in front of the scan)
-  UploadBatch ub(c, c->stream);
   if ((rc = dev_in(c, S_FS_JOBS, piece_off.data(), piece_off.size(), &d_piece, &ub)) ||
       (rc = dev_in(c, S_FS_LIST, in->read_off, (size_t)nr, &d_roff, &ub)) ||
       (rc = dev_in(c, S_FS_OUT0, in->read_len, (size_t)nr, &d_rlen, &ub)) ||
@@ -693,40 +817,16 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     return rc;
   // Everything stage A hands back to the host lives in ONE device slab mirrored by ONE pinned slab, so that it comes back in a single
   // copy: fourteen separate hipMemcpyAsync D2H cost the host 0.3 ms of completion handling right after the event wait.
-  struct Slab {
-    size_t total = 0;
-    size_t add(size_t bytes) { const size_t o = total; total += (bytes + 255) & ~(size_t)255; return o; }
-  } slab;
-  const size_t o_ss = slab.add((size_t)nr * 4), o_se = slab.add((size_t)nr * 4), o_hl = slab.add((size_t)nr), o_hr = slab.add((size_t)nr);
-  size_t o_need = 0, o_nal = 0, o_alen = 0, o_ci = 0, o_nsp = 0, o_cls = 0, o_rank = 0, o_nspan = 0, o_toff = 0, o_flip = 0, o_gsz = 0, o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0;
+  o_ss = slab.add((size_t)nr * 4), o_se = slab.add((size_t)nr * 4), o_hl = slab.add((size_t)nr), o_hr = slab.add((size_t)nr);
   if (dev_gt) {
     o_need = slab.add((size_t)nl); o_nal = slab.add((size_t)nl * 4); o_alen = slab.add(2 * (size_t)nl * 4); o_ci = slab.add(4 * (size_t)nl * 4);
     o_nsp = slab.add(2 * (size_t)nl * 4); o_cls = slab.add((size_t)nr * 4); o_rank = slab.add((size_t)nr * 4); o_nspan = slab.add((size_t)nl * 4);
     o_toff = slab.add((2 * (size_t)nl + 1) * 8); o_flip = slab.add((size_t)nl);
     o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
   }
-  void *d_slab = nullptr, *h_slab = nullptr;
-  if ((rc = dev_get(c, S_LOCUS_4, slab.total, &d_slab)) || (rc = pin_get(c, P_SPAN_S, slab.total, &h_slab))) return rc;
-  auto dsl = [&](size_t o) { return (void*)((uint8_t*)d_slab + o); };
-  auto hsl = [&](size_t o) { return (void*)((uint8_t*)h_slab + o); };
-  d_ss = dsl(o_ss); d_se = dsl(o_se); d_hl = dsl(o_hl); d_hr = dsl(o_hr);
-  h_ss = hsl(o_ss); h_se = hsl(o_se); h_hl = hsl(o_hl); h_hr = hsl(o_hr);
-  // device genotyper: inputs it needs beyond stage A's, and its outputs (device + pinned mirrors)
-  struct GtDev {
-    const uint64_t* lrb = nullptr; const uint8_t* ploidy = nullptr; const uint8_t* tr = nullptr; const uint64_t* tr_off = nullptr;
-    const uint32_t* tr_len = nullptr; const uint64_t* al_off = nullptr; const uint32_t* al_cap = nullptr; const uint8_t* geno = nullptr;
-    void *need = nullptr, *nal = nullptr, *blob = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr,
-         *toff = nullptr, *packed = nullptr;
-    const double* rq = nullptr;
-  } g;
-  // the cluster loci of the call: [0] the shallow list (at most GT_MAX_READS reads: the one-wave chain), [1] the deep list (beyond that,
-  // up to the context's cluster_max_reads: locus_cluster_deep.hpp), each with its own pair slots, job lists, arenas and counters
-  struct ClPlan { std::vector<uint32_t> list; std::vector<uint64_t> moff; uint64_t pairs = 0, reads = 0; uint32_t max_nr = 0; const uint32_t* d_list = nullptr; const uint64_t* d_moff = nullptr; } clp[2];
-  std::vector<uint32_t>& cl_list = clp[0].list; std::vector<uint32_t>& cld_list = clp[1].list;
-  uint32_t cld_no_room = 0;  // deep loci inside the envelope that found no room in the call's budget (host path, stats[23])
-  // the deep size list: Genotyper::Size loci beyond GT_MAX_READS reads, up to the context's size_max_reads (locus_gt_deep.hpp)
-  std::vector<uint32_t> gsd_list; const uint32_t* d_gsd_list = nullptr;
-  struct GtHost { void *need = nullptr, *nal = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr, *toff = nullptr, *packed = nullptr; } gh;
+  if ((rc = dev_get(c, S_LOCUS_4, slab.total, &slab.dev)) || (rc = pin_get(c, P_SPAN_S, slab.total, &slab.host))) return rc;
+  d_ss = slab.d(o_ss); d_se = slab.d(o_se); d_hl = slab.d(o_hl); d_hr = slab.d(o_hr);
+  h_ss = slab.h(o_ss); h_se = slab.h(o_se); h_hl = slab.h(o_hl); h_hr = slab.h(o_hr);
   if (dev_gt) {
     if ((rc = dev_in(c, S_GT_LRB, in->locus_read_begin, (size_t)nl + 1, &g.lrb, &ub)) || (rc = dev_in(c, S_GT_PLOIDY, in->ploidy, (size_t)nl, &g.ploidy, &ub)) ||
         (rc = dev_in(c, S_GT_TR, in->tr_blob, (size_t)tr_total, &g.tr, &ub)) || (rc = dev_in(c, S_GT_TROFF, in->tr_off, (size_t)nl, &g.tr_off, &ub)) ||
@@ -735,50 +835,61 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         (presel && in->read_qual && (rc = dev_in(c, S_PUR_RQ, in->read_qual, (size_t)nr, &g.rq, &ub))) ||
         (rc = dev_get(c, S_GT_BLOB, (size_t)allele_total + 16, &g.blob)) || (rc = dev_get(c, S_GT_PACKED, (size_t)allele_total + 16, &g.packed)))
       return rc;
-    // Genotyper::Cluster loci stay on the device too (locus_cluster_dev.hpp) unless TRGT_HOST_CLUSTER / TRGT_SPLIT_HMM say otherwise: the
-    // list of them and the first pair slot of each (condensed distance matrix, sized for all reads of the locus)
-    if (in->genotyper && !c->knobs.host_cluster && !c->knobs.split_hmm) {
-      // budget of the deep list: an eighth of the context's workspace limit, at most 2 GB (64 loci of 600 reads take 0.7 GB, one of 2 048
-      // reads 0.13 GB); TRGT_CLUSTER_ARENA_KB, the developer switch that shrinks the arenas, shrinks it to 64 times that many KB
-      const uint64_t cl_deep_pair_bytes = sizeof(JobDev) + 4 + 8;
-      uint64_t cl_deep_budget = std::min<uint64_t>(c->ws_limit / 8, 2ull << 30);
-      if (c->knobs.cluster_arena_kb > 0) cl_deep_budget = std::min<uint64_t>(cl_deep_budget, (uint64_t)c->knobs.cluster_arena_kb << 16);
-      for (int64_t l = 0; l < nl; ++l) {
-        if (in->genotyper[l] != 1 || in->ploidy[l] == 0) continue;
-        const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
-        if (n == 0) continue;
-        if (n > (uint64_t)gt::GT_MAX_READS) {
-          // the deep list: admitted in catalog order while the pair slots (32-bit output indices) and the call's budget last -- per pair an
-          // edit-distance job, a score and a matrix entry; the per-read lists are sized by the batch.  No room: the host path, as before.
-          if (n > (uint64_t)c->cluster_max_reads) continue;
-          const uint64_t np = n * (n - 1) / 2;
-          if (clp[1].pairs + np > 0x7FFFFFF0ull || (clp[1].pairs + np) * cl_deep_pair_bytes > cl_deep_budget) { ++cld_no_room; continue; }
-          clp[1].list.push_back((uint32_t)l); clp[1].moff.push_back(clp[1].pairs);
-          clp[1].pairs += np; clp[1].reads += n; clp[1].max_nr = std::max(clp[1].max_nr, (uint32_t)n);
-          continue;
-        }
-        clp[0].list.push_back((uint32_t)l); clp[0].moff.push_back(clp[0].pairs);
-        clp[0].pairs += n * (n - 1) / 2; clp[0].reads += n; clp[0].max_nr = std::max(clp[0].max_nr, (uint32_t)n);
+  }
+  return TRGT_OK;
+}
+// The loci the opt-in device chains take: shallow and deep cluster lists, deep size list (their tables join the upload batch)
+int LocusCall::plan_device_lists() {
+  if (!dev_gt) return TRGT_OK;
+  int rc;
+  // Genotyper::Cluster loci stay on the device too (locus_cluster_dev.hpp) unless TRGT_HOST_CLUSTER / TRGT_SPLIT_HMM say otherwise: the
+  // list of them and the first pair slot of each (condensed distance matrix, sized for all reads of the locus)
+  if (in->genotyper && !c->knobs.host_cluster && !c->knobs.split_hmm) {
+    // budget of the deep list: an eighth of the context's workspace limit, at most 2 GB (64 loci of 600 reads take 0.7 GB, one of 2 048
+    // reads 0.13 GB); TRGT_CLUSTER_ARENA_KB, the developer switch that shrinks the arenas, shrinks it to 64 times that many KB
+    const uint64_t cl_deep_pair_bytes = sizeof(JobDev) + 4 + 8;
+    uint64_t cl_deep_budget = std::min<uint64_t>(c->ws_limit / 8, 2ull << 30);
+    if (c->knobs.cluster_arena_kb > 0) cl_deep_budget = std::min<uint64_t>(cl_deep_budget, (uint64_t)c->knobs.cluster_arena_kb << 16);
+    for (int64_t l = 0; l < nl; ++l) {
+      if (in->genotyper[l] != 1 || in->ploidy[l] == 0) continue;
+      const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
+      if (n == 0) continue;
+      if (n > (uint64_t)gt::GT_MAX_READS) {
+        // the deep list: admitted in catalog order while the pair slots (32-bit output indices) and the call's budget last -- per pair an
+        // edit-distance job, a score and a matrix entry; the per-read lists are sized by the batch.  No room: the host path, as before.
+        if (n > (uint64_t)c->cluster_max_reads) continue;
+        const uint64_t np = n * (n - 1) / 2;
+        if (clp[1].pairs + np > 0x7FFFFFF0ull || (clp[1].pairs + np) * cl_deep_pair_bytes > cl_deep_budget) { ++cld_no_room; continue; }
+        clp[1].list.push_back((uint32_t)l); clp[1].moff.push_back(clp[1].pairs);
+        clp[1].pairs += np; clp[1].reads += n; clp[1].max_nr = std::max(clp[1].max_nr, (uint32_t)n);
+        continue;
       }
-      if (clp[0].pairs > 0x7FFFFFF0ull) { clp[0].list.clear(); clp[0].moff.clear(); }  // (pair slots are 32-bit output indices: the host path takes such a batch)
-      for (int d = 0; d < 2; ++d)
-        if (!clp[d].list.empty() && ((rc = dev_in(c, d ? S_CLD_LIST : S_CL_LIST, clp[d].list.data(), clp[d].list.size(), &clp[d].d_list, &ub)) ||
-                                     (rc = dev_in(c, S_CL_MOFF + (d ? (int)S_CLD_LIST - (int)S_CL_LIST : 0), clp[d].moff.data(), clp[d].moff.size(), &clp[d].d_moff, &ub))))
-          return rc;
+      clp[0].list.push_back((uint32_t)l); clp[0].moff.push_back(clp[0].pairs);
+      clp[0].pairs += n * (n - 1) / 2; clp[0].reads += n; clp[0].max_nr = std::max(clp[0].max_nr, (uint32_t)n);
     }
-    // (not under TRGT_SPLIT_HMM: its first HMM batch reads need_host right behind the one-wave genotyper, before the deep kernels have spoken)
-    if (c->size_max_reads > gt::GT_MAX_READS && !c->knobs.split_hmm) {
-      for (int64_t l = 0; l < nl; ++l) {
-        if (is_cluster(l) || in->ploidy[l] == 0) continue;
-        const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
-        if (n > (uint64_t)gt::GT_MAX_READS && n <= (uint64_t)c->size_max_reads) gsd_list.push_back((uint32_t)l);
-      }
-      if (!gsd_list.empty() && (rc = dev_in(c, S_GSD_LIST, gsd_list.data(), gsd_list.size(), &d_gsd_list, &ub))) return rc;
+    if (clp[0].pairs > 0x7FFFFFF0ull) { clp[0].list.clear(); clp[0].moff.clear(); }  // (pair slots are 32-bit output indices: the host path takes such a batch)
+    for (int d = 0; d < 2; ++d)
+      if (!clp[d].list.empty() && ((rc = dev_in(c, cl_slot(d, S_CL_LIST), clp[d].list.data(), clp[d].list.size(), &clp[d].d_list, &ub)) ||
+                                   (rc = dev_in(c, cl_slot(d, S_CL_MOFF), clp[d].moff.data(), clp[d].moff.size(), &clp[d].d_moff, &ub))))
+        return rc;
+  }
+  // (not under TRGT_SPLIT_HMM: its first HMM batch reads need_host right behind the one-wave genotyper, before the deep kernels have spoken)
+  if (c->size_max_reads > gt::GT_MAX_READS && !c->knobs.split_hmm) {
+    for (int64_t l = 0; l < nl; ++l) {
+      if (is_cluster(l) || in->ploidy[l] == 0) continue;
+      const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
+      if (n > (uint64_t)gt::GT_MAX_READS && n <= (uint64_t)c->size_max_reads) gsd_list.push_back((uint32_t)l);
     }
-    g.need = dsl(o_need); g.nal = dsl(o_nal); g.alen = dsl(o_alen); g.ci = dsl(o_ci); g.nsp = dsl(o_nsp); g.cls = dsl(o_cls); g.rank = dsl(o_rank);
-    g.nspan = dsl(o_nspan); g.toff = dsl(o_toff);
-    gh.need = hsl(o_need); gh.nal = hsl(o_nal); gh.alen = hsl(o_alen); gh.ci = hsl(o_ci); gh.nsp = hsl(o_nsp); gh.cls = hsl(o_cls); gh.rank = hsl(o_rank);
-    gh.nspan = hsl(o_nspan); gh.toff = hsl(o_toff);
+    if (!gsd_list.empty() && (rc = dev_in(c, S_GSD_LIST, gsd_list.data(), gsd_list.size(), &d_gsd_list, &ub))) return rc;
+  }
+  return TRGT_OK;
+}
+int LocusCall::flush_uploads() {
+  if (dev_gt) {
+    g.need = slab.d(o_need); g.nal = slab.d(o_nal); g.alen = slab.d(o_alen); g.ci = slab.d(o_ci); g.nsp = slab.d(o_nsp); g.cls = slab.d(o_cls); g.rank = slab.d(o_rank);
+    g.nspan = slab.d(o_nspan); g.toff = slab.d(o_toff);
+    gh.need = slab.h(o_need); gh.nal = slab.h(o_nal); gh.alen = slab.h(o_alen); gh.ci = slab.h(o_ci); gh.nsp = slab.h(o_nsp); gh.cls = slab.h(o_cls); gh.rank = slab.h(o_rank);
+    gh.nspan = slab.h(o_nspan); gh.toff = slab.h(o_toff);
   }
   if (!ub.staging.empty()) {  // the host copies into pinned staging, spread over the pool's threads
     auto& st = ub.staging;
@@ -788,27 +899,29 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     pool->parallel_for((int64_t)parts.size(), 1, [&](int64_t k, int) { const auto& q = parts[(size_t)k]; std::memcpy((uint8_t*)st[q[0]].pinned + q[1], (const uint8_t*)st[q[0]].src + q[1], q[2]); });
     st.clear();
   }
-  if ((rc = ub.flush())) return rc;
-  c->dbg_ns[1] = now_ns() - t0;  // + uploads of the offset tables, buffer (re)allocation
-  TL("tables uploaded, buffers ready");
+  if (int rc = ub.flush()) return rc;
+  c->dbg_ns[DN_TABLES] = now_ns() - t0;  // + uploads of the offset tables, buffer (re)allocation
+  tl("tables uploaded, buffers ready");
+  return TRGT_OK;
+}
+// Stage A on the GPU (span_locater.rs:32-68), enqueued without host waits, and the motif-HMM tables, which depend only on the catalog
+int LocusCall::locate_flanks() {
+  int rc;
   trgt_span_params sp; sp.flank_len = F; sp.min_flank_id_frac = p->min_flank_id_frac; sp.mism = p->mism; sp.gapo = p->gapo; sp.gape = p->gape;
-  hipEvent_t evA = nullptr;
-  struct EvGuard { hipEvent_t& e; ~EvGuard() { if (e) (void)hipEventDestroy(e); } } ev_guard{evA};
   TRGT_HIP_TRY(c, hipEventCreateWithFlags(&evA, hipEventDisableTiming));
-  ((uint64_t*)h_cells)[0] = ((uint64_t*)h_cells)[1] = ((uint64_t*)h_cells)[2] = 0;
+  cell(HC_FLANK_ALL) = cell(HC_FLANK_FIRST) = cell(HC_LIGHT_SHORTCUT) = 0;
   // Several contexts on one GPU (one host thread each, trgt_amd/driver.py) form a pipeline: while one call is in its tail (results
   // back, the loci of the host path, HMM) the next ones' flank location has the GPU.  TRGT_STAGE_LOCK=1 lets only one call per device
   // be in stage A at a time -- that was worth 2x while the tails were host-bound (first half of round 2); since the stage-C job list
   // and the model tables are made on the device, letting the stages overlap freely is 14 % faster on the 10k-locus batch (1.50 -> 1.71 M
   // loci/s with four contexts) and neutral on the others.
-  std::unique_lock<std::mutex> stage_a_token(g_stage_a_mutex[(size_t)c->device % 16], std::defer_lock);
   if (c->knobs.stage_lock) stage_a_token.lock();
   if ((rc = find_spans_device(c, sp, nl, nr, d_flank, d_piece, d_reads, d_roff, d_rlen, d_rloc, max_read_len, (int32_t*)d_ss, (int32_t*)d_se,
                               (uint8_t*)d_hl, (uint8_t*)d_hr, d_heavy, heavy_tlen_max > 0 ? heavy_tlen_max - 1 : 0)))
     return rc;
   if (c->last_wfa_cells_dev) { const int d2h_rc = trgt::d2h(c, h_cells, c->last_wfa_cells_dev, 24, c->stream); if (d2h_rc) return d2h_rc; }
-  ((uint64_t*)h_cells)[4] = ((uint64_t*)h_cells)[5] = 0;  // pre-filter: offsets computed, alignments kept
-  if (c->last_filter_cells_dev) { const int d2h_rc = trgt::d2h(c, (uint64_t*)h_cells + 4, c->last_filter_cells_dev, 16, c->stream); if (d2h_rc) return d2h_rc; }
+  cell(HC_FILTER_OFFSETS) = cell(HC_FILTER_KEPT) = 0;  // pre-filter: offsets computed, alignments kept
+  if (c->last_filter_cells_dev) { const int d2h_rc = trgt::d2h(c, &cell(HC_FILTER_OFFSETS), c->last_filter_cells_dev, 16, c->stream); if (d2h_rc) return d2h_rc; }
   // the motif-HMM tables: built on the device (one small upload and one kernel on the copy stream, which has nothing in front of it:
   // the second stream may be busy with the heavy flank alignments for milliseconds, and the copy engine serves the streams' copies in
   // the order they were issued)
@@ -819,408 +932,385 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     return models.err.empty() ? rc : fail(c, rc, "%s", models.err.c_str());
   TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_upload, 0));
   TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_upload, 0));
-  TL("models uploaded");
+  tl("models uploaded");
   // ---------------- stage C of the device-genotyped loci is enqueued behind the genotyper and before the host has seen its results: the
   // job list is resolved on the device (hmm_enqueue_slots), so the HMM kernels start the moment the genotyper ends instead of after a
   // host round trip (event wait, job lists, uploads: 0.8 ms of a 10k-locus call, 2.6 ms with mixed model sizes).  Two batches: the loci
   // the genotyper settles (on the call's stream, next to the consensus repair of the others on the second stream), then the repaired ones.
-  const bool use_slots = dev_gt && models.rc == 0 && models.d_sets && !is_device_ptr(out->spans3) && !c->knobs.host_hmm_lists;
-  std::vector<uint8_t> slot_skip;
-  HmmSlots hs;
-  std::vector<uint32_t> nsB; std::vector<double> puB;  // n_spans / purity of the second batch (merged into the outputs slot by slot)
+  use_slots = dev_gt && models.rc == 0 && models.d_sets && !is_device_ptr(out->spans3) && !c->knobs.host_hmm_lists;
   if (use_slots) {
     hs.n_loci = nl; hs.cap = out->allele_cap; hs.seq_off = out->allele_off; hs.seq_blob_dev = (const uint8_t*)g.blob;
     hs.d_n_alleles = (const int32_t*)g.nal; hs.d_allele_len = (const uint32_t*)g.alen;
     if (in->genotyper && cl_list.empty() && cld_list.empty()) { slot_skip.assign(in->genotyper, in->genotyper + nl); for (auto& v : slot_skip) v = v == 1; hs.host_skip = slot_skip.data(); }
   }
-  if (dev_gt) {
-    gt::GtArgs ga;
-    ga.reads = d_reads; ga.read_off = d_roff; ga.read_len = d_rlen; ga.locus_read_begin = g.lrb;
-    ga.span_start = (const int32_t*)d_ss; ga.span_end = (const int32_t*)d_se;
-    ga.ploidy = g.ploidy; ga.tr_blob = g.tr; ga.tr_off = g.tr_off; ga.tr_len = g.tr_len; ga.allele_off = g.al_off; ga.allele_cap = g.al_cap;
-    ga.n_loci = nl; ga.flank_len = F; ga.max_depth = p->max_depth;
-    ga.need_host = (uint8_t*)g.need; ga.n_alleles = (int32_t*)g.nal; ga.allele_blob = (uint8_t*)g.blob; ga.allele_len = (uint32_t*)g.alen;
-    ga.ci = (int32_t*)g.ci; ga.num_spanning = (int32_t*)g.nsp; ga.classification = (int32_t*)g.cls; ga.read_rank = (int32_t*)g.rank;
-    ga.n_spanning_reads = (uint32_t*)g.nspan; ga.flipped = (uint8_t*)dsl(o_flip);
-    ga.gt_size = (int32_t*)dsl(o_gsz); ga.skip_b = (uint8_t*)dsl(o_skipb); ga.genotyper = g.geno;
-    // ---- stage B on the device for the loci whose pick lacks majority support (locus_gt.hpp): job list, vote groups and the
-    //      record of the decisions are written by the genotyper; the alignment kernel, the column voting and the finishing kernel
-    //      follow on the same stream, and the host first hears of these loci when they are done.  TRGT_HOST_REPAIR=1: the host path.
-    gt::RepairBufs& rp = ga.rp;
-    std::memset(&rp, 0, sizeof rp);
-    void *d_vout = nullptr, *d_vlen = nullptr, *d_vscr = nullptr, *d_rcig = nullptr, *d_rclen = nullptr;
-    const bool dev_repair = !c->knobs.host_repair;
-    const uint32_t* cl_counts_dev[2] = {nullptr, nullptr};  // count blocks of the device-side cluster genotyper (shallow, deep list), when it runs
-    // the deep list's selection: its lists and merge records are per read of the batch, like ClArgs::cls (one slab); with the purity
-    // filter on, its select / filter kernels run next to the shallow ones below and share their purity batch
-    cld::DeepArgs da, ds;  // (ds: the deep size list -- the same per-read lists, the loci of the two lists being different ones; its own counts)
-    std::memset(&da, 0, sizeof da); std::memset(&ds, 0, sizeof ds);
-    if (!cld_list.empty() || !gsd_list.empty()) {
-      size_t dt = 0;
-      auto dadd = [&](size_t bytes) { const size_t o = dt; dt += (bytes + 255) & ~(size_t)255; return o; };
-      const size_t do_read = dadd((size_t)nr * 4), do_start = dadd((size_t)nr * 4), do_len = dadd((size_t)nr * 4), do_job = dadd((size_t)nr * 4), do_n = dadd(cld_list.size() * 4), do_n2 = dadd(gsd_list.size() * 4),
-                   do_ma = dadd((size_t)nr * 2), do_mb = dadd((size_t)nr * 2), do_md = dadd((size_t)nr * 8);
-      void* d_ds = nullptr;
-      if ((rc = dev_get(c, S_CLD_SEL, dt, &d_ds))) return rc;
-      auto dsl2 = [&](size_t o) { return (void*)((uint8_t*)d_ds + o); };
-      da.sel_read = (uint32_t*)dsl2(do_read); da.sel_start = (uint32_t*)dsl2(do_start); da.sel_len = (uint32_t*)dsl2(do_len); da.sel_job = (uint32_t*)dsl2(do_job);
-      da.n_sel = (uint32_t*)dsl2(do_n); da.mg_a = (uint16_t*)dsl2(do_ma); da.mg_b = (uint16_t*)dsl2(do_mb); da.mg_d = (double*)dsl2(do_md);
-      da.c.list = clp[1].d_list; da.c.n_list = (uint32_t)cld_list.size();
-      ds.sel_read = da.sel_read; ds.sel_start = da.sel_start; ds.sel_len = da.sel_len; ds.sel_job = da.sel_job; ds.n_sel = (uint32_t*)dsl2(do_n2);
-      ds.c.list = d_gsd_list; ds.c.n_list = (uint32_t)gsd_list.size();
+  return TRGT_OK;
+}
+int LocusCall::repair_buffers() {
+  if (!dev_gt) return TRGT_OK;
+  int rc;
+  ga.reads = d_reads; ga.read_off = d_roff; ga.read_len = d_rlen; ga.locus_read_begin = g.lrb;
+  ga.span_start = (const int32_t*)d_ss; ga.span_end = (const int32_t*)d_se;
+  ga.ploidy = g.ploidy; ga.tr_blob = g.tr; ga.tr_off = g.tr_off; ga.tr_len = g.tr_len; ga.allele_off = g.al_off; ga.allele_cap = g.al_cap;
+  ga.n_loci = nl; ga.flank_len = F; ga.max_depth = p->max_depth;
+  ga.need_host = (uint8_t*)g.need; ga.n_alleles = (int32_t*)g.nal; ga.allele_blob = (uint8_t*)g.blob; ga.allele_len = (uint32_t*)g.alen;
+  ga.ci = (int32_t*)g.ci; ga.num_spanning = (int32_t*)g.nsp; ga.classification = (int32_t*)g.cls; ga.read_rank = (int32_t*)g.rank;
+  ga.n_spanning_reads = (uint32_t*)g.nspan; ga.flipped = (uint8_t*)slab.d(o_flip);
+  ga.gt_size = (int32_t*)slab.d(o_gsz); ga.skip_b = (uint8_t*)slab.d(o_skipb); ga.genotyper = g.geno;
+  // ---- stage B on the device for the loci whose pick lacks majority support (locus_gt.hpp): job list, vote groups and the
+  //      record of the decisions are written by the genotyper; the alignment kernel, the column voting and the finishing kernel
+  //      follow on the same stream, and the host first hears of these loci when they are done.  TRGT_HOST_REPAIR=1: the host path.
+  gt::RepairBufs& rp = ga.rp;
+  std::memset(&rp, 0, sizeof rp);
+  dev_repair = !c->knobs.host_repair;
+  // the deep list's selection: its lists and merge records are per read of the batch, like ClArgs::cls (one slab); with the purity
+  // filter on, its select / filter kernels run next to the shallow ones below and share their purity batch
+  std::memset(&da, 0, sizeof da); std::memset(&ds, 0, sizeof ds);
+  if (!cld_list.empty() || !gsd_list.empty()) {
+    Slab dsel;
+    const size_t do_read = dsel.add((size_t)nr * 4), do_start = dsel.add((size_t)nr * 4), do_len = dsel.add((size_t)nr * 4), do_job = dsel.add((size_t)nr * 4), do_n = dsel.add(cld_list.size() * 4), do_n2 = dsel.add(gsd_list.size() * 4),
+                 do_ma = dsel.add((size_t)nr * 2), do_mb = dsel.add((size_t)nr * 2), do_md = dsel.add((size_t)nr * 8);
+    if ((rc = dev_get(c, S_CLD_SEL, dsel.total, &dsel.dev))) return rc;
+    da.sel_read = (uint32_t*)dsel.d(do_read); da.sel_start = (uint32_t*)dsel.d(do_start); da.sel_len = (uint32_t*)dsel.d(do_len); da.sel_job = (uint32_t*)dsel.d(do_job);
+    da.n_sel = (uint32_t*)dsel.d(do_n); da.mg_a = (uint16_t*)dsel.d(do_ma); da.mg_b = (uint16_t*)dsel.d(do_mb); da.mg_d = (double*)dsel.d(do_md);
+    da.c.list = clp[1].d_list; da.c.n_list = (uint32_t)cld_list.size();
+    ds.sel_read = da.sel_read; ds.sel_start = da.sel_start; ds.sel_len = da.sel_len; ds.sel_job = da.sel_job; ds.n_sel = (uint32_t*)dsel.d(do_n2);
+    ds.c.list = d_gsd_list; ds.c.n_list = (uint32_t)gsd_list.size();
+  }
+  if (dev_repair) {
+    void* const z_rpc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
+    if (z_rpc) rp.counts = (uint32_t*)z_rpc;
+    else { void* d_cnt = nullptr; if ((rc = dev_get(c, S_RP_COUNTS, 256, &d_cnt))) return rc; rp.counts = (uint32_t*)d_cnt; }
+    rp.cap_groups = (uint32_t)std::min<int64_t>(2 * nl, 0x7FFFFFFF); rp.cap_jobs = (uint32_t)nr;
+    // (segments beyond what the register-resident kernels take go to the generic engine, whose workgroups are bounded by ws_budget: a batch of
+    //  10-kb alleles -- cfg3 -- is repaired on the device too instead of going back to the host: one-context call 22.2 -> 14.4 ms)
+    const uint32_t seg_auto = std::min<uint32_t>(16384u, std::max<uint32_t>(1024u, max_read_len > 2u * (uint32_t)F ? max_read_len - 2u * (uint32_t)F : 0u));
+    rp.max_seg = c->knobs.repair_max_seg > 0 ? (uint32_t)std::max(16, c->knobs.repair_max_seg) : seg_auto; rp.vote_lds_pos = (uint32_t)vote::VOTE_LDS_POS;
+    // room for the typical batch (a few per cent of the loci, segments of a few hundred bases); a locus that finds none takes the host path
+    rp.cap_cigar = std::min<uint64_t>((uint64_t)nr * (2ull * rp.max_seg + 1), 32ull << 20);       // words
+    rp.cap_out = std::min<uint64_t>((uint64_t)nr * (rp.max_seg + 16ull) + 64, 256ull << 20);      // bytes
+    rp.cap_scratch = std::min<uint64_t>(3ull * (uint64_t)nr + 3ull * (uint64_t)rp.cap_groups * (rp.max_seg + 1ull) + 64, 32ull << 20);  // words
+    void *d_g = nullptr, *d_j = nullptr, *d_l = nullptr, *d_p = nullptr;
+    if ((rc = dev_get(c, S_RP_GROUPS, (size_t)rp.cap_groups * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, S_RP_JOBS, (size_t)rp.cap_jobs * sizeof(JobDev), &d_j)) ||
+        (rc = dev_get(c, S_RP_LOCI, (size_t)nl * 4, &d_l)) || (rc = dev_get(c, S_RP_PEND, (size_t)nl * sizeof(gt::RepairPend), &d_p)) ||
+        (rc = dev_get(c, S_RP_CIGAR, (size_t)rp.cap_cigar * 4, &rb.cig)) || (rc = dev_get(c, S_RP_CLEN, (size_t)rp.cap_jobs * 4, &rb.clen)) ||
+        (rc = dev_get(c, S_RP_VOUT, (size_t)rp.cap_out + 16, &rb.vout)) || (rc = dev_get(c, S_RP_VLEN, (size_t)rp.cap_groups * 4, &rb.vlen)) ||
+        (rc = dev_get(c, S_RP_VSCR, (size_t)rp.cap_scratch * 4 + 16, &rb.vscr)))
+      return rc;
+    rp.groups = (gt::RGroup*)d_g; rp.jobs = (JobDev*)d_j; rp.loci = (uint32_t*)d_l; rp.pend = (gt::RepairPend*)d_p;
+    if (!z_rpc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, rp.counts, (uint32_t)gt::RC_WORDS);
+  }
+  small_gt = max_locus_reads <= 64;
+  return TRGT_OK;
+}
+int LocusCall::purity_chain() {
+  if (!presel) return TRGT_OK;
+  int rc;
+  // ---- filter_impure_trs in front of the genotypers (locus_purity.hpp): selection, purity jobs, HMM batch, filter.  The job list is
+  //      resolved by the host from the select kernel's compact output in pinned memory -- one wait for the spans (which the call
+  //      waits for anyway, later) and one for the purity batch; the purities stay in HBM, indexed by job, and the filter kernel
+  //      finds them through the job index of every selected slot
+  ga.sel_read = ga.sel_start = ga.sel_len = ga.n_sel = nullptr;
+  Slab ps;
+  const size_t po_read = ps.add((size_t)nr * 4), po_start = ps.add((size_t)nr * 4), po_len = ps.add((size_t)nr * 4), po_job = ps.add((size_t)nr * 4), po_n = ps.add((size_t)nl * 4),
+               po_pur = ps.add((size_t)nr * 8), po_nsp = ps.add((size_t)nr * 4), po_cnt = ps.add(64);
+  void* h_pj = nullptr;
+  if ((rc = dev_get(c, S_PUR_SLAB, ps.total, &ps.dev)) || (rc = pin_get(c, P_PUR_JOBS, 64 + (size_t)nr * sizeof(pur::PurityJob), &h_pj))) return rc;
+  pur::PurityArgs pa;
+  std::memset(&pa, 0, sizeof pa);
+  pa.read_qual = g.rq; pa.skip_cluster = cl_list.empty() ? 1 : 0;
+  pa.sel_read = (uint32_t*)ps.d(po_read); pa.sel_start = (uint32_t*)ps.d(po_start); pa.sel_len = (uint32_t*)ps.d(po_len); pa.sel_job = (uint32_t*)ps.d(po_job);
+  pa.n_sel = (uint32_t*)ps.d(po_n); pa.purity = (const double*)ps.d(po_pur);
+  pa.jobs = (pur::PurityJob*)((uint8_t*)h_pj + 64); pa.cap_jobs = (uint32_t)nr;
+  void* const z_cnt = zero_take(c, 64);  // (cleared with the call's zero arena; else by the kernel below)
+  pa.counter = z_cnt ? (uint32_t*)z_cnt : (uint32_t*)ps.d(po_cnt);
+  if (!z_cnt) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, pa.counter, 1u);
+  const dim3 pgrid((unsigned)nl);
+  k_purity_select.launch(!small_gt, true, pgrid, c->stream, ga, pa);
+  if (!cld_list.empty()) {  // (behind the shallow selection: it leaves the deep loci alone, and both append to one job list)
+    da.c.g = ga; da.purity_on = 1; da.read_qual = pa.read_qual; da.pj_counter = pa.counter; da.pj = pa.jobs; da.pj_cap = pa.cap_jobs; da.purity = pa.purity;
+    hipLaunchKernelGGL(cld::deep_select_kernel, dim3(da.c.n_list), dim3(cld::DW), 0, c->stream, da);
+  }
+  if (!gsd_list.empty()) {  // (the deep size list likewise)
+    ds.c.g = ga; ds.purity_on = 1; ds.read_qual = pa.read_qual; ds.pj_counter = pa.counter; ds.pj = pa.jobs; ds.pj_cap = pa.cap_jobs; ds.purity = pa.purity;
+    hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
+  }
+  TRGT_HIP_TRY(c, hipGetLastError());
+  *(uint32_t*)h_pj = 0;
+  { const int d2h_rc = trgt::d2h(c, h_pj, pa.counter, 4, c->stream); if (d2h_rc) return d2h_rc; }
+  tl_mark(c, "purity selection enqueued");
+  init_outputs(); outputs_ready = true;  // host-only work: done while the GPU locates the flanks
+  const int64_t tw_p = now_ns();
+  TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
+  tA += now_ns() - tw_p;
+  tl("purity jobs listed");
+  const int64_t n_pj = (int64_t)std::min<uint32_t>(*(const uint32_t*)h_pj, pa.cap_jobs);
+  if (n_pj > 0) {
+    const pur::PurityJob* pj = pa.jobs;
+    std::vector<uint32_t> pj_set((size_t)n_pj), pj_len((size_t)n_pj); std::vector<uint64_t> pj_off((size_t)n_pj), pj_cnt_off((size_t)n_pj);
+    uint64_t cnt_total = 0;
+    for (int64_t j = 0; j < n_pj; ++j) {
+      if ((int64_t)pj[j].locus >= nl) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: purity job %lld names locus %u", (long long)j, pj[j].locus);
+      pj_set[(size_t)j] = pj[j].locus; pj_off[(size_t)j] = pj[j].seq_off; pj_len[(size_t)j] = pj[j].seq_len;
+      pj_cnt_off[(size_t)j] = cnt_total; cnt_total += in->set_motif_begin[pj[j].locus + 1] - in->set_motif_begin[pj[j].locus];
     }
-    if (dev_repair) {
-      void* const z_rpc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
-      if (z_rpc) rp.counts = (uint32_t*)z_rpc;
-      else { void* d_cnt = nullptr; if ((rc = dev_get(c, S_RP_COUNTS, 256, &d_cnt))) return rc; rp.counts = (uint32_t*)d_cnt; }
-      rp.cap_groups = (uint32_t)std::min<int64_t>(2 * nl, 0x7FFFFFFF); rp.cap_jobs = (uint32_t)nr;
-      // (segments beyond what the register-resident kernels take go to the generic engine, whose workgroups are bounded by ws_budget: a batch of
-      //  10-kb alleles -- cfg3 -- is repaired on the device too instead of going back to the host: one-context call 22.2 -> 14.4 ms)
-      const uint32_t seg_auto = std::min<uint32_t>(16384u, std::max<uint32_t>(1024u, max_read_len > 2u * (uint32_t)F ? max_read_len - 2u * (uint32_t)F : 0u));
-      rp.max_seg = c->knobs.repair_max_seg > 0 ? (uint32_t)std::max(16, c->knobs.repair_max_seg) : seg_auto; rp.vote_lds_pos = (uint32_t)vote::VOTE_LDS_POS;
-      // room for the typical batch (a few per cent of the loci, segments of a few hundred bases); a locus that finds none takes the host path
-      rp.cap_cigar = std::min<uint64_t>((uint64_t)nr * (2ull * rp.max_seg + 1), 32ull << 20);       // words
-      rp.cap_out = std::min<uint64_t>((uint64_t)nr * (rp.max_seg + 16ull) + 64, 256ull << 20);      // bytes
-      rp.cap_scratch = std::min<uint64_t>(3ull * (uint64_t)nr + 3ull * (uint64_t)rp.cap_groups * (rp.max_seg + 1ull) + 64, 32ull << 20);  // words
-      void *d_g = nullptr, *d_j = nullptr, *d_l = nullptr, *d_p = nullptr;
-      if ((rc = dev_get(c, S_RP_GROUPS, (size_t)rp.cap_groups * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, S_RP_JOBS, (size_t)rp.cap_jobs * sizeof(JobDev), &d_j)) ||
-          (rc = dev_get(c, S_RP_LOCI, (size_t)nl * 4, &d_l)) || (rc = dev_get(c, S_RP_PEND, (size_t)nl * sizeof(gt::RepairPend), &d_p)) ||
-          (rc = dev_get(c, S_RP_CIGAR, (size_t)rp.cap_cigar * 4, &d_rcig)) || (rc = dev_get(c, S_RP_CLEN, (size_t)rp.cap_jobs * 4, &d_rclen)) ||
-          (rc = dev_get(c, S_RP_VOUT, (size_t)rp.cap_out + 16, &d_vout)) || (rc = dev_get(c, S_RP_VLEN, (size_t)rp.cap_groups * 4, &d_vlen)) ||
-          (rc = dev_get(c, S_RP_VSCR, (size_t)rp.cap_scratch * 4 + 16, &d_vscr)))
-        return rc;
-      rp.groups = (gt::RGroup*)d_g; rp.jobs = (JobDev*)d_j; rp.loci = (uint32_t*)d_l; rp.pend = (gt::RepairPend*)d_p;
-      if (!z_rpc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, rp.counts, (uint32_t)gt::RC_WORDS);
-    }
-    const bool small_gt = max_locus_reads <= 64;
-    if (presel) {
-      // ---- filter_impure_trs in front of the genotypers (locus_purity.hpp): selection, purity jobs, HMM batch, filter.  The job list is
-      //      resolved by the host from the select kernel's compact output in pinned memory -- one wait for the spans (which the call
-      //      waits for anyway, later) and one for the purity batch; the purities stay in HBM, indexed by job, and the filter kernel
-      //      finds them through the job index of every selected slot
-      ga.sel_read = ga.sel_start = ga.sel_len = ga.n_sel = nullptr;
-      size_t pt = 0;
-      auto padd = [&](size_t bytes) { const size_t o = pt; pt += (bytes + 255) & ~(size_t)255; return o; };
-      const size_t po_read = padd((size_t)nr * 4), po_start = padd((size_t)nr * 4), po_len = padd((size_t)nr * 4), po_job = padd((size_t)nr * 4), po_n = padd((size_t)nl * 4),
-                   po_pur = padd((size_t)nr * 8), po_nsp = padd((size_t)nr * 4), po_cnt = padd(64);
-      void *d_ps = nullptr, *h_pj = nullptr;
-      if ((rc = dev_get(c, S_PUR_SLAB, pt, &d_ps)) || (rc = pin_get(c, P_PUR_JOBS, 64 + (size_t)nr * sizeof(pur::PurityJob), &h_pj))) return rc;
-      auto psl = [&](size_t o) { return (void*)((uint8_t*)d_ps + o); };
-      pur::PurityArgs pa;
-      std::memset(&pa, 0, sizeof pa);
-      pa.read_qual = g.rq; pa.skip_cluster = cl_list.empty() ? 1 : 0;
-      pa.sel_read = (uint32_t*)psl(po_read); pa.sel_start = (uint32_t*)psl(po_start); pa.sel_len = (uint32_t*)psl(po_len); pa.sel_job = (uint32_t*)psl(po_job);
-      pa.n_sel = (uint32_t*)psl(po_n); pa.purity = (const double*)psl(po_pur);
-      pa.jobs = (pur::PurityJob*)((uint8_t*)h_pj + 64); pa.cap_jobs = (uint32_t)nr;
-      void* const z_cnt = zero_take(c, 64);  // (cleared with the call's zero arena; else by the kernel below)
-      pa.counter = z_cnt ? (uint32_t*)z_cnt : (uint32_t*)psl(po_cnt);
-      if (!z_cnt) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, pa.counter, 1u);
-      const dim3 pgrid((unsigned)nl);
-      if (small_gt) hipLaunchKernelGGL((pur::purity_select_kernel<64>), pgrid, dim3(64), 0, c->stream, ga, pa);
-      else hipLaunchKernelGGL((pur::purity_select_kernel<gt::GT_MAX_READS>), pgrid, dim3(64), 0, c->stream, ga, pa);
-      if (!cld_list.empty()) {  // (behind the shallow selection: it leaves the deep loci alone, and both append to one job list)
-        da.c.g = ga; da.purity_on = 1; da.read_qual = pa.read_qual; da.pj_counter = pa.counter; da.pj = pa.jobs; da.pj_cap = pa.cap_jobs; da.purity = pa.purity;
-        hipLaunchKernelGGL(cld::deep_select_kernel, dim3(da.c.n_list), dim3(cld::DW), 0, c->stream, da);
-      }
-      if (!gsd_list.empty()) {  // (the deep size list likewise)
-        ds.c.g = ga; ds.purity_on = 1; ds.read_qual = pa.read_qual; ds.pj_counter = pa.counter; ds.pj = pa.jobs; ds.pj_cap = pa.cap_jobs; ds.purity = pa.purity;
-        hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
-      }
-      TRGT_HIP_TRY(c, hipGetLastError());
-      *(uint32_t*)h_pj = 0;
-      { const int d2h_rc = trgt::d2h(c, h_pj, pa.counter, 4, c->stream); if (d2h_rc) return d2h_rc; }
-      tl_mark(c, "purity selection enqueued");
-      init_outputs(); outputs_ready = true;  // host-only work: done while the GPU locates the flanks
-      const int64_t tw_p = now_ns();
-      TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
-      tA += now_ns() - tw_p;
-      TL("purity jobs listed");
-      const int64_t n_pj = (int64_t)std::min<uint32_t>(*(const uint32_t*)h_pj, pa.cap_jobs);
-      if (n_pj > 0) {
-        const pur::PurityJob* pj = pa.jobs;
-        std::vector<uint32_t> pj_set((size_t)n_pj), pj_len((size_t)n_pj); std::vector<uint64_t> pj_off((size_t)n_pj), pj_cnt_off((size_t)n_pj);
-        uint64_t cnt_total = 0;
-        for (int64_t j = 0; j < n_pj; ++j) {
-          if ((int64_t)pj[j].locus >= nl) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: purity job %lld names locus %u", (long long)j, pj[j].locus);
-          pj_set[(size_t)j] = pj[j].locus; pj_off[(size_t)j] = pj[j].seq_off; pj_len[(size_t)j] = pj[j].seq_len;
-          pj_cnt_off[(size_t)j] = cnt_total; cnt_total += in->set_motif_begin[pj[j].locus + 1] - in->set_motif_begin[pj[j].locus];
-        }
-        void* d_pcnt = nullptr;
-        if ((rc = dev_get(c, S_PUR_CNT, ((size_t)cnt_total + 1) * 4, &d_pcnt))) return rc;
-        const int64_t tc0 = now_ns();
-        // (device pointers for every result: nothing is copied back, the call returns when the kernels are through)
-        rc = hmm_batch_impl(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, n_pj, pj_set.data(), d_reads, pj_off.data(), pj_len.data(),
-                            nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t*)psl(po_nsp), (uint32_t*)d_pcnt, pj_cnt_off.data(), (double*)psl(po_pur), nullptr, nullptr);
-        if (rc) return rc;
-        tC += now_ns() - tc0;
-        stat_hmm_jobs += n_pj;
-        TL("purity batch done");
-      }
-      if (small_gt) hipLaunchKernelGGL((pur::purity_filter_kernel<64>), pgrid, dim3(64), 0, c->stream, ga, pa);
-      else hipLaunchKernelGGL((pur::purity_filter_kernel<gt::GT_MAX_READS>), pgrid, dim3(64), 0, c->stream, ga, pa);
-      if (!cld_list.empty()) hipLaunchKernelGGL(cld::deep_filter_kernel, dim3(da.c.n_list), dim3(cld::DW), 0, c->stream, da);
-      if (!gsd_list.empty()) hipLaunchKernelGGL(cld::deep_filter_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      ga.sel_read = pa.sel_read; ga.sel_start = pa.sel_start; ga.sel_len = pa.sel_len; ga.n_sel = pa.n_sel;
-      if (small_gt) hipLaunchKernelGGL((gt::locus_genotype_kernel<64, 8 * 1024, true>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
-      else hipLaunchKernelGGL((gt::locus_genotype_kernel<gt::GT_MAX_READS, gt::GT_SEG_LDS, true>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
-    }
-    else if (small_gt) hipLaunchKernelGGL((gt::locus_genotype_kernel<64, 8 * 1024>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
-    else hipLaunchKernelGGL((gt::locus_genotype_kernel<gt::GT_MAX_READS, gt::GT_SEG_LDS>), dim3((unsigned)nl), dim3(64), 0, c->stream, ga);
-    if (!gsd_list.empty()) {
-      // ---- the deep size list, behind the one-wave genotyper (which marked these loci need_host = 1): selection unless it ran in front
-      //      of the purity batch, then the workgroup-wide genotyper; its loci without majority support join the repair chain below
-      ds.c.g = ga;
-      if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
-      hipLaunchKernelGGL(gtd::deep_size_genotype_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
-    }
-    TRGT_HIP_TRY(c, hipGetLastError());
-    tl_mark(c, "genotyper launched");
-    // Two ways to order the HMM of the settled loci and the repair of the others: one HMM batch behind the repair (default), or -- split_hmm,
-    // TRGT_SPLIT_HMM=1 -- the HMM of the settled loci on a stream of its own next to the repair and a second batch for the repaired loci.
-    // Measured: the split costs more in extra launches and streams than the overlap gives back, on every config.
-    const bool split = use_slots && dev_repair && c->knobs.split_hmm;
-    ga.finish_clears_need = split ? 0 : 1;  // (read by repair_finish_kernel only)
-    if (use_slots && split) {
-      if (!c->ev_gt) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_gt, hipEventDisableTiming));
-      if (!c->ev_rp) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_rp, hipEventDisableTiming));
-      if (!c->stream_hmm) TRGT_HIP_TRY(c, trgt::make_side_stream(c, &c->stream_hmm));
-      TRGT_HIP_TRY(c, hipEventRecord(c->ev_gt, c->stream));
-    }
-    if (use_slots && split) {
-      // the HMM batch of the loci the genotyper settled (need_host == 0), on a stream of its own: the call's stream goes on to the results
-      // the host waits for (they must not queue behind the HMM kernels), the second stream to the device-side repair
-      const hipStream_t main_stream = c->stream;
+    void* d_pcnt = nullptr;
+    if ((rc = dev_get(c, S_PUR_CNT, ((size_t)cnt_total + 1) * 4, &d_pcnt))) return rc;
+    const int64_t tc0 = now_ns();
+    // (device pointers for every result: nothing is copied back, the call returns when the kernels are through)
+    rc = hmm_batch_impl(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, n_pj, pj_set.data(), d_reads, pj_off.data(), pj_len.data(),
+                        nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t*)ps.d(po_nsp), (uint32_t*)d_pcnt, pj_cnt_off.data(), (double*)ps.d(po_pur), nullptr, nullptr);
+    if (rc) return rc;
+    tC += now_ns() - tc0;
+    stat_hmm_jobs += n_pj;
+    tl("purity batch done");
+  }
+  k_purity_filter.launch(!small_gt, true, pgrid, c->stream, ga, pa);
+  if (!cld_list.empty()) hipLaunchKernelGGL(cld::deep_filter_kernel, dim3(da.c.n_list), dim3(cld::DW), 0, c->stream, da);
+  if (!gsd_list.empty()) hipLaunchKernelGGL(cld::deep_filter_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  ga.sel_read = pa.sel_read; ga.sel_start = pa.sel_start; ga.sel_len = pa.sel_len; ga.n_sel = pa.n_sel;
+  return TRGT_OK;
+}
+int LocusCall::size_genotyper() {
+  if (!dev_gt) return TRGT_OK;
+  k_genotype.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, ga);
+  if (!gsd_list.empty()) {
+    // ---- the deep size list, behind the one-wave genotyper (which marked these loci need_host = 1): selection unless it ran in front
+    //      of the purity batch, then the workgroup-wide genotyper; its loci without majority support join the repair chain below
+    ds.c.g = ga;
+    if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
+    hipLaunchKernelGGL(gtd::deep_size_genotype_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
+  }
+  TRGT_HIP_TRY(c, hipGetLastError());
+  tl_mark(c, "genotyper launched");
+  // Two ways to order the HMM of the settled loci and the repair of the others: one HMM batch behind the repair (default), or -- split_hmm,
+  // TRGT_SPLIT_HMM=1 -- the HMM of the settled loci on a stream of its own next to the repair and a second batch for the repaired loci.
+  // Measured: the split costs more in extra launches and streams than the overlap gives back, on every config.
+  split = use_slots && dev_repair && c->knobs.split_hmm;
+  ga.finish_clears_need = split ? 0 : 1;  // (read by repair_finish_kernel only)
+  if (use_slots && split) {
+    if (!c->ev_gt) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_gt, hipEventDisableTiming));
+    if (!c->ev_rp) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_rp, hipEventDisableTiming));
+    if (!c->stream_hmm) TRGT_HIP_TRY(c, trgt::make_side_stream(c, &c->stream_hmm));
+    TRGT_HIP_TRY(c, hipEventRecord(c->ev_gt, c->stream));
+  }
+  if (use_slots && split) {
+    // the HMM batch of the loci the genotyper settled (need_host == 0), on a stream of its own: the call's stream goes on to the results
+    // the host waits for (they must not queue behind the HMM kernels), the second stream to the device-side repair
+    int rc; int64_t tc0;
+    {
+      StreamGuard keep(c);
       TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream_hmm, c->ev_gt, 0)); TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream_hmm, c->ev_upload, 0)); c->stream = c->stream_hmm;
       hs.d_skip = (const uint8_t*)g.need;
-      const int64_t tc0 = now_ns();
+      tc0 = now_ns();
       rc = hmm_enqueue_slots(c, &models, hs, out->spans3, out->span_off, out->n_spans, out->motif_counts, out->count_off, out->purity, &hmm_pending);
-      c->stream = main_stream;
-      if (rc) return rc;
-      tC += now_ns() - tc0;
-      TL("hmm1 enqueued (device-resolved job list)");
     }
-    if (dev_repair) {
-      // on the second stream: alignments, voting, finish, and the HMM batch of the repaired loci right behind
-      if (split) {
-        TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_gt, 0));
-        std::swap(c->stream, c->stream2);
-      }
-      struct SwapBackRp { trgt_hip_ctx* c; bool on; ~SwapBackRp() { if (on) std::swap(c->stream, c->stream2); } } swap_back_rp{c, split};
-      trgt_wfa_params wp;
-      trgt_wfa_default_params(&wp);  // THREAD_WFA_CONSENSUS (genotype.rs:82-86): BiWFA, gap-affine 2,5,1, default heuristic
-      wp.metric = 3; wp.mismatch = 2; wp.gap_open1 = 5; wp.gap_ext1 = 1; wp.span = 0; wp.scope = 1; wp.memory_mode = 3; sens_apply(c, wp);
-      WfaLaunch LR;
-      // (n_jobs_host bounds the workgroups and their workspaces, not the jobs: the count is read on the device)
-      LR.jobs_dev = rp.jobs; LR.n_jobs_host = (int64_t)std::min<uint64_t>(rp.cap_jobs, (uint64_t)std::max(64, c->knobs.repair_blocks)); LR.n_jobs_dev = rp.counts + gt::RC_JOBS; LR.jobs_bound = rp.cap_jobs;
-      LR.pat_base = d_reads; LR.txt_base = d_reads;
-      LR.max_plen = rp.max_seg; LR.max_tlen = rp.max_seg; LR.max_sum = 2 * (int64_t)rp.max_seg;
-      LR.cigar = (uint32_t*)d_rcig; LR.cigar_len = (uint32_t*)d_rclen; LR.buffer_set = 2; LR.ws_budget = 512ull << 20; LR.refused = rp.counts + gt::RC_REFUSED;
-      auto dbg_sync = [&](const char* what) -> int {  // TRGT_WFA_DEBUG: which kernel of the chain a device fault belongs to
-        if (!c->knobs.debug) return TRGT_OK;
-        const hipError_t e = trgt::stream_wait(c, c->stream);
-        uint32_t h[gt::RC_WORDS]; std::memset(h, 0, sizeof h);
-        if (e == hipSuccess) (void)hipMemcpy(h, rp.counts, sizeof h, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[repair] %s: %s (groups %u jobs %u loci %u failed %u cigar words %llu)\n", what, hipGetErrorString(e), h[gt::RC_GROUPS], h[gt::RC_JOBS], h[gt::RC_LOCI], h[gt::RC_FAILED],
-                (unsigned long long)h[gt::RC_CIGAR] | ((unsigned long long)h[gt::RC_CIGAR + 1] << 32));
-        return e == hipSuccess ? TRGT_OK : fail(c, TRGT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
-      };
-      if ((rc = dbg_sync("genotyper"))) return rc;
-      if (uint32_t* trace_host = repair_trace_buf()) { std::memset(trace_host, 0, 4096); hipLaunchKernelGGL(repair_trace_kernel, dim3(1), dim3(64), 0, c->stream, rp, trace_host); }
-      static const bool repair_check = TRGT_DEV_ENV("TRGT_REPAIR_CHECK") != nullptr;
-      if (repair_check) {
-        hipLaunchKernelGGL(repair_check_kernel, dim3(64), dim3(256), 0, c->stream, rp, (uint64_t)read_total);
-        uint32_t h[gt::RC_WORDS];
-        (void)trgt::stream_wait(c, c->stream);
-        (void)hipMemcpy(h, rp.counts, sizeof h, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[repair check] jobs %u groups %u loci %u bad %u (last bad job %u: plen %u tlen %u out_index %u cigar_off %u) caps: jobs %u cigar %llu max_seg %u read bytes %llu\n", h[1], h[0], h[2], h[10], h[11], h[12], h[13],
-                h[14], h[15], rp.cap_jobs, (unsigned long long)rp.cap_cigar, rp.max_seg, (unsigned long long)read_total);
-      }
-      if ((rc = wfa_launch(c, wp, LR))) return rc;
-      if ((rc = dbg_sync("consensus alignments"))) return rc;
-      vote::VoteArgs va{(const vote::Group*)rp.groups, 0u, rp.counts + gt::RC_GROUPS, d_reads, rp.jobs, (const uint32_t*)d_rcig, (const uint32_t*)d_rclen,
-                        (uint32_t*)d_vscr, (uint8_t*)d_vout, (uint32_t*)d_vlen};
-      hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)rp.cap_groups), dim3(vote::VOTE_THREADS), 0, c->stream, va);
-      const gt::FinishArgs fa{(const uint8_t*)d_vout, (const uint32_t*)d_vlen};
-      const dim3 fgrid((unsigned)nl);
-      if (presel) {
-        if (small_gt) hipLaunchKernelGGL((gt::repair_finish_kernel<64, true>), fgrid, dim3(64), 0, c->stream, ga, fa);
-        else hipLaunchKernelGGL((gt::repair_finish_kernel<gt::GT_MAX_READS, true>), fgrid, dim3(64), 0, c->stream, ga, fa);
-      }
-      else if (small_gt) hipLaunchKernelGGL((gt::repair_finish_kernel<64>), fgrid, dim3(64), 0, c->stream, ga, fa);
-      else hipLaunchKernelGGL((gt::repair_finish_kernel<gt::GT_MAX_READS>), fgrid, dim3(64), 0, c->stream, ga, fa);
-      if (!gsd_list.empty()) { ds.c.g = ga; hipLaunchKernelGGL(gtd::deep_size_finish_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds, fa); }
-      TRGT_HIP_TRY(c, hipGetLastError());
-      if ((rc = dbg_sync("vote + finish"))) return rc;
-      tl_mark(c, "repair chain enqueued");
-      if (split) {
-        TRGT_HIP_TRY(c, hipEventRecord(c->ev_rp, c->stream));  // (the results the host waits for do not wait for the second HMM batch)
-        hs.d_skip = (const uint8_t*)dsl(o_skipb);
-        nsB.assign(2 * (size_t)nl, 0); puB.assign(2 * (size_t)nl, 0.0);
-        const int64_t tc0 = now_ns();
-        if ((rc = hmm_enqueue_slots(c, &models, hs, out->spans3, out->span_off, nsB.data(), out->motif_counts, out->count_off, puB.data(), &hmm_pendingB, 1))) return rc;
-        tC += now_ns() - tc0;
-        std::swap(c->stream, c->stream2); swap_back_rp.on = false;
-        TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_rp, 0));
-      }
-    }
-    for (int deep = 0; deep < 2; ++deep) {
-      if (clp[deep].list.empty()) continue;
-      const uint64_t cl_pairs = clp[deep].pairs, cl_reads = clp[deep].reads;
-      const int so = deep ? (int)S_CLD_LIST - (int)S_CL_LIST : 0;  // the deep list's buffers: the same slots, second set
-      // ---- Genotyper::Cluster on the device (locus_cluster_dev.hpp): pair list -> edit distances -> linkage / groups / backbones ->
-      //      consensus round -> redo or dropped reads -> second round + edit distances -> genotype.  Four alignment launches and two
-      //      votes, most of them over empty lists after the first round; nothing waits for the host.
-      const uint32_t n_cl = (uint32_t)clp[deep].list.size();
-      const uint32_t max_seg = max_read_len > 2u * (uint32_t)F ? max_read_len - 2u * (uint32_t)F : 1u;
-      cl::ClArgs ca;
-      std::memset(&ca, 0, sizeof ca);
-      ca.g = ga; ca.list = clp[deep].d_list; ca.n_list = n_cl; ca.mat_off = clp[deep].d_moff;
-      ca.flags = (c->knobs.sens_ward_ties ? 1u : 0u) | (c->knobs.sens_lw_order ? 2u : 0u);
-      ca.cap_j = (uint32_t)cl_reads; ca.cap_g = 2 * n_cl; ca.vote_lds_pos = (uint32_t)vote::VOTE_LDS_POS;
-      // arenas for two consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
-      ca.cap_cigar = std::min<uint64_t>(2ull * cl_reads * (2ull * max_seg + 1), 96ull << 20);   // words
-      ca.cap_out = std::min<uint64_t>(2ull * (cl_reads + 2ull * n_cl) * ((uint64_t)max_seg + 16) + 64, 256ull << 20);  // bytes
-      ca.cap_scratch = std::min<uint64_t>(6ull * cl_reads + 12ull * n_cl * ((uint64_t)max_seg + 1) + 64, 32ull << 20);  // words
-      if (c->knobs.cluster_arena_kb > 0) {
-        const uint64_t kb = (uint64_t)c->knobs.cluster_arena_kb;
-        ca.cap_cigar = std::min<uint64_t>(ca.cap_cigar, kb * 256); ca.cap_out = std::min<uint64_t>(ca.cap_out, kb * 1024); ca.cap_scratch = std::min<uint64_t>(ca.cap_scratch, kb * 256);
-      }
-      const bool big = clp[deep].max_nr > 64;
-      void *d_cnt = nullptr, *d_rec = nullptr, *d_cls = nullptr, *d_es = nullptr, *d_gm = nullptr, *d_edj = nullptr, *d_j = nullptr, *d_g = nullptr, *d_ed2 = nullptr, *d_es2 = nullptr,
-           *d_cig = nullptr, *d_clen = nullptr, *d_vout = nullptr, *d_vlen = nullptr, *d_vscr = nullptr;
-      if ((rc = dev_get(c, S_CL_COUNTS + so, 256, &d_cnt)) || (rc = dev_get(c, S_CL_REC + so, (size_t)n_cl * sizeof(cl::ClRec), &d_rec)) || (rc = dev_get(c, S_CL_CLS + so, (size_t)nr + 16, &d_cls)) ||
-          (rc = dev_get(c, S_CL_ESCORE + so, (size_t)cl_pairs * 4 + 16, &d_es)) || (big && (rc = dev_get(c, S_CL_GMAT + so, (size_t)cl_pairs * 8 + 16, &d_gm))) ||
-          (rc = dev_get(c, S_CL_EDJOBS + so, (size_t)cl_pairs * sizeof(JobDev) + 16, &d_edj)) || (rc = dev_get(c, S_CL_JOBS + so, 2 * (size_t)ca.cap_j * sizeof(JobDev), &d_j)) ||
-          (rc = dev_get(c, S_CL_GROUPS + so, 2 * (size_t)ca.cap_g * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, S_CL_ED2JOBS + so, 2 * (size_t)cl_reads * sizeof(JobDev), &d_ed2)) ||
-          (rc = dev_get(c, S_CL_ESCORE2 + so, 2 * (size_t)nr * 4 + 16, &d_es2)) || (rc = dev_get(c, S_CL_CIGAR + so, (size_t)ca.cap_cigar * 4, &d_cig)) ||
-          (rc = dev_get(c, S_CL_CLEN + so, 2 * (size_t)ca.cap_j * 4, &d_clen)) || (rc = dev_get(c, S_CL_VOUT + so, (size_t)ca.cap_out + 16, &d_vout)) ||
-          (rc = dev_get(c, S_CL_VLEN + so, 2 * (size_t)ca.cap_g * 4, &d_vlen)) || (rc = dev_get(c, S_CL_VSCR + so, (size_t)ca.cap_scratch * 4 + 16, &d_vscr)))
-        return rc;
-      void* const z_clc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
-      ca.counts = z_clc ? (uint32_t*)z_clc : (uint32_t*)d_cnt; ca.rec = (cl::ClRec*)d_rec; ca.cls = (int8_t*)d_cls; ca.escore = (int32_t*)d_es; ca.gmat = (double*)d_gm;
-      ca.ed_jobs = (JobDev*)d_edj; ca.jobs = (JobDev*)d_j; ca.groups = (gt::RGroup*)d_g; ca.ed2_jobs = (JobDev*)d_ed2; ca.escore2 = (int32_t*)d_es2;
-      ca.vote_out = (const uint8_t*)d_vout; ca.vote_len = (const uint32_t*)d_vlen;
-      if (!z_clc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, ca.counts, (uint32_t)cl::CC_WORDS);
-      const dim3 cgrid(n_cl);
-      // (with filter_impure_trs on: the instantiations that load the filtered lists, like the length genotyper's)
-      if (deep) {  // (one workgroup per locus; the selection ran above when the purity filter is on)
-        da.c = ca;
-        if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
-        hipLaunchKernelGGL(cld::deep_front_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
-      }
-      else if (presel) {
-        if (big) hipLaunchKernelGGL((cl::cluster_front_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
-        else hipLaunchKernelGGL((cl::cluster_front_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
-      }
-      else if (big) hipLaunchKernelGGL((cl::cluster_front_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
-      else hipLaunchKernelGGL((cl::cluster_front_kernel<64>), cgrid, dim3(64), 0, c->stream, ca);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      const int64_t wg_bound = (int64_t)std::max(64, 2 * c->knobs.repair_blocks);
-      const int64_t ed_len = (int64_t)std::min<uint64_t>(max_seg, cl::CL_MAX_OPS);
-      trgt_wfa_params wed;
-      trgt_wfa_default_params(&wed);  // THREAD_WFA_ED (genotype.rs:88-92): edit distance, score only, BiWFA, default heuristic
-      wed.metric = 1; wed.span = 0; wed.scope = 0; wed.memory_mode = 3; sens_apply(c, wed);
-      trgt_wfa_params wco;
-      trgt_wfa_default_params(&wco);  // THREAD_WFA_CONSENSUS (genotype.rs:82-86)
-      wco.metric = 3; wco.mismatch = 2; wco.gap_open1 = 5; wco.gap_ext1 = 1; wco.span = 0; wco.scope = 1; wco.memory_mode = 3; sens_apply(c, wco);
-      auto ed_launch = [&](const JobDev* jobs, uint64_t bound, const uint32_t* count, const uint8_t* txt_base, int32_t* score) -> int {
-        WfaLaunch LE;
-        LE.jobs_dev = jobs; LE.n_jobs_host = std::min<int64_t>((int64_t)std::max<uint64_t>(bound, 1), wg_bound); LE.n_jobs_dev = count; LE.jobs_bound = (int64_t)std::max<uint64_t>(bound, 1);
-        // (a pair is aligned when li * lj <= MAX_OPS: an EMPTY segment pairs with one of any length -- gt_front keeps zero-length repeat
-        //  segments -- so either side reaches max_seg; with both non-empty the sum stays within MAX_OPS + 1.  ADVICE r4: sized by ed_len alone
-        //  the generic kernel's rings were too short for (0, > 10 kb) pairs)
-        LE.pat_base = d_reads; LE.txt_base = txt_base; LE.max_plen = (int64_t)max_seg; LE.max_tlen = (int64_t)max_seg;
-        LE.max_sum = std::max<int64_t>((int64_t)max_seg, std::min<int64_t>(2 * ed_len, (int64_t)cl::CL_MAX_OPS + 1));
-        LE.score = score; LE.buffer_set = 2; LE.ws_budget = 512ull << 20; LE.refused = ca.counts + cl::CC_REFUSED;
-        return wfa_launch(c, wed, LE);
-      };
-      auto cons_launch = [&](uint32_t first_job, const uint32_t* count, uint32_t first_group, const uint32_t* group_count) -> int {
-        WfaLaunch LC;
-        LC.jobs_dev = ca.jobs + first_job; LC.n_jobs_host = std::min<int64_t>((int64_t)ca.cap_j, wg_bound); LC.n_jobs_dev = count; LC.jobs_bound = (int64_t)ca.cap_j;
-        LC.pat_base = d_reads; LC.txt_base = d_reads; LC.max_plen = max_seg; LC.max_tlen = max_seg; LC.max_sum = 2 * (int64_t)max_seg;
-        LC.cigar = (uint32_t*)d_cig; LC.cigar_len = (uint32_t*)d_clen; LC.buffer_set = 2; LC.ws_budget = 512ull << 20; LC.refused = ca.counts + cl::CC_REFUSED;
-        if (int r = wfa_launch(c, wco, LC)) return r;
-        vote::VoteArgs va{(const vote::Group*)(ca.groups + first_group), 0u, group_count, d_reads, ca.jobs, (const uint32_t*)d_cig, (const uint32_t*)d_clen,
-                          (uint32_t*)d_vscr, (uint8_t*)d_vout, (uint32_t*)d_vlen + first_group};
-        hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)ca.cap_g), dim3(vote::VOTE_THREADS), 0, c->stream, va);
-        return TRGT_OK;
-      };
-      if ((rc = ed_launch(ca.ed_jobs, cl_pairs, ca.counts + cl::CC_ED, d_reads, ca.escore))) return rc;
-      if (deep) {
-        hipLaunchKernelGGL(cld::deep_linkage_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
-        hipLaunchKernelGGL(cld::deep_groups_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
-      }
-      else if (presel) {
-        if (big) hipLaunchKernelGGL((cl::cluster_ward_kernel<gt::GT_MAX_READS, false, true>), cgrid, dim3(64), 0, c->stream, ca);
-        else hipLaunchKernelGGL((cl::cluster_ward_kernel<64, true, true>), cgrid, dim3(64), 0, c->stream, ca);
-      }
-      else if (big) hipLaunchKernelGGL((cl::cluster_ward_kernel<gt::GT_MAX_READS, false>), cgrid, dim3(64), 0, c->stream, ca);
-      else hipLaunchKernelGGL((cl::cluster_ward_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      if ((rc = cons_launch(0, ca.counts + cl::CC_J1, 0, ca.counts + cl::CC_G1))) return rc;
-      if (deep) hipLaunchKernelGGL(cld::deep_round2_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
-      else if (presel) {
-        if (big) hipLaunchKernelGGL((cl::cluster_round2_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
-        else hipLaunchKernelGGL((cl::cluster_round2_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
-      }
-      else if (big) hipLaunchKernelGGL((cl::cluster_round2_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
-      else hipLaunchKernelGGL((cl::cluster_round2_kernel<64>), cgrid, dim3(64), 0, c->stream, ca);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      if ((rc = cons_launch(ca.cap_j, ca.counts + cl::CC_J2, ca.cap_g, ca.counts + cl::CC_G2))) return rc;
-      if ((rc = ed_launch(ca.ed2_jobs, 2 * cl_reads, ca.counts + cl::CC_ED2, (const uint8_t*)d_vout, ca.escore2))) return rc;
-      if (deep) hipLaunchKernelGGL(cld::deep_finish_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
-      else if (presel) {
-        if (big) hipLaunchKernelGGL((cl::cluster_finish_kernel<gt::GT_MAX_READS, true>), cgrid, dim3(64), 0, c->stream, ca);
-        else hipLaunchKernelGGL((cl::cluster_finish_kernel<64, true>), cgrid, dim3(64), 0, c->stream, ca);
-      }
-      else if (big) hipLaunchKernelGGL((cl::cluster_finish_kernel<gt::GT_MAX_READS>), cgrid, dim3(64), 0, c->stream, ca);
-      else hipLaunchKernelGGL((cl::cluster_finish_kernel<64>), cgrid, dim3(64), 0, c->stream, ca);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      tl_mark(c, deep ? "deep cluster chain enqueued" : "cluster chain enqueued");
-      cl_counts_dev[deep] = ca.counts;
-    }
+    if (rc) return rc;
+    tC += now_ns() - tc0;
+    tl("hmm1 enqueued (device-resolved job list)");
+  }
+  return TRGT_OK;
+}
+int LocusCall::repair_chain() {
+  if (!dev_gt || !dev_repair) return TRGT_OK;
+  int rc;
+  gt::RepairBufs& rp = ga.rp;
+  StreamGuard keep(c);
+  // on the second stream: alignments, voting, finish, and the HMM batch of the repaired loci right behind
+  if (split) {
+    TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_gt, 0));
+    std::swap(c->stream, c->stream2);
+  }
+  trgt_wfa_params wp;
+  trgt_wfa_default_params(&wp);  // THREAD_WFA_CONSENSUS (genotype.rs:82-86): BiWFA, gap-affine 2,5,1, default heuristic
+  wp.metric = 3; wp.mismatch = 2; wp.gap_open1 = 5; wp.gap_ext1 = 1; wp.span = 0; wp.scope = 1; wp.memory_mode = 3; sens_apply(c, wp);
+  WfaLaunch LR;
+  // (n_jobs_host bounds the workgroups and their workspaces, not the jobs: the count is read on the device)
+  LR.jobs_dev = rp.jobs; LR.n_jobs_host = (int64_t)std::min<uint64_t>(rp.cap_jobs, (uint64_t)std::max(64, c->knobs.repair_blocks)); LR.n_jobs_dev = rp.counts + gt::RC_JOBS; LR.jobs_bound = rp.cap_jobs;
+  LR.pat_base = d_reads; LR.txt_base = d_reads;
+  LR.max_plen = rp.max_seg; LR.max_tlen = rp.max_seg; LR.max_sum = 2 * (int64_t)rp.max_seg;
+  LR.cigar = (uint32_t*)rb.cig; LR.cigar_len = (uint32_t*)rb.clen; LR.buffer_set = 2; LR.ws_budget = 512ull << 20; LR.refused = rp.counts + gt::RC_REFUSED;
+  auto dbg_sync = [&](const char* what) -> int {  // TRGT_WFA_DEBUG: which kernel of the chain a device fault belongs to
+    if (!c->knobs.debug) return TRGT_OK;
+    const hipError_t e = trgt::stream_wait(c, c->stream);
+    uint32_t h[gt::RC_WORDS]; std::memset(h, 0, sizeof h);
+    if (e == hipSuccess) (void)hipMemcpy(h, rp.counts, sizeof h, hipMemcpyDeviceToHost);
+    fprintf(stderr, "[repair] %s: %s (groups %u jobs %u loci %u failed %u cigar words %llu)\n", what, hipGetErrorString(e), h[gt::RC_GROUPS], h[gt::RC_JOBS], h[gt::RC_LOCI], h[gt::RC_FAILED],
+            (unsigned long long)h[gt::RC_CIGAR] | ((unsigned long long)h[gt::RC_CIGAR + 1] << 32));
+    return e == hipSuccess ? TRGT_OK : fail(c, TRGT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
+  };
+  if ((rc = dbg_sync("genotyper"))) return rc;
+  if (uint32_t* trace_host = repair_trace_buf()) { std::memset(trace_host, 0, 4096); hipLaunchKernelGGL(repair_trace_kernel, dim3(1), dim3(64), 0, c->stream, rp, trace_host); }
+  static const bool repair_check = TRGT_DEV_ENV("TRGT_REPAIR_CHECK") != nullptr;
+  if (repair_check) {
+    hipLaunchKernelGGL(repair_check_kernel, dim3(64), dim3(256), 0, c->stream, rp, (uint64_t)read_total);
+    uint32_t h[gt::RC_WORDS];
+    (void)trgt::stream_wait(c, c->stream);
+    (void)hipMemcpy(h, rp.counts, sizeof h, hipMemcpyDeviceToHost);
+    fprintf(stderr, "[repair check] jobs %u groups %u loci %u bad %u (last bad job %u: plen %u tlen %u out_index %u cigar_off %u) caps: jobs %u cigar %llu max_seg %u read bytes %llu\n", h[1], h[0], h[2], h[10], h[11], h[12], h[13],
+            h[14], h[15], rp.cap_jobs, (unsigned long long)rp.cap_cigar, rp.max_seg, (unsigned long long)read_total);
+  }
+  if ((rc = wfa_launch(c, wp, LR))) return rc;
+  if ((rc = dbg_sync("consensus alignments"))) return rc;
+  vote::VoteArgs va{(const vote::Group*)rp.groups, 0u, rp.counts + gt::RC_GROUPS, d_reads, rp.jobs, (const uint32_t*)rb.cig, (const uint32_t*)rb.clen,
+                    (uint32_t*)rb.vscr, (uint8_t*)rb.vout, (uint32_t*)rb.vlen};
+  hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)rp.cap_groups), dim3(vote::VOTE_THREADS), 0, c->stream, va);
+  const gt::FinishArgs fa{(const uint8_t*)rb.vout, (const uint32_t*)rb.vlen};
+  const dim3 fgrid((unsigned)nl);
+  k_repair_finish.launch(!small_gt, presel, fgrid, c->stream, ga, fa);
+  if (!gsd_list.empty()) { ds.c.g = ga; hipLaunchKernelGGL(gtd::deep_size_finish_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds, fa); }
+  TRGT_HIP_TRY(c, hipGetLastError());
+  if ((rc = dbg_sync("vote + finish"))) return rc;
+  tl_mark(c, "repair chain enqueued");
+  if (split) {
+    TRGT_HIP_TRY(c, hipEventRecord(c->ev_rp, c->stream));  // (the results the host waits for do not wait for the second HMM batch)
+    hs.d_skip = (const uint8_t*)slab.d(o_skipb);
+    nsB.assign(2 * (size_t)nl, 0); puB.assign(2 * (size_t)nl, 0.0);
+    const int64_t tc0 = now_ns();
+    if ((rc = hmm_enqueue_slots(c, &models, hs, out->spans3, out->span_off, nsB.data(), out->motif_counts, out->count_off, puB.data(), &hmm_pendingB, 1))) return rc;
+    tC += now_ns() - tc0;
+    std::swap(c->stream, c->stream2);
+    TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_rp, 0));
+  }
+  return TRGT_OK;
+}
+int LocusCall::cluster_chain(int deep) {
+  if (!dev_gt || clp[deep].list.empty()) return TRGT_OK;
+  int rc;
+  const uint64_t cl_pairs = clp[deep].pairs, cl_reads = clp[deep].reads;
+  // ---- Genotyper::Cluster on the device (locus_cluster_dev.hpp): pair list -> edit distances -> linkage / groups / backbones ->
+  //      consensus round -> redo or dropped reads -> second round + edit distances -> genotype.  Four alignment launches and two
+  //      votes, most of them over empty lists after the first round; nothing waits for the host.
+  const uint32_t n_cl = (uint32_t)clp[deep].list.size();
+  const uint32_t max_seg = max_read_len > 2u * (uint32_t)F ? max_read_len - 2u * (uint32_t)F : 1u;
+  cl::ClArgs ca;
+  std::memset(&ca, 0, sizeof ca);
+  ca.g = ga; ca.list = clp[deep].d_list; ca.n_list = n_cl; ca.mat_off = clp[deep].d_moff;
+  ca.flags = (c->knobs.sens_ward_ties ? 1u : 0u) | (c->knobs.sens_lw_order ? 2u : 0u);
+  ca.cap_j = (uint32_t)cl_reads; ca.cap_g = 2 * n_cl; ca.vote_lds_pos = (uint32_t)vote::VOTE_LDS_POS;
+  // arenas for two consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
+  ca.cap_cigar = std::min<uint64_t>(2ull * cl_reads * (2ull * max_seg + 1), 96ull << 20);   // words
+  ca.cap_out = std::min<uint64_t>(2ull * (cl_reads + 2ull * n_cl) * ((uint64_t)max_seg + 16) + 64, 256ull << 20);  // bytes
+  ca.cap_scratch = std::min<uint64_t>(6ull * cl_reads + 12ull * n_cl * ((uint64_t)max_seg + 1) + 64, 32ull << 20);  // words
+  if (c->knobs.cluster_arena_kb > 0) {
+    const uint64_t kb = (uint64_t)c->knobs.cluster_arena_kb;
+    ca.cap_cigar = std::min<uint64_t>(ca.cap_cigar, kb * 256); ca.cap_out = std::min<uint64_t>(ca.cap_out, kb * 1024); ca.cap_scratch = std::min<uint64_t>(ca.cap_scratch, kb * 256);
+  }
+  const bool big = clp[deep].max_nr > 64;
+  void *d_cnt = nullptr, *d_rec = nullptr, *d_cls = nullptr, *d_es = nullptr, *d_gm = nullptr, *d_edj = nullptr, *d_j = nullptr, *d_g = nullptr, *d_ed2 = nullptr, *d_es2 = nullptr,
+       *d_cig = nullptr, *d_clen = nullptr, *d_vout = nullptr, *d_vlen = nullptr, *d_vscr = nullptr;
+  if ((rc = dev_get(c, cl_slot(deep, S_CL_COUNTS), 256, &d_cnt)) || (rc = dev_get(c, cl_slot(deep, S_CL_REC), (size_t)n_cl * sizeof(cl::ClRec), &d_rec)) || (rc = dev_get(c, cl_slot(deep, S_CL_CLS), (size_t)nr + 16, &d_cls)) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_ESCORE), (size_t)cl_pairs * 4 + 16, &d_es)) || (big && (rc = dev_get(c, cl_slot(deep, S_CL_GMAT), (size_t)cl_pairs * 8 + 16, &d_gm))) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_EDJOBS), (size_t)cl_pairs * sizeof(JobDev) + 16, &d_edj)) || (rc = dev_get(c, cl_slot(deep, S_CL_JOBS), 2 * (size_t)ca.cap_j * sizeof(JobDev), &d_j)) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_GROUPS), 2 * (size_t)ca.cap_g * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, cl_slot(deep, S_CL_ED2JOBS), 2 * (size_t)cl_reads * sizeof(JobDev), &d_ed2)) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_ESCORE2), 2 * (size_t)nr * 4 + 16, &d_es2)) || (rc = dev_get(c, cl_slot(deep, S_CL_CIGAR), (size_t)ca.cap_cigar * 4, &d_cig)) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_CLEN), 2 * (size_t)ca.cap_j * 4, &d_clen)) || (rc = dev_get(c, cl_slot(deep, S_CL_VOUT), (size_t)ca.cap_out + 16, &d_vout)) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_VLEN), 2 * (size_t)ca.cap_g * 4, &d_vlen)) || (rc = dev_get(c, cl_slot(deep, S_CL_VSCR), (size_t)ca.cap_scratch * 4 + 16, &d_vscr)))
+    return rc;
+  void* const z_clc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
+  ca.counts = z_clc ? (uint32_t*)z_clc : (uint32_t*)d_cnt; ca.rec = (cl::ClRec*)d_rec; ca.cls = (int8_t*)d_cls; ca.escore = (int32_t*)d_es; ca.gmat = (double*)d_gm;
+  ca.ed_jobs = (JobDev*)d_edj; ca.jobs = (JobDev*)d_j; ca.groups = (gt::RGroup*)d_g; ca.ed2_jobs = (JobDev*)d_ed2; ca.escore2 = (int32_t*)d_es2;
+  ca.vote_out = (const uint8_t*)d_vout; ca.vote_len = (const uint32_t*)d_vlen;
+  if (!z_clc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, ca.counts, (uint32_t)cl::CC_WORDS);
+  const dim3 cgrid(n_cl);
+  // a step of the chain: the deep list's kernel (one workgroup per locus) or the shallow list's instantiation (with filter_impure_trs on:
+  // the one that loads the filtered lists, like the length genotyper's)
+  auto step = [&](void (*deep_kernel)(cld::DeepArgs), const OneWave<cl::ClArgs>& shallow) {
+    if (deep) hipLaunchKernelGGL(deep_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+    else shallow.launch(big, presel, cgrid, c->stream, ca);
+  };
+  if (deep) {  // (the selection ran in front of the purity batch when the filter is on)
+    da.c = ca;
+    if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+  }
+  step(cld::deep_front_kernel, k_cluster_front);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  const int64_t wg_bound = (int64_t)std::max(64, 2 * c->knobs.repair_blocks);
+  const int64_t ed_len = (int64_t)std::min<uint64_t>(max_seg, cl::CL_MAX_OPS);
+  trgt_wfa_params wed;
+  trgt_wfa_default_params(&wed);  // THREAD_WFA_ED (genotype.rs:88-92): edit distance, score only, BiWFA, default heuristic
+  wed.metric = 1; wed.span = 0; wed.scope = 0; wed.memory_mode = 3; sens_apply(c, wed);
+  trgt_wfa_params wco;
+  trgt_wfa_default_params(&wco);  // THREAD_WFA_CONSENSUS (genotype.rs:82-86)
+  wco.metric = 3; wco.mismatch = 2; wco.gap_open1 = 5; wco.gap_ext1 = 1; wco.span = 0; wco.scope = 1; wco.memory_mode = 3; sens_apply(c, wco);
+  auto ed_launch = [&](const JobDev* jobs, uint64_t bound, const uint32_t* count, const uint8_t* txt_base, int32_t* score) -> int {
+    WfaLaunch LE;
+    LE.jobs_dev = jobs; LE.n_jobs_host = std::min<int64_t>((int64_t)std::max<uint64_t>(bound, 1), wg_bound); LE.n_jobs_dev = count; LE.jobs_bound = (int64_t)std::max<uint64_t>(bound, 1);
+    // (a pair is aligned when li * lj <= MAX_OPS: an EMPTY segment pairs with one of any length -- gt_front keeps zero-length repeat
+    //  segments -- so either side reaches max_seg; with both non-empty the sum stays within MAX_OPS + 1.  ADVICE r4: sized by ed_len alone
+    //  the generic kernel's rings were too short for (0, > 10 kb) pairs)
+    LE.pat_base = d_reads; LE.txt_base = txt_base; LE.max_plen = (int64_t)max_seg; LE.max_tlen = (int64_t)max_seg;
+    LE.max_sum = std::max<int64_t>((int64_t)max_seg, std::min<int64_t>(2 * ed_len, (int64_t)cl::CL_MAX_OPS + 1));
+    LE.score = score; LE.buffer_set = 2; LE.ws_budget = 512ull << 20; LE.refused = ca.counts + cl::CC_REFUSED;
+    return wfa_launch(c, wed, LE);
+  };
+  auto cons_launch = [&](uint32_t first_job, const uint32_t* count, uint32_t first_group, const uint32_t* group_count) -> int {
+    WfaLaunch LC;
+    LC.jobs_dev = ca.jobs + first_job; LC.n_jobs_host = std::min<int64_t>((int64_t)ca.cap_j, wg_bound); LC.n_jobs_dev = count; LC.jobs_bound = (int64_t)ca.cap_j;
+    LC.pat_base = d_reads; LC.txt_base = d_reads; LC.max_plen = max_seg; LC.max_tlen = max_seg; LC.max_sum = 2 * (int64_t)max_seg;
+    LC.cigar = (uint32_t*)d_cig; LC.cigar_len = (uint32_t*)d_clen; LC.buffer_set = 2; LC.ws_budget = 512ull << 20; LC.refused = ca.counts + cl::CC_REFUSED;
+    if (int r = wfa_launch(c, wco, LC)) return r;
+    vote::VoteArgs va{(const vote::Group*)(ca.groups + first_group), 0u, group_count, d_reads, ca.jobs, (const uint32_t*)d_cig, (const uint32_t*)d_clen,
+                      (uint32_t*)d_vscr, (uint8_t*)d_vout, (uint32_t*)d_vlen + first_group};
+    hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)ca.cap_g), dim3(vote::VOTE_THREADS), 0, c->stream, va);
+    return TRGT_OK;
+  };
+  if ((rc = ed_launch(ca.ed_jobs, cl_pairs, ca.counts + cl::CC_ED, d_reads, ca.escore))) return rc;
+  if (deep) hipLaunchKernelGGL(cld::deep_linkage_kernel, cgrid, dim3(cld::DW), 0, c->stream, da);
+  step(cld::deep_groups_kernel, k_cluster_ward);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  if ((rc = cons_launch(0, ca.counts + cl::CC_J1, 0, ca.counts + cl::CC_G1))) return rc;
+  step(cld::deep_round2_kernel, k_cluster_round2);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  if ((rc = cons_launch(ca.cap_j, ca.counts + cl::CC_J2, ca.cap_g, ca.counts + cl::CC_G2))) return rc;
+  if ((rc = ed_launch(ca.ed2_jobs, 2 * cl_reads, ca.counts + cl::CC_ED2, (const uint8_t*)d_vout, ca.escore2))) return rc;
+  step(cld::deep_finish_kernel, k_cluster_finish);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  tl_mark(c, deep ? "deep cluster chain enqueued" : "cluster chain enqueued");
+  cl_counts_dev[deep] = ca.counts;
+  return TRGT_OK;
+}
+int LocusCall::enqueue_results() {
+  int rc;
+  if (dev_gt) {
     // (the count blocks come back with the slab)
-    const CountCopy cc{dev_repair ? rp.counts : nullptr, (uint32_t*)dsl(o_rpc), (uint32_t)gt::RC_WORDS, cl_counts_dev[0], (uint32_t*)dsl(o_clc), (uint32_t)cl::CC_WORDS, cl_counts_dev[1], (uint32_t*)dsl(o_cldc), (uint32_t)cl::CC_WORDS};
+    const CountCopy cc{dev_repair ? ga.rp.counts : nullptr, (uint32_t*)slab.d(o_rpc), (uint32_t)gt::RC_WORDS, cl_counts_dev[0], (uint32_t*)slab.d(o_clc), (uint32_t)cl::CC_WORDS, cl_counts_dev[1], (uint32_t*)slab.d(o_cldc), (uint32_t)cl::CC_WORDS};
     hipLaunchKernelGGL(allele_prefix_kernel, dim3(1), dim3(1024), 0, c->stream, (const uint32_t*)g.alen, (uint64_t*)g.toff, (int64_t)(2 * nl), cc);
     hipLaunchKernelGGL(allele_pack_kernel, dim3((unsigned)((2 * nl + 3) / 4)), dim3(256), 0, c->stream, (const uint8_t*)g.blob, g.al_off,
                        (const uint32_t*)g.alen, (const uint64_t*)g.toff, (uint8_t*)g.packed, (int64_t)(2 * nl));
     TRGT_HIP_TRY(c, hipGetLastError());
   }
-  ((uint64_t*)h_cells)[6] = 0;  // wavefront offsets of the device-side consensus / edit-distance launches (timing runs only)
-  if (c->timing && c->wfa_cells_cur[2]) { const int d2h_rc = trgt::d2h(c, (uint64_t*)h_cells + 6, c->wfa_cells_cur[2], 8, c->stream); if (d2h_rc) return d2h_rc; }
-  { const int d2h_rc = trgt::d2h(c, h_slab, d_slab, slab.total, c->stream); if (d2h_rc) return d2h_rc; }
+  cell(HC_DEV_WFA) = 0;  // wavefront offsets of the device-side consensus / edit-distance launches (timing runs only)
+  if (c->timing && c->wfa_cells_cur[2]) { const int d2h_rc = trgt::d2h(c, &cell(HC_DEV_WFA), c->wfa_cells_cur[2], 8, c->stream); if (d2h_rc) return d2h_rc; }
+  { const int d2h_rc = trgt::d2h(c, slab.host, slab.dev, slab.total, c->stream); if (d2h_rc) return d2h_rc; }
   TRGT_HIP_TRY(c, hipEventRecord(evA, c->stream));
-  c->dbg_ns[2] = now_ns() - t0;  // + stage A enqueued
-  TL("stage A enqueued");
+  c->dbg_ns[DN_STAGE_A] = now_ns() - t0;  // + stage A enqueued
+  tl("stage A enqueued");
   if (!outputs_ready) init_outputs();  // host-only work: done while the GPU is already busy
-  const int64_t tw_a = now_ns();  // from here on the host waits for stage A (the table upload below sits behind it in the copy queue)
+  tw_a = now_ns();  // from here on the host waits for stage A (the table upload below sits behind it in the copy queue)
   if (use_slots && !hmm_pending && !hmm_pendingB) {  // one HMM batch behind the genotyper and the repair (need_host is final by then)
     hs.d_skip = (const uint8_t*)g.need;
     const int64_t tc0 = now_ns();
     if ((rc = hmm_enqueue_slots(c, &models, hs, out->spans3, out->span_off, out->n_spans, out->motif_counts, out->count_off, out->purity, &hmm_pending))) return rc;
     tC += now_ns() - tc0;
-    TL("hmm1 enqueued (device-resolved job list)");
+    tl("hmm1 enqueued (device-resolved job list)");
   }
   if ((rc = issue_pending_uploads(c))) return rc;  // the next batch's bytes: behind this call's tables and models, next to stage A
-
-  // ---------------- wait for the GPU, publish spans
-  {
-    { const hipError_t ea = trgt::event_wait(evA);
-      if (g_trace_dump && TRGT_DEV_ENV("TRGT_REPAIR_TRACE")) { const uint32_t* h = g_trace_dump; fprintf(stderr, "[repair trace] evA %s counts:", hipGetErrorString(ea)); for (int i = 0; i < 16; ++i) fprintf(stderr, " %u", h[i]);
-        fprintf(stderr, "\n"); }
-      if (ea != hipSuccess) return trgt::fail(c, TRGT_ERR_HIP, "trgt::event_wait(evA) failed: %s", hipGetErrorString(ea)); }
-    if (stage_a_token.owns_lock()) stage_a_token.unlock();
-    tA += now_ns() - tw_a;
-  TL("evA");
-  }
-  int64_t th_begin = now_ns();
+  return TRGT_OK;
+}
+int LocusCall::wait_stage_a() {
+  { const hipError_t ea = trgt::event_wait(evA);
+    if (g_trace_dump && TRGT_DEV_ENV("TRGT_REPAIR_TRACE")) { const uint32_t* h = g_trace_dump; fprintf(stderr, "[repair trace] evA %s counts:", hipGetErrorString(ea)); for (int i = 0; i < 16; ++i) fprintf(stderr, " %u", h[i]);
+      fprintf(stderr, "\n"); }
+    if (ea != hipSuccess) return trgt::fail(c, TRGT_ERR_HIP, "trgt::event_wait(evA) failed: %s", hipGetErrorString(ea)); }
+  if (stage_a_token.owns_lock()) stage_a_token.unlock();
+  tA += now_ns() - tw_a;
+  tl("evA");
+  th_begin = now_ns();
   // ---------------- loci for the host path: all of them without the device genotyper, else the ones it handed back
-  std::vector<int64_t> R;
-  std::vector<uint8_t> need_a;  // need_host as the first HMM batch saw it (2 = waiting for the device-side repair: not its job)
   if (dev_gt) {
     uint8_t* need = (uint8_t*)gh.need;
-    const uint8_t* skip_b = (const uint8_t*)hsl(o_skipb);
+    const uint8_t* skip_b = (const uint8_t*)slab.h(o_skipb);
     if (hmm_pendingB) need_a.assign(need, need + nl);
     for (const uint32_t l : gsd_list) {  // trgt_hip_size_deep_stats (skip_b is 0 only where a finish kernel completed a locus)
       const bool on_device = need[l] == 0 || (need[l] == 2 && !skip_b[l]);
@@ -1245,26 +1335,25 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     for (int64_t l = 0; l < nl; ++l) if (need[l]) R.push_back(l);
     // an alignment job of a device-built list that the generic kernel refused (longer than the workspace planned from the batch's maxima)
     // left INT32_MIN / an empty CIGAR behind: nothing downstream may use that -- the call fails (never seen in the sweeps)
-    if (const uint32_t refused = ((const uint32_t*)hsl(o_rpc))[gt::RC_REFUSED] + ((const uint32_t*)hsl(o_clc))[cl::CC_REFUSED] + ((const uint32_t*)hsl(o_cldc))[cl::CC_REFUSED])
+    if (const uint32_t refused = ((const uint32_t*)slab.h(o_rpc))[gt::RC_REFUSED] + ((const uint32_t*)slab.h(o_clc))[cl::CC_REFUSED] + ((const uint32_t*)slab.h(o_cldc))[cl::CC_REFUSED])
       return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_locus_batch: %u alignment job(s) of the device-side genotyper chains exceed the planned workspace", refused);
-    stat_cons_jobs += (int64_t)((const uint32_t*)hsl(o_rpc))[gt::RC_JOBS];  // consensus alignments of the device-side repair
-    for (const size_t o_cc : {o_clc, o_cldc}) { const uint32_t* cc = (const uint32_t*)hsl(o_cc);  // ... and of the device-side cluster genotyper (both lists), with its edit distances
+    stat_cons_jobs += (int64_t)((const uint32_t*)slab.h(o_rpc))[gt::RC_JOBS];  // consensus alignments of the device-side repair
+    for (const size_t o_cc : {o_clc, o_cldc}) { const uint32_t* cc = (const uint32_t*)slab.h(o_cc);  // ... and of the device-side cluster genotyper (both lists), with its edit distances
       stat_cons_jobs += (int64_t)cc[cl::CC_J1] + (int64_t)cc[cl::CC_J2]; stat_ed_jobs += (int64_t)cc[cl::CC_ED] + (int64_t)cc[cl::CC_ED2]; }
   }
   else { R.resize((size_t)nl); for (int64_t l = 0; l < nl; ++l) R[(size_t)l] = l; }
-  const int64_t nR = (int64_t)R.size();
-  const int32_t* const sp_s = (const int32_t*)h_ss; const int32_t* const sp_e = (const int32_t*)h_se;  // spans (pinned copies)
-  // host path, first part: spanning reads of the loci in R and the gather of their repeat segments (second stream), enqueued
-  // before anything else so that it does not have to share the GPU with the HMM batch below
-  TL("R listed");
+  nR = (int64_t)R.size();
+  sp_s = (const int32_t*)h_ss; sp_e = (const int32_t*)h_se;  // spans (pinned copies)
+  tl("R listed");
+  return TRGT_OK;
+}
   // job lists of stage C for the device-genotyped loci: host-only work, done first because HIP calls made in the ~0.3 ms after the
   // event wait returns block until the runtime has retired stage A's commands
-  std::vector<uint32_t> job_set, seq_len; std::vector<uint64_t> seq_off, span_off, count_off; std::vector<int64_t> slot;
-  std::vector<uint32_t> nsp; std::vector<double> pur;
+void LocusCall::stage_c_job_lists() {
   if (dev_gt && use_slots) {
     for (int64_t l = 0; l < nl; ++l) if (!((const uint8_t*)gh.need)[l]) stat_spanning += ((const uint32_t*)gh.nspan)[l];
     stat_hmm_jobs += hmm_slots_resolved(c, hmm_pending, &models, need_a.empty() ? (const uint8_t*)gh.need : need_a.data(), (const int32_t*)gh.nal, (const uint32_t*)gh.alen);
-    if (hmm_pendingB) stat_hmm_jobs += hmm_slots_resolved(c, hmm_pendingB, &models, (const uint8_t*)hsl(o_skipb), (const int32_t*)gh.nal, (const uint32_t*)gh.alen);
+    if (hmm_pendingB) stat_hmm_jobs += hmm_slots_resolved(c, hmm_pendingB, &models, (const uint8_t*)slab.h(o_skipb), (const int32_t*)gh.nal, (const uint32_t*)gh.alen);
   } else if (dev_gt) {
     const uint8_t* need = (const uint8_t*)gh.need;
     const int32_t* nal = (const int32_t*)gh.nal; const uint32_t* alen = (const uint32_t*)gh.alen;
@@ -1278,129 +1367,133 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         span_off.push_back(out->span_off[2 * l + a]); count_off.push_back(out->count_off[2 * l + a]); slot.push_back(2 * l + a);
       }
     }
-    TL("hmm1 job lists");
+    tl("hmm1 job lists");
   }
+}
   // the two device-resolved HMM batches: the first one's counts / purities arrive as whole arrays ("no allele" in every slot that was not
   // its job), so it is collected first and the second one's are merged in slot by slot
-  auto collect_ab = [&]() -> int {
-    if (!hmm_pendingB) return TRGT_OK;  // (a single batch is collected where it always was, below)
-    const int64_t tc0 = now_ns();
-    if (hmm_pending) {
-      HmmPending* pend = hmm_pending; hmm_pending = nullptr;
-      if (int r = hmm_collect(c, pend)) return r;
-      const uint8_t* need = (const uint8_t*)gh.need;
-      for (int64_t l = 0; l < nl; ++l) if (need[l]) { out->n_spans[2 * l] = out->n_spans[2 * l + 1] = 0; out->purity[2 * l] = out->purity[2 * l + 1] = std::nan(""); }
-      TL("hmm1 collected");
-    }
-    {
-      HmmPending* pend = hmm_pendingB; hmm_pendingB = nullptr;
-      if (int r = hmm_collect(c, pend)) return r;
-      const uint8_t* skip_b = (const uint8_t*)hsl(o_skipb); const int32_t* nal = (const int32_t*)gh.nal;
-      for (int64_t l = 0; l < nl; ++l)
-        if (!skip_b[l]) for (int a = 0; a < nal[l]; ++a) { out->n_spans[2 * l + a] = nsB[(size_t)(2 * l + a)]; out->purity[2 * l + a] = puB[(size_t)(2 * l + a)]; }
-      TL("hmm1b collected");
-    }
-    tC += now_ns() - tc0;
-    return TRGT_OK;
-  };
-  auto collect_hmm1 = [&]() -> int {  // stage C results of the device-genotyped loci (one batch)
-    if (!hmm_pending) return TRGT_OK;
-    const int64_t tc0 = now_ns();
+int LocusCall::collect_ab() {
+  if (!hmm_pendingB) return TRGT_OK;  // (a single batch is collected where it always was, below)
+  const int64_t tc0 = now_ns();
+  if (hmm_pending) {
     HmmPending* pend = hmm_pending; hmm_pending = nullptr;
     if (int r = hmm_collect(c, pend)) return r;
-    TL("hmm1 collected");
-    if (use_slots) {  // (the whole arrays came back: the slots of the loci that took the host path hold "no allele" until stage C of those)
-      const uint8_t* need = (const uint8_t*)gh.need;
-      for (int64_t l = 0; l < nl; ++l) if (need[l]) { out->n_spans[2 * l] = out->n_spans[2 * l + 1] = 0; out->purity[2 * l] = out->purity[2 * l + 1] = std::nan(""); }
-    }
-    for (size_t j = 0; j < slot.size(); ++j) { out->n_spans[slot[j]] = nsp[j]; out->purity[slot[j]] = pur[j]; }
-    tC += now_ns() - tc0;
-    return TRGT_OK;
-  };
-  std::vector<LocusWork> work((size_t)nR);
-  struct K { uint32_t read, s, e; };
-  std::vector<uint64_t> sel_begin((size_t)nR + 1, 0);
+    const uint8_t* need = (const uint8_t*)gh.need;
+    for (int64_t l = 0; l < nl; ++l) if (need[l]) { out->n_spans[2 * l] = out->n_spans[2 * l + 1] = 0; out->purity[2 * l] = out->purity[2 * l + 1] = std::nan(""); }
+    tl("hmm1 collected");
+  }
+  {
+    HmmPending* pend = hmm_pendingB; hmm_pendingB = nullptr;
+    if (int r = hmm_collect(c, pend)) return r;
+    const uint8_t* skip_b = (const uint8_t*)slab.h(o_skipb); const int32_t* nal = (const int32_t*)gh.nal;
+    for (int64_t l = 0; l < nl; ++l)
+      if (!skip_b[l]) for (int a = 0; a < nal[l]; ++a) { out->n_spans[2 * l + a] = nsB[(size_t)(2 * l + a)]; out->purity[2 * l + a] = puB[(size_t)(2 * l + a)]; }
+    tl("hmm1b collected");
+  }
+  tC += now_ns() - tc0;
+  return TRGT_OK;
+}
+int LocusCall::collect_hmm1() {  // stage C results of the device-genotyped loci (one batch)
+  if (!hmm_pending) return TRGT_OK;
+  const int64_t tc0 = now_ns();
+  HmmPending* pend = hmm_pending; hmm_pending = nullptr;
+  if (int r = hmm_collect(c, pend)) return r;
+  tl("hmm1 collected");
+  if (use_slots) {  // (the whole arrays came back: the slots of the loci that took the host path hold "no allele" until stage C of those)
+    const uint8_t* need = (const uint8_t*)gh.need;
+    for (int64_t l = 0; l < nl; ++l) if (need[l]) { out->n_spans[2 * l] = out->n_spans[2 * l + 1] = 0; out->purity[2 * l] = out->purity[2 * l + 1] = std::nan(""); }
+  }
+  for (size_t j = 0; j < slot.size(); ++j) { out->n_spans[slot[j]] = nsp[j]; out->purity[slot[j]] = pur[j]; }
+  tC += now_ns() - tc0;
+  return TRGT_OK;
+}
+  // host path, first part: spanning reads of the loci in R and the gather of their repeat segments (second stream), enqueued
+  // before anything else so that it does not have to share the GPU with the HMM batch below
+void LocusCall::select_host_reads() {
+  work.resize((size_t)nR);
+  sel_begin.assign((size_t)nR + 1, 0);
   for (int64_t li = 0; li < nR; ++li) sel_begin[(size_t)li + 1] = sel_begin[(size_t)li] + (in->locus_read_begin[R[(size_t)li] + 1] - in->locus_read_begin[R[(size_t)li]]);
-  std::vector<K> sel((size_t)sel_begin[(size_t)nR]);
-  std::vector<uint32_t> n_sel((size_t)nR, 0);
-  std::vector<Scratch> scratch((size_t)pool->size());
-  std::vector<uint64_t> seg_src, seg_dst; std::vector<uint32_t> seg_len, seg_read; std::vector<const uint8_t*> seg_ptr;
-  uint64_t n_seg = 0, seg_bytes = 0;
-  void* h_seg = nullptr;
-  if (nR > 0) {
-    int64_t th0 = now_ns();
-    // pass 1 (parallel over loci): filter (tr.rs:139-145), stable sort by span length (:157), uniform downsample (:172-184)
-    pool->parallel_for(nR, 32, [&](int64_t li, int) {
-      const int64_t l = R[(size_t)li];
-      if (in->ploidy[l] == 0) return;  // Ploidy::Zero -> LocusResult::empty (tr.rs:29-31)
-      K* ks = sel.data() + sel_begin[(size_t)li];
-      uint32_t n = 0;
-      for (uint64_t r = in->locus_read_begin[l]; r < in->locus_read_begin[l + 1]; ++r) {
-        const int32_t s = sp_s[r], e = sp_e[r];
-        if (s < 0) continue;
-        if (s >= F && (int64_t)in->read_len[r] - e >= F) {
-          const K kk{(uint32_t)r, (uint32_t)s, (uint32_t)e};
-          uint32_t i = n++;  // stable insertion sort by span length
-          while (i > 0 && (ks[i - 1].e - ks[i - 1].s) > (kk.e - kk.s)) { ks[i] = ks[i - 1]; --i; }
-          ks[i] = kk;
-        }
+  sel.resize((size_t)sel_begin[(size_t)nR]);
+  n_sel.assign((size_t)nR, 0);
+  scratch.resize((size_t)pool->size());
+  if (nR == 0) return;
+  th0 = now_ns();
+  // pass 1 (parallel over loci): filter (tr.rs:139-145), stable sort by span length (:157), uniform downsample (:172-184)
+  pool->parallel_for(nR, 32, [&](int64_t li, int) {
+    const int64_t l = R[(size_t)li];
+    if (in->ploidy[l] == 0) return;  // Ploidy::Zero -> LocusResult::empty (tr.rs:29-31)
+    K* ks = sel.data() + sel_begin[(size_t)li];
+    uint32_t n = 0;
+    for (uint64_t r = in->locus_read_begin[l]; r < in->locus_read_begin[l + 1]; ++r) {
+      const int32_t s = sp_s[r], e = sp_e[r];
+      if (s < 0) continue;
+      if (s >= F && (int64_t)in->read_len[r] - e >= F) {
+        const K kk{(uint32_t)r, (uint32_t)s, (uint32_t)e};
+        uint32_t i = n++;  // stable insertion sort by span length
+        while (i > 0 && (ks[i - 1].e - ks[i - 1].s) > (kk.e - kk.s)) { ks[i] = ks[i - 1]; --i; }
+        ks[i] = kk;
       }
-      if ((int64_t)n > p->max_depth) {
-        const double step = (double)n / (double)p->max_depth;
-        double fast = 0.0;
-        for (int i = 0; i < p->max_depth; ++i) { const size_t ind = (size_t)std::floor(fast); if (ind != (size_t)i) std::swap(ks[i], ks[ind]); fast += step; }
-        n = (uint32_t)p->max_depth;
-      }
-      n_sel[(size_t)li] = n;
-    });
-    // filter_impure_trs (tr.rs:400-452): purity of the repeat segment of every read without a quality >= 0.9 (one HMM batch),
-    // stable sort by purity (f64::total_cmp), drop at most max(1, round(0.1 n)) reads below 0.9
-    if (impure_filter) {
-      std::vector<uint32_t> pj_set, pj_len, pj_nsp; std::vector<uint64_t> pj_off, pj_cnt_off; std::vector<double> pj_pur;
-      std::vector<uint64_t> pj_begin((size_t)nR + 1, 0);
-      uint64_t cnt_total = 0;
-      for (int64_t li = 0; li < nR; ++li) {
-        const int64_t l = R[(size_t)li];
-        const K* ks = sel.data() + sel_begin[(size_t)li];
-        const uint32_t nm = in->set_motif_begin[l + 1] - in->set_motif_begin[l];
-        for (uint32_t i = 0; i < n_sel[(size_t)li]; ++i) {
-          const double rq = in->read_qual ? in->read_qual[ks[i].read] : std::nan("");
-          if (rq >= 0.9) continue;  // Some(rq) with rq >= cutoff keeps purity 1.0; None (NaN) and low qualities are scored
-          pj_set.push_back((uint32_t)l); pj_off.push_back(in->read_off[ks[i].read] + ks[i].s); pj_len.push_back(ks[i].e - ks[i].s);
-          pj_cnt_off.push_back(cnt_total); cnt_total += nm;
-        }
-        pj_begin[(size_t)li + 1] = pj_set.size();
-      }
-      if (!pj_set.empty()) {
-        // (the device-resolved stage-C batches of this call hold the HMM buffer sets: they are collected before this batch takes one)
-        if ((rc = collect_ab()) || (rc = collect_hmm1())) return rc;
-        pj_nsp.resize(pj_set.size()); pj_pur.resize(pj_set.size());
-        std::vector<uint32_t> pj_counts((size_t)cnt_total + 1);
-        rc = hmm_batch_impl(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, (int64_t)pj_set.size(), pj_set.data(),
-                            reads_on_device ? d_reads : in->read_blob, pj_off.data(), pj_len.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                            pj_nsp.data(), pj_counts.data(), pj_cnt_off.data(), pj_pur.data(), nullptr, nullptr);
-        if (rc) return rc;
-        stat_hmm_jobs += (int64_t)pj_set.size();
-      }
-      auto total_key = [](double d) { int64_t b; std::memcpy(&b, &d, 8); b ^= (int64_t)((uint64_t)(b >> 63) >> 1); return b; };
-      pool->parallel_for(nR, 32, [&](int64_t li, int) {
-        K* ks = sel.data() + sel_begin[(size_t)li];
-        const uint32_t n = n_sel[(size_t)li];
-        if (n == 0) return;
-        std::vector<std::pair<double, K>> pr((size_t)n);
-        uint64_t j = pj_begin[(size_t)li];
-        for (uint32_t i = 0; i < n; ++i) {
-          const double rq = in->read_qual ? in->read_qual[ks[i].read] : std::nan("");
-          pr[i] = {rq >= 0.9 ? 1.0 : pj_pur[(size_t)j++], ks[i]};
-        }
-        std::stable_sort(pr.begin(), pr.end(), [&](const std::pair<double, K>& a, const std::pair<double, K>& b) { return total_key(a.first) < total_key(b.first); });
-        const size_t max_filter = std::max<size_t>(1, (size_t)std::round(0.1 * (double)n));
-        size_t filtered = 0; uint32_t m = 0;
-        for (auto& q : pr) { if (q.first >= 0.9 || filtered >= max_filter) ks[m++] = q.second; else ++filtered; }
-        n_sel[(size_t)li] = m;
-      });
     }
-    TL("R pass 1");
+    if ((int64_t)n > p->max_depth) {
+      const double step = (double)n / (double)p->max_depth;
+      double fast = 0.0;
+      for (int i = 0; i < p->max_depth; ++i) { const size_t ind = (size_t)std::floor(fast); if (ind != (size_t)i) std::swap(ks[i], ks[ind]); fast += step; }
+      n = (uint32_t)p->max_depth;
+    }
+    n_sel[(size_t)li] = n;
+  });
+}
+int LocusCall::gather_host_segments() {
+  int rc;
+  // filter_impure_trs (tr.rs:400-452): purity of the repeat segment of every read without a quality >= 0.9 (one HMM batch),
+  // stable sort by purity (f64::total_cmp), drop at most max(1, round(0.1 n)) reads below 0.9
+  if (nR > 0 && impure_filter) {
+    std::vector<uint32_t> pj_set, pj_len, pj_nsp; std::vector<uint64_t> pj_off, pj_cnt_off; std::vector<double> pj_pur;
+    std::vector<uint64_t> pj_begin((size_t)nR + 1, 0);
+    uint64_t cnt_total = 0;
+    for (int64_t li = 0; li < nR; ++li) {
+      const int64_t l = R[(size_t)li];
+      const K* ks = sel.data() + sel_begin[(size_t)li];
+      const uint32_t nm = in->set_motif_begin[l + 1] - in->set_motif_begin[l];
+      for (uint32_t i = 0; i < n_sel[(size_t)li]; ++i) {
+        const double rq = in->read_qual ? in->read_qual[ks[i].read] : std::nan("");
+        if (rq >= 0.9) continue;  // Some(rq) with rq >= cutoff keeps purity 1.0; None (NaN) and low qualities are scored
+        pj_set.push_back((uint32_t)l); pj_off.push_back(in->read_off[ks[i].read] + ks[i].s); pj_len.push_back(ks[i].e - ks[i].s);
+        pj_cnt_off.push_back(cnt_total); cnt_total += nm;
+      }
+      pj_begin[(size_t)li + 1] = pj_set.size();
+    }
+    if (!pj_set.empty()) {
+      // (the device-resolved stage-C batches of this call hold the HMM buffer sets: they are collected before this batch takes one)
+      if ((rc = collect_ab()) || (rc = collect_hmm1())) return rc;
+      pj_nsp.resize(pj_set.size()); pj_pur.resize(pj_set.size());
+      std::vector<uint32_t> pj_counts((size_t)cnt_total + 1);
+      rc = hmm_batch_impl(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, (int64_t)pj_set.size(), pj_set.data(),
+                          reads_on_device ? d_reads : in->read_blob, pj_off.data(), pj_len.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
+                          pj_nsp.data(), pj_counts.data(), pj_cnt_off.data(), pj_pur.data(), nullptr, nullptr);
+      if (rc) return rc;
+      stat_hmm_jobs += (int64_t)pj_set.size();
+    }
+    auto total_key = [](double d) { int64_t b; std::memcpy(&b, &d, 8); b ^= (int64_t)((uint64_t)(b >> 63) >> 1); return b; };
+    pool->parallel_for(nR, 32, [&](int64_t li, int) {
+      K* ks = sel.data() + sel_begin[(size_t)li];
+      const uint32_t n = n_sel[(size_t)li];
+      if (n == 0) return;
+      std::vector<std::pair<double, K>> pr((size_t)n);
+      uint64_t j = pj_begin[(size_t)li];
+      for (uint32_t i = 0; i < n; ++i) {
+        const double rq = in->read_qual ? in->read_qual[ks[i].read] : std::nan("");
+        pr[i] = {rq >= 0.9 ? 1.0 : pj_pur[(size_t)j++], ks[i]};
+      }
+      std::stable_sort(pr.begin(), pr.end(), [&](const std::pair<double, K>& a, const std::pair<double, K>& b) { return total_key(a.first) < total_key(b.first); });
+      const size_t max_filter = std::max<size_t>(1, (size_t)std::round(0.1 * (double)n));
+      size_t filtered = 0; uint32_t m = 0;
+      for (auto& q : pr) { if (q.first >= 0.9 || filtered >= max_filter) ks[m++] = q.second; else ++filtered; }
+      n_sel[(size_t)li] = m;
+    });
+  }
+  if (nR > 0) {
+    tl("R pass 1");
     // pass 2: flat segment arrays (LocusResult.reads order within each locus)
     for (int64_t li = 0; li < nR; ++li) { work[(size_t)li].seg_begin = n_seg; n_seg += n_sel[(size_t)li]; work[(size_t)li].seg_end = n_seg; }
     seg_src.resize((size_t)n_seg); seg_dst.resize((size_t)n_seg); seg_len.resize((size_t)n_seg); seg_read.resize((size_t)n_seg); seg_ptr.resize((size_t)n_seg);
@@ -1413,8 +1506,8 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     });
     for (uint64_t s = 0; s < n_seg; ++s) { seg_dst[s] = seg_bytes; seg_bytes += seg_len[s]; }
     stat_spanning += (int64_t)n_seg;
-    c->dbg_ns[4] = now_ns() - th0;
-    TL("R pass 2");
+    c->dbg_ns[DN_SELECT] = now_ns() - th0;
+    tl("R pass 2");
     if (n_seg > 0 && reads_on_device) {
       // source offsets, destination offsets and lengths: the gather kernel reads them straight from pinned host memory (20 B per
       // segment over PCIe).  A hipMemcpyAsync of them took 0.37 ms on the host however small it was.
@@ -1426,28 +1519,34 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       std::memcpy(h_meta, seg_src.data(), (size_t)n_seg * 8);
       std::memcpy((uint8_t*)h_meta + (size_t)n_seg * 8, seg_dst.data(), (size_t)n_seg * 8);
       std::memcpy((uint8_t*)h_meta + (size_t)n_seg * 16, seg_len.data(), (size_t)n_seg * 4);
-      TL("R meta staged");
+      tl("R meta staged");
       void* const d_src = h_meta; void* const d_dst = (uint8_t*)h_meta + (size_t)n_seg * 8; void* const d_len = (uint8_t*)h_meta + (size_t)n_seg * 16;
       GatherArgs ga{d_reads, (const uint64_t*)d_src, (const uint64_t*)d_dst, (const uint32_t*)d_len, (uint64_t)n_seg, (uint8_t*)d_out};
       hipLaunchKernelGGL(gather_segments_kernel, dim3((unsigned)((n_seg + 3) / 4)), dim3(256), 0, c->stream2, ga);
       TRGT_HIP_TRY(c, hipGetLastError());
-      TL("R gather launched");
+      tl("R gather launched");
       { const int d2h_rc = trgt::d2h(c, h_seg, d_out, (size_t)seg_bytes, c->stream2); if (d2h_rc) return d2h_rc; }
     }
   }
-  TL("R selected, gather enqueued");
+  tl("R selected, gather enqueued");
   // ---------------- the alleles of the device-genotyped loci come back packed: a second, exact-size copy (second stream)
   if (dev_gt) {
     const uint64_t packed_total = ((const uint64_t*)gh.toff)[2 * nl];
     if ((rc = pin_get(c, P_GT_PACKED, (size_t)packed_total + 16, &gh.packed))) return rc;
     if (packed_total) { const int d2h_rc = trgt::d2h(c, gh.packed, g.packed, (size_t)packed_total, c->stream2); if (d2h_rc) return d2h_rc; }
   }
+  if (nR == 0 && (rc = hmm1_once())) return rc;
+  if (dev_gt || (n_seg > 0 && reads_on_device)) TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream2));  // gathered segments, packed alleles
+  tHost += now_ns() - th_begin;
+  tl("stream2 synced");
+  return TRGT_OK;
+}
   // ---------------- stage C for the device-genotyped loci (on alleles that already sit in HBM; collected at the end) and the
   // publishing of spans and device-genotyper results: host work of ~1.2 ms that needs the GPU only to start the HMM batch.  It runs
   // while the consensus alignments of the host-path loci are on the GPU (wfa_batch_impl calls it between launch and wait), or
   // right here when there are none.
-  bool published = false;
-  auto hmm1_enqueue = [&]() -> int {
+int LocusCall::hmm1_enqueue() {
+  int rc;
   if (dev_gt && !use_slots) {
     if (!job_set.empty()) {
       nsp.resize(job_set.size()); pur.resize(job_set.size());
@@ -1457,33 +1556,26 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
                        out->motif_counts, count_off.data(), pur.data(), nullptr, nullptr, &hmm_pending);
       if (rc) return rc;
       tC += now_ns() - tc0;
-      TL("hmm1 enqueued");
+      tl("hmm1 enqueued");
       stat_hmm_jobs += (int64_t)job_set.size();
     }
   }
   return TRGT_OK;
-  };
+}
   // (enqueued from the callback below when there are consensus alignments: its ~0.7 ms of host work then runs next to that kernel
   //  instead of in front of the host path that leads to it)
-  bool hmm1_done = false;
-  auto hmm1_once = [&]() -> int {  // on the first stream, whichever stream is current
-    if (hmm1_done) return TRGT_OK;
-    hmm1_done = true;
-    const bool swapped = c->stream == upload_stream;
-    if (swapped) std::swap(c->stream, c->stream2);
-    const int r = hmm1_enqueue();
-    if (swapped) std::swap(c->stream, c->stream2);
-    return r;
-  };
-  if (nR == 0 && (rc = hmm1_once())) return rc;
-  if (dev_gt || (n_seg > 0 && reads_on_device)) TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream2));  // gathered segments, packed alleles
-  tHost += now_ns() - th_begin;
-  TL("stream2 synced");
+int LocusCall::hmm1_once() {  // on the first stream, whichever stream is current
+  if (hmm1_done) return TRGT_OK;
+  hmm1_done = true;
+  StreamGuard keep(c);
+  if (c->stream == upload_stream) std::swap(c->stream, c->stream2);
+  return hmm1_enqueue();
+}
   // ---------------- publish spans and the device genotyper's results: host-only work, done while the consensus alignments of the
   // host-path loci are on the GPU (wfa_batch_impl calls it between launch and wait), or at the end when there are none
-  auto publish = [&]() -> int {
+int LocusCall::publish() {
   published = true;
-  TL("publish begins");
+  tl("publish begins");
   pool->parallel_for(8, 1, [&](int64_t part8, int) {  // ~6 MB of result arrays: spread the copies over a few threads
     auto piece = [&](void* dst, const void* src, size_t bytes, int64_t k, int64_t n) {
       const size_t b = bytes * (size_t)k / (size_t)n, e = bytes * (size_t)(k + 1) / (size_t)n;
@@ -1497,7 +1589,7 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
       piece(out->ci, gh.ci, 4 * (size_t)nl * 4, part8, 8); piece(out->num_spanning, gh.nsp, 2 * (size_t)nl * 4, part8, 8);
     }
   });
-  TL("publish: arrays copied");
+  tl("publish: arrays copied");
   {
     std::vector<int64_t> part((size_t)pool->size() * 8, 0);
     pool->parallel_for(nr, 8192, [&](int64_t r, int t) {
@@ -1508,16 +1600,16 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     for (int t = 0; t < pool->size(); ++t) { stat_flank_jobs += part[(size_t)t * 8]; stat_flank_heavy += part[(size_t)t * 8 + 1]; }
   }
   if (c->timing) {  // [0] all flank alignments, [1] those of the first (dominant) launch
-    c->k_cells[TRGT_K_WFA_FLANK] += (int64_t)((uint64_t*)h_cells)[1];
-    c->k_cells[TRGT_K_WFA_FLANK_REST] += (int64_t)(((uint64_t*)h_cells)[0] - ((uint64_t*)h_cells)[1]);
-    c->k_cells[TRGT_K_WFA_FILTER] += (int64_t)((uint64_t*)h_cells)[4];
-    c->k_cells[TRGT_K_WFA] += (int64_t)((uint64_t*)h_cells)[6];
+    c->k_cells[TRGT_K_WFA_FLANK] += (int64_t)cell(HC_FLANK_FIRST);
+    c->k_cells[TRGT_K_WFA_FLANK_REST] += (int64_t)(cell(HC_FLANK_ALL) - cell(HC_FLANK_FIRST));
+    c->k_cells[TRGT_K_WFA_FILTER] += (int64_t)cell(HC_FILTER_OFFSETS);
+    c->k_cells[TRGT_K_WFA] += (int64_t)cell(HC_DEV_WFA);
   }
   if (dev_gt) {
     const uint8_t* need = (const uint8_t*)gh.need;
     const uint64_t* toff = (const uint64_t*)gh.toff; const uint8_t* packed = (const uint8_t*)gh.packed;
-    const uint8_t* dev_flip = (const uint8_t*)hsl(o_flip);
-    const int32_t* dev_gsz = (const int32_t*)hsl(o_gsz);
+    const uint8_t* dev_flip = (const uint8_t*)slab.h(o_flip);
+    const int32_t* dev_gsz = (const int32_t*)slab.h(o_gsz);
     pool->parallel_for(nl, 256, [&](int64_t l, int) {
       if (out->flipped) out->flipped[l] = need[l] ? 0 : dev_flip[l];
       // (alleles the device genotyper settles have majority support: their length is the genotype's size)
@@ -1527,240 +1619,255 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
         std::memcpy(out->allele_blob + out->allele_off[2 * l + a], packed + toff[2 * l + a], out->allele_len[2 * l + a]);
     });
   }
-  TL("published");
+  tl("published");
   return TRGT_OK;
-  };
-
+}
   // ---------------- host path for the loci in R, second part (second stream for its GPU work: consensus alignments)
-  if (nR > 0) {
-    int64_t th0 = now_ns();
-    if (n_seg > 0 && reads_on_device) { for (uint64_t s = 0; s < n_seg; ++s) seg_ptr[s] = (const uint8_t*)h_seg + seg_dst[s]; }
-    else { for (uint64_t s = 0; s < n_seg; ++s) seg_ptr[s] = in->read_blob + seg_src[s]; }
-    // front half of the length genotyper, threaded over loci (per-thread scratch, no per-locus allocation)
-    int64_t tf0 = now_ns();
-    std::vector<ClusterLocus> cl_loci;
-    std::vector<std::vector<Seg>> cl_trs;
-    for (int64_t li = 0; li < nR; ++li) {
-      LocusWork& w = work[(size_t)li];
-      if (w.seg_begin == w.seg_end || !is_cluster(R[(size_t)li])) continue;
-      w.cluster = (int)cl_loci.size();
-      ClusterLocus L; L.li = li; L.ploidy = in->ploidy[R[(size_t)li]] == 1 ? 1 : 2; L.n = (int)(w.seg_end - w.seg_begin);
-      cl_loci.push_back(std::move(L));
-      cl_trs.emplace_back();
-      for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) cl_trs.back().push_back(Seg{seg_ptr[s], seg_len[s]});
-    }
-    for (size_t k = 0; k < cl_loci.size(); ++k) cl_loci[k].trs = cl_trs[k].data();
-    pool->parallel_for(nR, 16, [&](int64_t li, int t) {
-      LocusWork& w = work[(size_t)li];
-      if (w.seg_begin == w.seg_end || w.cluster >= 0) return;
-      Scratch& sc = scratch[(size_t)t];
-      sc.trs.clear();
-      for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) sc.trs.push_back(Seg{seg_ptr[s], seg_len[s]});
-      genotype_size_front(in->ploidy[R[(size_t)li]] == 1 ? 1 : 2, li, t, w, sc);
-    });
-    c->dbg_ns[6] = now_ns() - tf0;
-  TL("front");
-    tHost += now_ns() - th0;
-    // ---- stage B: consensus alignments (BiWFA, affine 2,5,1, default heuristic) for the loci that need them
-    std::swap(c->stream, c->stream2);
-    struct SwapBack { trgt_hip_ctx* c; ~SwapBack() { std::swap(c->stream, c->stream2); } } swap_back{c};
-    int64_t tb0 = now_ns();
-    struct JobRef { Repair* rep; int member; };
-    std::vector<JobRef> jrefs;
-    std::vector<uint8_t> cblob; std::vector<uint64_t> poff, toff; std::vector<uint32_t> plen, tlen;
-    for (auto& sc : scratch)
-      for (auto& rep : sc.repairs) {
-        const Seg bb = work[(size_t)rep.locus].pick[rep.allele];
-        const uint64_t bo = cblob.size();
-        cblob.insert(cblob.end(), bb.p, bb.p + bb.n);
-        for (size_t m = 0; m < rep.members.size(); ++m) {
-          const Seg& sg = rep.members[m];
-          poff.push_back(bo); plen.push_back(bb.n);
-          toff.push_back(cblob.size()); tlen.push_back(sg.n);
-          cblob.insert(cblob.end(), sg.p, sg.p + sg.n);
-          jrefs.push_back({&rep, (int)m});
-        }
-      }
-    std::vector<size_t> rep_first{0};  // jobs of one repair are contiguous
-    std::vector<Repair*> rep_of;
-    for (size_t j = 0; j < jrefs.size(); ++j)
-      if (jrefs[j].member == 0) { if (j) rep_first.push_back(j); rep_of.push_back(jrefs[j].rep); }
-    if (!jrefs.empty()) rep_first.push_back(jrefs.size());
-    if (jrefs.empty() && ((rc = hmm1_once()) || (!published && (rc = publish())))) return rc;
-    if (!jrefs.empty()) {
-      const std::function<int()> overlap = [&]() -> int {  // next to the alignment kernel: start the HMM batch, publish results
-        const int r = hmm1_once();
-        return r ? r : publish();
-      };
-      std::vector<std::string> repaired;
-      rc = consensus_repair_batch(c, (int64_t)jrefs.size(), cblob.data(), poff.data(), plen.data(), toff.data(), tlen.data(), rep_first, repaired, &overlap);
-      if (rc) return rc;
-      for (size_t g = 0; g < rep_of.size(); ++g) rep_of[g]->result.swap(repaired[g]);
-      stat_cons_jobs += (int64_t)jrefs.size();
-    }
-    // ---- Genotyper::Cluster loci: distance matrix, Ward linkage, consensus rounds, outlier assignment (locus_cluster.hpp)
-    if (!cl_loci.empty()) {
-      ClusterBatch cb(c, pool, cl_loci);
-      if ((rc = cb.run())) return rc;
-      stat_cons_jobs += cb.n_cons;
-      stat_ed_jobs += cb.n_ed;
-    }
-    tB = now_ns() - tb0;
-  TL("stageB");
-    // ---- host: repair_consensus, classification, reference allele first, output assembly
-    th0 = now_ns();
-    // ---- genotype_flank::genotype (genotype_flank.rs:9-42) for the loci whose two alleles are at most 10 bases apart (tr.rs:69-75)
-    struct FlankRes { bool on = false; std::string repaired[2]; Seg al[2]; uint32_t ci[4] = {0, 0, 0, 0}; std::vector<int8_t> assignment; int rep_group[2] = {-1, -1}; };
-    std::vector<FlankRes> fres((size_t)(flank_on ? nR : 0));
-    if (flank_on) {
-      struct FlankRepair { int64_t li; int a; Seg backbone; std::vector<Seg> members; };
-      std::vector<std::vector<FlankRepair>> freps((size_t)pool->size());
-      pool->parallel_for(nR, 16, [&](int64_t li, int t) {
-        LocusWork& w = work[(size_t)li];
-        if (w.seg_begin == w.seg_end) return;
-        int n_gt; uint32_t s0, s1;  // Gt sizes: the length genotyper's sizes, the cluster genotyper's allele lengths
-        if (w.cluster >= 0) { const ClusterLocus& L = cl_loci[(size_t)w.cluster]; n_gt = L.n_gt; s0 = (uint32_t)L.allele[0].size(); s1 = (uint32_t)L.allele[1].size(); }
-        else { n_gt = w.n_gt; s0 = w.size[0]; s1 = w.size[1]; }
-        if (n_gt != 2 || adiff(s0, s1) > 10) return;
-        std::vector<uint32_t> rd;
-        for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) rd.push_back(seg_read[s]);
-        FlankSplit sp;
-        if (!flank_split(flank_meta, rd.data(), rd.size(), sp)) return;
-        FlankRes fr;
-        for (int g = 0; g < 2; ++g) {
-          std::vector<Seg> seqs;
-          uint32_t lo = 0xFFFFFFFFu, hi = 0;
-          for (uint32_t i : sp.group[g]) { const uint64_t s = w.seg_begin + i; seqs.push_back(Seg{seg_ptr[s], seg_len[s]}); lo = std::min(lo, seg_len[s]); hi = std::max(hi, seg_len[s]); }
-          Seg best; double freq;
-          if (!flank_simple_consensus(seqs, best, freq)) return;  // an empty group: None
-          fr.al[g] = best; fr.ci[2 * g] = lo; fr.ci[2 * g + 1] = hi;
-          if (freq < 0.5) { fr.rep_group[g] = (int)freps[(size_t)t].size(); freps[(size_t)t].push_back(FlankRepair{li, g, best, std::move(seqs)}); }
-        }
-        fr.on = true; fr.assignment = std::move(sp.assignment);
-        fres[(size_t)li] = std::move(fr);
-      });
-      // groups without a majority sequence: align(backbone, members) + repair_consensus, one more batch on the device
-      std::vector<uint8_t> fb; std::vector<uint64_t> fpo, fto; std::vector<uint32_t> fpl, ftl; std::vector<size_t> ffirst{0};
-      std::vector<std::pair<int64_t, int>> fwho;
-      for (auto& v : freps)
-        for (auto& q : v) {
-          const uint64_t bo = fb.size();
-          fb.insert(fb.end(), q.backbone.p, q.backbone.p + q.backbone.n);
-          for (auto& m : q.members) { fpo.push_back(bo); fpl.push_back(q.backbone.n); fto.push_back(fb.size()); ftl.push_back(m.n); fb.insert(fb.end(), m.p, m.p + m.n); }
-          ffirst.push_back(fpo.size()); fwho.push_back({q.li, q.a});
-        }
-      if (!fwho.empty()) {
-        std::vector<std::string> repaired;
-        if ((rc = consensus_repair_batch(c, (int64_t)fpo.size(), fb.data(), fpo.data(), fpl.data(), fto.data(), ftl.data(), ffirst, repaired))) return rc;
-        stat_cons_jobs += (int64_t)fpo.size();
-        for (size_t g = 0; g < fwho.size(); ++g) {
-          FlankRes& fr = fres[(size_t)fwho[g].first];
-          fr.repaired[fwho[g].second].swap(repaired[g]);
-        }
-      }
-      for (auto& fr : fres) {
-        if (!fr.on) continue;
-        for (int g = 0; g < 2; ++g) if (fr.rep_group[g] >= 0) fr.al[g] = Seg{(const uint8_t*)fr.repaired[g].data(), (uint32_t)fr.repaired[g].size()};
-        if (fr.al[0].n > fr.al[1].n) {  // smaller allele first (:33-38)
-          std::swap(fr.al[0], fr.al[1]); std::swap(fr.ci[0], fr.ci[2]); std::swap(fr.ci[1], fr.ci[3]);
-          for (auto& a : fr.assignment) a = (int8_t)((a + 1) % 2);
-        }
-      }
-    }
-    std::vector<int8_t> seg_cls((size_t)n_seg, 0);
-    std::atomic<int> bad{0};
-    pool->parallel_for(nR, 64, [&](int64_t li, int) {
-      const int64_t l = R[(size_t)li];
-      LocusWork& w = work[(size_t)li];
-      if (w.seg_begin == w.seg_end) return;
-      const int ploidy = in->ploidy[l] == 1 ? 1 : 2;
-      Seg al[2];
-      int by_hap[2] = {0, 0};
-      if (w.cluster >= 0) {  // genotype_cluster::genotype results
-        const ClusterLocus& L = cl_loci[(size_t)w.cluster];
-        w.n_gt = L.n_gt;
-        for (int a = 0; a < L.n_gt; ++a) { al[a] = Seg{(const uint8_t*)L.allele[a].data(), (uint32_t)L.allele[a].size()}; w.ci[2 * a] = L.ci[2 * a]; w.ci[2 * a + 1] = L.ci[2 * a + 1]; }
-        for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) { const int cc = L.cls[(size_t)(s - w.seg_begin)]; seg_cls[s] = (int8_t)cc; by_hap[cc] += 1; }
-      } else {
-        for (int a = 0; a < w.n_pick; ++a) {
-          if (w.repair[a] >= 0) { const std::string& r = scratch[(size_t)w.repair_thread].repairs[(size_t)w.repair[a]].result; al[a] = Seg{(const uint8_t*)r.data(), (uint32_t)r.size()}; }
-          else al[a] = w.pick[a];
-        }
-        int n_al = w.n_pick;
-        if (ploidy == 2 && n_al == 1) { al[1] = al[0]; n_al = 2; }
-        int tie = 1;
-        for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) {
-          int cc = 0;
-          if (n_al == 2) {
-            const uint32_t d1 = adiff(seg_len[s], al[0].n), d2 = adiff(seg_len[s], al[1].n);
-            if (d1 < d2) cc = 0; else if (d1 > d2) cc = 1; else { tie = (tie + 1) % 2; cc = tie; }
-          }
-          seg_cls[s] = (int8_t)cc; by_hap[cc] += 1;
-        }
-      }
-      // TrSize::size of the genotype: the length genotyper's sizes; the cluster genotyper's and the flank genotype's are allele lengths
-      uint32_t gsz[2] = {w.cluster >= 0 ? al[0].n : w.size[0], w.cluster >= 0 ? (w.n_gt > 1 ? al[1].n : 0u) : w.size[1]};
-      if (flank_on && fres[(size_t)li].on) {  // the flank genotype replaces alleles, intervals and the read assignment
-        const FlankRes& fr = fres[(size_t)li];
-        w.n_gt = 2; al[0] = fr.al[0]; al[1] = fr.al[1]; gsz[0] = al[0].n; gsz[1] = al[1].n;
-        for (int k = 0; k < 4; ++k) w.ci[k] = fr.ci[k];
-        by_hap[0] = by_hap[1] = 0;
-        for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) { const int cc = fr.assignment[(size_t)(s - w.seg_begin)]; seg_cls[s] = (int8_t)cc; by_hap[cc] += 1; }
-      }
-      int order[2] = {0, 1};
-      const Seg ref{in->tr_blob + in->tr_off[l], in->tr_len[l]};
-      bool flip = false;
-      if (w.n_gt != 1 && !eq_seg(al[0], ref) && eq_seg(al[1], ref)) { order[0] = 1; order[1] = 0; flip = true; }  // tr.rs:95-101
-      out->n_alleles[l] = w.n_gt;
-      for (int oi = 0; oi < w.n_gt; ++oi) {
-        const int a = order[oi];
-        if (al[a].n > out->allele_cap[l]) { bad = 1; return; }
-        std::memcpy(out->allele_blob + out->allele_off[2 * l + oi], al[a].p, al[a].n);
-        out->allele_len[2 * l + oi] = al[a].n;
-        out->ci[4 * l + 2 * oi] = (int32_t)w.ci[2 * a]; out->ci[4 * l + 2 * oi + 1] = (int32_t)w.ci[2 * a + 1];
-        out->num_spanning[2 * l + oi] = by_hap[a];
-        if (out->gt_size) out->gt_size[2 * l + oi] = (int32_t)gsz[a];
-      }
-      if (out->flipped) out->flipped[l] = flip ? 1 : 0;
-      for (uint64_t r = in->locus_read_begin[l]; r < in->locus_read_begin[l + 1]; ++r) { out->classification[r] = -1; out->read_rank[r] = -1; }
-      for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) {
-        out->classification[seg_read[s]] = flip ? 1 - seg_cls[s] : seg_cls[s];
-        out->read_rank[seg_read[s]] = (int32_t)(s - w.seg_begin);
-      }
-    });
-    if (bad) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: allele_cap too small");
-    c->dbg_ns[7] = now_ns() - th0;
-  TL("back");
-    tHost += now_ns() - th0;
-    // ---- stage C for the host-path loci (label_with_hmm for every allele): enqueued here, on the second stream and the second set
-    // of HMM buffers, next to the batch of the device-genotyped loci that is still running
-    const int64_t tc0 = now_ns();
-    for (int64_t li = 0; li < nR; ++li) {
-      const int64_t l = R[(size_t)li];
-      for (int a = 0; a < out->n_alleles[l]; ++a) {
-        js2.push_back((uint32_t)l); so2.push_back(out->allele_off[2 * l + a]); sl2.push_back(out->allele_len[2 * l + a]);
-        spo2.push_back(out->span_off[2 * l + a]); co2.push_back(out->count_off[2 * l + a]); slot2.push_back(2 * l + a);
-      }
-    }
-    if (!js2.empty()) {
-      if ((rc = collect_ab())) return rc;  // (the second device-resolved batch holds buffer set 1)
-      ns2.resize(js2.size()); pu2.resize(js2.size());
-      // next to the batch of the device-genotyped loci, if there is one: the call's second stream and the second set of side streams
-      // (the two batches are independent; queued on the same streams the second one waited for the first -- config 3: 65 -> 5x ms per call)
-      struct StreamSwap { trgt_hip_ctx* c; hipStream_t saved; ~StreamSwap() { c->stream = saved; } } hmm2_stream{c, c->stream};
-      if (hmm_pending) c->stream = c->stream2;
-      rc = hmm_enqueue(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, (int64_t)js2.size(), js2.data(),
-                       out->allele_blob, so2.data(), sl2.data(), nullptr, nullptr, nullptr, out->spans3, spo2.data(), ns2.data(),
-                       out->motif_counts, co2.data(), pu2.data(), nullptr, nullptr, &hmm_pending2, hmm_pending ? 1 : 0);
-      if (rc) return rc;
-      stat_hmm_jobs += (int64_t)js2.size();
-    }
-    tC += now_ns() - tc0;
+int LocusCall::host_front() {
+  if (nR == 0) return TRGT_OK;
+  int rc;
+  th0 = now_ns();
+  if (n_seg > 0 && reads_on_device) { for (uint64_t s = 0; s < n_seg; ++s) seg_ptr[s] = (const uint8_t*)h_seg + seg_dst[s]; }
+  else { for (uint64_t s = 0; s < n_seg; ++s) seg_ptr[s] = in->read_blob + seg_src[s]; }
+  // front half of the length genotyper, threaded over loci (per-thread scratch, no per-locus allocation)
+  int64_t tf0 = now_ns();
+  for (int64_t li = 0; li < nR; ++li) {
+    LocusWork& w = work[(size_t)li];
+    if (w.seg_begin == w.seg_end || !is_cluster(R[(size_t)li])) continue;
+    w.cluster = (int)cl_loci.size();
+    ClusterLocus L; L.li = li; L.ploidy = in->ploidy[R[(size_t)li]] == 1 ? 1 : 2; L.n = (int)(w.seg_end - w.seg_begin);
+    cl_loci.push_back(std::move(L));
+    cl_trs.emplace_back();
+    for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) cl_trs.back().push_back(Seg{seg_ptr[s], seg_len[s]});
   }
+  for (size_t k = 0; k < cl_loci.size(); ++k) cl_loci[k].trs = cl_trs[k].data();
+  pool->parallel_for(nR, 16, [&](int64_t li, int t) {
+    LocusWork& w = work[(size_t)li];
+    if (w.seg_begin == w.seg_end || w.cluster >= 0) return;
+    Scratch& sc = scratch[(size_t)t];
+    sc.trs.clear();
+    for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) sc.trs.push_back(Seg{seg_ptr[s], seg_len[s]});
+    genotype_size_front(in->ploidy[R[(size_t)li]] == 1 ? 1 : 2, li, t, w, sc);
+  });
+  c->dbg_ns[DN_FRONT] = now_ns() - tf0;
+  tl("front");
+  tHost += now_ns() - th0;
+  // ---- stage B: consensus alignments (BiWFA, affine 2,5,1, default heuristic) for the loci that need them
+  host_streams.emplace(c);  // (put back when the host path is through: host_stage_c, or the destructor)
+  std::swap(c->stream, c->stream2);
+  int64_t tb0 = now_ns();
+  struct JobRef { Repair* rep; int member; };
+  std::vector<JobRef> jrefs;
+  std::vector<uint8_t> cblob; std::vector<uint64_t> poff, toff; std::vector<uint32_t> plen, tlen;
+  for (auto& sc : scratch)
+    for (auto& rep : sc.repairs) {
+      const Seg bb = work[(size_t)rep.locus].pick[rep.allele];
+      const uint64_t bo = cblob.size();
+      cblob.insert(cblob.end(), bb.p, bb.p + bb.n);
+      for (size_t m = 0; m < rep.members.size(); ++m) {
+        const Seg& sg = rep.members[m];
+        poff.push_back(bo); plen.push_back(bb.n);
+        toff.push_back(cblob.size()); tlen.push_back(sg.n);
+        cblob.insert(cblob.end(), sg.p, sg.p + sg.n);
+        jrefs.push_back({&rep, (int)m});
+      }
+    }
+  std::vector<size_t> rep_first{0};  // jobs of one repair are contiguous
+  std::vector<Repair*> rep_of;
+  for (size_t j = 0; j < jrefs.size(); ++j)
+    if (jrefs[j].member == 0) { if (j) rep_first.push_back(j); rep_of.push_back(jrefs[j].rep); }
+  if (!jrefs.empty()) rep_first.push_back(jrefs.size());
+  if (jrefs.empty() && ((rc = hmm1_once()) || (!published && (rc = publish())))) return rc;
+  if (!jrefs.empty()) {
+    const std::function<int()> overlap = [this]() -> int {  // next to the alignment kernel: start the HMM batch, publish results
+      const int r = hmm1_once();
+      return r ? r : publish();
+    };
+    std::vector<std::string> repaired;
+    rc = consensus_repair_batch(c, (int64_t)jrefs.size(), cblob.data(), poff.data(), plen.data(), toff.data(), tlen.data(), rep_first, repaired, &overlap);
+    if (rc) return rc;
+    for (size_t g = 0; g < rep_of.size(); ++g) rep_of[g]->result.swap(repaired[g]);
+    stat_cons_jobs += (int64_t)jrefs.size();
+  }
+  // ---- Genotyper::Cluster loci: distance matrix, Ward linkage, consensus rounds, outlier assignment (locus_cluster.hpp)
+  if (!cl_loci.empty()) {
+    ClusterBatch cb(c, pool, cl_loci);
+    if ((rc = cb.run())) return rc;
+    stat_cons_jobs += cb.n_cons;
+    stat_ed_jobs += cb.n_ed;
+  }
+  tB = now_ns() - tb0;
+  tl("stageB");
+  return TRGT_OK;
+}
+  // ---- genotype_flank::genotype (genotype_flank.rs:9-42) for the loci whose two alleles are at most 10 bases apart (tr.rs:69-75)
+int LocusCall::host_flank() {
+  if (nR == 0) return TRGT_OK;
+  int rc;
+  th0 = now_ns();
+  fres.resize((size_t)(flank_on ? nR : 0));
+  if (!flank_on) return TRGT_OK;
+  struct FlankRepair { int64_t li; int a; Seg backbone; std::vector<Seg> members; };
+  std::vector<std::vector<FlankRepair>> freps((size_t)pool->size());
+  pool->parallel_for(nR, 16, [&](int64_t li, int t) {
+    LocusWork& w = work[(size_t)li];
+    if (w.seg_begin == w.seg_end) return;
+    int n_gt; uint32_t s0, s1;  // Gt sizes: the length genotyper's sizes, the cluster genotyper's allele lengths
+    if (w.cluster >= 0) { const ClusterLocus& L = cl_loci[(size_t)w.cluster]; n_gt = L.n_gt; s0 = (uint32_t)L.allele[0].size(); s1 = (uint32_t)L.allele[1].size(); }
+    else { n_gt = w.n_gt; s0 = w.size[0]; s1 = w.size[1]; }
+    if (n_gt != 2 || adiff(s0, s1) > 10) return;
+    std::vector<uint32_t> rd;
+    for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) rd.push_back(seg_read[s]);
+    FlankSplit sp;
+    if (!flank_split(flank_meta, rd.data(), rd.size(), sp)) return;
+    FlankRes fr;
+    for (int g = 0; g < 2; ++g) {
+      std::vector<Seg> seqs;
+      uint32_t lo = 0xFFFFFFFFu, hi = 0;
+      for (uint32_t i : sp.group[g]) { const uint64_t s = w.seg_begin + i; seqs.push_back(Seg{seg_ptr[s], seg_len[s]}); lo = std::min(lo, seg_len[s]); hi = std::max(hi, seg_len[s]); }
+      Seg best; double freq;
+      if (!flank_simple_consensus(seqs, best, freq)) return;  // an empty group: None
+      fr.al[g] = best; fr.ci[2 * g] = lo; fr.ci[2 * g + 1] = hi;
+      if (freq < 0.5) { fr.rep_group[g] = (int)freps[(size_t)t].size(); freps[(size_t)t].push_back(FlankRepair{li, g, best, std::move(seqs)}); }
+    }
+    fr.on = true; fr.assignment = std::move(sp.assignment);
+    fres[(size_t)li] = std::move(fr);
+  });
+  // groups without a majority sequence: align(backbone, members) + repair_consensus, one more batch on the device
+  std::vector<uint8_t> fb; std::vector<uint64_t> fpo, fto; std::vector<uint32_t> fpl, ftl; std::vector<size_t> ffirst{0};
+  std::vector<std::pair<int64_t, int>> fwho;
+  for (auto& v : freps)
+    for (auto& q : v) {
+      const uint64_t bo = fb.size();
+      fb.insert(fb.end(), q.backbone.p, q.backbone.p + q.backbone.n);
+      for (auto& m : q.members) { fpo.push_back(bo); fpl.push_back(q.backbone.n); fto.push_back(fb.size()); ftl.push_back(m.n); fb.insert(fb.end(), m.p, m.p + m.n); }
+      ffirst.push_back(fpo.size()); fwho.push_back({q.li, q.a});
+    }
+  if (!fwho.empty()) {
+    std::vector<std::string> repaired;
+    if ((rc = consensus_repair_batch(c, (int64_t)fpo.size(), fb.data(), fpo.data(), fpl.data(), fto.data(), ftl.data(), ffirst, repaired))) return rc;
+    stat_cons_jobs += (int64_t)fpo.size();
+    for (size_t g = 0; g < fwho.size(); ++g) {
+      FlankRes& fr = fres[(size_t)fwho[g].first];
+      fr.repaired[fwho[g].second].swap(repaired[g]);
+    }
+  }
+  for (auto& fr : fres) {
+    if (!fr.on) continue;
+    for (int g = 0; g < 2; ++g) if (fr.rep_group[g] >= 0) fr.al[g] = Seg{(const uint8_t*)fr.repaired[g].data(), (uint32_t)fr.repaired[g].size()};
+    if (fr.al[0].n > fr.al[1].n) {  // smaller allele first (:33-38)
+      std::swap(fr.al[0], fr.al[1]); std::swap(fr.ci[0], fr.ci[2]); std::swap(fr.ci[1], fr.ci[3]);
+      for (auto& a : fr.assignment) a = (int8_t)((a + 1) % 2);
+    }
+  }
+  return TRGT_OK;
+}
+  // ---- host: repair_consensus, classification, reference allele first, output assembly
+int LocusCall::host_back() {
+  if (nR == 0) return TRGT_OK;
+  std::vector<int8_t> seg_cls((size_t)n_seg, 0);
+  std::atomic<int> bad{0};
+  pool->parallel_for(nR, 64, [&](int64_t li, int) {
+    const int64_t l = R[(size_t)li];
+    LocusWork& w = work[(size_t)li];
+    if (w.seg_begin == w.seg_end) return;
+    const int ploidy = in->ploidy[l] == 1 ? 1 : 2;
+    Seg al[2];
+    int by_hap[2] = {0, 0};
+    if (w.cluster >= 0) {  // genotype_cluster::genotype results
+      const ClusterLocus& L = cl_loci[(size_t)w.cluster];
+      w.n_gt = L.n_gt;
+      for (int a = 0; a < L.n_gt; ++a) { al[a] = Seg{(const uint8_t*)L.allele[a].data(), (uint32_t)L.allele[a].size()}; w.ci[2 * a] = L.ci[2 * a]; w.ci[2 * a + 1] = L.ci[2 * a + 1]; }
+      for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) { const int cc = L.cls[(size_t)(s - w.seg_begin)]; seg_cls[s] = (int8_t)cc; by_hap[cc] += 1; }
+    } else {
+      for (int a = 0; a < w.n_pick; ++a) {
+        if (w.repair[a] >= 0) { const std::string& r = scratch[(size_t)w.repair_thread].repairs[(size_t)w.repair[a]].result; al[a] = Seg{(const uint8_t*)r.data(), (uint32_t)r.size()}; }
+        else al[a] = w.pick[a];
+      }
+      int n_al = w.n_pick;
+      if (ploidy == 2 && n_al == 1) { al[1] = al[0]; n_al = 2; }
+      int tie = 1;
+      for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) {
+        int cc = 0;
+        if (n_al == 2) {
+          const uint32_t d1 = adiff(seg_len[s], al[0].n), d2 = adiff(seg_len[s], al[1].n);
+          if (d1 < d2) cc = 0; else if (d1 > d2) cc = 1; else { tie = (tie + 1) % 2; cc = tie; }
+        }
+        seg_cls[s] = (int8_t)cc; by_hap[cc] += 1;
+      }
+    }
+    // TrSize::size of the genotype: the length genotyper's sizes; the cluster genotyper's and the flank genotype's are allele lengths
+    uint32_t gsz[2] = {w.cluster >= 0 ? al[0].n : w.size[0], w.cluster >= 0 ? (w.n_gt > 1 ? al[1].n : 0u) : w.size[1]};
+    if (flank_on && fres[(size_t)li].on) {  // the flank genotype replaces alleles, intervals and the read assignment
+      const FlankRes& fr = fres[(size_t)li];
+      w.n_gt = 2; al[0] = fr.al[0]; al[1] = fr.al[1]; gsz[0] = al[0].n; gsz[1] = al[1].n;
+      for (int k = 0; k < 4; ++k) w.ci[k] = fr.ci[k];
+      by_hap[0] = by_hap[1] = 0;
+      for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) { const int cc = fr.assignment[(size_t)(s - w.seg_begin)]; seg_cls[s] = (int8_t)cc; by_hap[cc] += 1; }
+    }
+    int order[2] = {0, 1};
+    const Seg ref{in->tr_blob + in->tr_off[l], in->tr_len[l]};
+    bool flip = false;
+    if (w.n_gt != 1 && !eq_seg(al[0], ref) && eq_seg(al[1], ref)) { order[0] = 1; order[1] = 0; flip = true; }  // tr.rs:95-101
+    out->n_alleles[l] = w.n_gt;
+    for (int oi = 0; oi < w.n_gt; ++oi) {
+      const int a = order[oi];
+      if (al[a].n > out->allele_cap[l]) { bad = 1; return; }
+      std::memcpy(out->allele_blob + out->allele_off[2 * l + oi], al[a].p, al[a].n);
+      out->allele_len[2 * l + oi] = al[a].n;
+      out->ci[4 * l + 2 * oi] = (int32_t)w.ci[2 * a]; out->ci[4 * l + 2 * oi + 1] = (int32_t)w.ci[2 * a + 1];
+      out->num_spanning[2 * l + oi] = by_hap[a];
+      if (out->gt_size) out->gt_size[2 * l + oi] = (int32_t)gsz[a];
+    }
+    if (out->flipped) out->flipped[l] = flip ? 1 : 0;
+    for (uint64_t r = in->locus_read_begin[l]; r < in->locus_read_begin[l + 1]; ++r) { out->classification[r] = -1; out->read_rank[r] = -1; }
+    for (uint64_t s = w.seg_begin; s < w.seg_end; ++s) {
+      out->classification[seg_read[s]] = flip ? 1 - seg_cls[s] : seg_cls[s];
+      out->read_rank[seg_read[s]] = (int32_t)(s - w.seg_begin);
+    }
+  });
+  if (bad) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: allele_cap too small");
+  c->dbg_ns[DN_BACK] = now_ns() - th0;
+  tl("back");
+  tHost += now_ns() - th0;
+  return TRGT_OK;
+}
+  // ---- stage C for the host-path loci (label_with_hmm for every allele): enqueued here, on the second stream and the second set
+  // of HMM buffers, next to the batch of the device-genotyped loci that is still running
+int LocusCall::host_stage_c() {
+  if (nR == 0) return TRGT_OK;
+  int rc;
+  const int64_t tc0 = now_ns();
+  for (int64_t li = 0; li < nR; ++li) {
+    const int64_t l = R[(size_t)li];
+    for (int a = 0; a < out->n_alleles[l]; ++a) {
+      js2.push_back((uint32_t)l); so2.push_back(out->allele_off[2 * l + a]); sl2.push_back(out->allele_len[2 * l + a]);
+      spo2.push_back(out->span_off[2 * l + a]); co2.push_back(out->count_off[2 * l + a]); slot2.push_back(2 * l + a);
+    }
+  }
+  if (!js2.empty()) {
+    if ((rc = collect_ab())) return rc;  // (the second device-resolved batch holds buffer set 1)
+    ns2.resize(js2.size()); pu2.resize(js2.size());
+    // next to the batch of the device-genotyped loci, if there is one: the call's second stream and the second set of side streams
+    // (the two batches are independent; queued on the same streams the second one waited for the first -- config 3: 65 -> 5x ms per call)
+    StreamGuard keep(c);
+    if (hmm_pending) c->stream = c->stream2;
+    rc = hmm_enqueue(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, (int64_t)js2.size(), js2.data(),
+                     out->allele_blob, so2.data(), sl2.data(), nullptr, nullptr, nullptr, out->spans3, spo2.data(), ns2.data(),
+                     out->motif_counts, co2.data(), pu2.data(), nullptr, nullptr, &hmm_pending2, hmm_pending ? 1 : 0);
+    if (rc) return rc;
+    stat_hmm_jobs += (int64_t)js2.size();
+  }
+  tC += now_ns() - tc0;
+  host_streams.reset();
+  return TRGT_OK;
+}
+int LocusCall::collect_all() {
+  int rc;
   if ((rc = hmm1_once())) return rc;
   if (!published && (rc = publish())) return rc;
   // ---------------- stage C results of the device-genotyped loci
-  TL("hmm2 enqueued");
+  tl("hmm2 enqueued");
   if ((rc = collect_ab())) return rc;
   if ((rc = collect_hmm1())) return rc;
   if (hmm_pending2) {
@@ -1771,22 +1878,58 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
     for (size_t j = 0; j < slot2.size(); ++j) { out->n_spans[slot2[j]] = ns2[j]; out->purity[slot2[j]] = pu2[j]; }
     tC += now_ns() - tc0;
   }
-  TL("all collected");
-  if (c->timing) { resolve_timing(c); TL("timing events resolved"); }  // (all of the call's events have fired: reading them now keeps the list short)
-  if (out->stats) {
-    int64_t* s = out->stats;
-    s[0] = stat_flank_jobs; s[1] = stat_cons_jobs; s[2] = stat_spanning; s[3] = stat_hmm_jobs;
-    s[4] = tA; s[5] = tB; s[6] = tC; s[7] = tHost; s[8] = now_ns() - t0;
-    for (int i = 0; i < 5; ++i) s[9 + i] = c->dbg_ns[i + (i >= 3 ? 1 : 0)];
-    s[14] = stat_flank_heavy; s[15] = stat_ed_jobs;
-    s[16] = (int64_t)((uint64_t*)h_cells)[5]; s[17] = (int64_t)((uint64_t*)h_cells)[4];  // pre-filter: alignments kept, offsets computed
-    for (int i = 18; i < 24; ++i) s[i] = 0;
-    s[21] = (int64_t)((uint64_t*)h_cells)[2];  // light fallback alignments settled by the substitution shortcut of the window search
-    if (dev_gt) { const uint32_t* rc_ = (const uint32_t*)hsl(o_rpc); s[18] = rc_[gt::RC_LOCI]; s[19] = rc_[gt::RC_FAILED]; s[20] = rc_[gt::RC_JOBS];  // device-side consensus repair: loci, loci without room, alignments
-      const uint32_t* cc = (const uint32_t*)hsl(o_clc); const uint32_t* cd = (const uint32_t*)hsl(o_cldc);
-      s[22] = (int64_t)cc[cl::CC_DONE] + cd[cl::CC_DONE]; s[23] = (int64_t)cc[cl::CC_FAILED] + cd[cl::CC_FAILED] + cld_no_room; }  // device-side cluster genotyper: loci genotyped, loci handed to the host path
-  }
+  tl("all collected");
+  if (c->timing) { resolve_timing(c); tl("timing events resolved"); }  // (all of the call's events have fired: reading them now keeps the list short)
+  if (!out->stats) return TRGT_OK;
+  int64_t* s = out->stats;
+  s[0] = stat_flank_jobs; s[1] = stat_cons_jobs; s[2] = stat_spanning; s[3] = stat_hmm_jobs;
+  s[4] = tA; s[5] = tB; s[6] = tC; s[7] = tHost; s[8] = now_ns() - t0;
+  const int dn[5] = {DN_SETUP, DN_TABLES, DN_STAGE_A, DN_SELECT, DN_SPARE};
+  for (int i = 0; i < 5; ++i) s[9 + i] = c->dbg_ns[dn[i]];
+  s[14] = stat_flank_heavy; s[15] = stat_ed_jobs;
+  s[16] = (int64_t)cell(HC_FILTER_KEPT); s[17] = (int64_t)cell(HC_FILTER_OFFSETS);  // pre-filter: alignments kept, offsets computed
+  for (int i = 18; i < 24; ++i) s[i] = 0;
+  s[21] = (int64_t)cell(HC_LIGHT_SHORTCUT);  // light fallback alignments settled by the substitution shortcut of the window search
+  if (dev_gt) { const uint32_t* rc_ = (const uint32_t*)slab.h(o_rpc); s[18] = rc_[gt::RC_LOCI]; s[19] = rc_[gt::RC_FAILED]; s[20] = rc_[gt::RC_JOBS];  // device-side consensus repair: loci, loci without room, alignments
+    const uint32_t* cc = (const uint32_t*)slab.h(o_clc); const uint32_t* cd = (const uint32_t*)slab.h(o_cldc);
+    s[22] = (int64_t)cc[cl::CC_DONE] + cd[cl::CC_DONE]; s[23] = (int64_t)cc[cl::CC_FAILED] + cd[cl::CC_FAILED] + cld_no_room; }  // device-side cluster genotyper: loci genotyped, loci handed to the host path
   return TRGT_OK;
+}
+
+}  // namespace
+// staged_reads / staged_flank: device copies of in->read_blob / in->flank_blob made ahead of time by trgt_locus_batch_submit (the
+// caller's pointers stay what the host glue reads); `ready`: the event behind those copies.
+static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const trgt_locus_batch_in* in, trgt_locus_batch_out* out,
+                           const uint8_t* staged_reads, const uint8_t* staged_flank, hipEvent_t ready) {
+  if (!c) return TRGT_ERR_INVALID;
+  if (!p || !in || !out) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: null argument");
+  LocusCall k(c, p, in, out, staged_reads, staged_flank, ready);
+  int rc;
+  if ((rc = k.check_args()) || k.done) return rc;
+  if ((rc = k.host_tables()) || k.done) return rc;
+  // ---- stage A and, with the reads in HBM, the device genotyper chains: enqueued without a host wait (the purity filter has one)
+  if ((rc = k.upload_tables())) return rc;
+  if ((rc = k.plan_device_lists())) return rc;
+  if ((rc = k.flush_uploads())) return rc;
+  if ((rc = k.locate_flanks())) return rc;
+  if ((rc = k.repair_buffers())) return rc;
+  if ((rc = k.purity_chain())) return rc;
+  if ((rc = k.size_genotyper())) return rc;
+  if ((rc = k.repair_chain())) return rc;
+  if ((rc = k.cluster_chain(0))) return rc;
+  if ((rc = k.cluster_chain(1))) return rc;
+  if ((rc = k.enqueue_results())) return rc;
+  // ---- the GPU's results; the loci the host path takes
+  if ((rc = k.wait_stage_a())) return rc;
+  k.stage_c_job_lists();
+  k.select_host_reads();
+  if ((rc = k.gather_host_segments())) return rc;
+  // ---- host genotyper of the loci in R (hmm1_once and publish run inside stage B's alignment batch when there is one)
+  if ((rc = k.host_front())) return rc;
+  if ((rc = k.host_flank())) return rc;
+  if ((rc = k.host_back())) return rc;
+  if ((rc = k.host_stage_c())) return rc;
+  return k.collect_all();
 }
 
 // ---- C ABI: exceptions never cross it (std::bad_alloc from the host-side vectors becomes TRGT_ERR_NOMEM) ----
