@@ -41,7 +41,8 @@ enum SpanCount : int {
   SC_LBAND = 13,    // long reads (SC_LONG) whose windows named the penalty and the end diagonal: back-traced inside a band
   SC_LREST = 14,    // ... the other long reads the window filter keeps: back-traced over the whole read
   SC_LNOSEED = 15,  // long reads' alignments the seed search could neither settle nor window (or whose window did not stand): the window filter's list
-  SC_WORDS = 16
+  SC_SIBDROP = 16,  // missed pieces the scan did not turn into a job: the exactly found sibling leaves them fewer than min_matches bases (ScanArgs::min_matches)
+  SC_WORDS = 17
 };
 
 struct ScanArgs {
@@ -60,6 +61,15 @@ struct ScanArgs {
   const uint32_t* heavy_len; uint32_t jobs_cap;
   JobDev* wfa_jobs_long; uint32_t long_tlen;  // reads longer than long_tlen go to a second list (wfa_count[1]): they would not fit the
                                               // LDS budget of the dedicated kernel and must not drag the whole batch onto the generic one
+  // > 0: the sibling rule of flank_scan_wide_kernel.  The reference combines the two flank hits of a read as (lf.end, rf.start) and
+  // returns None when either is missing or lf.end > rf.start (span_locater.rs:52-66); nothing else of a flank alignment leaves
+  // find_tr_spans.  With one piece found exactly and the other missed, the missed piece's alignment therefore counts only if its text
+  // span lies on the far side of the sibling: inside [p0 + F, n) for a missed right piece (left found at p0), inside [0, p1) for a
+  // missed left piece (right found at p1).  count_matches() cannot exceed the text span, so where that region holds fewer than
+  // min_matches = ceil(flank_len * min_flank_id_frac) bases the read's span is None whatever the alignment is -- below the threshold
+  // (:18-22) if it stays inside the region, discordant if it leaves it -- and no job is emitted.  The hit byte of such a piece reads 0
+  // where the alignment might have made it 2: callers that hand the bytes out keep the rule off (find_spans_device, span_only).
+  int32_t min_matches;
 };
 
 __device__ __forceinline__ uint32_t load_u32(const uint8_t* p) {
@@ -408,8 +418,8 @@ __global__ void __launch_bounds__(256) flank_window_kernel(const WindowArgs a) {
 constexpr int SCAN_READS_PER_WG = 64;
 __global__ void __launch_bounds__(256) flank_scan_wide_kernel(const ScanArgs a) {
   __shared__ JobDev l_jobs[2 * SCAN_READS_PER_WG];  // expensive jobs fill it from the front, the others from the back
-  __shared__ uint32_t l_n, l_n2, l_base, l_base2;
-  if (threadIdx.x == 0) { l_n = 0; l_n2 = 0; }
+  __shared__ uint32_t l_n, l_n2, l_base, l_base2, l_drop;
+  if (threadIdx.x == 0) { l_n = 0; l_n2 = 0; l_drop = 0; }
   __syncthreads();
   const int lane = threadIdx.x & 63;
   const uint64_t n_reads = a.n_jobs >> 1;
@@ -510,7 +520,10 @@ __global__ void __launch_bounds__(256) flank_scan_wide_kernel(const ScanArgs a) 
     for (int side = 0; side < 2; ++side) {
       const uint64_t j = 2 * r + side;
       a.pos[j] = found[side]; a.n_match[j] = -1;
-      if (found[side] < 0) {  // fall back to the wavefront aligner (span_locater.rs:13-26)
+      // (ScanArgs::min_matches) what the exactly found sibling leaves this piece: the read behind the left piece, or in front of the right one
+      const int room = found[side ^ 1] < 0 ? 0x7FFFFFFF : side ? n - found[0] - F : found[1];
+      if (found[side] < 0 && room < a.min_matches) atomicAdd(&l_drop, 1u);
+      else if (found[side] < 0) {  // fall back to the wavefront aligner (span_locater.rs:13-26)
         JobDev jd;
         jd.pat_off = side ? po1 : po0; jd.txt_off = r_off;
         jd.cigar_off = 0; jd.ops_off = 0; jd.pat_len = (uint32_t)F; jd.txt_len = (uint32_t)n; jd.out_index = (uint32_t)j; jd.pad = 0;
@@ -524,6 +537,7 @@ __global__ void __launch_bounds__(256) flank_scan_wide_kernel(const ScanArgs a) 
   __syncthreads();
   if (threadIdx.x == 0 && l_n) l_base = atomicAdd(a.wfa_count + SC_HEAVY, l_n);
   if (threadIdx.x == 64 && l_n2) l_base2 = atomicAdd(a.wfa_count + SC_LIGHT, l_n2);
+  if (threadIdx.x == 128 && l_drop) atomicAdd(a.wfa_count + SC_SIBDROP, l_drop);
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < l_n; i += blockDim.x) a.wfa_jobs[l_base + i] = l_jobs[i];
   for (uint32_t i = threadIdx.x; i < l_n2; i += blockDim.x) a.wfa_jobs[a.jobs_cap - 1u - (l_base2 + i)] = l_jobs[2 * SCAN_READS_PER_WG - 1 - i];
@@ -708,7 +722,7 @@ __global__ void long_kept_kernel(const LongWinArgs a) {
 int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci, int64_t n_reads, const uint8_t* d_flank,
                       const uint64_t* d_piece_off, const uint8_t* d_reads, const uint64_t* d_read_off, const uint32_t* d_read_len,
                       const uint32_t* d_read_locus, uint32_t max_read_len, int32_t* d_span_start, int32_t* d_span_end,
-                      uint8_t* d_lf_hit, uint8_t* d_rf_hit, const uint32_t* d_heavy_len, uint32_t heavy_tlen_max) {
+                      uint8_t* d_lf_hit, uint8_t* d_rf_hit, const uint32_t* d_heavy_len, uint32_t heavy_tlen_max, bool span_only) {
   const uint64_t n_jobs = 2ull * (uint64_t)n_reads;
   void *d_pos = nullptr, *d_wjobs = nullptr, *d_count = nullptr, *d_span4 = nullptr, *d_nmatch = nullptr;
   int rc;
@@ -721,6 +735,13 @@ int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci
   sa.read_locus = d_read_locus; sa.n_jobs = n_jobs; sa.flank_len = p.flank_len; sa.pos = (int32_t*)d_pos; sa.n_match = (int32_t*)d_nmatch;
   sa.wfa_jobs = (JobDev*)d_wjobs; sa.wfa_count = (uint32_t*)d_count;
   sa.heavy_len = d_heavy_len; sa.jobs_cap = (uint32_t)n_jobs;
+  // the smallest count_matches() that passes span_locater.rs:18-22
+  const double thr = (double)(uint64_t)p.flank_len * p.min_flank_id_frac;
+  int64_t min_matches = thr > 0 ? (int64_t)std::ceil(thr) : 0;
+  while (min_matches > 0 && (double)(min_matches - 1) >= thr) --min_matches;
+  while ((double)min_matches < thr) ++min_matches;
+  // (the one-wave-per-piece scan of pieces shorter than four bases does not know the sibling and keeps emitting every job)
+  sa.min_matches = span_only && !c->knobs.no_sibling_rule ? (int32_t)std::min<int64_t>(min_matches, 0x7FFFFFFF) : 0;
   // reads up to long_tlen keep the dedicated kernel at 4 workgroups per CU (LDS: ring + windows <= ~39 KB per alignment)
   const int ring_slots = std::max(p.mism, p.gapo + p.gape) + 1 + 2 * (p.gape + 1);
   const int64_t fit = 39000 / (2 * (int64_t)ring_slots + 4) - p.flank_len - 16;
@@ -816,10 +837,6 @@ int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci
     // count_matches() without history or back-trace; only those whose bound reaches the threshold (a quarter of the jobs, 5 % of
     // the wavefront offsets on the bench workload) are aligned again by the back-tracing kernel.  span_locater.rs:18-22 does
     // nothing with the others but drop them.
-    const double thr = (double)(uint64_t)p.flank_len * p.min_flank_id_frac;
-    int64_t min_matches = thr > 0 ? (int64_t)std::ceil(thr) : 0;
-    while (min_matches > 0 && (double)(min_matches - 1) >= thr) --min_matches;
-    while ((double)min_matches < thr) ++min_matches;
     // (texts beyond the filter's diagonals are kept unseen, job by job: a batch with a few long reads still filters the others)
     const int64_t flt_tlen = flank_filter_max_tlen(p.flank_len);
     const bool filter_pen = (p.mism == 2 && p.gapo == 5 && p.gape == 1) || (p.mism == 1 && p.gapo == 0 && p.gape == 1);  // wgs / targeted presets (cli.rs:271-280)
@@ -962,10 +979,6 @@ int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci
     L2.keep_cells = true; L2.timer_slot = TRGT_K_WFA_FLANK_REST;
     // the pre-filter over windows of the long reads (see LongWinArgs): what it rejects never reaches the exact kernel
     {
-      const double thr = (double)(uint64_t)p.flank_len * p.min_flank_id_frac;
-      int64_t min_matches = thr > 0 ? (int64_t)std::ceil(thr) : 0;
-      while (min_matches > 0 && (double)(min_matches - 1) >= thr) --min_matches;
-      while ((double)min_matches < thr) ++min_matches;
       const int64_t wl = flank_filter_max_tlen(p.flank_len);
       const int64_t span_max = 2 * (int64_t)p.flank_len + p.gapo + 8, step = wl - span_max;
       // It pays where the exact kernel is the generic one (wavefronts in HBM): texts beyond what the LDS kernel of wfa_launch takes
@@ -1044,15 +1057,16 @@ int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci
   hipLaunchKernelGGL(span_combine_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, c->stream, ca);
   TRGT_HIP_TRY(c, hipGetLastError());
   if (c->knobs.debug) {  // (synchronises: developer output only)
-    uint32_t h[16];
+    uint32_t h[SC_WORDS];
     TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
-    TRGT_HIP_TRY(c, hipMemcpy(h, d_count, 64, hipMemcpyDeviceToHost));
+    TRGT_HIP_TRY(c, hipMemcpy(h, d_count, 4 * SC_WORDS, hipMemcpyDeviceToHost));
     if (win_q > 0)
       fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u -> windowed %u, whole read %u (that is %u without seeds + %u windows that did not stand), settled by the shortcuts %u (one-base gaps: %u)\n",
               h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT], h[SC_WIN], h[SC_REST], h[SC_LIGHT] - h[SC_WIN] - h[SC_SHORTCUT], h[SC_REST] - (h[SC_LIGHT] - h[SC_WIN] - h[SC_SHORTCUT]), h[SC_SHORTCUT], h[SC_GAPS]);
     if (win_q <= 0) fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u (no seeded windows for this configuration)\n", h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT]);
     if (win_q > 0 && heavy_window) fprintf(stderr, "[spans+] (the seed search ran over the first launch's list too: %u of its %u alignments had no seeds and met the pre-filter; the counts of the windowed list and of the shortcut include the others)\n", h[SC_NOSEED], h[SC_HEAVY]);
     if (has_long) fprintf(stderr, "[spans+] long reads kept by the window filter: back-traced inside a band %u, over the whole read %u\n", h[SC_LBAND], h[SC_LREST]);
+    fprintf(stderr, "[spans+] sibling rule %s: %u missed pieces without a job (fewer than %d bases beside the exactly found sibling)\n", sa.min_matches > 0 ? "on" : "off", h[SC_SIBDROP], sa.min_matches);
     if (heavy_band) fprintf(stderr, "[spans+] kept by the pre-filter: %u -> back-traced inside a band %u (did not stand: %u), over the whole read %u\n", h[SC_KEEP], h[SC_BAND], h[SC_BANDFAIL], h[SC_HREST]);
   }
   (void)n_loci;
@@ -1114,7 +1128,7 @@ extern "C" int trgt_find_spans_batch(trgt_hip_ctx* c, const trgt_span_params* p,
       (rc = o_l.init(c, S_FS_HIT0, lf_hit, (size_t)n_reads)) || (rc = o_r.init(c, S_FS_HIT1, rf_hit, (size_t)n_reads)))
     return rc;
   if ((rc = find_spans_device(c, *p, n_loci, n_reads, d_flank, d_piece, d_reads, d_roff, d_rlen, d_rloc, max_read_len, o_s.dev,
-                              o_e.dev, o_l.dev, o_r.dev, d_heavy, heavy_tlen_max > 0 ? heavy_tlen_max - 1 : 0)))
+                              o_e.dev, o_l.dev, o_r.dev, d_heavy, heavy_tlen_max > 0 ? heavy_tlen_max - 1 : 0, !lf_hit && !rf_hit)))
     return rc;
   if ((rc = o_s.finish(c)) || (rc = o_e.finish(c)) || (rc = o_l.finish(c)) || (rc = o_r.finish(c))) return rc;
   unsigned long long cells[2] = {0, 0}, fcells[2] = {0, 0};  // total, first launch; pre-filter: offsets, alignments kept
