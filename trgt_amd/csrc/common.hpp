@@ -37,6 +37,7 @@ struct trgt_knobs {
   int band_threads = 64;     // TRGT_BAND_THREADS: ... of the banded back-trace of what the pre-filter keeps (64, 128 or 256)
   int win_threads = 64;      // TRGT_WIN_THREADS: ... of the windowed launch
   int win_segments = 8;      // TRGT_WIN_SEGMENTS: 4 / 6 / 8 segments for the window search
+  bool win_lds = false;      // TRGT_WIN_LDS (DEV): the windowed launch by the LDS kernel (wfa_fast_kernel<64, 2>) instead of the one-wave register kernel (wfa_win.hip)
   int grid_per_cu = 0;       // TRGT_WFA_GRID_PER_CU: persistent workgroups per CU of the dedicated kernel (0: occupancy query)
   int filter_per_cu = 0;     // TRGT_FILTER_PER_CU: persistent waves per CU of the pre-filter (0: occupancy query)
   bool one_launch = false;   // TRGT_WFA_ONE_LAUNCH: all flank alignments in one launch

@@ -23,7 +23,7 @@
 
 namespace trgt {
 
-// The counter block of a find_spans call (16 words in HBM, cleared in front of the scan): list lengths and tallies shared by its kernels.
+// The counter block of a find_spans call (SC_WORDS words in HBM, cleared in front of the scan): list lengths and tallies shared by its kernels.
 enum SpanCount : int {
   SC_HEAVY = 0,     // expensive fallback alignments: the front of the two-ended job list
   SC_LONG = 1,      // reads beyond the dedicated kernels' texts (second list)
@@ -42,7 +42,9 @@ enum SpanCount : int {
   SC_LREST = 14,    // ... the other long reads the window filter keeps: back-traced over the whole read
   SC_LNOSEED = 15,  // long reads' alignments the seed search could neither settle nor window (or whose window did not stand): the window filter's list
   SC_SIBDROP = 16,  // missed pieces the scan did not turn into a job: the exactly found sibling leaves them fewer than min_matches bases (ScanArgs::min_matches)
-  SC_WORDS = 17
+  SC_WINCLAIM = 17, // job claims of the register kernel over the windowed list (wfa_win.hip)
+  SC_WINFALL = 18,  // windowed alignments that kernel did not take (sequences beyond its staging buffers): they go on to the whole-read launch
+  SC_WORDS = 19
 };
 
 struct ScanArgs {
@@ -808,6 +810,7 @@ int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci
   heavy_tlen_max = std::min(heavy_tlen_max, short_max);
   bool heavy_window = false;  // the seed search runs over the expensive list as well (below)
   bool heavy_band = false;    // ... and what the pre-filter keeps of it is back-traced inside a band (BandArgs)
+  bool win_reg = false;       // the windowed launch is the register kernel's (wfa_win.hip)
   auto window_args = [&]() {
     WindowArgs wa;
     wa.flank_blob = d_flank; wa.read_blob = d_reads; wa.wfa_jobs = (const JobDev*)d_wjobs; wa.jobs_cap = (uint32_t)n_jobs; wa.count = (uint32_t*)d_count;
@@ -956,9 +959,20 @@ int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci
       LW.threads = c->knobs.win_threads;
       trgt_wfa_params wpw = wp;
       wpw.text_begin_free = 2 * win_margin + win_spread;
-      if ((rc = wfa_launch(c, wpw, LW))) return rc;
+      // one wave per job with wavefronts and history in registers (wfa_win.hip) where its layout holds the launch; else, and under
+      // TRGT_WIN_LDS (developer build: A/B, tests), the LDS kernel.  The register kernel counts no wavefront offsets.
+      win_reg = !c->knobs.win_lds && !c->knobs.skip_bt && !c->knobs.no_spec && wfa_win_fits(p.mism, p.gapo, p.gape, wpw.text_begin_free, win_s0, p.flank_len, win_tlen);
+      if (win_reg) {
+        WfaWinLaunch WR;
+        WR.jobs_dev = LW.jobs_dev; WR.n_jobs_host = (int64_t)n_jobs; WR.n_jobs_dev = LW.n_jobs_dev; WR.pat_base = d_flank; WR.txt_base = d_reads;
+        WR.tbf = wpw.text_begin_free; WR.s_max = win_s0; WR.counter = (unsigned int*)d_count + SC_WINCLAIM; WR.fallback = (unsigned int*)d_count + SC_WINFALL;
+        WR.score = (int32_t*)d_score; WR.n_match = (int32_t*)d_nmatch; WR.span4 = (uint32_t*)d_span4; WR.timer_slot = LW.timer_slot;
+        if ((rc = wfa_win_launch(c, WR))) return rc;
+      } else {
+        if ((rc = wfa_launch(c, wpw, LW))) return rc;
+        L.keep_cells = true;
+      }
       tl_mark(c, "window launch");
-      L.keep_cells = true;
       WinCheckArgs wc;
       wc.win_jobs = (const JobDev*)d_winjobs; wc.n_win = (const uint32_t*)d_count + SC_WIN; wc.score = (const int32_t*)d_score;
       wc.span4 = (uint32_t*)d_span4; wc.n_match = (int32_t*)d_nmatch; wc.s0 = win_s0;
@@ -1064,6 +1078,7 @@ int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci
       fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u -> windowed %u, whole read %u (that is %u without seeds + %u windows that did not stand), settled by the shortcuts %u (one-base gaps: %u)\n",
               h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT], h[SC_WIN], h[SC_REST], h[SC_LIGHT] - h[SC_WIN] - h[SC_SHORTCUT], h[SC_REST] - (h[SC_LIGHT] - h[SC_WIN] - h[SC_SHORTCUT]), h[SC_SHORTCUT], h[SC_GAPS]);
     if (win_q <= 0) fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u (no seeded windows for this configuration)\n", h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT]);
+    if (win_q > 0) fprintf(stderr, "[spans+] windowed launch: %s, %u alignments it did not take\n", win_reg ? "one wave per alignment, history in registers" : "LDS kernel", h[SC_WINFALL]);
     if (win_q > 0 && heavy_window) fprintf(stderr, "[spans+] (the seed search ran over the first launch's list too: %u of its %u alignments had no seeds and met the pre-filter; the counts of the windowed list and of the shortcut include the others)\n", h[SC_NOSEED], h[SC_HEAVY]);
     if (has_long) fprintf(stderr, "[spans+] long reads kept by the window filter: back-traced inside a band %u, over the whole read %u\n", h[SC_LBAND], h[SC_LREST]);
     fprintf(stderr, "[spans+] sibling rule %s: %u missed pieces without a job (fewer than %d bases beside the exactly found sibling)\n", sa.min_matches > 0 ? "on" : "off", h[SC_SIBDROP], sa.min_matches);

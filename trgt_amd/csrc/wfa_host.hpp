@@ -47,6 +47,23 @@ struct WfaLaunch {  // everything device-resident
 // accumulated in device memory at ctx->last_wfa_cells_dev.
 int wfa_launch(trgt_hip_ctx* c, const trgt_wfa_params& p, const WfaLaunch& L);
 
+// The windowed flank alignments of trgt_find_spans_batch on one wave each, wavefronts and history in registers (wfa_win.hip): gap-affine
+// (2, 5, 1), pattern ends fixed, text free at both ends, started on the diagonals [0, tbf], given up above the penalty s_max.  Writes
+// score (-penalty, INT32_MIN when given up or not taken), n_match and span4 by JobDev::out_index, exactly as wfa_launch with
+// kernel_tag 2 and max_score = s_max does for the alignments that come out at s_max or below.
+struct WfaWinLaunch {
+  const JobDev* jobs_dev = nullptr; int64_t n_jobs_host = 0; const uint32_t* n_jobs_dev = nullptr;
+  const uint8_t* pat_base = nullptr; const uint8_t* txt_base = nullptr;
+  int tbf = 0, s_max = 0;
+  unsigned int* counter = nullptr;   // cleared device word: job claims
+  unsigned int* fallback = nullptr;  // device word that counts the jobs the kernel does not take (sequences beyond its staging buffers)
+  int32_t* score = nullptr; int32_t* n_match = nullptr; uint32_t* span4 = nullptr;
+  int timer_slot = TRGT_K_WFA_FLANK_REST;
+};
+// wfa_win_fits: can the kernel hold a launch with these parameters at all (else: wfa_launch)
+bool wfa_win_fits(int mism, int gapo, int gape, int tbf, int s_max, int64_t max_plen, int64_t max_tlen);
+int wfa_win_launch(trgt_hip_ctx* c, const WfaWinLaunch& L);
+
 // The register-resident BiWFA kernel for small end-to-end alignments (wfa_lean.hip), launched by wfa_launch in front of the generic
 // kernel: alignments it does not take are appended to retry_jobs / *retry_count (device memory) and redone there from scratch.
 int wfa_lean_launch(trgt_hip_ctx* c, const trgt_wfa_params& p, const WfaLaunch& L, JobDev* mid_jobs, JobDev* retry_jobs, unsigned int* retry_count, uint32_t retry_cap,
