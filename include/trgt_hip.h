@@ -100,6 +100,21 @@ int trgt_hip_set_cluster_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
 int32_t trgt_hip_size_max_reads_limit(void);
 int trgt_hip_set_size_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
 int trgt_hip_size_deep_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
+/* genotype_flank::genotype (genotype_flank.rs:9-290), which analyze applies to every diploid locus whose two sizes are at most 10 bases
+ * apart (tr.rs:69-75), first tries the split by haplotype tag (get_trs_with_hp, genotype_flank.rs:43-76).  By default the host does this
+ * step: a device-genotyped locus whose reads split is genotyped again from the start on the host path.  On a context set with on != 0,
+ * calls whose batch carries hp_tag run the tag branch inside the device genotyper: assignment by tag, acceptance (70 % tagged, both
+ * haplotypes), simple_consensus of either group, the call's consensus repair for a group without a majority sequence, smaller allele
+ * first.  What stays on the host: the SNV-clustering branch (get_trs_with_clustering, :78-138), tried for the loci whose tags do not
+ * split the reads exactly as before; Genotyper::Cluster loci; loci of more than 256 reads; contexts created under TRGT_HOST_GENOTYPER;
+ * and a locus on this route that finds no room in the repair chain, has a segment beyond its longest (every such locus under
+ * TRGT_HOST_REPAIR) or an allele beyond allele_cap.  Results are the same either way.  trgt_hip_flank_stats: of the context's last
+ * trgt_locus_batch -- out[0] loci whose genotype the device replaced by the tag split, out[1] those among them with at least one
+ * repaired group, out[2] device-genotyped loci sent to the host path for the flank step (the SNV branch splits them, or this route
+ * handed them back), out[3] reserved (0); all zero with the setting off or a batch without hp_tag.  The contexts of a pool are set and
+ * asked one by one through trgt_hip_pool_context. */
+int trgt_hip_set_flank_device(trgt_hip_ctx* ctx, int on);
+int trgt_hip_flank_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
 
 /* ---- kernel timing (HIP events on the ctx stream, for bench.py's roofline) ---- */
 #define TRGT_K_FLANK_SCAN 0   /* exact flank search (+ the segment search for the seeded windows of the fallback alignments) */

@@ -72,7 +72,7 @@ class LocusBatchOut(C.Structure):
 EXPORTS = [
     "trgt_inflate_raw", "trgt_inflate_blocks", "trgt_deflate_blocks",
     "trgt_hip_abi_version", "trgt_hip_create", "trgt_hip_destroy", "trgt_hip_last_error", "trgt_hip_set_stream",
-    "trgt_hip_set_workspace_limit", "trgt_hip_cluster_max_reads_limit", "trgt_hip_set_cluster_max_reads", "trgt_hip_size_max_reads_limit", "trgt_hip_set_size_max_reads", "trgt_hip_size_deep_stats", "trgt_hip_timing_enable", "trgt_hip_timing_reset", "trgt_hip_timing_get",
+    "trgt_hip_set_workspace_limit", "trgt_hip_cluster_max_reads_limit", "trgt_hip_set_cluster_max_reads", "trgt_hip_size_max_reads_limit", "trgt_hip_set_size_max_reads", "trgt_hip_size_deep_stats", "trgt_hip_set_flank_device", "trgt_hip_flank_stats", "trgt_hip_timing_enable", "trgt_hip_timing_reset", "trgt_hip_timing_get",
     "trgt_wfa_default_params", "trgt_wfa_batch", "trgt_flank_filter_batch", "trgt_find_spans_batch", "trgt_hmm_batch", "trgt_hmm_path_capacity", "trgt_hmm_models_check",
     "trgt_locus_batch", "trgt_locus_batch_submit", "trgt_locus_batch_wait", "trgt_locus_default_params", "trgt_reads_pack_bam4",
     "trgt_hip_pool_create", "trgt_hip_pool_destroy", "trgt_hip_pool_size", "trgt_hip_pool_context", "trgt_hip_pool_last_error", "trgt_locus_batch_many",
@@ -127,6 +127,8 @@ def lib():
         L.trgt_hip_size_max_reads_limit.restype = C.c_int32
         L.trgt_hip_set_size_max_reads.argtypes = [_VP, C.c_int32]
         L.trgt_hip_size_deep_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
+        L.trgt_hip_set_flank_device.argtypes = [_VP, C.c_int]
+        L.trgt_hip_flank_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_timing_enable.argtypes = [_VP, C.c_int]
         L.trgt_hip_timing_reset.argtypes = [_VP]
         L.trgt_hip_timing_get.argtypes = [_VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -193,6 +195,18 @@ class Context:
         self.check(lib().trgt_hip_size_deep_stats(self.handle, out))
         return tuple(int(v) for v in out)
 
+    def set_flank_device(self, on=True):
+        """trgt_hip_set_flank_device: the haplotype-tag branch of genotype_flank (genotype_flank.rs:43-76) runs inside the device genotyper for
+        batches that carry hp_tag (off, the default: on the host path).  Every later call on this context uses it."""
+        self.check(lib().trgt_hip_set_flank_device(self.handle, int(bool(on))))
+
+    def flank_stats(self):
+        """trgt_hip_flank_stats of the context's last trgt_locus_batch: (loci whose genotype the device replaced by the tag split, those
+        among them with a repaired group, device-genotyped loci sent to the host path for the flank step, 0)."""
+        out = (C.c_int64 * 4)()
+        self.check(lib().trgt_hip_flank_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def timing_enable(self, on=True):
         self.check(lib().trgt_hip_timing_enable(self.handle, int(on)))
 
@@ -219,7 +233,7 @@ class Context:
 class Pool:
     """trgt_hip_pool: several contexts (devices[i] = ordinal of context i, ordinals may repeat) behind one queue of batches."""
 
-    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None):
+    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None):
         L = lib()
         L.trgt_hip_pool_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
         L.trgt_hip_pool_destroy.argtypes = [C.c_void_p]
@@ -249,6 +263,9 @@ class Pool:
         if size_max_reads is not None:
             for c in self.contexts:
                 c.set_size_max_reads(size_max_reads)
+        if flank_device is not None:
+            for c in self.contexts:
+                c.set_flank_device(flank_device)
 
     def run_many(self, params_struct, cins, couts, out_per_context=False):
         """cins / couts: lists of LocusBatchIn / LocusBatchOut structures (couts: one per batch, or one per context)"""

@@ -109,6 +109,8 @@ struct trgt_hip_ctx {
   int32_t cluster_max_reads = 256;  // trgt_hip_set_cluster_max_reads: deepest Genotyper::Cluster locus the device chains take (256 = the one-wave chain only)
   int32_t size_max_reads = 256;     // trgt_hip_set_size_max_reads: deepest Genotyper::Size locus the device genotypers take (256 = the one-wave kernel only)
   int64_t size_deep_stats[4] = {0, 0, 0, 0};  // trgt_hip_size_deep_stats: the deep size loci of the last trgt_locus_batch (genotyped on the device, repaired among them, handed to the host, reserved)
+  bool flank_device = false;  // trgt_hip_set_flank_device: the haplotype-tag branch of genotype_flank runs in the device genotyper (locus_gt.hpp, FLANK forms)
+  int64_t flank_stats[4] = {0, 0, 0, 0};  // trgt_hip_flank_stats: of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, loci sent to the host path for the flank step, reserved)
   int num_cus = 256;
   // cached device buffers, indexed by slot
   struct Buf { void* p = nullptr; size_t cap = 0; };
@@ -269,6 +271,7 @@ enum Slot {
   S_CLD_LIST, S_CLD_LAST = S_CLD_LIST + (S_CL_VSCR - S_CL_LIST),  // the deep list of the cluster genotyper (locus_cluster_deep.hpp): a second set of the S_CL_ slots
   S_CLD_SEL,  // ... and its selected lists and merge records (one slab, shared with the deep size list)
   S_GSD_LIST,  // the deep list of the size genotyper (locus_gt_deep.hpp)
+  S_GT_HP,     // the reads' haplotype tags for the FLANK forms of the device genotyper (locus_gt.hpp)
   S_COUNT
 };
 // pinned host buffer slots

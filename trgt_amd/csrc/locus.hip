@@ -555,6 +555,10 @@ const OneWave<gt::GtArgs, pur::PurityArgs> k_purity_filter{{{pur::purity_filter_
 const OneWave<gt::GtArgs> k_genotype{{{gt::locus_genotype_kernel<64, 8 * 1024>, gt::locus_genotype_kernel<64, 8 * 1024, true>},
                                       {gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS>, gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS, true>}}};
 const OneWave<gt::GtArgs, gt::FinishArgs> k_repair_finish{{{gt::repair_finish_kernel<64>, gt::repair_finish_kernel<64, true>}, {gt::repair_finish_kernel<GT_BIG>, gt::repair_finish_kernel<GT_BIG, true>}}};
+// (the FLANK forms of the two: contexts that opted in to the haplotype-tag split on the device, calls whose reads carry tags)
+const OneWave<gt::GtFlankArgs> k_genotype_flank{{{gt::locus_genotype_kernel<64, 8 * 1024, false, true>, gt::locus_genotype_kernel<64, 8 * 1024, true, true>},
+                                            {gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS, false, true>, gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS, true, true>}}};
+const OneWave<gt::GtFlankArgs, gt::FinishArgs> k_repair_finish_flank{{{gt::repair_finish_kernel<64, false, true>, gt::repair_finish_kernel<64, true, true>}, {gt::repair_finish_kernel<GT_BIG, false, true>, gt::repair_finish_kernel<GT_BIG, true, true>}}};
 const OneWave<cl::ClArgs> k_cluster_front{{{cl::cluster_front_kernel<64>, cl::cluster_front_kernel<64, true>}, {cl::cluster_front_kernel<GT_BIG>, cl::cluster_front_kernel<GT_BIG, true>}}};
 // (the ward kernel's second argument is LDS_MAT: the distance matrix of a small locus fits the LDS -- it follows the size, not the filter)
 const OneWave<cl::ClArgs> k_cluster_ward{{{cl::cluster_ward_kernel<64, true>, cl::cluster_ward_kernel<64, true, true>}, {cl::cluster_ward_kernel<GT_BIG, false>, cl::cluster_ward_kernel<GT_BIG, false, true>}}};
@@ -594,7 +598,7 @@ struct LocusCall {
     const uint32_t* tr_len = nullptr; const uint64_t* al_off = nullptr; const uint32_t* al_cap = nullptr; const uint8_t* geno = nullptr;
     void *need = nullptr, *nal = nullptr, *blob = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr,
          *toff = nullptr, *packed = nullptr;
-    const double* rq = nullptr;
+    const double* rq = nullptr; const int16_t* hp = nullptr;
   };
   struct GtHost { void *need = nullptr, *nal = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr, *toff = nullptr, *packed = nullptr; };
   struct ClPlan { std::vector<uint32_t> list; std::vector<uint64_t> moff; uint64_t pairs = 0, reads = 0; uint32_t max_nr = 0; const uint32_t* d_list = nullptr; const uint64_t* d_moff = nullptr; };
@@ -608,7 +612,7 @@ struct LocusCall {
   const int64_t nl; int64_t nr = 0; int F = 0;
   bool done = false;  // nothing left to do (a call without loci or without reads)
   trgt_locus_batch_in in_expanded; std::vector<uint64_t> expanded_off;  // TRGT_READS_BAM4: the batch with its reads expanded in HBM
-  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
+  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
   FlankMeta flank_meta{};
   // ---- clean-up state (see the destructor)
   bool zeroed = false;
@@ -626,7 +630,7 @@ struct LocusCall {
   void *d_ss = nullptr, *d_se = nullptr, *d_hl = nullptr, *d_hr = nullptr, *h_ss = nullptr, *h_se = nullptr, *h_hl = nullptr, *h_hr = nullptr, *h_cells = nullptr;
   Slab slab;
   size_t o_ss = 0, o_se = 0, o_hl = 0, o_hr = 0, o_need = 0, o_nal = 0, o_alen = 0, o_ci = 0, o_nsp = 0, o_cls = 0, o_rank = 0, o_nspan = 0, o_toff = 0, o_flip = 0, o_gsz = 0,
-         o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0;
+         o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0, o_fdone = 0;
   GtDev g; GtHost gh;
   // ---- the device chains.  The cluster loci of the call: [0] the shallow list (at most GT_MAX_READS reads: the one-wave chain), [1] the
   // deep list (beyond that, up to the context's cluster_max_reads: locus_cluster_deep.hpp), each with its own pair slots, job lists, arenas
@@ -674,6 +678,8 @@ struct LocusCall {
   }
 
   bool is_cluster(int64_t l) const { return in->genotyper && in->genotyper[l] == 1; }
+  // ga as it stands, with what the FLANK forms read beyond it
+  gt::GtFlankArgs flank_args() const { gt::GtFlankArgs fa; static_cast<gt::GtArgs&>(fa) = ga; fa.hp_tag = g.hp; fa.flank_done = (uint8_t*)slab.d(o_fdone); return fa; }
   uint64_t& cell(int w) { return ((uint64_t*)h_cells)[w]; }
   void tl(const char* name) const { if (tl_on) fprintf(stderr, "[tl] %-28s %7.2f ms  ctx=%p\n", name, (double)(now_ns() - t0) / 1e6, (void*)c); }
 
@@ -689,6 +695,7 @@ struct LocusCall {
 int LocusCall::check_args() {
   if (nl < 0) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: negative n_loci");
   for (int64_t& v : c->size_deep_stats) v = 0;
+  for (int64_t& v : c->flank_stats) v = 0;
   if (nl == 0) { done = true; return TRGT_OK; }
   if (!in->flank_blob || !in->lf_off || !in->lf_len || !in->rf_off || !in->rf_len || !in->tr_blob || !in->tr_off || !in->tr_len ||
       !in->motif_blob || !in->motif_off || !in->set_motif_begin || !in->ploidy || !in->locus_read_begin || !in->read_blob ||
@@ -801,6 +808,9 @@ int LocusCall::upload_tables() {
   // genotype_flank (tr.rs:69-75) can only change a genotype when reads carry haplotype tags or mismatch offsets
   flank_on = in->hp_tag != nullptr || (in->mismatch_offsets != nullptr && in->mismatch_off != nullptr);
   flank_meta = FlankMeta{in->hp_tag, in->start_offset, in->end_offset, in->mismatch_offsets, in->mismatch_off};
+  // ... and its haplotype-tag branch runs inside the device genotyper on a context that opted in (trgt_hip_set_flank_device): the FLANK
+  // forms of locus_gt.hpp, which read the tags and leave one byte per locus
+  flank_dev = dev_gt && c->flank_device && in->hp_tag != nullptr;
   int rc;
   if (ready) TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, ready, 0));
   if (staged_flank) d_flank = staged_flank;
@@ -823,6 +833,7 @@ int LocusCall::upload_tables() {
     o_nsp = slab.add(2 * (size_t)nl * 4); o_cls = slab.add((size_t)nr * 4); o_rank = slab.add((size_t)nr * 4); o_nspan = slab.add((size_t)nl * 4);
     o_toff = slab.add((2 * (size_t)nl + 1) * 8); o_flip = slab.add((size_t)nl);
     o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
+    if (flank_dev) o_fdone = slab.add((size_t)nl);
   }
   if ((rc = dev_get(c, S_LOCUS_4, slab.total, &slab.dev)) || (rc = pin_get(c, P_SPAN_S, slab.total, &slab.host))) return rc;
   d_ss = slab.d(o_ss); d_se = slab.d(o_se); d_hl = slab.d(o_hl); d_hr = slab.d(o_hr);
@@ -833,6 +844,7 @@ int LocusCall::upload_tables() {
         (rc = dev_in(c, S_GT_TRLEN, in->tr_len, (size_t)nl, &g.tr_len, &ub)) || (rc = dev_in(c, S_GT_ALOFF, out->allele_off, 2 * (size_t)nl, &g.al_off, &ub)) ||
         (rc = dev_in(c, S_GT_ALCAP, out->allele_cap, (size_t)nl, &g.al_cap, &ub)) || (in->genotyper && (rc = dev_in(c, S_GT_GENO, in->genotyper, (size_t)nl, &g.geno, &ub))) ||
         (presel && in->read_qual && (rc = dev_in(c, S_PUR_RQ, in->read_qual, (size_t)nr, &g.rq, &ub))) ||
+        (flank_dev && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
         (rc = dev_get(c, S_GT_BLOB, (size_t)allele_total + 16, &g.blob)) || (rc = dev_get(c, S_GT_PACKED, (size_t)allele_total + 16, &g.packed)))
       return rc;
   }
@@ -1073,7 +1085,8 @@ int LocusCall::purity_chain() {
 }
 int LocusCall::size_genotyper() {
   if (!dev_gt) return TRGT_OK;
-  k_genotype.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, ga);
+  if (flank_dev) k_genotype_flank.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, flank_args());
+  else k_genotype.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, ga);
   if (!gsd_list.empty()) {
     // ---- the deep size list, behind the one-wave genotyper (which marked these loci need_host = 1): selection unless it ran in front
     //      of the purity batch, then the workgroup-wide genotyper; its loci without majority support join the repair chain below
@@ -1157,7 +1170,8 @@ int LocusCall::repair_chain() {
   hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)rp.cap_groups), dim3(vote::VOTE_THREADS), 0, c->stream, va);
   const gt::FinishArgs fa{(const uint8_t*)rb.vout, (const uint32_t*)rb.vlen};
   const dim3 fgrid((unsigned)nl);
-  k_repair_finish.launch(!small_gt, presel, fgrid, c->stream, ga, fa);
+  if (flank_dev) k_repair_finish_flank.launch(!small_gt, presel, fgrid, c->stream, flank_args(), fa);
+  else k_repair_finish.launch(!small_gt, presel, fgrid, c->stream, ga, fa);
   if (!gsd_list.empty()) { ds.c.g = ga; hipLaunchKernelGGL(gtd::deep_size_finish_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds, fa); }
   TRGT_HIP_TRY(c, hipGetLastError());
   if ((rc = dbg_sync("vote + finish"))) return rc;
@@ -1322,15 +1336,25 @@ int LocusCall::wait_stage_a() {
     if (flank_on) {
       // device-genotyped loci whose two alleles are at most 10 bases apart and whose reads DO split by haplotype tag or flank SNVs
       // take the host path, where the genotype is replaced (genotype_flank below); the split only needs the per-read fields
+      // (not the loci whose genotype the FLANK forms of the device genotyper already replaced by the tag split)
       const int32_t* nal = (const int32_t*)gh.nal; const uint32_t* alen = (const uint32_t*)gh.alen; const int32_t* rank = (const int32_t*)gh.rank;
+      const uint8_t* fdone = flank_dev ? (const uint8_t*)slab.h(o_fdone) : nullptr;
+      std::atomic<int64_t> sent{0};
       pool->parallel_for(nl, 64, [&](int64_t l, int) {
-        if (need[l] || nal[l] != 2 || adiff(alen[2 * l], alen[2 * l + 1]) > 10) return;
+        if (need[l] || (fdone && (fdone[l] & gt::FL_DONE)) || nal[l] != 2 || adiff(alen[2 * l], alen[2 * l + 1]) > 10) return;
         const uint64_t r0 = in->locus_read_begin[l], r1 = in->locus_read_begin[l + 1];
         std::vector<uint32_t> order;
         for (uint64_t r = r0; r < r1; ++r) if (rank[r] >= 0) { if ((size_t)rank[r] >= order.size()) order.resize((size_t)rank[r] + 1, 0); order[(size_t)rank[r]] = (uint32_t)r; }
         FlankSplit sp;
-        if (flank_split(flank_meta, order.data(), order.size(), sp)) need[l] = 1;
+        if (flank_split(flank_meta, order.data(), order.size(), sp)) { need[l] = 1; sent += 1; }
       });
+      if (fdone) {  // trgt_hip_flank_stats
+        for (int64_t l = 0; l < nl; ++l) {
+          if ((fdone[l] & gt::FL_DONE) && !need[l]) { c->flank_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_stats[1] += 1; }
+          else if (fdone[l] == gt::FL_HANDED) c->flank_stats[2] += 1;
+        }
+        c->flank_stats[2] += sent.load();
+      }
     }
     for (int64_t l = 0; l < nl; ++l) if (need[l]) R.push_back(l);
     // an alignment job of a device-built list that the generic kernel refused (longer than the workspace planned from the batch's maxima)
@@ -1960,6 +1984,18 @@ extern "C" int trgt_hip_set_size_max_reads(trgt_hip_ctx* c, int32_t max_reads) {
 extern "C" int trgt_hip_size_deep_stats(const trgt_hip_ctx* c, int64_t out[4]) {
   if (!c || !out) return TRGT_ERR_INVALID;
   for (int i = 0; i < 4; ++i) out[i] = c->size_deep_stats[i];
+  return TRGT_OK;
+}
+
+// ---- the haplotype-tag branch of genotype_flank inside the device genotyper is opt-in per context as well (locus_gt.hpp, FLANK forms)
+extern "C" int trgt_hip_set_flank_device(trgt_hip_ctx* c, int on) {
+  if (!c) return TRGT_ERR_INVALID;
+  c->flank_device = on != 0;
+  return TRGT_OK;
+}
+extern "C" int trgt_hip_flank_stats(const trgt_hip_ctx* c, int64_t out[4]) {
+  if (!c || !out) return TRGT_ERR_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = c->flank_stats[i];
   return TRGT_OK;
 }
 

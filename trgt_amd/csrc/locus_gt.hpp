@@ -10,7 +10,11 @@
 // locus.hip.  A locus whose pick lacks majority support waits (need_host = 2) for the consensus alignments of stage B
 // (repair_consensus, consensus.rs:5-111) and repair_finish_kernel below, or goes to the host path when that chain has no room for it.
 // The arithmetic (f64 penalties, tie-breaks) is written operation for operation like the host version in locus.hip, which the oracle pins.
+// The FLANK instantiations (contexts that opted in, trgt_hip_set_flank_device) also run the haplotype-tag branch of
+// genotype_flank::genotype (genotype_flank.rs:9-76, 147-170; tr.rs:69-75) for a locus whose two sizes are at most 10 apart: see flank_route.
 #pragma once
+#include <type_traits>
+
 #include "common.hpp"
 #include "wfa_host.hpp"
 
@@ -35,6 +39,12 @@ struct RGroup {  // = vote::Group (consensus_vote.hpp; the layouts are asserted 
 struct RepairPend {  // what the genotyper had decided for a locus that waits for its repaired alleles
   int32_t n_gt, n_pick; uint32_t size[2]; int32_t civ[4]; int32_t rep[2] /* rank of the pick */; int32_t grp[2] /* vote group, -1: the pick stands */;
 };
+// n_pick of a record the haplotype-tag route wrote (FLANK instantiations only): rep[] are the backbones of the two tag groups, civ[] the
+// groups' length ranges, and the finish is flank_finish's
+constexpr int32_t RP_FLANK = 0x100;
+// GtFlankArgs::flank_done, per locus: the tag split replaced the genotype (FL_DONE; FL_DONE | FL_REPAIRED: behind the repair chain), or the
+// split was accepted and the locus handed to the host path (no room in the chain, a segment beyond max_seg, allele_cap)
+enum { FL_DONE = 1, FL_REPAIRED = 2, FL_HANDED = 4 };
 enum { RC_GROUPS = 0, RC_JOBS = 1, RC_LOCI = 2, RC_FAILED = 3, RC_CIGAR = 4 /* u64 */, RC_OUT = 6 /* u64 */, RC_SCRATCH = 8 /* u64 */, RC_REFUSED = 10 /* alignment jobs of the chain the generic kernel refused (beyond its planned workspace) */, RC_WORDS = 16 };
 struct RepairBufs {
   uint32_t* counts;  // [RC_WORDS]; nullptr: no device-side repair (every such locus takes the host path)
@@ -61,9 +71,23 @@ struct GtArgs {
   // ordered and filtered, in slots [locus_read_begin[l], + n_sel[l]) -- read (index inside the locus), span start, span length
   const uint32_t *sel_read, *sel_start, *sel_len, *n_sel;
 };
+// The arguments of the FLANK instantiations (contexts that opted in to the tag split on the device).  A struct of its own: GtArgs is part
+// of the arguments of every cluster and deep kernel, whose register allocation follows its size.
+struct GtFlankArgs : GtArgs {
+  const int16_t* hp_tag;  // per read of the batch: the HP tag (-1 = None)
+  uint8_t* flank_done;    // [n_loci] FL_* above
+};
+template <bool FLANK> using GtArgsOf = std::conditional_t<FLANK, GtFlankArgs, GtArgs>;
 
-template <int MAXR, int SEG>
-struct GtShared {
+// what the haplotype-tag route adds to the LDS of the FLANK instantiations (1.5 KB for 256 reads); the assignment lives in cls[]
+template <int MAXR, bool FLANK> struct FlankShared {};
+template <int MAXR> struct FlankShared<MAXR, true> {
+  uint16_t f_uidx[MAXR];    // per kept read: its unique sequence -- first the position of the first read that carries it, then its rank in u_rep
+  uint16_t f_cnt[2][MAXR];  // multiplicity of every unique sequence inside either tag group
+  uint32_t f_med[2][2];     // the two middle lengths of either group
+};
+template <int MAXR, int SEG, bool FLANK = false>
+struct GtShared : FlankShared<MAXR, FLANK> {
   uint32_t r_s[MAXR], r_len[MAXR];     // per read of the locus: span start / span length (0xFFFFFFFF start = not kept)
   uint64_t r_off[MAXR];                        // per read: byte offset of the read in the blob
   uint32_t s_read[MAXR], s_start[MAXR], s_len[MAXR];  // kept reads in LocusResult.reads order
@@ -214,9 +238,189 @@ __device__ __forceinline__ void gt_selected(SH& sh, const GtArgs& a, int64_t l, 
   }
 }
 
-template <int MAXR, int SEG, bool PRESEL = false>
-__global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgs a) {  // exactly one wave per locus: the lane-0 sections and the ballots rely on it
-  __shared__ GtShared<MAXR, SEG> sh;
+// ---- the haplotype-tag branch of genotype_flank::genotype on the device (genotype_flank.rs:9-76; applied by analyze at tr.rs:69-75 to a
+// diploid locus whose two sizes are at most 10 apart).  The SNV-clustering branch (:78-138) stays on the host: a locus whose tags do not
+// split its reads leaves the kernels with the length genotype, and the host tries that branch for it as before.
+__device__ __forceinline__ uint32_t wave_min_u(uint32_t v) { for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o); v = w < v ? w : v; } return v; }
+__device__ __forceinline__ uint32_t wave_max_u(uint32_t v) { for (int o = 32; o > 0; o >>= 1) { const uint32_t w = (uint32_t)__shfl_xor((int)v, o); v = w > v ? w : v; } return v; }
+
+// get_trs_with_hp (:43-76) over the kept reads in sh.s_read order: tag 1 -> group 0, tag 2 -> group 1, every other read alternates (the
+// k-th untagged read, k from 0, goes to group k % 2: assignment_tie_breaker starts at 1 and is advanced before use).  64 reads per round:
+// a ballot of the untagged lanes and the count of those below a lane give k.  Leaves the assignment in sh.cls and the group sizes in
+// cnt; true when the split is accepted (both groups occur, at least 70 % of the reads tagged).  Uniform arguments, uniform result.
+template <class SH>
+__device__ __forceinline__ bool flank_assign(SH& sh, const int16_t* __restrict__ hp, uint64_t r0, int n, int lane, int cnt[2]) {
+  int untagged = 0;
+  cnt[0] = cnt[1] = 0;
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    const int tag = i < n ? (int)hp[r0 + sh.s_read[i]] : 0;
+    const bool un = i < n && tag != 1 && tag != 2;
+    const unsigned long long ub = __ballot(un);
+    const int k = untagged + __popcll(ub & ((1ull << lane) - 1ull));
+    const int g = un ? (k & 1) : tag - 1;
+    if (i < n) sh.cls[i] = (int8_t)g;
+    const int ones = __popcll(__ballot(i < n && g == 1));
+    cnt[1] += ones; cnt[0] += (n - base < 64 ? n - base : 64) - ones;
+    untagged += __popcll(ub);
+  }
+  __syncthreads();
+  return cnt[0] > 0 && cnt[1] > 0 && (double)(n - untagged) / (double)n >= 0.7;
+}
+
+// The route inside the genotype kernel, behind get_seq_hist (nu unique sequences in sh.u_rep, sh.f_uidx[i] = position of the first read
+// with read i's sequence).  false: the tags do not split the reads and the locus continues with the length genotype.  true: the locus is
+// settled here -- simple_consensus (:147-170) of either group; without a group below 50 % the genotype is written to sh.res_* / sh.cls
+// like the length genotyper's, else the groups join the call's repair chain (sh.bail = 2: flank_finish completes the locus), or the locus
+// is handed to the host path (sh.bail = 1).  Called by the whole wave with uniform arguments.
+template <class SH>
+__device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_t l, uint64_t r0, int n, int nu, int lane, bool fits, uint32_t refn, uint64_t refo) {
+  int cnt[2];
+  if (!flank_assign(sh, a.hp_tag, r0, n, lane, cnt)) return false;
+  // ---- the unique sequence of every read as its rank in u_rep (the insertions of get_seq_hist moved the ranks while the list grew)
+  uint16_t* inv = sh.f_cnt[0];
+  for (int q = lane; q < nu; q += 64) inv[sh.u_rep[q]] = (uint16_t)q;
+  __syncthreads();
+  for (int i = lane; i < n; i += 64) sh.f_uidx[i] = inv[sh.f_uidx[i]];
+  __syncthreads();
+  // ---- multiplicities inside the groups (lane q owns unique sequence q), and the middle lengths of either group by rank
+  for (int q = lane; q < nu; q += 64) {
+    int c0 = 0, c1 = 0;
+    for (int i = 0; i < n; ++i) if (sh.f_uidx[i] == q) { if (sh.cls[i]) ++c1; else ++c0; }
+    sh.f_cnt[0][q] = (uint16_t)c0; sh.f_cnt[1][q] = (uint16_t)c1;
+  }
+  for (int i = lane; i < n; i += 64) {
+    const int g = sh.cls[i]; const uint32_t li = sh.s_len[i];
+    int r = 0;
+    for (int j = 0; j < n; ++j) { const uint32_t lj = sh.s_len[j]; r += sh.cls[j] == g && (lj < li || (lj == li && j < i)); }
+    if (r == cnt[g] / 2) sh.f_med[g][1] = li;
+    if (r == cnt[g] / 2 - 1) sh.f_med[g][0] = li;
+  }
+  __syncthreads();
+  int rep[2]; uint32_t aln[2], lo[2], hi[2]; bool lacks[2];
+  for (int g = 0; g < 2; ++g) {
+    // utils::math::median (math.rs:73-98) as f32, truncated: the middle value, or (a + b) as i32, then / 2.0
+    const float med = (cnt[g] & 1) ? (float)(int32_t)sh.f_med[g][1] : (float)((int32_t)sh.f_med[g][0] + (int32_t)sh.f_med[g][1]) / 2.0f;
+    const uint32_t median_len = (uint32_t)med;
+    uint32_t top = 0, mn = 0xFFFFFFFFu, mx = 0;
+    for (int q = lane; q < nu; q += 64) top = sh.f_cnt[g][q] > top ? sh.f_cnt[g][q] : top;
+    top = wave_max_u(top);
+    // among the sequences with the largest multiplicity, in u_rep order: the first minimum of |len - median|
+    uint32_t bd = 0xFFFFFFFFu; int bq = 0x7FFFFFFF;
+    for (int q = lane; q < nu; q += 64)
+      if (sh.f_cnt[g][q] == top) { const uint32_t d = adiff_u(sh.s_len[sh.u_rep[q]], median_len); if (d < bd) { bd = d; bq = q; } }
+    for (int o = 32; o > 0; o >>= 1) {
+      const uint32_t od = (uint32_t)__shfl_xor((int)bd, o); const int oq = __shfl_xor(bq, o);
+      if (od < bd || (od == bd && oq < bq)) { bd = od; bq = oq; }
+    }
+    for (int i = lane; i < n; i += 64) if (sh.cls[i] == g) { mn = sh.s_len[i] < mn ? sh.s_len[i] : mn; mx = sh.s_len[i] > mx ? sh.s_len[i] : mx; }
+    lo[g] = wave_min_u(mn); hi[g] = wave_max_u(mx);
+    rep[g] = sh.u_rep[bq]; aln[g] = sh.s_len[rep[g]];
+    lacks[g] = (double)top / (double)cnt[g] < 0.5;
+  }
+  if (lacks[0] || lacks[1]) {
+    // ---- a group below 50 %: backbone = its sequence, one member per read of the group in read order, duplicates included; the
+    //      reservations are the size route's
+    const RepairBufs& rp = a.rp;
+    bool can = rp.counts != nullptr;
+    uint32_t nm[2] = {0, 0}; unsigned long long mbytes[2] = {0, 0}, cig[2] = {0, 0};
+    if (can)
+      for (int g = 0; g < 2; ++g) {
+        if (!lacks[g]) continue;
+        if (aln[g] > rp.max_seg) can = false;
+        for (int i = 0; i < n; ++i) {
+          if (sh.cls[i] != g) continue;
+          const uint32_t ln = sh.s_len[i];
+          if (ln > rp.max_seg) can = false;
+          nm[g] += 1; mbytes[g] += ln; cig[g] += (unsigned long long)aln[g] + ln + 1;
+        }
+      }
+    unsigned long long out_need[2] = {0, 0}, scr_need[2] = {0, 0};
+    uint32_t out_cap[2] = {0, 0};
+    if (can) {
+      for (int g = 0; g < 2; ++g) {
+        if (!lacks[g]) continue;
+        out_cap[g] = (uint32_t)(aln[g] + mbytes[g] + 16);
+        out_need[g] = ((unsigned long long)out_cap[g] + 15ull) & ~15ull;
+        scr_need[g] = (aln[g] + 1 <= rp.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)aln[g] + 1)) + 3ull * nm[g];
+      }
+      if (lane == 0) {
+        const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
+        int ok = 1;
+        unsigned long long c0 = 0, o0 = 0, s0 = 0;
+        c0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_CIGAR), cn);
+        if (c0 + cn > rp.cap_cigar) ok = 0;
+        if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_OUT), on); if (o0 + on > rp.cap_out) ok = 0; }
+        if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_SCRATCH), sn); if (s0 + sn > rp.cap_scratch) ok = 0; }
+        if (ok) {
+          sh.rp_j0 = atomicAdd(rp.counts + RC_JOBS, nm[0] + nm[1]);
+          sh.rp_g0 = atomicAdd(rp.counts + RC_GROUPS, (uint32_t)lacks[0] + (uint32_t)lacks[1]);
+          if (sh.rp_j0 + nm[0] + nm[1] > rp.cap_jobs || sh.rp_g0 + 2 > rp.cap_groups) ok = 0;  // (cannot happen: the caps are the read and locus counts)
+          else { const uint32_t slot = atomicAdd(rp.counts + RC_LOCI, 1u); if (slot < (uint32_t)a.n_loci) rp.loci[slot] = (uint32_t)l; else ok = 0; }
+        } else atomicAdd(rp.counts + RC_FAILED, 1u);
+        sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
+      }
+      __syncthreads();
+      can = sh.rp_ok != 0;
+    }
+    if (!can) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED; return true; }
+    uint32_t gi = sh.rp_g0, j = sh.rp_j0;
+    unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
+    RepairPend pd;
+    pd.n_gt = 2; pd.n_pick = 2 | RP_FLANK; pd.size[0] = aln[0]; pd.size[1] = aln[1];
+    for (int g = 0; g < 2; ++g) { pd.civ[2 * g] = (int32_t)lo[g]; pd.civ[2 * g + 1] = (int32_t)hi[g]; pd.rep[g] = rep[g]; pd.grp[g] = -1; }
+    for (int g = 0; g < 2; ++g) {
+      if (!lacks[g]) continue;
+      const unsigned long long bb_off = sh.r_off[sh.s_read[rep[g]]] + sh.s_start[rep[g]];
+      if (lane == 0) {
+        RGroup G;
+        G.job_first = j; G.n_members = nm[g]; G.bb_len = aln[g]; G.out_cap = out_cap[g];
+        G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
+        rp.groups[gi] = G;
+      }
+      pd.grp[g] = (int32_t)gi;
+      uint32_t k = 0;
+      for (int i = 0; i < n; ++i) {
+        if (sh.cls[i] != g) continue;
+        if ((int)(k & 63u) == lane) {
+          JobDev jd;
+          jd.pat_off = bb_off; jd.pat_len = aln[g];
+          jd.txt_off = sh.r_off[sh.s_read[i]] + sh.s_start[i]; jd.txt_len = sh.s_len[i];
+          jd.cigar_off = co; jd.ops_off = 0; jd.out_index = j + k; jd.pad = 0;
+          rp.jobs[j + k] = jd;
+        }
+        co += (unsigned long long)aln[g] + sh.s_len[i] + 1;
+        ++k;
+      }
+      j += nm[g]; oo += out_need[g]; so += scr_need[g]; ++gi;
+    }
+    if (lane == 0) rp.pend[l] = pd;
+    sh.bail = 2;  // the locus waits for repair_finish_kernel
+    return true;
+  }
+  // ---- both groups have their sequence: smaller allele first (:33-38: alleles and intervals swap, the assignment flips), the
+  //      assignment is the classification, then reference allele first (tr.rs:95-101)
+  const int sw = aln[0] > aln[1] ? 1 : 0;
+  if (sw) for (int i = lane; i < n; i += 64) sh.cls[i] = (int8_t)(1 - sh.cls[i]);
+  auto seg_glob = [&](int i) { return a.reads + sh.r_off[sh.s_read[i]] + sh.s_start[i]; };
+  auto eq_ref = [&](int g) {
+    return fits ? cmp_lds(sh.bytes + sh.s_loff[rep[g]], aln[g], sh.bytes + sh.ref_off, refn) == 0 : cmp_bytes(seg_glob(rep[g]), aln[g], a.tr_blob + refo, refn) == 0;
+  };
+  int order[2] = {sw, 1 - sw}; int flip = 0;
+  if (!eq_ref(order[0]) && eq_ref(order[1])) { order[0] = 1 - sw; order[1] = sw; flip = 1; }
+  if (aln[0] > a.allele_cap[l] || aln[1] > a.allele_cap[l]) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED; return true; }  // the host path reports the error
+  sh.res_n_gt = 2; sh.res_flip = flip;
+  for (int oi = 0; oi < 2; ++oi) {
+    const int g = order[oi];
+    sh.res_rep[oi] = rep[g]; sh.res_ci[2 * oi] = (int)lo[g]; sh.res_ci[2 * oi + 1] = (int)hi[g]; sh.res_hap[oi] = cnt[g];
+  }
+  if (lane == 0) a.flank_done[l] = FL_DONE;
+  return true;
+}
+
+template <int MAXR, int SEG, bool PRESEL = false, bool FLANK = false>
+__global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK> a) {  // exactly one wave per locus: the lane-0 sections and the ballots rely on it
+  __shared__ GtShared<MAXR, SEG, FLANK> sh;
   const int64_t l = blockIdx.x;
   if (l >= a.n_loci) return;
   const int lane = threadIdx.x;
@@ -228,6 +432,7 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgs a) {  /
     if (a.skip_b) a.skip_b[l] = 1;
     a.need_host[l] = 0; a.n_alleles[l] = 0; a.n_spanning_reads[l] = 0; a.flipped[l] = 0;
     a.allele_len[2 * l] = a.allele_len[2 * l + 1] = 0; a.num_spanning[2 * l] = a.num_spanning[2 * l + 1] = 0;
+    if constexpr (FLANK) a.flank_done[l] = 0;
   }
   const bool cluster = a.genotyper && a.genotyper[l] == 1;
   if (a.ploidy[l] == 0 || nr == 0 || nr > MAXR || cluster) {  // Ploidy::Zero -> LocusResult::empty (tr.rs:29-31); oversized, cluster genotyper -> host
@@ -351,12 +556,19 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgs a) {  /
           if (c < 0) hi = mid; else lo = mid + 1;
         }
         // (the list is written by lane 0 only; the comparisons of the next round read it back in program order: one wave, one LDS queue)
-        if (eq >= 0) { if (lane == 0) sh.u_cnt[eq] += 1; continue; }
+        if (eq >= 0) { if (lane == 0) { sh.u_cnt[eq] += 1; if constexpr (FLANK) sh.f_uidx[i] = sh.u_rep[eq]; } continue; }
         if (lane == 0) {
           for (int q = nu; q > lo; --q) { sh.u_rep[q] = sh.u_rep[q - 1]; sh.u_cnt[q] = sh.u_cnt[q - 1]; }
           sh.u_rep[lo] = (uint16_t)i; sh.u_cnt[lo] = 1;
+          if constexpr (FLANK) sh.f_uidx[i] = (uint16_t)i;
         }
         ++nu;
+      }
+      // ---- FLANK: two sizes at most 10 apart (tr.rs:69-75) and tags that split the reads replace everything below; the size
+      //      genotyper's own repair is not queued for such a locus
+      bool by_tags = false;
+      if constexpr (FLANK) {
+        if (a.hp_tag && n_gt == 2 && adiff_u(size[0], size[1]) <= 10) by_tags = flank_route(sh, a, l, r0, n, nu, lane, fits, refn, refo);
       }
       auto ulen_of = [&](int q) { return sh.s_len[sh.u_rep[q]]; };
       auto closest = [&](uint32_t target) { uint32_t c = ulen_of(0); for (int q = 0; q < nu; ++q) if (adiff_u(c, target) > adiff_u(ulen_of(q), target)) c = ulen_of(q); return c; };
@@ -379,7 +591,8 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgs a) {  /
         }
         if (!(2 * ref_count >= coverage)) { majority = false; lacks[al] = true; }
       }
-      if (!majority) {
+      if (by_tags) {}
+      else if (!majority) {
         // ---- stage B on the device: one vote group per allele without majority support, one alignment job per unique sequence of
         //      its group against the pick (the members of make_consensus, genotype_size.rs:32-37), all segments of the read blob
         const RepairBufs& rp = a.rp;
@@ -545,8 +758,55 @@ __device__ __forceinline__ bool wave_equal(const uint8_t* __restrict__ p, uint32
   for (uint32_t i = threadIdx.x & 63; i < n; i += 64) diff = diff || p[i] != q[i];
   return __ballot(diff) == 0ull;
 }
-template <int MAXR, bool PRESEL = false>
-__global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgs a, const FinishArgs f) {
+// ... and of a locus the haplotype-tag route left waiting (RP_FLANK): the assignment is recomputed from the tags (deterministic from the
+// same list of kept reads), the alleles are the repaired sequences or the backbones; smaller allele first (genotype_flank.rs:33-38), the
+// assignment is the classification, its counts are num_spanning, the sizes of the genotype are the allele lengths
+template <class SH>
+__device__ __forceinline__ void flank_finish(SH& sh, const GtFlankArgs& a, const FinishArgs& f, const RepairPend& pd, int64_t l, uint64_t r0, int n, int lane) {
+  const RepairBufs& rp = a.rp;
+  int cnt[2] = {0, 0};
+  bool fail = n == 0 || !flank_assign(sh, a.hp_tag, r0, n, lane, cnt);
+  const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
+  for (int g = 0; g < 2 && !fail; ++g) {
+    if (pd.grp[g] >= 0) {
+      const uint32_t len = f.vote_len[pd.grp[g]];
+      if (len == 0xFFFFFFFFu) { fail = true; break; }
+      ap[g] = f.vote_out + rp.groups[pd.grp[g]].out_off; aln[g] = len;
+    } else {
+      const int rep = pd.rep[g];
+      ap[g] = a.reads + sh.r_off[sh.s_read[rep]] + sh.s_start[rep]; aln[g] = sh.s_len[rep];
+    }
+  }
+  const int sw = aln[0] > aln[1] ? 1 : 0;
+  int order[2] = {sw, 1 - sw}, flip = 0;  // output allele -> tag group
+  if (!fail) {
+    const uint8_t* ref = a.tr_blob + a.tr_off[l]; const uint32_t refn = a.tr_len[l];
+    if (!wave_equal(ap[order[0]], aln[order[0]], ref, refn) && wave_equal(ap[order[1]], aln[order[1]], ref, refn)) { order[0] = 1 - sw; order[1] = sw; flip = 1; }
+    if (aln[0] > a.allele_cap[l] || aln[1] > a.allele_cap[l]) fail = true;  // the host path reports the error
+  }
+  if (fail) { if (lane == 0) { a.need_host[l] = 1; a.flank_done[l] = FL_HANDED; } return; }
+  for (int oi = 0; oi < 2; ++oi) {
+    const int g = order[oi];
+    uint8_t* dst = a.allele_blob + a.allele_off[2 * l + oi];
+    for (uint32_t b = lane; b < aln[g]; b += 64) dst[b] = ap[g][b];
+    if (lane == 0) {
+      a.allele_len[2 * l + oi] = aln[g];
+      a.ci[4 * l + 2 * oi] = pd.civ[2 * g]; a.ci[4 * l + 2 * oi + 1] = pd.civ[2 * g + 1];
+      a.num_spanning[2 * l + oi] = cnt[g];
+      if (a.gt_size) a.gt_size[2 * l + oi] = (int32_t)aln[g];
+    }
+  }
+  for (int i = lane; i < n; i += 64) {
+    a.classification[r0 + sh.s_read[i]] = sh.cls[i] == order[0] ? 0 : 1;
+    a.read_rank[r0 + sh.s_read[i]] = i;
+  }
+  if (lane == 0) {
+    a.n_alleles[l] = 2; a.n_spanning_reads[l] = (uint32_t)n; a.flipped[l] = (uint8_t)flip; a.skip_b[l] = 0; if (a.finish_clears_need) a.need_host[l] = 0;
+    a.flank_done[l] = FL_DONE | FL_REPAIRED;
+  }
+}
+template <int MAXR, bool PRESEL = false, bool FLANK = false>
+__global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgsOf<FLANK> a, const FinishArgs f) {
   __shared__ FinShared<MAXR> sh;
   const RepairBufs& rp = a.rp;
   if (blockIdx.x >= rp.counts[RC_LOCI]) return;
@@ -559,6 +819,9 @@ __global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgs a, const
   gt_selected<MAXR, PRESEL>(sh, a, l, r0, nr, lane);
   const int n = sh.n;
   const RepairPend pd = rp.pend[l];
+  if constexpr (FLANK) {
+    if (pd.n_pick & RP_FLANK) { flank_finish(sh, a, f, pd, l, r0, n, lane); return; }
+  }
   const int ploidy = a.ploidy[l] == 1 ? 1 : 2;
   // the alleles: the repaired sequence of a group, or the pick that had majority support
   const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};

@@ -17,9 +17,9 @@ from . import _lib, locus
 
 
 class ChunkDriver:
-    """devices: one entry per context (ordinals may repeat: several contexts on one GPU).  cluster_max_reads, size_max_reads: passed to every context."""
+    """devices: one entry per context (ordinals may repeat: several contexts on one GPU).  cluster_max_reads, size_max_reads, flank_device: passed to every context."""
 
-    def __init__(self, devices=(0,), params=None, context_factory=None, run_fn=None, cluster_max_reads=None, size_max_reads=None):
+    def __init__(self, devices=(0,), params=None, context_factory=None, run_fn=None, cluster_max_reads=None, size_max_reads=None, flank_device=None):
         self.params = params or locus.Params()
         self._make = context_factory or (lambda dev: _lib.Context(dev))
         self._run = run_fn or (lambda ctx, chunk, params, kw: locus.run_batch(chunk, params, ctx, **kw))
@@ -31,6 +31,9 @@ class ChunkDriver:
         if size_max_reads is not None:  # deep Genotyper::Size loci on the device (Context.set_size_max_reads), likewise
             for c in self.contexts:
                 c.set_size_max_reads(size_max_reads)
+        if flank_device is not None:  # the haplotype-tag branch of genotype_flank inside the device genotyper (Context.set_flank_device), likewise
+            for c in self.contexts:
+                c.set_flank_device(flank_device)
         self.chunks_by_context = [0] * len(self.contexts)
 
     def close(self):
