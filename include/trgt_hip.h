@@ -92,10 +92,13 @@ int trgt_hip_set_cluster_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
  * the reference's default --max-depth 250 the reservoir hands over up to 750 -- go through the host path.  A context set to
  * max_reads > 256 also keeps size loci with 256 < reads <= max_reads on the device (one workgroup per locus, locus_gt_deep.hpp); a locus
  * whose pick lacks majority support joins the call's device-side consensus repair, and one that finds no room there, has a segment
- * beyond the repair's longest or an allele beyond allele_cap takes the host path.  Results are the same either way.
+ * beyond the repair's longest or an allele beyond allele_cap takes the host path.  Results are the same either way.  On a context that
+ * is also set with trgt_hip_set_flank_device, a haplotagged batch's deep loci run the tag branch of genotype_flank inside the same
+ * workgroup (below); without that setting a deep locus whose tags split its reads is genotyped on the device and then again on the host.
  * trgt_hip_size_max_reads_limit: the compiled ceiling (2048), no GPU needed.  max_reads outside [256, limit]: TRGT_ERR_INVALID, the
  * setting stays.  trgt_hip_size_deep_stats: of the context's last trgt_locus_batch -- out[0] deep size loci genotyped on the device,
- * out[1] those among them that went through the repair, out[2] deep size loci inside the setting that were handed to the host path,
+ * out[1] those among them that went through the repair, out[2] deep size loci inside the setting that were handed to the host path
+ * (a deep locus the tag branch settled counts in out[0], in out[1] if a tag group was repaired; one it handed back in out[2]),
  * out[3] reserved (0).  The contexts of a pool are set and asked one by one through trgt_hip_pool_context. */
 int32_t trgt_hip_size_max_reads_limit(void);
 int trgt_hip_set_size_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
@@ -106,12 +109,14 @@ int trgt_hip_size_deep_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
  * calls whose batch carries hp_tag run the tag branch inside the device genotyper: assignment by tag, acceptance (70 % tagged, both
  * haplotypes), simple_consensus of either group, the call's consensus repair for a group without a majority sequence, smaller allele
  * first.  What stays on the host: the SNV-clustering branch (get_trs_with_clustering, :78-138), tried for the loci whose tags do not
- * split the reads exactly as before; Genotyper::Cluster loci; loci of more than 256 reads; contexts created under TRGT_HOST_GENOTYPER;
- * and a locus on this route that finds no room in the repair chain, has a segment beyond its longest (every such locus under
+ * split the reads exactly as before; Genotyper::Cluster loci; loci of more than 256 reads unless the context is also set with
+ * trgt_hip_set_size_max_reads (then: loci beyond that setting or the 2048-read ceiling; inside it the deep size kernels of
+ * locus_gt_deep.hpp run the same branch, one workgroup per locus); contexts created under TRGT_HOST_GENOTYPER; and a locus on this route that finds no room in the repair chain, has a segment beyond its longest (every such locus under
  * TRGT_HOST_REPAIR) or an allele beyond allele_cap.  Results are the same either way.  trgt_hip_flank_stats: of the context's last
  * trgt_locus_batch -- out[0] loci whose genotype the device replaced by the tag split, out[1] those among them with at least one
  * repaired group, out[2] device-genotyped loci sent to the host path for the flank step (the SNV branch splits them, or this route
- * handed them back), out[3] reserved (0); all zero with the setting off or a batch without hp_tag.  The contexts of a pool are set and
+ * handed them back), out[3] those of out[0] that have more than 256 candidate reads (0 unless trgt_hip_set_size_max_reads is set too);
+ * all zero with the setting off or a batch without hp_tag.  The contexts of a pool are set and
  * asked one by one through trgt_hip_pool_context. */
 int trgt_hip_set_flank_device(trgt_hip_ctx* ctx, int on);
 int trgt_hip_flank_stats(const trgt_hip_ctx* ctx, int64_t out[4]);

@@ -185,7 +185,8 @@ class Context:
 
     def set_size_max_reads(self, n):
         """trgt_hip_set_size_max_reads: Genotyper::Size loci of up to n candidate reads stay on the device (256, the default: the one-wave
-        genotyper only; up to size_max_reads_limit(): the workgroup-wide one as well).  Every later call on this context uses it."""
+        genotyper only; up to size_max_reads_limit(): the workgroup-wide one as well, which with set_flank_device(True) also runs the
+        haplotype-tag branch of genotype_flank for these loci).  Every later call on this context uses it."""
         self.check(lib().trgt_hip_set_size_max_reads(self.handle, int(n)))
 
     def size_deep_stats(self):
@@ -197,12 +198,14 @@ class Context:
 
     def set_flank_device(self, on=True):
         """trgt_hip_set_flank_device: the haplotype-tag branch of genotype_flank (genotype_flank.rs:43-76) runs inside the device genotyper for
-        batches that carry hp_tag (off, the default: on the host path).  Every later call on this context uses it."""
+        batches that carry hp_tag (off, the default: on the host path): for loci of at most 256 candidate reads, and on a context that is
+        also set with set_size_max_reads(n) for Genotyper::Size loci of up to n reads.  Every later call on this context uses it."""
         self.check(lib().trgt_hip_set_flank_device(self.handle, int(bool(on))))
 
     def flank_stats(self):
         """trgt_hip_flank_stats of the context's last trgt_locus_batch: (loci whose genotype the device replaced by the tag split, those
-        among them with a repaired group, device-genotyped loci sent to the host path for the flank step, 0)."""
+        among them with a repaired group, device-genotyped loci sent to the host path for the flank step, those of the first count that
+        have more than 256 candidate reads -- 0 unless set_size_max_reads is set too)."""
         out = (C.c_int64 * 4)()
         self.check(lib().trgt_hip_flank_stats(self.handle, out))
         return tuple(int(v) for v in out)

@@ -680,6 +680,7 @@ struct LocusCall {
   bool is_cluster(int64_t l) const { return in->genotyper && in->genotyper[l] == 1; }
   // ga as it stands, with what the FLANK forms read beyond it
   gt::GtFlankArgs flank_args() const { gt::GtFlankArgs fa; static_cast<gt::GtArgs&>(fa) = ga; fa.hp_tag = g.hp; fa.flank_done = (uint8_t*)slab.d(o_fdone); return fa; }
+  gtd::DeepFlankArgs deep_flank_args() const { return gtd::DeepFlankArgs{ds, g.hp, (uint8_t*)slab.d(o_fdone)}; }  // the deep size list's FLANK forms (ds.c.g = ga is the caller's)
   uint64_t& cell(int w) { return ((uint64_t*)h_cells)[w]; }
   void tl(const char* name) const { if (tl_on) fprintf(stderr, "[tl] %-28s %7.2f ms  ctx=%p\n", name, (double)(now_ns() - t0) / 1e6, (void*)c); }
 
@@ -1092,7 +1093,8 @@ int LocusCall::size_genotyper() {
     //      of the purity batch, then the workgroup-wide genotyper; its loci without majority support join the repair chain below
     ds.c.g = ga;
     if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
-    hipLaunchKernelGGL(gtd::deep_size_genotype_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
+    if (flank_dev) hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<true>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_flank_args());
+    else hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<false>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
   }
   TRGT_HIP_TRY(c, hipGetLastError());
   tl_mark(c, "genotyper launched");
@@ -1172,7 +1174,11 @@ int LocusCall::repair_chain() {
   const dim3 fgrid((unsigned)nl);
   if (flank_dev) k_repair_finish_flank.launch(!small_gt, presel, fgrid, c->stream, flank_args(), fa);
   else k_repair_finish.launch(!small_gt, presel, fgrid, c->stream, ga, fa);
-  if (!gsd_list.empty()) { ds.c.g = ga; hipLaunchKernelGGL(gtd::deep_size_finish_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds, fa); }
+  if (!gsd_list.empty()) {
+    ds.c.g = ga;
+    if (flank_dev) hipLaunchKernelGGL(gtd::deep_size_finish_kernel<true>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_flank_args(), fa);
+    else hipLaunchKernelGGL(gtd::deep_size_finish_kernel<false>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds, fa);
+  }
   TRGT_HIP_TRY(c, hipGetLastError());
   if ((rc = dbg_sync("vote + finish"))) return rc;
   tl_mark(c, "repair chain enqueued");
@@ -1350,7 +1356,10 @@ int LocusCall::wait_stage_a() {
       });
       if (fdone) {  // trgt_hip_flank_stats
         for (int64_t l = 0; l < nl; ++l) {
-          if ((fdone[l] & gt::FL_DONE) && !need[l]) { c->flank_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_stats[1] += 1; }
+          if ((fdone[l] & gt::FL_DONE) && !need[l]) {
+            c->flank_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_stats[1] += 1;
+            if (in->locus_read_begin[l + 1] - in->locus_read_begin[l] > (uint64_t)gt::GT_MAX_READS) c->flank_stats[3] += 1;  // the deep size list's
+          }
           else if (fdone[l] == gt::FL_HANDED) c->flank_stats[2] += 1;
         }
         c->flank_stats[2] += sent.load();

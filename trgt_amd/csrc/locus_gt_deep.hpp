@@ -14,7 +14,12 @@
 // reductions here.  Ties as in locus_cluster_deep.hpp: every "first / last in index order" of a sequential scan is a lexicographic
 // (value, index) reduction.  The f64 penalties are those of locus_gt.hpp: one thread sums one candidate in ascending histogram order.
 // Segments are compared where they lie in the read blob; per-read state that no single thread walks stays in the global lists.
+//
+// The FLANK forms of both kernels (contexts that also opted in to trgt_hip_set_flank_device) run the haplotype-tag branch of
+// genotype_flank::genotype for a deep locus whose two sizes are at most 10 apart: flank_route / flank_finish of locus_gt.hpp restated for
+// the workgroup, see deep_flank_route.
 #pragma once
+#include <cstddef>
 #include "locus_cluster_deep.hpp"
 #include "locus_gt.hpp"
 
@@ -25,6 +30,17 @@ constexpr int GT_DEEP_MAX_READS = cld::CL_DEEP_MAX_READS;  // one ceiling: the t
 constexpr int MAXR = GT_DEEP_MAX_READS;
 using cld::DeepArgs; using cld::DT; using cld::DW; using cld::DWAVES; using cld::Red;
 using gt::adiff_u;
+
+// The arguments of the FLANK forms.  A struct of its own, like gt::GtFlankArgs: DeepArgs is the argument of every deep kernel, whose
+// register allocation follows its size.
+struct DeepFlankArgs {
+  DeepArgs d;
+  const int16_t* hp_tag;  // per read of the batch: the HP tag (-1 = None)
+  uint8_t* flank_done;    // [n_loci] gt::FL_*
+};
+template <bool FLANK> using DeepArgsOf = std::conditional_t<FLANK, DeepFlankArgs, DeepArgs>;
+__device__ __forceinline__ const DeepArgs& deep_of(const DeepArgs& a) { return a; }
+__device__ __forceinline__ const DeepArgs& deep_of(const DeepFlankArgs& a) { return a.d; }
 
 // exclusive prefix sum of x over the workgroup in thread order, and the total
 __device__ __forceinline__ uint32_t block_excl_scan_u32(uint32_t x, uint32_t& total, Red& r) {
@@ -66,8 +82,13 @@ __device__ __forceinline__ int cmp_seg_thread(const uint8_t* __restrict__ a, uin
 // workgroup.  ap / aln / civ / gsz are indexed by allele as genotyped; n_al: alleles the reads are classified against.  The tie-breaker
 // starts at 1 and flips at every tie, so the k-th tied read (k from 0) gets k & 1: a prefix count over the kept reads.  false: an allele
 // exceeds allele_cap (the host path reports the error), nothing was written.
+// TAGS (the haplotype-tag route, genotype_flank.rs:43-76): the classification is the assignment by tag instead -- tag 1 -> group 0, tag 2
+// -> group 1, the k-th other read of the kept list (k from 0) -> group k & 1, the same prefix count -- and the alleles arrive smaller one
+// first: sw = 1 says that allele 0 is tag group 1's.
+template <bool TAGS = false>
 __device__ __forceinline__ bool deep_size_write(const DeepArgs& a, int64_t l, uint64_t r0, int n, int n_gt, int n_al, const uint8_t* const ap[2],
-                                                const uint32_t aln[2], const int32_t civ[4], const uint32_t gsz[2], Red& red) {
+                                                const uint32_t aln[2], const int32_t civ[4], const uint32_t gsz[2], Red& red,
+                                                const int16_t* __restrict__ hp = nullptr, int sw = 0) {
   const gt::GtArgs& g = a.c.g;
   const int tid = threadIdx.x;
   const uint8_t* ref = g.tr_blob + g.tr_off[l]; const uint32_t refn = g.tr_len[l];
@@ -80,12 +101,16 @@ __device__ __forceinline__ bool deep_size_write(const DeepArgs& a, int64_t l, ui
     const int i = base + tid;
     const bool valid = i < n;
     uint32_t d1 = 0, d2 = 0;
-    if (valid && n_al == 2) { const uint32_t ln = a.sel_len[r0 + i]; d1 = adiff_u(ln, aln[0]); d2 = adiff_u(ln, aln[1]); }
-    const bool tie = valid && n_al == 2 && d1 == d2;
+    int tag = 0;
+    if constexpr (TAGS) { if (valid) tag = (int)hp[r0 + a.sel_read[r0 + i]]; }
+    else if (valid && n_al == 2) { const uint32_t ln = a.sel_len[r0 + i]; d1 = adiff_u(ln, aln[0]); d2 = adiff_u(ln, aln[1]); }
+    const bool tie = TAGS ? valid && tag != 1 && tag != 2 : valid && n_al == 2 && d1 == d2;
     uint32_t total;
     const uint32_t pos = ties + cld::block_rank(tie, total, red);
     if (valid) {
-      const int cc = n_al == 2 ? (d1 < d2 ? 0 : (d1 > d2 ? 1 : (int)(pos & 1u))) : 0;
+      int cc;
+      if constexpr (TAGS) cc = (tie ? (int)(pos & 1u) : tag - 1) ^ sw;
+      else cc = n_al == 2 ? (d1 < d2 ? 0 : (d1 > d2 ? 1 : (int)(pos & 1u))) : 0;
       h1 += (uint32_t)cc;
       const uint32_t rd = a.sel_read[r0 + i];
       g.classification[r0 + rd] = flip ? 1 - cc : cc;
@@ -124,8 +149,191 @@ struct DeepSize {
 };
 static_assert(sizeof(DeepSize) <= 64 * 1024, "static LDS of the deep size genotyper");
 
-__global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgs a) {
+// ---- the haplotype-tag branch of genotype_flank::genotype (genotype_flank.rs:9-76, 147-170; applied at tr.rs:69-75) for a workgroup:
+// flank_route / flank_finish of locus_gt.hpp with every lane-0 loop and wave ballot as a workgroup prefix or a (value, index) reduction.
+// Its LDS lies over DeepSize::ulen / ucnt, which are dead once the intervals are computed.
+struct DeepFlank {
+  uint16_t start[MAXR];   // per unique sequence: where its run of equal segments begins in DeepSize::ord
+  uint16_t cnt[2][MAXR];  // multiplicity of every unique sequence inside either tag group
+  uint8_t grp[MAXR];      // per kept read: its tag group
+  uint32_t med[2][2];     // the two middle lengths of either group
+};
+static_assert(sizeof(DeepFlank) <= 2 * sizeof(uint32_t) * MAXR && offsetof(DeepSize, ucnt) == offsetof(DeepSize, ulen) + sizeof(uint32_t) * MAXR &&
+              offsetof(DeepSize, ulen) % alignof(DeepFlank) == 0, "the tag route's LDS lies over ulen / ucnt");
+__device__ __forceinline__ DeepFlank& deep_flank_lds(DeepSize& sh) { return *reinterpret_cast<DeepFlank*>(static_cast<void*>(sh.ulen)); }
+
+// get_trs_with_hp (:43-76) over the kept reads in kept order: tag 1 -> group 0, tag 2 -> group 1, the k-th other read (k from 0, a running
+// count over the whole list: a workgroup prefix carried across the rounds) -> group k & 1.  true: the split is accepted (both groups
+// occur, at least 70 % of the reads tagged).  Uniform arguments, uniform result; grp is visible to every thread on return.
+__device__ __forceinline__ bool deep_flank_assign(uint8_t* grp, const DeepArgs& a, const int16_t* __restrict__ hp, uint64_t r0, int n, int cnt[2], Red& red) {
+  const int tid = threadIdx.x;
+  uint32_t untagged = 0, ones = 0;
+  for (int base = 0; base < n; base += DW) {
+    const int i = base + tid;
+    const bool valid = i < n;
+    const int tag = valid ? (int)hp[r0 + a.sel_read[r0 + i]] : 1;
+    const bool un = valid && tag != 1 && tag != 2;
+    uint32_t total;
+    const uint32_t k = untagged + cld::block_rank(un, total, red);
+    if (valid) { const uint32_t g = un ? (k & 1u) : (uint32_t)(tag - 1); grp[i] = (uint8_t)g; ones += g; }
+    untagged += total;
+  }
+  ones = cld::block_sum_u32(ones, red);
+  cnt[1] = (int)ones; cnt[0] = n - (int)ones;
+  return cnt[0] > 0 && cnt[1] > 0 && (double)(n - (int)untagged) / (double)n >= 0.7;
+}
+
+// The route inside the genotype kernel, behind the sequence histogram (ord, tmp, u_rep, u_cnt, nu final; fl.start filled).  false: the
+// tags do not split the reads and the locus continues with the length genotype.  true: the locus is settled here -- simple_consensus
+// (:147-170) of either group; without a group below 50 % the genotype is written out, else the groups join the call's repair chain
+// (need_host = 2, the FLANK finish kernel completes the locus) or the locus is handed to the host path (need_host = 1, FL_HANDED).
+__device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankArgs& fa, int64_t l, uint64_t r0, int n, int nu) {
+  const DeepArgs& a = fa.d;
+  const gt::GtArgs& g = a.c.g;
+  DeepFlank& fl = deep_flank_lds(sh);
+  const int tid = threadIdx.x;
+  constexpr int NONE = 0x7FFFFFFF;
+  int cnt[2];
+  if (!deep_flank_assign(fl.grp, a, fa.hp_tag, r0, n, cnt, sh.red)) return false;
+  // ---- multiplicities inside the groups (thread q walks the run of unique sequence q), the middle lengths of either group by rank
+  for (int q = tid; q < nu; q += DW) {
+    const int s = fl.start[q], m = sh.u_cnt[q];
+    int c1 = 0;
+    for (int r = s; r < s + m; ++r) c1 += fl.grp[sh.ord[r]];
+    fl.cnt[0][q] = (uint16_t)(m - c1); fl.cnt[1][q] = (uint16_t)c1;
+  }
+  for (int i = tid; i < n; i += DW) {
+    const uint32_t gi = fl.grp[i], li = sh.ln[i];
+    int r = 0;
+    for (int j = 0; j < n; ++j) { const uint32_t lj = sh.ln[j]; r += fl.grp[j] == gi && (lj < li || (lj == li && j < i)); }
+    const int half = (gi ? cnt[1] : cnt[0]) / 2;
+    if (r == half) fl.med[gi][1] = li;
+    if (r == half - 1) fl.med[gi][0] = li;
+  }
+  __syncthreads();
+  int rep[2] = {0, 0}; uint32_t aln[2] = {0, 0}, lo[2] = {0, 0}, hi[2] = {0, 0}; bool lacks[2] = {false, false};
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    // utils::math::median (math.rs:73-98) as f32, truncated: the middle value, or (a + b) as i32, then / 2.0
+    const float med = (cnt[t] & 1) ? (float)(int32_t)fl.med[t][1] : (float)((int32_t)fl.med[t][0] + (int32_t)fl.med[t][1]) / 2.0f;
+    const uint32_t median_len = (uint32_t)med;
+    uint32_t top = 0;
+    for (int q = tid; q < nu; q += DW) top = fl.cnt[t][q] > top ? fl.cnt[t][q] : top;
+    top = block_max_u32(top, sh.red);
+    // among the sequences with the largest multiplicity, in u_rep order: the first minimum of |len - median|
+    double bd = __builtin_huge_val(); int bq = NONE;
+    for (int q = tid; q < nu; q += DW)
+      if (fl.cnt[t][q] == top) { const double d = (double)adiff_u(sh.ln[sh.u_rep[q]], median_len); if (d < bd) { bd = d; bq = q; } }
+    cld::block_min_vi(bd, bq, sh.red);
+    uint32_t mn = 0xFFFFFFFFu, mx = 0;
+    for (int i = tid; i < n; i += DW) if (fl.grp[i] == (uint32_t)t) { const uint32_t li = sh.ln[i]; mn = li < mn ? li : mn; mx = li > mx ? li : mx; }
+    lo[t] = block_min_u32(mn, sh.red); hi[t] = block_max_u32(mx, sh.red);
+    rep[t] = sh.u_rep[bq == NONE ? 0 : bq]; aln[t] = sh.ln[rep[t]];  // (the group is not empty: some thread has a value)
+    lacks[t] = (double)top / (double)cnt[t] < 0.5;
+  }
+  if (lacks[0] || lacks[1]) {
+    // ---- a group below 50 %: backbone = its sequence, one member per read of the group in kept order, duplicates included; the
+    //      reservations are the one-wave route's, in its order
+    const gt::RepairBufs& rp = g.rp;
+    bool can = rp.counts != nullptr;
+    uint32_t nm[2] = {0, 0}, mbytes[2] = {0, 0}; unsigned long long cig[2] = {0, 0};
+    if (can) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (!lacks[t]) continue;
+        uint32_t bytes = 0, over = aln[t] > rp.max_seg;
+        for (int i = tid; i < n; i += DW) if (fl.grp[i] == (uint32_t)t) { const uint32_t li = sh.ln[i]; over += li > rp.max_seg; bytes += li > rp.max_seg ? 0u : li; }
+        nm[t] = (uint32_t)cnt[t]; mbytes[t] = cld::block_sum_u32(bytes, sh.red);
+        if (cld::block_sum_u32(over, sh.red)) can = false;
+        cig[t] = (unsigned long long)nm[t] * ((unsigned long long)aln[t] + 1) + mbytes[t];
+      }
+    }
+    unsigned long long out_need[2] = {0, 0}, scr_need[2] = {0, 0};
+    uint32_t out_cap[2] = {0, 0};
+    if (can) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (!lacks[t]) continue;
+        out_cap[t] = (uint32_t)(aln[t] + mbytes[t] + 16);
+        out_need[t] = ((unsigned long long)out_cap[t] + 15ull) & ~15ull;
+        scr_need[t] = (aln[t] + 1 <= rp.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)aln[t] + 1)) + 3ull * nm[t];
+      }
+      if (tid == 0) {  // cigar words, result bytes and vote scratch first: a failed reservation must not leave holes in the job list
+        const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
+        int ok = 1;
+        unsigned long long c0 = 0, o0 = 0, s0 = 0;
+        c0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_CIGAR), cn);
+        if (c0 + cn > rp.cap_cigar) ok = 0;
+        if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_OUT), on); if (o0 + on > rp.cap_out) ok = 0; }
+        if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_SCRATCH), sn); if (s0 + sn > rp.cap_scratch) ok = 0; }
+        if (ok) {
+          sh.rp_j0 = atomicAdd(rp.counts + gt::RC_JOBS, nm[0] + nm[1]);
+          sh.rp_g0 = atomicAdd(rp.counts + gt::RC_GROUPS, (uint32_t)lacks[0] + (uint32_t)lacks[1]);
+          if (sh.rp_j0 + nm[0] + nm[1] > rp.cap_jobs || sh.rp_g0 + 2 > rp.cap_groups) ok = 0;  // (cannot happen: the caps are the read and locus counts)
+          else { const uint32_t slot = atomicAdd(rp.counts + gt::RC_LOCI, 1u); if (slot < (uint32_t)g.n_loci) rp.loci[slot] = (uint32_t)l; else ok = 0; }
+        } else atomicAdd(rp.counts + gt::RC_FAILED, 1u);
+        sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
+      }
+      __syncthreads();
+      can = sh.rp_ok != 0;
+    }
+    if (!can) { if (tid == 0) { g.need_host[l] = 1; fa.flank_done[l] = gt::FL_HANDED; } return true; }
+    uint32_t gi = sh.rp_g0, j = sh.rp_j0;
+    unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
+    gt::RepairPend pd;
+    pd.n_gt = 2; pd.n_pick = 2 | gt::RP_FLANK; pd.size[0] = aln[0]; pd.size[1] = aln[1];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) { pd.civ[2 * t] = (int32_t)lo[t]; pd.civ[2 * t + 1] = (int32_t)hi[t]; pd.rep[t] = rep[t]; pd.grp[t] = -1; }
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      if (!lacks[t]) continue;
+      const unsigned long long bb_off = sh.off[rep[t]];
+      const uint32_t bb = aln[t];
+      if (tid == 0) {
+        gt::RGroup G;
+        G.job_first = j; G.n_members = nm[t]; G.bb_len = bb; G.out_cap = out_cap[t];
+        G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
+        rp.groups[gi] = G;
+      }
+      pd.grp[t] = (int32_t)gi;
+      // job k of the group is its k-th read in kept order; its CIGAR slot starts behind those of the reads before it (aln + len + 1 words each)
+      uint32_t k0 = 0; unsigned long long b0 = 0;
+      for (int base = 0; base < n; base += DW) {
+        const int i = base + tid;
+        const bool in = i < n && fl.grp[i] == (uint32_t)t;
+        const uint32_t ln = in ? sh.ln[i] : 0u;
+        uint32_t tk, tb;
+        const uint32_t kk = k0 + cld::block_rank(in, tk, sh.red);
+        const unsigned long long before = b0 + block_excl_scan_u32(ln, tb, sh.red);
+        if (in) {
+          JobDev jd;
+          jd.pat_off = bb_off; jd.pat_len = bb;
+          jd.txt_off = sh.off[i]; jd.txt_len = ln;
+          jd.cigar_off = co + (unsigned long long)kk * ((unsigned long long)bb + 1) + before; jd.ops_off = 0; jd.out_index = j + kk; jd.pad = 0;
+          rp.jobs[j + kk] = jd;
+        }
+        k0 += tk; b0 += tb;
+      }
+      co += cig[t]; j += nm[t]; oo += out_need[t]; so += scr_need[t]; ++gi;
+    }
+    if (tid == 0) { rp.pend[l] = pd; g.need_host[l] = 2; }  // the locus waits for the FLANK form of deep_size_finish_kernel
+    return true;
+  }
+  // ---- both groups have their sequence: smaller allele first (:33-38: alleles and intervals swap, the assignment flips), the
+  //      assignment is the classification, then reference allele first (tr.rs:95-101): deep_size_write<TAGS>
+  const int sw = aln[0] > aln[1] ? 1 : 0;
+  const uint8_t* ap[2] = {g.reads + sh.off[sw ? rep[1] : rep[0]], g.reads + sh.off[sw ? rep[0] : rep[1]]};
+  const uint32_t al2[2] = {sw ? aln[1] : aln[0], sw ? aln[0] : aln[1]};
+  const int32_t civ[4] = {(int32_t)(sw ? lo[1] : lo[0]), (int32_t)(sw ? hi[1] : hi[0]), (int32_t)(sw ? lo[0] : lo[1]), (int32_t)(sw ? hi[0] : hi[1])};
+  const bool ok = deep_size_write<true>(a, l, r0, n, 2, 2, ap, al2, civ, al2, sh.red, fa.hp_tag, sw);
+  if (tid == 0) { g.need_host[l] = ok ? 0 : 1; fa.flank_done[l] = ok ? gt::FL_DONE : gt::FL_HANDED; }  // (an allele beyond allele_cap: the host path reports the error)
+  return true;
+}
+
+template <bool FLANK = false>
+__global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgsOf<FLANK> aa) {
   __shared__ DeepSize sh;
+  const DeepArgs& a = deep_of(aa);
   const uint32_t k = blockIdx.x;
   if (k >= a.c.n_list) return;
   const gt::GtArgs& g = a.c.g;
@@ -244,9 +452,15 @@ __global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgs a
     uint32_t total;
     const uint32_t q = (uint32_t)nu + cld::block_rank(first, total, sh.red);
     if (first) { sh.u_rep[q] = (uint16_t)i; sh.u_cnt[q] = (uint16_t)(sh.tmp[i] & 0x7FFFFFFFu); }
+    if constexpr (FLANK) { if (first) deep_flank_lds(sh).start[q] = (uint16_t)r; }
     nu += (int)total;
   }
   __syncthreads();
+  // ---- FLANK: two sizes at most 10 apart (tr.rs:69-75) and tags that split the reads replace everything below; the size genotyper's
+  //      own repair is not queued for such a locus
+  if constexpr (FLANK) {
+    if (aa.hp_tag && n_gt == 2 && adiff_u(size[0], size[1]) <= 10 && deep_flank_route(sh, aa, l, r0, n, nu)) return;
+  }
   auto ulen_of = [&](int q) { return sh.ln[sh.u_rep[q]]; };
   // get_closest_len: the first length in sequence order at the smallest distance
   auto closest = [&](uint32_t target) {
@@ -391,8 +605,10 @@ __global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgs a
 // ---- behind the consensus alignments and the column voting: the rest of genotype_size::genotype for the loci of the deep size list that
 // wait for a repair (need_host = 2; they are in rp.loci too, where repair_finish_kernel passes them over by their read count).  A locus
 // whose repaired allele does not fit (vote overflow, allele_cap) goes to the host path after all.
-__global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgs a, const gt::FinishArgs f) {
+template <bool FLANK = false>
+__global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgsOf<FLANK> aa, const gt::FinishArgs f) {
   __shared__ Red red;
+  const DeepArgs& a = deep_of(aa);
   const uint32_t k = blockIdx.x;
   if (k >= a.c.n_list) return;
   const gt::GtArgs& g = a.c.g;
@@ -407,6 +623,39 @@ __global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgs a, 
   const int n = min((int)a.n_sel[k], min(nr, MAXR));
   const gt::RepairPend pd = rp.pend[l];
   const int ploidy = g.ploidy[l] == 1 ? 1 : 2;
+  if constexpr (FLANK) {
+    // ... of a locus the haplotype-tag route left waiting (RP_FLANK): the alleles are the repaired sequences or the backbones of the tag
+    // groups, smaller allele first (genotype_flank.rs:33-38); deep_size_write<TAGS> recomputes the assignment from the tags (deterministic
+    // from the same list of kept reads), which is the classification; its counts are num_spanning, the sizes are the allele lengths
+    if (pd.n_pick & gt::RP_FLANK) {
+      const uint8_t* tp[2] = {nullptr, nullptr}; uint32_t tl[2] = {0, 0};
+      bool bad = n == 0;
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        if (bad) break;
+        if (pd.grp[t] >= 0) {
+          const uint32_t len = f.vote_len[pd.grp[t]];
+          if (len == 0xFFFFFFFFu) { bad = true; break; }
+          tp[t] = f.vote_out + rp.groups[pd.grp[t]].out_off; tl[t] = len;
+        } else {
+          const int rep = pd.rep[t];
+          tp[t] = g.reads + cld::seg_off(a, r0, rep); tl[t] = a.sel_len[r0 + rep];
+        }
+      }
+      if (!bad) {
+        const int sw = tl[0] > tl[1] ? 1 : 0;
+        const uint8_t* sp[2] = {sw ? tp[1] : tp[0], sw ? tp[0] : tp[1]};
+        const uint32_t sl[2] = {sw ? tl[1] : tl[0], sw ? tl[0] : tl[1]};
+        const int32_t sc[4] = {sw ? pd.civ[2] : pd.civ[0], sw ? pd.civ[3] : pd.civ[1], sw ? pd.civ[0] : pd.civ[2], sw ? pd.civ[1] : pd.civ[3]};
+        bad = !deep_size_write<true>(a, l, r0, n, 2, 2, sp, sl, sc, sl, red, aa.hp_tag, sw);
+      }
+      if (tid == 0) {
+        if (bad) { g.need_host[l] = 1; aa.flank_done[l] = gt::FL_HANDED; }
+        else { g.skip_b[l] = 0; if (g.finish_clears_need) g.need_host[l] = 0; aa.flank_done[l] = gt::FL_DONE | gt::FL_REPAIRED; }
+      }
+      return;
+    }
+  }
   // the alleles: the repaired sequence of a group, or the pick that had majority support
   const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
   bool fail = n == 0;

@@ -17,7 +17,8 @@ from . import _lib, locus
 
 
 class ChunkDriver:
-    """devices: one entry per context (ordinals may repeat: several contexts on one GPU).  cluster_max_reads, size_max_reads, flank_device: passed to every context."""
+    """devices: one entry per context (ordinals may repeat: several contexts on one GPU).  cluster_max_reads, size_max_reads, flank_device: passed to every context
+    (size_max_reads and flank_device combine: deep size loci of a haplotagged batch then run the tag branch of genotype_flank on the device)."""
 
     def __init__(self, devices=(0,), params=None, context_factory=None, run_fn=None, cluster_max_reads=None, size_max_reads=None, flank_device=None):
         self.params = params or locus.Params()
