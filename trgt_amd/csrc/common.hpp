@@ -87,6 +87,7 @@ struct trgt_knobs {
   bool hmm_four_rounds = false;  // TRGT_HMM_FOUR_ROUNDS: the register fill fetches across lanes once per pass of a column (four rounds) instead of twice per column
   bool hmm_lds_fill = false;  // TRGT_HMM_LDS_FILL: one-wave motif sets fill their Viterbi columns through LDS like the larger ones (not in registers)
   int cluster_arena_kb = 0;  // TRGT_CLUSTER_ARENA_KB: developer switch -- the CIGAR / result / scratch arenas of the device-side cluster genotyper capped at this many KB (loci that find no room take the host path: the mixed case of the tests)
+  int repair_arena_kb = 0;   // TRGT_REPAIR_ARENA_KB: the same for the arenas of the repair chain of the size and haplotype-tag routes (RepairBufs)
   bool host_cluster = false; // TRGT_HOST_CLUSTER: Genotyper::Cluster loci take the host path (linkage, groups and round sequencing on host threads, locus_cluster.hpp)
   bool host_purity = false;  // TRGT_HOST_PURITY (DEV): calls with filter_impure_trs on (min_read_qual < 0.9) send every locus down the host path, as until the filter ran on the device (locus_purity.hpp)
   bool host_repair = false;  // TRGT_HOST_REPAIR: loci whose pick lacks majority support go back to the host (no device-side consensus repair)

@@ -1002,6 +1002,10 @@ int LocusCall::repair_buffers() {
     rp.cap_cigar = std::min<uint64_t>((uint64_t)nr * (2ull * rp.max_seg + 1), 32ull << 20);       // words
     rp.cap_out = std::min<uint64_t>((uint64_t)nr * (rp.max_seg + 16ull) + 64, 256ull << 20);      // bytes
     rp.cap_scratch = std::min<uint64_t>(3ull * (uint64_t)nr + 3ull * (uint64_t)rp.cap_groups * (rp.max_seg + 1ull) + 64, 32ull << 20);  // words
+    if (c->knobs.repair_arena_kb > 0) {
+      const uint64_t kb = (uint64_t)c->knobs.repair_arena_kb;
+      rp.cap_cigar = std::min<uint64_t>(rp.cap_cigar, kb * 256); rp.cap_out = std::min<uint64_t>(rp.cap_out, kb * 1024); rp.cap_scratch = std::min<uint64_t>(rp.cap_scratch, kb * 256);
+    }
     void *d_g = nullptr, *d_j = nullptr, *d_l = nullptr, *d_p = nullptr;
     if ((rc = dev_get(c, S_RP_GROUPS, (size_t)rp.cap_groups * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, S_RP_JOBS, (size_t)rp.cap_jobs * sizeof(JobDev), &d_j)) ||
         (rc = dev_get(c, S_RP_LOCI, (size_t)nl * 4, &d_l)) || (rc = dev_get(c, S_RP_PEND, (size_t)nl * sizeof(gt::RepairPend), &d_p)) ||

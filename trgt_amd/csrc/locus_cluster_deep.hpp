@@ -11,7 +11,8 @@
 //   deep_filter_kernel    tr.rs:438-448 on that list (behind the purity-only HMM batch of locus.hip, which is shared with the shallow loci)
 //   deep_front_kernel     pair list / length differences (get_dist_matrix :250-286)           -> the score-only BiWFA launch
 //   deep_linkage_kernel   Ward linkage, Muellner's NN-chain with in-place Lance-Williams updates; the merges go to global memory
-//   deep_groups_kernel    stable sort of the merges, SciPy labels, cut-off, groups, backbones, consensus jobs -> BiWFA launch + votes
+//   deep_groups_kernel    stable sort of the merges, SciPy labels, cut-off, groups, backbones, consensus jobs (reserved and written by
+//                         repair_queue.hpp, as in every chain) -> BiWFA launch + votes
 //   deep_round2_kernel    small_group_is_outlier and the even / odd redo, dropped reads against both alleles -> second round
 //   deep_finish_kernel    classifications, allele order, reference allele first, outputs
 // The matrix lives in HBM (ClArgs::gmat); per-read state that the one-wave kernels keep in LDS structs is in LDS where a single thread
@@ -366,7 +367,7 @@ struct DeepGroups {
   int8_t cls[CL_DEEP_MAX_READS];
   uint32_t ln[CL_DEEP_MAX_READS];
   Red red;
-  int rp_ok; uint32_t rp_g0, rp_j0; unsigned long long rp_c0, rp_o0, rp_s0;
+  gt::Reserved rsv;  // (ok: also the size of the group at hand)
 };
 // central_read (:12-39) as central_read_wave: every member's sum in the reference's order, the first minimum over the members
 __device__ __forceinline__ int central_read_block(const double* D, uint32_t n, const uint16_t* gm, int cnt, Red& red) {
@@ -477,9 +478,9 @@ __global__ void __launch_bounds__(DW) deep_groups_kernel(const DeepArgs a) {
   unsigned long long mbytes[2] = {0, 0};
   for (int g = 0; g < n_groups; ++g) {
     __syncthreads();
-    if (tid == 0) { int c = 0; for (int i = 0; i < n; ++i) if (sh.cls[i] == g) sh.gm[c++] = (uint16_t)i; sh.rp_ok = c; }
+    if (tid == 0) { int c = 0; for (int i = 0; i < n; ++i) if (sh.cls[i] == g) sh.gm[c++] = (uint16_t)i; sh.rsv.ok = c; }
     __syncthreads();
-    gcnt[g] = sh.rp_ok;
+    gcnt[g] = sh.rsv.ok;
     bb[g] = central_read_block(D, un, sh.gm, gcnt[g], sh.red);
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
     for (int q = 0; q < gcnt[g]; ++q) { const uint32_t ln = sh.ln[sh.gm[q]]; lo = ln < lo ? ln : lo; hi = ln > hi ? ln : hi; mbytes[g] += ln; }
@@ -488,70 +489,28 @@ __global__ void __launch_bounds__(DW) deep_groups_kernel(const DeepArgs a) {
   if (!one_group && n >= 3) {  // the even / odd split, should round 2 ask for it
     for (int g = 0; g < 2; ++g) {
       __syncthreads();
-      if (tid == 0) { int c = 0; for (int i = g; i < n; i += 2) sh.gm[c++] = (uint16_t)i; sh.rp_ok = c; }
+      if (tid == 0) { int c = 0; for (int i = g; i < n; i += 2) sh.gm[c++] = (uint16_t)i; sh.rsv.ok = c; }
       __syncthreads();
-      rec.cr_eo[g] = central_read_block(D, un, sh.gm, sh.rp_ok, sh.red);
+      rec.cr_eo[g] = central_read_block(D, un, sh.gm, sh.rsv.ok, sh.red);
       uint32_t lo = 0xFFFFFFFFu, hi = 0;
       for (int i = g; i < n; i += 2) { const uint32_t ln = sh.ln[i]; lo = ln < lo ? ln : lo; hi = ln > hi ? ln : hi; }
       rec.ci_eo[2 * g] = lo; rec.ci_eo[2 * g + 1] = hi;
     }
   }
-  // reservations: CIGAR words, result bytes and vote scratch first (a failed reservation must not leave holes in the job list)
-  unsigned long long cig[2] = {0, 0}, out_need[2] = {0, 0}, scr_need[2] = {0, 0};
-  uint32_t out_cap[2] = {0, 0};
-  for (int g = 0; g < n_groups; ++g) {
-    const uint32_t bl = sh.ln[bb[g]];
-    cig[g] = (unsigned long long)gcnt[g] * ((unsigned long long)bl + 1) + mbytes[g];
-    out_cap[g] = (uint32_t)(bl + mbytes[g] + 16);
-    out_need[g] = ((unsigned long long)out_cap[g] + 15ull) & ~15ull;
-    scr_need[g] = (bl + 1 <= a.c.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)bl + 1)) + 3ull * (unsigned long long)gcnt[g];
-  }
+  gt::GroupNeeds nd[2] = {};
+#pragma unroll
+  for (int g = 0; g < 2; ++g) if (g < n_groups) nd[g] = gt::group_needs(sh.ln[bb[g]], (uint32_t)gcnt[g], mbytes[g], a.c.vote_lds_pos);
   __syncthreads();
-  if (tid == 0) {
-    const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
-    int ok = 1;
-    unsigned long long c0 = 0, o0 = 0, s0 = 0;
-    c0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.c.counts + cl::CC_CIGAR), cn);
-    if (c0 + cn > a.c.cap_cigar) ok = 0;
-    if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.c.counts + cl::CC_OUT), on); if (o0 + on > a.c.cap_out) ok = 0; }
-    if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.c.counts + cl::CC_SCRATCH), sn); if (s0 + sn > a.c.cap_scratch) ok = 0; }
-    if (ok) {
-      sh.rp_j0 = atomicAdd(a.c.counts + cl::CC_J1, (uint32_t)(gcnt[0] + gcnt[1]));
-      sh.rp_g0 = atomicAdd(a.c.counts + cl::CC_G1, (uint32_t)n_groups);
-    } else atomicAdd(a.c.counts + cl::CC_FAILED, 1u);
-    sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
-  }
+  if (tid == 0) cl::cluster_reserve(a.c, false, (uint32_t)(gcnt[0] + gcnt[1]), (uint32_t)n_groups, nd, sh.rsv);
   __syncthreads();
-  if (!sh.rp_ok) { rec.state = -1; if (tid == 0) a.c.rec[k] = rec; return; }
-  {
-    uint32_t g_at = sh.rp_g0, j_at = sh.rp_j0;
-    unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
-    for (int g = 0; g < n_groups; ++g) {
-      const int b = bb[g];
-      const unsigned long long bb_off = seg_off(a, r0, b);
-      const uint32_t bl = sh.ln[b];
-      if (tid == 0) {
-        gt::RGroup G;
-        G.job_first = j_at; G.n_members = (uint32_t)gcnt[g]; G.bb_len = bl; G.out_cap = out_cap[g];
-        G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
-        a.c.groups[g_at] = G;
-      }
-      rec.grp[g] = (int32_t)g_at; rec.gsize[g] = gcnt[g];
-      uint32_t q = 0;
-      for (int i = 0; i < n; ++i) {
-        if (sh.cls[i] != g) continue;
-        if ((int)(q & (uint32_t)(DW - 1)) == tid) {
-          JobDev jd;
-          jd.pat_off = bb_off; jd.pat_len = bl;
-          jd.txt_off = seg_off(a, r0, i); jd.txt_len = sh.ln[i];
-          jd.cigar_off = co; jd.ops_off = 0; jd.out_index = j_at + q; jd.pad = 0;
-          a.c.jobs[j_at + q] = jd;
-        }
-        co += (unsigned long long)bl + sh.ln[i] + 1;
-        ++q;
-      }
-      j_at += (uint32_t)gcnt[g]; oo += out_need[g]; so += scr_need[g]; ++g_at;
-    }
+  if (!sh.rsv.ok) { rec.state = -1; if (tid == 0) a.c.rec[k] = rec; return; }
+  gt::Reserved at = sh.rsv;
+  auto seg_of = [&](int i) { return gt::Seg{seg_off(a, r0, i), sh.ln[i]}; };
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    if (g >= n_groups) break;
+    rec.grp[g] = (int32_t)gt::queue_group<DW>(a.c.groups, a.c.jobs, at, seg_of(bb[g]), (uint32_t)gcnt[g], nd[g], n, [&, g](int i) { return sh.cls[i] == g; }, seg_of);
+    rec.gsize[g] = gcnt[g];
   }
   rec.n_groups = n_groups;
   for (int q = 0; q < 4; ++q) rec.ci[q] = ci[q];
@@ -560,7 +519,7 @@ __global__ void __launch_bounds__(DW) deep_groups_kernel(const DeepArgs a) {
 }
 
 // ---- 5. behind the first consensus round: the homozygous redo, or the dropped reads against both alleles
-struct DeepRound2 { uint32_t ln[CL_DEEP_MAX_READS]; int ok; uint32_t g0, j0; unsigned long long c0, o0, s0; };
+struct DeepRound2 { uint32_t ln[CL_DEEP_MAX_READS]; gt::Reserved rsv; };
 __global__ void __launch_bounds__(DW) deep_round2_kernel(const DeepArgs a) {
   __shared__ DeepRound2 sh;
   const uint32_t k = blockIdx.x;
@@ -581,56 +540,20 @@ __global__ void __launch_bounds__(DW) deep_round2_kernel(const DeepArgs a) {
   const uint32_t cmin = c1 < c2 ? c1 : c2, cmax = c1 < c2 ? c2 : c1;
   if ((l1 > l2 ? l1 - l2 : l2 - l1) < 100u && cmin * 4u < cmax) {  // small_group_is_outlier (:84-98): redo the homozygous case
     int gcnt[2] = {(n + 1) / 2, n / 2};
-    unsigned long long cig[2], out_need[2], scr_need[2], mbytes[2] = {0, 0};
-    uint32_t out_cap[2];
+    unsigned long long mbytes[2] = {0, 0};
     for (int i = 0; i < n; ++i) mbytes[i & 1] += sh.ln[i];
-    for (int g = 0; g < 2; ++g) {
-      const uint32_t bl = sh.ln[rec.cr_eo[g]];
-      cig[g] = (unsigned long long)gcnt[g] * ((unsigned long long)bl + 1) + mbytes[g];
-      out_cap[g] = (uint32_t)(bl + mbytes[g] + 16);
-      out_need[g] = ((unsigned long long)out_cap[g] + 15ull) & ~15ull;
-      scr_need[g] = (bl + 1 <= a.c.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)bl + 1)) + 3ull * (unsigned long long)gcnt[g];
-    }
-    if (tid == 0) {
-      const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
-      int ok = 1;
-      unsigned long long c0 = 0, o0 = 0, s0 = 0;
-      c0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.c.counts + cl::CC_CIGAR), cn);
-      if (c0 + cn > a.c.cap_cigar) ok = 0;
-      if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.c.counts + cl::CC_OUT), on); if (o0 + on > a.c.cap_out) ok = 0; }
-      if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.c.counts + cl::CC_SCRATCH), sn); if (s0 + sn > a.c.cap_scratch) ok = 0; }
-      if (ok) { sh.j0 = atomicAdd(a.c.counts + cl::CC_J2, (uint32_t)n); sh.g0 = atomicAdd(a.c.counts + cl::CC_G2, 2u); }
-      else atomicAdd(a.c.counts + cl::CC_FAILED, 1u);
-      sh.ok = ok; sh.c0 = c0; sh.o0 = o0; sh.s0 = s0;
-    }
+    gt::GroupNeeds nd[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) nd[g] = gt::group_needs(sh.ln[rec.cr_eo[g]], (uint32_t)gcnt[g], mbytes[g], a.c.vote_lds_pos);
+    if (tid == 0) cl::cluster_reserve(a.c, true, (uint32_t)n, 2u, nd, sh.rsv);
     __syncthreads();
-    if (!sh.ok) { rec.state = -1; if (tid == 0) a.c.rec[k] = rec; return; }
-    uint32_t g_at = a.c.cap_g + sh.g0, j_at = a.c.cap_j + sh.j0;
-    unsigned long long co = sh.c0, oo = sh.o0, so = sh.s0;
+    if (!sh.rsv.ok) { rec.state = -1; if (tid == 0) a.c.rec[k] = rec; return; }
+    gt::Reserved at = sh.rsv;
+    auto seg_of = [&](int i) { return gt::Seg{seg_off(a, r0, i), sh.ln[i]}; };
+#pragma unroll
     for (int g = 0; g < 2; ++g) {
-      const int b = rec.cr_eo[g];
-      const unsigned long long bb_off = seg_off(a, r0, b);
-      const uint32_t bl = sh.ln[b];
-      if (tid == 0) {
-        gt::RGroup G;
-        G.job_first = j_at; G.n_members = (uint32_t)gcnt[g]; G.bb_len = bl; G.out_cap = out_cap[g];
-        G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
-        a.c.groups[g_at] = G;
-      }
-      rec.grp[g] = (int32_t)g_at; rec.gsize[g] = gcnt[g];
-      uint32_t q = 0;
-      for (int i = g; i < n; i += 2) {
-        if ((int)(q & (uint32_t)(DW - 1)) == tid) {
-          JobDev jd;
-          jd.pat_off = bb_off; jd.pat_len = bl;
-          jd.txt_off = seg_off(a, r0, i); jd.txt_len = sh.ln[i];
-          jd.cigar_off = co; jd.ops_off = 0; jd.out_index = j_at + q; jd.pad = 0;
-          a.c.jobs[j_at + q] = jd;
-        }
-        co += (unsigned long long)bl + sh.ln[i] + 1;
-        ++q;
-      }
-      j_at += (uint32_t)gcnt[g]; oo += out_need[g]; so += scr_need[g]; ++g_at;
+      rec.grp[g] = (int32_t)gt::queue_group<DW>(a.c.groups, a.c.jobs, at, seg_of(rec.cr_eo[g]), (uint32_t)gcnt[g], nd[g], n, [g](int i) { return (i & 1) == g; }, seg_of);
+      rec.gsize[g] = gcnt[g];
     }
     rec.redo = 1;
     for (int q = 0; q < 4; ++q) rec.ci[q] = rec.ci_eo[q];

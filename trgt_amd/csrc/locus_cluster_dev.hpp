@@ -6,7 +6,7 @@
 //                                                      difference beyond MAX_OPS) -> ONE score-only BiWFA launch for all loci
 //   cluster (:154-227)                                 cluster_ward_kernel: Ward linkage (kodama 0.3.0: Muellner's NN-chain, in-place
 //                                                      Lance-Williams updates, stable sort, SciPy labels), cut-off, groups
-//   central_read (:12-39), make_consensus (:41-56)     the same kernel: backbone per group, consensus jobs + vote groups
+//   central_read (:12-39), make_consensus (:41-56)     the same kernel: backbone per group, consensus jobs + vote groups (repair_queue.hpp)
 //                                                      -> BiWFA launch (utils::align) + consensus_vote_kernel (repair_consensus)
 //   small_group_is_outlier + the homozygous redo       cluster_round2_kernel (second, usually empty, consensus round)
 //     (:84-115), outlier reads (:117-142)              and the edit distances of the reads cluster() dropped to both alleles
@@ -57,6 +57,14 @@ struct ClArgs {
   uint64_t cap_cigar, cap_out, cap_scratch; uint32_t vote_lds_pos;
   uint32_t flags;  // tools/unpinned_sensitivity.py: 1 = nearest-neighbour ties to the last candidate, 2 = Lance-Williams summed in another order
 };
+
+// One thread reserves what the (at most two) groups of a locus take in a consensus round (repair_queue.hpp): the arenas, then nj jobs
+// and ng vote groups of that round's lists -- round 1 from 0, round 2 from cap_j / cap_g.
+__device__ __forceinline__ void cluster_reserve(const ClArgs& a, bool round2, uint32_t nj, uint32_t ng, const gt::GroupNeeds (&nd)[2], gt::Reserved& r) {
+  if (!gt::reserve_arenas(a.counts + CC_CIGAR, a.counts + CC_OUT, a.counts + CC_SCRATCH, a.cap_cigar, a.cap_out, a.cap_scratch, nd, r)) { atomicAdd(a.counts + CC_FAILED, 1u); return; }
+  r.j0 = (round2 ? a.cap_j : 0u) + atomicAdd(a.counts + (round2 ? CC_J2 : CC_J1), nj);
+  r.g0 = (round2 ? a.cap_g : 0u) + atomicAdd(a.counts + (round2 ? CC_G2 : CC_G1), ng);
+}
 
 template <int MAXR>
 struct ClFront {
@@ -150,7 +158,7 @@ struct ClWard {
   int16_t gsz[MAXR];
   int8_t cls[MAXR];
   int16_t gm[MAXR];  // members of the group at hand
-  int rp_ok; uint32_t rp_g0, rp_j0; unsigned long long rp_c0, rp_o0, rp_s0;
+  gt::Reserved rsv;  // (ok: also the size of the group at hand)
   alignas(16) double mat[LDS_MAT ? MAXR * (MAXR - 1) / 2 : 1];
 };
 
@@ -345,9 +353,9 @@ __global__ void __launch_bounds__(64) cluster_ward_kernel(const ClArgs a) {
   unsigned long long mbytes[2] = {0, 0};
   for (int g = 0; g < n_groups; ++g) {
     __syncthreads();
-    if (lane == 0) { int c = 0; for (int i = 0; i < n; ++i) if (sh.cls[i] == g) sh.gm[c++] = (int16_t)i; sh.rp_ok = c; }
+    if (lane == 0) { int c = 0; for (int i = 0; i < n; ++i) if (sh.cls[i] == g) sh.gm[c++] = (int16_t)i; sh.rsv.ok = c; }
     __syncthreads();
-    gcnt[g] = sh.rp_ok;
+    gcnt[g] = sh.rsv.ok;
     bb[g] = central_read_wave<MAXR>(D, un, sh.gm, gcnt[g], lane);
     uint32_t lo = 0xFFFFFFFFu, hi = 0;
     for (int q = 0; q < gcnt[g]; ++q) { const uint32_t ln = sh.f.s_len[sh.gm[q]]; lo = ln < lo ? ln : lo; hi = ln > hi ? ln : hi; mbytes[g] += ln; }
@@ -356,70 +364,28 @@ __global__ void __launch_bounds__(64) cluster_ward_kernel(const ClArgs a) {
   if (!one_group && n >= 3) {  // the even / odd split, should round 2 ask for it
     for (int g = 0; g < 2; ++g) {
       __syncthreads();
-      if (lane == 0) { int c = 0; for (int i = g; i < n; i += 2) sh.gm[c++] = (int16_t)i; sh.rp_ok = c; }
+      if (lane == 0) { int c = 0; for (int i = g; i < n; i += 2) sh.gm[c++] = (int16_t)i; sh.rsv.ok = c; }
       __syncthreads();
-      rec.cr_eo[g] = central_read_wave<MAXR>(D, un, sh.gm, sh.rp_ok, lane);
+      rec.cr_eo[g] = central_read_wave<MAXR>(D, un, sh.gm, sh.rsv.ok, lane);
       uint32_t lo = 0xFFFFFFFFu, hi = 0;
       for (int i = g; i < n; i += 2) { const uint32_t ln = sh.f.s_len[i]; lo = ln < lo ? ln : lo; hi = ln > hi ? ln : hi; }
       rec.ci_eo[2 * g] = lo; rec.ci_eo[2 * g + 1] = hi;
     }
   }
-  // reservations: CIGAR words, result bytes and vote scratch first (a failed reservation must not leave holes in the job list)
-  unsigned long long cig[2] = {0, 0}, out_need[2] = {0, 0}, scr_need[2] = {0, 0};
-  uint32_t out_cap[2] = {0, 0};
-  for (int g = 0; g < n_groups; ++g) {
-    const uint32_t bl = sh.f.s_len[bb[g]];
-    cig[g] = (unsigned long long)gcnt[g] * ((unsigned long long)bl + 1) + mbytes[g];
-    out_cap[g] = (uint32_t)(bl + mbytes[g] + 16);
-    out_need[g] = ((unsigned long long)out_cap[g] + 15ull) & ~15ull;
-    scr_need[g] = (bl + 1 <= a.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)bl + 1)) + 3ull * (unsigned long long)gcnt[g];
-  }
+  gt::GroupNeeds nd[2] = {};
+#pragma unroll
+  for (int g = 0; g < 2; ++g) if (g < n_groups) nd[g] = gt::group_needs(sh.f.s_len[bb[g]], (uint32_t)gcnt[g], mbytes[g], a.vote_lds_pos);
   __syncthreads();
-  if (lane == 0) {
-    const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
-    int ok = 1;
-    unsigned long long c0 = 0, o0 = 0, s0 = 0;
-    c0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.counts + CC_CIGAR), cn);
-    if (c0 + cn > a.cap_cigar) ok = 0;
-    if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.counts + CC_OUT), on); if (o0 + on > a.cap_out) ok = 0; }
-    if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.counts + CC_SCRATCH), sn); if (s0 + sn > a.cap_scratch) ok = 0; }
-    if (ok) {
-      sh.rp_j0 = atomicAdd(a.counts + CC_J1, (uint32_t)(gcnt[0] + gcnt[1]));
-      sh.rp_g0 = atomicAdd(a.counts + CC_G1, (uint32_t)n_groups);
-    } else atomicAdd(a.counts + CC_FAILED, 1u);
-    sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
-  }
+  if (lane == 0) cluster_reserve(a, false, (uint32_t)(gcnt[0] + gcnt[1]), (uint32_t)n_groups, nd, sh.rsv);
   __syncthreads();
-  if (!sh.rp_ok) { rec.state = -1; if (lane == 0) a.rec[k] = rec; return; }
-  {
-    uint32_t g_at = sh.rp_g0, j_at = sh.rp_j0;
-    unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
-    for (int g = 0; g < n_groups; ++g) {
-      const int b = bb[g];
-      const unsigned long long bb_off = sh.f.r_off[sh.f.s_read[b]] + sh.f.s_start[b];
-      const uint32_t bl = sh.f.s_len[b];
-      if (lane == 0) {
-        gt::RGroup G;
-        G.job_first = j_at; G.n_members = (uint32_t)gcnt[g]; G.bb_len = bl; G.out_cap = out_cap[g];
-        G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
-        a.groups[g_at] = G;
-      }
-      rec.grp[g] = (int32_t)g_at; rec.gsize[g] = gcnt[g];
-      uint32_t q = 0;
-      for (int i = 0; i < n; ++i) {
-        if (sh.cls[i] != g) continue;
-        if ((int)(q & 63u) == lane) {
-          JobDev jd;
-          jd.pat_off = bb_off; jd.pat_len = bl;
-          jd.txt_off = sh.f.r_off[sh.f.s_read[i]] + sh.f.s_start[i]; jd.txt_len = sh.f.s_len[i];
-          jd.cigar_off = co; jd.ops_off = 0; jd.out_index = j_at + q; jd.pad = 0;
-          a.jobs[j_at + q] = jd;
-        }
-        co += (unsigned long long)bl + sh.f.s_len[i] + 1;
-        ++q;
-      }
-      j_at += (uint32_t)gcnt[g]; oo += out_need[g]; so += scr_need[g]; ++g_at;
-    }
+  if (!sh.rsv.ok) { rec.state = -1; if (lane == 0) a.rec[k] = rec; return; }
+  gt::Reserved at = sh.rsv;
+  auto seg_of = [&](int i) { return gt::Seg{sh.f.r_off[sh.f.s_read[i]] + sh.f.s_start[i], sh.f.s_len[i]}; };
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    if (g >= n_groups) break;
+    rec.grp[g] = (int32_t)gt::queue_group<64>(a.groups, a.jobs, at, seg_of(bb[g]), (uint32_t)gcnt[g], nd[g], n, [&, g](int i) { return sh.cls[i] == g; }, seg_of);
+    rec.gsize[g] = gcnt[g];
   }
   rec.n_groups = n_groups;
   for (int q = 0; q < 4; ++q) rec.ci[q] = ci[q];
@@ -428,10 +394,11 @@ __global__ void __launch_bounds__(64) cluster_ward_kernel(const ClArgs a) {
 }
 
 // ---- 3. behind the first consensus round: the homozygous redo, or the dropped reads against both alleles
+template <int MAXR>
+struct ClRound2 { ClFront<MAXR> f; gt::Reserved rsv; };
 template <int MAXR, bool PRESEL = false>
 __global__ void __launch_bounds__(64) cluster_round2_kernel(const ClArgs a) {
-  __shared__ ClFront<MAXR> sh;
-  __shared__ int s_ok; __shared__ uint32_t s_g0, s_j0; __shared__ unsigned long long s_c0, s_o0, s_s0;
+  __shared__ ClRound2<MAXR> sh;
   const uint32_t k = blockIdx.x;
   if (k >= a.n_list) return;
   ClRec rec = a.rec[k];
@@ -443,64 +410,28 @@ __global__ void __launch_bounds__(64) cluster_round2_kernel(const ClArgs a) {
   const int64_t l = a.list[k];
   const uint64_t r0 = a.g.locus_read_begin[l];
   const int nr = (int)(a.g.locus_read_begin[l + 1] - r0);
-  if (lane == 0) sh.n = 0;
-  gt::gt_selected<MAXR, PRESEL>(sh, a.g, l, r0, nr, lane);
-  const int n = sh.n;
+  if (lane == 0) sh.f.n = 0;
+  gt::gt_selected<MAXR, PRESEL>(sh.f, a.g, l, r0, nr, lane);
+  const int n = sh.f.n;
   const uint32_t l1 = a.vote_len[rec.grp[0]], l2 = a.vote_len[rec.grp[1]];
   const uint32_t c1 = (uint32_t)rec.gsize[0], c2 = (uint32_t)rec.gsize[1];
   const uint32_t cmin = c1 < c2 ? c1 : c2, cmax = c1 < c2 ? c2 : c1;
   if ((l1 > l2 ? l1 - l2 : l2 - l1) < 100u && cmin * 4u < cmax) {  // small_group_is_outlier (:84-98): redo the homozygous case
     int gcnt[2] = {(n + 1) / 2, n / 2};
-    unsigned long long cig[2], out_need[2], scr_need[2], mbytes[2] = {0, 0};
-    uint32_t out_cap[2];
-    for (int i = 0; i < n; ++i) mbytes[i & 1] += sh.s_len[i];
-    for (int g = 0; g < 2; ++g) {
-      const uint32_t bl = sh.s_len[rec.cr_eo[g]];
-      cig[g] = (unsigned long long)gcnt[g] * ((unsigned long long)bl + 1) + mbytes[g];
-      out_cap[g] = (uint32_t)(bl + mbytes[g] + 16);
-      out_need[g] = ((unsigned long long)out_cap[g] + 15ull) & ~15ull;
-      scr_need[g] = (bl + 1 <= a.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)bl + 1)) + 3ull * (unsigned long long)gcnt[g];
-    }
-    if (lane == 0) {
-      const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
-      int ok = 1;
-      unsigned long long c0 = 0, o0 = 0, s0 = 0;
-      c0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.counts + CC_CIGAR), cn);
-      if (c0 + cn > a.cap_cigar) ok = 0;
-      if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.counts + CC_OUT), on); if (o0 + on > a.cap_out) ok = 0; }
-      if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(a.counts + CC_SCRATCH), sn); if (s0 + sn > a.cap_scratch) ok = 0; }
-      if (ok) { s_j0 = atomicAdd(a.counts + CC_J2, (uint32_t)n); s_g0 = atomicAdd(a.counts + CC_G2, 2u); }
-      else atomicAdd(a.counts + CC_FAILED, 1u);
-      s_ok = ok; s_c0 = c0; s_o0 = o0; s_s0 = s0;
-    }
+    unsigned long long mbytes[2] = {0, 0};
+    for (int i = 0; i < n; ++i) mbytes[i & 1] += sh.f.s_len[i];
+    gt::GroupNeeds nd[2];
+#pragma unroll
+    for (int g = 0; g < 2; ++g) nd[g] = gt::group_needs(sh.f.s_len[rec.cr_eo[g]], (uint32_t)gcnt[g], mbytes[g], a.vote_lds_pos);
+    if (lane == 0) cluster_reserve(a, true, (uint32_t)n, 2u, nd, sh.rsv);
     __syncthreads();
-    if (!s_ok) { rec.state = -1; if (lane == 0) a.rec[k] = rec; return; }
-    uint32_t g_at = a.cap_g + s_g0, j_at = a.cap_j + s_j0;
-    unsigned long long co = s_c0, oo = s_o0, so = s_s0;
+    if (!sh.rsv.ok) { rec.state = -1; if (lane == 0) a.rec[k] = rec; return; }
+    gt::Reserved at = sh.rsv;
+    auto seg_of = [&](int i) { return gt::Seg{sh.f.r_off[sh.f.s_read[i]] + sh.f.s_start[i], sh.f.s_len[i]}; };
+#pragma unroll
     for (int g = 0; g < 2; ++g) {
-      const int b = rec.cr_eo[g];
-      const unsigned long long bb_off = sh.r_off[sh.s_read[b]] + sh.s_start[b];
-      const uint32_t bl = sh.s_len[b];
-      if (lane == 0) {
-        gt::RGroup G;
-        G.job_first = j_at; G.n_members = (uint32_t)gcnt[g]; G.bb_len = bl; G.out_cap = out_cap[g];
-        G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
-        a.groups[g_at] = G;
-      }
-      rec.grp[g] = (int32_t)g_at; rec.gsize[g] = gcnt[g];
-      uint32_t q = 0;
-      for (int i = g; i < n; i += 2) {
-        if ((int)(q & 63u) == lane) {
-          JobDev jd;
-          jd.pat_off = bb_off; jd.pat_len = bl;
-          jd.txt_off = sh.r_off[sh.s_read[i]] + sh.s_start[i]; jd.txt_len = sh.s_len[i];
-          jd.cigar_off = co; jd.ops_off = 0; jd.out_index = j_at + q; jd.pad = 0;
-          a.jobs[j_at + q] = jd;
-        }
-        co += (unsigned long long)bl + sh.s_len[i] + 1;
-        ++q;
-      }
-      j_at += (uint32_t)gcnt[g]; oo += out_need[g]; so += scr_need[g]; ++g_at;
+      rec.grp[g] = (int32_t)gt::queue_group<64>(a.groups, a.jobs, at, seg_of(rec.cr_eo[g]), (uint32_t)gcnt[g], nd[g], n, [g](int i) { return (i & 1) == g; }, seg_of);
+      rec.gsize[g] = gcnt[g];
     }
     rec.redo = 1;
     for (int q = 0; q < 4; ++q) rec.ci[q] = rec.ci_eo[q];
@@ -513,7 +444,7 @@ __global__ void __launch_bounds__(64) cluster_round2_kernel(const ClArgs a) {
   for (int ib = 0; ib < n; ib += 64) {
     const int i = ib + lane;
     const bool out = i < n && a.cls[r0 + i] == 2;
-    const uint32_t li = i < n ? sh.s_len[i] : 0u;
+    const uint32_t li = i < n ? sh.f.s_len[i] : 0u;
     uint32_t want = 0;
     if (out) for (int q = 0; q < 2; ++q) want += (uint64_t)li * (uint64_t)alen[q] <= CL_MAX_OPS;
     uint32_t inc = want;
@@ -527,7 +458,7 @@ __global__ void __launch_bounds__(64) cluster_round2_kernel(const ClArgs a) {
         const uint64_t slot = 2 * (r0 + (uint64_t)i) + (uint64_t)q;
         if ((uint64_t)li * (uint64_t)alen[q] <= CL_MAX_OPS) {
           JobDev jd;
-          jd.pat_off = sh.r_off[sh.s_read[i]] + sh.s_start[i]; jd.pat_len = li;
+          jd.pat_off = sh.f.r_off[sh.f.s_read[i]] + sh.f.s_start[i]; jd.pat_len = li;
           jd.txt_off = aoff[q]; jd.txt_len = alen[q];
           jd.cigar_off = 0; jd.ops_off = 0; jd.out_index = (uint32_t)slot; jd.pad = 0;
           a.ed2_jobs[at++] = jd;

@@ -16,7 +16,7 @@
 #include <type_traits>
 
 #include "common.hpp"
-#include "wfa_host.hpp"
+#include "repair_queue.hpp"
 
 namespace trgt {
 namespace gt {
@@ -30,28 +30,15 @@ constexpr int GT_SEG_LDS = 16 * 1024;  // bytes of repeat segments staged per lo
 // lacks majority support no longer goes back to the host.  The genotyper writes the consensus alignments it needs (backbone = the pick,
 // texts = the unique sequences of the allele's group, all of them segments of the read blob) into a job list, one vote group per allele
 // and a record of what it had decided; behind it run the alignment kernel over that list, the column voting and repair_finish_kernel,
-// which classifies the reads against the repaired alleles and writes the locus out.  Space is handed out with atomic counters; a locus
-// that finds no room (or is out of the envelope: a segment longer than max_seg) takes the host path as before.
-struct RGroup {  // = vote::Group (consensus_vote.hpp; the layouts are asserted equal in locus.hip)
-  uint32_t job_first, n_members, bb_len, out_cap;
-  uint64_t bb_off, out_off, scratch_off;
-};
-struct RepairPend {  // what the genotyper had decided for a locus that waits for its repaired alleles
-  int32_t n_gt, n_pick; uint32_t size[2]; int32_t civ[4]; int32_t rep[2] /* rank of the pick */; int32_t grp[2] /* vote group, -1: the pick stands */;
-};
+// which classifies the reads against the repaired alleles and writes the locus out.  The records, the reservation of space and the job
+// writer are those of repair_queue.hpp, shared with every other route; a locus that finds no room (or is out of the envelope: a segment
+// longer than max_seg) takes the host path as before.
 // n_pick of a record the haplotype-tag route wrote (FLANK instantiations only): rep[] are the backbones of the two tag groups, civ[] the
 // groups' length ranges, and the finish is flank_finish's
 constexpr int32_t RP_FLANK = 0x100;
 // GtFlankArgs::flank_done, per locus: the tag split replaced the genotype (FL_DONE; FL_DONE | FL_REPAIRED: behind the repair chain), or the
 // split was accepted and the locus handed to the host path (no room in the chain, a segment beyond max_seg, allele_cap)
 enum { FL_DONE = 1, FL_REPAIRED = 2, FL_HANDED = 4 };
-enum { RC_GROUPS = 0, RC_JOBS = 1, RC_LOCI = 2, RC_FAILED = 3, RC_CIGAR = 4 /* u64 */, RC_OUT = 6 /* u64 */, RC_SCRATCH = 8 /* u64 */, RC_REFUSED = 10 /* alignment jobs of the chain the generic kernel refused (beyond its planned workspace) */, RC_WORDS = 16 };
-struct RepairBufs {
-  uint32_t* counts;  // [RC_WORDS]; nullptr: no device-side repair (every such locus takes the host path)
-  RGroup* groups; JobDev* jobs; uint32_t* loci; RepairPend* pend;
-  uint32_t cap_groups, cap_jobs, max_seg, vote_lds_pos;
-  uint64_t cap_cigar, cap_out, cap_scratch;
-};
 
 struct GtArgs {
   const uint8_t* reads; const uint64_t* read_off; const uint32_t* read_len; const uint64_t* locus_read_begin;
@@ -98,8 +85,7 @@ struct GtShared : FlankShared<MAXR, FLANK> {
   int n, n_sizes, bail, fits;
   // decisions of lane 0, written out by the whole wave
   int res_n_gt, res_flip, res_rep[2], res_ci[4], res_hap[2];
-  // device-side repair: reservations of lane 0
-  int rp_ok; uint32_t rp_g0, rp_j0; unsigned long long rp_c0, rp_o0, rp_s0;
+  Reserved rsv;  // device-side repair: the reservation of lane 0
   uint32_t ref_off;                                    // the reference repeat staged behind the segments
   alignas(16) uint8_t bytes[SEG];
 };
@@ -319,81 +305,37 @@ __device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_
     lacks[g] = (double)top / (double)cnt[g] < 0.5;
   }
   if (lacks[0] || lacks[1]) {
-    // ---- a group below 50 %: backbone = its sequence, one member per read of the group in read order, duplicates included; the
-    //      reservations are the size route's
+    // ---- a group below 50 %: backbone = its sequence, one member per read of the group in read order, duplicates included
     const RepairBufs& rp = a.rp;
     bool can = rp.counts != nullptr;
-    uint32_t nm[2] = {0, 0}; unsigned long long mbytes[2] = {0, 0}, cig[2] = {0, 0};
+    uint32_t nm[2] = {0, 0}; unsigned long long mbytes[2] = {0, 0};
     if (can)
       for (int g = 0; g < 2; ++g) {
         if (!lacks[g]) continue;
         if (aln[g] > rp.max_seg) can = false;
         for (int i = 0; i < n; ++i) {
           if (sh.cls[i] != g) continue;
-          const uint32_t ln = sh.s_len[i];
-          if (ln > rp.max_seg) can = false;
-          nm[g] += 1; mbytes[g] += ln; cig[g] += (unsigned long long)aln[g] + ln + 1;
+          if (sh.s_len[i] > rp.max_seg) can = false;
+          nm[g] += 1; mbytes[g] += sh.s_len[i];
         }
       }
-    unsigned long long out_need[2] = {0, 0}, scr_need[2] = {0, 0};
-    uint32_t out_cap[2] = {0, 0};
+    GroupNeeds nd[2] = {};
     if (can) {
-      for (int g = 0; g < 2; ++g) {
-        if (!lacks[g]) continue;
-        out_cap[g] = (uint32_t)(aln[g] + mbytes[g] + 16);
-        out_need[g] = ((unsigned long long)out_cap[g] + 15ull) & ~15ull;
-        scr_need[g] = (aln[g] + 1 <= rp.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)aln[g] + 1)) + 3ull * nm[g];
-      }
-      if (lane == 0) {
-        const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
-        int ok = 1;
-        unsigned long long c0 = 0, o0 = 0, s0 = 0;
-        c0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_CIGAR), cn);
-        if (c0 + cn > rp.cap_cigar) ok = 0;
-        if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_OUT), on); if (o0 + on > rp.cap_out) ok = 0; }
-        if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_SCRATCH), sn); if (s0 + sn > rp.cap_scratch) ok = 0; }
-        if (ok) {
-          sh.rp_j0 = atomicAdd(rp.counts + RC_JOBS, nm[0] + nm[1]);
-          sh.rp_g0 = atomicAdd(rp.counts + RC_GROUPS, (uint32_t)lacks[0] + (uint32_t)lacks[1]);
-          if (sh.rp_j0 + nm[0] + nm[1] > rp.cap_jobs || sh.rp_g0 + 2 > rp.cap_groups) ok = 0;  // (cannot happen: the caps are the read and locus counts)
-          else { const uint32_t slot = atomicAdd(rp.counts + RC_LOCI, 1u); if (slot < (uint32_t)a.n_loci) rp.loci[slot] = (uint32_t)l; else ok = 0; }
-        } else atomicAdd(rp.counts + RC_FAILED, 1u);
-        sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
-      }
+#pragma unroll
+      for (int g = 0; g < 2; ++g) if (lacks[g]) nd[g] = group_needs(aln[g], nm[g], mbytes[g], rp.vote_lds_pos);
+      if (lane == 0) repair_reserve(rp, l, a.n_loci, nm[0] + nm[1], (uint32_t)lacks[0] + (uint32_t)lacks[1], nd, sh.rsv);
       __syncthreads();
-      can = sh.rp_ok != 0;
+      can = sh.rsv.ok != 0;
     }
     if (!can) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED; return true; }
-    uint32_t gi = sh.rp_g0, j = sh.rp_j0;
-    unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
+    Reserved at = sh.rsv;
+    auto seg_of = [&](int i) { return Seg{sh.r_off[sh.s_read[i]] + sh.s_start[i], sh.s_len[i]}; };
     RepairPend pd;
     pd.n_gt = 2; pd.n_pick = 2 | RP_FLANK; pd.size[0] = aln[0]; pd.size[1] = aln[1];
     for (int g = 0; g < 2; ++g) { pd.civ[2 * g] = (int32_t)lo[g]; pd.civ[2 * g + 1] = (int32_t)hi[g]; pd.rep[g] = rep[g]; pd.grp[g] = -1; }
-    for (int g = 0; g < 2; ++g) {
-      if (!lacks[g]) continue;
-      const unsigned long long bb_off = sh.r_off[sh.s_read[rep[g]]] + sh.s_start[rep[g]];
-      if (lane == 0) {
-        RGroup G;
-        G.job_first = j; G.n_members = nm[g]; G.bb_len = aln[g]; G.out_cap = out_cap[g];
-        G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
-        rp.groups[gi] = G;
-      }
-      pd.grp[g] = (int32_t)gi;
-      uint32_t k = 0;
-      for (int i = 0; i < n; ++i) {
-        if (sh.cls[i] != g) continue;
-        if ((int)(k & 63u) == lane) {
-          JobDev jd;
-          jd.pat_off = bb_off; jd.pat_len = aln[g];
-          jd.txt_off = sh.r_off[sh.s_read[i]] + sh.s_start[i]; jd.txt_len = sh.s_len[i];
-          jd.cigar_off = co; jd.ops_off = 0; jd.out_index = j + k; jd.pad = 0;
-          rp.jobs[j + k] = jd;
-        }
-        co += (unsigned long long)aln[g] + sh.s_len[i] + 1;
-        ++k;
-      }
-      j += nm[g]; oo += out_need[g]; so += scr_need[g]; ++gi;
-    }
+#pragma unroll
+    for (int g = 0; g < 2; ++g)
+      if (lacks[g]) pd.grp[g] = (int32_t)queue_group<64>(rp.groups, rp.jobs, at, seg_of(rep[g]), nm[g], nd[g], n, [&, g](int i) { return sh.cls[i] == g; }, seg_of);
     if (lane == 0) rp.pend[l] = pd;
     sh.bail = 2;  // the locus waits for repair_finish_kernel
     return true;
@@ -597,85 +539,38 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
         //      its group against the pick (the members of make_consensus, genotype_size.rs:32-37), all segments of the read blob
         const RepairBufs& rp = a.rp;
         bool can = rp.counts != nullptr;
-        uint32_t nm[2] = {0, 0}; unsigned long long mbytes[2] = {0, 0}, cig[2] = {0, 0};
+        uint32_t nm[2] = {0, 0}; unsigned long long mbytes[2] = {0, 0};
         if (can)
           for (int al = 0; al < n_pick; ++al) {
             if (!lacks[al]) continue;
-            const uint32_t bb = ulen_of(pick[al]);
-            if (bb > rp.max_seg) can = false;
+            if (ulen_of(pick[al]) > rp.max_seg) can = false;
             for (int q = 0; q < nu; ++q) {
               if (!in_group(q, al)) continue;
-              const uint32_t ln = ulen_of(q);
-              if (ln > rp.max_seg) can = false;
-              nm[al] += 1; mbytes[al] += ln; cig[al] += (unsigned long long)bb + ln + 1;
+              if (ulen_of(q) > rp.max_seg) can = false;
+              nm[al] += 1; mbytes[al] += ulen_of(q);
             }
           }
-        unsigned long long out_need[2] = {0, 0}, scr_need[2] = {0, 0};
-        uint32_t out_cap[2] = {0, 0};
+        GroupNeeds nd[2] = {};
         if (can) {
-          for (int al = 0; al < n_pick; ++al) {
-            if (!lacks[al]) continue;
-            const uint32_t bb = ulen_of(pick[al]);
-            // at most one base per backbone position plus the insertions taken, each of which is a piece of some member
-            out_cap[al] = (uint32_t)(bb + mbytes[al] + 16);
-            out_need[al] = ((unsigned long long)out_cap[al] + 15ull) & ~15ull;
-            scr_need[al] = (bb + 1 <= rp.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)bb + 1)) + 3ull * nm[al];
-          }
-          if (lane == 0) {  // cigar words, result bytes and vote scratch first: a failed reservation must not leave holes in the job list
-            const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
-            int ok = 1;
-            unsigned long long c0 = 0, o0 = 0, s0 = 0;
-            c0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_CIGAR), cn);
-            if (c0 + cn > rp.cap_cigar) ok = 0;
-            if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_OUT), on); if (o0 + on > rp.cap_out) ok = 0; }
-            if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + RC_SCRATCH), sn); if (s0 + sn > rp.cap_scratch) ok = 0; }
-            if (ok) {
-              sh.rp_j0 = atomicAdd(rp.counts + RC_JOBS, nm[0] + nm[1]);
-              sh.rp_g0 = atomicAdd(rp.counts + RC_GROUPS, (uint32_t)lacks[0] + (uint32_t)lacks[1]);
-              rp.loci[atomicAdd(rp.counts + RC_LOCI, 1u)] = (uint32_t)l;
-              if (sh.rp_j0 + nm[0] + nm[1] > rp.cap_jobs || sh.rp_g0 + 2 > rp.cap_groups) ok = 0;  // (cannot happen: the caps are the read and locus counts)
-            } else atomicAdd(rp.counts + RC_FAILED, 1u);
-            sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
-          }
+#pragma unroll
+          for (int al = 0; al < 2; ++al) if (lacks[al]) nd[al] = group_needs(ulen_of(pick[al]), nm[al], mbytes[al], rp.vote_lds_pos);
+          if (lane == 0) repair_reserve(rp, l, a.n_loci, nm[0] + nm[1], (uint32_t)lacks[0] + (uint32_t)lacks[1], nd, sh.rsv);
           __syncthreads();
-          can = sh.rp_ok != 0;
+          can = sh.rsv.ok != 0;
         }
         if (!can) sh.bail = 1;
         else {
-          uint32_t g = sh.rp_g0, j = sh.rp_j0;
-          unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
+          Reserved at = sh.rsv;
+          auto seg_of = [&](int q) { const int r = sh.u_rep[q]; return Seg{sh.r_off[sh.s_read[r]] + sh.s_start[r], sh.s_len[r]}; };  // of a unique sequence
           RepairPend pd;
           pd.n_gt = n_gt; pd.n_pick = n_pick; pd.size[0] = size[0]; pd.size[1] = size[1];
           for (int k = 0; k < 4; ++k) pd.civ[k] = (int32_t)civ[k];
           pd.rep[0] = pd.rep[1] = -1; pd.grp[0] = pd.grp[1] = -1;
-          for (int al = 0; al < n_pick; ++al) {
-            const int rep = sh.u_rep[pick[al]];
-            pd.rep[al] = rep;
-            if (!lacks[al]) continue;
-            const unsigned long long bb_off = sh.r_off[sh.s_read[rep]] + sh.s_start[rep];
-            const uint32_t bb = sh.s_len[rep];
-            if (lane == 0) {
-              RGroup G;
-              G.job_first = j; G.n_members = nm[al]; G.bb_len = bb; G.out_cap = out_cap[al];
-              G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
-              rp.groups[g] = G;
-            }
-            pd.grp[al] = (int32_t)g;
-            uint32_t k = 0;
-            for (int q = 0; q < nu; ++q) {
-              if (!in_group(q, al)) continue;
-              const int rq = sh.u_rep[q];
-              if ((int)(k & 63u) == lane) {
-                JobDev jd;
-                jd.pat_off = bb_off; jd.pat_len = bb;
-                jd.txt_off = sh.r_off[sh.s_read[rq]] + sh.s_start[rq]; jd.txt_len = sh.s_len[rq];
-                jd.cigar_off = co; jd.ops_off = 0; jd.out_index = j + k; jd.pad = 0;
-                rp.jobs[j + k] = jd;
-              }
-              co += (unsigned long long)bb + sh.s_len[rq] + 1;
-              ++k;
-            }
-            j += nm[al]; oo += out_need[al]; so += scr_need[al]; ++g;
+#pragma unroll
+          for (int al = 0; al < 2; ++al) {
+            if (al >= n_pick) break;
+            pd.rep[al] = sh.u_rep[pick[al]];
+            if (lacks[al]) pd.grp[al] = (int32_t)queue_group<64>(rp.groups, rp.jobs, at, seg_of(pick[al]), nm[al], nd[al], nu, [&, al](int q) { return in_group(q, al); }, seg_of);
           }
           if (lane == 0) rp.pend[l] = pd;
           sh.bail = 2;  // the locus waits for repair_finish_kernel
@@ -743,7 +638,6 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
 // (classification of the reads against the repaired alleles, genotype_size.rs:42-61), reference allele first (tr.rs:95-101), outputs.
 // One wave per waiting locus (list in rp.loci).  A locus whose repaired allele does not fit (vote overflow, allele_cap) goes to the
 // host path after all (need_host = 1); the others leave with need_host = 0.
-struct FinishArgs { const uint8_t* vote_out; const uint32_t* vote_len; };
 template <int MAXR>
 struct FinShared {
   uint32_t r_s[MAXR], r_len[MAXR]; uint64_t r_off[MAXR];
@@ -767,16 +661,8 @@ __device__ __forceinline__ void flank_finish(SH& sh, const GtFlankArgs& a, const
   int cnt[2] = {0, 0};
   bool fail = n == 0 || !flank_assign(sh, a.hp_tag, r0, n, lane, cnt);
   const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
-  for (int g = 0; g < 2 && !fail; ++g) {
-    if (pd.grp[g] >= 0) {
-      const uint32_t len = f.vote_len[pd.grp[g]];
-      if (len == 0xFFFFFFFFu) { fail = true; break; }
-      ap[g] = f.vote_out + rp.groups[pd.grp[g]].out_off; aln[g] = len;
-    } else {
-      const int rep = pd.rep[g];
-      ap[g] = a.reads + sh.r_off[sh.s_read[rep]] + sh.s_start[rep]; aln[g] = sh.s_len[rep];
-    }
-  }
+  auto seg_of = [&](int i) { return Seg{sh.r_off[sh.s_read[i]] + sh.s_start[i], sh.s_len[i]}; };
+  for (int g = 0; g < 2 && !fail; ++g) fail = !repaired_allele(pd, g, f, rp, a.reads, seg_of, ap[g], aln[g]);
   const int sw = aln[0] > aln[1] ? 1 : 0;
   int order[2] = {sw, 1 - sw}, flip = 0;  // output allele -> tag group
   if (!fail) {
@@ -826,16 +712,8 @@ __global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgsOf<FLANK>
   // the alleles: the repaired sequence of a group, or the pick that had majority support
   const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
   bool fail = n == 0;
-  for (int al = 0; al < pd.n_pick && !fail; ++al) {
-    if (pd.grp[al] >= 0) {
-      const uint32_t len = f.vote_len[pd.grp[al]];
-      if (len == 0xFFFFFFFFu) { fail = true; break; }
-      ap[al] = f.vote_out + rp.groups[pd.grp[al]].out_off; aln[al] = len;
-    } else {
-      const int rep = pd.rep[al];
-      ap[al] = a.reads + sh.r_off[sh.s_read[rep]] + sh.s_start[rep]; aln[al] = sh.s_len[rep];
-    }
-  }
+  auto seg_of = [&](int i) { return Seg{sh.r_off[sh.s_read[i]] + sh.s_start[i], sh.s_len[i]}; };
+  for (int al = 0; al < pd.n_pick && !fail; ++al) fail = !repaired_allele(pd, al, f, rp, a.reads, seg_of, ap[al], aln[al]);
   int n_al = pd.n_pick;
   if (!fail && ploidy == 2 && n_al == 1) { ap[1] = ap[0]; aln[1] = aln[0]; n_al = 2; }
   int by_hap[2] = {0, 0}, order[2] = {0, 1}, flip = 0;

@@ -8,7 +8,8 @@
 //   cld::deep_select_kernel / cld::deep_filter_kernel   the kept reads, in global lists (shared with the deep cluster chain)
 //   deep_size_genotype_kernel   length histogram, diploid / haploid candidates, collapse, intervals, sequence histogram, picks, split();
 //                               a locus with majority support is classified and written out, the others write vote groups, alignment jobs
-//                               and a RepairPend into the call's RepairBufs (the repair chain of locus.hip is the same for both depths)
+//                               and a RepairPend into the call's RepairBufs (the repair chain of locus.hip is the same for both depths;
+//                               needs, reservation and records are repair_queue.hpp's, the job writer is queue_group_scan below)
 //   deep_size_finish_kernel     behind the vote: classification against the repaired alleles, reference allele first, outputs
 // The sequential scans of the one-wave kernel (histogram insertion, binary-insertion sort, lane-0 loops) are rank sorts and workgroup
 // reductions here.  Ties as in locus_cluster_deep.hpp: every "first / last in index order" of a sequential scan is a lexicographic
@@ -138,6 +139,28 @@ __device__ __forceinline__ bool deep_size_write(const DeepArgs& a, int64_t l, ui
   return true;
 }
 
+// gt::queue_group for the workgroup of a deep locus: thread t takes items t, t + DW, ...; the place of a member among the jobs of its
+// group and the CIGAR words of the members before it are workgroup prefixes, carried across the rounds
+template <class IsMember, class SegOf>
+__device__ __forceinline__ uint32_t queue_group_scan(gt::RGroup* groups, JobDev* jobs, gt::Reserved& at, gt::Seg bb, uint32_t nm, const gt::GroupNeeds& nd, int n, IsMember is_member, SegOf seg, Red& red) {
+  const int tid = threadIdx.x;
+  const uint32_t g = at.g0;
+  if (tid == 0) gt::put_group(groups, at, bb, nm, nd);
+  uint32_t k0 = 0; unsigned long long b0 = 0;
+  for (int base = 0; base < n; base += DW) {
+    const int i = base + tid;
+    const bool in = i < n && is_member(i);
+    const gt::Seg s = in ? seg(i) : gt::Seg{0, 0};
+    uint32_t tk, tb;
+    const uint32_t kk = k0 + cld::block_rank(in, tk, red);
+    const unsigned long long before = b0 + block_excl_scan_u32(s.len, tb, red);
+    if (in) gt::put_job(jobs, at.j0 + kk, bb, s, at.c0 + (unsigned long long)kk * ((unsigned long long)bb.len + 1) + before);
+    k0 += tk; b0 += tb;
+  }
+  at.c0 += nd.cig; at.j0 += nm; at.o0 += nd.out_need; at.s0 += nd.scr_need; ++at.g0;
+  return g;
+}
+
 struct DeepSize {
   uint32_t ln[MAXR]; uint64_t off[MAXR];  // kept reads in LocusResult.reads order: span length, blob offset of the repeat segment
   uint32_t ulen[MAXR], ucnt[MAXR];        // unique lengths ascending, multiplicities
@@ -145,7 +168,7 @@ struct DeepSize {
   uint16_t ord[MAXR];                     // first read of every length in the sorted list; later the kept reads in byte-lexicographic order (stable)
   uint16_t u_rep[MAXR], u_cnt[MAXR];      // unique sequences in that order: representative (the earliest read), multiplicity
   Red red;
-  int rp_ok; uint32_t rp_g0, rp_j0; unsigned long long rp_c0, rp_o0, rp_s0;
+  gt::Reserved rsv;
 };
 static_assert(sizeof(DeepSize) <= 64 * 1024, "static LDS of the deep size genotyper");
 
@@ -232,11 +255,10 @@ __device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankAr
     lacks[t] = (double)top / (double)cnt[t] < 0.5;
   }
   if (lacks[0] || lacks[1]) {
-    // ---- a group below 50 %: backbone = its sequence, one member per read of the group in kept order, duplicates included; the
-    //      reservations are the one-wave route's, in its order
+    // ---- a group below 50 %: backbone = its sequence, one member per read of the group in kept order, duplicates included
     const gt::RepairBufs& rp = g.rp;
     bool can = rp.counts != nullptr;
-    uint32_t nm[2] = {0, 0}, mbytes[2] = {0, 0}; unsigned long long cig[2] = {0, 0};
+    uint32_t nm[2] = {0, 0}, mbytes[2] = {0, 0};
     if (can) {
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
@@ -245,77 +267,26 @@ __device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankAr
         for (int i = tid; i < n; i += DW) if (fl.grp[i] == (uint32_t)t) { const uint32_t li = sh.ln[i]; over += li > rp.max_seg; bytes += li > rp.max_seg ? 0u : li; }
         nm[t] = (uint32_t)cnt[t]; mbytes[t] = cld::block_sum_u32(bytes, sh.red);
         if (cld::block_sum_u32(over, sh.red)) can = false;
-        cig[t] = (unsigned long long)nm[t] * ((unsigned long long)aln[t] + 1) + mbytes[t];
       }
     }
-    unsigned long long out_need[2] = {0, 0}, scr_need[2] = {0, 0};
-    uint32_t out_cap[2] = {0, 0};
+    gt::GroupNeeds nd[2] = {};
     if (can) {
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        if (!lacks[t]) continue;
-        out_cap[t] = (uint32_t)(aln[t] + mbytes[t] + 16);
-        out_need[t] = ((unsigned long long)out_cap[t] + 15ull) & ~15ull;
-        scr_need[t] = (aln[t] + 1 <= rp.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)aln[t] + 1)) + 3ull * nm[t];
-      }
-      if (tid == 0) {  // cigar words, result bytes and vote scratch first: a failed reservation must not leave holes in the job list
-        const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
-        int ok = 1;
-        unsigned long long c0 = 0, o0 = 0, s0 = 0;
-        c0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_CIGAR), cn);
-        if (c0 + cn > rp.cap_cigar) ok = 0;
-        if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_OUT), on); if (o0 + on > rp.cap_out) ok = 0; }
-        if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_SCRATCH), sn); if (s0 + sn > rp.cap_scratch) ok = 0; }
-        if (ok) {
-          sh.rp_j0 = atomicAdd(rp.counts + gt::RC_JOBS, nm[0] + nm[1]);
-          sh.rp_g0 = atomicAdd(rp.counts + gt::RC_GROUPS, (uint32_t)lacks[0] + (uint32_t)lacks[1]);
-          if (sh.rp_j0 + nm[0] + nm[1] > rp.cap_jobs || sh.rp_g0 + 2 > rp.cap_groups) ok = 0;  // (cannot happen: the caps are the read and locus counts)
-          else { const uint32_t slot = atomicAdd(rp.counts + gt::RC_LOCI, 1u); if (slot < (uint32_t)g.n_loci) rp.loci[slot] = (uint32_t)l; else ok = 0; }
-        } else atomicAdd(rp.counts + gt::RC_FAILED, 1u);
-        sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
-      }
+      for (int t = 0; t < 2; ++t) if (lacks[t]) nd[t] = gt::group_needs(aln[t], nm[t], mbytes[t], rp.vote_lds_pos);
+      if (tid == 0) gt::repair_reserve(rp, l, g.n_loci, nm[0] + nm[1], (uint32_t)lacks[0] + (uint32_t)lacks[1], nd, sh.rsv);
       __syncthreads();
-      can = sh.rp_ok != 0;
+      can = sh.rsv.ok != 0;
     }
     if (!can) { if (tid == 0) { g.need_host[l] = 1; fa.flank_done[l] = gt::FL_HANDED; } return true; }
-    uint32_t gi = sh.rp_g0, j = sh.rp_j0;
-    unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
+    gt::Reserved at = sh.rsv;
+    auto seg_of = [&](int i) { return gt::Seg{sh.off[i], sh.ln[i]}; };
     gt::RepairPend pd;
     pd.n_gt = 2; pd.n_pick = 2 | gt::RP_FLANK; pd.size[0] = aln[0]; pd.size[1] = aln[1];
 #pragma unroll
     for (int t = 0; t < 2; ++t) { pd.civ[2 * t] = (int32_t)lo[t]; pd.civ[2 * t + 1] = (int32_t)hi[t]; pd.rep[t] = rep[t]; pd.grp[t] = -1; }
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      if (!lacks[t]) continue;
-      const unsigned long long bb_off = sh.off[rep[t]];
-      const uint32_t bb = aln[t];
-      if (tid == 0) {
-        gt::RGroup G;
-        G.job_first = j; G.n_members = nm[t]; G.bb_len = bb; G.out_cap = out_cap[t];
-        G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
-        rp.groups[gi] = G;
-      }
-      pd.grp[t] = (int32_t)gi;
-      // job k of the group is its k-th read in kept order; its CIGAR slot starts behind those of the reads before it (aln + len + 1 words each)
-      uint32_t k0 = 0; unsigned long long b0 = 0;
-      for (int base = 0; base < n; base += DW) {
-        const int i = base + tid;
-        const bool in = i < n && fl.grp[i] == (uint32_t)t;
-        const uint32_t ln = in ? sh.ln[i] : 0u;
-        uint32_t tk, tb;
-        const uint32_t kk = k0 + cld::block_rank(in, tk, sh.red);
-        const unsigned long long before = b0 + block_excl_scan_u32(ln, tb, sh.red);
-        if (in) {
-          JobDev jd;
-          jd.pat_off = bb_off; jd.pat_len = bb;
-          jd.txt_off = sh.off[i]; jd.txt_len = ln;
-          jd.cigar_off = co + (unsigned long long)kk * ((unsigned long long)bb + 1) + before; jd.ops_off = 0; jd.out_index = j + kk; jd.pad = 0;
-          rp.jobs[j + kk] = jd;
-        }
-        k0 += tk; b0 += tb;
-      }
-      co += cig[t]; j += nm[t]; oo += out_need[t]; so += scr_need[t]; ++gi;
-    }
+    for (int t = 0; t < 2; ++t)  // job k of a group is its k-th read in kept order
+      if (lacks[t]) pd.grp[t] = (int32_t)queue_group_scan(rp.groups, rp.jobs, at, seg_of(rep[t]), nm[t], nd[t], n, [&, t](int i) { return fl.grp[i] == (uint32_t)t; }, seg_of, sh.red);
     if (tid == 0) { rp.pend[l] = pd; g.need_host[l] = 2; }  // the locus waits for the FLANK form of deep_size_finish_kernel
     return true;
   }
@@ -505,16 +476,15 @@ __global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgsOf
     return;
   }
   // ---- stage B on the device: one vote group per allele without majority support, one alignment job per unique sequence of its group
-  //      against the pick, in sequence order; the reservations are those of the one-wave kernel, in its order
+  //      against the pick, in sequence order (job k of a group is its k-th member in that order)
   const gt::RepairBufs& rp = g.rp;
   bool can = rp.counts != nullptr;
-  uint32_t nm[2] = {0, 0}, mbytes[2] = {0, 0}; unsigned long long cig[2] = {0, 0};
+  uint32_t nm[2] = {0, 0}, mbytes[2] = {0, 0};
   if (can) {
 #pragma unroll
     for (int al = 0; al < 2; ++al) {
       if (al >= n_pick || !lacks[al]) continue;
-      const uint32_t bb = ulen_of(pick[al]);
-      uint32_t cnt = 0, bytes = 0, over = bb > rp.max_seg;
+      uint32_t cnt = 0, bytes = 0, over = ulen_of(pick[al]) > rp.max_seg;
       for (int q = tid; q < nu; q += DW) {
         if (!in_group(q, al)) continue;
         const uint32_t ln = ulen_of(q);
@@ -522,43 +492,19 @@ __global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgsOf
       }
       nm[al] = cld::block_sum_u32(cnt, sh.red); mbytes[al] = cld::block_sum_u32(bytes, sh.red);
       if (cld::block_sum_u32(over, sh.red)) can = false;
-      cig[al] = (unsigned long long)nm[al] * ((unsigned long long)bb + 1) + mbytes[al];
     }
   }
-  unsigned long long out_need[2] = {0, 0}, scr_need[2] = {0, 0};
-  uint32_t out_cap[2] = {0, 0};
+  gt::GroupNeeds nd[2] = {};
   if (can) {
 #pragma unroll
-    for (int al = 0; al < 2; ++al) {
-      if (al >= n_pick || !lacks[al]) continue;
-      const uint32_t bb = ulen_of(pick[al]);
-      // at most one base per backbone position plus the insertions taken, each of which is a piece of some member
-      out_cap[al] = (uint32_t)(bb + mbytes[al] + 16);
-      out_need[al] = ((unsigned long long)out_cap[al] + 15ull) & ~15ull;
-      scr_need[al] = (bb + 1 <= rp.vote_lds_pos + 1 ? 0ull : 3ull * ((unsigned long long)bb + 1)) + 3ull * nm[al];
-    }
-    if (tid == 0) {  // cigar words, result bytes and vote scratch first: a failed reservation must not leave holes in the job list
-      const unsigned long long cn = cig[0] + cig[1], on = out_need[0] + out_need[1], sn = scr_need[0] + scr_need[1];
-      int ok = 1;
-      unsigned long long c0 = 0, o0 = 0, s0 = 0;
-      c0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_CIGAR), cn);
-      if (c0 + cn > rp.cap_cigar) ok = 0;
-      if (ok) { o0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_OUT), on); if (o0 + on > rp.cap_out) ok = 0; }
-      if (ok) { s0 = atomicAdd(reinterpret_cast<unsigned long long*>(rp.counts + gt::RC_SCRATCH), sn); if (s0 + sn > rp.cap_scratch) ok = 0; }
-      if (ok) {
-        sh.rp_j0 = atomicAdd(rp.counts + gt::RC_JOBS, nm[0] + nm[1]);
-        sh.rp_g0 = atomicAdd(rp.counts + gt::RC_GROUPS, (uint32_t)lacks[0] + (uint32_t)lacks[1]);
-        rp.loci[atomicAdd(rp.counts + gt::RC_LOCI, 1u)] = (uint32_t)l;
-        if (sh.rp_j0 + nm[0] + nm[1] > rp.cap_jobs || sh.rp_g0 + 2 > rp.cap_groups) ok = 0;  // (cannot happen: the caps are the read and locus counts)
-      } else atomicAdd(rp.counts + gt::RC_FAILED, 1u);
-      sh.rp_ok = ok; sh.rp_c0 = c0; sh.rp_o0 = o0; sh.rp_s0 = s0;
-    }
+    for (int al = 0; al < 2; ++al) if (al < n_pick && lacks[al]) nd[al] = gt::group_needs(ulen_of(pick[al]), nm[al], mbytes[al], rp.vote_lds_pos);
+    if (tid == 0) gt::repair_reserve(rp, l, g.n_loci, nm[0] + nm[1], (uint32_t)lacks[0] + (uint32_t)lacks[1], nd, sh.rsv);
     __syncthreads();
-    can = sh.rp_ok != 0;
+    can = sh.rsv.ok != 0;
   }
   if (!can) { if (tid == 0) g.need_host[l] = 1; return; }  // no room, a segment beyond max_seg, no device-side repair: the host path
-  uint32_t gi = sh.rp_g0, j = sh.rp_j0;
-  unsigned long long co = sh.rp_c0, oo = sh.rp_o0, so = sh.rp_s0;
+  gt::Reserved at = sh.rsv;
+  auto seg_of = [&](int q) { const int r = sh.u_rep[q]; return gt::Seg{sh.off[r], sh.ln[r]}; };  // of a unique sequence
   gt::RepairPend pd;
   pd.n_gt = n_gt; pd.n_pick = n_pick; pd.size[0] = size[0]; pd.size[1] = size[1];
   for (int q = 0; q < 4; ++q) pd.civ[q] = civ[q];
@@ -566,38 +512,8 @@ __global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgsOf
 #pragma unroll
   for (int al = 0; al < 2; ++al) {
     if (al >= n_pick) break;
-    const int rep = sh.u_rep[pick[al]];
-    pd.rep[al] = rep;
-    if (!lacks[al]) continue;
-    const unsigned long long bb_off = sh.off[rep];
-    const uint32_t bb = sh.ln[rep];
-    if (tid == 0) {
-      gt::RGroup G;
-      G.job_first = j; G.n_members = nm[al]; G.bb_len = bb; G.out_cap = out_cap[al];
-      G.bb_off = bb_off; G.out_off = oo; G.scratch_off = so;
-      rp.groups[gi] = G;
-    }
-    pd.grp[al] = (int32_t)gi;
-    // job k of the group is its k-th member in sequence order; its CIGAR slot starts behind those of the members before it
-    uint32_t k0 = 0; unsigned long long b0 = 0;
-    for (int base = 0; base < nu; base += DW) {
-      const int q = base + tid;
-      const bool in = q < nu && in_group(q, al);
-      const int rq = in ? sh.u_rep[q] : 0;
-      const uint32_t ln = in ? sh.ln[rq] : 0u;
-      uint32_t tk, tb;
-      const uint32_t kk = k0 + cld::block_rank(in, tk, sh.red);
-      const unsigned long long before = b0 + block_excl_scan_u32(ln, tb, sh.red);
-      if (in) {
-        JobDev jd;
-        jd.pat_off = bb_off; jd.pat_len = bb;
-        jd.txt_off = sh.off[rq]; jd.txt_len = ln;
-        jd.cigar_off = co + (unsigned long long)kk * ((unsigned long long)bb + 1) + before; jd.ops_off = 0; jd.out_index = j + kk; jd.pad = 0;
-        rp.jobs[j + kk] = jd;
-      }
-      k0 += tk; b0 += tb;
-    }
-    co += cig[al]; j += nm[al]; oo += out_need[al]; so += scr_need[al]; ++gi;
+    pd.rep[al] = sh.u_rep[pick[al]];
+    if (lacks[al]) pd.grp[al] = (int32_t)queue_group_scan(rp.groups, rp.jobs, at, seg_of(pick[al]), nm[al], nd[al], nu, [&, al](int q) { return in_group(q, al); }, seg_of, sh.red);
   }
   if (tid == 0) { rp.pend[l] = pd; g.need_host[l] = 2; }  // the locus waits for deep_size_finish_kernel
 }
@@ -623,6 +539,7 @@ __global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgsOf<F
   const int n = min((int)a.n_sel[k], min(nr, MAXR));
   const gt::RepairPend pd = rp.pend[l];
   const int ploidy = g.ploidy[l] == 1 ? 1 : 2;
+  auto seg_of = [&](int i) { return gt::Seg{cld::seg_off(a, r0, i), a.sel_len[r0 + i]}; };  // of a kept read
   if constexpr (FLANK) {
     // ... of a locus the haplotype-tag route left waiting (RP_FLANK): the alleles are the repaired sequences or the backbones of the tag
     // groups, smaller allele first (genotype_flank.rs:33-38); deep_size_write<TAGS> recomputes the assignment from the tags (deterministic
@@ -631,17 +548,7 @@ __global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgsOf<F
       const uint8_t* tp[2] = {nullptr, nullptr}; uint32_t tl[2] = {0, 0};
       bool bad = n == 0;
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        if (bad) break;
-        if (pd.grp[t] >= 0) {
-          const uint32_t len = f.vote_len[pd.grp[t]];
-          if (len == 0xFFFFFFFFu) { bad = true; break; }
-          tp[t] = f.vote_out + rp.groups[pd.grp[t]].out_off; tl[t] = len;
-        } else {
-          const int rep = pd.rep[t];
-          tp[t] = g.reads + cld::seg_off(a, r0, rep); tl[t] = a.sel_len[r0 + rep];
-        }
-      }
+      for (int t = 0; t < 2; ++t) if (!bad) bad = !gt::repaired_allele(pd, t, f, rp, g.reads, seg_of, tp[t], tl[t]);
       if (!bad) {
         const int sw = tl[0] > tl[1] ? 1 : 0;
         const uint8_t* sp[2] = {sw ? tp[1] : tp[0], sw ? tp[0] : tp[1]};
@@ -660,17 +567,7 @@ __global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgsOf<F
   const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
   bool fail = n == 0;
 #pragma unroll
-  for (int al = 0; al < 2; ++al) {
-    if (al >= pd.n_pick || fail) break;
-    if (pd.grp[al] >= 0) {
-      const uint32_t len = f.vote_len[pd.grp[al]];
-      if (len == 0xFFFFFFFFu) { fail = true; break; }
-      ap[al] = f.vote_out + rp.groups[pd.grp[al]].out_off; aln[al] = len;
-    } else {
-      const int rep = pd.rep[al];
-      ap[al] = g.reads + cld::seg_off(a, r0, rep); aln[al] = a.sel_len[r0 + rep];
-    }
-  }
+  for (int al = 0; al < 2; ++al) if (al < pd.n_pick && !fail) fail = !gt::repaired_allele(pd, al, f, rp, g.reads, seg_of, ap[al], aln[al]);
   int n_al = pd.n_pick;
   if (!fail && ploidy == 2 && n_al == 1) { ap[1] = ap[0]; aln[1] = aln[0]; n_al = 2; }
   if (!fail) fail = !deep_size_write(a, l, r0, n, pd.n_gt, n_al, ap, aln, pd.civ, pd.size, red);
