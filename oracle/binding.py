@@ -378,6 +378,28 @@ def cluster_groups(dists, n):
     return k, g, d
 
 
+def repair_consensus(backbone, members, cigars):
+    """repair_consensus (consensus.rs:5-111) of one group on the caller's CIGARs: cigars[m] = the dense `len << 4 | code` words of
+    member m (empty: its alignment failed).  Returns the consensus as bytes."""
+    backbone = backbone.encode() if isinstance(backbone, str) else bytes(backbone)
+    members = [m.encode() if isinstance(m, str) else bytes(m) for m in members]
+    blob = _u8(backbone + b"".join(members))
+    m_len = np.array([len(m) for m in members], np.uint32)
+    m_off = np.zeros(max(len(members), 1), np.uint64)
+    m_off[:len(members)] = len(backbone) + np.concatenate([[0], np.cumsum(m_len[:-1], dtype=np.uint64)]) if members else 0
+    first = np.zeros(len(members) + 1, np.uint64)
+    first[1:] = np.cumsum([len(c) for c in cigars])
+    words = np.array([w for c in cigars for w in c] + [0], np.uint32)
+    cap = len(backbone) + int(m_len.sum()) + 16
+    out = np.zeros(cap, np.uint8)
+    f = lib().orc_repair_consensus
+    f.restype = C.c_int64
+    n = f(_p(blob), C.c_uint64(0), C.c_uint32(len(backbone)), C.c_int64(len(members)), _p(m_off), _p(m_len), _p(words), _p(first),
+          _p(out), C.c_int64(cap))
+    assert n >= 0, n
+    return bytes(out[:n])
+
+
 def genotype_sizes(ploidy, sizes, counts):
     """haploid::genotype / diploid::genotype on a length histogram -> [(size, (ci_lo, ci_hi)), ...]"""
     s, c = np.ascontiguousarray(sizes, np.int32), np.ascontiguousarray(counts, np.int32)

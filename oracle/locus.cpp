@@ -620,6 +620,28 @@ int orc_cluster_groups(double* dists, int n, int32_t* group_of) {
   return (int)groups.size();
 }
 
+// repair_consensus above on hand-built CIGARs (tests/test_consensus_cases.py): the words are decoded as align_all decodes them
+int64_t orc_repair_consensus(const uint8_t* blob, uint64_t bb_off, uint32_t bb_len, int64_t n_members, const uint64_t* m_off,
+                             const uint32_t* m_len, const uint32_t* cigar, const uint64_t* cigar_first, uint8_t* out, int64_t out_cap) {
+  const std::string backbone((const char*)blob + bb_off, (size_t)bb_len);
+  std::vector<std::string> seqs; std::vector<Cigar> aligns;
+  for (int64_t m = 0; m < n_members; ++m) {
+    seqs.emplace_back((const char*)blob + m_off[m], (size_t)m_len[m]);
+    Cigar c;
+    for (uint64_t k = cigar_first[m]; k < cigar_first[m + 1]; ++k) {
+      static const char* dec = "MIDNSHP=X";
+      const uint32_t code = cigar[k] & 0xF;
+      if (!(code <= 2 || code == 7 || code == 8)) return -2;
+      c.push_back({(int)(cigar[k] >> 4), dec[code]});
+    }
+    aligns.push_back(c);
+  }
+  const std::string r = repair_consensus(backbone, seqs, aligns);
+  if ((int64_t)r.size() > out_cap) return -1;
+  std::memcpy(out, r.data(), r.size());
+  return (int64_t)r.size();
+}
+
 int orc_genotype_flank(int n, const uint8_t* tr_blob, const uint64_t* tr_off, const uint32_t* tr_len, const orc_read_meta* meta,
                        int32_t* sizes, int32_t* ci, char* allele0, char* allele1, int allele_cap, int32_t* assignment) {
   std::vector<FlankRead> fr; std::vector<std::string> trs;

@@ -210,6 +210,13 @@ int orc_genotype_sizes(int ploidy, const int32_t* sizes, const int32_t* counts, 
 int orc_ward_linkage(double* dists, int n, int32_t* steps3 /* cluster1, cluster2, size */, double* dissimilarity);
 int orc_cluster_groups(double* dists, int n, int32_t* group_of);
 
+/* repair_consensus (consensus.rs:5-111) of one group on CIGARs given by the caller, in the dense `len << 4 | code` words of
+ * cigar_get_CIGAR (codes "MIDNSHP=X"): member m is blob[m_off[m] .. + m_len[m]) with the words cigar[cigar_first[m] ..
+ * cigar_first[m + 1]) (none: its alignment failed).  Returns the length of the consensus written to out, -1 when it does not fit
+ * out_cap, -2 for a word whose code is none of M I D = X. */
+int64_t orc_repair_consensus(const uint8_t* blob, uint64_t bb_off, uint32_t bb_len, int64_t n_members, const uint64_t* m_off,
+                             const uint32_t* m_len, const uint32_t* cigar, const uint64_t* cigar_first, uint8_t* out, int64_t out_cap);
+
 #ifdef __cplusplus
 }
 #endif

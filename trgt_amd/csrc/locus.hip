@@ -299,28 +299,21 @@ static_assert(sizeof(vote::Group) == sizeof(gt::RGroup) && offsetof(vote::Group,
               offsetof(vote::Group, out_off) == offsetof(gt::RGroup, out_off) && offsetof(vote::Group, scratch_off) == offsetof(gt::RGroup, scratch_off) &&
               offsetof(vote::Group, out_cap) == offsetof(gt::RGroup, out_cap), "gt::RGroup mirrors vote::Group");
 
-// make_consensus / repair_consensus (consensus.rs:5-111) for a batch of groups: the members of group g are jobs [first[g], first[g + 1])
-// of ONE alignment batch (BiWFA, gap-affine 2,5,1, default heuristic: THREAD_WFA_CONSENSUS, genotype.rs:82-86), each against the
-// group's backbone (the pattern of its jobs).  The run-length CIGARs stay in HBM; the column voting runs there too
-// (consensus_vote_kernel) and only the consensus sequences come back.  results[g] = repaired sequence of group g.
-int consensus_repair_batch(trgt_hip_ctx* c, int64_t n_jobs, const uint8_t* seqs, const uint64_t* po, const uint32_t* pl, const uint64_t* to,
-                           const uint32_t* tl, const std::vector<size_t>& first, std::vector<std::string>& results,
-                           const std::function<int()>* while_running = nullptr) {
-  const size_t n_groups = first.empty() ? 0 : first.size() - 1;
-  results.assign(n_groups, std::string());
-  if (n_jobs == 0 || n_groups == 0) { if (while_running && *while_running) return (*while_running)(); return TRGT_OK; }
-  trgt_wfa_params wp;
-  trgt_wfa_default_params(&wp);
-  wp.metric = 3; wp.mismatch = 2; wp.gap_open1 = 5; wp.gap_ext1 = 1; wp.span = 0; wp.scope = 1; wp.memory_mode = 3; sens_apply(c, wp);
-  const bool tl_on = c->knobs.timeline;
-  const int64_t tl0 = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
 #define RTL(name) do { if (tl_on) fprintf(stderr, "[tl]     repair %-20s +%7.2f ms\n", name, (double)(std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count() - tl0) / 1e6); } while (0)
-  WfaOnDevice dev;
-  int rc = wfa_batch_impl(c, &wp, n_jobs, seqs, po, pl, to, tl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, while_running, &dev);
-  if (rc) return rc;
-  RTL("alignments done");
-  std::vector<vote::Group> groups(n_groups);
+
+// repair_consensus (consensus.rs:5-111) behind the alignments: the members of group g are jobs [first[g], first[g + 1]) of the batch whose
+// job list, CIGAR slots and sequences `dev` names (pl / tl: the jobs' pattern and text lengths, po: their pattern offsets).  Builds the
+// groups (out_cap: at most one base per backbone position plus the insertions taken, unless out_cap_override[g] != 0 says otherwise -- the
+// developer build's trgt_dev_consensus_vote), plans the scratch, launches consensus_vote_kernel (count_on_device: the way the device chains
+// launch it, a grid larger than the count, which is read from device memory) and brings back the raw length words (0xFFFFFFFF: the
+// result does not fit out_cap) and the output slots (group g at groups[g].out_off).
+int vote_groups(trgt_hip_ctx* c, const WfaOnDevice& dev, const uint64_t* po, const uint32_t* pl, const uint32_t* tl, const std::vector<size_t>& first,
+                const uint32_t* out_cap_override, bool count_on_device, int64_t tl0, std::vector<vote::Group>& groups, std::vector<uint32_t>& lens,
+                std::vector<uint8_t>& bytes) {
+  const bool tl_on = c->knobs.timeline;
+  const size_t n_groups = first.size() - 1;
+  int rc;
+  groups.assign(n_groups, vote::Group());
   uint64_t out_total = 0, scratch_words = 0;
   for (size_t g = 0; g < n_groups; ++g) {
     vote::Group& G = groups[g];
@@ -333,6 +326,7 @@ int consensus_repair_batch(trgt_hip_ctx* c, int64_t n_jobs, const uint8_t* seqs,
     for (size_t j = j0; j < j1; ++j) member_bytes += tl[j];
     // at most one base per backbone position plus the insertions taken, each of which is a piece of some member
     G.out_cap = (uint32_t)std::min<uint64_t>((uint64_t)G.bb_len + member_bytes + 16, 0xFFFFFFF0ull);
+    if (out_cap_override && out_cap_override[g]) G.out_cap = out_cap_override[g];
     G.out_off = out_total; out_total += ((uint64_t)G.out_cap + 15) & ~15ull;
     G.scratch_off = scratch_words;
     scratch_words += (G.bb_len + 1 <= (uint32_t)vote::VOTE_LDS_POS + 1 ? 0 : 3 * ((uint64_t)G.bb_len + 1)) + 3 * (uint64_t)G.n_members;
@@ -340,27 +334,125 @@ int consensus_repair_batch(trgt_hip_ctx* c, int64_t n_jobs, const uint8_t* seqs,
   RTL("groups built");
   void *d_groups = nullptr, *d_scratch = nullptr, *d_out = nullptr, *d_len = nullptr;
   if ((rc = dev_get(c, S_VOTE_GROUPS, n_groups * sizeof(vote::Group), &d_groups)) || (rc = dev_get(c, S_VOTE_SCRATCH, (size_t)scratch_words * 4 + 16, &d_scratch)) ||
-      (rc = dev_get(c, S_VOTE_OUT, (size_t)out_total + 16, &d_out)) || (rc = dev_get(c, S_VOTE_LEN, n_groups * 4, &d_len)))
+      (rc = dev_get(c, S_VOTE_OUT, (size_t)out_total + 16, &d_out)) || (rc = dev_get(c, S_VOTE_LEN, n_groups * 4 + (count_on_device ? 16 : 0), &d_len)))
     return rc;
   if ((rc = h2d_small(c, d_groups, groups.data(), n_groups * sizeof(vote::Group), c->stream, S_VOTE_GROUPS))) return rc;
-  vote::VoteArgs va{(const vote::Group*)d_groups, (uint32_t)n_groups, nullptr, dev.seqs, dev.jobs, dev.cigar, dev.cigar_len, (uint32_t*)d_scratch, (uint8_t*)d_out, (uint32_t*)d_len};
-  hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)n_groups), dim3(vote::VOTE_THREADS), 0, c->stream, va);
+  const uint32_t* d_count = nullptr;
+  if (count_on_device) {  // the count behind the length words
+    const uint32_t ng = (uint32_t)n_groups;
+    if ((rc = h2d_small(c, (uint32_t*)d_len + n_groups, &ng, 4, c->stream, S_VOTE_LEN))) return rc;
+    d_count = (const uint32_t*)d_len + n_groups;
+  }
+  vote::VoteArgs va{(const vote::Group*)d_groups, count_on_device ? 0u : (uint32_t)n_groups, d_count, dev.seqs, dev.jobs, dev.cigar, dev.cigar_len, (uint32_t*)d_scratch, (uint8_t*)d_out, (uint32_t*)d_len};
+  hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)n_groups + (count_on_device ? 3u : 0u)), dim3(vote::VOTE_THREADS), 0, c->stream, va);
   TRGT_HIP_TRY(c, hipGetLastError());
   RTL("vote launched");
-  std::vector<uint32_t> lens(n_groups);
-  std::vector<uint8_t> bytes((size_t)out_total);
+  lens.assign(n_groups, 0);
+  bytes.assign((size_t)out_total, 0);
   { const int d2h_rc = trgt::d2h(c, lens.data(), d_len, n_groups * 4, c->stream); if (d2h_rc) return d2h_rc; }
   { const int d2h_rc = trgt::d2h(c, bytes.data(), d_out, (size_t)out_total, c->stream); if (d2h_rc) return d2h_rc; }
   RTL("d2h enqueued");
   TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
   if (tl_on) fprintf(stderr, "[tl]     repair outputs: %zu groups, %.2f MB of output slots, %.2f MB of scratch\n", n_groups, (double)out_total / 1e6, (double)scratch_words * 4 / 1e6);
   RTL("synced");
+  return TRGT_OK;
+}
+
+// make_consensus / repair_consensus (consensus.rs:5-111) for a batch of groups: the members of group g are jobs [first[g], first[g + 1])
+// of ONE alignment batch (BiWFA, gap-affine 2,5,1, default heuristic: THREAD_WFA_CONSENSUS, genotype.rs:82-86), each against the
+// group's backbone (the pattern of its jobs).  The run-length CIGARs stay in HBM; the column voting runs there too
+// (vote_groups) and only the consensus sequences come back.  results[g] = repaired sequence of group g.
+int consensus_repair_batch(trgt_hip_ctx* c, int64_t n_jobs, const uint8_t* seqs, const uint64_t* po, const uint32_t* pl, const uint64_t* to,
+                           const uint32_t* tl, const std::vector<size_t>& first, std::vector<std::string>& results,
+                           const std::function<int()>* while_running = nullptr) {
+  const size_t n_groups = first.empty() ? 0 : first.size() - 1;
+  results.assign(n_groups, std::string());
+  if (n_jobs == 0 || n_groups == 0) { if (while_running && *while_running) return (*while_running)(); return TRGT_OK; }
+  trgt_wfa_params wp;
+  trgt_wfa_default_params(&wp);
+  wp.metric = 3; wp.mismatch = 2; wp.gap_open1 = 5; wp.gap_ext1 = 1; wp.span = 0; wp.scope = 1; wp.memory_mode = 3; sens_apply(c, wp);
+  const bool tl_on = c->knobs.timeline;
+  const int64_t tl0 = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+  WfaOnDevice dev;
+  int rc = wfa_batch_impl(c, &wp, n_jobs, seqs, po, pl, to, tl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                          nullptr, nullptr, while_running, &dev);
+  if (rc) return rc;
+  RTL("alignments done");
+  std::vector<vote::Group> groups;
+  std::vector<uint32_t> lens;
+  std::vector<uint8_t> bytes;
+  if ((rc = vote_groups(c, dev, po, pl, tl, first, nullptr, false, tl0, groups, lens, bytes))) return rc;
   for (size_t g = 0; g < n_groups; ++g) {
     if (lens[g] == 0xFFFFFFFFu) return fail(c, TRGT_ERR_UNSUPPORTED, "consensus: repaired sequence of group %zu longer than %u bases", g, groups[g].out_cap);
     results[g].assign((const char*)bytes.data() + groups[g].out_off, lens[g]);
   }
   return TRGT_OK;
 }
+
+#ifdef TRGT_DEV_BUILD
+// trgt_dev_consensus_vote (below): hand-built groups and CIGARs through vote_groups.  Jobs are laid out as an alignment batch lays them
+// out -- out_index = j, CIGAR slot j of pat_len + txt_len + 1 words -- and every word of a slot behind the job's cigar_len is 0xFFFFFFFF
+// (a run of 2^28 - 1 with code 15), so that a read past the length cannot go unnoticed in the result.
+int dev_consensus_vote(trgt_hip_ctx* c, int64_t n_groups, const uint8_t* seqs, uint64_t seq_bytes, const uint64_t* bb_off, const uint32_t* bb_len,
+                       const uint64_t* group_first, const uint64_t* m_off, const uint32_t* m_len, const uint32_t* cigar, const uint64_t* cigar_first,
+                       const uint32_t* out_cap, int32_t count_on_device, uint32_t* out_len, uint8_t* out_bytes, const uint64_t* out_off) {
+  if (n_groups <= 0 || !seqs || !bb_off || !bb_len || !group_first || !m_off || !m_len || !cigar_first || !out_len || !out_bytes || !out_off)
+    return fail(c, TRGT_ERR_INVALID, "trgt_dev_consensus_vote: null argument or no group");
+  const size_t n_members = (size_t)group_first[n_groups];
+  if (n_members == 0 || (cigar_first[n_members] && !cigar)) return fail(c, TRGT_ERR_INVALID, "trgt_dev_consensus_vote: no member, or CIGAR words missing");
+  std::vector<JobDev> jobs(n_members);
+  std::vector<uint64_t> po(n_members);
+  std::vector<uint32_t> pl(n_members), clen(n_members);
+  std::vector<size_t> first((size_t)n_groups + 1);
+  uint64_t slot_words = 0;
+  for (int64_t g = 0; g < n_groups; ++g) {
+    first[(size_t)g] = (size_t)group_first[g];
+    if (group_first[g + 1] <= group_first[g] || bb_off[g] + bb_len[g] > seq_bytes) return fail(c, TRGT_ERR_INVALID, "trgt_dev_consensus_vote: group %lld is empty or its backbone lies outside the blob", (long long)g);
+    for (uint64_t j = group_first[g]; j < group_first[g + 1]; ++j) {
+      if (m_off[j] + m_len[j] > seq_bytes) return fail(c, TRGT_ERR_INVALID, "trgt_dev_consensus_vote: member %llu lies outside the blob", (unsigned long long)j);
+      const uint64_t nc = cigar_first[j + 1] - cigar_first[j];
+      if (cigar_first[j + 1] < cigar_first[j] || nc > (uint64_t)bb_len[g] + m_len[j] + 1) return fail(c, TRGT_ERR_INVALID, "trgt_dev_consensus_vote: CIGAR of member %llu does not fit its slot", (unsigned long long)j);
+      uint64_t x = 0, y = 0;  // what an alignment guarantees the kernel: runs of M I D = X that end at both sequences' ends
+      for (uint64_t k = cigar_first[j]; k < cigar_first[j + 1]; ++k) {
+        const uint32_t len = cigar[k] >> 4, code = cigar[k] & 0xFu;
+        if (code == 0 || code == 7 || code == 8) { x += len; y += len; } else if (code == 1) x += len; else if (code == 2) y += len;
+        else return fail(c, TRGT_ERR_INVALID, "trgt_dev_consensus_vote: CIGAR code %u in member %llu", code, (unsigned long long)j);
+      }
+      if (nc && (x != m_len[j] || y != bb_len[g])) return fail(c, TRGT_ERR_INVALID, "trgt_dev_consensus_vote: CIGAR of member %llu ends at (%llu, %llu), not at (%u, %u)", (unsigned long long)j, (unsigned long long)x, (unsigned long long)y, m_len[j], bb_len[g]);
+      JobDev& jd = jobs[(size_t)j];
+      jd.pat_off = bb_off[g]; jd.pat_len = bb_len[g]; jd.txt_off = m_off[j]; jd.txt_len = m_len[j]; jd.cigar_off = slot_words; jd.ops_off = 0; jd.out_index = (uint32_t)j; jd.pad = 0;
+      po[(size_t)j] = bb_off[g]; pl[(size_t)j] = bb_len[g]; clen[(size_t)j] = (uint32_t)nc;
+      slot_words += (uint64_t)bb_len[g] + m_len[j] + 1;
+    }
+  }
+  first[(size_t)n_groups] = n_members;
+  std::vector<uint32_t> slots((size_t)slot_words, 0xFFFFFFFFu);
+  for (size_t j = 0; j < n_members; ++j) std::copy(cigar + cigar_first[j], cigar + cigar_first[j + 1], slots.begin() + (ptrdiff_t)jobs[j].cigar_off);
+  int rc;
+  void *d_seq = nullptr, *d_jobs = nullptr, *d_cig = nullptr, *d_clen = nullptr;
+  if ((rc = dev_get(c, S_WFA_SEQ, (size_t)seq_bytes + 16, &d_seq)) || (rc = dev_get(c, S_WFA_JOBS, n_members * sizeof(JobDev), &d_jobs)) ||
+      (rc = dev_get(c, S_WFA_CIGAR, (size_t)slot_words * 4 + 16, &d_cig)) || (rc = dev_get(c, S_WFA_CLEN, n_members * 4, &d_clen)))
+    return rc;
+  TRGT_HIP_TRY(c, hipMemcpyAsync(d_seq, seqs, (size_t)seq_bytes, hipMemcpyHostToDevice, c->stream));
+  TRGT_HIP_TRY(c, hipMemcpyAsync(d_jobs, jobs.data(), n_members * sizeof(JobDev), hipMemcpyHostToDevice, c->stream));
+  TRGT_HIP_TRY(c, hipMemcpyAsync(d_cig, slots.data(), (size_t)slot_words * 4, hipMemcpyHostToDevice, c->stream));
+  TRGT_HIP_TRY(c, hipMemcpyAsync(d_clen, clen.data(), n_members * 4, hipMemcpyHostToDevice, c->stream));
+  TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));  // (pageable sources)
+  WfaOnDevice dev;
+  dev.jobs = (const JobDev*)d_jobs; dev.cigar = (const uint32_t*)d_cig; dev.cigar_len = (const uint32_t*)d_clen; dev.seqs = (const uint8_t*)d_seq;
+  std::vector<vote::Group> groups;
+  std::vector<uint32_t> lens;
+  std::vector<uint8_t> bytes;
+  if ((rc = vote_groups(c, dev, po.data(), pl.data(), m_len, first, out_cap, count_on_device != 0, 0, groups, lens, bytes))) return rc;
+  for (int64_t g = 0; g < n_groups; ++g) {
+    out_len[g] = lens[(size_t)g];
+    if (lens[(size_t)g] == 0xFFFFFFFFu) continue;
+    const uint64_t room = out_off[g + 1] - out_off[g];
+    std::memcpy(out_bytes + out_off[g], bytes.data() + groups[(size_t)g].out_off, (size_t)std::min<uint64_t>(room, lens[(size_t)g]));
+  }
+  return TRGT_OK;
+}
+#endif
 
 #include "locus_cluster.hpp"
 
@@ -1974,6 +2066,22 @@ static int locus_batch_run(trgt_hip_ctx* c, const trgt_locus_params* p, const tr
   try { return (call); }                                                                           \
   catch (const std::bad_alloc&) { return trgt::fail((ctx), TRGT_ERR_NOMEM, "out of host memory"); } \
   catch (const std::exception& e) { return trgt::fail((ctx), TRGT_ERR_INVALID, "unexpected exception: %s", e.what()); }
+
+#ifdef TRGT_DEV_BUILD
+// Developer build only (not in include/trgt_hip.h; tests/test_consensus_vote_gpu.py): consensus_vote_kernel on groups and CIGARs given by
+// the caller, launched by the same vote_groups that consensus_repair_batch uses.  Group g: backbone seqs[bb_off[g] .. + bb_len[g]) and the
+// members [group_first[g], group_first[g + 1]); member j: seqs[m_off[j] .. + m_len[j]) with the dense `len << 4 | code` words
+// cigar[cigar_first[j] .. cigar_first[j + 1]) (none: its alignment failed).  out_cap (may be NULL): per group, 0 = the product's formula.
+// count_on_device != 0: the launch of the device chains (grid of n_groups + 3 workgroups, the count read from device memory).
+// out_len[g]: the kernel's raw length word (0xFFFFFFFF: does not fit); the bytes go to out_bytes[out_off[g] .. out_off[g + 1]).
+extern "C" int trgt_dev_consensus_vote(trgt_hip_ctx* c, int64_t n_groups, const uint8_t* seqs, uint64_t seq_bytes, const uint64_t* bb_off, const uint32_t* bb_len,
+                                       const uint64_t* group_first, const uint64_t* m_off, const uint32_t* m_len, const uint32_t* cigar,
+                                       const uint64_t* cigar_first, const uint32_t* out_cap, int32_t count_on_device, uint32_t* out_len, uint8_t* out_bytes,
+                                       const uint64_t* out_off) {
+  if (!c) return TRGT_ERR_INVALID;
+  TRGT_ABI_GUARD(c, dev_consensus_vote(c, n_groups, seqs, seq_bytes, bb_off, bb_len, group_first, m_off, m_len, cigar, cigar_first, out_cap, count_on_device, out_len, out_bytes, out_off));
+}
+#endif
 
 // ---- the deep instantiation of the device-side cluster genotyper is opt-in per context (include/trgt_hip.h)
 extern "C" int32_t trgt_hip_cluster_max_reads_limit(void) { return cld::CL_DEEP_MAX_READS; }
