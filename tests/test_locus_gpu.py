@@ -466,7 +466,11 @@ def test_flank_launch_variants_agree(oracle, mods, monkeypatch):
                      # zero arena, the round-4 HMM fills, the position-per-lane fills of a class one after the other, other claim sizes and
                      # the 128-diagonal tier of the lean kernel
                      ("TRGT_BAND_THREADS", "128"), ("TRGT_BAND_THREADS", "256"), ("TRGT_NO_ZERO_ARENA", "1"), ("TRGT_HMM_NO_PPL", "1"),
-                     ("TRGT_HMM_PPL_SERIAL", "1"), ("TRGT_HMM_PPL_PER_CLASS", "1"), ("TRGT_HMM_PPL_WIDE", "1"), ("TRGT_LEAN_CHUNK", "1"), ("TRGT_LEAN_CHUNK", "16"), ("TRGT_WFA_LEAN_MID_TIER", "1")):
+                     ("TRGT_HMM_PPL_SERIAL", "1"), ("TRGT_HMM_PPL_PER_CLASS", "1"), ("TRGT_HMM_PPL_WIDE", "1"), ("TRGT_LEAN_CHUNK", "1"), ("TRGT_LEAN_CHUNK", "16"), ("TRGT_WFA_LEAN_MID_TIER", "1"),
+                     # the branches of the flank-location plan (span_plan, spans.hip) nothing else takes: the expensive list in front of the
+                     # others on one stream, no seed search over it, a pre-filter that runs every alignment to its end, no band (sequences
+                     # not staged in LDS)
+                     ("TRGT_FLANK_ONE_STREAM", "1"), ("TRGT_NO_HEAVY_WINDOW", "1"), ("TRGT_WFA_NO_EARLY", "1"), ("TRGT_WFA_NO_STAGE", "1")):
         from trgt_amd import _lib
         vctx = _lib.context_with_env(**{env: val})
         try:

@@ -145,8 +145,8 @@ def test_windows_are_in_use_and_some_do_not_stand(oracle, capfd, monkeypatch):
 
 @pytest.mark.parametrize("scoring,flank_len", [((1, 2, 1), 250), ((4, 6, 2), 250), ((2, 5, 1), 150), ((2, 5, 1), 100), ((3, 1, 1), 250), ((1, 0, 1), 200)])
 def test_other_penalties_and_flank_lengths(oracle, scoring, flank_len):
-    # the bound, the margins and whether windows are used at all follow from the penalties and the flank length (window_plan in
-    # find_spans_device): synthetic loci under other settings, every locus against the oracle
+    # the bound, the margins and whether windows are used at all follow from the penalties and the flank length (the window plan of
+    # span_plan, spans.hip): synthetic loci under other settings, every locus against the oracle
     import torch
     from trgt_amd import locus, synth
     from test_locus_gpu import _compare

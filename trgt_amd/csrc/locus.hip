@@ -40,11 +40,6 @@
 
 namespace trgt {
 
-int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci, int64_t n_reads, const uint8_t* d_flank,
-                      const uint64_t* d_piece_off, const uint8_t* d_reads, const uint64_t* d_read_off, const uint32_t* d_read_len,
-                      const uint32_t* d_read_locus, uint32_t max_read_len, int32_t* d_span_start, int32_t* d_span_end,
-                      uint8_t* d_lf_hit, uint8_t* d_rf_hit, const uint32_t* d_heavy_len, uint32_t heavy_tlen_max, bool span_only);
-
 namespace {
 
 struct Seg { const uint8_t* p; uint32_t n; };
@@ -1021,7 +1016,7 @@ int LocusCall::locate_flanks() {
   // and the model tables are made on the device, letting the stages overlap freely is 14 % faster on the 10k-locus batch (1.50 -> 1.71 M
   // loci/s with four contexts) and neutral on the others.
   if (c->knobs.stage_lock) stage_a_token.lock();
-  if ((rc = find_spans_device(c, sp, nl, nr, d_flank, d_piece, d_reads, d_roff, d_rlen, d_rloc, max_read_len, (int32_t*)d_ss, (int32_t*)d_se,
+  if ((rc = find_spans_device(c, sp, nr, d_flank, d_piece, d_reads, d_roff, d_rlen, d_rloc, max_read_len, (int32_t*)d_ss, (int32_t*)d_se,
                               (uint8_t*)d_hl, (uint8_t*)d_hr, d_heavy, heavy_tlen_max > 0 ? heavy_tlen_max - 1 : 0, /*span_only=*/true)))
     return rc;
   if (c->last_wfa_cells_dev) { const int d2h_rc = trgt::d2h(c, h_cells, c->last_wfa_cells_dev, 24, c->stream); if (d2h_rc) return d2h_rc; }

@@ -18,6 +18,7 @@
 //   3. span_combine_kernel per read: threshold test and (lf.end, rf.start) combination.
 #include <algorithm>
 #include <cmath>
+#include <optional>
 
 #include "wfa_host.hpp"
 
@@ -720,372 +721,418 @@ __global__ void long_kept_kernel(const LongWinArgs a) {
     }
 }
 
-// Device-side part shared with trgt_locus_batch: everything already resident, results left on the device.
-int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_loci, int64_t n_reads, const uint8_t* d_flank,
-                      const uint64_t* d_piece_off, const uint8_t* d_reads, const uint64_t* d_read_off, const uint32_t* d_read_len,
-                      const uint32_t* d_read_locus, uint32_t max_read_len, int32_t* d_span_start, int32_t* d_span_end,
-                      uint8_t* d_lf_hit, uint8_t* d_rf_hit, const uint32_t* d_heavy_len, uint32_t heavy_tlen_max, bool span_only) {
-  const uint64_t n_jobs = 2ull * (uint64_t)n_reads;
-  void *d_pos = nullptr, *d_wjobs = nullptr, *d_count = nullptr, *d_span4 = nullptr, *d_nmatch = nullptr;
-  int rc;
-  if ((rc = dev_get(c, S_FS_POS, n_jobs * 4, &d_pos)) || (rc = dev_get(c, S_FS_WFAJOBS, n_jobs * sizeof(JobDev), &d_wjobs)) ||
-      (rc = dev_get_zeroed(c, S_FS_COUNT, 4 * SC_WORDS, &d_count, c->stream)) || (rc = dev_get(c, S_FS_SPAN, n_jobs * 16, &d_span4)) ||
-      (rc = dev_get(c, S_FS_NMATCH, n_jobs * 4, &d_nmatch)))
-    return rc;
-  ScanArgs sa;
-  sa.flank_blob = d_flank; sa.read_blob = d_reads; sa.piece_off = d_piece_off; sa.read_off = d_read_off; sa.read_len = d_read_len;
-  sa.read_locus = d_read_locus; sa.n_jobs = n_jobs; sa.flank_len = p.flank_len; sa.pos = (int32_t*)d_pos; sa.n_match = (int32_t*)d_nmatch;
-  sa.wfa_jobs = (JobDev*)d_wjobs; sa.wfa_count = (uint32_t*)d_count;
-  sa.heavy_len = d_heavy_len; sa.jobs_cap = (uint32_t)n_jobs;
+// ---- The plan of a find_spans_device call: everything that is decided, once, by span_plan() and before anything is enqueued (no HIP
+// call, no buffer of the context).  The stages of SpanCall (below) read the plan and no flank-planning knob.
+struct SpanPlan {
+  int64_t min_matches = 0; double threshold = 0; int32_t scan_min_matches = 0;  // the smallest count_matches() that passes; the combine's test; the scan's sibling rule (0: off)
+  int ring_slots = 0; uint32_t long_tlen = 0, short_max = 0, heavy_tlen_max = 0; bool has_long = false;
+  int32_t win_m = WIN_SEGMENTS_DEFAULT, win_q = 0, win_s0 = 0, win_margin = 0, win_spread = 0, win_tbf = 0; uint32_t win_tlen = 0;  // seeded windows (win_q == 0: none)
+  int32_t hamming_max = 0, indel_ok = 0; bool win_reg = false;  // (win_reg: the windowed launch is the register kernel's, wfa_win.hip)
+  bool split = false, use_filter = false, two_streams = false; int64_t flt_tlen = 0;
+  bool heavy_window = false;  // the seed search runs over the expensive list as well
+  bool heavy_band = false;    // ... and what the pre-filter keeps of it is back-traced inside a band (BandArgs)
+  bool long_window = false;   // the long reads' list goes through the light list's seed search
+  bool long_filter = false, long_band = false; int64_t long_wl = 0, long_step = 0; uint64_t long_cap = 0;  // the window filter of the long reads (LongWinArgs)
+  int flank_threads = 0, heavy_threads = 0, win_threads = 0, band_threads = 0, band_s_max = 0; bool early_reject = false, count_offsets = false;  // (the last two: of the pre-filter's launches)
+};
+static SpanPlan span_plan(const trgt_hip_ctx* c, const trgt_span_params& p, uint64_t n_jobs, uint32_t max_read_len, uint32_t heavy_tlen_max, bool have_heavy_len, bool span_only) {
+  const trgt_knobs& k = c->knobs;
+  const bool wgs = preset_wgs(p.mism, p.gapo, p.gape), filter_pen = preset_has_filter(p.mism, p.gapo, p.gape);
+  SpanPlan P;
   // the smallest count_matches() that passes span_locater.rs:18-22
   const double thr = (double)(uint64_t)p.flank_len * p.min_flank_id_frac;
   int64_t min_matches = thr > 0 ? (int64_t)std::ceil(thr) : 0;
   while (min_matches > 0 && (double)(min_matches - 1) >= thr) --min_matches;
   while ((double)min_matches < thr) ++min_matches;
+  P.min_matches = min_matches; P.threshold = thr;  // (the combine's test: span_locater.rs:46)
   // (the one-wave-per-piece scan of pieces shorter than four bases does not know the sibling and keeps emitting every job)
-  sa.min_matches = span_only && !c->knobs.no_sibling_rule ? (int32_t)std::min<int64_t>(min_matches, 0x7FFFFFFF) : 0;
+  P.scan_min_matches = span_only && !k.no_sibling_rule ? (int32_t)std::min<int64_t>(min_matches, 0x7FFFFFFF) : 0;
   // reads up to long_tlen keep the dedicated kernel at 4 workgroups per CU (LDS: ring + windows <= ~39 KB per alignment)
-  const int ring_slots = std::max(p.mism, p.gapo + p.gape) + 1 + 2 * (p.gape + 1);
-  const int64_t fit = 39000 / (2 * (int64_t)ring_slots + 4) - p.flank_len - 16;
-  const uint32_t long_tlen = (uint32_t)std::max<int64_t>(fit, 64);
-  const bool has_long = max_read_len > long_tlen;
-  void* d_wjobs_long = nullptr;
-  if (has_long && (rc = dev_get(c, S_FS_WFAJOBS_LONG, n_jobs * sizeof(JobDev), &d_wjobs_long))) return rc;
-  sa.wfa_jobs_long = (JobDev*)d_wjobs_long; sa.long_tlen = has_long ? long_tlen : 0xFFFFFFFFu;
-  // Seeded windows (piece_window): eight segments by default; the conditions make a mismatch the cheapest way to spoil a segment
-  // (a gap inside one segment costs o + e, a deletion across t segments o + ((t - 2) q + 2) e >= t x), so that S0 = (segments) x - 1.
-  int32_t win_s0 = 0, win_q = 0, win_margin = 0, win_spread = 0, win_m = WIN_SEGMENTS_DEFAULT; uint32_t win_tlen = 0;
-  void *d_winjobs = nullptr, *d_restjobs = nullptr, *d_score = nullptr;
-  {
-    int m = c->knobs.win_segments;
-    if (m != 4 && m != 6 && m != 8) m = WIN_SEGMENTS_DEFAULT;
-    win_m = m;
-    const int q = p.flank_len / m, x = p.mism, o = p.gapo, e = p.gape;
-    const bool two_launches = d_heavy_len && heavy_tlen_max > 0 && !c->knobs.one_launch;
-    const bool ok = two_launches && !c->knobs.no_window && q >= 12 && x >= 1 && e >= 1 && o >= 0 &&
-                    q * e >= x && o + 2 * e >= 2 * x && o + e >= x;
-    if (ok) {
-      win_s0 = x * m - 1;
-      const int G = win_s0 >= o + e ? (win_s0 - o) / e : 0, C = win_s0 / e;
-      win_q = q; win_margin = G + C; win_spread = 2 * G;
-      win_tlen = (uint32_t)(p.flank_len + 2 * win_margin + win_spread);
-      if (win_tlen + 64 >= max_read_len) win_q = 0;  // reads hardly longer than a window
-    }
-    if (win_q > 0 && ((rc = dev_get(c, S_FS_WINJOBS, n_jobs * sizeof(JobDev), &d_winjobs)) || (rc = dev_get(c, S_FS_RESTJOBS, n_jobs * sizeof(JobDev), &d_restjobs)) ||
-                      (rc = dev_get(c, S_FS_SCORE, n_jobs * 4, &d_score))))
-      return rc;
-  }
-  {
-    KTimer t(c, TRGT_K_FLANK_SCAN);
-    if (p.flank_len >= 4) hipLaunchKernelGGL(flank_scan_wide_kernel, dim3((unsigned)((n_reads + SCAN_READS_PER_WG - 1) / SCAN_READS_PER_WG)), dim3(256), 0, c->stream, sa);
-    else hipLaunchKernelGGL(flank_scan_kernel, dim3((unsigned)((n_jobs + 3) / 4)), dim3(256), 0, c->stream, sa);
-    TRGT_HIP_TRY(c, hipGetLastError());
-    t.stop(0);
-  }
-  tl_mark(c, "scan launched");
-  trgt_wfa_params wp;
-  trgt_wfa_default_params(&wp);  // THREAD_WFA_FLANK (genotype.rs:66-80)
-  wp.metric = 3; wp.mismatch = p.mism; wp.gap_open1 = p.gapo; wp.gap_ext1 = p.gape;
-  wp.span = 1; wp.pattern_begin_free = 0; wp.pattern_end_free = 0; wp.text_begin_free = -1; wp.text_end_free = -1;
-  wp.scope = 1; wp.memory_mode = 0; wp.heuristic = 0;
-  // The number of fallback alignments is known only on the device: the kernel reads it there (n_jobs_dev), the planner sizes
-  // the workspace for the upper bound (every job falls back), and nothing here waits for the GPU -- trgt_locus_batch enqueues
-  // this function chunk after chunk.
-  c->last_wfa_cells_dev = nullptr;
-  WfaLaunch L;
-  L.jobs_dev = (const JobDev*)d_wjobs; L.n_jobs_host = (int64_t)n_jobs; L.n_jobs_dev = (const uint32_t*)d_count;
-  L.n_jobs2_dev = (const uint32_t*)d_count + SC_LIGHT; L.jobs_cap = (uint32_t)n_jobs;
-  L.pat_base = d_flank; L.txt_base = d_reads;
-  const uint32_t short_max = has_long ? long_tlen : max_read_len;
-  L.max_plen = p.flank_len; L.max_tlen = short_max; L.max_sum = (int64_t)p.flank_len + short_max;
-  L.threads = c->knobs.flank_threads;
-  L.timer_slot = TRGT_K_WFA_FLANK;
-  L.n_match = (int32_t*)d_nmatch; L.span4 = (uint32_t*)d_span4;
+  P.ring_slots = std::max(p.mism, p.gapo + p.gape) + 1 + 2 * (p.gape + 1);
+  const int64_t fit = 39000 / (2 * (int64_t)P.ring_slots + 4) - p.flank_len - 16;
+  P.long_tlen = (uint32_t)std::max<int64_t>(fit, 64);
+  P.has_long = max_read_len > P.long_tlen;
+  P.short_max = P.has_long ? P.long_tlen : max_read_len;
   // Two launches.  The front of the list (reads too short to span their locus: 95 % of the wavefront offsets) holds short texts
   // only, so its launch is planned for heavy_tlen_max: a smaller LDS ring per alignment and one more resident workgroup per CU
   // (occupancy is what this latency-bound kernel lives on: 16.9 -> 15.1 ms from 4 to 5 per CU).  The rest follows at the full size.
   // (a catalog with a few long-read loci has heavy_tlen_max beyond the dedicated kernel's texts: those reads are on the long list
   //  anyway, the launch over the expensive alignments is planned for what is left)
-  const bool split = d_heavy_len && heavy_tlen_max > 0 && !c->knobs.one_launch;
-  heavy_tlen_max = std::min(heavy_tlen_max, short_max);
-  bool heavy_window = false;  // the seed search runs over the expensive list as well (below)
-  bool heavy_band = false;    // ... and what the pre-filter keeps of it is back-traced inside a band (BandArgs)
-  bool win_reg = false;       // the windowed launch is the register kernel's (wfa_win.hip)
-  auto window_args = [&]() {
-    WindowArgs wa;
-    wa.flank_blob = d_flank; wa.read_blob = d_reads; wa.wfa_jobs = (const JobDev*)d_wjobs; wa.jobs_cap = (uint32_t)n_jobs; wa.count = (uint32_t*)d_count;
-    wa.win_jobs = (JobDev*)d_winjobs; wa.rest_jobs = (JobDev*)d_restjobs; wa.flank_len = p.flank_len; wa.q = win_q; wa.margin = win_margin; wa.spread = win_spread; wa.tbf = 2 * win_margin + win_spread;
-    wa.front = 0; wa.long_jobs = nullptr; wa.long_rest = nullptr;
-    wa.hamming_max = c->knobs.no_hamming ? 0 : std::min(std::min(win_m - 1, (p.gapo + p.gape - 1) / p.mism), 4);  // (4: the kernel's count is exact up to there)
-    wa.indel_ok = !c->knobs.no_hamming && !c->knobs.no_indel_shortcut && p.mism == 2 && p.gapo == 5 && p.gape == 1 && wa.hamming_max == 2 ? 1 : 0;
-    wa.n_match = (int32_t*)d_nmatch; wa.span4 = (uint32_t*)d_span4;
-    return wa;
-  };
-  auto launch_window = [&](const WindowArgs& wa) {  // on the current stream
-    const dim3 wgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->num_cus * 8, (int64_t)((n_jobs + WIN_JOBS_PER_WG - 1) / WIN_JOBS_PER_WG))));
-    if (win_m == 4) hipLaunchKernelGGL(flank_window_kernel<4>, wgrid, dim3(256), 0, c->stream, wa);
-    else if (win_m == 6) hipLaunchKernelGGL(flank_window_kernel<6>, wgrid, dim3(256), 0, c->stream, wa);
-    else hipLaunchKernelGGL(flank_window_kernel<8>, wgrid, dim3(256), 0, c->stream, wa);
-  };
-  void* d_long_noseed = nullptr;                                   // the long reads' list behind the seed search (when that runs over it)
-  const JobDev* long_in = (const JobDev*)d_wjobs_long; int long_in_count = SC_LONG;
-  c->last_filter_cells_dev = nullptr;
-  bool heavy_join = false;         // the expensive alignments run on the second stream: wait for it before the spans are combined
-  void* heavy_cells_dev = nullptr; // ... and their offset counter lives in workspace set 1
-  if (split) {
-    WfaLaunch LH = L;
-    LH.n_jobs2_dev = nullptr; LH.jobs_cap = 0;
-    LH.max_tlen = heavy_tlen_max; LH.max_sum = (int64_t)p.flank_len + heavy_tlen_max;
+  P.split = have_heavy_len && heavy_tlen_max > 0 && !k.one_launch;
+  P.heavy_tlen_max = std::min(heavy_tlen_max, P.short_max);
+  // Seeded windows (piece_window): eight segments by default; the conditions make a mismatch the cheapest way to spoil a segment
+  // (a gap inside one segment costs o + e, a deletion across t segments o + ((t - 2) q + 2) e >= t x), so that S0 = (segments) x - 1.
+  int m = k.win_segments;
+  if (m != 4 && m != 6 && m != 8) m = WIN_SEGMENTS_DEFAULT;
+  P.win_m = m;
+  const int q = p.flank_len / m, x = p.mism, o = p.gapo, e = p.gape;
+  if (P.split && !k.no_window && q >= 12 && x >= 1 && e >= 1 && o >= 0 && q * e >= x && o + 2 * e >= 2 * x && o + e >= x) {
+    P.win_s0 = x * m - 1;
+    const int G = P.win_s0 >= o + e ? (P.win_s0 - o) / e : 0, C = P.win_s0 / e;
+    P.win_q = q; P.win_margin = G + C; P.win_spread = 2 * G;
+    P.win_tlen = (uint32_t)(p.flank_len + 2 * P.win_margin + P.win_spread);
+    if (P.win_tlen + 64 >= max_read_len) P.win_q = 0;  // reads hardly longer than a window
+  }
+  if (P.win_q > 0) {
+    // only the diagonals that can matter start a windowed alignment: a wavefront of 2 margin + spread + 1 diagonals instead of one per
+    // base of the window, i.e. one strip of one wave per level
+    P.win_tbf = 2 * P.win_margin + P.win_spread;
+    P.hamming_max = k.no_hamming ? 0 : std::min(std::min(P.win_m - 1, (p.gapo + p.gape - 1) / p.mism), 4);  // (4: the kernel's count is exact up to there)
+    P.indel_ok = !k.no_hamming && !k.no_indel_shortcut && wgs && P.hamming_max == 2 ? 1 : 0;
+    // one wave per job with wavefronts and history in registers (wfa_win.hip) where its layout holds the launch; else, and under
+    // TRGT_WIN_LDS (developer build: A/B, tests), the LDS kernel.  The register kernel counts no wavefront offsets.
+    P.win_reg = !k.win_lds && !k.skip_bt && !k.no_spec && wfa_win_fits(p.mism, p.gapo, p.gape, P.win_tbf, P.win_s0, p.flank_len, P.win_tlen);
+  }
+  const bool band_ok = k.heavy_band > 0 && wgs && !k.no_spec && !k.skip_bt && !k.wfa_no_stage;  // (the banded launch exists as the LDS kernel of TRGT's configuration only)
+  if (P.split) {
     // The expensive alignments first meet the register-resident pre-filter (wfa_reg.hip): exact penalty and an upper bound on
     // count_matches() without history or back-trace; only those whose bound reaches the threshold (a quarter of the jobs, 5 % of
     // the wavefront offsets on the bench workload) are aligned again by the back-tracing kernel.  span_locater.rs:18-22 does
     // nothing with the others but drop them.
     // (texts beyond the filter's diagonals are kept unseen, job by job: a batch with a few long reads still filters the others)
-    const int64_t flt_tlen = flank_filter_max_tlen(p.flank_len);
-    const bool filter_pen = (p.mism == 2 && p.gapo == 5 && p.gape == 1) || (p.mism == 1 && p.gapo == 0 && p.gape == 1);  // wgs / targeted presets (cli.rs:271-280)
-    const bool use_filter = filter_pen && flt_tlen >= 2 * (int64_t)p.flank_len &&
-                            heavy_tlen_max >= (uint32_t)p.flank_len && min_matches <= 254 && !c->knobs.no_filter;
+    P.flt_tlen = flank_filter_max_tlen(p.flank_len);
+    P.use_filter = filter_pen && P.flt_tlen >= 2 * (int64_t)p.flank_len &&
+                   P.heavy_tlen_max >= (uint32_t)p.flank_len && min_matches <= 254 && !k.no_filter;
     // Two streams: the expensive alignments (pre-filter, then the back-tracing kernel over what it keeps) run on the second stream
     // NEXT TO the other fallback alignments (segment search, windowed launch, whole-read launch) instead of in front of them.  The
     // filter is bound by VALU issue at three waves per SIMD, the light launches by latency and by their job-claim atomics: they
     // fill each other's gaps (measured: see DESIGN.md).  Workspace set 1 for the back-tracing launch of that stream.
-    const bool two_streams = use_filter && !c->knobs.one_stream;
-    void* cells_heavy = nullptr;
-    if (two_streams) {
-      if (!c->stream2) TRGT_HIP_TRY(c, trgt::make_stream(c, &c->stream2));
-      if (!c->ev_scan) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming));
-      if (!c->ev_heavy) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_heavy, hipEventDisableTiming));
-      TRGT_HIP_TRY(c, hipEventRecord(c->ev_scan, c->stream));
-      TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_scan, 0));
-      std::swap(c->stream, c->stream2);
-    }
-    struct StreamBack { trgt_hip_ctx* c; bool on; ~StreamBack() { if (on) std::swap(c->stream, c->stream2); } } stream_back{c, two_streams};
+    P.two_streams = P.use_filter && !k.one_stream;
     // The expensive list first meets the seed search too.  "Too short to span the locus" says nothing about the flank the read DOES
     // hold: a fifth of these alignments have a penalty below 8 (tools/filter_hist.py) -- the pre-filter let them through after a few
     // levels and the back-tracing kernel aligned them a second time, at the end of this stream's chain.  With seeds they are settled
     // by the substitution shortcut or join the windowed launch of the other stream; the pre-filter sees the jobs WITHOUT seeds only.
-    heavy_window = use_filter && two_streams && win_q > 0 && !c->knobs.no_heavy_window;
-    void* d_noseed = nullptr;
-    if (heavy_window) {
-      if ((rc = dev_get(c, S_FS_NOSEED, n_jobs * sizeof(JobDev), &d_noseed))) return rc;
-      if (!c->ev_hwin) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_hwin, hipEventDisableTiming));
-      WindowArgs wh = window_args();
-      wh.front = 1; wh.rest_jobs = (JobDev*)d_noseed;
-      KTimer t(c, TRGT_K_FLANK_WINDOW);
-      launch_window(wh);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      t.stop(0);
-      TRGT_HIP_TRY(c, hipEventRecord(c->ev_hwin, c->stream));
-    }
-    if (use_filter) {
-      void* d_keepjobs = nullptr;
-      if ((rc = dev_get(c, S_FS_KEEPJOBS, n_jobs * sizeof(JobDev), &d_keepjobs))) return rc;
-      FilterLaunch FL;
-      FL.jobs_dev = heavy_window ? (const JobDev*)d_noseed : (const JobDev*)d_wjobs; FL.n_jobs_host = (int64_t)n_jobs;
-      FL.n_jobs_dev = (const uint32_t*)d_count + (heavy_window ? SC_NOSEED : SC_HEAVY);
-      FL.pat_base = d_flank; FL.txt_base = d_reads; FL.max_plen = p.flank_len; FL.max_tlen = std::min<int64_t>(heavy_tlen_max, flt_tlen);
-      FL.mism = p.mism; FL.gapo = p.gapo; FL.gape = p.gape; FL.count_offsets = c->timing; FL.min_matches = (int32_t)min_matches; FL.early_reject = !c->knobs.no_early; FL.keep_jobs = (JobDev*)d_keepjobs; FL.keep_count = (uint32_t*)d_count + SC_KEEP;
-      if ((rc = flank_filter_launch(c, FL))) return rc;
-      tl_mark(c, "filter launched");
-      LH.jobs_dev = (const JobDev*)d_keepjobs; LH.n_jobs_dev = (const uint32_t*)d_count + SC_KEEP;
-      heavy_band = c->knobs.heavy_band > 0 && p.mism == 2 && p.gapo == 5 && p.gape == 1 && !c->knobs.no_spec && !c->knobs.skip_bt && !c->knobs.wfa_no_stage;  // (the banded launch exists as the LDS kernel of TRGT's configuration only)
-    }
-    if (heavy_band) {  // (see BandArgs) the kept alignments inside their band, one wave each; then whatever is left over the whole read
-      void *d_band = nullptr, *d_hrest = nullptr, *d_bscore = nullptr;
-      if ((rc = dev_get(c, S_FS_BANDJOBS, n_jobs * sizeof(JobDev), &d_band)) || (rc = dev_get(c, S_FS_HRESTJOBS, n_jobs * sizeof(JobDev), &d_hrest)) ||
-          (rc = dev_get(c, S_FS_BSCORE, n_jobs * 4, &d_bscore)))
-        return rc;
-      const int s_max = c->knobs.heavy_band;
-      BandArgs ba;
-      ba.keep_jobs = LH.jobs_dev; ba.n_keep = LH.n_jobs_dev; ba.band_jobs = (JobDev*)d_band; ba.rest_jobs = (JobDev*)d_hrest; ba.count = (uint32_t*)d_count;
-      ba.s_max = s_max; ba.score = (const int32_t*)d_bscore; ba.span4 = (uint32_t*)d_span4; ba.n_match = (int32_t*)d_nmatch;
-      ba.read_off = d_read_off; ba.read_len = d_read_len; ba.i_band = SC_BAND; ba.i_rest = SC_HREST;
-      hipLaunchKernelGGL(heavy_band_kernel, dim3(64), dim3(256), 0, c->stream, ba);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      WfaLaunch LB = LH;
-      LB.jobs_dev = (const JobDev*)d_band; LB.n_jobs_dev = (const uint32_t*)d_count + SC_BAND;
-      LB.max_tlen = (int64_t)p.flank_len + 2 * s_max; LB.max_sum = (int64_t)p.flank_len + LB.max_tlen;
-      LB.score = (int32_t*)d_bscore; LB.kernel_tag = 3; LB.max_score = s_max; LB.threads = c->knobs.band_threads;
-      if (two_streams) LB.buffer_set = 1;
-      trgt_wfa_params wpb = wp;
-      wpb.text_begin_free = 2 * s_max;
-      if ((rc = wfa_launch(c, wpb, LB))) return rc;
-      hipLaunchKernelGGL(band_check_kernel, dim3(64), dim3(256), 0, c->stream, ba);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      LH.jobs_dev = (const JobDev*)d_hrest; LH.n_jobs_dev = (const uint32_t*)d_count + SC_HREST; LH.keep_cells = true;
-    }
-    // three waves per alignment here: the wavefronts of these short texts are narrow (on average less than one 128-diagonal strip per
-    // wave and level), and a wave without a strip still pays the per-level prologue and barrier (7.39 -> 7.21 ms)
-    LH.threads = c->knobs.heavy_threads > 0 ? c->knobs.heavy_threads : (L.threads == 256 ? 192 : L.threads);
-    if (two_streams) LH.buffer_set = 1;
-    if ((rc = wfa_launch(c, wp, LH))) return rc;
-    tl_mark(c, "heavy launch");
-    cells_heavy = c->last_wfa_cells_dev;
-    if (two_streams) {
-      TRGT_HIP_TRY(c, hipEventRecord(c->ev_heavy, c->stream));
-      std::swap(c->stream, c->stream2);
-      stream_back.on = false;
-      heavy_join = true;
-    } else {
-      // offsets of the first launch, kept next to the running total (cells[1]): the roofline of the dominant launch counts its own
-      TRGT_HIP_TRY(c, hipMemcpyAsync((uint8_t*)c->last_wfa_cells_dev + 8, c->last_wfa_cells_dev, 8, hipMemcpyDeviceToDevice, c->stream));
-    }
-    heavy_cells_dev = cells_heavy;
-    L.n_jobs_dev = (const uint32_t*)d_count + SC_ZERO;  // always 0: this launch takes the back part of the list only
-    L.keep_cells = !two_streams; L.timer_slot = TRGT_K_WFA_FLANK_REST;  // (two streams: the first launch of THIS stream resets the counter of set 0)
-    if (win_q > 0) {  // the alignments with a seeded window: short texts, more of them per CU; then sort out which of them stand
-      // (the other stream's seed search appends to the same windowed list; this stream's search waits for it rather than running next to
-      //  it: the pre-filter behind that one is the critical path of a call, this stream has 0.5 ms of slack -- side by side the short
-      //  search took 0.34 instead of 0.08 ms)
-      if (heavy_window) TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_hwin, 0));
-      {
-        KTimer t(c, TRGT_K_FLANK_WINDOW);
-        WindowArgs wl2 = window_args();
-        if (has_long && !c->knobs.no_long_window) {  // the long reads' alignments meet the seed search too: shortcuts and windows do not care how long the read is
-          if ((rc = dev_get(c, S_FS_LONGNOSEED, n_jobs * sizeof(JobDev), &d_long_noseed))) return rc;
-          wl2.long_jobs = (const JobDev*)d_wjobs_long; wl2.long_rest = (JobDev*)d_long_noseed;
-          long_in = (const JobDev*)d_long_noseed; long_in_count = SC_LNOSEED;
-        }
-        launch_window(wl2);
-        TRGT_HIP_TRY(c, hipGetLastError());
-        t.stop(0);
-      }
-      WfaLaunch LW = L;
-      LW.jobs_dev = (const JobDev*)d_winjobs; LW.n_jobs_dev = (const uint32_t*)d_count + SC_WIN; LW.n_jobs2_dev = nullptr; LW.jobs_cap = 0;
-      LW.max_tlen = win_tlen; LW.max_sum = (int64_t)p.flank_len + win_tlen;
-      LW.score = (int32_t*)d_score; LW.kernel_tag = 2; LW.max_score = win_s0;
-      // only the diagonals that can matter start the alignment: a wavefront of 2 margin + spread + 1 diagonals instead of one per base
-      // of the window, i.e. one strip of one wave per level
-      LW.threads = c->knobs.win_threads;
-      trgt_wfa_params wpw = wp;
-      wpw.text_begin_free = 2 * win_margin + win_spread;
-      // one wave per job with wavefronts and history in registers (wfa_win.hip) where its layout holds the launch; else, and under
-      // TRGT_WIN_LDS (developer build: A/B, tests), the LDS kernel.  The register kernel counts no wavefront offsets.
-      win_reg = !c->knobs.win_lds && !c->knobs.skip_bt && !c->knobs.no_spec && wfa_win_fits(p.mism, p.gapo, p.gape, wpw.text_begin_free, win_s0, p.flank_len, win_tlen);
-      if (win_reg) {
-        WfaWinLaunch WR;
-        WR.jobs_dev = LW.jobs_dev; WR.n_jobs_host = (int64_t)n_jobs; WR.n_jobs_dev = LW.n_jobs_dev; WR.pat_base = d_flank; WR.txt_base = d_reads;
-        WR.tbf = wpw.text_begin_free; WR.s_max = win_s0; WR.counter = (unsigned int*)d_count + SC_WINCLAIM; WR.fallback = (unsigned int*)d_count + SC_WINFALL;
-        WR.score = (int32_t*)d_score; WR.n_match = (int32_t*)d_nmatch; WR.span4 = (uint32_t*)d_span4; WR.timer_slot = LW.timer_slot;
-        if ((rc = wfa_win_launch(c, WR))) return rc;
-      } else {
-        if ((rc = wfa_launch(c, wpw, LW))) return rc;
-        L.keep_cells = true;
-      }
-      tl_mark(c, "window launch");
-      WinCheckArgs wc;
-      wc.win_jobs = (const JobDev*)d_winjobs; wc.n_win = (const uint32_t*)d_count + SC_WIN; wc.score = (const int32_t*)d_score;
-      wc.span4 = (uint32_t*)d_span4; wc.n_match = (int32_t*)d_nmatch; wc.s0 = win_s0;
-      wc.wfa_jobs = (JobDev*)d_restjobs; wc.wfa_count = (uint32_t*)d_count; wc.jobs_cap = (uint32_t)n_jobs;
-      wc.read_off = d_read_off; wc.read_len = d_read_len; wc.long_rest = (JobDev*)d_long_noseed; wc.long_tlen = long_tlen;
-      hipLaunchKernelGGL(window_check_kernel, dim3(256), dim3(256), 0, c->stream, wc);
-      TRGT_HIP_TRY(c, hipGetLastError());
-      L.jobs_dev = (const JobDev*)d_restjobs; L.n_jobs_dev = (const uint32_t*)d_count + SC_REST; L.n_jobs2_dev = nullptr; L.jobs_cap = 0;
+    P.heavy_window = P.use_filter && P.two_streams && P.win_q > 0 && !k.no_heavy_window;
+    P.heavy_band = P.use_filter && band_ok;
+  }
+  P.long_window = P.has_long && P.win_q > 0 && !k.no_long_window;  // shortcuts and windows do not care how long the read is
+  if (P.has_long) {  // the pre-filter over windows of the long reads (see LongWinArgs): what it rejects never reaches the exact kernel
+    const int64_t wl = flank_filter_max_tlen(p.flank_len);
+    const int64_t span_max = 2 * (int64_t)p.flank_len + p.gapo + 8, step = wl - span_max;
+    // It pays where the exact kernel is the generic one (wavefronts in HBM): texts beyond what the LDS kernel of wfa_launch takes
+    // (ring of 11 levels x 2 B + 4 B of windows per diagonal in 96 KB: about 3 500 bases for 250-base pieces).  Reads just above the
+    // dedicated launches' length (cfg4: up to 1 300 bases) go to that LDS kernel, and the extra filter launch cost 5 % there.
+    const int64_t lds_kernel_tlen = (96 * 1024) / (2 * P.ring_slots + 4) - p.flank_len - 32;
+    P.long_filter = filter_pen && min_matches >= 1 && min_matches <= 254 && step >= 256 && (int64_t)max_read_len > lds_kernel_tlen &&
+                    !k.no_filter && !k.no_long_filter;
+    if (P.long_filter) {
+      const uint64_t w_max = (uint64_t)((int64_t)max_read_len > wl ? ((int64_t)max_read_len - wl + step - 1) / step + 1 : 1);
+      P.long_cap = std::min<uint64_t>((uint64_t)n_jobs * w_max, 1ull << 21);
+      P.long_wl = wl; P.long_step = step;
+      P.long_band = band_ok && max_read_len < 0xF000u;
     }
   }
-  if ((rc = wfa_launch(c, wp, L))) return rc;
-  tl_mark(c, "rest launch");
-  if (!split) TRGT_HIP_TRY(c, hipMemcpyAsync((uint8_t*)c->last_wfa_cells_dev + 8, c->last_wfa_cells_dev, 8, hipMemcpyDeviceToDevice, c->stream));
-  if (has_long) {  // the long reads: same parameters, workspace and kernel choice planned for their size
-    WfaLaunch L2 = L;
-    L2.jobs_dev = long_in; L2.n_jobs_dev = (const uint32_t*)d_count + long_in_count; L2.n_jobs2_dev = nullptr; L2.jobs_cap = 0;
-    L2.max_tlen = max_read_len; L2.max_sum = (int64_t)p.flank_len + max_read_len;
-    L2.keep_cells = true; L2.timer_slot = TRGT_K_WFA_FLANK_REST;
-    // the pre-filter over windows of the long reads (see LongWinArgs): what it rejects never reaches the exact kernel
-    {
-      const int64_t wl = flank_filter_max_tlen(p.flank_len);
-      const int64_t span_max = 2 * (int64_t)p.flank_len + p.gapo + 8, step = wl - span_max;
-      // It pays where the exact kernel is the generic one (wavefronts in HBM): texts beyond what the LDS kernel of wfa_launch takes
-      // (ring of 11 levels x 2 B + 4 B of windows per diagonal in 96 KB: about 3 500 bases for 250-base pieces).  Reads just above the
-      // dedicated launches' length (cfg4: up to 1 300 bases) go to that LDS kernel, and the extra filter launch cost 5 % there.
-      const int64_t lds_kernel_tlen = (96 * 1024) / (2 * ring_slots + 4) - p.flank_len - 32;
-      if (((p.mism == 2 && p.gapo == 5 && p.gape == 1) || (p.mism == 1 && p.gapo == 0 && p.gape == 1)) && min_matches >= 1 && min_matches <= 254 && step >= 256 && (int64_t)max_read_len > lds_kernel_tlen &&
-          !c->knobs.no_filter && !c->knobs.no_long_filter) {
-        const uint64_t w_max = (uint64_t)((int64_t)max_read_len > wl ? ((int64_t)max_read_len - wl + step - 1) / step + 1 : 1);
-        const uint64_t cap = std::min<uint64_t>((uint64_t)n_jobs * w_max, 1ull << 21);
-        void *d_sub = nullptr, *d_parent = nullptr, *d_subkeep = nullptr, *d_jobkeep = nullptr, *d_kept = nullptr, *d_lwc = nullptr;
-        if ((rc = dev_get(c, S_LW_SUB, cap * sizeof(JobDev), &d_sub)) ||
-            (rc = dev_get(c, S_LW_PARENT, cap * 4, &d_parent)) || (rc = dev_get(c, S_LW_SUBKEEP, cap, &d_subkeep)) ||
-            (rc = dev_get(c, S_LW_JOBKEEP, n_jobs, &d_jobkeep)) || (rc = dev_get(c, S_LW_KEPT, n_jobs * sizeof(JobDev), &d_kept)) ||
-            (rc = dev_get_zeroed(c, S_LW_COUNT, 16, &d_lwc, c->stream)))
-          return rc;
-        LongWinArgs lw;
-        lw.jobs = long_in; lw.n_jobs = (const uint32_t*)d_count + long_in_count; 
-        lw.sub = (JobDev*)d_sub; lw.parent = (uint32_t*)d_parent; lw.sub_keep = (uint8_t*)d_subkeep; lw.n_sub = (uint32_t*)d_lwc; lw.cap = (uint32_t)cap;
-        lw.job_keep = (uint8_t*)d_jobkeep; lw.kept = (JobDev*)d_kept; lw.n_kept = (uint32_t*)d_lwc + 1; lw.wl = (int32_t)wl; lw.step = (int32_t)step;
-        const bool long_band = c->knobs.heavy_band > 0 && p.mism == 2 && p.gapo == 5 && p.gape == 1 && !c->knobs.no_spec && !c->knobs.skip_bt && !c->knobs.wfa_no_stage && max_read_len < 0xF000u;
-        void *d_sband = nullptr, *d_jbest = nullptr, *d_jrej = nullptr;
-        if (long_band && ((rc = dev_get(c, S_LW_SUBBAND, cap * 4, &d_sband)) || (rc = dev_get(c, S_LW_JOBBEST, n_jobs * 4, &d_jbest)) || (rc = dev_get(c, S_LW_JOBREJ, n_jobs * 4, &d_jrej)))) return rc;
-        lw.sub_band = (const uint32_t*)d_sband; lw.job_best = (uint32_t*)d_jbest; lw.job_rej = (uint32_t*)d_jrej;
-        const dim3 g((unsigned)c->num_cus * 2), b(256);
-        hipLaunchKernelGGL(long_windows_kernel, g, b, 0, c->stream, lw);
-        TRGT_HIP_TRY(c, hipGetLastError());
-        FilterLaunch FW;
-        FW.jobs_dev = (const JobDev*)d_sub; FW.n_jobs_host = (int64_t)cap; FW.n_jobs_dev = (const uint32_t*)d_lwc;
-        FW.pat_base = d_flank; FW.txt_base = d_reads; FW.max_plen = p.flank_len; FW.max_tlen = wl;
-        FW.mism = p.mism; FW.gapo = p.gapo; FW.gape = p.gape; FW.min_matches = (int32_t)min_matches; FW.early_reject = !c->knobs.no_early; FW.keep = (uint8_t*)d_subkeep; FW.band = (uint32_t*)d_sband; FW.set = 1;
-        if ((rc = flank_filter_launch(c, FW))) return rc;
-        hipLaunchKernelGGL(long_verdict_kernel, g, b, 0, c->stream, lw);
-        hipLaunchKernelGGL(long_kept_kernel, g, b, 0, c->stream, lw);
-        TRGT_HIP_TRY(c, hipGetLastError());
-        L2.jobs_dev = (const JobDev*)d_kept; L2.n_jobs_dev = (const uint32_t*)d_lwc + 1;
-        if (long_band) {  // the kept reads whose windows named penalty and end diagonal: inside their band, as the short reads (BandArgs)
-          void *d_lband = nullptr, *d_lrest = nullptr, *d_lscore = nullptr;
-          if ((rc = dev_get(c, S_LW_BANDJOBS, n_jobs * sizeof(JobDev), &d_lband)) || (rc = dev_get(c, S_LW_RESTJOBS, n_jobs * sizeof(JobDev), &d_lrest)) ||
-              (rc = dev_get(c, S_LW_BSCORE, n_jobs * 4, &d_lscore)))
-            return rc;
-          const int s_max = c->knobs.heavy_band;
-          BandArgs ba;
-          ba.keep_jobs = (const JobDev*)d_kept; ba.n_keep = (const uint32_t*)d_lwc + 1; ba.band_jobs = (JobDev*)d_lband; ba.rest_jobs = (JobDev*)d_lrest; ba.count = (uint32_t*)d_count;
-          ba.s_max = s_max; ba.score = (const int32_t*)d_lscore; ba.span4 = (uint32_t*)d_span4; ba.n_match = (int32_t*)d_nmatch;
-          ba.read_off = d_read_off; ba.read_len = d_read_len; ba.i_band = SC_LBAND; ba.i_rest = SC_LREST;
-          hipLaunchKernelGGL(heavy_band_kernel, dim3(64), dim3(256), 0, c->stream, ba);
-          TRGT_HIP_TRY(c, hipGetLastError());
-          WfaLaunch LB = L2;
-          LB.jobs_dev = (const JobDev*)d_lband; LB.n_jobs_dev = (const uint32_t*)d_count + SC_LBAND;
-          LB.max_tlen = (int64_t)p.flank_len + 2 * s_max; LB.max_sum = (int64_t)p.flank_len + LB.max_tlen;
-          LB.score = (int32_t*)d_lscore; LB.kernel_tag = 3; LB.max_score = s_max; LB.threads = c->knobs.band_threads;
-          trgt_wfa_params wpb = wp;
-          wpb.text_begin_free = 2 * s_max;
-          if ((rc = wfa_launch(c, wpb, LB))) return rc;
-          hipLaunchKernelGGL(band_check_kernel, dim3(64), dim3(256), 0, c->stream, ba);
-          TRGT_HIP_TRY(c, hipGetLastError());
-          L2.jobs_dev = (const JobDev*)d_lrest; L2.n_jobs_dev = (const uint32_t*)d_count + SC_LREST;
-        }
-      }
-    }
-    if ((rc = wfa_launch(c, wp, L2))) return rc;
+  P.flank_threads = k.flank_threads; P.win_threads = k.win_threads; P.band_threads = k.band_threads; P.band_s_max = k.heavy_band;
+  // three waves per expensive alignment: the wavefronts of these short texts are narrow (on average less than one 128-diagonal strip per
+  // wave and level), and a wave without a strip still pays the per-level prologue and barrier (7.39 -> 7.21 ms)
+  P.heavy_threads = k.heavy_threads > 0 ? k.heavy_threads : (k.flank_threads == 256 ? 192 : k.flank_threads);
+  P.early_reject = !k.no_early; P.count_offsets = c->timing;
+  return P;
+}
+struct JobList { const JobDev* jobs; const uint32_t* count; };  // a device-built job list and the word that holds its length
+struct OnStream2 {  // inside this scope the context's launches go to its second stream
+  trgt_hip_ctx* c;
+  explicit OnStream2(trgt_hip_ctx* c_) : c(c_) { std::swap(c->stream, c->stream2); }
+  ~OnStream2() { std::swap(c->stream, c->stream2); }
+};
+// The state of one find_spans_device call: arguments, plan, workspace and the three base launch descriptors.  find_spans_device (below)
+// runs the stages in order; what a stage leaves for a later one is a member.  The number of fallback alignments is known only on the
+// device: the kernels read it there (n_jobs_dev), the workspace is sized for the upper bound (every job falls back), and nothing here
+// waits for the GPU -- trgt_locus_batch enqueues this function chunk after chunk.
+struct SpanCall {
+  trgt_hip_ctx* const c; const trgt_span_params& p; const int64_t n_reads; const uint64_t n_jobs;
+  const uint8_t* d_flank; const uint64_t* d_piece_off; const uint8_t* d_reads; const uint64_t* d_read_off; const uint32_t* d_read_len; const uint32_t* d_read_locus;
+  const uint32_t max_read_len; int32_t* d_span_start; int32_t* d_span_end; uint8_t* d_lf_hit; uint8_t* d_rf_hit; const uint32_t* d_heavy_len;
+  const SpanPlan plan;
+  // workspace (long_noseed: the long reads' list behind the seed search, when that runs over it)
+  JobDev *wjobs = nullptr, *wjobs_long = nullptr, *winjobs = nullptr, *restjobs = nullptr, *long_noseed = nullptr;
+  uint32_t *count = nullptr, *span4 = nullptr; int32_t *pos = nullptr, *nmatch = nullptr, *score = nullptr;
+  // launches: the alignment parameters; the descriptors of the expensive list, the light list (after the seeded windows: the rest list) and the long reads
+  trgt_wfa_params wp; WfaLaunch heavy, light, longl;
+  JobList long_in{nullptr, nullptr};  // the long reads' list
+  bool set_started[2] = {false, false}; void* heavy_cells = nullptr;  // see launch()
+  template <class T> int get(int slot, size_t bytes, T*& out) { void* v = nullptr; const int rc = dev_get(c, slot, bytes, &v); out = (T*)v; return rc; }
+  int seed_search(bool front, JobDev* rest, JobDev* long_rest);
+  int band_backtrace(JobList& list, int slot_band, int slot_rest, int slot_score, int i_band, int i_rest, const WfaLaunch& base, int buffer_set);
+  // ---- The offset counters (16 bytes per buffer set: [0] a running total, [1] see below).  The first wfa_launch of a call on a buffer
+  // set resets that set's counter, every later one keeps counting into it; c->last_wfa_cells_dev, which the caller reads, is the
+  // counter of the call's last launch -- one on set 0.  Its [1] holds the offsets of the launches over the expensive list (without
+  // two launches: of the one launch over all short reads), the roofline of the dominant launch counts its own: on one stream these
+  // are what set 0 has counted when first_launch_done() is called; on two streams they are the total of set 1, merged at the join.
+  int launch(const trgt_wfa_params& wpl, WfaLaunch L) {
+    bool& started = set_started[L.buffer_set ? 1 : 0];
+    L.keep_cells = started; started = true;
+    return wfa_launch(c, wpl, L);
   }
-  if (heavy_join) {
-    TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_heavy, 0));
-    // one counter pair again: [0] all flank alignments, [1] those of the launch over the expensive ones
-    hipLaunchKernelGGL(cells_merge_kernel, dim3(1), dim3(1), 0, c->stream, (unsigned long long*)c->last_wfa_cells_dev, (const unsigned long long*)heavy_cells_dev);
+  int first_launch_done() {
+    if (plan.two_streams) { heavy_cells = c->last_wfa_cells_dev; return TRGT_OK; }
+    TRGT_HIP_TRY(c, hipMemcpyAsync((uint8_t*)c->last_wfa_cells_dev + 8, c->last_wfa_cells_dev, 8, hipMemcpyDeviceToDevice, c->stream));
+    return TRGT_OK;
+  }
+  int merge_cells() {  // one counter pair again: [0] all flank alignments, [1] those of the launches over the expensive ones
+    hipLaunchKernelGGL(cells_merge_kernel, dim3(1), dim3(1), 0, c->stream, (unsigned long long*)c->last_wfa_cells_dev, (const unsigned long long*)heavy_cells);
     TRGT_HIP_TRY(c, hipGetLastError());
+    return TRGT_OK;
+  }
+  // the stages, in the order find_spans_device calls them
+  int workspace(), scan(), heavy_list(), light_windows(), rest_launch(), long_reads(), join_and_combine(), debug_report();
+};
+int SpanCall::workspace() {  // ... and the base launch descriptors over it
+  int rc; void* zeroed = nullptr;
+  if ((rc = get(S_FS_POS, n_jobs * 4, pos)) || (rc = get(S_FS_WFAJOBS, n_jobs * sizeof(JobDev), wjobs)) || (rc = dev_get_zeroed(c, S_FS_COUNT, 4 * SC_WORDS, &zeroed, c->stream)) ||
+      (rc = get(S_FS_SPAN, n_jobs * 16, span4)) || (rc = get(S_FS_NMATCH, n_jobs * 4, nmatch)))
+    return rc;
+  count = (uint32_t*)zeroed;
+  if (plan.has_long && (rc = get(S_FS_WFAJOBS_LONG, n_jobs * sizeof(JobDev), wjobs_long))) return rc;
+  if (plan.win_q > 0 && ((rc = get(S_FS_WINJOBS, n_jobs * sizeof(JobDev), winjobs)) || (rc = get(S_FS_RESTJOBS, n_jobs * sizeof(JobDev), restjobs)) ||
+                         (rc = get(S_FS_SCORE, n_jobs * 4, score))))
+    return rc;
+  long_in = {wjobs_long, count + SC_LONG};
+  trgt_wfa_default_params(&wp);  // THREAD_WFA_FLANK (genotype.rs:66-80)
+  wp.metric = 3; wp.mismatch = p.mism; wp.gap_open1 = p.gapo; wp.gap_ext1 = p.gape;
+  wp.span = 1; wp.pattern_begin_free = 0; wp.pattern_end_free = 0; wp.text_begin_free = -1; wp.text_end_free = -1;
+  wp.scope = 1; wp.memory_mode = 0; wp.heuristic = 0;
+  c->last_wfa_cells_dev = nullptr; c->last_filter_cells_dev = nullptr;
+  WfaLaunch L;  // the two-ended list as the scan leaves it, planned for the short reads
+  L.jobs_dev = wjobs; L.n_jobs_host = (int64_t)n_jobs; L.n_jobs_dev = count; L.n_jobs2_dev = count + SC_LIGHT; L.jobs_cap = (uint32_t)n_jobs;
+  L.pat_base = d_flank; L.txt_base = d_reads;
+  L.max_plen = p.flank_len; L.max_tlen = plan.short_max; L.max_sum = (int64_t)p.flank_len + plan.short_max;
+  L.threads = plan.flank_threads; L.timer_slot = TRGT_K_WFA_FLANK;
+  L.n_match = nmatch; L.span4 = span4;
+  heavy = light = longl = L;
+  heavy.n_jobs2_dev = nullptr; heavy.jobs_cap = 0;  // the front of the list, on workspace set 1 when it has a stream of its own
+  heavy.max_tlen = plan.heavy_tlen_max; heavy.max_sum = (int64_t)p.flank_len + plan.heavy_tlen_max;
+  heavy.threads = plan.heavy_threads; heavy.buffer_set = plan.two_streams ? 1 : 0;
+  if (plan.split) { light.n_jobs_dev = count + SC_ZERO; light.timer_slot = TRGT_K_WFA_FLANK_REST; }  // (SC_ZERO, always 0: this launch takes the back part of the list only)
+  longl.n_jobs2_dev = nullptr; longl.jobs_cap = 0;  // same parameters, workspace and kernel choice planned for the long reads' size
+  longl.max_tlen = max_read_len; longl.max_sum = (int64_t)p.flank_len + max_read_len; longl.timer_slot = TRGT_K_WFA_FLANK_REST;
+  return TRGT_OK;
+}
+int SpanCall::scan() {
+  ScanArgs sa;
+  sa.flank_blob = d_flank; sa.read_blob = d_reads; sa.piece_off = d_piece_off; sa.read_off = d_read_off; sa.read_len = d_read_len;
+  sa.read_locus = d_read_locus; sa.n_jobs = n_jobs; sa.flank_len = p.flank_len; sa.pos = pos; sa.n_match = nmatch;
+  sa.wfa_jobs = wjobs; sa.wfa_count = count; sa.heavy_len = d_heavy_len; sa.jobs_cap = (uint32_t)n_jobs;
+  sa.min_matches = plan.scan_min_matches;
+  sa.wfa_jobs_long = wjobs_long; sa.long_tlen = plan.has_long ? plan.long_tlen : 0xFFFFFFFFu;
+  KTimer t(c, TRGT_K_FLANK_SCAN);
+  if (p.flank_len >= 4) hipLaunchKernelGGL(flank_scan_wide_kernel, dim3((unsigned)((n_reads + SCAN_READS_PER_WG - 1) / SCAN_READS_PER_WG)), dim3(256), 0, c->stream, sa);
+  else hipLaunchKernelGGL(flank_scan_kernel, dim3((unsigned)((n_jobs + 3) / 4)), dim3(256), 0, c->stream, sa);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  t.stop(0);
+  tl_mark(c, "scan launched");
+  return TRGT_OK;
+}
+// The seed search on the current stream, over the front of the two-ended list or over its back (then with the long reads' list behind it,
+// if long_rest is given): shortcuts, windowed jobs to winjobs, the jobs without a window to rest / long_rest.
+int SpanCall::seed_search(bool front, JobDev* rest, JobDev* long_rest) {
+  WindowArgs wa;
+  wa.flank_blob = d_flank; wa.read_blob = d_reads; wa.wfa_jobs = wjobs; wa.jobs_cap = (uint32_t)n_jobs; wa.count = count;
+  wa.win_jobs = winjobs; wa.rest_jobs = rest; wa.flank_len = p.flank_len; wa.q = plan.win_q; wa.margin = plan.win_margin; wa.spread = plan.win_spread; wa.tbf = plan.win_tbf;
+  wa.front = front ? 1 : 0; wa.long_jobs = long_rest ? wjobs_long : nullptr; wa.long_rest = long_rest;
+  wa.hamming_max = plan.hamming_max; wa.indel_ok = plan.indel_ok;
+  wa.n_match = nmatch; wa.span4 = span4;
+  KTimer t(c, TRGT_K_FLANK_WINDOW);
+  const dim3 wgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->num_cus * 8, (int64_t)((n_jobs + WIN_JOBS_PER_WG - 1) / WIN_JOBS_PER_WG))));
+  if (plan.win_m == 4) hipLaunchKernelGGL(flank_window_kernel<4>, wgrid, dim3(256), 0, c->stream, wa);
+  else if (plan.win_m == 6) hipLaunchKernelGGL(flank_window_kernel<6>, wgrid, dim3(256), 0, c->stream, wa);
+  else hipLaunchKernelGGL(flank_window_kernel<8>, wgrid, dim3(256), 0, c->stream, wa);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  t.stop(0);
+  return TRGT_OK;
+}
+// The banded back-trace (see BandArgs) of a kept list: the alignments inside their band, one wave each, by a launch like `base` on the
+// given buffer set; `list` then names whatever is left over for the launch over the whole read.
+int SpanCall::band_backtrace(JobList& list, int slot_band, int slot_rest, int slot_score, int i_band, int i_rest, const WfaLaunch& base, int buffer_set) {
+  int rc; JobDev *band = nullptr, *rest = nullptr; int32_t* bscore = nullptr;
+  if ((rc = get(slot_band, n_jobs * sizeof(JobDev), band)) || (rc = get(slot_rest, n_jobs * sizeof(JobDev), rest)) || (rc = get(slot_score, n_jobs * 4, bscore)))
+    return rc;
+  const int s_max = plan.band_s_max;
+  BandArgs ba;
+  ba.keep_jobs = list.jobs; ba.n_keep = list.count; ba.band_jobs = band; ba.rest_jobs = rest; ba.count = count;
+  ba.s_max = s_max; ba.score = bscore; ba.span4 = span4; ba.n_match = nmatch;
+  ba.read_off = d_read_off; ba.read_len = d_read_len; ba.i_band = i_band; ba.i_rest = i_rest;
+  hipLaunchKernelGGL(heavy_band_kernel, dim3(64), dim3(256), 0, c->stream, ba);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  WfaLaunch LB = base;
+  LB.jobs_dev = band; LB.n_jobs_dev = count + i_band;
+  LB.max_tlen = (int64_t)p.flank_len + 2 * s_max; LB.max_sum = (int64_t)p.flank_len + LB.max_tlen;
+  LB.score = bscore; LB.kernel_tag = 3; LB.max_score = s_max; LB.threads = plan.band_threads; LB.buffer_set = buffer_set;
+  trgt_wfa_params wpb = wp;
+  wpb.text_begin_free = 2 * s_max;
+  if ((rc = launch(wpb, LB))) return rc;
+  hipLaunchKernelGGL(band_check_kernel, dim3(64), dim3(256), 0, c->stream, ba);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  list = {rest, count + i_rest};
+  return TRGT_OK;
+}
+// The expensive list, on the second stream where the plan says so: seed search over the front of the list, pre-filter, banded
+// back-trace of what it keeps, back-tracing launch over the rest of that.  Leaves the event the join waits for.
+int SpanCall::heavy_list() {
+  int rc;
+  std::optional<OnStream2> on_stream2;
+  if (plan.two_streams) {
+    if (!c->stream2) TRGT_HIP_TRY(c, trgt::make_stream(c, &c->stream2));
+    if (!c->ev_scan) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_scan, hipEventDisableTiming));
+    if (!c->ev_heavy) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_heavy, hipEventDisableTiming));
+    TRGT_HIP_TRY(c, hipEventRecord(c->ev_scan, c->stream));
+    TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream2, c->ev_scan, 0));
+    on_stream2.emplace(c);
+  }
+  JobList list{wjobs, count + SC_HEAVY};
+  if (plan.heavy_window) {
+    JobDev* noseed = nullptr;
+    if ((rc = get(S_FS_NOSEED, n_jobs * sizeof(JobDev), noseed))) return rc;
+    if (!c->ev_hwin) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_hwin, hipEventDisableTiming));
+    if ((rc = seed_search(true, noseed, nullptr))) return rc;
+    TRGT_HIP_TRY(c, hipEventRecord(c->ev_hwin, c->stream));
+    list = {noseed, count + SC_NOSEED};
+  }
+  if (plan.use_filter) {
+    JobDev* keepjobs = nullptr;
+    if ((rc = get(S_FS_KEEPJOBS, n_jobs * sizeof(JobDev), keepjobs))) return rc;
+    FilterLaunch FL;
+    FL.jobs_dev = list.jobs; FL.n_jobs_host = (int64_t)n_jobs; FL.n_jobs_dev = list.count;
+    FL.pat_base = d_flank; FL.txt_base = d_reads; FL.max_plen = p.flank_len; FL.max_tlen = std::min<int64_t>(plan.heavy_tlen_max, plan.flt_tlen);
+    FL.mism = p.mism; FL.gapo = p.gapo; FL.gape = p.gape; FL.count_offsets = plan.count_offsets; FL.min_matches = (int32_t)plan.min_matches; FL.early_reject = plan.early_reject;
+    FL.keep_jobs = keepjobs; FL.keep_count = count + SC_KEEP;
+    if ((rc = flank_filter_launch(c, FL))) return rc;
+    tl_mark(c, "filter launched");
+    list = {keepjobs, count + SC_KEEP};
+  }
+  if (plan.heavy_band && (rc = band_backtrace(list, S_FS_BANDJOBS, S_FS_HRESTJOBS, S_FS_BSCORE, SC_BAND, SC_HREST, heavy, heavy.buffer_set))) return rc;
+  WfaLaunch LH = heavy;
+  LH.jobs_dev = list.jobs; LH.n_jobs_dev = list.count;
+  if ((rc = launch(wp, LH))) return rc;
+  tl_mark(c, "heavy launch");
+  if ((rc = first_launch_done())) return rc;
+  if (plan.two_streams) TRGT_HIP_TRY(c, hipEventRecord(c->ev_heavy, c->stream));
+  return TRGT_OK;
+}
+// The alignments of the light list with a seeded window: short texts, more of them per CU; then sort out which of them stand.
+int SpanCall::light_windows() {
+  int rc;
+  // (the other stream's seed search appends to the same windowed list; this stream's search waits for it rather than running next to
+  //  it: the pre-filter behind that one is the critical path of a call, this stream has 0.5 ms of slack -- side by side the short
+  //  search took 0.34 instead of 0.08 ms)
+  if (plan.heavy_window) TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_hwin, 0));
+  if (plan.long_window) {  // the long reads' alignments meet the seed search too
+    if ((rc = get(S_FS_LONGNOSEED, n_jobs * sizeof(JobDev), long_noseed))) return rc;
+    long_in = {long_noseed, count + SC_LNOSEED};
+  }
+  if ((rc = seed_search(false, restjobs, long_noseed))) return rc;
+  if (plan.win_reg) {
+    WfaWinLaunch WR;
+    WR.jobs_dev = winjobs; WR.n_jobs_host = (int64_t)n_jobs; WR.n_jobs_dev = count + SC_WIN; WR.pat_base = d_flank; WR.txt_base = d_reads;
+    WR.tbf = plan.win_tbf; WR.s_max = plan.win_s0; WR.counter = count + SC_WINCLAIM; WR.fallback = count + SC_WINFALL;
+    WR.score = score; WR.n_match = nmatch; WR.span4 = span4; WR.timer_slot = light.timer_slot;
+    if ((rc = wfa_win_launch(c, WR))) return rc;
+  } else {
+    WfaLaunch LW = light;
+    LW.jobs_dev = winjobs; LW.n_jobs_dev = count + SC_WIN; LW.n_jobs2_dev = nullptr; LW.jobs_cap = 0;
+    LW.max_tlen = plan.win_tlen; LW.max_sum = (int64_t)p.flank_len + plan.win_tlen;
+    LW.score = score; LW.kernel_tag = 2; LW.max_score = plan.win_s0; LW.threads = plan.win_threads;
+    trgt_wfa_params wpw = wp;
+    wpw.text_begin_free = plan.win_tbf;
+    if ((rc = launch(wpw, LW))) return rc;
+  }
+  tl_mark(c, "window launch");
+  WinCheckArgs wc;
+  wc.win_jobs = winjobs; wc.n_win = count + SC_WIN; wc.score = score; wc.span4 = span4; wc.n_match = nmatch; wc.s0 = plan.win_s0;
+  wc.wfa_jobs = restjobs; wc.wfa_count = count; wc.jobs_cap = (uint32_t)n_jobs;
+  wc.read_off = d_read_off; wc.read_len = d_read_len; wc.long_rest = long_noseed; wc.long_tlen = plan.long_tlen;
+  hipLaunchKernelGGL(window_check_kernel, dim3(256), dim3(256), 0, c->stream, wc);
+  TRGT_HIP_TRY(c, hipGetLastError());
+  light.jobs_dev = restjobs; light.n_jobs_dev = count + SC_REST; light.n_jobs2_dev = nullptr; light.jobs_cap = 0;
+  return TRGT_OK;
+}
+int SpanCall::rest_launch() {  // the light list against the whole read -- without two launches: every short read's alignment
+  if (const int rc = launch(wp, light)) return rc;
+  tl_mark(c, "rest launch");
+  return plan.split ? TRGT_OK : first_launch_done();
+}
+// The long reads: their window filter (see LongWinArgs), the banded back-trace of the kept reads whose windows named penalty and end
+// diagonal, as for the short reads (BandArgs), and the exact kernel over what is left.
+int SpanCall::long_reads() {
+  int rc; const uint64_t cap = plan.long_cap; JobList list = long_in;
+  if (plan.long_filter) {
+    JobDev *sub = nullptr, *kept = nullptr; uint32_t *parent = nullptr, *sband = nullptr, *jbest = nullptr, *jrej = nullptr; uint8_t *subkeep = nullptr, *jobkeep = nullptr; void* lwc = nullptr;
+    if ((rc = get(S_LW_SUB, cap * sizeof(JobDev), sub)) ||
+        (rc = get(S_LW_PARENT, cap * 4, parent)) || (rc = get(S_LW_SUBKEEP, cap, subkeep)) ||
+        (rc = get(S_LW_JOBKEEP, n_jobs, jobkeep)) || (rc = get(S_LW_KEPT, n_jobs * sizeof(JobDev), kept)) ||
+        (rc = dev_get_zeroed(c, S_LW_COUNT, 16, &lwc, c->stream)))
+      return rc;
+    LongWinArgs lw;
+    lw.jobs = list.jobs; lw.n_jobs = list.count;
+    lw.sub = sub; lw.parent = parent; lw.sub_keep = subkeep; lw.n_sub = (uint32_t*)lwc; lw.cap = (uint32_t)cap;
+    lw.job_keep = jobkeep; lw.kept = kept; lw.n_kept = (uint32_t*)lwc + 1; lw.wl = (int32_t)plan.long_wl; lw.step = (int32_t)plan.long_step;
+    if (plan.long_band && ((rc = get(S_LW_SUBBAND, cap * 4, sband)) || (rc = get(S_LW_JOBBEST, n_jobs * 4, jbest)) || (rc = get(S_LW_JOBREJ, n_jobs * 4, jrej)))) return rc;
+    lw.sub_band = sband; lw.job_best = jbest; lw.job_rej = jrej;
+    const dim3 g((unsigned)c->num_cus * 2), b(256);
+    hipLaunchKernelGGL(long_windows_kernel, g, b, 0, c->stream, lw);
+    TRGT_HIP_TRY(c, hipGetLastError());
+    FilterLaunch FW;
+    FW.jobs_dev = sub; FW.n_jobs_host = (int64_t)cap; FW.n_jobs_dev = (const uint32_t*)lwc;
+    FW.pat_base = d_flank; FW.txt_base = d_reads; FW.max_plen = p.flank_len; FW.max_tlen = plan.long_wl;
+    FW.mism = p.mism; FW.gapo = p.gapo; FW.gape = p.gape; FW.min_matches = (int32_t)plan.min_matches; FW.early_reject = plan.early_reject; FW.keep = subkeep; FW.band = sband; FW.set = 1;
+    if ((rc = flank_filter_launch(c, FW))) return rc;
+    hipLaunchKernelGGL(long_verdict_kernel, g, b, 0, c->stream, lw);
+    hipLaunchKernelGGL(long_kept_kernel, g, b, 0, c->stream, lw);
+    TRGT_HIP_TRY(c, hipGetLastError());
+    list = {kept, (const uint32_t*)lwc + 1};
+    if (plan.long_band && (rc = band_backtrace(list, S_LW_BANDJOBS, S_LW_RESTJOBS, S_LW_BSCORE, SC_LBAND, SC_LREST, longl, 0))) return rc;
+  }
+  WfaLaunch L2 = longl;
+  L2.jobs_dev = list.jobs; L2.n_jobs_dev = list.count;
+  return launch(wp, L2);
+}
+int SpanCall::join_and_combine() {
+  if (plan.two_streams) {  // the expensive alignments ran on the second stream: wait for it before the spans are combined
+    TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_heavy, 0));
+    if (const int rc = merge_cells()) return rc;
   }
   CombineArgs ca;
-  ca.n_reads = (uint64_t)n_reads; ca.flank_len = p.flank_len;
-  ca.threshold = (double)(uint64_t)p.flank_len * p.min_flank_id_frac;  // span_locater.rs:46
-  ca.pos = (const int32_t*)d_pos; ca.n_match = (const int32_t*)d_nmatch; ca.span4 = (const uint32_t*)d_span4;
+  ca.n_reads = (uint64_t)n_reads; ca.flank_len = p.flank_len; ca.threshold = plan.threshold;
+  ca.pos = pos; ca.n_match = nmatch; ca.span4 = span4;
   ca.span_start = d_span_start; ca.span_end = d_span_end; ca.lf_hit = d_lf_hit; ca.rf_hit = d_rf_hit;
-  ca.count = (const uint32_t*)d_count; ca.cells = (unsigned long long*)c->last_wfa_cells_dev;
+  ca.count = count; ca.cells = (unsigned long long*)c->last_wfa_cells_dev;
   hipLaunchKernelGGL(span_combine_kernel, dim3((unsigned)((n_reads + 255) / 256)), dim3(256), 0, c->stream, ca);
   TRGT_HIP_TRY(c, hipGetLastError());
-  if (c->knobs.debug) {  // (synchronises: developer output only)
-    uint32_t h[SC_WORDS];
-    TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
-    TRGT_HIP_TRY(c, hipMemcpy(h, d_count, 4 * SC_WORDS, hipMemcpyDeviceToHost));
-    if (win_q > 0)
-      fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u -> windowed %u, whole read %u (that is %u without seeds + %u windows that did not stand), settled by the shortcuts %u (one-base gaps: %u)\n",
-              h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT], h[SC_WIN], h[SC_REST], h[SC_LIGHT] - h[SC_WIN] - h[SC_SHORTCUT], h[SC_REST] - (h[SC_LIGHT] - h[SC_WIN] - h[SC_SHORTCUT]), h[SC_SHORTCUT], h[SC_GAPS]);
-    if (win_q <= 0) fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u (no seeded windows for this configuration)\n", h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT]);
-    if (win_q > 0) fprintf(stderr, "[spans+] windowed launch: %s, %u alignments it did not take\n", win_reg ? "one wave per alignment, history in registers" : "LDS kernel", h[SC_WINFALL]);
-    if (win_q > 0 && heavy_window) fprintf(stderr, "[spans+] (the seed search ran over the first launch's list too: %u of its %u alignments had no seeds and met the pre-filter; the counts of the windowed list and of the shortcut include the others)\n", h[SC_NOSEED], h[SC_HEAVY]);
-    if (has_long) fprintf(stderr, "[spans+] long reads kept by the window filter: back-traced inside a band %u, over the whole read %u\n", h[SC_LBAND], h[SC_LREST]);
-    fprintf(stderr, "[spans+] sibling rule %s: %u missed pieces without a job (fewer than %d bases beside the exactly found sibling)\n", sa.min_matches > 0 ? "on" : "off", h[SC_SIBDROP], sa.min_matches);
-    if (heavy_band) fprintf(stderr, "[spans+] kept by the pre-filter: %u -> back-traced inside a band %u (did not stand: %u), over the whole read %u\n", h[SC_KEEP], h[SC_BAND], h[SC_BANDFAIL], h[SC_HREST]);
-  }
-  (void)n_loci;
   return TRGT_OK;
+}
+int SpanCall::debug_report() {  // (synchronises: developer output only)
+  uint32_t h[SC_WORDS];
+  TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
+  TRGT_HIP_TRY(c, hipMemcpy(h, count, 4 * SC_WORDS, hipMemcpyDeviceToHost));
+  const bool win = plan.win_q > 0;
+  if (win)
+    fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u -> windowed %u, whole read %u (that is %u without seeds + %u windows that did not stand), settled by the shortcuts %u (one-base gaps: %u)\n",
+            h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT], h[SC_WIN], h[SC_REST], h[SC_LIGHT] - h[SC_WIN] - h[SC_SHORTCUT], h[SC_REST] - (h[SC_LIGHT] - h[SC_WIN] - h[SC_SHORTCUT]), h[SC_SHORTCUT], h[SC_GAPS]);
+  if (!win) fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u (no seeded windows for this configuration)\n", h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT]);
+  if (win) fprintf(stderr, "[spans+] windowed launch: %s, %u alignments it did not take\n", plan.win_reg ? "one wave per alignment, history in registers" : "LDS kernel", h[SC_WINFALL]);
+  if (win && plan.heavy_window) fprintf(stderr, "[spans+] (the seed search ran over the first launch's list too: %u of its %u alignments had no seeds and met the pre-filter; the counts of the windowed list and of the shortcut include the others)\n", h[SC_NOSEED], h[SC_HEAVY]);
+  if (plan.has_long) fprintf(stderr, "[spans+] long reads kept by the window filter: back-traced inside a band %u, over the whole read %u\n", h[SC_LBAND], h[SC_LREST]);
+  fprintf(stderr, "[spans+] sibling rule %s: %u missed pieces without a job (fewer than %d bases beside the exactly found sibling)\n", plan.scan_min_matches > 0 ? "on" : "off", h[SC_SIBDROP], plan.scan_min_matches);
+  if (plan.heavy_band) fprintf(stderr, "[spans+] kept by the pre-filter: %u -> back-traced inside a band %u (did not stand: %u), over the whole read %u\n", h[SC_KEEP], h[SC_BAND], h[SC_BANDFAIL], h[SC_HREST]);
+  return TRGT_OK;
+}
+
+// Device-side part shared with trgt_locus_batch: everything already resident, results left on the device.
+int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_reads, const uint8_t* d_flank, const uint64_t* d_piece_off,
+                      const uint8_t* d_reads, const uint64_t* d_read_off, const uint32_t* d_read_len, const uint32_t* d_read_locus,
+                      uint32_t max_read_len, int32_t* d_span_start, int32_t* d_span_end, uint8_t* d_lf_hit, uint8_t* d_rf_hit,
+                      const uint32_t* d_heavy_len, uint32_t heavy_tlen_max, bool span_only) {
+  const uint64_t n_jobs = 2ull * (uint64_t)n_reads;
+  SpanCall s{c, p, n_reads, n_jobs, d_flank, d_piece_off, d_reads, d_read_off, d_read_len, d_read_locus, max_read_len, d_span_start, d_span_end, d_lf_hit, d_rf_hit, d_heavy_len,
+             span_plan(c, p, n_jobs, max_read_len, heavy_tlen_max, d_heavy_len != nullptr, span_only)};
+  int rc;
+  if ((rc = s.workspace()) || (rc = s.scan())) return rc;
+  if (s.plan.split && (rc = s.heavy_list())) return rc;
+  if (s.plan.win_q > 0 && (rc = s.light_windows())) return rc;
+  if ((rc = s.rest_launch())) return rc;
+  if (s.plan.has_long && (rc = s.long_reads())) return rc;
+  if ((rc = s.join_and_combine())) return rc;
+  return c->knobs.debug ? s.debug_report() : TRGT_OK;
 }
 
 }  // namespace trgt
@@ -1142,7 +1189,7 @@ extern "C" int trgt_find_spans_batch(trgt_hip_ctx* c, const trgt_span_params* p,
   if ((rc = o_s.init(c, S_LOCUS_0, span_start, (size_t)n_reads)) || (rc = o_e.init(c, S_LOCUS_1, span_end, (size_t)n_reads)) ||
       (rc = o_l.init(c, S_FS_HIT0, lf_hit, (size_t)n_reads)) || (rc = o_r.init(c, S_FS_HIT1, rf_hit, (size_t)n_reads)))
     return rc;
-  if ((rc = find_spans_device(c, *p, n_loci, n_reads, d_flank, d_piece, d_reads, d_roff, d_rlen, d_rloc, max_read_len, o_s.dev,
+  if ((rc = find_spans_device(c, *p, n_reads, d_flank, d_piece, d_reads, d_roff, d_rlen, d_rloc, max_read_len, o_s.dev,
                               o_e.dev, o_l.dev, o_r.dev, d_heavy, heavy_tlen_max > 0 ? heavy_tlen_max - 1 : 0, !lf_hit && !rf_hit)))
     return rc;
   if ((rc = o_s.finish(c)) || (rc = o_e.finish(c)) || (rc = o_l.finish(c)) || (rc = o_r.finish(c))) return rc;

@@ -19,6 +19,11 @@ inline uint32_t heavy_read_len(uint32_t locus_max_read_len, int flank_len) {
   return locus_max_read_len > margin ? locus_max_read_len - margin : 0;
 }
 
+// The --aln-scoring presets of the reference (cli.rs:271-280): 2,5,1 (wgs) is the configuration the specialised kernels are compiled
+// for; the pre-filter (wfa_reg.hip) has an instantiation for 1,0,1 (targeted) as well.
+inline bool preset_wgs(int mism, int gapo, int gape) { return mism == 2 && gapo == 5 && gape == 1; }
+inline bool preset_has_filter(int mism, int gapo, int gape) { return preset_wgs(mism, gapo, gape) || (mism == 1 && gapo == 0 && gape == 1); }
+
 struct WfaLaunch {  // everything device-resident
   const JobDev* jobs_dev = nullptr; int64_t n_jobs_host = 0; const uint32_t* n_jobs_dev = nullptr;
   int64_t jobs_bound = 0;  // with n_jobs_dev: the most jobs the list can hold (0: n_jobs_host is that bound, not just a bound on the workgroups)
@@ -99,6 +104,13 @@ struct FilterLaunch {
 int flank_filter_max_tlen(int flank_len);
 // Enqueue the filter on the ctx stream (asynchronous); offsets computed are accumulated at ctx->last_filter_cells_dev.
 int flank_filter_launch(trgt_hip_ctx* c, const FilterLaunch& L);
+
+// ---- flank location (spans.hip) ----
+// The device-side part of trgt_find_spans_batch, shared with trgt_locus_batch: everything already resident, results left on the device.
+int find_spans_device(trgt_hip_ctx* c, const trgt_span_params& p, int64_t n_reads, const uint8_t* d_flank, const uint64_t* d_piece_off,
+                      const uint8_t* d_reads, const uint64_t* d_read_off, const uint32_t* d_read_len, const uint32_t* d_read_locus,
+                      uint32_t max_read_len, int32_t* d_span_start, int32_t* d_span_end, uint8_t* d_lf_hit, uint8_t* d_rf_hit,
+                      const uint32_t* d_heavy_len, uint32_t heavy_tlen_max, bool span_only);
 
 // Run-length CIGARs of a whole batch in one dense array: job j = data[off[j] .. off[j + 1]) (len << 4 | code, as cigar_get_CIGAR).
 struct PackedCigars { std::vector<uint32_t> data; std::vector<uint64_t> off; };

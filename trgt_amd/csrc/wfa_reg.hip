@@ -586,8 +586,8 @@ int flank_filter_launch(trgt_hip_ctx* c, const FilterLaunch& L) {
   // instantiation by the number of diagonals the longest text of the launch needs (jobs that do not fit are kept unseen)
   const int64_t diag = L.max_plen + L.max_tlen + 1;
   // (nine strips of 128 diagonals for texts that need up to 1152: 8 % faster there than the five strips of 256, which carry 128 dead ones)
-  const bool targeted = L.mism == 1 && L.gapo == 0 && L.gape == 1;  // the other preset: 1,0,1 (cli.rs:271-280)
-  if (!targeted && !(L.mism == 2 && L.gapo == 5 && L.gape == 1)) return fail(c, TRGT_ERR_UNSUPPORTED, "flank filter: no instantiation for penalties %d,%d,%d", L.mism, L.gapo, L.gape);
+  if (!preset_has_filter(L.mism, L.gapo, L.gape)) return fail(c, TRGT_ERR_UNSUPPORTED, "flank filter: no instantiation for penalties %d,%d,%d", L.mism, L.gapo, L.gape);
+  const bool targeted = !preset_wgs(L.mism, L.gapo, L.gape);  // the other preset: 1,0,1 (cli.rs:271-280)
   void (*fn)(const FilterArgs) = diag <= 4 * 256 ? wfa_filter_kernel<4, 2> : diag <= 9 * 128 ? wfa_filter_kernel<9, 1> : diag <= 5 * 256 ? wfa_filter_kernel<5, 2> : wfa_filter_kernel<6, 2>;
   void (*fn4)(const FilterArgs) = wfa_filter_kernel<4, 2>;
   if (targeted) { fn = diag <= 4 * 256 ? wfa_filter_kernel<4, 2, 1, 1> : diag <= 5 * 256 ? wfa_filter_kernel<5, 2, 1, 1> : wfa_filter_kernel<6, 2, 1, 1>; fn4 = wfa_filter_kernel<4, 2, 1, 1>; }
@@ -661,7 +661,7 @@ extern "C" int trgt_flank_filter_batch(trgt_hip_ctx* c, const trgt_span_params* 
   if (!c) return TRGT_ERR_INVALID;
   if (!p || n_jobs < 0 || (n_jobs > 0 && (!seqs || !pat_off || !pat_len || !txt_off || !txt_len)))
     return fail(c, TRGT_ERR_INVALID, "trgt_flank_filter_batch: null argument");
-  if (!(p->mism == 2 && p->gapo == 5 && p->gape == 1) && !(p->mism == 1 && p->gapo == 0 && p->gape == 1))
+  if (!preset_has_filter(p->mism, p->gapo, p->gape))
     return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_flank_filter_batch: only --aln-scoring 2,5,1 and 1,0,1 have a filter kernel");
   if (offsets_computed) *offsets_computed = 0;
   if (n_jobs == 0) return TRGT_OK;

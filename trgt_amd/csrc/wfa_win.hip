@@ -262,7 +262,7 @@ __global__ void __launch_bounds__(64) wfa_win_kernel(const WinKArgs a) {
 
 bool wfa_win_fits(int mism, int gapo, int gape, int tbf, int s_max, int64_t max_plen, int64_t max_tlen) {
   // level s lives on the diagonals [-s, text_begin_free + s]; the lanes hold [WIN_KBASE, WIN_KBASE + 127]
-  return mism == 2 && gapo == 5 && gape == 1 && s_max >= 1 && s_max <= WIN_LEVELS - 1 && s_max <= -WIN_KBASE && tbf >= 0 &&
+  return preset_wgs(mism, gapo, gape) && s_max >= 1 && s_max <= WIN_LEVELS - 1 && s_max <= -WIN_KBASE && tbf >= 0 &&
          tbf + s_max <= WIN_KBASE + 127 && max_plen >= 8 && max_plen <= WIN_SEQ_CAP && max_tlen <= WIN_SEQ_CAP;
 }
 
