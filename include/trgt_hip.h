@@ -120,6 +120,23 @@ int trgt_hip_size_deep_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
  * asked one by one through trgt_hip_pool_context. */
 int trgt_hip_set_flank_device(trgt_hip_ctx* ctx, int on);
 int trgt_hip_flank_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
+/* The same step for Genotyper::Cluster loci (genotype_flank.rs:9-76, 147-170; tr.rs:64-75: analyze re-genotypes a close pair of alleles
+ * whichever genotyper produced it), a setting of its own and independent of trgt_hip_set_flank_device.  By default the device cluster
+ * chain genotypes such a locus and the host, where the tags split its reads, redoes it from the start.  On a context set with on != 0,
+ * calls whose batch carries hp_tag run the tag branch behind the one-wave cluster chain (locus_cluster_flank.hpp) for the cluster loci
+ * of at most 256 candidate reads: assignment by tag, acceptance, simple_consensus of either group, a third consensus round of the chain
+ * for a group without a majority sequence, smaller allele first, reference allele first.  What stays on the host, with the same
+ * results: the SNV-clustering branch (get_trs_with_clustering), tried for the loci whose tags do not split the reads exactly as before;
+ * deep cluster loci (257 to 2048 reads on a context set with trgt_hip_set_cluster_max_reads), which the host redoes as before;
+ * contexts created under TRGT_HOST_CLUSTER or TRGT_HOST_GENOTYPER; and a locus on this route that finds no room in the chain's arenas,
+ * whose repaired group overflows its slot, or that has an allele beyond allele_cap.  trgt_hip_flank_cluster_stats: of the context's
+ * last trgt_locus_batch -- out[0] cluster loci whose genotype the device replaced by the tag split, out[1] those among them with at
+ * least one repaired group, out[2] cluster loci on the route that the device handed back to the host path (not counted in stats[23]);
+ * all zero with the setting off or a batch without hp_tag.  trgt_hip_flank_stats never counts a cluster locus in out[0], out[1] or
+ * out[3], and on a context with this setting not in out[2] either where this route settled the locus or handed it back.
+ * The two prototypes -- trgt_hip_set_flank_cluster_device(ctx, on), trgt_hip_flank_cluster_stats(ctx, out[3]) -- are declared in
+ * trgt_hip_flank_cluster.h, which this header includes: every program that includes trgt_hip.h has them. */
+#include "trgt_hip_flank_cluster.h"
 
 /* ---- kernel timing (HIP events on the ctx stream, for bench.py's roofline) ---- */
 #define TRGT_K_FLANK_SCAN 0   /* exact flank search (+ the segment search for the seeded windows of the fallback alignments) */

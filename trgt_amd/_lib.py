@@ -82,6 +82,9 @@ EXPORTS = [
     "trgt_cigar_ref_len", "trgt_cigar_query_len", "trgt_cigar_total_query_len", "trgt_read_mismatch_offsets", "trgt_read_meth", "trgt_read_clip_to_region",
     "trgt_read_clip_bases", "trgt_median_i32", "trgt_synth_default_params", "trgt_synth_generate", "trgt_synth_free",
 ]
+# The two entry points of the tag branch behind the cluster chain (locus_cluster_flank.hpp).  A list of its own, checked by lib() like EXPORTS:
+# tests/test_flank_deep_api.py pins the trgt_hip_*flank* names of EXPORTS to the two of the size genotyper's setting.
+CLUSTER_FLANK_EXPORTS = ["trgt_hip_set_flank_cluster_device", "trgt_hip_flank_cluster_stats"]
 
 
 def build_extension(force=False, verbose=False, dev=False):
@@ -110,7 +113,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(_SO)
-        missing = [n for n in EXPORTS if not hasattr(L, n)]
+        missing = [n for n in EXPORTS + CLUSTER_FLANK_EXPORTS if not hasattr(L, n)]
         if missing:
             raise TrgtHipError("%s does not export %s (stale build?)" % (_SO, ", ".join(missing)))
         L.trgt_hip_last_error.restype = C.c_char_p
@@ -129,6 +132,8 @@ def lib():
         L.trgt_hip_size_deep_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_set_flank_device.argtypes = [_VP, C.c_int]
         L.trgt_hip_flank_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
+        L.trgt_hip_set_flank_cluster_device.argtypes = [_VP, C.c_int]
+        L.trgt_hip_flank_cluster_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_timing_enable.argtypes = [_VP, C.c_int]
         L.trgt_hip_timing_reset.argtypes = [_VP]
         L.trgt_hip_timing_get.argtypes = [_VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -210,6 +215,19 @@ class Context:
         self.check(lib().trgt_hip_flank_stats(self.handle, out))
         return tuple(int(v) for v in out)
 
+    def set_flank_cluster_device(self, on=True):
+        """trgt_hip_set_flank_cluster_device: the haplotype-tag branch of genotype_flank behind the one-wave cluster chain, for the
+        Genotyper::Cluster loci of at most 256 candidate reads of batches that carry hp_tag (off, the default: the host redoes such a
+        locus).  Independent of set_flank_device.  Every later call on this context uses it."""
+        self.check(lib().trgt_hip_set_flank_cluster_device(self.handle, int(bool(on))))
+
+    def flank_cluster_stats(self):
+        """trgt_hip_flank_cluster_stats of the context's last trgt_locus_batch: (cluster loci whose genotype the device replaced by the
+        tag split, those among them with a repaired group, cluster loci on the route handed back to the host path)."""
+        out = (C.c_int64 * 3)()
+        self.check(lib().trgt_hip_flank_cluster_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def timing_enable(self, on=True):
         self.check(lib().trgt_hip_timing_enable(self.handle, int(on)))
 
@@ -236,7 +254,7 @@ class Context:
 class Pool:
     """trgt_hip_pool: several contexts (devices[i] = ordinal of context i, ordinals may repeat) behind one queue of batches."""
 
-    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None):
+    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None):
         L = lib()
         L.trgt_hip_pool_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
         L.trgt_hip_pool_destroy.argtypes = [C.c_void_p]
@@ -269,6 +287,9 @@ class Pool:
         if flank_device is not None:
             for c in self.contexts:
                 c.set_flank_device(flank_device)
+        if flank_cluster_device is not None:
+            for c in self.contexts:
+                c.set_flank_cluster_device(flank_cluster_device)
 
     def run_many(self, params_struct, cins, couts, out_per_context=False):
         """cins / couts: lists of LocusBatchIn / LocusBatchOut structures (couts: one per batch, or one per context)"""

@@ -35,6 +35,7 @@
 #include "locus_purity.hpp"
 #include "locus_cluster_dev.hpp"
 #include "locus_cluster_deep.hpp"
+#include "locus_cluster_flank.hpp"
 #include "locus_gt_deep.hpp"
 #include "wfa_host.hpp"
 
@@ -651,6 +652,9 @@ const OneWave<cl::ClArgs> k_cluster_front{{{cl::cluster_front_kernel<64>, cl::cl
 const OneWave<cl::ClArgs> k_cluster_ward{{{cl::cluster_ward_kernel<64, true>, cl::cluster_ward_kernel<64, true, true>}, {cl::cluster_ward_kernel<GT_BIG, false>, cl::cluster_ward_kernel<GT_BIG, false, true>}}};
 const OneWave<cl::ClArgs> k_cluster_round2{{{cl::cluster_round2_kernel<64>, cl::cluster_round2_kernel<64, true>}, {cl::cluster_round2_kernel<GT_BIG>, cl::cluster_round2_kernel<GT_BIG, true>}}};
 const OneWave<cl::ClArgs> k_cluster_finish{{{cl::cluster_finish_kernel<64>, cl::cluster_finish_kernel<64, true>}, {cl::cluster_finish_kernel<GT_BIG>, cl::cluster_finish_kernel<GT_BIG, true>}}};
+// (the tag branch of genotype_flank behind the chain: contexts that opted in with trgt_hip_set_flank_cluster_device, calls whose reads carry tags)
+const OneWave<clf::ClFlankArgs> k_cluster_flank{{{clf::cluster_flank_kernel<64>, clf::cluster_flank_kernel<64, true>}, {clf::cluster_flank_kernel<GT_BIG>, clf::cluster_flank_kernel<GT_BIG, true>}}};
+const OneWave<clf::ClFlankArgs> k_cluster_flank_finish{{{clf::cluster_flank_finish_kernel<64>, clf::cluster_flank_finish_kernel<64, true>}, {clf::cluster_flank_finish_kernel<GT_BIG>, clf::cluster_flank_finish_kernel<GT_BIG, true>}}};
 
 // the deep cluster list's buffers: the same slots as the shallow list's, second set
 inline int cl_slot(bool deep, int s) { return s + (deep ? (int)S_CLD_LIST - (int)S_CL_LIST : 0); }
@@ -699,7 +703,7 @@ struct LocusCall {
   const int64_t nl; int64_t nr = 0; int F = 0;
   bool done = false;  // nothing left to do (a call without loci or without reads)
   trgt_locus_batch_in in_expanded; std::vector<uint64_t> expanded_off;  // TRGT_READS_BAM4: the batch with its reads expanded in HBM
-  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
+  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, flank_cl_dev = false, cf_route = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
   FlankMeta flank_meta{};
   // ---- clean-up state (see the destructor)
   bool zeroed = false;
@@ -717,7 +721,7 @@ struct LocusCall {
   void *d_ss = nullptr, *d_se = nullptr, *d_hl = nullptr, *d_hr = nullptr, *h_ss = nullptr, *h_se = nullptr, *h_hl = nullptr, *h_hr = nullptr, *h_cells = nullptr;
   Slab slab;
   size_t o_ss = 0, o_se = 0, o_hl = 0, o_hr = 0, o_need = 0, o_nal = 0, o_alen = 0, o_ci = 0, o_nsp = 0, o_cls = 0, o_rank = 0, o_nspan = 0, o_toff = 0, o_flip = 0, o_gsz = 0,
-         o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0, o_fdone = 0;
+         o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0, o_fdone = 0, o_cfc = 0;
   GtDev g; GtHost gh;
   // ---- the device chains.  The cluster loci of the call: [0] the shallow list (at most GT_MAX_READS reads: the one-wave chain), [1] the
   // deep list (beyond that, up to the context's cluster_max_reads: locus_cluster_deep.hpp), each with its own pair slots, job lists, arenas
@@ -784,6 +788,7 @@ int LocusCall::check_args() {
   if (nl < 0) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: negative n_loci");
   for (int64_t& v : c->size_deep_stats) v = 0;
   for (int64_t& v : c->flank_stats) v = 0;
+  for (int64_t& v : c->flank_cluster_stats) v = 0;
   if (nl == 0) { done = true; return TRGT_OK; }
   if (!in->flank_blob || !in->lf_off || !in->lf_len || !in->rf_off || !in->rf_len || !in->tr_blob || !in->tr_off || !in->tr_len ||
       !in->motif_blob || !in->motif_off || !in->set_motif_begin || !in->ploidy || !in->locus_read_begin || !in->read_blob ||
@@ -899,6 +904,8 @@ int LocusCall::upload_tables() {
   // ... and its haplotype-tag branch runs inside the device genotyper on a context that opted in (trgt_hip_set_flank_device): the FLANK
   // forms of locus_gt.hpp, which read the tags and leave one byte per locus
   flank_dev = dev_gt && c->flank_device && in->hp_tag != nullptr;
+  // ... and, a setting of its own (trgt_hip_set_flank_cluster_device), behind the one-wave cluster chain: locus_cluster_flank.hpp
+  flank_cl_dev = dev_gt && c->flank_cluster_device && in->hp_tag != nullptr;
   int rc;
   if (ready) TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, ready, 0));
   if (staged_flank) d_flank = staged_flank;
@@ -921,7 +928,8 @@ int LocusCall::upload_tables() {
     o_nsp = slab.add(2 * (size_t)nl * 4); o_cls = slab.add((size_t)nr * 4); o_rank = slab.add((size_t)nr * 4); o_nspan = slab.add((size_t)nl * 4);
     o_toff = slab.add((2 * (size_t)nl + 1) * 8); o_flip = slab.add((size_t)nl);
     o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
-    if (flank_dev) o_fdone = slab.add((size_t)nl);
+    if (flank_dev || flank_cl_dev) o_fdone = slab.add((size_t)nl);
+    if (flank_cl_dev) o_cfc = slab.add(clf::CF_WORDS * 4);
   }
   if ((rc = dev_get(c, S_LOCUS_4, slab.total, &slab.dev)) || (rc = pin_get(c, P_SPAN_S, slab.total, &slab.host))) return rc;
   d_ss = slab.d(o_ss); d_se = slab.d(o_se); d_hl = slab.d(o_hl); d_hr = slab.d(o_hr);
@@ -932,7 +940,7 @@ int LocusCall::upload_tables() {
         (rc = dev_in(c, S_GT_TRLEN, in->tr_len, (size_t)nl, &g.tr_len, &ub)) || (rc = dev_in(c, S_GT_ALOFF, out->allele_off, 2 * (size_t)nl, &g.al_off, &ub)) ||
         (rc = dev_in(c, S_GT_ALCAP, out->allele_cap, (size_t)nl, &g.al_cap, &ub)) || (in->genotyper && (rc = dev_in(c, S_GT_GENO, in->genotyper, (size_t)nl, &g.geno, &ub))) ||
         (presel && in->read_qual && (rc = dev_in(c, S_PUR_RQ, in->read_qual, (size_t)nr, &g.rq, &ub))) ||
-        (flank_dev && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
+        ((flank_dev || flank_cl_dev) && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
         (rc = dev_get(c, S_GT_BLOB, (size_t)allele_total + 16, &g.blob)) || (rc = dev_get(c, S_GT_PACKED, (size_t)allele_total + 16, &g.packed)))
       return rc;
   }
@@ -1299,10 +1307,15 @@ int LocusCall::cluster_chain(int deep) {
   ca.g = ga; ca.list = clp[deep].d_list; ca.n_list = n_cl; ca.mat_off = clp[deep].d_moff;
   ca.flags = (c->knobs.sens_ward_ties ? 1u : 0u) | (c->knobs.sens_lw_order ? 2u : 0u);
   ca.cap_j = (uint32_t)cl_reads; ca.cap_g = 2 * n_cl; ca.vote_lds_pos = (uint32_t)vote::VOTE_LDS_POS;
-  // arenas for two consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
-  ca.cap_cigar = std::min<uint64_t>(2ull * cl_reads * (2ull * max_seg + 1), 96ull << 20);   // words
-  ca.cap_out = std::min<uint64_t>(2ull * (cl_reads + 2ull * n_cl) * ((uint64_t)max_seg + 16) + 64, 256ull << 20);  // bytes
-  ca.cap_scratch = std::min<uint64_t>(6ull * cl_reads + 12ull * n_cl * ((uint64_t)max_seg + 1) + 64, 32ull << 20);  // words
+  // the tag branch of genotype_flank behind the chain (locus_cluster_flank.hpp): the shallow list of a haplotagged call, on a context that
+  // opted in; it adds a third consensus round, and only then do the arenas and the job / group / length lists grow from two parts to three
+  const bool route = !deep && flank_cl_dev;
+  if (route) cf_route = true;  // (read by wait_stage_a)
+  const uint64_t rounds = route ? 3 : 2;
+  // arenas for the consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
+  ca.cap_cigar = std::min<uint64_t>(rounds * cl_reads * (2ull * max_seg + 1), 96ull << 20);   // words
+  ca.cap_out = std::min<uint64_t>(rounds * (cl_reads + 2ull * n_cl) * ((uint64_t)max_seg + 16) + 64, 256ull << 20);  // bytes
+  ca.cap_scratch = std::min<uint64_t>(3ull * rounds * cl_reads + 6ull * rounds * n_cl * ((uint64_t)max_seg + 1) + 64, 32ull << 20);  // words
   if (c->knobs.cluster_arena_kb > 0) {
     const uint64_t kb = (uint64_t)c->knobs.cluster_arena_kb;
     ca.cap_cigar = std::min<uint64_t>(ca.cap_cigar, kb * 256); ca.cap_out = std::min<uint64_t>(ca.cap_out, kb * 1024); ca.cap_scratch = std::min<uint64_t>(ca.cap_scratch, kb * 256);
@@ -1312,11 +1325,11 @@ int LocusCall::cluster_chain(int deep) {
        *d_cig = nullptr, *d_clen = nullptr, *d_vout = nullptr, *d_vlen = nullptr, *d_vscr = nullptr;
   if ((rc = dev_get(c, cl_slot(deep, S_CL_COUNTS), 256, &d_cnt)) || (rc = dev_get(c, cl_slot(deep, S_CL_REC), (size_t)n_cl * sizeof(cl::ClRec), &d_rec)) || (rc = dev_get(c, cl_slot(deep, S_CL_CLS), (size_t)nr + 16, &d_cls)) ||
       (rc = dev_get(c, cl_slot(deep, S_CL_ESCORE), (size_t)cl_pairs * 4 + 16, &d_es)) || (big && (rc = dev_get(c, cl_slot(deep, S_CL_GMAT), (size_t)cl_pairs * 8 + 16, &d_gm))) ||
-      (rc = dev_get(c, cl_slot(deep, S_CL_EDJOBS), (size_t)cl_pairs * sizeof(JobDev) + 16, &d_edj)) || (rc = dev_get(c, cl_slot(deep, S_CL_JOBS), 2 * (size_t)ca.cap_j * sizeof(JobDev), &d_j)) ||
-      (rc = dev_get(c, cl_slot(deep, S_CL_GROUPS), 2 * (size_t)ca.cap_g * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, cl_slot(deep, S_CL_ED2JOBS), 2 * (size_t)cl_reads * sizeof(JobDev), &d_ed2)) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_EDJOBS), (size_t)cl_pairs * sizeof(JobDev) + 16, &d_edj)) || (rc = dev_get(c, cl_slot(deep, S_CL_JOBS), (size_t)rounds * ca.cap_j * sizeof(JobDev), &d_j)) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_GROUPS), (size_t)rounds * ca.cap_g * sizeof(gt::RGroup), &d_g)) || (rc = dev_get(c, cl_slot(deep, S_CL_ED2JOBS), 2 * (size_t)cl_reads * sizeof(JobDev), &d_ed2)) ||
       (rc = dev_get(c, cl_slot(deep, S_CL_ESCORE2), 2 * (size_t)nr * 4 + 16, &d_es2)) || (rc = dev_get(c, cl_slot(deep, S_CL_CIGAR), (size_t)ca.cap_cigar * 4, &d_cig)) ||
-      (rc = dev_get(c, cl_slot(deep, S_CL_CLEN), 2 * (size_t)ca.cap_j * 4, &d_clen)) || (rc = dev_get(c, cl_slot(deep, S_CL_VOUT), (size_t)ca.cap_out + 16, &d_vout)) ||
-      (rc = dev_get(c, cl_slot(deep, S_CL_VLEN), 2 * (size_t)ca.cap_g * 4, &d_vlen)) || (rc = dev_get(c, cl_slot(deep, S_CL_VSCR), (size_t)ca.cap_scratch * 4 + 16, &d_vscr)))
+      (rc = dev_get(c, cl_slot(deep, S_CL_CLEN), (size_t)rounds * ca.cap_j * 4, &d_clen)) || (rc = dev_get(c, cl_slot(deep, S_CL_VOUT), (size_t)ca.cap_out + 16, &d_vout)) ||
+      (rc = dev_get(c, cl_slot(deep, S_CL_VLEN), (size_t)rounds * ca.cap_g * 4, &d_vlen)) || (rc = dev_get(c, cl_slot(deep, S_CL_VSCR), (size_t)ca.cap_scratch * 4 + 16, &d_vscr)))
     return rc;
   void* const z_clc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
   ca.counts = z_clc ? (uint32_t*)z_clc : (uint32_t*)d_cnt; ca.rec = (cl::ClRec*)d_rec; ca.cls = (int8_t*)d_cls; ca.escore = (int32_t*)d_es; ca.gmat = (double*)d_gm;
@@ -1377,6 +1390,22 @@ int LocusCall::cluster_chain(int deep) {
   if ((rc = ed_launch(ca.ed2_jobs, 2 * cl_reads, ca.counts + cl::CC_ED2, (const uint8_t*)d_vout, ca.escore2))) return rc;
   step(cld::deep_finish_kernel, k_cluster_finish);
   TRGT_HIP_TRY(c, hipGetLastError());
+  if (route) {
+    // ---- genotype_flank's tag branch for the loci the chain completed with two close alleles: settled at once, or behind a third
+    //      consensus round over the third part of the lists (usually short: the groups without a majority sequence)
+    void *d_fc = nullptr, *d_fp = nullptr;
+    if ((rc = dev_get(c, S_CLF_PEND, (size_t)n_cl * sizeof(clf::ClFlankPend), &d_fp))) return rc;
+    void* const z_cfc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
+    if (!z_cfc && (rc = dev_get(c, S_CLF_COUNTS, 256, &d_fc))) return rc;
+    clf::ClFlankArgs fa{ca, g.hp, (uint8_t*)slab.d(o_fdone), z_cfc ? (uint32_t*)z_cfc : (uint32_t*)d_fc, (clf::ClFlankPend*)d_fp, 2 * ca.cap_j, 2 * ca.cap_g};
+    if (!z_cfc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, fa.fcounts, (uint32_t)clf::CF_WORDS);
+    k_cluster_flank.launch(big, presel, cgrid, c->stream, fa);
+    TRGT_HIP_TRY(c, hipGetLastError());
+    if ((rc = cons_launch(2 * ca.cap_j, fa.fcounts + clf::CF_J3, 2 * ca.cap_g, fa.fcounts + clf::CF_G3))) return rc;
+    k_cluster_flank_finish.launch(big, presel, cgrid, c->stream, fa);
+    TRGT_HIP_TRY(c, hipGetLastError());
+    TRGT_HIP_TRY(c, hipMemcpyAsync(slab.d(o_cfc), fa.fcounts, clf::CF_WORDS * 4, hipMemcpyDeviceToDevice, c->stream));  // (the counts come back with the slab)
+  }
   tl_mark(c, deep ? "deep cluster chain enqueued" : "cluster chain enqueued");
   cl_counts_dev[deep] = ca.counts;
   return TRGT_OK;
@@ -1435,18 +1464,33 @@ int LocusCall::wait_stage_a() {
       // take the host path, where the genotype is replaced (genotype_flank below); the split only needs the per-read fields
       // (not the loci whose genotype the FLANK forms of the device genotyper already replaced by the tag split)
       const int32_t* nal = (const int32_t*)gh.nal; const uint32_t* alen = (const uint32_t*)gh.alen; const int32_t* rank = (const int32_t*)gh.rank;
-      const uint8_t* fdone = flank_dev ? (const uint8_t*)slab.h(o_fdone) : nullptr;
+      // (the byte of a locus is read only where a kernel wrote it: every locus with the FLANK size kernels, the shallow cluster list with the
+      //  cluster route; a cluster locus has a byte of the cluster route's or none)
+      const uint8_t* fdone = flank_dev || cf_route ? (const uint8_t*)slab.h(o_fdone) : nullptr;
+      auto fl_byte = [&](int64_t l) -> uint8_t {
+        if (!is_cluster(l)) return flank_dev ? fdone[l] : (uint8_t)0;
+        const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
+        return cf_route && in->ploidy[l] != 0 && n > 0 && n <= (uint64_t)gt::GT_MAX_READS ? fdone[l] : (uint8_t)0;
+      };
       std::atomic<int64_t> sent{0};
       pool->parallel_for(nl, 64, [&](int64_t l, int) {
-        if (need[l] || (fdone && (fdone[l] & gt::FL_DONE)) || nal[l] != 2 || adiff(alen[2 * l], alen[2 * l + 1]) > 10) return;
+        if (need[l] || (fdone && (fl_byte(l) & gt::FL_DONE)) || nal[l] != 2 || adiff(alen[2 * l], alen[2 * l + 1]) > 10) return;
         const uint64_t r0 = in->locus_read_begin[l], r1 = in->locus_read_begin[l + 1];
         std::vector<uint32_t> order;
         for (uint64_t r = r0; r < r1; ++r) if (rank[r] >= 0) { if ((size_t)rank[r] >= order.size()) order.resize((size_t)rank[r] + 1, 0); order[(size_t)rank[r]] = (uint32_t)r; }
         FlankSplit sp;
         if (flank_split(flank_meta, order.data(), order.size(), sp)) { need[l] = 1; sent += 1; }
       });
-      if (fdone) {  // trgt_hip_flank_stats
+      if (cf_route) {  // trgt_hip_flank_cluster_stats
+        for (const uint32_t l : cl_list) {
+          if ((fdone[l] & gt::FL_DONE) && !need[l]) { c->flank_cluster_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_cluster_stats[1] += 1; }
+          else if (fdone[l] == gt::FL_HANDED) c->flank_cluster_stats[2] += 1;
+        }
+        stat_cons_jobs += (int64_t)((const uint32_t*)slab.h(o_cfc))[clf::CF_J3];  // consensus alignments of the third round
+      }
+      if (flank_dev) {  // trgt_hip_flank_stats (never a cluster locus in [0], [1], [3])
         for (int64_t l = 0; l < nl; ++l) {
+          if (is_cluster(l)) continue;
           if ((fdone[l] & gt::FL_DONE) && !need[l]) {
             c->flank_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_stats[1] += 1;
             if (in->locus_read_begin[l + 1] - in->locus_read_begin[l] > (uint64_t)gt::GT_MAX_READS) c->flank_stats[3] += 1;  // the deep size list's
@@ -2112,6 +2156,18 @@ extern "C" int trgt_hip_set_flank_device(trgt_hip_ctx* c, int on) {
 extern "C" int trgt_hip_flank_stats(const trgt_hip_ctx* c, int64_t out[4]) {
   if (!c || !out) return TRGT_ERR_INVALID;
   for (int i = 0; i < 4; ++i) out[i] = c->flank_stats[i];
+  return TRGT_OK;
+}
+
+// ---- ... and behind the one-wave cluster chain, a setting of its own (locus_cluster_flank.hpp)
+extern "C" int trgt_hip_set_flank_cluster_device(trgt_hip_ctx* c, int on) {
+  if (!c) return TRGT_ERR_INVALID;
+  c->flank_cluster_device = on != 0;
+  return TRGT_OK;
+}
+extern "C" int trgt_hip_flank_cluster_stats(const trgt_hip_ctx* c, int64_t out[3]) {
+  if (!c || !out) return TRGT_ERR_INVALID;
+  for (int i = 0; i < 3; ++i) out[i] = c->flank_cluster_stats[i];
   return TRGT_OK;
 }
 

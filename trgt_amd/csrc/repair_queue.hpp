@@ -1,6 +1,7 @@
 // trgt_amd/csrc/repair_queue.hpp -- the queue in front of a consensus repair (repair_consensus, consensus.rs:5-111), stated once for every
 // genotyper that feeds one: the size and haplotype-tag routes of locus_gt.hpp / locus_gt_deep.hpp (RepairBufs, RC_* counters) and the
-// two consensus rounds of locus_cluster_dev.hpp / locus_cluster_deep.hpp (ClArgs, CC_* counters).  A vote group is a backbone and its
+// two consensus rounds of locus_cluster_dev.hpp / locus_cluster_deep.hpp (ClArgs, CC_* counters), with the third round the tag route of
+// locus_cluster_flank.hpp adds behind the one-wave cluster chain (the chain's arenas, counters of its own).  A vote group is a backbone and its
 // members, all segments of the read blob; queueing one means
 //   group_needs      what the group takes from the three arenas: CIGAR words, result bytes, vote scratch words
 //   reserve_arenas   the reservation of a locus (at most two groups) by ONE thread, broadcast through a Reserved record in LDS
