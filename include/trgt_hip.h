@@ -137,6 +137,27 @@ int trgt_hip_flank_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
  * The two prototypes -- trgt_hip_set_flank_cluster_device(ctx, on), trgt_hip_flank_cluster_stats(ctx, out[3]) -- are declared in
  * trgt_hip_flank_cluster.h, which this header includes: every program that includes trgt_hip.h has them. */
 #include "trgt_hip_flank_cluster.h"
+/* The other branch of genotype_flank::genotype: where the tags do not split the reads (or there are none), the split by heterozygous
+ * SNVs of the flanks (get_trs_with_clustering with its analysis region, SNV calls, profiles, candidate genotypes and log-likelihoods,
+ * genotype_flank.rs:78-138, 171-290; applied by analyze at tr.rs:69-75).  By default the host does this step for every
+ * device-genotyped locus with two close alleles, and redoes the loci whose SNVs split the reads from the start.  On a context set with
+ * on != 0, calls whose batch carries mismatch_offsets and mismatch_off run it inside the one-wave size genotyper (the SNV forms of
+ * locus_gt.hpp) for Genotyper::Size loci of ploidy 2 and at most 256 candidate reads, in the reference's order: tags that split the
+ * reads own the locus (the device's tag branch with trgt_hip_set_flank_device also on, else the host as before), the SNVs are tried
+ * only without them.  Everything but exp and log is restated bit for bit; the candidate search is decided on the device only when its
+ * winner is ahead of every other candidate by more than 2^-30 * (1 + |log-likelihood|), far beyond what two libms can differ by.
+ * What stays on the host, with the same results: Genotyper::Cluster loci; size loci of more than 256 reads, the deep size list of
+ * trgt_hip_set_size_max_reads included; contexts created under TRGT_HOST_GENOTYPER; the tag branch where trgt_hip_set_flank_device is
+ * off; searches not decided beyond the margin; and a locus on this route that finds no room in the repair chain, has a segment beyond
+ * its longest (TRGT_REPAIR_MAX_SEG; every such locus under TRGT_HOST_REPAIR), an allele beyond allele_cap, more than 64 called SNVs,
+ * more than 16 distinct fully observed profiles, or more than 8 in-region mismatch offsets per candidate read.
+ * trgt_hip_snv_split_stats: of the context's last trgt_locus_batch -- out[0] loci whose genotype the device replaced through the SNV
+ * branch, out[1] those among them with a repaired group, out[2] loci on the route handed back for room or limits, out[3] loci handed
+ * back because the search was not decided beyond the margin (not in out[2]); all zero with the setting off or a batch without
+ * mismatch offsets.  A locus this route settles is not counted by trgt_hip_flank_stats, one it hands back is in no other count;
+ * trgt_hip_flank_stats out[2] keeps counting the loci the host's own flank step sends. */
+int trgt_hip_set_snv_split_device(trgt_hip_ctx* ctx, int on);
+int trgt_hip_snv_split_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
 
 /* ---- kernel timing (HIP events on the ctx stream, for bench.py's roofline) ---- */
 #define TRGT_K_FLANK_SCAN 0   /* exact flank search (+ the segment search for the seeded windows of the fallback alignments) */

@@ -72,7 +72,7 @@ class LocusBatchOut(C.Structure):
 EXPORTS = [
     "trgt_inflate_raw", "trgt_inflate_blocks", "trgt_deflate_blocks",
     "trgt_hip_abi_version", "trgt_hip_create", "trgt_hip_destroy", "trgt_hip_last_error", "trgt_hip_set_stream",
-    "trgt_hip_set_workspace_limit", "trgt_hip_cluster_max_reads_limit", "trgt_hip_set_cluster_max_reads", "trgt_hip_size_max_reads_limit", "trgt_hip_set_size_max_reads", "trgt_hip_size_deep_stats", "trgt_hip_set_flank_device", "trgt_hip_flank_stats", "trgt_hip_timing_enable", "trgt_hip_timing_reset", "trgt_hip_timing_get",
+    "trgt_hip_set_workspace_limit", "trgt_hip_cluster_max_reads_limit", "trgt_hip_set_cluster_max_reads", "trgt_hip_size_max_reads_limit", "trgt_hip_set_size_max_reads", "trgt_hip_size_deep_stats", "trgt_hip_set_flank_device", "trgt_hip_flank_stats", "trgt_hip_set_snv_split_device", "trgt_hip_snv_split_stats", "trgt_hip_timing_enable", "trgt_hip_timing_reset", "trgt_hip_timing_get",
     "trgt_wfa_default_params", "trgt_wfa_batch", "trgt_flank_filter_batch", "trgt_find_spans_batch", "trgt_hmm_batch", "trgt_hmm_path_capacity", "trgt_hmm_models_check",
     "trgt_locus_batch", "trgt_locus_batch_submit", "trgt_locus_batch_wait", "trgt_locus_default_params", "trgt_reads_pack_bam4",
     "trgt_hip_pool_create", "trgt_hip_pool_destroy", "trgt_hip_pool_size", "trgt_hip_pool_context", "trgt_hip_pool_last_error", "trgt_locus_batch_many",
@@ -132,6 +132,8 @@ def lib():
         L.trgt_hip_size_deep_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_set_flank_device.argtypes = [_VP, C.c_int]
         L.trgt_hip_flank_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
+        L.trgt_hip_set_snv_split_device.argtypes = [_VP, C.c_int]
+        L.trgt_hip_snv_split_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_set_flank_cluster_device.argtypes = [_VP, C.c_int]
         L.trgt_hip_flank_cluster_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_timing_enable.argtypes = [_VP, C.c_int]
@@ -215,6 +217,19 @@ class Context:
         self.check(lib().trgt_hip_flank_stats(self.handle, out))
         return tuple(int(v) for v in out)
 
+    def set_snv_split_device(self, on=True):
+        """trgt_hip_set_snv_split_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) runs inside the one-wave size
+        genotyper for batches that carry mismatch offsets; a locus whose candidate search is not decided beyond the margin, or that is
+        beyond the route's limits, goes to the host path as before.  Independent of set_flank_device.  Every later call on this context uses it."""
+        self.check(lib().trgt_hip_set_snv_split_device(self.handle, int(bool(on))))
+
+    def snv_split_stats(self):
+        """trgt_hip_snv_split_stats of the context's last trgt_locus_batch: (loci whose genotype the device replaced through the SNV
+        branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided)."""
+        out = (C.c_int64 * 4)()
+        self.check(lib().trgt_hip_snv_split_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def set_flank_cluster_device(self, on=True):
         """trgt_hip_set_flank_cluster_device: the haplotype-tag branch of genotype_flank behind the one-wave cluster chain, for the
         Genotyper::Cluster loci of at most 256 candidate reads of batches that carry hp_tag (off, the default: the host redoes such a
@@ -254,7 +269,7 @@ class Context:
 class Pool:
     """trgt_hip_pool: several contexts (devices[i] = ordinal of context i, ordinals may repeat) behind one queue of batches."""
 
-    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None):
+    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, snv_split_device=None):
         L = lib()
         L.trgt_hip_pool_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
         L.trgt_hip_pool_destroy.argtypes = [C.c_void_p]
@@ -290,6 +305,9 @@ class Pool:
         if flank_cluster_device is not None:
             for c in self.contexts:
                 c.set_flank_cluster_device(flank_cluster_device)
+        if snv_split_device is not None:
+            for c in self.contexts:
+                c.set_snv_split_device(snv_split_device)
 
     def run_many(self, params_struct, cins, couts, out_per_context=False):
         """cins / couts: lists of LocusBatchIn / LocusBatchOut structures (couts: one per batch, or one per context)"""

@@ -112,6 +112,8 @@ struct trgt_hip_ctx {
   int64_t size_deep_stats[4] = {0, 0, 0, 0};  // trgt_hip_size_deep_stats: the deep size loci of the last trgt_locus_batch (genotyped on the device, repaired among them, handed to the host, reserved)
   bool flank_device = false;  // trgt_hip_set_flank_device: the haplotype-tag branch of genotype_flank runs in the device genotyper (locus_gt.hpp, FLANK forms)
   int64_t flank_stats[4] = {0, 0, 0, 0};  // trgt_hip_flank_stats: of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, loci sent to the host path for the flank step, reserved)
+  bool snv_split_device = false;  // trgt_hip_set_snv_split_device: the SNV branch of genotype_flank runs in the device genotyper (locus_gt.hpp, SNV forms)
+  int64_t snv_split_stats[4] = {0, 0, 0, 0};  // trgt_hip_snv_split_stats: of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, handed back for room or limits, handed back undecided)
   bool flank_cluster_device = false;  // trgt_hip_set_flank_cluster_device: the same branch behind the one-wave cluster chain (locus_cluster_flank.hpp)
   int64_t flank_cluster_stats[3] = {0, 0, 0};  // trgt_hip_flank_cluster_stats: cluster loci of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, handed back to the host path)
   int num_cus = 256;
@@ -275,6 +277,7 @@ enum Slot {
   S_CLD_SEL,  // ... and its selected lists and merge records (one slab, shared with the deep size list)
   S_GSD_LIST,  // the deep list of the size genotyper (locus_gt_deep.hpp)
   S_GT_HP,     // the reads' haplotype tags for the FLANK forms of the device genotyper (locus_gt.hpp)
+  S_SNV_SO, S_SNV_EO, S_SNV_MM, S_SNV_MMOFF, S_SNV_READ,  // the SNV forms' inputs (start / end offsets, mismatch offsets and their table) and per-read byte
   S_CLF_COUNTS,  // the counters of the tag branch behind the one-wave cluster chain (locus_cluster_flank.hpp)
   S_CLF_PEND,    // ... and its records of the loci that wait for the third consensus round
   S_COUNT

@@ -647,6 +647,11 @@ const OneWave<gt::GtArgs, gt::FinishArgs> k_repair_finish{{{gt::repair_finish_ke
 const OneWave<gt::GtFlankArgs> k_genotype_flank{{{gt::locus_genotype_kernel<64, 8 * 1024, false, true>, gt::locus_genotype_kernel<64, 8 * 1024, true, true>},
                                             {gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS, false, true>, gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS, true, true>}}};
 const OneWave<gt::GtFlankArgs, gt::FinishArgs> k_repair_finish_flank{{{gt::repair_finish_kernel<64, false, true>, gt::repair_finish_kernel<64, true, true>}, {gt::repair_finish_kernel<GT_BIG, false, true>, gt::repair_finish_kernel<GT_BIG, true, true>}}};
+// (the SNV forms: contexts that opted in to the SNV split on the device, trgt_hip_set_snv_split_device, calls whose reads carry mismatch offsets)
+const OneWave<gt::SnvArgs> k_genotype_snv{{{gt::locus_genotype_kernel<64, 8 * 1024, false, true, true>, gt::locus_genotype_kernel<64, 8 * 1024, true, true, true>},
+                                        {gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS, false, true, true>, gt::locus_genotype_kernel<GT_BIG, gt::GT_SEG_LDS, true, true, true>}}};
+const OneWave<gt::SnvArgs, gt::FinishArgs> k_repair_finish_snv{{{gt::repair_finish_kernel<64, false, true, true>, gt::repair_finish_kernel<64, true, true, true>},
+                                                              {gt::repair_finish_kernel<GT_BIG, false, true, true>, gt::repair_finish_kernel<GT_BIG, true, true, true>}}};
 const OneWave<cl::ClArgs> k_cluster_front{{{cl::cluster_front_kernel<64>, cl::cluster_front_kernel<64, true>}, {cl::cluster_front_kernel<GT_BIG>, cl::cluster_front_kernel<GT_BIG, true>}}};
 // (the ward kernel's second argument is LDS_MAT: the distance matrix of a small locus fits the LDS -- it follows the size, not the filter)
 const OneWave<cl::ClArgs> k_cluster_ward{{{cl::cluster_ward_kernel<64, true>, cl::cluster_ward_kernel<64, true, true>}, {cl::cluster_ward_kernel<GT_BIG, false>, cl::cluster_ward_kernel<GT_BIG, false, true>}}};
@@ -690,6 +695,7 @@ struct LocusCall {
     void *need = nullptr, *nal = nullptr, *blob = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr,
          *toff = nullptr, *packed = nullptr;
     const double* rq = nullptr; const int16_t* hp = nullptr;
+    const int32_t *so = nullptr, *eo = nullptr, *mm = nullptr; const uint64_t* mm_off = nullptr; void* snv_read = nullptr;  // the SNV forms' inputs, their per-read byte
   };
   struct GtHost { void *need = nullptr, *nal = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr, *toff = nullptr, *packed = nullptr; };
   struct ClPlan { std::vector<uint32_t> list; std::vector<uint64_t> moff; uint64_t pairs = 0, reads = 0; uint32_t max_nr = 0; const uint32_t* d_list = nullptr; const uint64_t* d_moff = nullptr; };
@@ -703,7 +709,7 @@ struct LocusCall {
   const int64_t nl; int64_t nr = 0; int F = 0;
   bool done = false;  // nothing left to do (a call without loci or without reads)
   trgt_locus_batch_in in_expanded; std::vector<uint64_t> expanded_off;  // TRGT_READS_BAM4: the batch with its reads expanded in HBM
-  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, flank_cl_dev = false, cf_route = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
+  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, snv_dev = false, flank_cl_dev = false, cf_route = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
   FlankMeta flank_meta{};
   // ---- clean-up state (see the destructor)
   bool zeroed = false;
@@ -771,6 +777,13 @@ struct LocusCall {
   bool is_cluster(int64_t l) const { return in->genotyper && in->genotyper[l] == 1; }
   // ga as it stands, with what the FLANK forms read beyond it
   gt::GtFlankArgs flank_args() const { gt::GtFlankArgs fa; static_cast<gt::GtArgs&>(fa) = ga; fa.hp_tag = g.hp; fa.flank_done = (uint8_t*)slab.d(o_fdone); return fa; }
+  // ... and with what the SNV forms read beyond that (the three logarithms are the host's: flank_split's own)
+  gt::SnvArgs snv_args() const {
+    gt::SnvArgs sa; static_cast<gt::GtFlankArgs&>(sa) = flank_args();
+    sa.start_offset = g.so; sa.end_offset = g.eo; sa.mismatch_offsets = g.mm; sa.mismatch_off = g.mm_off; sa.snv_read = (uint8_t*)g.snv_read;
+    sa.ln_match = std::log(0.9); sa.ln_mis = std::log(1.0 - 0.9); sa.ln2 = std::log(2.0); sa.tag_route = flank_dev ? 1 : 0;
+    return sa;
+  }
   gtd::DeepFlankArgs deep_flank_args() const { return gtd::DeepFlankArgs{ds, g.hp, (uint8_t*)slab.d(o_fdone)}; }  // the deep size list's FLANK forms (ds.c.g = ga is the caller's)
   uint64_t& cell(int w) { return ((uint64_t*)h_cells)[w]; }
   void tl(const char* name) const { if (tl_on) fprintf(stderr, "[tl] %-28s %7.2f ms  ctx=%p\n", name, (double)(now_ns() - t0) / 1e6, (void*)c); }
@@ -789,6 +802,7 @@ int LocusCall::check_args() {
   for (int64_t& v : c->size_deep_stats) v = 0;
   for (int64_t& v : c->flank_stats) v = 0;
   for (int64_t& v : c->flank_cluster_stats) v = 0;
+  for (int64_t& v : c->snv_split_stats) v = 0;
   if (nl == 0) { done = true; return TRGT_OK; }
   if (!in->flank_blob || !in->lf_off || !in->lf_len || !in->rf_off || !in->rf_len || !in->tr_blob || !in->tr_off || !in->tr_len ||
       !in->motif_blob || !in->motif_off || !in->set_motif_begin || !in->ploidy || !in->locus_read_begin || !in->read_blob ||
@@ -904,6 +918,9 @@ int LocusCall::upload_tables() {
   // ... and its haplotype-tag branch runs inside the device genotyper on a context that opted in (trgt_hip_set_flank_device): the FLANK
   // forms of locus_gt.hpp, which read the tags and leave one byte per locus
   flank_dev = dev_gt && c->flank_device && in->hp_tag != nullptr;
+  // ... and its SNV branch likewise on a context that opted in to that (trgt_hip_set_snv_split_device), for a batch with mismatch offsets:
+  // the SNV forms, which take the place of the FLANK forms of the one-wave kernels (the deep size list keeps its own)
+  snv_dev = dev_gt && c->snv_split_device && in->mismatch_offsets != nullptr && in->mismatch_off != nullptr;
   // ... and, a setting of its own (trgt_hip_set_flank_cluster_device), behind the one-wave cluster chain: locus_cluster_flank.hpp
   flank_cl_dev = dev_gt && c->flank_cluster_device && in->hp_tag != nullptr;
   int rc;
@@ -928,7 +945,7 @@ int LocusCall::upload_tables() {
     o_nsp = slab.add(2 * (size_t)nl * 4); o_cls = slab.add((size_t)nr * 4); o_rank = slab.add((size_t)nr * 4); o_nspan = slab.add((size_t)nl * 4);
     o_toff = slab.add((2 * (size_t)nl + 1) * 8); o_flip = slab.add((size_t)nl);
     o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
-    if (flank_dev || flank_cl_dev) o_fdone = slab.add((size_t)nl);
+    if (flank_dev || flank_cl_dev || snv_dev) o_fdone = slab.add((size_t)nl);
     if (flank_cl_dev) o_cfc = slab.add(clf::CF_WORDS * 4);
   }
   if ((rc = dev_get(c, S_LOCUS_4, slab.total, &slab.dev)) || (rc = pin_get(c, P_SPAN_S, slab.total, &slab.host))) return rc;
@@ -940,7 +957,12 @@ int LocusCall::upload_tables() {
         (rc = dev_in(c, S_GT_TRLEN, in->tr_len, (size_t)nl, &g.tr_len, &ub)) || (rc = dev_in(c, S_GT_ALOFF, out->allele_off, 2 * (size_t)nl, &g.al_off, &ub)) ||
         (rc = dev_in(c, S_GT_ALCAP, out->allele_cap, (size_t)nl, &g.al_cap, &ub)) || (in->genotyper && (rc = dev_in(c, S_GT_GENO, in->genotyper, (size_t)nl, &g.geno, &ub))) ||
         (presel && in->read_qual && (rc = dev_in(c, S_PUR_RQ, in->read_qual, (size_t)nr, &g.rq, &ub))) ||
-        ((flank_dev || flank_cl_dev) && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
+        ((flank_dev || flank_cl_dev || (snv_dev && in->hp_tag)) && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
+        (snv_dev && ((in->start_offset && (rc = dev_in(c, S_SNV_SO, in->start_offset, (size_t)nr, &g.so, &ub))) ||
+                     (in->end_offset && (rc = dev_in(c, S_SNV_EO, in->end_offset, (size_t)nr, &g.eo, &ub))) ||
+                     (rc = dev_in(c, S_SNV_MMOFF, in->mismatch_off, (size_t)nr + 1, &g.mm_off, &ub)) ||
+                     (rc = dev_in(c, S_SNV_MM, in->mismatch_offsets, (size_t)in->mismatch_off[nr], &g.mm, &ub)) ||
+                     (rc = dev_get(c, S_SNV_READ, (size_t)nr + 16, &g.snv_read)))) ||
         (rc = dev_get(c, S_GT_BLOB, (size_t)allele_total + 16, &g.blob)) || (rc = dev_get(c, S_GT_PACKED, (size_t)allele_total + 16, &g.packed)))
       return rc;
   }
@@ -1185,7 +1207,8 @@ int LocusCall::purity_chain() {
 }
 int LocusCall::size_genotyper() {
   if (!dev_gt) return TRGT_OK;
-  if (flank_dev) k_genotype_flank.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, flank_args());
+  if (snv_dev) k_genotype_snv.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, snv_args());
+  else if (flank_dev) k_genotype_flank.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, flank_args());
   else k_genotype.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, ga);
   if (!gsd_list.empty()) {
     // ---- the deep size list, behind the one-wave genotyper (which marked these loci need_host = 1): selection unless it ran in front
@@ -1271,7 +1294,8 @@ int LocusCall::repair_chain() {
   hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)rp.cap_groups), dim3(vote::VOTE_THREADS), 0, c->stream, va);
   const gt::FinishArgs fa{(const uint8_t*)rb.vout, (const uint32_t*)rb.vlen};
   const dim3 fgrid((unsigned)nl);
-  if (flank_dev) k_repair_finish_flank.launch(!small_gt, presel, fgrid, c->stream, flank_args(), fa);
+  if (snv_dev) k_repair_finish_snv.launch(!small_gt, presel, fgrid, c->stream, snv_args(), fa);
+  else if (flank_dev) k_repair_finish_flank.launch(!small_gt, presel, fgrid, c->stream, flank_args(), fa);
   else k_repair_finish.launch(!small_gt, presel, fgrid, c->stream, ga, fa);
   if (!gsd_list.empty()) {
     ds.c.g = ga;
@@ -1466,15 +1490,17 @@ int LocusCall::wait_stage_a() {
       const int32_t* nal = (const int32_t*)gh.nal; const uint32_t* alen = (const uint32_t*)gh.alen; const int32_t* rank = (const int32_t*)gh.rank;
       // (the byte of a locus is read only where a kernel wrote it: every locus with the FLANK size kernels, the shallow cluster list with the
       //  cluster route; a cluster locus has a byte of the cluster route's or none)
-      const uint8_t* fdone = flank_dev || cf_route ? (const uint8_t*)slab.h(o_fdone) : nullptr;
+      //  cluster route; a cluster locus has a byte of the cluster route's or none.  The SNV forms write every locus' byte as well, and
+      //  add FL_NOSPLIT: both branches of flank_split were evaluated on the device and neither splits the reads)
+      const uint8_t* fdone = flank_dev || snv_dev || cf_route ? (const uint8_t*)slab.h(o_fdone) : nullptr;
       auto fl_byte = [&](int64_t l) -> uint8_t {
-        if (!is_cluster(l)) return flank_dev ? fdone[l] : (uint8_t)0;
+        if (!is_cluster(l)) return flank_dev || snv_dev ? fdone[l] : (uint8_t)0;
         const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
         return cf_route && in->ploidy[l] != 0 && n > 0 && n <= (uint64_t)gt::GT_MAX_READS ? fdone[l] : (uint8_t)0;
       };
       std::atomic<int64_t> sent{0};
       pool->parallel_for(nl, 64, [&](int64_t l, int) {
-        if (need[l] || (fdone && (fl_byte(l) & gt::FL_DONE)) || nal[l] != 2 || adiff(alen[2 * l], alen[2 * l + 1]) > 10) return;
+        if (need[l] || (fdone && (fl_byte(l) & (gt::FL_DONE | gt::FL_NOSPLIT))) || nal[l] != 2 || adiff(alen[2 * l], alen[2 * l + 1]) > 10) return;
         const uint64_t r0 = in->locus_read_begin[l], r1 = in->locus_read_begin[l + 1];
         std::vector<uint32_t> order;
         for (uint64_t r = r0; r < r1; ++r) if (rank[r] >= 0) { if ((size_t)rank[r] >= order.size()) order.resize((size_t)rank[r] + 1, 0); order[(size_t)rank[r]] = (uint32_t)r; }
@@ -1491,6 +1517,7 @@ int LocusCall::wait_stage_a() {
       if (flank_dev) {  // trgt_hip_flank_stats (never a cluster locus in [0], [1], [3])
         for (int64_t l = 0; l < nl; ++l) {
           if (is_cluster(l)) continue;
+          if (fdone[l] & gt::FL_SNV) continue;  // trgt_hip_snv_split_stats'
           if ((fdone[l] & gt::FL_DONE) && !need[l]) {
             c->flank_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_stats[1] += 1;
             if (in->locus_read_begin[l + 1] - in->locus_read_begin[l] > (uint64_t)gt::GT_MAX_READS) c->flank_stats[3] += 1;  // the deep size list's
@@ -1498,6 +1525,15 @@ int LocusCall::wait_stage_a() {
           else if (fdone[l] == gt::FL_HANDED) c->flank_stats[2] += 1;
         }
         c->flank_stats[2] += sent.load();
+      }
+      if (snv_dev) {  // trgt_hip_snv_split_stats: the bytes the SNV branch of the one-wave kernels left
+        for (int64_t l = 0; l < nl; ++l) {
+          const uint8_t b = fdone[l];
+          if (is_cluster(l) || !(b & gt::FL_SNV)) continue;
+          if ((b & gt::FL_DONE) && !need[l]) { c->snv_split_stats[0] += 1; if (b & gt::FL_REPAIRED) c->snv_split_stats[1] += 1; }
+          else if (b & gt::FL_UNDECIDED) c->snv_split_stats[3] += 1;
+          else if (b & gt::FL_HANDED) c->snv_split_stats[2] += 1;
+        }
       }
     }
     for (int64_t l = 0; l < nl; ++l) if (need[l]) R.push_back(l);
@@ -2156,6 +2192,18 @@ extern "C" int trgt_hip_set_flank_device(trgt_hip_ctx* c, int on) {
 extern "C" int trgt_hip_flank_stats(const trgt_hip_ctx* c, int64_t out[4]) {
   if (!c || !out) return TRGT_ERR_INVALID;
   for (int i = 0; i < 4; ++i) out[i] = c->flank_stats[i];
+  return TRGT_OK;
+}
+
+// ---- ... and the SNV branch of genotype_flank, a setting of its own (locus_gt.hpp, SNV forms)
+extern "C" int trgt_hip_set_snv_split_device(trgt_hip_ctx* c, int on) {
+  if (!c) return TRGT_ERR_INVALID;
+  c->snv_split_device = on != 0;
+  return TRGT_OK;
+}
+extern "C" int trgt_hip_snv_split_stats(const trgt_hip_ctx* c, int64_t out[4]) {
+  if (!c || !out) return TRGT_ERR_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = c->snv_split_stats[i];
   return TRGT_OK;
 }
 

@@ -12,6 +12,8 @@
 // The arithmetic (f64 penalties, tie-breaks) is written operation for operation like the host version in locus.hip, which the oracle pins.
 // The FLANK instantiations (contexts that opted in, trgt_hip_set_flank_device) also run the haplotype-tag branch of
 // genotype_flank::genotype (genotype_flank.rs:9-76, 147-170; tr.rs:69-75) for a locus whose two sizes are at most 10 apart: see flank_route.
+// The SNV instantiations (contexts that opted in, trgt_hip_set_snv_split_device; batches that carry mismatch offsets) add the other branch,
+// the split by heterozygous SNVs of the flanks (genotype_flank.rs:78-138, 171-290): see snv_route.
 #pragma once
 #include <type_traits>
 
@@ -36,9 +38,21 @@ constexpr int GT_SEG_LDS = 16 * 1024;  // bytes of repeat segments staged per lo
 // n_pick of a record the haplotype-tag route wrote (FLANK instantiations only): rep[] are the backbones of the two tag groups, civ[] the
 // groups' length ranges, and the finish is flank_finish's
 constexpr int32_t RP_FLANK = 0x100;
+constexpr int32_t RP_SNV = 0x200;  // with RP_FLANK: the groups are the SNV branch's (SNV instantiations only)
 // GtFlankArgs::flank_done, per locus: the tag split replaced the genotype (FL_DONE; FL_DONE | FL_REPAIRED: behind the repair chain), or the
 // split was accepted and the locus handed to the host path (no room in the chain, a segment beyond max_seg, allele_cap)
-enum { FL_DONE = 1, FL_REPAIRED = 2, FL_HANDED = 4 };
+// The SNV instantiations add: FL_NOSPLIT -- the kernel evaluated both branches of genotype_flank for the locus and neither splits its reads
+// (the host need not look again); FL_SNV -- the byte is the SNV branch's (its loci are counted by trgt_hip_snv_split_stats and by no other
+// count); FL_UNDECIDED, with FL_HANDED -- handed to the host path because the candidate search was not decided beyond the margin
+enum { FL_DONE = 1, FL_REPAIRED = 2, FL_HANDED = 4, FL_NOSPLIT = 8, FL_SNV = 16, FL_UNDECIDED = 32 };
+// limits of the SNV branch on the device; a locus beyond one of them is handed to the host path (FL_HANDED | FL_SNV)
+constexpr int SNV_MAX_SNVS = 64;        // called SNVs: one bit each in the two masks of a read's profile
+constexpr int SNV_MAX_HAPS = 16;        // distinct fully observed profiles: 136 candidate genotypes, three rounds of one lane per candidate
+constexpr int SNV_OFFS_PER_READ = 8;    // in-region mismatch offsets of a locus (occurrences, all reads together): 8 * MAXR.  They are counted
+                                        // all against all: at the cap every lane compares its 8 * MAXR / 64 entries with 8 * MAXR others,
+                                        // (8 * MAXR)^2 / 64 LDS reads per lane -- 4 096 for MAXR = 64, 65 536 for MAXR = 256
+// the per-read byte of a locus the SNV branch left waiting for the repair chain (SnvArgs::snv_read): assignment, membership of either group
+enum { SR_ASSIGN = 1, SR_IN0 = 2, SR_IN1 = 4 };
 
 struct GtArgs {
   const uint8_t* reads; const uint64_t* read_off; const uint32_t* read_len; const uint64_t* locus_read_begin;
@@ -64,7 +78,15 @@ struct GtFlankArgs : GtArgs {
   const int16_t* hp_tag;  // per read of the batch: the HP tag (-1 = None)
   uint8_t* flank_done;    // [n_loci] FL_* above
 };
-template <bool FLANK> using GtArgsOf = std::conditional_t<FLANK, GtFlankArgs, GtArgs>;
+// The arguments of the SNV instantiations (contexts that opted in to the SNV split on the device, batches with mismatch offsets).
+struct SnvArgs : GtFlankArgs {
+  const int32_t *start_offset, *end_offset;  // per read of the batch (NULL = 0 for every read, as in flank_split)
+  const int32_t* mismatch_offsets; const uint64_t* mismatch_off;  // per read r: its ascending offsets in [mismatch_off[r], mismatch_off[r + 1])
+  uint8_t* snv_read;      // per read slot of the batch, by position in the kept list: SR_* of a locus that waits for the repair chain
+  double ln_match, ln_mis, ln2;  // ln 0.9, ln(1.0 - 0.9), ln 2 as the host's libm rounds them
+  int32_t tag_route;      // 1: tags that split the reads are flank_route's (trgt_hip_set_flank_device is on as well); 0: such a locus is the host's
+};
+template <bool FLANK, bool SNV = false> using GtArgsOf = std::conditional_t<SNV, SnvArgs, std::conditional_t<FLANK, GtFlankArgs, GtArgs>>;
 
 // what the haplotype-tag route adds to the LDS of the FLANK instantiations (1.5 KB for 256 reads); the assignment lives in cls[]
 template <int MAXR, bool FLANK> struct FlankShared {};
@@ -73,8 +95,23 @@ template <int MAXR> struct FlankShared<MAXR, true> {
   uint16_t f_cnt[2][MAXR];  // multiplicity of every unique sequence inside either tag group
   uint32_t f_med[2][2];     // the two middle lengths of either group
 };
-template <int MAXR, int SEG, bool FLANK = false>
-struct GtShared : FlankShared<MAXR, FLANK> {
+// ... and the SNV branch (10.9 KB for 256 reads, 3 KB for 64): offsets of the reads, the in-region mismatch offsets while the SNVs are
+// called and -- in the same bytes, the offsets being done with -- the profiles, the candidates' haplotypes and log-likelihoods
+template <int MAXR, bool SNV> struct SnvShared {};
+template <int MAXR> struct SnvShared<MAXR, true> {
+  int32_t v_so[MAXR], v_eo[MAXR];  // per kept read: start_offset / end_offset
+  union {
+    int32_t offs[SNV_OFFS_PER_READ * MAXR];         // the in-region offsets of all reads, in read order
+    struct { uint64_t obs[MAXR], val[MAXR]; } p;  // per kept read: SNV k is bit k of obs (the read covers it) and of val (it carries the mismatch)
+  } v;
+  int32_t v_snv[SNV_MAX_SNVS], v_tmp[SNV_MAX_SNVS];  // the called SNVs ascending (v_tmp: as found)
+  uint64_t v_hap[SNV_MAX_HAPS];                      // the distinct fully observed profiles in the derived order of Option<bool>
+  double v_ll[SNV_MAX_HAPS * (SNV_MAX_HAPS + 1) / 2];
+  uint8_t v_tie[MAXR];                               // per kept read: it agrees equally with both haplotypes and belongs to both groups
+  int32_t v_reg[2];
+};
+template <int MAXR, int SEG, bool FLANK = false, bool SNV = false>
+struct GtShared : FlankShared<MAXR, FLANK>, SnvShared<MAXR, SNV> {
   uint32_t r_s[MAXR], r_len[MAXR];     // per read of the locus: span start / span length (0xFFFFFFFF start = not kept)
   uint64_t r_off[MAXR];                        // per read: byte offset of the read in the blob
   uint32_t s_read[MAXR], s_start[MAXR], s_len[MAXR];  // kept reads in LocusResult.reads order
@@ -254,15 +291,21 @@ __device__ __forceinline__ bool flank_assign(SH& sh, const int16_t* __restrict__
   return cnt[0] > 0 && cnt[1] > 0 && (double)(n - untagged) / (double)n >= 0.7;
 }
 
-// The route inside the genotype kernel, behind get_seq_hist (nu unique sequences in sh.u_rep, sh.f_uidx[i] = position of the first read
-// with read i's sequence).  false: the tags do not split the reads and the locus continues with the length genotype.  true: the locus is
-// settled here -- simple_consensus (:147-170) of either group; without a group below 50 % the genotype is written to sh.res_* / sh.cls
-// like the length genotyper's, else the groups join the call's repair chain (sh.bail = 2: flank_finish completes the locus), or the locus
-// is handed to the host path (sh.bail = 1).  Called by the whole wave with uniform arguments.
-template <class SH>
-__device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_t l, uint64_t r0, int n, int nu, int lane, bool fits, uint32_t refn, uint64_t refo) {
-  int cnt[2];
-  if (!flank_assign(sh, a.hp_tag, r0, n, lane, cnt)) return false;
+// Who belongs to group g of a split whose assignment is in sh.cls.  By tags: the reads assigned to it.  By SNVs (:114-137): those, and the
+// reads that agree equally with both haplotypes (sh.v_tie), which join both groups while their assignment alternates.
+struct TagMembers { static constexpr bool BOTH = false; template <class SH> static __device__ __forceinline__ bool in(const SH& sh, int i, int g) { return sh.cls[i] == g; } };
+struct SnvMembers { static constexpr bool BOTH = true; template <class SH> static __device__ __forceinline__ bool in(const SH& sh, int i, int g) { return sh.cls[i] == g || sh.v_tie[i]; } };
+
+// What follows an accepted split (genotype_flank.rs:20-41), behind get_seq_hist (nu unique sequences in sh.u_rep, sh.f_uidx[i] = position
+// of the first read with read i's sequence): simple_consensus (:147-170) of either group -- cnt[g] members, MEM says who; hap[g] reads are
+// assigned to it (num_spanning, tr.rs:79-82).  Without a group below 50 % the genotype is written to sh.res_* / sh.cls like the length
+// genotyper's, else the groups join the call's repair chain (sh.bail = 2: flank_finish completes the locus), or the locus is handed to
+// the host path (sh.bail = 1).  mark: FL_SNV for the SNV branch, 0 for the tags'.  false (BOTH only): a group is empty, there is no split.
+// Called by the whole wave with uniform arguments.
+template <class MEM, class SH>
+__device__ __forceinline__ bool flank_tail(SH& sh, const GtFlankArgs& a, int64_t l, int n, int nu, int lane, bool fits, uint32_t refn, uint64_t refo, const int cnt[2],
+                                           const int hap[2], const uint8_t mark) {
+  if constexpr (MEM::BOTH) { if (cnt[0] == 0 || cnt[1] == 0) return false; }
   // ---- the unique sequence of every read as its rank in u_rep (the insertions of get_seq_hist moved the ranks while the list grew)
   uint16_t* inv = sh.f_cnt[0];
   for (int q = lane; q < nu; q += 64) inv[sh.u_rep[q]] = (uint16_t)q;
@@ -272,15 +315,20 @@ __device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_
   // ---- multiplicities inside the groups (lane q owns unique sequence q), and the middle lengths of either group by rank
   for (int q = lane; q < nu; q += 64) {
     int c0 = 0, c1 = 0;
-    for (int i = 0; i < n; ++i) if (sh.f_uidx[i] == q) { if (sh.cls[i]) ++c1; else ++c0; }
+    if constexpr (MEM::BOTH) { for (int i = 0; i < n; ++i) if (sh.f_uidx[i] == q) { c0 += MEM::in(sh, i, 0); c1 += MEM::in(sh, i, 1); } }
+    else for (int i = 0; i < n; ++i) if (sh.f_uidx[i] == q) { if (sh.cls[i]) ++c1; else ++c0; }
     sh.f_cnt[0][q] = (uint16_t)c0; sh.f_cnt[1][q] = (uint16_t)c1;
   }
-  for (int i = lane; i < n; i += 64) {
-    const int g = sh.cls[i]; const uint32_t li = sh.s_len[i];
+  auto middle = [&](int i, int g) {  // read i is a middle element of group g: its rank among the group's lengths
+    const uint32_t li = sh.s_len[i];
     int r = 0;
-    for (int j = 0; j < n; ++j) { const uint32_t lj = sh.s_len[j]; r += sh.cls[j] == g && (lj < li || (lj == li && j < i)); }
+    for (int j = 0; j < n; ++j) { const uint32_t lj = sh.s_len[j]; r += MEM::in(sh, j, g) && (lj < li || (lj == li && j < i)); }
     if (r == cnt[g] / 2) sh.f_med[g][1] = li;
     if (r == cnt[g] / 2 - 1) sh.f_med[g][0] = li;
+  };
+  for (int i = lane; i < n; i += 64) {
+    if constexpr (MEM::BOTH) { for (int g = 0; g < 2; ++g) if (MEM::in(sh, i, g)) middle(i, g); }
+    else middle(i, sh.cls[i]);
   }
   __syncthreads();
   int rep[2]; uint32_t aln[2], lo[2], hi[2]; bool lacks[2];
@@ -299,7 +347,7 @@ __device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_
       const uint32_t od = (uint32_t)__shfl_xor((int)bd, o); const int oq = __shfl_xor(bq, o);
       if (od < bd || (od == bd && oq < bq)) { bd = od; bq = oq; }
     }
-    for (int i = lane; i < n; i += 64) if (sh.cls[i] == g) { mn = sh.s_len[i] < mn ? sh.s_len[i] : mn; mx = sh.s_len[i] > mx ? sh.s_len[i] : mx; }
+    for (int i = lane; i < n; i += 64) if (MEM::in(sh, i, g)) { mn = sh.s_len[i] < mn ? sh.s_len[i] : mn; mx = sh.s_len[i] > mx ? sh.s_len[i] : mx; }
     lo[g] = wave_min_u(mn); hi[g] = wave_max_u(mx);
     rep[g] = sh.u_rep[bq]; aln[g] = sh.s_len[rep[g]];
     lacks[g] = (double)top / (double)cnt[g] < 0.5;
@@ -314,7 +362,7 @@ __device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_
         if (!lacks[g]) continue;
         if (aln[g] > rp.max_seg) can = false;
         for (int i = 0; i < n; ++i) {
-          if (sh.cls[i] != g) continue;
+          if (!MEM::in(sh, i, g)) continue;
           if (sh.s_len[i] > rp.max_seg) can = false;
           nm[g] += 1; mbytes[g] += sh.s_len[i];
         }
@@ -327,15 +375,15 @@ __device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_
       __syncthreads();
       can = sh.rsv.ok != 0;
     }
-    if (!can) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED; return true; }
+    if (!can) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED | mark; return true; }
     Reserved at = sh.rsv;
     auto seg_of = [&](int i) { return Seg{sh.r_off[sh.s_read[i]] + sh.s_start[i], sh.s_len[i]}; };
     RepairPend pd;
-    pd.n_gt = 2; pd.n_pick = 2 | RP_FLANK; pd.size[0] = aln[0]; pd.size[1] = aln[1];
+    pd.n_gt = 2; pd.n_pick = 2 | RP_FLANK | (MEM::BOTH ? RP_SNV : 0); pd.size[0] = aln[0]; pd.size[1] = aln[1];
     for (int g = 0; g < 2; ++g) { pd.civ[2 * g] = (int32_t)lo[g]; pd.civ[2 * g + 1] = (int32_t)hi[g]; pd.rep[g] = rep[g]; pd.grp[g] = -1; }
 #pragma unroll
     for (int g = 0; g < 2; ++g)
-      if (lacks[g]) pd.grp[g] = (int32_t)queue_group<64>(rp.groups, rp.jobs, at, seg_of(rep[g]), nm[g], nd[g], n, [&, g](int i) { return sh.cls[i] == g; }, seg_of);
+      if (lacks[g]) pd.grp[g] = (int32_t)queue_group<64>(rp.groups, rp.jobs, at, seg_of(rep[g]), nm[g], nd[g], n, [&, g](int i) { return MEM::in(sh, i, g); }, seg_of);
     if (lane == 0) rp.pend[l] = pd;
     sh.bail = 2;  // the locus waits for repair_finish_kernel
     return true;
@@ -350,19 +398,228 @@ __device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_
   };
   int order[2] = {sw, 1 - sw}; int flip = 0;
   if (!eq_ref(order[0]) && eq_ref(order[1])) { order[0] = 1 - sw; order[1] = sw; flip = 1; }
-  if (aln[0] > a.allele_cap[l] || aln[1] > a.allele_cap[l]) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED; return true; }  // the host path reports the error
+  if (aln[0] > a.allele_cap[l] || aln[1] > a.allele_cap[l]) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED | mark; return true; }  // the host path reports the error
   sh.res_n_gt = 2; sh.res_flip = flip;
   for (int oi = 0; oi < 2; ++oi) {
     const int g = order[oi];
-    sh.res_rep[oi] = rep[g]; sh.res_ci[2 * oi] = (int)lo[g]; sh.res_ci[2 * oi + 1] = (int)hi[g]; sh.res_hap[oi] = cnt[g];
+    sh.res_rep[oi] = rep[g]; sh.res_ci[2 * oi] = (int)lo[g]; sh.res_ci[2 * oi + 1] = (int)hi[g]; sh.res_hap[oi] = hap[g];
   }
-  if (lane == 0) a.flank_done[l] = FL_DONE;
+  if (lane == 0) a.flank_done[l] = FL_DONE | mark;
   return true;
 }
 
-template <int MAXR, int SEG, bool PRESEL = false, bool FLANK = false>
-__global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK> a) {  // exactly one wave per locus: the lane-0 sections and the ballots rely on it
-  __shared__ GtShared<MAXR, SEG, FLANK> sh;
+// The tag route inside the genotype kernel.  false: the tags do not split the reads and the locus continues with the length genotype (or,
+// SNV forms, with snv_route).  true: the locus is settled by flank_tail.
+template <class SH>
+__device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_t l, uint64_t r0, int n, int nu, int lane, bool fits, uint32_t refn, uint64_t refo) {
+  int cnt[2];
+  if (!flank_assign(sh, a.hp_tag, r0, n, lane, cnt)) return false;
+  return flank_tail<TagMembers>(sh, a, l, n, nu, lane, fits, refn, refo, cnt, cnt, (uint8_t)0);
+}
+
+// ---- the SNV branch of genotype_flank::genotype on the device (get_trs_with_clustering, genotype_flank.rs:78-138, with get_analysis_region,
+// call_snvs, the profiles, the candidate genotypes and their log-likelihoods, :171-290), tried where the tags do not split the reads.
+// Everything in it is integer work or f64 additions in the host's order (flank_split of locus.hip, which the oracle pins), except two
+// calls per read and candidate: exp and log, which are the device library's here and the platform libm's there.  The candidate search
+// is therefore decided on the device only when it cannot depend on them:
+//   every term is (mx + log(exp(t1 - mx) + exp(t2 - mx))) - ln2 with t1, t2, mx and the differences bit-identical on both sides (running
+//   f64 sums of the same two constants in the same order; one of the differences is exactly 0 and its exp is taken as 1.0).  The other
+//   argument d <= 0 gives exp(d) in (0, 1], the sum lies in [1, 2], its log L in [0, ln 2].  glibc documents at most 1 ulp for f64 exp
+//   and log ("Known Maximum Errors in Math Functions" of its manual, every platform's column); the device library implements the
+//   accuracy table of the OpenCL C specification (OpenCL 3.0 C, "Relative Error as ULPs", double precision: exp <= 3 ulp, log <= 3 ulp),
+//   which the ROCm device-libs' OCML documentation names as its contract.  One ulp of a result <= 1 is at most 2^-52, of one below 1
+//   2^-53.  So the two exps differ by at most 4 * 2^-52, the rounded sums by that and one ulp of [1, 2] more, the logs (slope <= 1) by
+//   as much plus their own 4 * 2^-53: |L_host - L_device| < 2^-49.  mx + L and the subtraction of ln2 round once each, values of
+//   magnitude <= |term| + 1.4 (every term is ln((e^t1 + e^t2) / 2) <= 0, so |M| is the sum of the |term|): at most 2^-51 * (|term| + 1.4)
+//   between the two sides; the running sum over the reads rounds a partial sum <= |M| once per read on either side.  Over n <= 256
+//   reads: n * 2^-49 + 2^-51 * (|M| + 1.4 n) + n * 2^-52 * |M| < 6.5e-13 * (1 + |M|) between the host's and the device's sum of one candidate.
+// A locus is decided when the maximum M is ahead of every other candidate by more than delta = 2^-30 * (1 + |M|) -- 1 400 times that
+// bound -- so that the host's search has the same single winner; otherwise it is handed to the host path (FL_UNDECIDED).  Margins
+// of generated and hostile inputs, relative to 1 + |M|, are 0 (or a few 1e-15, where equal sums round apart) or >= 8e-4 (DESIGN.md
+// section 2; tests/test_snv_split_cases.py holds its cases to <= 1e-12 or >= 1e-6).
+// false: no split (FL_NOSPLIT: neither branch splits the reads, the host need not look) and the locus continues with the length
+// genotype.  true: settled by flank_tail, or handed to the host path (sh.bail = 1).  Called by the whole wave with uniform arguments.
+template <int MAXR, class SH>
+__device__ __forceinline__ bool snv_route(SH& sh, const SnvArgs& a, int64_t l, uint64_t r0, int n, int nu, int lane, bool fits, uint32_t refn, uint64_t refo) {
+  constexpr int CAP = SNV_OFFS_PER_READ * MAXR;
+  static_assert(CAP / 64 <= 32, "one bit per owned entry in `called`");
+  auto nosplit = [&]() { if (lane == 0) a.flank_done[l] = FL_NOSPLIT | FL_SNV; return false; };
+  auto handed = [&](uint8_t why) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED | FL_SNV | why; return true; };
+  // ---- get_analysis_region (:206-226): the skip-th largest start offset, the skip-th smallest end offset, by rank
+  const int skip = (int)round((double)n * (1.0 - 0.85));
+  if (skip >= n) return nosplit();
+  for (int i = lane; i < n; i += 64) {
+    const uint64_t r = r0 + sh.s_read[i];
+    sh.v_so[i] = a.start_offset ? a.start_offset[r] : 0; sh.v_eo[i] = a.end_offset ? a.end_offset[r] : 0;
+  }
+  __syncthreads();
+  for (int i = lane; i < n; i += 64) {
+    const int32_t s = sh.v_so[i], e = sh.v_eo[i];
+    int rs = 0, re = 0;
+    for (int j = 0; j < n; ++j) { const int32_t sj = sh.v_so[j], ej = sh.v_eo[j]; rs += sj < s || (sj == s && j < i); re += ej < e || (ej == e && j < i); }
+    if (rs == n - 1 - skip) sh.v_reg[0] = s;
+    if (re == skip) sh.v_reg[1] = e;
+  }
+  __syncthreads();
+  const int32_t reg0 = sh.v_reg[0], reg1 = sh.v_reg[1];
+  // ---- call_snvs (:271-286): the in-region offsets of all reads, 64 of one read's list per round, packed in read order
+  int total = 0;
+  for (int i = 0; i < n; ++i) {
+    const uint64_t r = r0 + sh.s_read[i];
+    const uint64_t m0 = a.mismatch_off[r], m1 = a.mismatch_off[r + 1];
+    for (uint64_t base = m0; base < m1; base += 64) {
+      const uint64_t k = base + (uint64_t)lane;
+      const int32_t o = k < m1 ? a.mismatch_offsets[k] : 0;
+      const bool in = k < m1 && reg0 <= o && o <= reg1;
+      const unsigned long long bal = __ballot(in);
+      const int at = total + __popcll(bal & ((1ull << lane) - 1ull));
+      if (in && at < CAP) sh.v.offs[at] = o;
+      total += __popcll(bal);
+    }
+  }
+  __syncthreads();
+  if (total == 0) return nosplit();  // no SNV: every profile is empty, one candidate genotype
+  if (total > CAP) return handed(0);
+  // an offset is called when its occurrences are at least 20 % of the reads; lane e owns entries e, e + 64, ...: the first occurrence speaks
+  uint32_t called = 0;  // bit t: entry lane + 64 t is the first occurrence of a called offset
+  for (int t = 0; t < CAP / 64; ++t) {
+    const int e = lane + 64 * t;
+    if (e >= total) break;
+    const int32_t o = sh.v.offs[e];
+    int c = 0; bool first = true;
+    for (int j = 0; j < total; ++j) { const bool same = sh.v.offs[j] == o; c += same; first = first && !(same && j < e); }
+    if (first && (double)c / (double)n >= 0.20) called |= 1u << t;
+  }
+  int ns = 0;
+  for (int t = 0; t < CAP / 64; ++t) {
+    if (64 * t >= total) break;
+    const bool mine = (called >> t) & 1u;
+    const unsigned long long bal = __ballot(mine);
+    const int at = ns + __popcll(bal & ((1ull << lane) - 1ull));
+    if (mine && at < SNV_MAX_SNVS) sh.v_tmp[at] = sh.v.offs[lane + 64 * t];
+    ns += __popcll(bal);
+  }
+  __syncthreads();
+  if (ns == 0) return nosplit();
+  if (ns > SNV_MAX_SNVS) return handed(0);
+  if (lane < ns) {  // ascending
+    const int32_t o = sh.v_tmp[lane];
+    int r = 0;
+    for (int j = 0; j < ns; ++j) r += sh.v_tmp[j] < o;
+    sh.v_snv[r] = o;
+  }
+  __syncthreads();  // (the offsets are done with: their bytes become the profiles)
+  // ---- profiles (:250-269): SNV k of a read is None outside [start_offset, end_offset], else whether its list has the offset
+  const uint64_t all = ns == 64 ? ~0ull : (1ull << ns) - 1ull;
+  int full = 0;
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    uint64_t obs = 0, val = 0;
+    if (i < n) {
+      const uint64_t r = r0 + sh.s_read[i];
+      const int32_t* m = a.mismatch_offsets + a.mismatch_off[r];
+      const int nm = (int)(a.mismatch_off[r + 1] - a.mismatch_off[r]);
+      const int32_t s = sh.v_so[i], e = sh.v_eo[i];
+      for (int k = 0; k < ns; ++k) {
+        const int32_t o = sh.v_snv[k];
+        if (o < s || o > e) continue;
+        obs |= 1ull << k;
+        int lo = 0, hi = nm;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (m[mid] < o) lo = mid + 1; else hi = mid; }
+        if (lo < nm && m[lo] == o) val |= 1ull << k;
+      }
+      sh.v.p.obs[i] = obs; sh.v.p.val[i] = val;
+    }
+    full += __popcll(__ballot(i < n && obs == all));
+  }
+  __syncthreads();
+  // ---- candidate genotypes (:228-248): the distinct fully observed profiles in the derived order of Option<bool> -- first SNV most
+  //      significant, false before true: the bit-reversed value mask -- and their pairs a <= b, a outer
+  if ((double)full / (double)n < 0.40) return nosplit();
+  int nh = 0;
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    bool first = i < n && sh.v.p.obs[i] == all;
+    if (first) { const uint64_t v = sh.v.p.val[i]; for (int j = 0; j < i; ++j) first = first && !(sh.v.p.obs[j] == all && sh.v.p.val[j] == v); }
+    if (i < n) sh.v_tie[i] = first ? 1 : 0;
+    nh += __popcll(__ballot(first));
+  }
+  __syncthreads();
+  if (nh * (nh + 1) / 2 <= 1) return nosplit();
+  if (nh > SNV_MAX_HAPS) return handed(0);
+  for (int i = lane; i < n; i += 64) {
+    if (!sh.v_tie[i]) continue;
+    const uint64_t key = __brevll(sh.v.p.val[i]);
+    int r = 0;
+    for (int j = 0; j < n; ++j) r += sh.v_tie[j] && __brevll(sh.v.p.val[j]) < key;
+    sh.v_hap[r] = sh.v.p.val[i];
+  }
+  __syncthreads();
+  // ---- log-likelihoods (:171-204), one lane per candidate, the reads in kept order; eval() is a running sum over the SNVs ascending
+  const int nc = nh * (nh + 1) / 2;
+  for (int c = lane; c < nc; c += 64) {
+    int ha = 0, hb = 0;
+    { int p = 0; for (int x = 0; x < nh; ++x) for (int y = x; y < nh; ++y, ++p) if (p == c) { ha = x; hb = y; } }
+    const uint64_t h1 = sh.v_hap[ha], h2 = sh.v_hap[hb];
+    double ll = 0.0;
+    for (int i = 0; i < n; ++i) {
+      const uint64_t obs = sh.v.p.obs[i], val = sh.v.p.val[i];
+      double t1 = 0.0, t2 = 0.0;
+      for (int k = 0; k < ns; ++k) {
+        if (!((obs >> k) & 1ull)) continue;
+        t1 += ((val ^ h1) >> k) & 1ull ? a.ln_mis : a.ln_match;
+        t2 += ((val ^ h2) >> k) & 1ull ? a.ln_mis : a.ln_match;
+      }
+      const double mx = t1 > t2 ? t1 : t2;
+      const double d1 = t1 - mx, d2 = t2 - mx;
+      const double e1 = d1 == 0.0 ? 1.0 : exp(d1), e2 = d2 == 0.0 ? 1.0 : exp(d2);
+      ll += (mx + log(e1 + e2)) - a.ln2;
+    }
+    sh.v_ll[c] = ll;
+  }
+  __syncthreads();
+  // ---- the decision: max_by's winner is the last maximum in candidate order; every other candidate must stay below M - delta
+  double M = sh.v_ll[0]; int win = 0;
+  for (int c = 1; c < nc; ++c) if (sh.v_ll[c] >= M) { M = sh.v_ll[c]; win = c; }
+  const double delta = 0x1p-30 * (1.0 + fabs(M));
+  bool decided = true;
+  for (int c = 0; c < nc; ++c) if (c != win && sh.v_ll[c] >= M - delta) decided = false;
+  if (!decided) return handed(FL_UNDECIDED);
+  int wa = 0, wb = 0;
+  { int p = 0; for (int x = 0; x < nh; ++x) for (int y = x; y < nh; ++y, ++p) if (p == win) { wa = x; wb = y; } }
+  if (wa == wb) return nosplit();  // "homozygous"
+  const uint64_t top1 = sh.v_hap[wa], top2 = sh.v_hap[wb];
+  __syncthreads();  // (v_tie changes its meaning)
+  // ---- the assignment (:114-137): fewer agreements with the first haplotype -> group 0, more -> group 1, as many -> both groups, and the
+  //      assignment alternates from 0 (the k-th such read, k from 0, gets k % 2)
+  int ties = 0, cnt[2] = {0, 0}, hap[2] = {0, 0};
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    int d1 = 0, d2 = 0;
+    if (i < n) { const uint64_t obs = sh.v.p.obs[i], val = sh.v.p.val[i]; d1 = __popcll(obs & ~(val ^ top1)); d2 = __popcll(obs & ~(val ^ top2)); }
+    const bool tie = i < n && d1 == d2;
+    const unsigned long long tb = __ballot(tie);
+    const int k = ties + __popcll(tb & ((1ull << lane) - 1ull));
+    const int g = tie ? (k & 1) : (d1 < d2 ? 0 : 1);
+    if (i < n) { sh.cls[i] = (int8_t)g; sh.v_tie[i] = tie ? 1 : 0; }
+    const int here = n - base < 64 ? n - base : 64;
+    const int ones = __popcll(__ballot(i < n && g == 1)), m1 = __popcll(__ballot(i < n && (g == 1 || tie))), m0 = __popcll(__ballot(i < n && (g == 0 || tie)));
+    hap[1] += ones; hap[0] += here - ones; cnt[0] += m0; cnt[1] += m1;
+    ties += __popcll(tb);
+  }
+  __syncthreads();
+  if (!flank_tail<SnvMembers>(sh, a, l, n, nu, lane, fits, refn, refo, cnt, hap, (uint8_t)FL_SNV)) return nosplit();
+  // a locus that waits for the repair chain leaves its split behind: flank_finish reads it and does not recompute it
+  if (sh.bail == 2)
+    for (int i = lane; i < n; i += 64)
+      a.snv_read[r0 + i] = (uint8_t)((sh.cls[i] ? SR_ASSIGN : 0) | (SnvMembers::in(sh, i, 0) ? SR_IN0 : 0) | (SnvMembers::in(sh, i, 1) ? SR_IN1 : 0));
+  return true;
+}
+
+template <int MAXR, int SEG, bool PRESEL = false, bool FLANK = false, bool SNV = false>
+__global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK, SNV> a) {  // exactly one wave per locus: the lane-0 sections and the ballots rely on it
+  static_assert(FLANK || !SNV, "the SNV forms are FLANK forms: they share the tail of the route and its LDS");
+  __shared__ GtShared<MAXR, SEG, FLANK, SNV> sh;
   const int64_t l = blockIdx.x;
   if (l >= a.n_loci) return;
   const int lane = threadIdx.x;
@@ -509,7 +766,15 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
       // ---- FLANK: two sizes at most 10 apart (tr.rs:69-75) and tags that split the reads replace everything below; the size
       //      genotyper's own repair is not queued for such a locus
       bool by_tags = false;
-      if constexpr (FLANK) {
+      if constexpr (SNV) {
+        // ---- SNV: in the reference's order -- tags that split the reads own the locus (flank_route with both settings on; else the host
+        //      finds the split as before: the byte stays 0), and only without such tags the SNVs of the flanks are tried
+        if (n_gt == 2 && adiff_u(size[0], size[1]) <= 10) {
+          int cnt[2];
+          if (a.hp_tag && flank_assign(sh, a.hp_tag, r0, n, lane, cnt)) by_tags = a.tag_route && flank_tail<TagMembers>(sh, a, l, n, nu, lane, fits, refn, refo, cnt, cnt, (uint8_t)0);
+          else by_tags = snv_route<MAXR>(sh, a, l, r0, n, nu, lane, fits, refn, refo);
+        }
+      } else if constexpr (FLANK) {
         if (a.hp_tag && n_gt == 2 && adiff_u(size[0], size[1]) <= 10) by_tags = flank_route(sh, a, l, r0, n, nu, lane, fits, refn, refo);
       }
       auto ulen_of = [&](int q) { return sh.s_len[sh.u_rep[q]]; };
@@ -655,11 +920,25 @@ __device__ __forceinline__ bool wave_equal(const uint8_t* __restrict__ p, uint32
 // ... and of a locus the haplotype-tag route left waiting (RP_FLANK): the assignment is recomputed from the tags (deterministic from the
 // same list of kept reads), the alleles are the repaired sequences or the backbones; smaller allele first (genotype_flank.rs:33-38), the
 // assignment is the classification, its counts are num_spanning, the sizes of the genotype are the allele lengths
+// (snv: the record is the SNV branch's -- its assignment is read back from SnvArgs::snv_read, SR_ASSIGN of every kept read, instead)
 template <class SH>
-__device__ __forceinline__ void flank_finish(SH& sh, const GtFlankArgs& a, const FinishArgs& f, const RepairPend& pd, int64_t l, uint64_t r0, int n, int lane) {
+__device__ __forceinline__ void flank_finish(SH& sh, const GtFlankArgs& a, const FinishArgs& f, const RepairPend& pd, int64_t l, uint64_t r0, int n, int lane,
+                                             const uint8_t* __restrict__ snv = nullptr) {
   const RepairBufs& rp = a.rp;
   int cnt[2] = {0, 0};
-  bool fail = n == 0 || !flank_assign(sh, a.hp_tag, r0, n, lane, cnt);
+  const uint8_t mark = snv ? (uint8_t)FL_SNV : (uint8_t)0;
+  bool fail;
+  if (snv) {
+    for (int base = 0; base < n; base += 64) {
+      const int i = base + lane;
+      const int g = i < n ? snv[r0 + i] & SR_ASSIGN : 0;
+      if (i < n) sh.cls[i] = (int8_t)g;
+      const int ones = __popcll(__ballot(i < n && g == 1));
+      cnt[1] += ones; cnt[0] += (n - base < 64 ? n - base : 64) - ones;
+    }
+    __syncthreads();
+    fail = n == 0;
+  } else fail = n == 0 || !flank_assign(sh, a.hp_tag, r0, n, lane, cnt);
   const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
   auto seg_of = [&](int i) { return Seg{sh.r_off[sh.s_read[i]] + sh.s_start[i], sh.s_len[i]}; };
   for (int g = 0; g < 2 && !fail; ++g) fail = !repaired_allele(pd, g, f, rp, a.reads, seg_of, ap[g], aln[g]);
@@ -670,7 +949,7 @@ __device__ __forceinline__ void flank_finish(SH& sh, const GtFlankArgs& a, const
     if (!wave_equal(ap[order[0]], aln[order[0]], ref, refn) && wave_equal(ap[order[1]], aln[order[1]], ref, refn)) { order[0] = 1 - sw; order[1] = sw; flip = 1; }
     if (aln[0] > a.allele_cap[l] || aln[1] > a.allele_cap[l]) fail = true;  // the host path reports the error
   }
-  if (fail) { if (lane == 0) { a.need_host[l] = 1; a.flank_done[l] = FL_HANDED; } return; }
+  if (fail) { if (lane == 0) { a.need_host[l] = 1; a.flank_done[l] = FL_HANDED | mark; } return; }
   for (int oi = 0; oi < 2; ++oi) {
     const int g = order[oi];
     uint8_t* dst = a.allele_blob + a.allele_off[2 * l + oi];
@@ -688,11 +967,11 @@ __device__ __forceinline__ void flank_finish(SH& sh, const GtFlankArgs& a, const
   }
   if (lane == 0) {
     a.n_alleles[l] = 2; a.n_spanning_reads[l] = (uint32_t)n; a.flipped[l] = (uint8_t)flip; a.skip_b[l] = 0; if (a.finish_clears_need) a.need_host[l] = 0;
-    a.flank_done[l] = FL_DONE | FL_REPAIRED;
+    a.flank_done[l] = FL_DONE | FL_REPAIRED | mark;
   }
 }
-template <int MAXR, bool PRESEL = false, bool FLANK = false>
-__global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgsOf<FLANK> a, const FinishArgs f) {
+template <int MAXR, bool PRESEL = false, bool FLANK = false, bool SNV = false>
+__global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgsOf<FLANK, SNV> a, const FinishArgs f) {
   __shared__ FinShared<MAXR> sh;
   const RepairBufs& rp = a.rp;
   if (blockIdx.x >= rp.counts[RC_LOCI]) return;
@@ -706,6 +985,9 @@ __global__ void __launch_bounds__(64) repair_finish_kernel(const GtArgsOf<FLANK>
   const int n = sh.n;
   const RepairPend pd = rp.pend[l];
   if constexpr (FLANK) {
+    if constexpr (SNV) {
+      if (pd.n_pick & RP_SNV) { flank_finish(sh, a, f, pd, l, r0, n, lane, a.snv_read); return; }
+    }
     if (pd.n_pick & RP_FLANK) { flank_finish(sh, a, f, pd, l, r0, n, lane); return; }
   }
   const int ploidy = a.ploidy[l] == 1 ? 1 : 2;
