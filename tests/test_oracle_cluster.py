@@ -1,10 +1,11 @@
 """CPU checks of the oracle's cluster genotyper pieces.
 
 The Ward linkage lives in kodama 0.3.0, an un-vendored crates.io dependency of the reference (Cargo.lock:839-842), and the
-reference has no test of genotype_cluster::cluster(): PARITY UNPINNED.  What can be checked here is that the oracle's
-restatement of the NN-chain algorithm builds the same dendrogram as an independent implementation
-(scipy.cluster.hierarchy.linkage(method="ward")) on tie-free inputs, and that cluster() / genotype() behave as
-genotype_cluster.rs:58-227 reads.
+reference has no test of genotype_cluster::cluster(): PARITY UNPINNED.  Checked here: the oracle's restatement of the NN-chain
+algorithm builds the same dendrogram as an independent implementation (scipy.cluster.hierarchy.linkage(method="ward")) on
+tie-free inputs, and cluster() / genotype() behave as genotype_cluster.rs:58-227 reads on a few hand-made inputs.  This is one of
+two anchors: on tie-heavy matrices, where the unpinned choices decide, tests/test_cluster_independent.py holds the oracle to
+tests/pyward.py.
 """
 import numpy as np
 import pytest
