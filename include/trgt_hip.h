@@ -95,11 +95,15 @@ int trgt_hip_set_cluster_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
  * beyond the repair's longest or an allele beyond allele_cap takes the host path.  Results are the same either way.  On a context that
  * is also set with trgt_hip_set_flank_device, a haplotagged batch's deep loci run the tag branch of genotype_flank inside the same
  * workgroup (below); without that setting a deep locus whose tags split its reads is genotyped on the device and then again on the host.
+ * The two settings combine in the same way with trgt_hip_set_snv_split_device: on a context that has both, the deep loci of a batch
+ * with mismatch offsets run the SNV branch of genotype_flank inside the same workgroup as well (the SNV forms of the deep size kernels,
+ * further below); with this setting alone the host's flank step looks at every deep close-allele locus and redoes the ones it splits.
  * trgt_hip_size_max_reads_limit: the compiled ceiling (2048), no GPU needed.  max_reads outside [256, limit]: TRGT_ERR_INVALID, the
  * setting stays.  trgt_hip_size_deep_stats: of the context's last trgt_locus_batch -- out[0] deep size loci genotyped on the device,
  * out[1] those among them that went through the repair, out[2] deep size loci inside the setting that were handed to the host path
  * (a deep locus the tag branch settled counts in out[0], in out[1] if a tag group was repaired; one it handed back in out[2]),
- * out[3] reserved (0).  The contexts of a pool are set and asked one by one through trgt_hip_pool_context. */
+ * out[3] those of out[0] that the SNV branch settled on the device (0 unless trgt_hip_set_snv_split_device is set too and the batch
+ * carries mismatch offsets; such a locus counts in out[1] if a group was repaired, one the branch handed back in out[2]).  The contexts of a pool are set and asked one by one through trgt_hip_pool_context. */
 int32_t trgt_hip_size_max_reads_limit(void);
 int trgt_hip_set_size_max_reads(trgt_hip_ctx* ctx, int32_t max_reads);
 int trgt_hip_size_deep_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
@@ -109,7 +113,8 @@ int trgt_hip_size_deep_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
  * calls whose batch carries hp_tag run the tag branch inside the device genotyper: assignment by tag, acceptance (70 % tagged, both
  * haplotypes), simple_consensus of either group, the call's consensus repair for a group without a majority sequence, smaller allele
  * first.  What stays on the host: the SNV-clustering branch (get_trs_with_clustering, :78-138), tried for the loci whose tags do not
- * split the reads exactly as before; Genotyper::Cluster loci; loci of more than 256 reads unless the context is also set with
+ * split the reads exactly as before unless the context is also set with trgt_hip_set_snv_split_device (below: with both settings
+ * both branches run on the device, tags first, for one-wave and deep size loci alike); Genotyper::Cluster loci; loci of more than 256 reads unless the context is also set with
  * trgt_hip_set_size_max_reads (then: loci beyond that setting or the 2048-read ceiling; inside it the deep size kernels of
  * locus_gt_deep.hpp run the same branch, one workgroup per locus); contexts created under TRGT_HOST_GENOTYPER; and a locus on this route that finds no room in the repair chain, has a segment beyond its longest (every such locus under
  * TRGT_HOST_REPAIR) or an allele beyond allele_cap.  Results are the same either way.  trgt_hip_flank_stats: of the context's last
@@ -144,17 +149,21 @@ int trgt_hip_flank_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
  * on != 0, calls whose batch carries mismatch_offsets and mismatch_off run it inside the one-wave size genotyper (the SNV forms of
  * locus_gt.hpp) for Genotyper::Size loci of ploidy 2 and at most 256 candidate reads, in the reference's order: tags that split the
  * reads own the locus (the device's tag branch with trgt_hip_set_flank_device also on, else the host as before), the SNVs are tried
- * only without them.  Everything but exp and log is restated bit for bit; the candidate search is decided on the device only when its
+ * only without them.  The setting combines with trgt_hip_set_size_max_reads: on a context that has both, the size loci of 257 reads up
+ * to that setting run the same branch in the SNV forms of the deep size kernels (locus_gt_deep.hpp, one workgroup per locus; the
+ * per-read masks and the staged offsets live in HBM), in the same order, and trgt_hip_set_flank_device again selects whose the tag
+ * branch is.  Everything but exp and log is restated bit for bit; the candidate search is decided on the device only when its
  * winner is ahead of every other candidate by more than 2^-30 * (1 + |log-likelihood|), far beyond what two libms can differ by.
- * What stays on the host, with the same results: Genotyper::Cluster loci; size loci of more than 256 reads, the deep size list of
- * trgt_hip_set_size_max_reads included; contexts created under TRGT_HOST_GENOTYPER; the tag branch where trgt_hip_set_flank_device is
+ * What stays on the host, with the same results: Genotyper::Cluster loci; size loci of more than 256 reads on a context without
+ * trgt_hip_set_size_max_reads, and beyond that setting or the 2048-read ceiling on one that has it; contexts created under TRGT_HOST_GENOTYPER; the tag branch where trgt_hip_set_flank_device is
  * off; searches not decided beyond the margin; and a locus on this route that finds no room in the repair chain, has a segment beyond
  * its longest (TRGT_REPAIR_MAX_SEG; every such locus under TRGT_HOST_REPAIR), an allele beyond allele_cap, more than 64 called SNVs,
- * more than 16 distinct fully observed profiles, or more than 8 in-region mismatch offsets per candidate read.
+ * more than 16 distinct fully observed profiles, or more than 8 in-region mismatch offsets per candidate read slot of the kernel form
+ * (512, 2048, and 16384 occurrences per locus for the 64-read, 256-read and deep forms).
  * trgt_hip_snv_split_stats: of the context's last trgt_locus_batch -- out[0] loci whose genotype the device replaced through the SNV
  * branch, out[1] those among them with a repaired group, out[2] loci on the route handed back for room or limits, out[3] loci handed
- * back because the search was not decided beyond the margin (not in out[2]); all zero with the setting off or a batch without
- * mismatch offsets.  A locus this route settles is not counted by trgt_hip_flank_stats, one it hands back is in no other count;
+ * back because the search was not decided beyond the margin (not in out[2]); deep loci count by the same rules where both settings
+ * are on, and never otherwise; all zero with the setting off or a batch without mismatch offsets.  A locus this route settles is not counted by trgt_hip_flank_stats, one it hands back is in no other count;
  * trgt_hip_flank_stats out[2] keeps counting the loci the host's own flank step sends. */
 int trgt_hip_set_snv_split_device(trgt_hip_ctx* ctx, int on);
 int trgt_hip_snv_split_stats(const trgt_hip_ctx* ctx, int64_t out[4]);

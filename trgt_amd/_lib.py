@@ -198,7 +198,8 @@ class Context:
 
     def size_deep_stats(self):
         """trgt_hip_size_deep_stats of the context's last trgt_locus_batch: (deep size loci genotyped on the device, those among them that
-        went through the consensus repair, deep size loci inside the setting handed to the host path, 0)."""
+        went through the consensus repair, deep size loci inside the setting handed to the host path, those of the first that the SNV
+        branch of genotype_flank settled on the device: 0 unless set_snv_split_device is on too and the batch carries mismatch offsets)."""
         out = (C.c_int64 * 4)()
         self.check(lib().trgt_hip_size_deep_stats(self.handle, out))
         return tuple(int(v) for v in out)
@@ -220,12 +221,15 @@ class Context:
     def set_snv_split_device(self, on=True):
         """trgt_hip_set_snv_split_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) runs inside the one-wave size
         genotyper for batches that carry mismatch offsets; a locus whose candidate search is not decided beyond the margin, or that is
-        beyond the route's limits, goes to the host path as before.  Independent of set_flank_device.  Every later call on this context uses it."""
+        beyond the route's limits, goes to the host path as before.  Independent of set_flank_device.  Combines with set_size_max_reads: a
+        context that has both runs the branch for the size loci of 257 reads up to that setting too (the SNV forms of the deep size kernels);
+        with this setting alone such loci are the host's from the start.  Every later call on this context uses it."""
         self.check(lib().trgt_hip_set_snv_split_device(self.handle, int(bool(on))))
 
     def snv_split_stats(self):
         """trgt_hip_snv_split_stats of the context's last trgt_locus_batch: (loci whose genotype the device replaced through the SNV
-        branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided)."""
+        branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided).  Deep size loci
+        count by the same rules on a context that has set_size_max_reads as well, and never otherwise."""
         out = (C.c_int64 * 4)()
         self.check(lib().trgt_hip_snv_split_stats(self.handle, out))
         return tuple(int(v) for v in out)

@@ -278,6 +278,7 @@ enum Slot {
   S_GSD_LIST,  // the deep list of the size genotyper (locus_gt_deep.hpp)
   S_GT_HP,     // the reads' haplotype tags for the FLANK forms of the device genotyper (locus_gt.hpp)
   S_SNV_SO, S_SNV_EO, S_SNV_MM, S_SNV_MMOFF, S_SNV_READ,  // the SNV forms' inputs (start / end offsets, mismatch offsets and their table) and per-read byte
+  S_SNV_DEEP,  // the workspace of the deep size list's SNV forms (locus_gt_deep.hpp): per-read masks and staged offsets, one slab
   S_CLF_COUNTS,  // the counters of the tag branch behind the one-wave cluster chain (locus_cluster_flank.hpp)
   S_CLF_PEND,    // ... and its records of the loci that wait for the third consensus round
   S_COUNT

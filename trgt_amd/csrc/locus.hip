@@ -696,6 +696,7 @@ struct LocusCall {
          *toff = nullptr, *packed = nullptr;
     const double* rq = nullptr; const int16_t* hp = nullptr;
     const int32_t *so = nullptr, *eo = nullptr, *mm = nullptr; const uint64_t* mm_off = nullptr; void* snv_read = nullptr;  // the SNV forms' inputs, their per-read byte
+    void *snv_prof = nullptr, *snv_stage = nullptr;  // the deep size list's SNV forms: masks per read slot, staged offsets
   };
   struct GtHost { void *need = nullptr, *nal = nullptr, *alen = nullptr, *ci = nullptr, *nsp = nullptr, *cls = nullptr, *rank = nullptr, *nspan = nullptr, *toff = nullptr, *packed = nullptr; };
   struct ClPlan { std::vector<uint32_t> list; std::vector<uint64_t> moff; uint64_t pairs = 0, reads = 0; uint32_t max_nr = 0; const uint32_t* d_list = nullptr; const uint64_t* d_moff = nullptr; };
@@ -785,6 +786,15 @@ struct LocusCall {
     return sa;
   }
   gtd::DeepFlankArgs deep_flank_args() const { return gtd::DeepFlankArgs{ds, g.hp, (uint8_t*)slab.d(o_fdone)}; }  // the deep size list's FLANK forms (ds.c.g = ga is the caller's)
+  // ... and its SNV forms (snv_dev with a deep size list): what snv_args() adds, and the route's workspace
+  gtd::DeepSnvArgs deep_snv_args() const {
+    gtd::DeepSnvArgs da; static_cast<gtd::DeepFlankArgs&>(da) = deep_flank_args();
+    const gt::SnvArgs sa = snv_args();
+    da.start_offset = sa.start_offset; da.end_offset = sa.end_offset; da.mismatch_offsets = sa.mismatch_offsets; da.mismatch_off = sa.mismatch_off; da.snv_read = sa.snv_read;
+    da.ln_match = sa.ln_match; da.ln_mis = sa.ln_mis; da.ln2 = sa.ln2; da.tag_route = sa.tag_route;
+    da.prof = (uint64_t*)g.snv_prof; da.stage = (int32_t*)g.snv_stage; da.stage_cap = in->mismatch_off[nr];
+    return da;
+  }
   uint64_t& cell(int w) { return ((uint64_t*)h_cells)[w]; }
   void tl(const char* name) const { if (tl_on) fprintf(stderr, "[tl] %-28s %7.2f ms  ctx=%p\n", name, (double)(now_ns() - t0) / 1e6, (void*)c); }
 
@@ -919,7 +929,8 @@ int LocusCall::upload_tables() {
   // forms of locus_gt.hpp, which read the tags and leave one byte per locus
   flank_dev = dev_gt && c->flank_device && in->hp_tag != nullptr;
   // ... and its SNV branch likewise on a context that opted in to that (trgt_hip_set_snv_split_device), for a batch with mismatch offsets:
-  // the SNV forms, which take the place of the FLANK forms of the one-wave kernels (the deep size list keeps its own)
+  // the SNV forms, which take the place of the FLANK forms of the one-wave kernels and -- where the context also has a deep size list
+  // (trgt_hip_set_size_max_reads) -- of the two deep size kernels; flank_dev then only says whose the tag branch inside them is
   snv_dev = dev_gt && c->snv_split_device && in->mismatch_offsets != nullptr && in->mismatch_off != nullptr;
   // ... and, a setting of its own (trgt_hip_set_flank_cluster_device), behind the one-wave cluster chain: locus_cluster_flank.hpp
   flank_cl_dev = dev_gt && c->flank_cluster_device && in->hp_tag != nullptr;
@@ -1011,6 +1022,11 @@ int LocusCall::plan_device_lists() {
       if (n > (uint64_t)gt::GT_MAX_READS && n <= (uint64_t)c->size_max_reads) gsd_list.push_back((uint32_t)l);
     }
     if (!gsd_list.empty() && (rc = dev_in(c, S_GSD_LIST, gsd_list.data(), gsd_list.size(), &d_gsd_list, &ub))) return rc;
+    if (!gsd_list.empty() && snv_dev) {  // the SNV forms' workspace: two masks per read slot, then room for every mismatch offset of the batch
+      void* ws = nullptr;
+      if ((rc = dev_get(c, S_SNV_DEEP, 16 * (size_t)nr + 4 * (size_t)in->mismatch_off[nr] + 16, &ws))) return rc;
+      g.snv_prof = ws; g.snv_stage = (uint8_t*)ws + 16 * (size_t)nr;
+    }
   }
   return TRGT_OK;
 }
@@ -1215,7 +1231,8 @@ int LocusCall::size_genotyper() {
     //      of the purity batch, then the workgroup-wide genotyper; its loci without majority support join the repair chain below
     ds.c.g = ga;
     if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
-    if (flank_dev) hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<true>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_flank_args());
+    if (snv_dev) hipLaunchKernelGGL((gtd::deep_size_genotype_kernel<true, true>), dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_snv_args());
+    else if (flank_dev) hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<true>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_flank_args());
     else hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<false>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
   }
   TRGT_HIP_TRY(c, hipGetLastError());
@@ -1299,7 +1316,8 @@ int LocusCall::repair_chain() {
   else k_repair_finish.launch(!small_gt, presel, fgrid, c->stream, ga, fa);
   if (!gsd_list.empty()) {
     ds.c.g = ga;
-    if (flank_dev) hipLaunchKernelGGL(gtd::deep_size_finish_kernel<true>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_flank_args(), fa);
+    if (snv_dev) hipLaunchKernelGGL((gtd::deep_size_finish_kernel<true, true>), dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_snv_args(), fa);
+    else if (flank_dev) hipLaunchKernelGGL(gtd::deep_size_finish_kernel<true>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_flank_args(), fa);
     else hipLaunchKernelGGL(gtd::deep_size_finish_kernel<false>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds, fa);
   }
   TRGT_HIP_TRY(c, hipGetLastError());
@@ -1526,11 +1544,14 @@ int LocusCall::wait_stage_a() {
         }
         c->flank_stats[2] += sent.load();
       }
-      if (snv_dev) {  // trgt_hip_snv_split_stats: the bytes the SNV branch of the one-wave kernels left
+      if (snv_dev) {  // trgt_hip_snv_split_stats: the bytes the SNV branch of the one-wave kernels and of the deep size list's SNV forms left
         for (int64_t l = 0; l < nl; ++l) {
           const uint8_t b = fdone[l];
           if (is_cluster(l) || !(b & gt::FL_SNV)) continue;
-          if ((b & gt::FL_DONE) && !need[l]) { c->snv_split_stats[0] += 1; if (b & gt::FL_REPAIRED) c->snv_split_stats[1] += 1; }
+          if ((b & gt::FL_DONE) && !need[l]) {
+            c->snv_split_stats[0] += 1; if (b & gt::FL_REPAIRED) c->snv_split_stats[1] += 1;
+            if (in->locus_read_begin[l + 1] - in->locus_read_begin[l] > (uint64_t)gt::GT_MAX_READS) c->size_deep_stats[3] += 1;  // trgt_hip_size_deep_stats: the deep size list's
+          }
           else if (b & gt::FL_UNDECIDED) c->snv_split_stats[3] += 1;
           else if (b & gt::FL_HANDED) c->snv_split_stats[2] += 1;
         }

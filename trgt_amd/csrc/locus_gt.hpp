@@ -439,6 +439,30 @@ __device__ __forceinline__ bool flank_route(SH& sh, const GtFlankArgs& a, int64_
 // section 2; tests/test_snv_split_cases.py holds its cases to <= 1e-12 or >= 1e-6).
 // false: no split (FL_NOSPLIT: neither branch splits the reads, the host need not look) and the locus continues with the length
 // genotype.  true: settled by flank_tail, or handed to the host path (sh.bail = 1).  Called by the whole wave with uniform arguments.
+// The log-likelihood of one candidate genotype (h1, h2) over the kept reads in kept order (:171-204), by one thread: eval() of a read
+// against either haplotype is a running sum over the ns SNVs ascending, the candidate's a running sum over the reads.  The expression
+// order is flank_split's; prof(i, obs, val) loads the two masks of kept read i.  One function for the one-wave route below and the
+// workgroup's (deep_snv_route of locus_gt_deep.hpp); a: the route's arguments with the three host-computed logarithms.
+template <class A, class P>
+__device__ __forceinline__ double snv_candidate_ll(const A& a, int n, int ns, uint64_t h1, uint64_t h2, P prof) {
+  double ll = 0.0;
+  for (int i = 0; i < n; ++i) {
+    uint64_t obs, val;
+    prof(i, obs, val);
+    double t1 = 0.0, t2 = 0.0;
+    for (int k = 0; k < ns; ++k) {
+      if (!((obs >> k) & 1ull)) continue;
+      t1 += ((val ^ h1) >> k) & 1ull ? a.ln_mis : a.ln_match;
+      t2 += ((val ^ h2) >> k) & 1ull ? a.ln_mis : a.ln_match;
+    }
+    const double mx = t1 > t2 ? t1 : t2;
+    const double d1 = t1 - mx, d2 = t2 - mx;
+    const double e1 = d1 == 0.0 ? 1.0 : exp(d1), e2 = d2 == 0.0 ? 1.0 : exp(d2);
+    ll += (mx + log(e1 + e2)) - a.ln2;
+  }
+  return ll;
+}
+
 template <int MAXR, class SH>
 __device__ __forceinline__ bool snv_route(SH& sh, const SnvArgs& a, int64_t l, uint64_t r0, int n, int nu, int lane, bool fits, uint32_t refn, uint64_t refo) {
   constexpr int CAP = SNV_OFFS_PER_READ * MAXR;
@@ -560,22 +584,7 @@ __device__ __forceinline__ bool snv_route(SH& sh, const SnvArgs& a, int64_t l, u
   for (int c = lane; c < nc; c += 64) {
     int ha = 0, hb = 0;
     { int p = 0; for (int x = 0; x < nh; ++x) for (int y = x; y < nh; ++y, ++p) if (p == c) { ha = x; hb = y; } }
-    const uint64_t h1 = sh.v_hap[ha], h2 = sh.v_hap[hb];
-    double ll = 0.0;
-    for (int i = 0; i < n; ++i) {
-      const uint64_t obs = sh.v.p.obs[i], val = sh.v.p.val[i];
-      double t1 = 0.0, t2 = 0.0;
-      for (int k = 0; k < ns; ++k) {
-        if (!((obs >> k) & 1ull)) continue;
-        t1 += ((val ^ h1) >> k) & 1ull ? a.ln_mis : a.ln_match;
-        t2 += ((val ^ h2) >> k) & 1ull ? a.ln_mis : a.ln_match;
-      }
-      const double mx = t1 > t2 ? t1 : t2;
-      const double d1 = t1 - mx, d2 = t2 - mx;
-      const double e1 = d1 == 0.0 ? 1.0 : exp(d1), e2 = d2 == 0.0 ? 1.0 : exp(d2);
-      ll += (mx + log(e1 + e2)) - a.ln2;
-    }
-    sh.v_ll[c] = ll;
+    sh.v_ll[c] = snv_candidate_ll(a, n, ns, sh.v_hap[ha], sh.v_hap[hb], [&](int i, uint64_t& obs, uint64_t& val) { obs = sh.v.p.obs[i]; val = sh.v.p.val[i]; });
   }
   __syncthreads();
   // ---- the decision: max_by's winner is the last maximum in candidate order; every other candidate must stay below M - delta

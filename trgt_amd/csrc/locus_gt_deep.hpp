@@ -18,7 +18,9 @@
 //
 // The FLANK forms of both kernels (contexts that also opted in to trgt_hip_set_flank_device) run the haplotype-tag branch of
 // genotype_flank::genotype for a deep locus whose two sizes are at most 10 apart: flank_route / flank_finish of locus_gt.hpp restated for
-// the workgroup, see deep_flank_route.
+// the workgroup, see deep_flank_route.  The SNV forms (contexts that opted in to trgt_hip_set_snv_split_device as well, batches that carry
+// mismatch offsets) add the other branch, the split by heterozygous SNVs of the flanks (genotype_flank.rs:78-138, 171-290): snv_route of
+// locus_gt.hpp restated for the workgroup, see deep_snv_route.
 #pragma once
 #include <cstddef>
 #include "locus_cluster_deep.hpp"
@@ -39,7 +41,21 @@ struct DeepFlankArgs {
   const int16_t* hp_tag;  // per read of the batch: the HP tag (-1 = None)
   uint8_t* flank_done;    // [n_loci] gt::FL_*
 };
-template <bool FLANK> using DeepArgsOf = std::conditional_t<FLANK, DeepFlankArgs, DeepArgs>;
+// The arguments of the SNV forms: what gt::SnvArgs adds to gt::GtFlankArgs, and the route's workspace in HBM.  The per-read masks (32 KB at
+// the ceiling) and the staged in-region offsets (64 KB at the cap) do not fit beside the 60 KB of DeepSize, of which only tmp and the part
+// of the tag route's overlay behind start are dead when the route runs; so both live in global memory, per read slot of the batch like
+// snv_read, and the LDS of the SNV forms is that of the FLANK forms.
+struct DeepSnvArgs : DeepFlankArgs {
+  const int32_t *start_offset, *end_offset;  // per read of the batch (NULL = 0 for every read, as in flank_split)
+  const int32_t* mismatch_offsets; const uint64_t* mismatch_off;  // per read r: its ascending offsets in [mismatch_off[r], mismatch_off[r + 1])
+  uint8_t* snv_read;      // per read slot of the batch, by position in the kept list: gt::SR_* of a locus the route split
+  double ln_match, ln_mis, ln2;  // ln 0.9, ln(1.0 - 0.9), ln 2 as the host's libm rounds them
+  int32_t tag_route;      // 1: tags that split the reads are deep_flank_route's (trgt_hip_set_flank_device is on as well); 0: such a locus is the host's
+  uint64_t* prof;         // [2 x read slots of the batch] kept read i of a locus: its observed mask at 2 (r0 + i), its value mask behind it
+  int32_t* stage;         // [stage_cap = mismatch_off[reads of the batch]] the in-region offsets of a locus' kept reads, packed from mismatch_off[r0] on (a subset of its lists)
+  uint64_t stage_cap;
+};
+template <bool FLANK, bool SNV = false> using DeepArgsOf = std::conditional_t<SNV, DeepSnvArgs, std::conditional_t<FLANK, DeepFlankArgs, DeepArgs>>;
 __device__ __forceinline__ const DeepArgs& deep_of(const DeepArgs& a) { return a; }
 __device__ __forceinline__ const DeepArgs& deep_of(const DeepFlankArgs& a) { return a.d; }
 
@@ -83,13 +99,16 @@ __device__ __forceinline__ int cmp_seg_thread(const uint8_t* __restrict__ a, uin
 // workgroup.  ap / aln / civ / gsz are indexed by allele as genotyped; n_al: alleles the reads are classified against.  The tie-breaker
 // starts at 1 and flips at every tie, so the k-th tied read (k from 0) gets k & 1: a prefix count over the kept reads.  false: an allele
 // exceeds allele_cap (the host path reports the error), nothing was written.
-// TAGS (the haplotype-tag route, genotype_flank.rs:43-76): the classification is the assignment by tag instead -- tag 1 -> group 0, tag 2
+// BY_TAGS (the haplotype-tag route, genotype_flank.rs:43-76): the classification is the assignment by tag instead -- tag 1 -> group 0, tag 2
 // -> group 1, the k-th other read of the kept list (k from 0) -> group k & 1, the same prefix count -- and the alleles arrive smaller one
 // first: sw = 1 says that allele 0 is tag group 1's.
-template <bool TAGS = false>
+// BY_SNV (the SNV route, genotype_flank.rs:114-137): likewise, with the assignment the route left in sr (gt::SR_ASSIGN per kept read).
+enum { BY_LEN = 0, BY_TAGS = 1, BY_SNV = 2 };
+template <int HOW = BY_LEN>
 __device__ __forceinline__ bool deep_size_write(const DeepArgs& a, int64_t l, uint64_t r0, int n, int n_gt, int n_al, const uint8_t* const ap[2],
                                                 const uint32_t aln[2], const int32_t civ[4], const uint32_t gsz[2], Red& red,
-                                                const int16_t* __restrict__ hp = nullptr, int sw = 0) {
+                                                const int16_t* __restrict__ hp = nullptr, int sw = 0, const uint8_t* __restrict__ sr = nullptr) {
+  constexpr bool TAGS = HOW == BY_TAGS;
   const gt::GtArgs& g = a.c.g;
   const int tid = threadIdx.x;
   const uint8_t* ref = g.tr_blob + g.tr_off[l]; const uint32_t refn = g.tr_len[l];
@@ -104,13 +123,15 @@ __device__ __forceinline__ bool deep_size_write(const DeepArgs& a, int64_t l, ui
     uint32_t d1 = 0, d2 = 0;
     int tag = 0;
     if constexpr (TAGS) { if (valid) tag = (int)hp[r0 + a.sel_read[r0 + i]]; }
+    else if constexpr (HOW == BY_SNV) { if (valid) tag = (int)(sr[r0 + i] & gt::SR_ASSIGN); }
     else if (valid && n_al == 2) { const uint32_t ln = a.sel_len[r0 + i]; d1 = adiff_u(ln, aln[0]); d2 = adiff_u(ln, aln[1]); }
-    const bool tie = TAGS ? valid && tag != 1 && tag != 2 : valid && n_al == 2 && d1 == d2;
+    const bool tie = TAGS ? valid && tag != 1 && tag != 2 : HOW == BY_SNV ? false : valid && n_al == 2 && d1 == d2;
     uint32_t total;
     const uint32_t pos = ties + cld::block_rank(tie, total, red);
     if (valid) {
       int cc;
       if constexpr (TAGS) cc = (tie ? (int)(pos & 1u) : tag - 1) ^ sw;
+      else if constexpr (HOW == BY_SNV) cc = tag ^ sw;
       else cc = n_al == 2 ? (d1 < d2 ? 0 : (d1 > d2 ? 1 : (int)(pos & 1u))) : 0;
       h1 += (uint32_t)cc;
       const uint32_t rd = a.sel_read[r0 + i];
@@ -206,32 +227,57 @@ __device__ __forceinline__ bool deep_flank_assign(uint8_t* grp, const DeepArgs& 
   return cnt[0] > 0 && cnt[1] > 0 && (double)(n - (int)untagged) / (double)n >= 0.7;
 }
 
-// The route inside the genotype kernel, behind the sequence histogram (ord, tmp, u_rep, u_cnt, nu final; fl.start filled).  false: the
-// tags do not split the reads and the locus continues with the length genotype.  true: the locus is settled here -- simple_consensus
-// (:147-170) of either group; without a group below 50 % the genotype is written out, else the groups join the call's repair chain
-// (need_host = 2, the FLANK finish kernel completes the locus) or the locus is handed to the host path (need_host = 1, FL_HANDED).
-__device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankArgs& fa, int64_t l, uint64_t r0, int n, int nu) {
+// Who belongs to group t of a split, from the byte of a kept read in DeepFlank::grp.  By tags: the byte is the group.  By SNVs (:114-137):
+// bit 0 is the assignment, bit 1 says that the read agrees equally with both haplotypes and is a member of both groups.
+struct DeepTagMembers { static constexpr bool BOTH = false; static __device__ __forceinline__ bool in(uint32_t b, int t) { return b == (uint32_t)t; } };
+struct DeepSnvMembers { static constexpr bool BOTH = true; static __device__ __forceinline__ bool in(uint32_t b, int t) { return (b & 1u) == (uint32_t)t || (b & 2u); } };
+
+// What follows an accepted split (genotype_flank.rs:20-41), behind the sequence histogram (ord, tmp, u_rep, u_cnt, nu final; fl.start
+// filled) and the assignment (fl.grp; cnt: the members of either group, MEM says who): simple_consensus (:147-170) of either group;
+// without a group below 50 % the genotype is written out, else the groups join the call's repair chain (need_host = 2, the FLANK / SNV
+// finish kernel completes the locus) or the locus is handed to the host path (need_host = 1, FL_HANDED).  sr (BOTH only): the SNV
+// route's per-read bytes, which hold the assignment.  false (BOTH only): a group is empty, there is no split, nothing was written.
+template <class MEM>
+__device__ __forceinline__ bool deep_flank_tail(DeepSize& sh, const DeepFlankArgs& fa, int64_t l, uint64_t r0, int n, int nu, const int cnt[2], const uint8_t* __restrict__ sr = nullptr) {
   const DeepArgs& a = fa.d;
   const gt::GtArgs& g = a.c.g;
   DeepFlank& fl = deep_flank_lds(sh);
   const int tid = threadIdx.x;
   constexpr int NONE = 0x7FFFFFFF;
-  int cnt[2];
-  if (!deep_flank_assign(fl.grp, a, fa.hp_tag, r0, n, cnt, sh.red)) return false;
+  constexpr uint8_t mark = MEM::BOTH ? (uint8_t)gt::FL_SNV : (uint8_t)0;
+  if constexpr (MEM::BOTH) { if (cnt[0] == 0 || cnt[1] == 0) return false; }
   // ---- multiplicities inside the groups (thread q walks the run of unique sequence q), the middle lengths of either group by rank
   for (int q = tid; q < nu; q += DW) {
     const int s = fl.start[q], m = sh.u_cnt[q];
-    int c1 = 0;
-    for (int r = s; r < s + m; ++r) c1 += fl.grp[sh.ord[r]];
-    fl.cnt[0][q] = (uint16_t)(m - c1); fl.cnt[1][q] = (uint16_t)c1;
+    if constexpr (MEM::BOTH) {
+      int c0 = 0, c1 = 0;
+      for (int r = s; r < s + m; ++r) { const uint32_t b = fl.grp[sh.ord[r]]; c0 += MEM::in(b, 0); c1 += MEM::in(b, 1); }
+      fl.cnt[0][q] = (uint16_t)c0; fl.cnt[1][q] = (uint16_t)c1;
+    } else {
+      int c1 = 0;
+      for (int r = s; r < s + m; ++r) c1 += fl.grp[sh.ord[r]];
+      fl.cnt[0][q] = (uint16_t)(m - c1); fl.cnt[1][q] = (uint16_t)c1;
+    }
   }
   for (int i = tid; i < n; i += DW) {
     const uint32_t gi = fl.grp[i], li = sh.ln[i];
-    int r = 0;
-    for (int j = 0; j < n; ++j) { const uint32_t lj = sh.ln[j]; r += fl.grp[j] == gi && (lj < li || (lj == li && j < i)); }
-    const int half = (gi ? cnt[1] : cnt[0]) / 2;
-    if (r == half) fl.med[gi][1] = li;
-    if (r == half - 1) fl.med[gi][0] = li;
+    if constexpr (MEM::BOTH) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {  // a read of both groups has a rank in either
+        if (!MEM::in(gi, t)) continue;
+        int r = 0;
+        for (int j = 0; j < n; ++j) { const uint32_t lj = sh.ln[j]; r += MEM::in(fl.grp[j], t) && (lj < li || (lj == li && j < i)); }
+        const int half = cnt[t] / 2;
+        if (r == half) fl.med[t][1] = li;
+        if (r == half - 1) fl.med[t][0] = li;
+      }
+    } else {
+      int r = 0;
+      for (int j = 0; j < n; ++j) { const uint32_t lj = sh.ln[j]; r += fl.grp[j] == gi && (lj < li || (lj == li && j < i)); }
+      const int half = (gi ? cnt[1] : cnt[0]) / 2;
+      if (r == half) fl.med[gi][1] = li;
+      if (r == half - 1) fl.med[gi][0] = li;
+    }
   }
   __syncthreads();
   int rep[2] = {0, 0}; uint32_t aln[2] = {0, 0}, lo[2] = {0, 0}, hi[2] = {0, 0}; bool lacks[2] = {false, false};
@@ -249,7 +295,7 @@ __device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankAr
       if (fl.cnt[t][q] == top) { const double d = (double)adiff_u(sh.ln[sh.u_rep[q]], median_len); if (d < bd) { bd = d; bq = q; } }
     cld::block_min_vi(bd, bq, sh.red);
     uint32_t mn = 0xFFFFFFFFu, mx = 0;
-    for (int i = tid; i < n; i += DW) if (fl.grp[i] == (uint32_t)t) { const uint32_t li = sh.ln[i]; mn = li < mn ? li : mn; mx = li > mx ? li : mx; }
+    for (int i = tid; i < n; i += DW) if (MEM::in(fl.grp[i], t)) { const uint32_t li = sh.ln[i]; mn = li < mn ? li : mn; mx = li > mx ? li : mx; }
     lo[t] = block_min_u32(mn, sh.red); hi[t] = block_max_u32(mx, sh.red);
     rep[t] = sh.u_rep[bq == NONE ? 0 : bq]; aln[t] = sh.ln[rep[t]];  // (the group is not empty: some thread has a value)
     lacks[t] = (double)top / (double)cnt[t] < 0.5;
@@ -264,7 +310,7 @@ __device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankAr
       for (int t = 0; t < 2; ++t) {
         if (!lacks[t]) continue;
         uint32_t bytes = 0, over = aln[t] > rp.max_seg;
-        for (int i = tid; i < n; i += DW) if (fl.grp[i] == (uint32_t)t) { const uint32_t li = sh.ln[i]; over += li > rp.max_seg; bytes += li > rp.max_seg ? 0u : li; }
+        for (int i = tid; i < n; i += DW) if (MEM::in(fl.grp[i], t)) { const uint32_t li = sh.ln[i]; over += li > rp.max_seg; bytes += li > rp.max_seg ? 0u : li; }
         nm[t] = (uint32_t)cnt[t]; mbytes[t] = cld::block_sum_u32(bytes, sh.red);
         if (cld::block_sum_u32(over, sh.red)) can = false;
       }
@@ -277,32 +323,230 @@ __device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankAr
       __syncthreads();
       can = sh.rsv.ok != 0;
     }
-    if (!can) { if (tid == 0) { g.need_host[l] = 1; fa.flank_done[l] = gt::FL_HANDED; } return true; }
+    if (!can) { if (tid == 0) { g.need_host[l] = 1; fa.flank_done[l] = gt::FL_HANDED | mark; } return true; }
     gt::Reserved at = sh.rsv;
     auto seg_of = [&](int i) { return gt::Seg{sh.off[i], sh.ln[i]}; };
     gt::RepairPend pd;
-    pd.n_gt = 2; pd.n_pick = 2 | gt::RP_FLANK; pd.size[0] = aln[0]; pd.size[1] = aln[1];
+    pd.n_gt = 2; pd.n_pick = 2 | gt::RP_FLANK | (MEM::BOTH ? gt::RP_SNV : 0); pd.size[0] = aln[0]; pd.size[1] = aln[1];
 #pragma unroll
     for (int t = 0; t < 2; ++t) { pd.civ[2 * t] = (int32_t)lo[t]; pd.civ[2 * t + 1] = (int32_t)hi[t]; pd.rep[t] = rep[t]; pd.grp[t] = -1; }
 #pragma unroll
     for (int t = 0; t < 2; ++t)  // job k of a group is its k-th read in kept order
-      if (lacks[t]) pd.grp[t] = (int32_t)queue_group_scan(rp.groups, rp.jobs, at, seg_of(rep[t]), nm[t], nd[t], n, [&, t](int i) { return fl.grp[i] == (uint32_t)t; }, seg_of, sh.red);
-    if (tid == 0) { rp.pend[l] = pd; g.need_host[l] = 2; }  // the locus waits for the FLANK form of deep_size_finish_kernel
+      if (lacks[t]) pd.grp[t] = (int32_t)queue_group_scan(rp.groups, rp.jobs, at, seg_of(rep[t]), nm[t], nd[t], n, [&, t](int i) { return MEM::in(fl.grp[i], t); }, seg_of, sh.red);
+    if (tid == 0) { rp.pend[l] = pd; g.need_host[l] = 2; }  // the locus waits for the FLANK / SNV form of deep_size_finish_kernel
     return true;
   }
   // ---- both groups have their sequence: smaller allele first (:33-38: alleles and intervals swap, the assignment flips), the
-  //      assignment is the classification, then reference allele first (tr.rs:95-101): deep_size_write<TAGS>
+  //      assignment is the classification, then reference allele first (tr.rs:95-101): deep_size_write<BY_TAGS / BY_SNV>
   const int sw = aln[0] > aln[1] ? 1 : 0;
   const uint8_t* ap[2] = {g.reads + sh.off[sw ? rep[1] : rep[0]], g.reads + sh.off[sw ? rep[0] : rep[1]]};
   const uint32_t al2[2] = {sw ? aln[1] : aln[0], sw ? aln[0] : aln[1]};
   const int32_t civ[4] = {(int32_t)(sw ? lo[1] : lo[0]), (int32_t)(sw ? hi[1] : hi[0]), (int32_t)(sw ? lo[0] : lo[1]), (int32_t)(sw ? hi[0] : hi[1])};
-  const bool ok = deep_size_write<true>(a, l, r0, n, 2, 2, ap, al2, civ, al2, sh.red, fa.hp_tag, sw);
-  if (tid == 0) { g.need_host[l] = ok ? 0 : 1; fa.flank_done[l] = ok ? gt::FL_DONE : gt::FL_HANDED; }  // (an allele beyond allele_cap: the host path reports the error)
+  const bool ok = deep_size_write<MEM::BOTH ? BY_SNV : BY_TAGS>(a, l, r0, n, 2, 2, ap, al2, civ, al2, sh.red, fa.hp_tag, sw, sr);
+  if (tid == 0) { g.need_host[l] = ok ? 0 : 1; fa.flank_done[l] = (uint8_t)((ok ? gt::FL_DONE : gt::FL_HANDED) | mark); }  // (an allele beyond allele_cap: the host path reports the error)
   return true;
 }
 
-template <bool FLANK = false>
-__global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgsOf<FLANK> aa) {
+// The tag route inside the genotype kernel.  false: the tags do not split the reads and the locus continues with the length genotype.
+// true: the locus is settled by deep_flank_tail.
+__device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankArgs& fa, int64_t l, uint64_t r0, int n, int nu) {
+  int cnt[2];
+  if (!deep_flank_assign(deep_flank_lds(sh).grp, fa.d, fa.hp_tag, r0, n, cnt, sh.red)) return false;
+  return deep_flank_tail<DeepTagMembers>(sh, fa, l, r0, n, nu, cnt);
+}
+
+// ---- the SNV branch of genotype_flank::genotype (get_trs_with_clustering, genotype_flank.rs:78-138, with get_analysis_region, call_snvs,
+// the profiles, the candidate genotypes and their log-likelihoods, :171-290) for a workgroup, tried where the tags do not split the reads:
+// gt::snv_route with every lane-0 loop and wave ballot as a workgroup prefix, and every selection as a (value, index) rank.  What the
+// route decides, when it decides (the margin rule) and why that is safe are snv_route's, see there; the bound on the difference between
+// the host's and the device's sum of one candidate grows with the reads of a locus, and for n <= 2 048 its three terms give
+// n * 2^-49 + 2^-51 * (|M| + 1.4 n) + n * 2^-52 * |M| < 5e-12 * (1 + |M|), of which the margin 2^-30 * (1 + |M|) is still about 180 times.
+// The small lists of the route lie over DeepFlank::cnt, which the tail fills only after them; the offsets whose rank is taken over
+// DeepSize::tmp; masks and staged offsets in DeepSnvArgs::prof / stage.
+// false: no split (FL_NOSPLIT | FL_SNV: neither branch splits the reads, the host need not look) and the locus continues with the length
+// genotype.  true: settled by deep_flank_tail, or handed to the host path (need_host = 1, FL_HANDED | FL_SNV).
+struct DeepSnv {
+  uint64_t v_hap[gt::SNV_MAX_HAPS], v_htmp[gt::SNV_MAX_HAPS];  // the distinct fully observed profiles in the derived order of Option<bool> (v_htmp: as found)
+  double v_ll[gt::SNV_MAX_HAPS * (gt::SNV_MAX_HAPS + 1) / 2];
+  int32_t v_snv[gt::SNV_MAX_SNVS], v_tmp[gt::SNV_MAX_SNVS];    // the called SNVs ascending (v_tmp: as found)
+  int32_t v_reg[2];
+};
+static_assert(sizeof(DeepSnv) <= sizeof(DeepFlank::cnt) && offsetof(DeepFlank, cnt) % alignof(DeepSnv) == 0, "the SNV route's lists lie over the tag route's multiplicities");
+constexpr int SNV_DEEP_CAP = gt::SNV_OFFS_PER_READ * MAXR;  // in-region occurrences of a locus: 8 per read slot of the kernel
+static_assert(SNV_DEEP_CAP / DW <= 64, "one bit per owned entry in `called`");
+
+__device__ __forceinline__ bool deep_snv_route(DeepSize& sh, const DeepSnvArgs& sa, int64_t l, uint64_t r0, int n, int nu) {
+  const DeepArgs& a = sa.d;
+  const gt::GtArgs& g = a.c.g;
+  DeepFlank& fl = deep_flank_lds(sh);
+  DeepSnv& sv = *reinterpret_cast<DeepSnv*>(static_cast<void*>(fl.cnt));
+  int32_t* const key = reinterpret_cast<int32_t*>(sh.tmp);
+  const int tid = threadIdx.x;
+  auto nosplit = [&]() { if (tid == 0) sa.flank_done[l] = gt::FL_NOSPLIT | gt::FL_SNV; return false; };
+  auto handed = [&](uint8_t why) { if (tid == 0) { g.need_host[l] = 1; sa.flank_done[l] = (uint8_t)(gt::FL_HANDED | gt::FL_SNV | why); } return true; };
+  auto read_of = [&](int i) { return r0 + a.sel_read[r0 + i]; };
+  // ---- get_analysis_region (:206-226): the skip-th largest start offset, the skip-th smallest end offset, by (value, index) rank
+  const int skip = (int)round((double)n * (1.0 - 0.85));
+  if (skip >= n) return nosplit();
+#pragma unroll
+  for (int side = 0; side < 2; ++side) {
+    const int32_t* __restrict__ src = side ? sa.end_offset : sa.start_offset;
+    const int want = side ? skip : n - 1 - skip;
+    for (int i = tid; i < n; i += DW) key[i] = src ? src[read_of(i)] : 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += DW) {
+      const int32_t v = key[i];
+      int r = 0;
+      for (int j = 0; j < n; ++j) { const int32_t vj = key[j]; r += vj < v || (vj == v && j < i); }
+      if (r == want) sv.v_reg[side] = v;
+    }
+    __syncthreads();
+  }
+  const int32_t reg0 = sv.v_reg[0], reg1 = sv.v_reg[1];
+  // ---- call_snvs (:271-286): the in-region offsets of all kept reads, packed in kept order (thread i counts and writes the ones of read
+  //      i; its place is a workgroup prefix carried across the rounds)
+  //      (room: the locus' own part of the table holds them all; a table that does not ascend cannot make a thread write beyond the buffer)
+  const uint64_t stage0 = sa.mismatch_off[r0];
+  const uint64_t room = stage0 < sa.stage_cap ? sa.stage_cap - stage0 : 0;
+  int32_t* const stage = sa.stage + (room ? stage0 : 0);
+  uint32_t total = 0;
+  for (int base = 0; base < n; base += DW) {
+    const int i = base + tid;
+    uint64_t m0 = 0, m1 = 0;
+    if (i < n) { const uint64_t r = read_of(i); m0 = sa.mismatch_off[r]; m1 = sa.mismatch_off[r + 1]; }
+    uint32_t c = 0;
+    for (uint64_t k = m0; k < m1; ++k) { const int32_t o = sa.mismatch_offsets[k]; c += reg0 <= o && o <= reg1; }
+    uint32_t tot;
+    uint32_t at = total + block_excl_scan_u32(c, tot, sh.red);
+    for (uint64_t k = m0; k < m1; ++k) { const int32_t o = sa.mismatch_offsets[k]; if (reg0 <= o && o <= reg1) { if (at < room) stage[at] = o; ++at; } }
+    total += tot;
+  }
+  __syncthreads();
+  if (total == 0) return nosplit();  // no SNV: every profile is empty, one candidate genotype
+  if (total > (uint32_t)SNV_DEEP_CAP || total > room) return handed(0);
+  // an offset is called when its occurrences are at least 20 % of the reads; thread e owns entries e, e + DW, ...: the first occurrence speaks
+  uint64_t called = 0;  // bit t: entry tid + DW t is the first occurrence of a called offset
+  for (int t = 0; t < SNV_DEEP_CAP / DW; ++t) {
+    const uint32_t e = (uint32_t)tid + (uint32_t)DW * (uint32_t)t;
+    if (e >= total) break;
+    const int32_t o = stage[e];
+    int c = 0; bool first = true;
+    for (uint32_t j = 0; j < total; ++j) { const bool same = stage[j] == o; c += same; first = first && !(same && j < e); }
+    if (first && (double)c / (double)n >= 0.20) called |= 1ull << t;
+  }
+  int ns = 0;
+  for (int t = 0; t < SNV_DEEP_CAP / DW; ++t) {
+    if ((uint32_t)DW * (uint32_t)t >= total) break;
+    const bool mine = (called >> t) & 1ull;
+    uint32_t tot;
+    const uint32_t at = (uint32_t)ns + cld::block_rank(mine, tot, sh.red);
+    if (mine && at < (uint32_t)gt::SNV_MAX_SNVS) sv.v_tmp[at] = stage[(uint32_t)tid + (uint32_t)DW * (uint32_t)t];
+    ns += (int)tot;
+  }
+  __syncthreads();
+  if (ns == 0) return nosplit();
+  if (ns > gt::SNV_MAX_SNVS) return handed(0);
+  if (tid < ns) {  // ascending
+    const int32_t o = sv.v_tmp[tid];
+    int r = 0;
+    for (int j = 0; j < ns; ++j) r += sv.v_tmp[j] < o;
+    sv.v_snv[r] = o;
+  }
+  __syncthreads();
+  // ---- profiles (:250-269): SNV k of a read is None outside [start_offset, end_offset], else whether its list has the offset
+  const uint64_t all = ns == 64 ? ~0ull : (1ull << ns) - 1ull;
+  uint64_t* const prof = sa.prof + 2 * r0;
+  uint32_t full = 0;
+  for (int i = tid; i < n; i += DW) {
+    const uint64_t r = read_of(i);
+    const int32_t* m = sa.mismatch_offsets + sa.mismatch_off[r];
+    const int nm = (int)(sa.mismatch_off[r + 1] - sa.mismatch_off[r]);
+    const int32_t s = sa.start_offset ? sa.start_offset[r] : 0, e = sa.end_offset ? sa.end_offset[r] : 0;
+    uint64_t obs = 0, val = 0;
+    for (int k = 0; k < ns; ++k) {
+      const int32_t o = sv.v_snv[k];
+      if (o < s || o > e) continue;
+      obs |= 1ull << k;
+      int lo = 0, hi = nm;
+      while (lo < hi) { const int mid = (lo + hi) >> 1; if (m[mid] < o) lo = mid + 1; else hi = mid; }
+      if (lo < nm && m[lo] == o) val |= 1ull << k;
+    }
+    prof[2 * i] = obs; prof[2 * i + 1] = val;
+    full += obs == all;
+  }
+  full = cld::block_sum_u32(full, sh.red);  // (its barriers also publish the masks to the workgroup)
+  // ---- candidate genotypes (:228-248): the distinct fully observed profiles in the derived order of Option<bool> -- first SNV most
+  //      significant, false before true: the bit-reversed value mask -- and their pairs a <= b, a outer
+  if ((double)full / (double)n < 0.40) return nosplit();
+  int nh = 0;
+  for (int base = 0; base < n; base += DW) {
+    const int i = base + tid;
+    bool first = i < n && prof[2 * i] == all;
+    uint64_t v = 0;
+    if (first) { v = prof[2 * i + 1]; for (int j = 0; j < i; ++j) first = first && !(prof[2 * j] == all && prof[2 * j + 1] == v); }
+    uint32_t tot;
+    const uint32_t q = (uint32_t)nh + cld::block_rank(first, tot, sh.red);
+    if (first && q < (uint32_t)gt::SNV_MAX_HAPS) sv.v_htmp[q] = v;
+    nh += (int)tot;
+  }
+  __syncthreads();
+  if (nh * (nh + 1) / 2 <= 1) return nosplit();
+  if (nh > gt::SNV_MAX_HAPS) return handed(0);
+  if (tid < nh) {
+    const uint64_t v = sv.v_htmp[tid], kv = __brevll(v);
+    int r = 0;
+    for (int j = 0; j < nh; ++j) r += __brevll(sv.v_htmp[j]) < kv;
+    sv.v_hap[r] = v;
+  }
+  __syncthreads();
+  // ---- log-likelihoods (:171-204), one thread per candidate (at most 136), the reads in kept order: gt::snv_candidate_ll
+  const int nc = nh * (nh + 1) / 2;
+  for (int c = tid; c < nc; c += DW) {
+    int ha = 0, hb = 0;
+    { int p = 0; for (int x = 0; x < nh; ++x) for (int y = x; y < nh; ++y, ++p) if (p == c) { ha = x; hb = y; } }
+    sv.v_ll[c] = gt::snv_candidate_ll(sa, n, ns, sv.v_hap[ha], sv.v_hap[hb], [&](int i, uint64_t& obs, uint64_t& val) { obs = prof[2 * i]; val = prof[2 * i + 1]; });
+  }
+  __syncthreads();
+  // ---- the decision: max_by's winner is the last maximum in candidate order; every other candidate must stay below M - delta
+  double M = sv.v_ll[0]; int win = 0;
+  for (int c = 1; c < nc; ++c) if (sv.v_ll[c] >= M) { M = sv.v_ll[c]; win = c; }
+  const double delta = 0x1p-30 * (1.0 + fabs(M));
+  bool decided = true;
+  for (int c = 0; c < nc; ++c) if (c != win && sv.v_ll[c] >= M - delta) decided = false;
+  if (!decided) return handed(gt::FL_UNDECIDED);
+  int wa = 0, wb = 0;
+  { int p = 0; for (int x = 0; x < nh; ++x) for (int y = x; y < nh; ++y, ++p) if (p == win) { wa = x; wb = y; } }
+  if (wa == wb) return nosplit();  // "homozygous"
+  const uint64_t top1 = sv.v_hap[wa], top2 = sv.v_hap[wb];
+  // ---- the assignment (:114-137): fewer agreements with the first haplotype -> group 0, more -> group 1, as many -> both groups, and the
+  //      assignment alternates from 0 (the k-th such read of the kept list, k from 0, gets k % 2: a workgroup prefix carried across the rounds)
+  uint32_t ties = 0, c0 = 0, c1 = 0;
+  for (int base = 0; base < n; base += DW) {
+    const int i = base + tid;
+    const bool valid = i < n;
+    int d1 = 0, d2 = 0;
+    if (valid) { const uint64_t obs = prof[2 * i], val = prof[2 * i + 1]; d1 = __popcll(obs & ~(val ^ top1)); d2 = __popcll(obs & ~(val ^ top2)); }
+    const bool tie = valid && d1 == d2;
+    uint32_t tot;
+    const uint32_t k = ties + cld::block_rank(tie, tot, sh.red);
+    if (valid) {
+      const uint32_t gi = tie ? (k & 1u) : (d1 < d2 ? 0u : 1u);
+      const bool in0 = gi == 0 || tie, in1 = gi == 1 || tie;
+      fl.grp[i] = (uint8_t)(gi | (tie ? 2u : 0u));
+      sa.snv_read[r0 + i] = (uint8_t)((gi ? gt::SR_ASSIGN : 0) | (in0 ? gt::SR_IN0 : 0) | (in1 ? gt::SR_IN1 : 0));
+      c0 += in0; c1 += in1;
+    }
+    ties += tot;
+  }
+  // (the barriers of the sums: every thread is done with the route's lists, whose bytes the tail fills next, and sees grp and the bytes)
+  const int cnt[2] = {(int)cld::block_sum_u32(c0, sh.red), (int)cld::block_sum_u32(c1, sh.red)};
+  if (!deep_flank_tail<DeepSnvMembers>(sh, sa, l, r0, n, nu, cnt, sa.snv_read)) return nosplit();
+  return true;
+}
+
+template <bool FLANK = false, bool SNV = false>
+__global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgsOf<FLANK, SNV> aa) {
+  static_assert(FLANK || !SNV, "the SNV forms are FLANK forms: they share the tail of the route and its LDS");
   __shared__ DeepSize sh;
   const DeepArgs& a = deep_of(aa);
   const uint32_t k = blockIdx.x;
@@ -429,7 +673,16 @@ __global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgsOf
   __syncthreads();
   // ---- FLANK: two sizes at most 10 apart (tr.rs:69-75) and tags that split the reads replace everything below; the size genotyper's
   //      own repair is not queued for such a locus
-  if constexpr (FLANK) {
+  if constexpr (SNV) {
+    // ---- SNV: in the reference's order -- tags that split the reads own the locus (the tag route with both settings on; else the host
+    //      finds the split as before: the byte stays 0), and only without such tags the SNVs of the flanks are tried
+    if (n_gt == 2 && adiff_u(size[0], size[1]) <= 10) {
+      int cnt[2];
+      if (aa.hp_tag && deep_flank_assign(deep_flank_lds(sh).grp, a, aa.hp_tag, r0, n, cnt, sh.red)) {
+        if (aa.tag_route) { deep_flank_tail<DeepTagMembers>(sh, aa, l, r0, n, nu, cnt); return; }
+      } else if (deep_snv_route(sh, aa, l, r0, n, nu)) return;
+    }
+  } else if constexpr (FLANK) {
     if (aa.hp_tag && n_gt == 2 && adiff_u(size[0], size[1]) <= 10 && deep_flank_route(sh, aa, l, r0, n, nu)) return;
   }
   auto ulen_of = [&](int q) { return sh.ln[sh.u_rep[q]]; };
@@ -521,8 +774,9 @@ __global__ void __launch_bounds__(DW) deep_size_genotype_kernel(const DeepArgsOf
 // ---- behind the consensus alignments and the column voting: the rest of genotype_size::genotype for the loci of the deep size list that
 // wait for a repair (need_host = 2; they are in rp.loci too, where repair_finish_kernel passes them over by their read count).  A locus
 // whose repaired allele does not fit (vote overflow, allele_cap) goes to the host path after all.
-template <bool FLANK = false>
-__global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgsOf<FLANK> aa, const gt::FinishArgs f) {
+template <bool FLANK = false, bool SNV = false>
+__global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgsOf<FLANK, SNV> aa, const gt::FinishArgs f) {
+  static_assert(FLANK || !SNV, "the SNV forms are FLANK forms");
   __shared__ Red red;
   const DeepArgs& a = deep_of(aa);
   const uint32_t k = blockIdx.x;
@@ -542,9 +796,12 @@ __global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgsOf<F
   auto seg_of = [&](int i) { return gt::Seg{cld::seg_off(a, r0, i), a.sel_len[r0 + i]}; };  // of a kept read
   if constexpr (FLANK) {
     // ... of a locus the haplotype-tag route left waiting (RP_FLANK): the alleles are the repaired sequences or the backbones of the tag
-    // groups, smaller allele first (genotype_flank.rs:33-38); deep_size_write<TAGS> recomputes the assignment from the tags (deterministic
+    // groups, smaller allele first (genotype_flank.rs:33-38); deep_size_write<BY_TAGS> recomputes the assignment from the tags (deterministic
     // from the same list of kept reads), which is the classification; its counts are num_spanning, the sizes are the allele lengths
+    // (SNV forms, a record of the SNV route -- RP_SNV: the assignment is read back from DeepSnvArgs::snv_read instead, deep_size_write<BY_SNV>)
     if (pd.n_pick & gt::RP_FLANK) {
+      uint8_t mark = 0;
+      if constexpr (SNV) mark = pd.n_pick & gt::RP_SNV ? (uint8_t)gt::FL_SNV : (uint8_t)0;
       const uint8_t* tp[2] = {nullptr, nullptr}; uint32_t tl[2] = {0, 0};
       bool bad = n == 0;
 #pragma unroll
@@ -554,11 +811,12 @@ __global__ void __launch_bounds__(DW) deep_size_finish_kernel(const DeepArgsOf<F
         const uint8_t* sp[2] = {sw ? tp[1] : tp[0], sw ? tp[0] : tp[1]};
         const uint32_t sl[2] = {sw ? tl[1] : tl[0], sw ? tl[0] : tl[1]};
         const int32_t sc[4] = {sw ? pd.civ[2] : pd.civ[0], sw ? pd.civ[3] : pd.civ[1], sw ? pd.civ[0] : pd.civ[2], sw ? pd.civ[1] : pd.civ[3]};
-        bad = !deep_size_write<true>(a, l, r0, n, 2, 2, sp, sl, sc, sl, red, aa.hp_tag, sw);
+        if constexpr (SNV) bad = mark ? !deep_size_write<BY_SNV>(a, l, r0, n, 2, 2, sp, sl, sc, sl, red, aa.hp_tag, sw, aa.snv_read) : !deep_size_write<BY_TAGS>(a, l, r0, n, 2, 2, sp, sl, sc, sl, red, aa.hp_tag, sw);
+        else bad = !deep_size_write<BY_TAGS>(a, l, r0, n, 2, 2, sp, sl, sc, sl, red, aa.hp_tag, sw);
       }
       if (tid == 0) {
-        if (bad) { g.need_host[l] = 1; aa.flank_done[l] = gt::FL_HANDED; }
-        else { g.skip_b[l] = 0; if (g.finish_clears_need) g.need_host[l] = 0; aa.flank_done[l] = gt::FL_DONE | gt::FL_REPAIRED; }
+        if (bad) { g.need_host[l] = 1; aa.flank_done[l] = (uint8_t)(gt::FL_HANDED | mark); }
+        else { g.skip_b[l] = 0; if (g.finish_clears_need) g.need_host[l] = 0; aa.flank_done[l] = (uint8_t)(gt::FL_DONE | gt::FL_REPAIRED | mark); }
       }
       return;
     }
