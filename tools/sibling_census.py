@@ -8,6 +8,12 @@ locus minus 1.2 flank lengths).  Where the other piece of the read was found exa
 inside the admissible region Adm -- [p + F, n) for a missed right piece, [0, p) for a missed left one -- and the table gives |Adm|
 among the expensive jobs: below min_matches (the scan's drop rule), below F, then by the number of 256-diagonal strips of
 F + |Adm| + 1 diagonals a pre-filter run over Adm alone would walk, next to the strips of the whole read it walks today.
+
+The expensive jobs the scan does emit then meet the front seed search (flank_window_kernel), restated here as front_search(): settled
+by a shortcut (one or two substitutions on one diagonal, one inserted or deleted base), windowed, or left without seeds for the
+pre-filter.  The last rows count the jobs without seeds whose sibling is settled by a shortcut and leaves them fewer than min_matches
+bases -- what settled_sibling_kernel drops, to hold the device's TRGT_WFA_DEBUG count against (reads beyond the dedicated kernels' text
+length, which the device keeps on a list of their own, are not modelled: a few dozen jobs on cfg4, none on cfg2).
 """
 import argparse
 import math
@@ -20,9 +26,73 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from trgt_amd import synth  # noqa: E402
 
 
-def census(config, n_loci, F=250, frac=0.7):
+def seed_plan(F, x, o, e, segments=8):
+    """what span_plan (spans.hip) decides for the seed search of F-base pieces under penalties x, o, e: segment length, the bound on the
+    spread of the seeded diagonals, and which shortcuts exist (hamming_max substitutions; the one-base gap under 2,5,1 only)"""
+    q = F // segments
+    ok = q >= 12 and x >= 1 and e >= 1 and o >= 0 and q * e >= x and o + 2 * e >= 2 * x and o + e >= x
+    s0 = x * segments - 1
+    G = (s0 - o) // e if s0 >= o + e else 0
+    hamming_max = min(segments - 1, (o + e - 1) // x, 4) if ok else 0
+    return dict(ok=ok, F=F, m=segments, q=q, spread=2 * G, hamming_max=hamming_max, indel_ok=ok and (x, o, e) == (2, 5, 1) and hamming_max == 2)
+
+
+def seeded_diagonals(read, piece, plan):
+    """(kmin, kmax) over the occurrences in the read of the first twelve bases of every segment of the piece; None without any"""
+    ks = []
+    if len(read) >= 12:
+        for i in range(plan["m"]):
+            head, t = piece[i * plan["q"]:i * plan["q"] + 12], -1
+            while True:
+                t = read.find(head, t + 1)
+                if t < 0:
+                    break
+                ks.append(t - i * plan["q"])
+    return (min(ks), max(ks)) if ks else None
+
+
+def front_search(read, piece, plan):
+    """flank_window_kernel over one expensive job, restated: ("settled", st, en) when a shortcut names the alignment (its text span is
+    [st, en)), ("window",) when the job joins the windowed launch, ("noseed",) when it goes on to the pre-filter"""
+    F, n = plan["F"], len(read)
+    kk = seeded_diagonals(read, piece, plan) if plan["ok"] else None
+    if kk is None:
+        return ("noseed",)
+    kmin, kmax = kk
+    if plan["hamming_max"] > 0 and kmin == kmax and kmin >= 0 and kmin + F <= n:  # one or two substitutions on the one seeded diagonal
+        d = sum(a != b for a, b in zip(piece, read[kmin:kmin + F]))
+        if 1 <= d <= plan["hamming_max"]:
+            return ("settled", kmin, kmin + F)
+    if plan["indel_ok"] and kmax - kmin == 1 and kmin >= 0 and kmax + F <= n and F <= 255:  # one inserted or deleted base
+        m0 = [piece[b] != read[kmin + b] for b in range(F)]
+        m1 = [piece[b] != read[kmin + 1 + b] for b in range(F)]
+        lcp = lambda m: m.index(True) if True in m else F
+        sfx = lambda m: F - m[::-1].index(True) if True in m else 0
+        lcp0, lcp1, sfx0, sfx1 = lcp(m0), lcp(m1), sfx(m0), sfx(m1)
+        last_head = (plan["m"] - 1) * plan["q"]
+        margins = sfx0 > 13 and sfx1 > 13 and lcp0 < last_head - 1 and lcp1 < last_head - 1
+        ins_ok, del_ok = sfx1 <= lcp0, max(sfx0 - 1, 0) <= min(lcp1, F - 1)
+        if margins and ins_ok != del_ok and sum(m0) >= 4 and sum(m1) >= 4:
+            return ("settled", kmin, kmin + F + 1) if ins_ok else ("settled", kmax, kmax + F - 1)
+    if kmax - kmin <= plan["spread"] and kmin >= 0 and kmax + F <= n:
+        return ("window",)
+    return ("noseed",)
+
+
+def settled_rule_drops(read, pieces, side, plan, min_matches):
+    """the rule of settled_sibling_kernel for the missed piece `side` of a read whose other piece was missed by the exact scan too:
+    True when that sibling is settled by a shortcut and leaves this piece fewer than min_matches bases of the read"""
+    sib = front_search(read, pieces[side ^ 1], plan)
+    if sib[0] != "settled":
+        return False
+    return (len(read) - sib[2] if side else sib[1]) < min_matches
+
+
+def census(config, n_loci, F=250, frac=0.7, scoring=(2, 5, 1)):
     b = synth.generate(n_loci, first_locus=0, config=config)
     min_matches = int(math.ceil(F * frac))
+    plan = seed_plan(F, *scoring)
+    front = dict(settled=0, window=0, noseed=0, noseed_drop=0, strips=0, strips_drop=0)
     blob, flank = b["read_blob"].tobytes(), b["flank_blob"].tobytes()
     jobs = dict(all=0, heavy=0, heavy_sibling=0, light=0, light_sibling=0, light_drop=0)
     hist = dict(drop=0, below_F=0)
@@ -51,6 +121,14 @@ def census(config, n_loci, F=250, frac=0.7):
                 jobs["heavy"] += 1
                 now = (F + n + 1 + 255) // 256
                 strips_now_all += now
+                if adm is None or adm >= min_matches:  # a job of the front seed search
+                    kind = front_search(read, pieces[side], plan)[0]
+                    front[kind] += 1
+                    if kind == "noseed":
+                        front["strips"] += now
+                        if sib < 0 and settled_rule_drops(read, pieces, side, plan, min_matches):
+                            front["noseed_drop"] += 1
+                            front["strips_drop"] += now
                 if adm is None:
                     continue
                 jobs["heavy_sibling"] += 1
@@ -62,7 +140,7 @@ def census(config, n_loci, F=250, frac=0.7):
                 k = (F + max(adm, F) + 1 + 255) // 256
                 strips_adm[k] = strips_adm.get(k, 0) + 1
                 strips_now[k] = strips_now.get(k, 0) + now
-    return dict(config=config, n_loci=n_loci, n_reads=int(b["n_reads"]), min_matches=min_matches, jobs=jobs, hist=hist, strips_adm=strips_adm,
+    return dict(config=config, n_loci=n_loci, n_reads=int(b["n_reads"]), min_matches=min_matches, jobs=jobs, hist=hist, front=front, strips_adm=strips_adm,
                 strips_now=strips_now, strips_now_all=strips_now_all)
 
 
@@ -87,6 +165,12 @@ def main():
                   % (k, n, pct(n, j["heavy"]), c["strips_now"][k] / n))
         left = j["heavy"] - j["heavy_sibling"]
         print("    no exact sibling (judged on the whole read):   %6d  %s" % (left, pct(left, j["heavy"])))
+        f = c["front"]
+        print("  front seed search over the %d expensive jobs the scan emits: settled by a shortcut %d, windowed %d, without seeds (pre-filter) %d"
+              % (f["settled"] + f["window"] + f["noseed"], f["settled"], f["window"], f["noseed"]))
+        print("    of those without seeds: sibling settled by a shortcut, |Adm| < min_matches (settled-sibling rule): %d (%s)"
+              % (f["noseed_drop"], pct(f["noseed_drop"], f["noseed"])))
+        print("    their 256-diagonal strips of the whole read: %d of %d (%s)" % (f["strips_drop"], f["strips"], pct(f["strips_drop"], f["strips"])))
         print("  strips summed over the expensive jobs, whole reads: %d (%.2f per job)" % (c["strips_now_all"], c["strips_now_all"] / max(j["heavy"], 1)))
 
 

@@ -46,6 +46,7 @@ struct trgt_knobs {
   bool early_adaptive = true;   // TRGT_EARLY_ADAPTIVE=0: the pre-filter's early-rejection test every 16th level (else scheduled by the smallest deficit seen)
   bool no_heavy_window = false;  // TRGT_NO_HEAVY_WINDOW: the expensive fallback alignments go to the pre-filter without the seed search first
   bool no_sibling_rule = false;  // TRGT_NO_SIBLING_RULE (DEV): the scan emits a fallback job for every missed flank piece, also where the exactly found sibling leaves it no room to count (spans.hip, ScanArgs::min_matches)
+  bool no_settled_sibling_rule = false;  // TRGT_NO_SETTLED_SIBLING_RULE (DEV): ... but a missed piece beside a sibling the seed search's shortcuts settled still meets the pre-filter (spans.hip, settled_sibling_kernel)
   bool no_indel_shortcut = false;  // TRGT_NO_INDEL_SHORTCUT: one-base gaps are aligned (the substitution shortcut stays)
   bool no_hamming = false;   // TRGT_NO_HAMMING: no substitution-only shortcut in the window search (every light fallback is aligned)
   bool no_filter = false;    // TRGT_WFA_NO_FILTER: no pre-filter in front of the expensive alignments
@@ -281,6 +282,7 @@ enum Slot {
   S_SNV_DEEP,  // the workspace of the deep size list's SNV forms (locus_gt_deep.hpp): per-read masks and staged offsets, one slab
   S_CLF_COUNTS,  // the counters of the tag branch behind the one-wave cluster chain (locus_cluster_flank.hpp)
   S_CLF_PEND,    // ... and its records of the loci that wait for the third consensus round
+  S_FS_SETTLED, S_FS_FILTERJOBS,  // flank location: the marks of what the seed search's shortcuts settled, and the pre-filter's list behind the settled-sibling rule (spans.hip)
   S_COUNT
 };
 // pinned host buffer slots

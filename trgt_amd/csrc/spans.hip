@@ -45,7 +45,9 @@ enum SpanCount : int {
   SC_SIBDROP = 16,  // missed pieces the scan did not turn into a job: the exactly found sibling leaves them fewer than min_matches bases (ScanArgs::min_matches)
   SC_WINCLAIM = 17, // job claims of the register kernel over the windowed list (wfa_win.hip)
   SC_WINFALL = 18,  // windowed alignments that kernel did not take (sequences beyond its staging buffers): they go on to the whole-read launch
-  SC_WORDS = 19
+  SC_SETDROP = 19,  // of SC_NOSEED: jobs the pre-filter never sees, the sibling the shortcuts settled leaves them fewer than min_matches bases (settled_sibling_kernel)
+  SC_FILTER = 20,   // ... the others: the pre-filter's list where that rule is on
+  SC_WORDS = 21
 };
 
 struct ScanArgs {
@@ -73,6 +75,7 @@ struct ScanArgs {
   // (:18-22) if it stays inside the region, discordant if it leaves it -- and no job is emitted.  The hit byte of such a piece reads 0
   // where the alignment might have made it 2: callers that hand the bytes out keep the rule off (find_spans_device, span_only).
   int32_t min_matches;
+  uint8_t* settled;  // not NULL: [n_jobs] cleared here, one byte per (read, side); the front seed search marks what its shortcuts settle (SettledArgs)
 };
 
 __device__ __forceinline__ uint32_t load_u32(const uint8_t* p) {
@@ -114,6 +117,7 @@ __global__ void __launch_bounds__(256) flank_scan_kernel(const ScanArgs a) {
   }
   if (lane == 0) {
     a.pos[j] = found; a.n_match[j] = -1;
+    if (a.settled) a.settled[j] = 0;
     if (found < 0) {  // fall back to the wavefront aligner (span_locater.rs:13-26)
       const bool lng = (uint32_t)n > a.long_tlen;
       const uint32_t slot = atomicAdd(a.wfa_count + (lng ? SC_LONG : SC_HEAVY), 1u);
@@ -240,6 +244,7 @@ struct WindowArgs {
   int32_t hamming_max;                 // > 0: the substitution-only shortcut below, for up to this many mismatches
   int32_t indel_ok;                    // 1: the one-base-gap shortcut (penalties 2,5,1)
   int32_t* n_match; uint32_t* span4;   // per (read, side): what the alignment kernels would have written for such a job
+  uint8_t* settled;                    // not NULL: per (read, side), set to 1 where a shortcut wrote them (the scan cleared it)
 };
 constexpr int WIN_JOBS_PER_WG = 64;
 template <int WIN_SEGMENTS>
@@ -319,6 +324,7 @@ __global__ void __launch_bounds__(256) flank_window_kernel(const WindowArgs a) {
             const uint64_t j = jd.out_index;
             a.n_match[j] = F - (int)cnt;
             a.span4[4 * j] = 0u; a.span4[4 * j + 1] = (uint32_t)F; a.span4[4 * j + 2] = (uint32_t)kmin; a.span4[4 * j + 3] = (uint32_t)(kmin + F);
+            if (a.settled) a.settled[j] = 1;
             atomicAdd(&l_ns, 1u);  // (one global atomic per workgroup below: 60k of them on one address doubled this kernel's time)
           }
         }
@@ -373,6 +379,7 @@ __global__ void __launch_bounds__(256) flank_window_kernel(const WindowArgs a) {
             const int start = ins_ok ? kmin : kmax, len = ins_ok ? F + 1 : F - 1;
             a.n_match[j] = ins_ok ? F : F - 1;
             a.span4[4 * j] = 0u; a.span4[4 * j + 1] = (uint32_t)F; a.span4[4 * j + 2] = (uint32_t)start; a.span4[4 * j + 3] = (uint32_t)(start + len);
+            if (a.settled) a.settled[j] = 1;
             atomicAdd(&l_ns, 1u);
             atomicAdd(&l_ni, 1u);
           }
@@ -523,6 +530,7 @@ __global__ void __launch_bounds__(256) flank_scan_wide_kernel(const ScanArgs a) 
     for (int side = 0; side < 2; ++side) {
       const uint64_t j = 2 * r + side;
       a.pos[j] = found[side]; a.n_match[j] = -1;
+      if (a.settled) a.settled[j] = 0;
       // (ScanArgs::min_matches) what the exactly found sibling leaves this piece: the read behind the left piece, or in front of the right one
       const int room = found[side ^ 1] < 0 ? 0x7FFFFFFF : side ? n - found[0] - F : found[1];
       if (found[side] < 0 && room < a.min_matches) atomicAdd(&l_drop, 1u);
@@ -544,6 +552,45 @@ __global__ void __launch_bounds__(256) flank_scan_wide_kernel(const ScanArgs a) 
   __syncthreads();
   for (uint32_t i = threadIdx.x; i < l_n; i += blockDim.x) a.wfa_jobs[l_base + i] = l_jobs[i];
   for (uint32_t i = threadIdx.x; i < l_n2; i += blockDim.x) a.wfa_jobs[a.jobs_cap - 1u - (l_base2 + i)] = l_jobs[2 * SCAN_READS_PER_WG - 1 - i];
+}
+
+// ---- The sibling rule once more, behind the front seed search: beside a sibling its SHORTCUTS settled ----
+// The argument of ScanArgs::min_matches asks nothing of the sibling but its text span [st, en): a missed right piece counts only
+// inside [en, n), a missed left piece only inside [0, st) -- an alignment that leaves that region is discordant (lf.end > rf.start,
+// span_locater.rs:59-65), one that stays inside has count_matches() <= its text span <= the region -- so with fewer than min_matches
+// bases there the read's span is None whatever the missed piece's alignment is, and whether or not the sibling passes the threshold
+// itself.  For a sibling settled by a shortcut of flank_window_kernel the span in span4 is the reference's (the proofs there), and the
+// front seed search has written it before this kernel starts, on the same stream.  The windowed launch of the other stream writes
+// n_match and span4 of OTHER jobs of that list at the same time: nothing is read here but the settled mark, which only the front
+// seed search writes, and the span4 entry it stands for.  One thread per job of the list without seeds; the jobs that stay are
+// compacted (one atomic per wave) into the pre-filter's list, a dropped job keeps n_match = -1 as after the scan's drop.
+struct SettledArgs {
+  const JobDev* jobs; const uint32_t* n_jobs;  // the expensive jobs without seeds (count[SC_NOSEED])
+  JobDev* out; uint32_t* count;                // the jobs that stay, under count[SC_FILTER]; the others are tallied in count[SC_SETDROP]
+  const uint8_t* settled; const uint32_t* span4; int32_t min_matches;
+};
+__global__ void __launch_bounds__(256) settled_sibling_kernel(const SettledArgs a) {
+  const uint32_t n = *a.n_jobs, lane = threadIdx.x & 63u;
+  for (uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) & ~63u; i0 < n; i0 += gridDim.x * blockDim.x) {  // (i0: uniform per wave)
+    const uint32_t i = i0 + lane;
+    bool stay = false, drop = false;
+    JobDev jd;
+    if (i < n) {
+      jd = a.jobs[i];
+      const uint32_t j = jd.out_index, sib = j ^ 1u;
+      int room = 0x7FFFFFFF;  // bases of the read on the far side of the sibling (txt_len: the whole read, these jobs have no window)
+      if (a.settled[sib]) room = (j & 1u) ? (int)jd.txt_len - (int)a.span4[4 * (uint64_t)sib + 3] : (int)a.span4[4 * (uint64_t)sib + 2];
+      drop = room < a.min_matches; stay = !drop;
+    }
+    const unsigned long long ms = __ballot(stay), md = __ballot(drop);
+    uint32_t base = 0;
+    if (lane == 0) {
+      if (ms) base = atomicAdd(a.count + SC_FILTER, (uint32_t)__popcll(ms));
+      if (md) atomicAdd(a.count + SC_SETDROP, (uint32_t)__popcll(md));
+    }
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    if (stay) a.out[base + (uint32_t)__popcll(ms & ((1ull << lane) - 1ull))] = jd;
+  }
 }
 
 // After the windowed launch: a windowed alignment whose penalty is within the bound of piece_window's argument IS the alignment of
@@ -730,6 +777,7 @@ struct SpanPlan {
   int32_t hamming_max = 0, indel_ok = 0; bool win_reg = false;  // (win_reg: the windowed launch is the register kernel's, wfa_win.hip)
   bool split = false, use_filter = false, two_streams = false; int64_t flt_tlen = 0;
   bool heavy_window = false;  // the seed search runs over the expensive list as well
+  bool settled_rule = false;  // ... and the sibling rule is applied once more to what that search leaves without seeds (SettledArgs)
   bool heavy_band = false;    // ... and what the pre-filter keeps of it is back-traced inside a band (BandArgs)
   bool long_window = false;   // the long reads' list goes through the light list's seed search
   bool long_filter = false, long_band = false; int64_t long_wl = 0, long_step = 0; uint64_t long_cap = 0;  // the window filter of the long reads (LongWinArgs)
@@ -803,6 +851,8 @@ static SpanPlan span_plan(const trgt_hip_ctx* c, const trgt_span_params& p, uint
     // levels and the back-tracing kernel aligned them a second time, at the end of this stream's chain.  With seeds they are settled
     // by the substitution shortcut or join the windowed launch of the other stream; the pre-filter sees the jobs WITHOUT seeds only.
     P.heavy_window = P.use_filter && P.two_streams && P.win_q > 0 && !k.no_heavy_window;
+    // (on where the scan's rule is on -- callers that hand out hit bytes keep both off -- and a shortcut exists that could settle a sibling)
+    P.settled_rule = P.heavy_window && P.scan_min_matches > 0 && P.hamming_max > 0 && !k.no_settled_sibling_rule;
     P.heavy_band = P.use_filter && band_ok;
   }
   P.long_window = P.has_long && P.win_q > 0 && !k.no_long_window;  // shortcuts and windows do not care how long the read is
@@ -847,6 +897,7 @@ struct SpanCall {
   // workspace (long_noseed: the long reads' list behind the seed search, when that runs over it)
   JobDev *wjobs = nullptr, *wjobs_long = nullptr, *winjobs = nullptr, *restjobs = nullptr, *long_noseed = nullptr;
   uint32_t *count = nullptr, *span4 = nullptr; int32_t *pos = nullptr, *nmatch = nullptr, *score = nullptr;
+  uint8_t* settled = nullptr;  // the marks of what the front seed search's shortcuts settled (plan.settled_rule; else NULL)
   // launches: the alignment parameters; the descriptors of the expensive list, the light list (after the seeded windows: the rest list) and the long reads
   trgt_wfa_params wp; WfaLaunch heavy, light, longl;
   JobList long_in{nullptr, nullptr};  // the long reads' list
@@ -884,6 +935,7 @@ int SpanCall::workspace() {  // ... and the base launch descriptors over it
     return rc;
   count = (uint32_t*)zeroed;
   if (plan.has_long && (rc = get(S_FS_WFAJOBS_LONG, n_jobs * sizeof(JobDev), wjobs_long))) return rc;
+  if (plan.settled_rule && (rc = get(S_FS_SETTLED, n_jobs, settled))) return rc;
   if (plan.win_q > 0 && ((rc = get(S_FS_WINJOBS, n_jobs * sizeof(JobDev), winjobs)) || (rc = get(S_FS_RESTJOBS, n_jobs * sizeof(JobDev), restjobs)) ||
                          (rc = get(S_FS_SCORE, n_jobs * 4, score))))
     return rc;
@@ -913,7 +965,7 @@ int SpanCall::scan() {
   sa.flank_blob = d_flank; sa.read_blob = d_reads; sa.piece_off = d_piece_off; sa.read_off = d_read_off; sa.read_len = d_read_len;
   sa.read_locus = d_read_locus; sa.n_jobs = n_jobs; sa.flank_len = p.flank_len; sa.pos = pos; sa.n_match = nmatch;
   sa.wfa_jobs = wjobs; sa.wfa_count = count; sa.heavy_len = d_heavy_len; sa.jobs_cap = (uint32_t)n_jobs;
-  sa.min_matches = plan.scan_min_matches;
+  sa.min_matches = plan.scan_min_matches; sa.settled = settled;
   sa.wfa_jobs_long = wjobs_long; sa.long_tlen = plan.has_long ? plan.long_tlen : 0xFFFFFFFFu;
   KTimer t(c, TRGT_K_FLANK_SCAN);
   if (p.flank_len >= 4) hipLaunchKernelGGL(flank_scan_wide_kernel, dim3((unsigned)((n_reads + SCAN_READS_PER_WG - 1) / SCAN_READS_PER_WG)), dim3(256), 0, c->stream, sa);
@@ -931,7 +983,7 @@ int SpanCall::seed_search(bool front, JobDev* rest, JobDev* long_rest) {
   wa.win_jobs = winjobs; wa.rest_jobs = rest; wa.flank_len = p.flank_len; wa.q = plan.win_q; wa.margin = plan.win_margin; wa.spread = plan.win_spread; wa.tbf = plan.win_tbf;
   wa.front = front ? 1 : 0; wa.long_jobs = long_rest ? wjobs_long : nullptr; wa.long_rest = long_rest;
   wa.hamming_max = plan.hamming_max; wa.indel_ok = plan.indel_ok;
-  wa.n_match = nmatch; wa.span4 = span4;
+  wa.n_match = nmatch; wa.span4 = span4; wa.settled = front ? settled : nullptr;  // (the marks are the front search's alone: SettledArgs)
   KTimer t(c, TRGT_K_FLANK_WINDOW);
   const dim3 wgrid((unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)c->num_cus * 8, (int64_t)((n_jobs + WIN_JOBS_PER_WG - 1) / WIN_JOBS_PER_WG))));
   if (plan.win_m == 4) hipLaunchKernelGGL(flank_window_kernel<4>, wgrid, dim3(256), 0, c->stream, wa);
@@ -966,7 +1018,8 @@ int SpanCall::band_backtrace(JobList& list, int slot_band, int slot_rest, int sl
   list = {rest, count + i_rest};
   return TRGT_OK;
 }
-// The expensive list, on the second stream where the plan says so: seed search over the front of the list, pre-filter, banded
+// The expensive list, on the second stream where the plan says so: seed search over the front of the list, the sibling rule beside what
+// its shortcuts settled (SettledArgs), pre-filter, banded
 // back-trace of what it keeps, back-tracing launch over the rest of that.  Leaves the event the join waits for.
 int SpanCall::heavy_list() {
   int rc;
@@ -987,6 +1040,16 @@ int SpanCall::heavy_list() {
     if ((rc = seed_search(true, noseed, nullptr))) return rc;
     TRGT_HIP_TRY(c, hipEventRecord(c->ev_hwin, c->stream));
     list = {noseed, count + SC_NOSEED};
+    if (plan.settled_rule) {  // (behind the event: the other stream's seed search does not wait for this)
+      JobDev* fjobs = nullptr;
+      if ((rc = get(S_FS_FILTERJOBS, n_jobs * sizeof(JobDev), fjobs))) return rc;
+      SettledArgs sg;
+      sg.jobs = list.jobs; sg.n_jobs = list.count; sg.out = fjobs; sg.count = count;
+      sg.settled = settled; sg.span4 = span4; sg.min_matches = plan.scan_min_matches;
+      hipLaunchKernelGGL(settled_sibling_kernel, dim3(64), dim3(256), 0, c->stream, sg);
+      TRGT_HIP_TRY(c, hipGetLastError());
+      list = {fjobs, count + SC_FILTER};
+    }
   }
   if (plan.use_filter) {
     JobDev* keepjobs = nullptr;
@@ -1113,6 +1176,7 @@ int SpanCall::debug_report() {  // (synchronises: developer output only)
   if (win && plan.heavy_window) fprintf(stderr, "[spans+] (the seed search ran over the first launch's list too: %u of its %u alignments had no seeds and met the pre-filter; the counts of the windowed list and of the shortcut include the others)\n", h[SC_NOSEED], h[SC_HEAVY]);
   if (plan.has_long) fprintf(stderr, "[spans+] long reads kept by the window filter: back-traced inside a band %u, over the whole read %u\n", h[SC_LBAND], h[SC_LREST]);
   fprintf(stderr, "[spans+] sibling rule %s: %u missed pieces without a job (fewer than %d bases beside the exactly found sibling)\n", plan.scan_min_matches > 0 ? "on" : "off", h[SC_SIBDROP], plan.scan_min_matches);
+  if (win && plan.heavy_window) fprintf(stderr, "[spans+] settled-sibling rule %s: %u jobs without seeds never met the pre-filter (fewer than %d bases beside a sibling the shortcuts settled)\n", plan.settled_rule ? "on" : "off", h[SC_SETDROP], plan.scan_min_matches);
   if (plan.heavy_band) fprintf(stderr, "[spans+] kept by the pre-filter: %u -> back-traced inside a band %u (did not stand: %u), over the whole read %u\n", h[SC_KEEP], h[SC_BAND], h[SC_BANDFAIL], h[SC_HREST]);
   return TRGT_OK;
 }
