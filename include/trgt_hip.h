@@ -131,7 +131,9 @@ int trgt_hip_flank_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
  * calls whose batch carries hp_tag run the tag branch behind the one-wave cluster chain (locus_cluster_flank.hpp) for the cluster loci
  * of at most 256 candidate reads: assignment by tag, acceptance, simple_consensus of either group, a third consensus round of the chain
  * for a group without a majority sequence, smaller allele first, reference allele first.  What stays on the host, with the same
- * results: the SNV-clustering branch (get_trs_with_clustering), tried for the loci whose tags do not split the reads exactly as before;
+ * results: the SNV-clustering branch (get_trs_with_clustering), tried for the loci whose tags do not split the reads exactly as before
+ * unless the context is also set with trgt_hip_set_snv_cluster_device (trgt_hip_flank_cluster.h: with both settings both branches run
+ * behind the chain, tags first);
  * deep cluster loci (257 to 2048 reads on a context set with trgt_hip_set_cluster_max_reads), which the host redoes as before;
  * contexts created under TRGT_HOST_CLUSTER or TRGT_HOST_GENOTYPER; and a locus on this route that finds no room in the chain's arenas,
  * whose repaired group overflows its slot, or that has an allele beyond allele_cap.  trgt_hip_flank_cluster_stats: of the context's
@@ -154,7 +156,8 @@ int trgt_hip_flank_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
  * per-read masks and the staged offsets live in HBM), in the same order, and trgt_hip_set_flank_device again selects whose the tag
  * branch is.  Everything but exp and log is restated bit for bit; the candidate search is decided on the device only when its
  * winner is ahead of every other candidate by more than 2^-30 * (1 + |log-likelihood|), far beyond what two libms can differ by.
- * What stays on the host, with the same results: Genotyper::Cluster loci; size loci of more than 256 reads on a context without
+ * What stays on the host, with the same results: Genotyper::Cluster loci unless the context is also set with
+ * trgt_hip_set_snv_cluster_device (a setting of its own, trgt_hip_flank_cluster.h); size loci of more than 256 reads on a context without
  * trgt_hip_set_size_max_reads, and beyond that setting or the 2048-read ceiling on one that has it; contexts created under TRGT_HOST_GENOTYPER; the tag branch where trgt_hip_set_flank_device is
  * off; searches not decided beyond the margin; and a locus on this route that finds no room in the repair chain, has a segment beyond
  * its longest (TRGT_REPAIR_MAX_SEG; every such locus under TRGT_HOST_REPAIR), an allele beyond allele_cap, more than 64 called SNVs,

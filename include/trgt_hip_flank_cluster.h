@@ -1,7 +1,7 @@
-/* trgt_hip_flank_cluster.h -- the two entry points of the haplotype-tag branch of genotype_flank behind the device cluster chain
- * (genotype_flank.rs:9-76, 147-170; tr.rs:64-75).  Part of include/trgt_hip.h, which includes this file inside its extern "C" block and
- * documents both functions (what runs on the device, what stays on the host, the three counts); not meant to be included on its own.
- * Additions to ABI 11. */
+/* trgt_hip_flank_cluster.h -- the entry points of genotype_flank behind the device cluster chain: the two of the haplotype-tag branch
+ * (genotype_flank.rs:9-76, 147-170; tr.rs:64-75), which include/trgt_hip.h documents (what runs on the device, what stays on the host,
+ * the three counts), and the two of the SNV branch, documented below.  Part of include/trgt_hip.h, which includes this file inside its
+ * extern "C" block; not meant to be included on its own.  Additions to ABI 11. */
 #ifndef TRGT_HIP_FLANK_CLUSTER_H
 #define TRGT_HIP_FLANK_CLUSTER_H
 #ifndef TRGT_HIP_H
@@ -9,4 +9,29 @@
 #endif
 int trgt_hip_set_flank_cluster_device(trgt_hip_ctx* ctx, int on);
 int trgt_hip_flank_cluster_stats(const trgt_hip_ctx* ctx, int64_t out[3]);
+/* The other branch of the same step for Genotyper::Cluster loci: the split by heterozygous SNVs of the flanks (get_trs_with_clustering
+ * with its analysis region, SNV calls, profiles, candidate genotypes and log-likelihoods, genotype_flank.rs:78-138, 171-290; applied by
+ * analyze at tr.rs:64-75 whichever genotyper produced the alleles).  A setting of its own, independent of the three others.  By default
+ * the host runs this step for every device-genotyped cluster locus with two alleles at most 10 bases apart, and redoes the loci whose
+ * SNVs split the reads from the start.  On a context set with on != 0, calls whose batch carries mismatch_offsets and mismatch_off run
+ * it behind the one-wave cluster chain (the SNV forms of locus_cluster_flank.hpp) for the cluster loci of ploidy 2 and at most 256
+ * candidate reads, in the reference's order, tags first: tags that split the reads own the locus (the device's tag branch with
+ * trgt_hip_set_flank_cluster_device also on, else the host as before), the SNVs are tried only without them.  The search is the one of
+ * trgt_hip_set_snv_split_device, stated once: everything but exp and log is restated bit for bit, and it is decided on the device only
+ * when its winner is ahead of every other candidate by more than 2^-30 * (1 + |log-likelihood|).  The groups of this branch overlap: a
+ * read that agrees equally with both haplotypes is a member of both; consensus, intervals and the third consensus round follow the
+ * membership, num_spanning and the classification the assignment.
+ * What stays on the host, with the same results: deep cluster loci (257 to 2048 reads on a context set with
+ * trgt_hip_set_cluster_max_reads), in both branches; contexts created under TRGT_HOST_CLUSTER or TRGT_HOST_GENOTYPER; searches not
+ * decided beyond the margin; loci beyond one of the three limits -- more than 64 called SNVs, more than 16 distinct fully observed
+ * profiles, more than 8 in-region mismatch offsets per candidate read slot of the kernel form (512 / 2048 occurrences per locus for
+ * the 64-read / 256-read forms); a locus on this route that finds no room in the chain's arenas, whose repaired group overflows its
+ * slot, or that has an allele beyond allele_cap; and the tag branch where trgt_hip_set_flank_cluster_device is off.
+ * trgt_hip_snv_cluster_stats: of the context's last trgt_locus_batch -- out[0] cluster loci whose genotype the device replaced through
+ * the SNV branch, out[1] those among them with a repaired group, out[2] loci on the route handed back for room or limits, out[3] loci
+ * handed back because the search was not decided beyond the margin (not in out[2]); all zero with the setting off, a batch without
+ * mismatch offsets or a call without a device cluster chain.  A locus this branch settles or hands back is in no other count:
+ * trgt_hip_flank_cluster_stats counts the tag branch only, trgt_hip_snv_split_stats and trgt_hip_flank_stats never a cluster locus. */
+int trgt_hip_set_snv_cluster_device(trgt_hip_ctx* ctx, int on);
+int trgt_hip_snv_cluster_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
 #endif

@@ -85,6 +85,9 @@ EXPORTS = [
 # The two entry points of the tag branch behind the cluster chain (locus_cluster_flank.hpp).  A list of its own, checked by lib() like EXPORTS:
 # tests/test_flank_deep_api.py pins the trgt_hip_*flank* names of EXPORTS to the two of the size genotyper's setting.
 CLUSTER_FLANK_EXPORTS = ["trgt_hip_set_flank_cluster_device", "trgt_hip_flank_cluster_stats"]
+# ... and the two of the SNV branch behind it, a third list checked the same way: tests/test_snv_deep_api.py pins the trgt_hip_*snv* names of
+# EXPORTS to the two of the size genotyper's setting, tests/test_flank_cluster_api.py the list above to its two.
+CLUSTER_SNV_EXPORTS = ["trgt_hip_set_snv_cluster_device", "trgt_hip_snv_cluster_stats"]
 
 
 def build_extension(force=False, verbose=False, dev=False):
@@ -113,7 +116,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(_SO)
-        missing = [n for n in EXPORTS + CLUSTER_FLANK_EXPORTS if not hasattr(L, n)]
+        missing = [n for n in EXPORTS + CLUSTER_FLANK_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_SNV_EXPORTS if not hasattr(L, n)]
         if missing:
             raise TrgtHipError("%s does not export %s (stale build?)" % (_SO, ", ".join(missing)))
         L.trgt_hip_last_error.restype = C.c_char_p
@@ -136,6 +139,8 @@ def lib():
         L.trgt_hip_snv_split_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_set_flank_cluster_device.argtypes = [_VP, C.c_int]
         L.trgt_hip_flank_cluster_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
+        L.trgt_hip_set_snv_cluster_device.argtypes = [_VP, C.c_int]
+        L.trgt_hip_snv_cluster_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_timing_enable.argtypes = [_VP, C.c_int]
         L.trgt_hip_timing_reset.argtypes = [_VP]
         L.trgt_hip_timing_get.argtypes = [_VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -247,6 +252,21 @@ class Context:
         self.check(lib().trgt_hip_flank_cluster_stats(self.handle, out))
         return tuple(int(v) for v in out)
 
+    def set_snv_cluster_device(self, on=True):
+        """trgt_hip_set_snv_cluster_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) behind the one-wave cluster
+        chain, for the Genotyper::Cluster loci of at most 256 candidate reads of batches that carry mismatch offsets; tags that split the
+        reads come first (set_flank_cluster_device, else the host).  A locus whose candidate search is not decided beyond the margin, or
+        that is beyond the route's limits, goes to the host path as before.  Independent of the other settings.  Every later call on this
+        context uses it."""
+        self.check(lib().trgt_hip_set_snv_cluster_device(self.handle, int(bool(on))))
+
+    def snv_cluster_stats(self):
+        """trgt_hip_snv_cluster_stats of the context's last trgt_locus_batch: (cluster loci whose genotype the device replaced through the
+        SNV branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided)."""
+        out = (C.c_int64 * 4)()
+        self.check(lib().trgt_hip_snv_cluster_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def timing_enable(self, on=True):
         self.check(lib().trgt_hip_timing_enable(self.handle, int(on)))
 
@@ -273,7 +293,7 @@ class Context:
 class Pool:
     """trgt_hip_pool: several contexts (devices[i] = ordinal of context i, ordinals may repeat) behind one queue of batches."""
 
-    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, snv_split_device=None):
+    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, snv_split_device=None, snv_cluster_device=None):
         L = lib()
         L.trgt_hip_pool_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
         L.trgt_hip_pool_destroy.argtypes = [C.c_void_p]
@@ -312,6 +332,9 @@ class Pool:
         if snv_split_device is not None:
             for c in self.contexts:
                 c.set_snv_split_device(snv_split_device)
+        if snv_cluster_device is not None:
+            for c in self.contexts:
+                c.set_snv_cluster_device(snv_cluster_device)
 
     def run_many(self, params_struct, cins, couts, out_per_context=False):
         """cins / couts: lists of LocusBatchIn / LocusBatchOut structures (couts: one per batch, or one per context)"""

@@ -116,6 +116,8 @@ struct trgt_hip_ctx {
   bool snv_split_device = false;  // trgt_hip_set_snv_split_device: the SNV branch of genotype_flank runs in the device genotyper (locus_gt.hpp, SNV forms)
   int64_t snv_split_stats[4] = {0, 0, 0, 0};  // trgt_hip_snv_split_stats: of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, handed back for room or limits, handed back undecided)
   bool flank_cluster_device = false;  // trgt_hip_set_flank_cluster_device: the same branch behind the one-wave cluster chain (locus_cluster_flank.hpp)
+  bool snv_cluster_device = false;  // trgt_hip_set_snv_cluster_device: the SNV branch behind that chain (the SNV forms of locus_cluster_flank.hpp)
+  int64_t snv_cluster_stats[4] = {0, 0, 0, 0};  // trgt_hip_snv_cluster_stats: cluster loci of the last trgt_locus_batch, counted like snv_split_stats
   int64_t flank_cluster_stats[3] = {0, 0, 0};  // trgt_hip_flank_cluster_stats: cluster loci of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, handed back to the host path)
   int num_cus = 256;
   // cached device buffers, indexed by slot

@@ -660,6 +660,10 @@ const OneWave<cl::ClArgs> k_cluster_finish{{{cl::cluster_finish_kernel<64>, cl::
 // (the tag branch of genotype_flank behind the chain: contexts that opted in with trgt_hip_set_flank_cluster_device, calls whose reads carry tags)
 const OneWave<clf::ClFlankArgs> k_cluster_flank{{{clf::cluster_flank_kernel<64>, clf::cluster_flank_kernel<64, true>}, {clf::cluster_flank_kernel<GT_BIG>, clf::cluster_flank_kernel<GT_BIG, true>}}};
 const OneWave<clf::ClFlankArgs> k_cluster_flank_finish{{{clf::cluster_flank_finish_kernel<64>, clf::cluster_flank_finish_kernel<64, true>}, {clf::cluster_flank_finish_kernel<GT_BIG>, clf::cluster_flank_finish_kernel<GT_BIG, true>}}};
+// (the SNV forms of the two: contexts that opted in with trgt_hip_set_snv_cluster_device, calls whose reads carry mismatch offsets)
+const OneWave<clf::ClSnvArgs> k_cluster_flank_snv{{{clf::cluster_flank_kernel<64, false, true>, clf::cluster_flank_kernel<64, true, true>}, {clf::cluster_flank_kernel<GT_BIG, false, true>, clf::cluster_flank_kernel<GT_BIG, true, true>}}};
+const OneWave<clf::ClSnvArgs> k_cluster_flank_finish_snv{{{clf::cluster_flank_finish_kernel<64, false, true>, clf::cluster_flank_finish_kernel<64, true, true>},
+                                                          {clf::cluster_flank_finish_kernel<GT_BIG, false, true>, clf::cluster_flank_finish_kernel<GT_BIG, true, true>}}};
 
 // the deep cluster list's buffers: the same slots as the shallow list's, second set
 inline int cl_slot(bool deep, int s) { return s + (deep ? (int)S_CLD_LIST - (int)S_CL_LIST : 0); }
@@ -710,7 +714,7 @@ struct LocusCall {
   const int64_t nl; int64_t nr = 0; int F = 0;
   bool done = false;  // nothing left to do (a call without loci or without reads)
   trgt_locus_batch_in in_expanded; std::vector<uint64_t> expanded_off;  // TRGT_READS_BAM4: the batch with its reads expanded in HBM
-  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, snv_dev = false, flank_cl_dev = false, cf_route = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
+  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, snv_dev = false, flank_cl_dev = false, snv_cl_dev = false, cf_route = false, cf_snv = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
   FlankMeta flank_meta{};
   // ---- clean-up state (see the destructor)
   bool zeroed = false;
@@ -813,6 +817,7 @@ int LocusCall::check_args() {
   for (int64_t& v : c->flank_stats) v = 0;
   for (int64_t& v : c->flank_cluster_stats) v = 0;
   for (int64_t& v : c->snv_split_stats) v = 0;
+  for (int64_t& v : c->snv_cluster_stats) v = 0;
   if (nl == 0) { done = true; return TRGT_OK; }
   if (!in->flank_blob || !in->lf_off || !in->lf_len || !in->rf_off || !in->rf_len || !in->tr_blob || !in->tr_off || !in->tr_len ||
       !in->motif_blob || !in->motif_off || !in->set_motif_begin || !in->ploidy || !in->locus_read_begin || !in->read_blob ||
@@ -934,6 +939,9 @@ int LocusCall::upload_tables() {
   snv_dev = dev_gt && c->snv_split_device && in->mismatch_offsets != nullptr && in->mismatch_off != nullptr;
   // ... and, a setting of its own (trgt_hip_set_flank_cluster_device), behind the one-wave cluster chain: locus_cluster_flank.hpp
   flank_cl_dev = dev_gt && c->flank_cluster_device && in->hp_tag != nullptr;
+  // ... and the SNV branch behind that chain (trgt_hip_set_snv_cluster_device), for a batch with mismatch offsets: the SNV forms of the
+  // same two kernels, which take the place of the tag forms; flank_cl_dev then only says whose the tag branch inside them is
+  snv_cl_dev = dev_gt && c->snv_cluster_device && in->mismatch_offsets != nullptr && in->mismatch_off != nullptr;
   int rc;
   if (ready) TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, ready, 0));
   if (staged_flank) d_flank = staged_flank;
@@ -956,8 +964,8 @@ int LocusCall::upload_tables() {
     o_nsp = slab.add(2 * (size_t)nl * 4); o_cls = slab.add((size_t)nr * 4); o_rank = slab.add((size_t)nr * 4); o_nspan = slab.add((size_t)nl * 4);
     o_toff = slab.add((2 * (size_t)nl + 1) * 8); o_flip = slab.add((size_t)nl);
     o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
-    if (flank_dev || flank_cl_dev || snv_dev) o_fdone = slab.add((size_t)nl);
-    if (flank_cl_dev) o_cfc = slab.add(clf::CF_WORDS * 4);
+    if (flank_dev || flank_cl_dev || snv_dev || snv_cl_dev) o_fdone = slab.add((size_t)nl);
+    if (flank_cl_dev || snv_cl_dev) o_cfc = slab.add(clf::CF_WORDS * 4);
   }
   if ((rc = dev_get(c, S_LOCUS_4, slab.total, &slab.dev)) || (rc = pin_get(c, P_SPAN_S, slab.total, &slab.host))) return rc;
   d_ss = slab.d(o_ss); d_se = slab.d(o_se); d_hl = slab.d(o_hl); d_hr = slab.d(o_hr);
@@ -968,8 +976,8 @@ int LocusCall::upload_tables() {
         (rc = dev_in(c, S_GT_TRLEN, in->tr_len, (size_t)nl, &g.tr_len, &ub)) || (rc = dev_in(c, S_GT_ALOFF, out->allele_off, 2 * (size_t)nl, &g.al_off, &ub)) ||
         (rc = dev_in(c, S_GT_ALCAP, out->allele_cap, (size_t)nl, &g.al_cap, &ub)) || (in->genotyper && (rc = dev_in(c, S_GT_GENO, in->genotyper, (size_t)nl, &g.geno, &ub))) ||
         (presel && in->read_qual && (rc = dev_in(c, S_PUR_RQ, in->read_qual, (size_t)nr, &g.rq, &ub))) ||
-        ((flank_dev || flank_cl_dev || (snv_dev && in->hp_tag)) && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
-        (snv_dev && ((in->start_offset && (rc = dev_in(c, S_SNV_SO, in->start_offset, (size_t)nr, &g.so, &ub))) ||
+        ((flank_dev || flank_cl_dev || ((snv_dev || snv_cl_dev) && in->hp_tag)) && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
+        ((snv_dev || snv_cl_dev) && ((in->start_offset && (rc = dev_in(c, S_SNV_SO, in->start_offset, (size_t)nr, &g.so, &ub))) ||
                      (in->end_offset && (rc = dev_in(c, S_SNV_EO, in->end_offset, (size_t)nr, &g.eo, &ub))) ||
                      (rc = dev_in(c, S_SNV_MMOFF, in->mismatch_off, (size_t)nr + 1, &g.mm_off, &ub)) ||
                      (rc = dev_in(c, S_SNV_MM, in->mismatch_offsets, (size_t)in->mismatch_off[nr], &g.mm, &ub)) ||
@@ -1351,9 +1359,13 @@ int LocusCall::cluster_chain(int deep) {
   ca.cap_j = (uint32_t)cl_reads; ca.cap_g = 2 * n_cl; ca.vote_lds_pos = (uint32_t)vote::VOTE_LDS_POS;
   // the tag branch of genotype_flank behind the chain (locus_cluster_flank.hpp): the shallow list of a haplotagged call, on a context that
   // opted in; it adds a third consensus round, and only then do the arenas and the job / group / length lists grow from two parts to three
-  const bool route = !deep && flank_cl_dev;
+  // ... and its SNV branch (the SNV forms of the same kernels).  The groups of that branch overlap -- a read can be a member of both -- so
+  // the third part of the job list (and of the CIGAR lengths beside it) then has room for two jobs per read: a fourth part's worth
+  const bool snv_route = !deep && snv_cl_dev;
+  const bool route = (!deep && flank_cl_dev) || snv_route;
   if (route) cf_route = true;  // (read by wait_stage_a)
-  const uint64_t rounds = route ? 3 : 2;
+  if (snv_route) cf_snv = true;
+  const uint64_t rounds = snv_route ? 4 : route ? 3 : 2;
   // arenas for the consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
   ca.cap_cigar = std::min<uint64_t>(rounds * cl_reads * (2ull * max_seg + 1), 96ull << 20);   // words
   ca.cap_out = std::min<uint64_t>(rounds * (cl_reads + 2ull * n_cl) * ((uint64_t)max_seg + 16) + 64, 256ull << 20);  // bytes
@@ -1410,9 +1422,9 @@ int LocusCall::cluster_chain(int deep) {
     LE.score = score; LE.buffer_set = 2; LE.ws_budget = 512ull << 20; LE.refused = ca.counts + cl::CC_REFUSED;
     return wfa_launch(c, wed, LE);
   };
-  auto cons_launch = [&](uint32_t first_job, const uint32_t* count, uint32_t first_group, const uint32_t* group_count) -> int {
+  auto cons_launch = [&](uint32_t first_job, const uint32_t* count, uint32_t first_group, const uint32_t* group_count, int64_t parts = 1) -> int {  // parts: of cap_j jobs each
     WfaLaunch LC;
-    LC.jobs_dev = ca.jobs + first_job; LC.n_jobs_host = std::min<int64_t>((int64_t)ca.cap_j, wg_bound); LC.n_jobs_dev = count; LC.jobs_bound = (int64_t)ca.cap_j;
+    LC.jobs_dev = ca.jobs + first_job; LC.n_jobs_host = std::min<int64_t>(parts * (int64_t)ca.cap_j, wg_bound); LC.n_jobs_dev = count; LC.jobs_bound = parts * (int64_t)ca.cap_j;
     LC.pat_base = d_reads; LC.txt_base = d_reads; LC.max_plen = max_seg; LC.max_tlen = max_seg; LC.max_sum = 2 * (int64_t)max_seg;
     LC.cigar = (uint32_t*)d_cig; LC.cigar_len = (uint32_t*)d_clen; LC.buffer_set = 2; LC.ws_budget = 512ull << 20; LC.refused = ca.counts + cl::CC_REFUSED;
     if (int r = wfa_launch(c, wco, LC)) return r;
@@ -1436,15 +1448,22 @@ int LocusCall::cluster_chain(int deep) {
     // ---- genotype_flank's tag branch for the loci the chain completed with two close alleles: settled at once, or behind a third
     //      consensus round over the third part of the lists (usually short: the groups without a majority sequence)
     void *d_fc = nullptr, *d_fp = nullptr;
-    if ((rc = dev_get(c, S_CLF_PEND, (size_t)n_cl * sizeof(clf::ClFlankPend), &d_fp))) return rc;
+    if ((rc = dev_get(c, S_CLF_PEND, (size_t)n_cl * (sizeof(clf::ClFlankPend) + (snv_route ? 8 : 0)), &d_fp))) return rc;  // (SNV forms: pend_hap behind the records)
     void* const z_cfc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
     if (!z_cfc && (rc = dev_get(c, S_CLF_COUNTS, 256, &d_fc))) return rc;
     clf::ClFlankArgs fa{ca, g.hp, (uint8_t*)slab.d(o_fdone), z_cfc ? (uint32_t*)z_cfc : (uint32_t*)d_fc, (clf::ClFlankPend*)d_fp, 2 * ca.cap_j, 2 * ca.cap_g};
     if (!z_cfc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, fa.fcounts, (uint32_t)clf::CF_WORDS);
-    k_cluster_flank.launch(big, presel, cgrid, c->stream, fa);
+    clf::ClSnvArgs sa;
+    if (snv_route) {  // (the three logarithms are the host's: flank_split's own)
+      static_cast<clf::ClFlankArgs&>(sa) = fa;
+      sa.start_offset = g.so; sa.end_offset = g.eo; sa.mismatch_offsets = g.mm; sa.mismatch_off = g.mm_off; sa.snv_read = (uint8_t*)g.snv_read; sa.pend_hap = (int32_t*)((clf::ClFlankPend*)d_fp + n_cl);
+      sa.ln_match = std::log(0.9); sa.ln_mis = std::log(1.0 - 0.9); sa.ln2 = std::log(2.0); sa.tag_route = flank_cl_dev ? 1 : 0;
+      k_cluster_flank_snv.launch(big, presel, cgrid, c->stream, sa);
+    } else k_cluster_flank.launch(big, presel, cgrid, c->stream, fa);
     TRGT_HIP_TRY(c, hipGetLastError());
-    if ((rc = cons_launch(2 * ca.cap_j, fa.fcounts + clf::CF_J3, 2 * ca.cap_g, fa.fcounts + clf::CF_G3))) return rc;
-    k_cluster_flank_finish.launch(big, presel, cgrid, c->stream, fa);
+    if ((rc = cons_launch(2 * ca.cap_j, fa.fcounts + clf::CF_J3, 2 * ca.cap_g, fa.fcounts + clf::CF_G3, snv_route ? 2 : 1))) return rc;
+    if (snv_route) k_cluster_flank_finish_snv.launch(big, presel, cgrid, c->stream, sa);
+    else k_cluster_flank_finish.launch(big, presel, cgrid, c->stream, fa);
     TRGT_HIP_TRY(c, hipGetLastError());
     TRGT_HIP_TRY(c, hipMemcpyAsync(slab.d(o_cfc), fa.fcounts, clf::CF_WORDS * 4, hipMemcpyDeviceToDevice, c->stream));  // (the counts come back with the slab)
   }
@@ -1525,8 +1544,18 @@ int LocusCall::wait_stage_a() {
         FlankSplit sp;
         if (flank_split(flank_meta, order.data(), order.size(), sp)) { need[l] = 1; sent += 1; }
       });
-      if (cf_route) {  // trgt_hip_flank_cluster_stats
+      if (cf_snv) {  // trgt_hip_snv_cluster_stats: the bytes the SNV branch of the route left
         for (const uint32_t l : cl_list) {
+          const uint8_t b = fdone[l];
+          if (!(b & gt::FL_SNV)) continue;
+          if ((b & gt::FL_DONE) && !need[l]) { c->snv_cluster_stats[0] += 1; if (b & gt::FL_REPAIRED) c->snv_cluster_stats[1] += 1; }
+          else if (b & gt::FL_UNDECIDED) c->snv_cluster_stats[3] += 1;
+          else if (b & gt::FL_HANDED) c->snv_cluster_stats[2] += 1;
+        }
+      }
+      if (cf_route) {  // trgt_hip_flank_cluster_stats (never a locus of the SNV branch)
+        for (const uint32_t l : cl_list) {
+          if (fdone[l] & gt::FL_SNV) continue;  // trgt_hip_snv_cluster_stats'
           if ((fdone[l] & gt::FL_DONE) && !need[l]) { c->flank_cluster_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_cluster_stats[1] += 1; }
           else if (fdone[l] == gt::FL_HANDED) c->flank_cluster_stats[2] += 1;
         }
@@ -2229,6 +2258,16 @@ extern "C" int trgt_hip_snv_split_stats(const trgt_hip_ctx* c, int64_t out[4]) {
 }
 
 // ---- ... and behind the one-wave cluster chain, a setting of its own (locus_cluster_flank.hpp)
+extern "C" int trgt_hip_set_snv_cluster_device(trgt_hip_ctx* c, int on) {
+  if (!c) return TRGT_ERR_INVALID;
+  c->snv_cluster_device = on != 0;
+  return TRGT_OK;
+}
+extern "C" int trgt_hip_snv_cluster_stats(const trgt_hip_ctx* c, int64_t out[4]) {
+  if (!c) return TRGT_ERR_INVALID;
+  for (int i = 0; i < 4; ++i) out[i] = c->snv_cluster_stats[i];
+  return TRGT_OK;
+}
 extern "C" int trgt_hip_set_flank_cluster_device(trgt_hip_ctx* c, int on) {
   if (!c) return TRGT_ERR_INVALID;
   c->flank_cluster_device = on != 0;

@@ -463,12 +463,28 @@ __device__ __forceinline__ double snv_candidate_ll(const A& a, int n, int ns, ui
   return ll;
 }
 
-template <int MAXR, class SH>
-__device__ __forceinline__ bool snv_route(SH& sh, const SnvArgs& a, int64_t l, uint64_t r0, int n, int nu, int lane, bool fits, uint32_t refn, uint64_t refo) {
+// The route is stated once, for the one-wave size genotyper and for the SNV forms behind the one-wave cluster chain
+// (locus_cluster_flank.hpp).  sh: the route's LDS -- an SnvShared<MAXR, true> block beside the kept reads (s_read) and the assignment (cls);
+// a: the route's arguments -- start_offset / end_offset (NULL = 0 for every read), mismatch_offsets / mismatch_off, and the three
+// host-rounded logarithms ln_match, ln_mis, ln2.  END says how the route ends for its caller, and its results are snv_route's:
+//   END::nosplit(sh, a, l, lane)       no split
+//   END::handed(sh, a, l, lane, why)   beyond one of the three limits (why = 0) or not decided beyond the margin (FL_UNDECIDED)
+//   END::split(sh, a, l, lane, cnt, hap)   the assignment is in sh.cls, sh.v_tie marks the reads that belong to both groups, cnt[g]
+//                                      members and hap[g] assigned reads of either group (a group may be empty: no split)
+// SizeEnd is the size genotyper's (the byte of the locus, sh.bail); its split is flank_tail, which stays where it was, inside snv_route
+// (END::SIZE): the figures of the four SNV forms of locus_genotype_kernel move when it is called from anywhere else (two SGPR spills of
+// one of them; profiles/snv_cluster_resource_usage.txt).  nu, fits, refn, refo are read by that tail only.
+struct SizeEnd {
+  static constexpr bool SIZE = true;
+  template <class SH> static __device__ __forceinline__ bool nosplit(SH&, const SnvArgs& a, int64_t l, int lane) { if (lane == 0) a.flank_done[l] = FL_NOSPLIT | FL_SNV; return false; }
+  template <class SH> static __device__ __forceinline__ bool handed(SH& sh, const SnvArgs& a, int64_t l, int lane, uint8_t why) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED | FL_SNV | why; return true; }
+};
+template <int MAXR, class END = SizeEnd, class SH, class A>
+__device__ __forceinline__ bool snv_route(SH& sh, const A& a, int64_t l, uint64_t r0, int n, int nu, int lane, bool fits, uint32_t refn, uint64_t refo) {
   constexpr int CAP = SNV_OFFS_PER_READ * MAXR;
   static_assert(CAP / 64 <= 32, "one bit per owned entry in `called`");
-  auto nosplit = [&]() { if (lane == 0) a.flank_done[l] = FL_NOSPLIT | FL_SNV; return false; };
-  auto handed = [&](uint8_t why) { sh.bail = 1; if (lane == 0) a.flank_done[l] = FL_HANDED | FL_SNV | why; return true; };
+  auto nosplit = [&]() { return END::nosplit(sh, a, l, lane); };
+  auto handed = [&](uint8_t why) { return END::handed(sh, a, l, lane, why); };
   // ---- get_analysis_region (:206-226): the skip-th largest start offset, the skip-th smallest end offset, by rank
   const int skip = (int)round((double)n * (1.0 - 0.85));
   if (skip >= n) return nosplit();
@@ -617,12 +633,14 @@ __device__ __forceinline__ bool snv_route(SH& sh, const SnvArgs& a, int64_t l, u
     ties += __popcll(tb);
   }
   __syncthreads();
-  if (!flank_tail<SnvMembers>(sh, a, l, n, nu, lane, fits, refn, refo, cnt, hap, (uint8_t)FL_SNV)) return nosplit();
-  // a locus that waits for the repair chain leaves its split behind: flank_finish reads it and does not recompute it
-  if (sh.bail == 2)
-    for (int i = lane; i < n; i += 64)
-      a.snv_read[r0 + i] = (uint8_t)((sh.cls[i] ? SR_ASSIGN : 0) | (SnvMembers::in(sh, i, 0) ? SR_IN0 : 0) | (SnvMembers::in(sh, i, 1) ? SR_IN1 : 0));
-  return true;
+  if constexpr (END::SIZE) {
+    if (!flank_tail<SnvMembers>(sh, a, l, n, nu, lane, fits, refn, refo, cnt, hap, (uint8_t)FL_SNV)) return nosplit();
+    // a locus that waits for the repair chain leaves its split behind: flank_finish reads it and does not recompute it
+    if (sh.bail == 2)
+      for (int i = lane; i < n; i += 64)
+        a.snv_read[r0 + i] = (uint8_t)((sh.cls[i] ? SR_ASSIGN : 0) | (SnvMembers::in(sh, i, 0) ? SR_IN0 : 0) | (SnvMembers::in(sh, i, 1) ? SR_IN1 : 0));
+    return true;
+  } else return END::split(sh, a, l, lane, cnt, hap);
 }
 
 template <int MAXR, int SEG, bool PRESEL = false, bool FLANK = false, bool SNV = false>
