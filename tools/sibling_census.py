@@ -14,6 +14,13 @@ by a shortcut (one or two substitutions on one diagonal, one inserted or deleted
 pre-filter.  The last rows count the jobs without seeds whose sibling is settled by a shortcut and leaves them fewer than min_matches
 bases -- what settled_sibling_kernel drops, to hold the device's TRGT_WFA_DEBUG count against (reads beyond the dedicated kernels' text
 length, which the device keeps on a list of their own, are not modelled: a few dozen jobs on cfg4, none on cfg2).
+
+The common-subsequence rule (lcs_rule_kernel) then looks at the jobs without seeds that are left beside a sibling whose span is known --
+found exactly, or settled by a shortcut: an alignment of the missed piece that stays inside Adm has at most LCS(piece, read[Adm])
+matches, so with LCS < min_matches the read has no span.  lcs_bound() / lcs_rule_drops() restate it (Python integers as bit vectors,
+bytes outside ACGT match everything, |Adm| <= LCS_MAX_ADM); the rows give what it certifies beside either kind of sibling, the share of
+the jobs without seeds and of their strips, the certified jobs by |Adm| WITHOUT the cap (what LCS_MAX_ADM was chosen from), and what the
+same bound would certify among the light jobs (not built).
 """
 import argparse
 import math
@@ -88,11 +95,65 @@ def settled_rule_drops(read, pieces, side, plan, min_matches):
     return (len(read) - sib[2] if side else sib[1]) < min_matches
 
 
+LCS_MAX_ADM = 352  # spans.hip: beyond this the bound certifies fewer than 1 % of what it certifies at all (cfg2)
+LCS_MAX_F = 256    # the kernel's bit vector: eight dwords
+
+
+def lcs_bound(piece, text):
+    """length of the longest common subsequence of piece and text, bit-parallel as lcs_rule_kernel computes it: one bit per base of the
+    piece, per text byte u = V & Peq[c]; V = (V + u) | (V - u); the zero bits of V are the LCS.  A byte outside ACGT, in the piece or in
+    the text, matches everything (that can only raise the bound)"""
+    F = len(piece)
+    ones = (1 << F) - 1
+    peq = {c: 0 for c in b"ACGT"}
+    for i, ch in enumerate(piece):
+        for c in peq:
+            if ch == c or ch not in peq:
+                peq[c] |= 1 << i
+    v = ones
+    for ch in text:
+        u = v & peq.get(ch, ones)
+        v = ((v + u) | (v - u)) & ones
+    return F - bin(v).count("1")
+
+
+def admissible(read, side, span):
+    """the part of the read an alignment of the missed piece `side` can count in, beside a sibling with text span [st, en)"""
+    return read[span[1]:] if side else read[:span[0]]
+
+
+def lcs_rule_drops(read, piece, side, span, min_matches, cap=LCS_MAX_ADM):
+    """the rule of lcs_rule_kernel for a missed piece beside a sibling whose text span (st, en) is known: True when
+    min_matches <= |Adm| <= cap, the piece fits the bit vector and LCS(piece, read[Adm]) < min_matches"""
+    adm = admissible(read, side, span)
+    if len(piece) > LCS_MAX_F or not min_matches <= len(adm) <= cap:
+        return False
+    return lcs_bound(piece, adm) < min_matches
+
+
+def known_sibling_span(read, pieces, side, plan):
+    """((st, en), kind) of the sibling of the missed piece `side` where the device knows it without a race: "exact" (the scan found it,
+    leftmost occurrence) or "settled" (the front seed search's shortcuts); (None, None) otherwise"""
+    other = pieces[side ^ 1]
+    p = read.find(other)
+    if p >= 0:
+        return (p, p + len(other)), "exact"
+    sib = front_search(read, other, plan)
+    return ((sib[1], sib[2]), "settled") if sib[0] == "settled" else (None, None)
+
+
+def lcs_rule_job_drops(read, pieces, side, plan, min_matches, cap=LCS_MAX_ADM):
+    """the rule over one job of the list without seeds: the kind of sibling ("exact" / "settled") when it drops the job, else None"""
+    span, kind = known_sibling_span(read, pieces, side, plan)
+    return kind if span is not None and lcs_rule_drops(read, pieces[side], side, span, min_matches, cap) else None
+
+
 def census(config, n_loci, F=250, frac=0.7, scoring=(2, 5, 1)):
     b = synth.generate(n_loci, first_locus=0, config=config)
     min_matches = int(math.ceil(F * frac))
     plan = seed_plan(F, *scoring)
     front = dict(settled=0, window=0, noseed=0, noseed_drop=0, strips=0, strips_drop=0)
+    lcs = dict(exact=0, settled=0, strips=0, known=0, by_adm={}, seen_by_adm={}, light_seen=0, light_cert=0)
     blob, flank = b["read_blob"].tobytes(), b["flank_blob"].tobytes()
     jobs = dict(all=0, heavy=0, heavy_sibling=0, light=0, light_sibling=0, light_drop=0)
     hist = dict(drop=0, below_F=0)
@@ -117,6 +178,9 @@ def census(config, n_loci, F=250, frac=0.7, scoring=(2, 5, 1)):
                     jobs["light"] += 1
                     jobs["light_sibling"] += adm is not None
                     jobs["light_drop"] += adm is not None and adm < min_matches
+                    if adm is not None and min_matches <= adm <= LCS_MAX_ADM:  # (reported, not built: the rule runs over the expensive list only)
+                        lcs["light_seen"] += 1
+                        lcs["light_cert"] += lcs_rule_drops(read, pieces[side], side, (sib, sib + F), min_matches)
                     continue
                 jobs["heavy"] += 1
                 now = (F + n + 1 + 255) // 256
@@ -129,6 +193,18 @@ def census(config, n_loci, F=250, frac=0.7, scoring=(2, 5, 1)):
                         if sib < 0 and settled_rule_drops(read, pieces, side, plan, min_matches):
                             front["noseed_drop"] += 1
                             front["strips_drop"] += now
+                        else:  # the jobs settled_sibling_kernel leaves: the common-subsequence rule where the sibling's span is known
+                            span, sib_kind = known_sibling_span(read, pieces, side, plan)
+                            if span is not None:
+                                lcs["known"] += 1
+                                room = len(admissible(read, side, span))
+                                bin_ = room // 32 * 32
+                                lcs["seen_by_adm"][bin_] = lcs["seen_by_adm"].get(bin_, 0) + 1
+                                if lcs_rule_drops(read, pieces[side], side, span, min_matches, cap=1 << 30):
+                                    lcs["by_adm"][bin_] = lcs["by_adm"].get(bin_, 0) + 1
+                                    if room <= LCS_MAX_ADM:
+                                        lcs[sib_kind] += 1
+                                        lcs["strips"] += now
                 if adm is None:
                     continue
                 jobs["heavy_sibling"] += 1
@@ -140,7 +216,7 @@ def census(config, n_loci, F=250, frac=0.7, scoring=(2, 5, 1)):
                 k = (F + max(adm, F) + 1 + 255) // 256
                 strips_adm[k] = strips_adm.get(k, 0) + 1
                 strips_now[k] = strips_now.get(k, 0) + now
-    return dict(config=config, n_loci=n_loci, n_reads=int(b["n_reads"]), min_matches=min_matches, jobs=jobs, hist=hist, front=front, strips_adm=strips_adm,
+    return dict(config=config, n_loci=n_loci, n_reads=int(b["n_reads"]), min_matches=min_matches, jobs=jobs, hist=hist, front=front, lcs=lcs, strips_adm=strips_adm,
                 strips_now=strips_now, strips_now_all=strips_now_all)
 
 
@@ -171,6 +247,17 @@ def main():
         print("    of those without seeds: sibling settled by a shortcut, |Adm| < min_matches (settled-sibling rule): %d (%s)"
               % (f["noseed_drop"], pct(f["noseed_drop"], f["noseed"])))
         print("    their 256-diagonal strips of the whole read: %d of %d (%s)" % (f["strips_drop"], f["strips"], pct(f["strips_drop"], f["strips"])))
+        q = c["lcs"]
+        cert = q["exact"] + q["settled"]
+        print("    of the others, sibling span known (exact or settled): %d; LCS(piece, read[Adm]) < min_matches with |Adm| <= %d (common-subsequence rule): "
+              "%d beside an exact sibling, %d beside a settled one (%s of those without seeds)" % (q["known"], LCS_MAX_ADM, q["exact"], q["settled"], pct(cert, f["noseed"])))
+        print("    their 256-diagonal strips of the whole read: %d of %d (%s)" % (q["strips"], f["strips"], pct(q["strips"], f["strips"])))
+        total = sum(q["by_adm"].values())
+        print("    certified without the cap, by |Adm| (jobs seen / certified / share of all certified):")
+        for k in sorted(q["seen_by_adm"]):
+            n = q["by_adm"].get(k, 0)
+            print("      %4d-%4d: %6d %6d  %s" % (k, k + 31, q["seen_by_adm"][k], n, pct(n, total)))
+        print("  light jobs beside an exact sibling with min_matches <= |Adm| <= %d: %d, of those LCS < min_matches: %d (not built)" % (LCS_MAX_ADM, q["light_seen"], q["light_cert"]))
         print("  strips summed over the expensive jobs, whole reads: %d (%.2f per job)" % (c["strips_now_all"], c["strips_now_all"] / max(j["heavy"], 1)))
 
 

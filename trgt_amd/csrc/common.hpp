@@ -47,6 +47,7 @@ struct trgt_knobs {
   bool no_heavy_window = false;  // TRGT_NO_HEAVY_WINDOW: the expensive fallback alignments go to the pre-filter without the seed search first
   bool no_sibling_rule = false;  // TRGT_NO_SIBLING_RULE (DEV): the scan emits a fallback job for every missed flank piece, also where the exactly found sibling leaves it no room to count (spans.hip, ScanArgs::min_matches)
   bool no_settled_sibling_rule = false;  // TRGT_NO_SETTLED_SIBLING_RULE (DEV): ... but a missed piece beside a sibling the seed search's shortcuts settled still meets the pre-filter (spans.hip, settled_sibling_kernel)
+  bool no_lcs_rule = false;  // TRGT_NO_LCS_RULE (DEV): ... and a missed piece whose longest common subsequence with the read beside a known sibling span is below min_matches still meets it (spans.hip, lcs_rule_kernel)
   bool no_indel_shortcut = false;  // TRGT_NO_INDEL_SHORTCUT: one-base gaps are aligned (the substitution shortcut stays)
   bool no_hamming = false;   // TRGT_NO_HAMMING: no substitution-only shortcut in the window search (every light fallback is aligned)
   bool no_filter = false;    // TRGT_WFA_NO_FILTER: no pre-filter in front of the expensive alignments

@@ -46,8 +46,9 @@ enum SpanCount : int {
   SC_WINCLAIM = 17, // job claims of the register kernel over the windowed list (wfa_win.hip)
   SC_WINFALL = 18,  // windowed alignments that kernel did not take (sequences beyond its staging buffers): they go on to the whole-read launch
   SC_SETDROP = 19,  // of SC_NOSEED: jobs the pre-filter never sees, the sibling the shortcuts settled leaves them fewer than min_matches bases (settled_sibling_kernel)
-  SC_FILTER = 20,   // ... the others: the pre-filter's list where that rule is on
-  SC_WORDS = 21
+  SC_FILTER = 20,   // ... the others: the pre-filter's list where that rule or the next is on
+  SC_LCSDROP = 21,  // of SC_NOSEED: jobs the pre-filter never sees, their piece has no common subsequence of min_matches bases with the read beside a known sibling span (lcs_below)
+  SC_WORDS = 22
 };
 
 struct ScanArgs {
@@ -564,29 +565,131 @@ __global__ void __launch_bounds__(256) flank_scan_wide_kernel(const ScanArgs a) 
 // n_match and span4 of OTHER jobs of that list at the same time: nothing is read here but the settled mark, which only the front
 // seed search writes, and the span4 entry it stands for.  One thread per job of the list without seeds; the jobs that stay are
 // compacted (one atomic per wave) into the pre-filter's list, a dropped job keeps n_match = -1 as after the scan's drop.
+//
+// ---- ... and the common-subsequence rule, in the same pass ----
+// |Adm| is the crudest bound on count_matches() of an alignment inside the admissible region Adm; the sharp one costs about one level
+// of the pre-filter.  The matched bases of an alignment of the piece P that stays inside Adm are, in order, a common subsequence of P
+// and T[Adm], so count_matches() <= LCS(P, T[Adm]); an alignment that leaves Adm is discordant as before.  With LCS(P, T[Adm]) <
+// min_matches the read's span is None whatever the aligner returns -- no tie-breaking, no wavefront enters the argument -- and the job
+// is dropped like the others (n_match stays -1).  The sibling's span must be the reference's and must be readable without a race: found
+// exactly (pos[sib] >= 0: the scan wrote it, nothing writes it again) or settled by a shortcut (the mark and its span4 entry, as above;
+// only where the settled rule is on, a.settled is NULL otherwise).  A byte outside ACGT, in the piece or in the read, counts as
+// matching everything, which can only raise the bound.  Pieces of up to LCS_MAX_F bases, regions of min_matches .. lcs_max_adm bases:
+// beyond LCS_MAX_ADM the bound hardly ever certifies anything (the census of tools/sibling_census.py) and the
+// pass would only be longer.
+constexpr int LCS_MAX_F = 256, LCS_MAX_ADM = 352;
 struct SettledArgs {
   const JobDev* jobs; const uint32_t* n_jobs;  // the expensive jobs without seeds (count[SC_NOSEED])
-  JobDev* out; uint32_t* count;                // the jobs that stay, under count[SC_FILTER]; the others are tallied in count[SC_SETDROP]
-  const uint8_t* settled; const uint32_t* span4; int32_t min_matches;
+  JobDev* out; uint32_t* count;                // the jobs that stay, under count[SC_FILTER]; the others are tallied in count[SC_SETDROP] / count[SC_LCSDROP]
+  const uint8_t* settled; const uint32_t* span4; int32_t min_matches;  // (settled NULL: the settled rule is off, and so is everything beside a settled sibling)
+  int32_t lcs_max_adm;  // > 0: the common-subsequence rule, over regions of up to this many bases
+  const int32_t* pos; const uint8_t* flank_blob; const uint8_t* read_blob;
 };
-__global__ void __launch_bounds__(256) settled_sibling_kernel(const SettledArgs a) {
+// Is the longest common subsequence of pat[0, F) and txt[0, n) shorter than min_matches?  Bit-parallel (Crochemore et al. 2001, Hyyro
+// 2004): one bit per base of the piece in eight dwords, V all ones, per text byte u = V & Peq[c]; V = (V + u) | (V - u), where V - u
+// is V & ~u (u is a subset of V: no borrow); the LCS is the number of zero bits among the low F.  The bits from F up are in no mask:
+// V & ~u keeps them set whatever carry the sum sends through them, so the zero bits of all 256 are counted.  One thread per job: V in
+// registers (the loops over its dwords are unrolled), the five masks -- A, C, T, G and "any other byte", which is every base of the
+// piece -- in the thread's own column of LDS (peq[c][w][lane]: conflict-free, and never shared, so no barrier).  The piece comes in 32
+// bases per round, the text in sixteen, the next sixteen loaded ahead of the 16 x ~50 instructions over the current ones.  F <= 256;
+// nothing is read outside the two ranges.
+constexpr int LCS_ROWS = 5;
+// the mask row of a byte, without a branch: bits 1-2 of 'A', 'C', 'T', 'G' are 0, 1, 2, 3; any other byte (lower case too) has row 4
+__device__ __forceinline__ uint32_t lcs_row(uint32_t c) {
+  const uint32_t code = (c >> 1) & 3u;
+  return ((0x47544341u >> (8u * code)) & 0xFFu) == c ? code : 4u;
+}
+__device__ __forceinline__ void lcs_step(uint32_t (&V)[8], const uint32_t (*peq)[8][64], uint32_t lane, uint32_t c) {
+  const uint32_t row = lcs_row(c);
+  uint32_t m[8], carry = 0;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) m[w] = peq[row][w][lane];
+#pragma unroll
+  for (int w = 0; w < 8; ++w) {
+    const uint32_t u = V[w] & m[w];
+    const uint32_t sum = __builtin_addc(V[w], u, carry, &carry);
+    V[w] = sum | (V[w] & ~u);
+  }
+}
+__device__ __forceinline__ bool lcs_below(uint32_t (*peq)[8][64], uint32_t lane, const uint8_t* __restrict__ pat, int F, const uint8_t* __restrict__ txt, int n, int min_matches) {
+  for (int w = 0; w < 8; ++w) {  // the masks of bases [32 w, 32 w + 32) of the piece
+    uint32_t x[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int b0 = w * 32 + q * 4;
+      x[q] = 0;
+      if (b0 + 4 <= F) x[q] = load_u32(pat + b0);
+      else
+        for (int k = 0; b0 + k < F; ++k) x[q] |= (uint32_t)pat[b0 + k] << (8 * k);
+    }
+    uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const uint32_t row = lcs_row((x[q] >> (8 * k)) & 0xFFu), sel = (1u << row) | (0u - (row >> 2));  // one mask, or all four
+        m0 |= (sel & 1u) << (q * 4 + k); m1 |= ((sel >> 1) & 1u) << (q * 4 + k); m2 |= ((sel >> 2) & 1u) << (q * 4 + k); m3 |= ((sel >> 3) & 1u) << (q * 4 + k);
+      }
+    const uint32_t valid = F >= (w + 1) * 32 ? 0xFFFFFFFFu : (F > w * 32 ? (1u << (F - w * 32)) - 1u : 0u);  // (the zero bytes behind the piece are no bases)
+    peq[0][w][lane] = m0 & valid; peq[1][w][lane] = m1 & valid; peq[2][w][lane] = m2 & valid; peq[3][w][lane] = m3 & valid; peq[4][w][lane] = valid;
+  }
+  uint32_t V[8];
+#pragma unroll
+  for (int w = 0; w < 8; ++w) V[w] = 0xFFFFFFFFu;
+  const int full = n & ~15;
+  uint32_t cur[4] = {0, 0, 0, 0}, nxt[4] = {0, 0, 0, 0};
+  if (full) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cur[k] = load_u32(txt + 4 * k);
+  }
+  for (int i = 0; i < full; i += 16) {
+    if (i + 16 < full) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) nxt[k] = load_u32(txt + i + 16 + 4 * k);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+      for (int b = 0; b < 4; ++b) lcs_step(V, peq, lane, (cur[k] >> (8 * b)) & 0xFFu);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
+  }
+  for (int i = full; i < n; ++i) lcs_step(V, peq, lane, txt[i]);
+  int ones = 0;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) ones += __popc(V[w]);
+  return 256 - ones < min_matches;
+}
+__global__ void __launch_bounds__(64) settled_sibling_kernel(const SettledArgs a) {  // (64: one wave, lcs_below's LDS columns are per lane)
+  __shared__ uint32_t l_peq[LCS_ROWS][8][64];
   const uint32_t n = *a.n_jobs, lane = threadIdx.x & 63u;
   for (uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) & ~63u; i0 < n; i0 += gridDim.x * blockDim.x) {  // (i0: uniform per wave)
     const uint32_t i = i0 + lane;
-    bool stay = false, drop = false;
+    bool stay = false, drop = false, lcs = false;
     JobDev jd;
     if (i < n) {
       jd = a.jobs[i];
       const uint32_t j = jd.out_index, sib = j ^ 1u;
-      int room = 0x7FFFFFFF;  // bases of the read on the far side of the sibling (txt_len: the whole read, these jobs have no window)
-      if (a.settled[sib]) room = (j & 1u) ? (int)jd.txt_len - (int)a.span4[4 * (uint64_t)sib + 3] : (int)a.span4[4 * (uint64_t)sib + 2];
-      drop = room < a.min_matches; stay = !drop;
+      int room = 0x7FFFFFFF, st = 0, en = 0;  // bases of the read on the far side of the sibling (txt_len: the whole read, these jobs have no window)
+      bool known = false;
+      if (a.settled && a.settled[sib]) {
+        st = (int)a.span4[4 * (uint64_t)sib + 2]; en = (int)a.span4[4 * (uint64_t)sib + 3]; known = true;
+        room = (j & 1u) ? (int)jd.txt_len - en : st;
+        drop = room < a.min_matches;
+      } else if (a.lcs_max_adm > 0) {
+        st = a.pos[sib]; en = st + (int)jd.pat_len; known = st >= 0;
+        if (known) room = (j & 1u) ? (int)jd.txt_len - en : st;
+      }
+      if (known && !drop && a.lcs_max_adm > 0 && jd.pat_len <= (uint32_t)LCS_MAX_F && room >= a.min_matches && room <= a.lcs_max_adm && (uint32_t)room <= jd.txt_len)
+        lcs = lcs_below(l_peq, lane, a.flank_blob + jd.pat_off, (int)jd.pat_len, a.read_blob + jd.txt_off + ((j & 1u) ? (uint32_t)en : 0u), room, a.min_matches);
+      stay = !drop && !lcs;
     }
-    const unsigned long long ms = __ballot(stay), md = __ballot(drop);
+    const unsigned long long ms = __ballot(stay), md = __ballot(drop), ml = __ballot(lcs);
     uint32_t base = 0;
     if (lane == 0) {
       if (ms) base = atomicAdd(a.count + SC_FILTER, (uint32_t)__popcll(ms));
       if (md) atomicAdd(a.count + SC_SETDROP, (uint32_t)__popcll(md));
+      if (ml) atomicAdd(a.count + SC_LCSDROP, (uint32_t)__popcll(ml));
     }
     base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
     if (stay) a.out[base + (uint32_t)__popcll(ms & ((1ull << lane) - 1ull))] = jd;
@@ -778,6 +881,8 @@ struct SpanPlan {
   bool split = false, use_filter = false, two_streams = false; int64_t flt_tlen = 0;
   bool heavy_window = false;  // the seed search runs over the expensive list as well
   bool settled_rule = false;  // ... and the sibling rule is applied once more to what that search leaves without seeds (SettledArgs)
+  int32_t lcs_max_adm = 0;    // ... as is the common-subsequence rule, over regions of up to this many bases (0: off)
+  bool sibling_pass = false;  // either of the two: settled_sibling_kernel compacts the list without seeds into the pre-filter's
   bool heavy_band = false;    // ... and what the pre-filter keeps of it is back-traced inside a band (BandArgs)
   bool long_window = false;   // the long reads' list goes through the light list's seed search
   bool long_filter = false, long_band = false; int64_t long_wl = 0, long_step = 0; uint64_t long_cap = 0;  // the window filter of the long reads (LongWinArgs)
@@ -853,6 +958,9 @@ static SpanPlan span_plan(const trgt_hip_ctx* c, const trgt_span_params& p, uint
     P.heavy_window = P.use_filter && P.two_streams && P.win_q > 0 && !k.no_heavy_window;
     // (on where the scan's rule is on -- callers that hand out hit bytes keep both off -- and a shortcut exists that could settle a sibling)
     P.settled_rule = P.heavy_window && P.scan_min_matches > 0 && P.hamming_max > 0 && !k.no_settled_sibling_rule;
+    // (the common-subsequence rule: on where the scan's rule is on; beside a settled sibling only where the settled rule is on too)
+    P.lcs_max_adm = P.heavy_window && P.scan_min_matches > 0 && p.flank_len <= LCS_MAX_F && !k.no_lcs_rule ? LCS_MAX_ADM : 0;
+    P.sibling_pass = P.settled_rule || P.lcs_max_adm > 0;
     P.heavy_band = P.use_filter && band_ok;
   }
   P.long_window = P.has_long && P.win_q > 0 && !k.no_long_window;  // shortcuts and windows do not care how long the read is
@@ -1040,13 +1148,16 @@ int SpanCall::heavy_list() {
     if ((rc = seed_search(true, noseed, nullptr))) return rc;
     TRGT_HIP_TRY(c, hipEventRecord(c->ev_hwin, c->stream));
     list = {noseed, count + SC_NOSEED};
-    if (plan.settled_rule) {  // (behind the event: the other stream's seed search does not wait for this)
+    if (plan.sibling_pass) {  // (behind the event: the other stream's seed search does not wait for this)
       JobDev* fjobs = nullptr;
       if ((rc = get(S_FS_FILTERJOBS, n_jobs * sizeof(JobDev), fjobs))) return rc;
       SettledArgs sg;
       sg.jobs = list.jobs; sg.n_jobs = list.count; sg.out = fjobs; sg.count = count;
-      sg.settled = settled; sg.span4 = span4; sg.min_matches = plan.scan_min_matches;
-      hipLaunchKernelGGL(settled_sibling_kernel, dim3(64), dim3(256), 0, c->stream, sg);
+      sg.settled = settled; sg.span4 = span4; sg.min_matches = plan.scan_min_matches;  // (settled: NULL where the settled rule is off)
+      sg.lcs_max_adm = plan.lcs_max_adm; sg.pos = pos; sg.flank_blob = d_flank; sg.read_blob = d_reads;
+      // one wave per workgroup: a wave of the common-subsequence rule runs for tens of microseconds and should have a SIMD to itself
+      const unsigned sgrid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)c->num_cus * 4, (n_jobs + 63) / 64));
+      hipLaunchKernelGGL(settled_sibling_kernel, dim3(sgrid), dim3(64), 0, c->stream, sg);
       TRGT_HIP_TRY(c, hipGetLastError());
       list = {fjobs, count + SC_FILTER};
     }
@@ -1177,6 +1288,7 @@ int SpanCall::debug_report() {  // (synchronises: developer output only)
   if (plan.has_long) fprintf(stderr, "[spans+] long reads kept by the window filter: back-traced inside a band %u, over the whole read %u\n", h[SC_LBAND], h[SC_LREST]);
   fprintf(stderr, "[spans+] sibling rule %s: %u missed pieces without a job (fewer than %d bases beside the exactly found sibling)\n", plan.scan_min_matches > 0 ? "on" : "off", h[SC_SIBDROP], plan.scan_min_matches);
   if (win && plan.heavy_window) fprintf(stderr, "[spans+] settled-sibling rule %s: %u jobs without seeds never met the pre-filter (fewer than %d bases beside a sibling the shortcuts settled)\n", plan.settled_rule ? "on" : "off", h[SC_SETDROP], plan.scan_min_matches);
+  if (win && plan.heavy_window) fprintf(stderr, "[spans+] common-subsequence rule %s: %u jobs without seeds never met the pre-filter (no common subsequence of %d bases with the %d to %d bases beside a sibling found exactly or settled by the shortcuts); %u met it\n", plan.lcs_max_adm > 0 ? "on" : "off", h[SC_LCSDROP], plan.scan_min_matches, plan.scan_min_matches, plan.lcs_max_adm, plan.sibling_pass ? h[SC_FILTER] : h[SC_NOSEED]);
   if (plan.heavy_band) fprintf(stderr, "[spans+] kept by the pre-filter: %u -> back-traced inside a band %u (did not stand: %u), over the whole read %u\n", h[SC_KEEP], h[SC_BAND], h[SC_BANDFAIL], h[SC_HREST]);
   return TRGT_OK;
 }
