@@ -134,7 +134,8 @@ int trgt_hip_flank_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
  * results: the SNV-clustering branch (get_trs_with_clustering), tried for the loci whose tags do not split the reads exactly as before
  * unless the context is also set with trgt_hip_set_snv_cluster_device (trgt_hip_flank_cluster.h: with both settings both branches run
  * behind the chain, tags first);
- * deep cluster loci (257 to 2048 reads on a context set with trgt_hip_set_cluster_max_reads), which the host redoes as before;
+ * deep cluster loci (257 to 2048 reads on a context set with trgt_hip_set_cluster_max_reads), which the host redoes as before
+ * unless the context is also set with trgt_hip_set_flank_cluster_deep_device (trgt_hip_flank_cluster.h, below);
  * contexts created under TRGT_HOST_CLUSTER or TRGT_HOST_GENOTYPER; and a locus on this route that finds no room in the chain's arenas,
  * whose repaired group overflows its slot, or that has an allele beyond allele_cap.  trgt_hip_flank_cluster_stats: of the context's
  * last trgt_locus_batch -- out[0] cluster loci whose genotype the device replaced by the tag split, out[1] those among them with at

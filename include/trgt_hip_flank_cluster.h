@@ -1,6 +1,6 @@
 /* trgt_hip_flank_cluster.h -- the entry points of genotype_flank behind the device cluster chain: the two of the haplotype-tag branch
  * (genotype_flank.rs:9-76, 147-170; tr.rs:64-75), which include/trgt_hip.h documents (what runs on the device, what stays on the host,
- * the three counts), and the two of the SNV branch, documented below.  Part of include/trgt_hip.h, which includes this file inside its
+ * the three counts), the two of the SNV branch and the two of the tag branch behind the deep chain, documented below.  Part of include/trgt_hip.h, which includes this file inside its
  * extern "C" block; not meant to be included on its own.  Additions to ABI 11. */
 #ifndef TRGT_HIP_FLANK_CLUSTER_H
 #define TRGT_HIP_FLANK_CLUSTER_H
@@ -22,7 +22,8 @@ int trgt_hip_flank_cluster_stats(const trgt_hip_ctx* ctx, int64_t out[3]);
  * read that agrees equally with both haplotypes is a member of both; consensus, intervals and the third consensus round follow the
  * membership, num_spanning and the classification the assignment.
  * What stays on the host, with the same results: deep cluster loci (257 to 2048 reads on a context set with
- * trgt_hip_set_cluster_max_reads), in both branches; contexts created under TRGT_HOST_CLUSTER or TRGT_HOST_GENOTYPER; searches not
+ * trgt_hip_set_cluster_max_reads), in both branches unless the context is also set with trgt_hip_set_flank_cluster_deep_device (below),
+ * which runs the tag branch for them; contexts created under TRGT_HOST_CLUSTER or TRGT_HOST_GENOTYPER; searches not
  * decided beyond the margin; loci beyond one of the three limits -- more than 64 called SNVs, more than 16 distinct fully observed
  * profiles, more than 8 in-region mismatch offsets per candidate read slot of the kernel form (512 / 2048 occurrences per locus for
  * the 64-read / 256-read forms); a locus on this route that finds no room in the chain's arenas, whose repaired group overflows its
@@ -34,4 +35,25 @@ int trgt_hip_flank_cluster_stats(const trgt_hip_ctx* ctx, int64_t out[3]);
  * trgt_hip_flank_cluster_stats counts the tag branch only, trgt_hip_snv_split_stats and trgt_hip_flank_stats never a cluster locus. */
 int trgt_hip_set_snv_cluster_device(trgt_hip_ctx* ctx, int on);
 int trgt_hip_snv_cluster_stats(const trgt_hip_ctx* ctx, int64_t out[4]);
+/* The haplotype-tag branch (genotype_flank.rs:9-76, 147-170; tr.rs:64-75) for DEEP cluster loci: Genotyper::Cluster loci of 257 to 2048
+ * candidate reads, which the seven-kernel deep chain genotypes on a context set with trgt_hip_set_cluster_max_reads.  A setting of its own,
+ * off by default and independent of the four others: it is not what trgt_hip_set_flank_cluster_device and
+ * trgt_hip_set_cluster_max_reads give together, and contexts with those two behave as they always did.  By default the host, where the
+ * tags split the reads of such a locus, redoes it from the start. */
+int trgt_hip_set_flank_cluster_deep_device(trgt_hip_ctx* ctx, int on);
+/* On a context set with on != 0 that also has a deep cluster chain, calls whose batch carries hp_tag run the tag branch behind that chain
+ * (locus_cluster_flank_deep.hpp, one workgroup per locus) for the loci of the deep list with ploidy 2 and two alleles at most 10 bases
+ * apart: assignment by tag with the rule of the deep size route, acceptance (both groups occur, 70 % of the kept reads tagged),
+ * simple_consensus of either group -- equal sequences found in the read blob through (length, hash) pairs and confirmed byte by byte --,
+ * a third consensus round of the deep list for a group without a majority sequence, smaller allele first, reference allele first.
+ * What stays on the host, with the same results: the SNV-clustering branch (get_trs_with_clustering) for deep cluster loci, tried for
+ * the loci whose tags do not split the reads exactly as before; loci beyond the context's cluster_max_reads setting or the ceiling of
+ * 2048 reads; deep loci that found no room in the call's pair budget; contexts created under TRGT_HOST_CLUSTER or TRGT_HOST_GENOTYPER;
+ * and the hand-backs -- a locus on this route that finds no room in the deep chain's arenas, whose repaired group overflows its slot, or
+ * that has an allele beyond allele_cap.
+ * trgt_hip_flank_cluster_deep_stats: of the context's last trgt_locus_batch -- out[0] deep cluster loci whose genotype the device
+ * replaced by the tag split, out[1] those among them with at least one repaired group, out[2] deep cluster loci on the route that the
+ * device handed back to the host path; all zero with the setting off, a batch without hp_tag or a call without a deep cluster list.
+ * These loci are in no other count: not in trgt_hip_flank_cluster_stats, not in trgt_hip_flank_stats, not in stats[23]. */
+int trgt_hip_flank_cluster_deep_stats(const trgt_hip_ctx* ctx, int64_t out[3]);
 #endif

@@ -88,6 +88,8 @@ CLUSTER_FLANK_EXPORTS = ["trgt_hip_set_flank_cluster_device", "trgt_hip_flank_cl
 # ... and the two of the SNV branch behind it, a third list checked the same way: tests/test_snv_deep_api.py pins the trgt_hip_*snv* names of
 # EXPORTS to the two of the size genotyper's setting, tests/test_flank_cluster_api.py the list above to its two.
 CLUSTER_SNV_EXPORTS = ["trgt_hip_set_snv_cluster_device", "trgt_hip_snv_cluster_stats"]
+# ... and the two of the tag branch behind the DEEP cluster chain (locus_cluster_flank_deep.hpp), a list of its own for the same reasons
+CLUSTER_DEEP_FLANK_EXPORTS = ["trgt_hip_set_flank_cluster_deep_device", "trgt_hip_flank_cluster_deep_stats"]
 
 
 def build_extension(force=False, verbose=False, dev=False):
@@ -116,7 +118,7 @@ def lib():
         except ImportError:
             pass
         L = C.CDLL(_SO)
-        missing = [n for n in EXPORTS + CLUSTER_FLANK_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_SNV_EXPORTS if not hasattr(L, n)]
+        missing = [n for n in EXPORTS + CLUSTER_FLANK_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_SNV_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_DEEP_FLANK_EXPORTS if not hasattr(L, n)]
         if missing:
             raise TrgtHipError("%s does not export %s (stale build?)" % (_SO, ", ".join(missing)))
         L.trgt_hip_last_error.restype = C.c_char_p
@@ -141,6 +143,8 @@ def lib():
         L.trgt_hip_flank_cluster_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_set_snv_cluster_device.argtypes = [_VP, C.c_int]
         L.trgt_hip_snv_cluster_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
+        L.trgt_hip_set_flank_cluster_deep_device.argtypes = [_VP, C.c_int]
+        L.trgt_hip_flank_cluster_deep_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_timing_enable.argtypes = [_VP, C.c_int]
         L.trgt_hip_timing_reset.argtypes = [_VP]
         L.trgt_hip_timing_get.argtypes = [_VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -252,6 +256,20 @@ class Context:
         self.check(lib().trgt_hip_flank_cluster_stats(self.handle, out))
         return tuple(int(v) for v in out)
 
+    def set_flank_cluster_deep_device(self, on=True):
+        """trgt_hip_set_flank_cluster_deep_device: the haplotype-tag branch of genotype_flank behind the DEEP cluster chain, for the
+        Genotyper::Cluster loci of 257 to set_cluster_max_reads candidate reads of batches that carry hp_tag (off, the default: the host
+        redoes such a locus).  It follows the deep chain, so it does nothing on a context without set_cluster_max_reads.  Independent of
+        set_flank_cluster_device and set_snv_cluster_device.  Every later call on this context uses it."""
+        self.check(lib().trgt_hip_set_flank_cluster_deep_device(self.handle, int(bool(on))))
+
+    def flank_cluster_deep_stats(self):
+        """trgt_hip_flank_cluster_deep_stats of the context's last trgt_locus_batch: (deep cluster loci whose genotype the device replaced
+        by the tag split, those among them with a repaired group, deep cluster loci on the route handed back to the host path)."""
+        out = (C.c_int64 * 3)()
+        self.check(lib().trgt_hip_flank_cluster_deep_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
     def set_snv_cluster_device(self, on=True):
         """trgt_hip_set_snv_cluster_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) behind the one-wave cluster
         chain, for the Genotyper::Cluster loci of at most 256 candidate reads of batches that carry mismatch offsets; tags that split the
@@ -293,7 +311,7 @@ class Context:
 class Pool:
     """trgt_hip_pool: several contexts (devices[i] = ordinal of context i, ordinals may repeat) behind one queue of batches."""
 
-    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, snv_split_device=None, snv_cluster_device=None):
+    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, flank_cluster_deep_device=None, snv_split_device=None, snv_cluster_device=None):
         L = lib()
         L.trgt_hip_pool_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
         L.trgt_hip_pool_destroy.argtypes = [C.c_void_p]
@@ -329,6 +347,9 @@ class Pool:
         if flank_cluster_device is not None:
             for c in self.contexts:
                 c.set_flank_cluster_device(flank_cluster_device)
+        if flank_cluster_deep_device is not None:
+            for c in self.contexts:
+                c.set_flank_cluster_deep_device(flank_cluster_deep_device)
         if snv_split_device is not None:
             for c in self.contexts:
                 c.set_snv_split_device(snv_split_device)

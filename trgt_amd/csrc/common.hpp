@@ -120,6 +120,8 @@ struct trgt_hip_ctx {
   bool snv_cluster_device = false;  // trgt_hip_set_snv_cluster_device: the SNV branch behind that chain (the SNV forms of locus_cluster_flank.hpp)
   int64_t snv_cluster_stats[4] = {0, 0, 0, 0};  // trgt_hip_snv_cluster_stats: cluster loci of the last trgt_locus_batch, counted like snv_split_stats
   int64_t flank_cluster_stats[3] = {0, 0, 0};  // trgt_hip_flank_cluster_stats: cluster loci of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, handed back to the host path)
+  bool flank_cluster_deep_device = false;  // trgt_hip_set_flank_cluster_deep_device: the same branch behind the deep cluster chain (locus_cluster_flank_deep.hpp)
+  int64_t flank_cluster_deep_stats[3] = {0, 0, 0};  // trgt_hip_flank_cluster_deep_stats: deep cluster loci of the last trgt_locus_batch, counted like flank_cluster_stats
   int num_cus = 256;
   // cached device buffers, indexed by slot
   struct Buf { void* p = nullptr; size_t cap = 0; };
@@ -285,6 +287,7 @@ enum Slot {
   S_SNV_DEEP,  // the workspace of the deep size list's SNV forms (locus_gt_deep.hpp): per-read masks and staged offsets, one slab
   S_CLF_COUNTS,  // the counters of the tag branch behind the one-wave cluster chain (locus_cluster_flank.hpp)
   S_CLF_PEND,    // ... and its records of the loci that wait for the third consensus round
+  S_CLDF_COUNTS, S_CLDF_PEND,  // the same two for the tag branch behind the deep cluster chain (locus_cluster_flank_deep.hpp)
   S_FS_SETTLED, S_FS_FILTERJOBS,  // flank location: the marks of what the seed search's shortcuts settled, and the pre-filter's list behind the settled-sibling rule (spans.hip)
   S_COUNT
 };

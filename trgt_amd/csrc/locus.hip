@@ -37,6 +37,7 @@
 #include "locus_cluster_deep.hpp"
 #include "locus_cluster_flank.hpp"
 #include "locus_gt_deep.hpp"
+#include "locus_cluster_flank_deep.hpp"
 #include "wfa_host.hpp"
 
 namespace trgt {
@@ -714,7 +715,7 @@ struct LocusCall {
   const int64_t nl; int64_t nr = 0; int F = 0;
   bool done = false;  // nothing left to do (a call without loci or without reads)
   trgt_locus_batch_in in_expanded; std::vector<uint64_t> expanded_off;  // TRGT_READS_BAM4: the batch with its reads expanded in HBM
-  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, snv_dev = false, flank_cl_dev = false, snv_cl_dev = false, cf_route = false, cf_snv = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
+  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, snv_dev = false, flank_cl_dev = false, snv_cl_dev = false, flank_cld_dev = false, cf_route = false, cf_snv = false, cfd_route = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
   FlankMeta flank_meta{};
   // ---- clean-up state (see the destructor)
   bool zeroed = false;
@@ -732,7 +733,7 @@ struct LocusCall {
   void *d_ss = nullptr, *d_se = nullptr, *d_hl = nullptr, *d_hr = nullptr, *h_ss = nullptr, *h_se = nullptr, *h_hl = nullptr, *h_hr = nullptr, *h_cells = nullptr;
   Slab slab;
   size_t o_ss = 0, o_se = 0, o_hl = 0, o_hr = 0, o_need = 0, o_nal = 0, o_alen = 0, o_ci = 0, o_nsp = 0, o_cls = 0, o_rank = 0, o_nspan = 0, o_toff = 0, o_flip = 0, o_gsz = 0,
-         o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0, o_fdone = 0, o_cfc = 0;
+         o_rpc = 0, o_skipb = 0, o_clc = 0, o_cldc = 0, o_fdone = 0, o_cfc = 0, o_cfdc = 0;
   GtDev g; GtHost gh;
   // ---- the device chains.  The cluster loci of the call: [0] the shallow list (at most GT_MAX_READS reads: the one-wave chain), [1] the
   // deep list (beyond that, up to the context's cluster_max_reads: locus_cluster_deep.hpp), each with its own pair slots, job lists, arenas
@@ -816,6 +817,7 @@ int LocusCall::check_args() {
   for (int64_t& v : c->size_deep_stats) v = 0;
   for (int64_t& v : c->flank_stats) v = 0;
   for (int64_t& v : c->flank_cluster_stats) v = 0;
+  for (int64_t& v : c->flank_cluster_deep_stats) v = 0;
   for (int64_t& v : c->snv_split_stats) v = 0;
   for (int64_t& v : c->snv_cluster_stats) v = 0;
   if (nl == 0) { done = true; return TRGT_OK; }
@@ -942,6 +944,11 @@ int LocusCall::upload_tables() {
   // ... and the SNV branch behind that chain (trgt_hip_set_snv_cluster_device), for a batch with mismatch offsets: the SNV forms of the
   // same two kernels, which take the place of the tag forms; flank_cl_dev then only says whose the tag branch inside them is
   snv_cl_dev = dev_gt && c->snv_cluster_device && in->mismatch_offsets != nullptr && in->mismatch_off != nullptr;
+  // ... and the tag branch behind the DEEP cluster chain (trgt_hip_set_flank_cluster_deep_device, a setting of its own again):
+  // locus_cluster_flank_deep.hpp.  Here: the context can have a deep cluster list at all (plan_device_lists decides which loci it holds;
+  // the route runs in cluster_chain(1), which is not reached with an empty list)
+  flank_cld_dev = dev_gt && c->flank_cluster_deep_device && in->hp_tag != nullptr && c->cluster_max_reads > gt::GT_MAX_READS && in->genotyper != nullptr &&
+                  !c->knobs.host_cluster && !c->knobs.split_hmm;
   int rc;
   if (ready) TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, ready, 0));
   if (staged_flank) d_flank = staged_flank;
@@ -964,8 +971,9 @@ int LocusCall::upload_tables() {
     o_nsp = slab.add(2 * (size_t)nl * 4); o_cls = slab.add((size_t)nr * 4); o_rank = slab.add((size_t)nr * 4); o_nspan = slab.add((size_t)nl * 4);
     o_toff = slab.add((2 * (size_t)nl + 1) * 8); o_flip = slab.add((size_t)nl);
     o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
-    if (flank_dev || flank_cl_dev || snv_dev || snv_cl_dev) o_fdone = slab.add((size_t)nl);
+    if (flank_dev || flank_cl_dev || snv_dev || snv_cl_dev || flank_cld_dev) o_fdone = slab.add((size_t)nl);
     if (flank_cl_dev || snv_cl_dev) o_cfc = slab.add(clf::CF_WORDS * 4);
+    if (flank_cld_dev) o_cfdc = slab.add(cldf::DF_WORDS * 4);
   }
   if ((rc = dev_get(c, S_LOCUS_4, slab.total, &slab.dev)) || (rc = pin_get(c, P_SPAN_S, slab.total, &slab.host))) return rc;
   d_ss = slab.d(o_ss); d_se = slab.d(o_se); d_hl = slab.d(o_hl); d_hr = slab.d(o_hr);
@@ -976,7 +984,7 @@ int LocusCall::upload_tables() {
         (rc = dev_in(c, S_GT_TRLEN, in->tr_len, (size_t)nl, &g.tr_len, &ub)) || (rc = dev_in(c, S_GT_ALOFF, out->allele_off, 2 * (size_t)nl, &g.al_off, &ub)) ||
         (rc = dev_in(c, S_GT_ALCAP, out->allele_cap, (size_t)nl, &g.al_cap, &ub)) || (in->genotyper && (rc = dev_in(c, S_GT_GENO, in->genotyper, (size_t)nl, &g.geno, &ub))) ||
         (presel && in->read_qual && (rc = dev_in(c, S_PUR_RQ, in->read_qual, (size_t)nr, &g.rq, &ub))) ||
-        ((flank_dev || flank_cl_dev || ((snv_dev || snv_cl_dev) && in->hp_tag)) && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
+        ((flank_dev || flank_cl_dev || flank_cld_dev || ((snv_dev || snv_cl_dev) && in->hp_tag)) && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
         ((snv_dev || snv_cl_dev) && ((in->start_offset && (rc = dev_in(c, S_SNV_SO, in->start_offset, (size_t)nr, &g.so, &ub))) ||
                      (in->end_offset && (rc = dev_in(c, S_SNV_EO, in->end_offset, (size_t)nr, &g.eo, &ub))) ||
                      (rc = dev_in(c, S_SNV_MMOFF, in->mismatch_off, (size_t)nr + 1, &g.mm_off, &ub)) ||
@@ -1365,7 +1373,10 @@ int LocusCall::cluster_chain(int deep) {
   const bool route = (!deep && flank_cl_dev) || snv_route;
   if (route) cf_route = true;  // (read by wait_stage_a)
   if (snv_route) cf_snv = true;
-  const uint64_t rounds = snv_route ? 4 : route ? 3 : 2;
+  // ... and the tag branch behind the deep chain (locus_cluster_flank_deep.hpp): a third round for the deep list, sized the same way
+  const bool deep_route = deep && flank_cld_dev;
+  if (deep_route) cfd_route = true;  // (read by wait_stage_a)
+  const uint64_t rounds = snv_route ? 4 : (route || deep_route) ? 3 : 2;
   // arenas for the consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
   ca.cap_cigar = std::min<uint64_t>(rounds * cl_reads * (2ull * max_seg + 1), 96ull << 20);   // words
   ca.cap_out = std::min<uint64_t>(rounds * (cl_reads + 2ull * n_cl) * ((uint64_t)max_seg + 16) + 64, 256ull << 20);  // bytes
@@ -1467,6 +1478,23 @@ int LocusCall::cluster_chain(int deep) {
     TRGT_HIP_TRY(c, hipGetLastError());
     TRGT_HIP_TRY(c, hipMemcpyAsync(slab.d(o_cfc), fa.fcounts, clf::CF_WORDS * 4, hipMemcpyDeviceToDevice, c->stream));  // (the counts come back with the slab)
   }
+  if (deep_route) {
+    // ---- the same branch for the deep list, one workgroup per locus: its own records, its own counts (both lists can be on their route
+    //      in one call), the deep list's arenas and the third part of its job / group lists
+    void *d_fc = nullptr, *d_fp = nullptr;
+    if ((rc = dev_get(c, S_CLDF_PEND, (size_t)n_cl * sizeof(clf::ClFlankPend), &d_fp))) return rc;
+    void* const z_cfc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
+    if (!z_cfc && (rc = dev_get(c, S_CLDF_COUNTS, 256, &d_fc))) return rc;
+    cldf::DeepClFlankArgs fa{da, g.hp, (uint8_t*)slab.d(o_fdone), z_cfc ? (uint32_t*)z_cfc : (uint32_t*)d_fc, (clf::ClFlankPend*)d_fp, 2 * ca.cap_j, 2 * ca.cap_g};
+    if (!z_cfc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, fa.fcounts, (uint32_t)cldf::DF_WORDS);
+    hipLaunchKernelGGL(cldf::deep_cluster_flank_kernel, cgrid, dim3(cld::DW), 0, c->stream, fa);
+    TRGT_HIP_TRY(c, hipGetLastError());
+    tl_mark(c, "deep cluster flank kernel enqueued");
+    if ((rc = cons_launch(2 * ca.cap_j, fa.fcounts + cldf::DF_J3, 2 * ca.cap_g, fa.fcounts + cldf::DF_G3))) return rc;
+    hipLaunchKernelGGL(cldf::deep_cluster_flank_finish_kernel, cgrid, dim3(cld::DW), 0, c->stream, fa);
+    TRGT_HIP_TRY(c, hipGetLastError());
+    TRGT_HIP_TRY(c, hipMemcpyAsync(slab.d(o_cfdc), fa.fcounts, cldf::DF_WORDS * 4, hipMemcpyDeviceToDevice, c->stream));  // (the counts come back with the slab)
+  }
   tl_mark(c, deep ? "deep cluster chain enqueued" : "cluster chain enqueued");
   cl_counts_dev[deep] = ca.counts;
   return TRGT_OK;
@@ -1529,11 +1557,16 @@ int LocusCall::wait_stage_a() {
       //  cluster route; a cluster locus has a byte of the cluster route's or none)
       //  cluster route; a cluster locus has a byte of the cluster route's or none.  The SNV forms write every locus' byte as well, and
       //  add FL_NOSPLIT: both branches of flank_split were evaluated on the device and neither splits the reads)
-      const uint8_t* fdone = flank_dev || snv_dev || cf_route ? (const uint8_t*)slab.h(o_fdone) : nullptr;
+      //  The deep cluster route (locus_cluster_flank_deep.hpp) writes the bytes of the loci admitted to the deep list, and only theirs: a
+      //  deep locus beyond the setting or without room in the pair budget never had its byte written.
+      const uint8_t* fdone = flank_dev || snv_dev || cf_route || cfd_route ? (const uint8_t*)slab.h(o_fdone) : nullptr;
+      std::vector<uint8_t> on_deep_list;
+      if (cfd_route) { on_deep_list.assign((size_t)nl, 0); for (const uint32_t l : cld_list) on_deep_list[l] = 1; }
       auto fl_byte = [&](int64_t l) -> uint8_t {
         if (!is_cluster(l)) return flank_dev || snv_dev ? fdone[l] : (uint8_t)0;
         const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
-        return cf_route && in->ploidy[l] != 0 && n > 0 && n <= (uint64_t)gt::GT_MAX_READS ? fdone[l] : (uint8_t)0;
+        if (n > (uint64_t)gt::GT_MAX_READS) return cfd_route && on_deep_list[(size_t)l] ? fdone[l] : (uint8_t)0;
+        return cf_route && in->ploidy[l] != 0 && n > 0 ? fdone[l] : (uint8_t)0;
       };
       std::atomic<int64_t> sent{0};
       pool->parallel_for(nl, 64, [&](int64_t l, int) {
@@ -1560,6 +1593,13 @@ int LocusCall::wait_stage_a() {
           else if (fdone[l] == gt::FL_HANDED) c->flank_cluster_stats[2] += 1;
         }
         stat_cons_jobs += (int64_t)((const uint32_t*)slab.h(o_cfc))[clf::CF_J3];  // consensus alignments of the third round
+      }
+      if (cfd_route) {  // trgt_hip_flank_cluster_deep_stats: the loci of the deep list, which are in no other count
+        for (const uint32_t l : cld_list) {
+          if ((fdone[l] & gt::FL_DONE) && !need[l]) { c->flank_cluster_deep_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_cluster_deep_stats[1] += 1; }
+          else if (fdone[l] == gt::FL_HANDED) c->flank_cluster_deep_stats[2] += 1;
+        }
+        stat_cons_jobs += (int64_t)((const uint32_t*)slab.h(o_cfdc))[cldf::DF_J3];  // consensus alignments of the deep list's third round
       }
       if (flank_dev) {  // trgt_hip_flank_stats (never a cluster locus in [0], [1], [3])
         for (int64_t l = 0; l < nl; ++l) {
@@ -2276,6 +2316,17 @@ extern "C" int trgt_hip_set_flank_cluster_device(trgt_hip_ctx* c, int on) {
 extern "C" int trgt_hip_flank_cluster_stats(const trgt_hip_ctx* c, int64_t out[3]) {
   if (!c || !out) return TRGT_ERR_INVALID;
   for (int i = 0; i < 3; ++i) out[i] = c->flank_cluster_stats[i];
+  return TRGT_OK;
+}
+// ---- ... and behind the deep cluster chain, a setting of its own again (locus_cluster_flank_deep.hpp)
+extern "C" int trgt_hip_set_flank_cluster_deep_device(trgt_hip_ctx* c, int on) {
+  if (!c) return TRGT_ERR_INVALID;
+  c->flank_cluster_deep_device = on != 0;
+  return TRGT_OK;
+}
+extern "C" int trgt_hip_flank_cluster_deep_stats(const trgt_hip_ctx* c, int64_t out[3]) {
+  if (!c || !out) return TRGT_ERR_INVALID;
+  for (int i = 0; i < 3; ++i) out[i] = c->flank_cluster_deep_stats[i];
   return TRGT_OK;
 }
 

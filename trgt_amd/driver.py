@@ -17,11 +17,11 @@ from . import _lib, locus
 
 
 class ChunkDriver:
-    """devices: one entry per context (ordinals may repeat: several contexts on one GPU).  cluster_max_reads, size_max_reads, flank_device, flank_cluster_device, snv_split_device, snv_cluster_device: passed to every context
+    """devices: one entry per context (ordinals may repeat: several contexts on one GPU).  cluster_max_reads, size_max_reads, flank_device, flank_cluster_device, flank_cluster_deep_device, snv_split_device, snv_cluster_device: passed to every context
     (size_max_reads and flank_device combine: deep size loci of a haplotagged batch then run the tag branch of genotype_flank on the device;
     size_max_reads and snv_split_device combine likewise: deep size loci of a batch with mismatch offsets then run its SNV branch there)."""
 
-    def __init__(self, devices=(0,), params=None, context_factory=None, run_fn=None, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, snv_split_device=None, snv_cluster_device=None):
+    def __init__(self, devices=(0,), params=None, context_factory=None, run_fn=None, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, flank_cluster_deep_device=None, snv_split_device=None, snv_cluster_device=None):
         self.params = params or locus.Params()
         self._make = context_factory or (lambda dev: _lib.Context(dev))
         self._run = run_fn or (lambda ctx, chunk, params, kw: locus.run_batch(chunk, params, ctx, **kw))
@@ -39,6 +39,9 @@ class ChunkDriver:
         if flank_cluster_device is not None:  # ... and behind the one-wave cluster chain (Context.set_flank_cluster_device), likewise
             for c in self.contexts:
                 c.set_flank_cluster_device(flank_cluster_device)
+        if flank_cluster_deep_device is not None:  # ... and behind the deep cluster chain (Context.set_flank_cluster_deep_device; it follows cluster_max_reads), likewise
+            for c in self.contexts:
+                c.set_flank_cluster_deep_device(flank_cluster_deep_device)
         if snv_split_device is not None:  # ... and the SNV branch inside the size genotyper (Context.set_snv_split_device: one-wave loci, and with size_max_reads the deep ones), likewise
             for c in self.contexts:
                 c.set_snv_split_device(snv_split_device)
