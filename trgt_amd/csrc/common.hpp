@@ -38,6 +38,7 @@ struct trgt_knobs {
   int win_threads = 64;      // TRGT_WIN_THREADS: ... of the windowed launch
   int win_segments = 8;      // TRGT_WIN_SEGMENTS: 4 / 6 / 8 segments for the window search
   bool win_lds = false;      // TRGT_WIN_LDS (DEV): the windowed launch by the LDS kernel (wfa_fast_kernel<64, 2>) instead of the one-wave register kernel (wfa_win.hip)
+  bool band_lds = false;     // TRGT_BAND_LDS (DEV): the banded back-trace by heavy_band_kernel, the LDS kernel (wfa_fast_kernel<64, 3>) and band_check_kernel instead of the one-wave forward kernel (wfa_band.hip)
   int grid_per_cu = 0;       // TRGT_WFA_GRID_PER_CU: persistent workgroups per CU of the dedicated kernel (0: occupancy query)
   int filter_per_cu = 0;     // TRGT_FILTER_PER_CU: persistent waves per CU of the pre-filter (0: occupancy query)
   bool one_launch = false;   // TRGT_WFA_ONE_LAUNCH: all flank alignments in one launch
@@ -123,6 +124,7 @@ struct trgt_hip_ctx {
   bool flank_cluster_deep_device = false;  // trgt_hip_set_flank_cluster_deep_device: the same branch behind the deep cluster chain (locus_cluster_flank_deep.hpp)
   int64_t flank_cluster_deep_stats[3] = {0, 0, 0};  // trgt_hip_flank_cluster_deep_stats: deep cluster loci of the last trgt_locus_batch, counted like flank_cluster_stats
   int num_cus = 256;
+  int band_occ = 0;  // resident workgroups per CU of wfa_band_kernel (wfa_band.hip), asked at its first launch (0: not yet)
   // cached device buffers, indexed by slot
   struct Buf { void* p = nullptr; size_t cap = 0; };
   std::vector<Buf> pool;
@@ -289,6 +291,7 @@ enum Slot {
   S_CLF_PEND,    // ... and its records of the loci that wait for the third consensus round
   S_CLDF_COUNTS, S_CLDF_PEND,  // the same two for the tag branch behind the deep cluster chain (locus_cluster_flank_deep.hpp)
   S_FS_SETTLED, S_FS_FILTERJOBS,  // flank location: the marks of what the seed search's shortcuts settled, and the pre-filter's list behind the settled-sibling rule (spans.hip)
+  S_FS_BANDFALL, S_LW_BANDFALL,  // flank location: the banded jobs the one-wave forward kernel leaves to the LDS launch (wfa_band.hip), short and long reads
   S_COUNT
 };
 // pinned host buffer slots

@@ -48,7 +48,12 @@ enum SpanCount : int {
   SC_SETDROP = 19,  // of SC_NOSEED: jobs the pre-filter never sees, the sibling the shortcuts settled leaves them fewer than min_matches bases (settled_sibling_kernel)
   SC_FILTER = 20,   // ... the others: the pre-filter's list where that rule or the next is on
   SC_LCSDROP = 21,  // of SC_NOSEED: jobs the pre-filter never sees, their piece has no common subsequence of min_matches bases with the read beside a known sibling span (lcs_below)
-  SC_WORDS = 22
+  // the one-wave forward kernel over a kept list (wfa_band.hip); with it SC_BAND / SC_LBAND count only what the LDS launch behind it bands
+  SC_BANDCLAIM = 22, // its job claims
+  SC_BANDFALL = 23,  // banded jobs it leaves to the LDS launch (penalty or piece beyond its layout)
+  SC_BANDREG = 24,   // of SC_KEEP: back-traced inside their band by it
+  SC_LBANDCLAIM = 25, SC_LBANDFALL = 26, SC_LBANDREG = 27,  // the same three for the long reads' kept list
+  SC_WORDS = 28
 };
 
 struct ScanArgs {
@@ -884,6 +889,7 @@ struct SpanPlan {
   int32_t lcs_max_adm = 0;    // ... as is the common-subsequence rule, over regions of up to this many bases (0: off)
   bool sibling_pass = false;  // either of the two: settled_sibling_kernel compacts the list without seeds into the pre-filter's
   bool heavy_band = false;    // ... and what the pre-filter keeps of it is back-traced inside a band (BandArgs)
+  bool band_reg = false;      // ... by the one-wave forward kernel (wfa_band.hip); the LDS launch takes what that leaves
   bool long_window = false;   // the long reads' list goes through the light list's seed search
   bool long_filter = false, long_band = false; int64_t long_wl = 0, long_step = 0; uint64_t long_cap = 0;  // the window filter of the long reads (LongWinArgs)
   int flank_threads = 0, heavy_threads = 0, win_threads = 0, band_threads = 0, band_s_max = 0; bool early_reject = false, count_offsets = false;  // (the last two: of the pre-filter's launches)
@@ -937,6 +943,7 @@ static SpanPlan span_plan(const trgt_hip_ctx* c, const trgt_span_params& p, uint
     P.win_reg = !k.win_lds && !k.skip_bt && !k.no_spec && wfa_win_fits(p.mism, p.gapo, p.gape, P.win_tbf, P.win_s0, p.flank_len, P.win_tlen);
   }
   const bool band_ok = k.heavy_band > 0 && wgs && !k.no_spec && !k.skip_bt && !k.wfa_no_stage;  // (the banded launch exists as the LDS kernel of TRGT's configuration only)
+  P.band_reg = band_ok && !k.band_lds;  // (TRGT_BAND_LDS, developer build: A/B, tests)
   if (P.split) {
     // The expensive alignments first meet the register-resident pre-filter (wfa_reg.hip): exact penalty and an upper bound on
     // count_matches() without history or back-trace; only those whose bound reaches the threshold (a quarter of the jobs, 5 % of
@@ -1013,6 +1020,7 @@ struct SpanCall {
   template <class T> int get(int slot, size_t bytes, T*& out) { void* v = nullptr; const int rc = dev_get(c, slot, bytes, &v); out = (T*)v; return rc; }
   int seed_search(bool front, JobDev* rest, JobDev* long_rest);
   int band_backtrace(JobList& list, int slot_band, int slot_rest, int slot_score, int i_band, int i_rest, const WfaLaunch& base, int buffer_set);
+  int band_lds_launches(const JobList& kept, JobDev* rest, int slot_band, int slot_score, int i_band, int i_rest, const WfaLaunch& base, int buffer_set);
   // ---- The offset counters (16 bytes per buffer set: [0] a running total, [1] see below).  The first wfa_launch of a call on a buffer
   // set resets that set's counter, every later one keeps counting into it; c->last_wfa_cells_dev, which the caller reads, is the
   // counter of the call's last launch -- one on set 0.  Its [1] holds the offsets of the launches over the expensive list (without
@@ -1104,12 +1112,38 @@ int SpanCall::seed_search(bool front, JobDev* rest, JobDev* long_rest) {
 // The banded back-trace (see BandArgs) of a kept list: the alignments inside their band, one wave each, by a launch like `base` on the
 // given buffer set; `list` then names whatever is left over for the launch over the whole read.
 int SpanCall::band_backtrace(JobList& list, int slot_band, int slot_rest, int slot_score, int i_band, int i_rest, const WfaLaunch& base, int buffer_set) {
-  int rc; JobDev *band = nullptr, *rest = nullptr; int32_t* bscore = nullptr;
-  if ((rc = get(slot_band, n_jobs * sizeof(JobDev), band)) || (rc = get(slot_rest, n_jobs * sizeof(JobDev), rest)) || (rc = get(slot_score, n_jobs * 4, bscore)))
-    return rc;
+  int rc; JobDev* rest = nullptr;
+  if ((rc = get(slot_rest, n_jobs * sizeof(JobDev), rest))) return rc;
+  const int s_max = plan.band_s_max;
+  if (plan.band_reg) {
+    // One wave per kept job, forward only (wfa_band.hip): it bands, aligns and checks by itself.  Only a plan that admits penalties or pieces
+    // beyond its layout leaves anything on the fallback list; then the three launches below run over that list.
+    const bool short_list = i_band == SC_BAND;
+    const bool may_fall = s_max > WFA_BAND_S_CAP || p.flank_len > WFA_BAND_PLEN_MAX;
+    JobDev* fall = nullptr;
+    if (may_fall && (rc = get(short_list ? S_FS_BANDFALL : S_LW_BANDFALL, n_jobs * sizeof(JobDev), fall))) return rc;
+    WfaBandLaunch BL;
+    BL.jobs_dev = list.jobs; BL.n_jobs_host = (int64_t)n_jobs; BL.n_jobs_dev = list.count; BL.pat_base = d_flank; BL.txt_base = d_reads;
+    BL.count = count; BL.i_claim = short_list ? SC_BANDCLAIM : SC_LBANDCLAIM; BL.i_reg = BL.i_claim + 2; BL.i_fall = BL.i_claim + 1;
+    BL.i_rest = i_rest; BL.i_fail = SC_BANDFAIL; BL.fall_jobs = fall; BL.rest_jobs = rest;
+    BL.n_match = nmatch; BL.span4 = span4; BL.read_off = d_read_off; BL.read_len = d_read_len; BL.s_max = s_max; BL.timer_slot = base.timer_slot;
+    if ((rc = wfa_band_launch(c, BL))) return rc;
+    list = {rest, count + i_rest};
+    if (!may_fall) return TRGT_OK;
+    // (the rest list keeps growing: the launch over the whole read comes behind all of this)
+    return band_lds_launches(JobList{fall, count + BL.i_fall}, rest, slot_band, slot_score, i_band, i_rest, base, buffer_set);
+  }
+  if ((rc = band_lds_launches(list, rest, slot_band, slot_score, i_band, i_rest, base, buffer_set))) return rc;
+  list = {rest, count + i_rest};
+  return TRGT_OK;
+}
+// ... by the LDS kernel: heavy_band_kernel cuts the windows, wfa_fast_kernel<64, 3> aligns and back-traces, band_check_kernel sorts out
+int SpanCall::band_lds_launches(const JobList& kept, JobDev* rest, int slot_band, int slot_score, int i_band, int i_rest, const WfaLaunch& base, int buffer_set) {
+  int rc; JobDev* band = nullptr; int32_t* bscore = nullptr;
+  if ((rc = get(slot_band, n_jobs * sizeof(JobDev), band)) || (rc = get(slot_score, n_jobs * 4, bscore))) return rc;
   const int s_max = plan.band_s_max;
   BandArgs ba;
-  ba.keep_jobs = list.jobs; ba.n_keep = list.count; ba.band_jobs = band; ba.rest_jobs = rest; ba.count = count;
+  ba.keep_jobs = kept.jobs; ba.n_keep = kept.count; ba.band_jobs = band; ba.rest_jobs = rest; ba.count = count;
   ba.s_max = s_max; ba.score = bscore; ba.span4 = span4; ba.n_match = nmatch;
   ba.read_off = d_read_off; ba.read_len = d_read_len; ba.i_band = i_band; ba.i_rest = i_rest;
   hipLaunchKernelGGL(heavy_band_kernel, dim3(64), dim3(256), 0, c->stream, ba);
@@ -1123,7 +1157,6 @@ int SpanCall::band_backtrace(JobList& list, int slot_band, int slot_rest, int sl
   if ((rc = launch(wpb, LB))) return rc;
   hipLaunchKernelGGL(band_check_kernel, dim3(64), dim3(256), 0, c->stream, ba);
   TRGT_HIP_TRY(c, hipGetLastError());
-  list = {rest, count + i_rest};
   return TRGT_OK;
 }
 // The expensive list, on the second stream where the plan says so: seed search over the front of the list, the sibling rule beside what
@@ -1285,11 +1318,12 @@ int SpanCall::debug_report() {  // (synchronises: developer output only)
   if (!win) fprintf(stderr, "[spans] fallback alignments: first launch %u, long reads %u, light %u (no seeded windows for this configuration)\n", h[SC_HEAVY], h[SC_LONG], h[SC_LIGHT]);
   if (win) fprintf(stderr, "[spans+] windowed launch: %s, %u alignments it did not take\n", plan.win_reg ? "one wave per alignment, history in registers" : "LDS kernel", h[SC_WINFALL]);
   if (win && plan.heavy_window) fprintf(stderr, "[spans+] (the seed search ran over the first launch's list too: %u of its %u alignments had no seeds and met the pre-filter; the counts of the windowed list and of the shortcut include the others)\n", h[SC_NOSEED], h[SC_HEAVY]);
-  if (plan.has_long) fprintf(stderr, "[spans+] long reads kept by the window filter: back-traced inside a band %u, over the whole read %u\n", h[SC_LBAND], h[SC_LREST]);
+  if (plan.has_long) fprintf(stderr, "[spans+] long reads kept by the window filter: back-traced inside a band %u, over the whole read %u\n", h[SC_LBAND] + h[SC_LBANDREG], h[SC_LREST]);
   fprintf(stderr, "[spans+] sibling rule %s: %u missed pieces without a job (fewer than %d bases beside the exactly found sibling)\n", plan.scan_min_matches > 0 ? "on" : "off", h[SC_SIBDROP], plan.scan_min_matches);
   if (win && plan.heavy_window) fprintf(stderr, "[spans+] settled-sibling rule %s: %u jobs without seeds never met the pre-filter (fewer than %d bases beside a sibling the shortcuts settled)\n", plan.settled_rule ? "on" : "off", h[SC_SETDROP], plan.scan_min_matches);
   if (win && plan.heavy_window) fprintf(stderr, "[spans+] common-subsequence rule %s: %u jobs without seeds never met the pre-filter (no common subsequence of %d bases with the %d to %d bases beside a sibling found exactly or settled by the shortcuts); %u met it\n", plan.lcs_max_adm > 0 ? "on" : "off", h[SC_LCSDROP], plan.scan_min_matches, plan.scan_min_matches, plan.lcs_max_adm, plan.sibling_pass ? h[SC_FILTER] : h[SC_NOSEED]);
-  if (plan.heavy_band) fprintf(stderr, "[spans+] kept by the pre-filter: %u -> back-traced inside a band %u (did not stand: %u), over the whole read %u\n", h[SC_KEEP], h[SC_BAND], h[SC_BANDFAIL], h[SC_HREST]);
+  if (plan.heavy_band) fprintf(stderr, "[spans+] kept by the pre-filter: %u -> back-traced inside a band %u (did not stand: %u), over the whole read %u\n", h[SC_KEEP], h[SC_BAND] + h[SC_BANDREG], h[SC_BANDFAIL], h[SC_HREST]);
+  if (plan.heavy_band || plan.long_band) fprintf(stderr, "[spans+] banded launch: %s, %u + %u alignments left to the LDS kernel\n", plan.band_reg ? "one wave per alignment, forward only" : "LDS kernel", h[SC_BANDFALL], h[SC_LBANDFALL]);
   return TRGT_OK;
 }
 

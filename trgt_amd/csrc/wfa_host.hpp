@@ -69,6 +69,24 @@ struct WfaWinLaunch {
 bool wfa_win_fits(int mism, int gapo, int gape, int tbf, int s_max, int64_t max_plen, int64_t max_tlen);
 int wfa_win_launch(trgt_hip_ctx* c, const WfaWinLaunch& L);
 
+// The banded alignments of what the pre-filter keeps, one wave each and forward only (wfa_band.hip): gap-affine (2, 5, 1).  The kernel reads
+// the kept list itself (penalty s* and end diagonal in JobDev::pad), aligns each piece inside its band and writes n_match and span4 of the
+// jobs that come out at s* with matches.  The others go to rest_jobs (whole read; counted in count[i_fail] where a banded run did not
+// stand), and banded jobs its layout cannot hold (s* > WFA_BAND_S_CAP, a piece beyond WFA_BAND_PLEN_MAX) to fall_jobs for wfa_launch.
+constexpr int WFA_BAND_S_CAP = 96, WFA_BAND_PLEN_MAX = 255;
+struct WfaBandLaunch {
+  const JobDev* jobs_dev = nullptr; int64_t n_jobs_host = 0; const uint32_t* n_jobs_dev = nullptr;
+  const uint8_t* pat_base = nullptr; const uint8_t* txt_base = nullptr;
+  uint32_t* count = nullptr;  // the call's cleared counter block, and the words of it: job claims, jobs taken, lengths of the two lists, failures
+  int i_claim = 0, i_reg = 0, i_fall = 0, i_rest = 0, i_fail = 0;
+  JobDev* fall_jobs = nullptr; JobDev* rest_jobs = nullptr;
+  int32_t* n_match = nullptr; uint32_t* span4 = nullptr;
+  const uint64_t* read_off = nullptr; const uint32_t* read_len = nullptr;  // by read (out_index / 2): the whole read of a job that did not stand
+  int s_max = 0;  // jobs whose penalty exceeds it are not banded at all
+  int timer_slot = TRGT_K_WFA_FLANK;
+};
+int wfa_band_launch(trgt_hip_ctx* c, const WfaBandLaunch& L);
+
 // The register-resident BiWFA kernel for small end-to-end alignments (wfa_lean.hip), launched by wfa_launch in front of the generic
 // kernel: alignments it does not take are appended to retry_jobs / *retry_count (device memory) and redone there from scratch.
 int wfa_lean_launch(trgt_hip_ctx* c, const trgt_wfa_params& p, const WfaLaunch& L, JobDev* mid_jobs, JobDev* retry_jobs, unsigned int* retry_count, uint32_t retry_cap,
