@@ -91,6 +91,57 @@ CLUSTER_SNV_EXPORTS = ["trgt_hip_set_snv_cluster_device", "trgt_hip_snv_cluster_
 # ... and the two of the tag branch behind the DEEP cluster chain (locus_cluster_flank_deep.hpp), a list of its own for the same reasons
 CLUSTER_DEEP_FLANK_EXPORTS = ["trgt_hip_set_flank_cluster_deep_device", "trgt_hip_flank_cluster_deep_stats"]
 
+# The opt-in device routes of genotype_flank (FlankRoute, csrc/common.hpp): (name, C setter, C statistics call, its width, docstring of
+# Context.set_<name>_device, docstring of Context.<statistics name without trgt_hip_>).  Context gets the two methods of every row below.
+ROUTES = [
+    ("flank", "trgt_hip_set_flank_device", "trgt_hip_flank_stats", 4,
+     """trgt_hip_set_flank_device: the haplotype-tag branch of genotype_flank (genotype_flank.rs:43-76) runs inside the device genotyper for
+        batches that carry hp_tag (off, the default: on the host path): for loci of at most 256 candidate reads, and on a context that is
+        also set with set_size_max_reads(n) for Genotyper::Size loci of up to n reads.  Every later call on this context uses it.""",
+     """trgt_hip_flank_stats of the context's last trgt_locus_batch: (loci whose genotype the device replaced by the tag split, those
+        among them with a repaired group, device-genotyped loci sent to the host path for the flank step, those of the first count that
+        have more than 256 candidate reads -- 0 unless set_size_max_reads is set too)."""),
+    ("snv_split", "trgt_hip_set_snv_split_device", "trgt_hip_snv_split_stats", 4,
+     """trgt_hip_set_snv_split_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) runs inside the one-wave size
+        genotyper for batches that carry mismatch offsets; a locus whose candidate search is not decided beyond the margin, or that is
+        beyond the route's limits, goes to the host path as before.  Independent of set_flank_device.  Combines with set_size_max_reads: a
+        context that has both runs the branch for the size loci of 257 reads up to that setting too (the SNV forms of the deep size kernels);
+        with this setting alone such loci are the host's from the start.  Every later call on this context uses it.""",
+     """trgt_hip_snv_split_stats of the context's last trgt_locus_batch: (loci whose genotype the device replaced through the SNV
+        branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided).  Deep size loci
+        count by the same rules on a context that has set_size_max_reads as well, and never otherwise."""),
+    ("flank_cluster", "trgt_hip_set_flank_cluster_device", "trgt_hip_flank_cluster_stats", 3,
+     """trgt_hip_set_flank_cluster_device: the haplotype-tag branch of genotype_flank behind the one-wave cluster chain, for the
+        Genotyper::Cluster loci of at most 256 candidate reads of batches that carry hp_tag (off, the default: the host redoes such a
+        locus).  Independent of set_flank_device.  Every later call on this context uses it.""",
+     """trgt_hip_flank_cluster_stats of the context's last trgt_locus_batch: (cluster loci whose genotype the device replaced by the
+        tag split, those among them with a repaired group, cluster loci on the route handed back to the host path)."""),
+    ("flank_cluster_deep", "trgt_hip_set_flank_cluster_deep_device", "trgt_hip_flank_cluster_deep_stats", 3,
+     """trgt_hip_set_flank_cluster_deep_device: the haplotype-tag branch of genotype_flank behind the DEEP cluster chain, for the
+        Genotyper::Cluster loci of 257 to set_cluster_max_reads candidate reads of batches that carry hp_tag (off, the default: the host
+        redoes such a locus).  It follows the deep chain, so it does nothing on a context without set_cluster_max_reads.  Independent of
+        set_flank_cluster_device and set_snv_cluster_device.  Every later call on this context uses it.""",
+     """trgt_hip_flank_cluster_deep_stats of the context's last trgt_locus_batch: (deep cluster loci whose genotype the device replaced
+        by the tag split, those among them with a repaired group, deep cluster loci on the route handed back to the host path)."""),
+    ("snv_cluster", "trgt_hip_set_snv_cluster_device", "trgt_hip_snv_cluster_stats", 4,
+     """trgt_hip_set_snv_cluster_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) behind the one-wave cluster
+        chain, for the Genotyper::Cluster loci of at most 256 candidate reads of batches that carry mismatch offsets; tags that split the
+        reads come first (set_flank_cluster_device, else the host).  A locus whose candidate search is not decided beyond the margin, or
+        that is beyond the route's limits, goes to the host path as before.  Independent of the other settings.  Every later call on this
+        context uses it.""",
+     """trgt_hip_snv_cluster_stats of the context's last trgt_locus_batch: (cluster loci whose genotype the device replaced through the
+        SNV branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided)."""),
+]
+
+
+def apply_settings(contexts, pairs):
+    """pairs: (value, name of the Context method that sets it) in the order to apply them; a value of None was not given.  Settings are
+    the contexts': each of `contexts` gets every given one."""
+    for value, setter in pairs:
+        if value is not None:
+            for c in contexts:
+                getattr(c, setter)(value)
+
 
 def build_extension(force=False, verbose=False, dev=False):
     """Compile every HIP translation unit for gfx950 into trgt_amd/libtrgt_hip.so (hipcc cross-compiles on CPU).  dev=True: the
@@ -135,16 +186,9 @@ def lib():
         L.trgt_hip_size_max_reads_limit.restype = C.c_int32
         L.trgt_hip_set_size_max_reads.argtypes = [_VP, C.c_int32]
         L.trgt_hip_size_deep_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
-        L.trgt_hip_set_flank_device.argtypes = [_VP, C.c_int]
-        L.trgt_hip_flank_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
-        L.trgt_hip_set_snv_split_device.argtypes = [_VP, C.c_int]
-        L.trgt_hip_snv_split_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
-        L.trgt_hip_set_flank_cluster_device.argtypes = [_VP, C.c_int]
-        L.trgt_hip_flank_cluster_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
-        L.trgt_hip_set_snv_cluster_device.argtypes = [_VP, C.c_int]
-        L.trgt_hip_snv_cluster_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
-        L.trgt_hip_set_flank_cluster_deep_device.argtypes = [_VP, C.c_int]
-        L.trgt_hip_flank_cluster_deep_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
+        for _, setter, stats, _, _, _ in ROUTES:
+            getattr(L, setter).argtypes = [_VP, C.c_int]
+            getattr(L, stats).argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_timing_enable.argtypes = [_VP, C.c_int]
         L.trgt_hip_timing_reset.argtypes = [_VP]
         L.trgt_hip_timing_get.argtypes = [_VP, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
@@ -213,78 +257,6 @@ class Context:
         self.check(lib().trgt_hip_size_deep_stats(self.handle, out))
         return tuple(int(v) for v in out)
 
-    def set_flank_device(self, on=True):
-        """trgt_hip_set_flank_device: the haplotype-tag branch of genotype_flank (genotype_flank.rs:43-76) runs inside the device genotyper for
-        batches that carry hp_tag (off, the default: on the host path): for loci of at most 256 candidate reads, and on a context that is
-        also set with set_size_max_reads(n) for Genotyper::Size loci of up to n reads.  Every later call on this context uses it."""
-        self.check(lib().trgt_hip_set_flank_device(self.handle, int(bool(on))))
-
-    def flank_stats(self):
-        """trgt_hip_flank_stats of the context's last trgt_locus_batch: (loci whose genotype the device replaced by the tag split, those
-        among them with a repaired group, device-genotyped loci sent to the host path for the flank step, those of the first count that
-        have more than 256 candidate reads -- 0 unless set_size_max_reads is set too)."""
-        out = (C.c_int64 * 4)()
-        self.check(lib().trgt_hip_flank_stats(self.handle, out))
-        return tuple(int(v) for v in out)
-
-    def set_snv_split_device(self, on=True):
-        """trgt_hip_set_snv_split_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) runs inside the one-wave size
-        genotyper for batches that carry mismatch offsets; a locus whose candidate search is not decided beyond the margin, or that is
-        beyond the route's limits, goes to the host path as before.  Independent of set_flank_device.  Combines with set_size_max_reads: a
-        context that has both runs the branch for the size loci of 257 reads up to that setting too (the SNV forms of the deep size kernels);
-        with this setting alone such loci are the host's from the start.  Every later call on this context uses it."""
-        self.check(lib().trgt_hip_set_snv_split_device(self.handle, int(bool(on))))
-
-    def snv_split_stats(self):
-        """trgt_hip_snv_split_stats of the context's last trgt_locus_batch: (loci whose genotype the device replaced through the SNV
-        branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided).  Deep size loci
-        count by the same rules on a context that has set_size_max_reads as well, and never otherwise."""
-        out = (C.c_int64 * 4)()
-        self.check(lib().trgt_hip_snv_split_stats(self.handle, out))
-        return tuple(int(v) for v in out)
-
-    def set_flank_cluster_device(self, on=True):
-        """trgt_hip_set_flank_cluster_device: the haplotype-tag branch of genotype_flank behind the one-wave cluster chain, for the
-        Genotyper::Cluster loci of at most 256 candidate reads of batches that carry hp_tag (off, the default: the host redoes such a
-        locus).  Independent of set_flank_device.  Every later call on this context uses it."""
-        self.check(lib().trgt_hip_set_flank_cluster_device(self.handle, int(bool(on))))
-
-    def flank_cluster_stats(self):
-        """trgt_hip_flank_cluster_stats of the context's last trgt_locus_batch: (cluster loci whose genotype the device replaced by the
-        tag split, those among them with a repaired group, cluster loci on the route handed back to the host path)."""
-        out = (C.c_int64 * 3)()
-        self.check(lib().trgt_hip_flank_cluster_stats(self.handle, out))
-        return tuple(int(v) for v in out)
-
-    def set_flank_cluster_deep_device(self, on=True):
-        """trgt_hip_set_flank_cluster_deep_device: the haplotype-tag branch of genotype_flank behind the DEEP cluster chain, for the
-        Genotyper::Cluster loci of 257 to set_cluster_max_reads candidate reads of batches that carry hp_tag (off, the default: the host
-        redoes such a locus).  It follows the deep chain, so it does nothing on a context without set_cluster_max_reads.  Independent of
-        set_flank_cluster_device and set_snv_cluster_device.  Every later call on this context uses it."""
-        self.check(lib().trgt_hip_set_flank_cluster_deep_device(self.handle, int(bool(on))))
-
-    def flank_cluster_deep_stats(self):
-        """trgt_hip_flank_cluster_deep_stats of the context's last trgt_locus_batch: (deep cluster loci whose genotype the device replaced
-        by the tag split, those among them with a repaired group, deep cluster loci on the route handed back to the host path)."""
-        out = (C.c_int64 * 3)()
-        self.check(lib().trgt_hip_flank_cluster_deep_stats(self.handle, out))
-        return tuple(int(v) for v in out)
-
-    def set_snv_cluster_device(self, on=True):
-        """trgt_hip_set_snv_cluster_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) behind the one-wave cluster
-        chain, for the Genotyper::Cluster loci of at most 256 candidate reads of batches that carry mismatch offsets; tags that split the
-        reads come first (set_flank_cluster_device, else the host).  A locus whose candidate search is not decided beyond the margin, or
-        that is beyond the route's limits, goes to the host path as before.  Independent of the other settings.  Every later call on this
-        context uses it."""
-        self.check(lib().trgt_hip_set_snv_cluster_device(self.handle, int(bool(on))))
-
-    def snv_cluster_stats(self):
-        """trgt_hip_snv_cluster_stats of the context's last trgt_locus_batch: (cluster loci whose genotype the device replaced through the
-        SNV branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided)."""
-        out = (C.c_int64 * 4)()
-        self.check(lib().trgt_hip_snv_cluster_stats(self.handle, out))
-        return tuple(int(v) for v in out)
-
     def timing_enable(self, on=True):
         self.check(lib().trgt_hip_timing_enable(self.handle, int(on)))
 
@@ -306,6 +278,25 @@ class Context:
             self.close()
         except Exception:
             pass
+
+
+def _route_methods(name, setter, stats, width, set_doc, stats_doc):
+    """Context.set_<name>_device(on=True) and Context.<name>_stats() of one row of ROUTES"""
+    def set_device(self, on=True):
+        self.check(getattr(lib(), setter)(self.handle, int(bool(on))))
+
+    def last_stats(self):
+        out = (C.c_int64 * width)()
+        self.check(getattr(lib(), stats)(self.handle, out))
+        return tuple(int(v) for v in out)
+
+    for f, fname, doc in ((set_device, "set_%s_device" % name, set_doc), (last_stats, "%s_stats" % name, stats_doc)):
+        f.__name__, f.__qualname__, f.__doc__ = fname, "Context." + fname, doc
+        setattr(Context, fname, f)
+
+
+for _row in ROUTES:
+    _route_methods(*_row)
 
 
 class Pool:
@@ -335,27 +326,9 @@ class Pool:
             c.device = devices[i]
             c.close = lambda: None
             self.contexts.append(c)
-        if cluster_max_reads is not None:  # (a setting of the contexts: each of the pool's gets it)
-            for c in self.contexts:
-                c.set_cluster_max_reads(cluster_max_reads)
-        if size_max_reads is not None:
-            for c in self.contexts:
-                c.set_size_max_reads(size_max_reads)
-        if flank_device is not None:
-            for c in self.contexts:
-                c.set_flank_device(flank_device)
-        if flank_cluster_device is not None:
-            for c in self.contexts:
-                c.set_flank_cluster_device(flank_cluster_device)
-        if flank_cluster_deep_device is not None:
-            for c in self.contexts:
-                c.set_flank_cluster_deep_device(flank_cluster_deep_device)
-        if snv_split_device is not None:
-            for c in self.contexts:
-                c.set_snv_split_device(snv_split_device)
-        if snv_cluster_device is not None:
-            for c in self.contexts:
-                c.set_snv_cluster_device(snv_cluster_device)
+        apply_settings(self.contexts, ((cluster_max_reads, "set_cluster_max_reads"), (size_max_reads, "set_size_max_reads"), (flank_device, "set_flank_device"),
+                                       (flank_cluster_device, "set_flank_cluster_device"), (flank_cluster_deep_device, "set_flank_cluster_deep_device"),
+                                       (snv_split_device, "set_snv_split_device"), (snv_cluster_device, "set_snv_cluster_device")))
 
     def run_many(self, params_struct, cins, couts, out_per_context=False):
         """cins / couts: lists of LocusBatchIn / LocusBatchOut structures (couts: one per batch, or one per context)"""

@@ -101,6 +101,25 @@ struct trgt_knobs {
   bool skip_bt = false;      // TRGT_DBG_SKIP_BT (make DEV=1 only): skip back-traces -- timing experiments, results are wrong
 };
 
+// The opt-in device routes of genotype_flank (tr.rs:69-75): each is a setting of the context (off when it is created) with the statistics
+// of the context's last trgt_locus_batch.  locus.hip decides in ONE place what a call runs of them (LocusCall::plan_routes) and counts
+// them in one (LocusCall::tally_route); the entry points are trgt_hip_set_<name>_device / trgt_hip_<name>_stats.
+enum FlankRoute {
+  FR_SIZE_TAG = 0,      // trgt_hip_set_flank_device: the haplotype-tag branch runs in the size genotypers (locus_gt.hpp, FLANK forms; with a deep size list those of
+                        // locus_gt_deep.hpp).  trgt_hip_flank_stats: genotypes replaced on the device, repaired among them, loci sent to the host path for the
+                        // flank step, those of the first with more than 256 reads
+  FR_SIZE_SNV,          // trgt_hip_set_snv_split_device: the SNV branch runs in the size genotypers (the SNV forms of the same two headers).  trgt_hip_snv_split_stats:
+                        // genotypes replaced on the device, repaired among them, handed back for room or limits, handed back undecided
+  FR_CLUSTER_TAG,       // trgt_hip_set_flank_cluster_device: the tag branch behind the one-wave cluster chain (locus_cluster_flank.hpp).  trgt_hip_flank_cluster_stats:
+                        // cluster loci whose genotype was replaced on the device, repaired among them, handed back to the host path ([3] stays 0)
+  FR_CLUSTER_SNV,       // trgt_hip_set_snv_cluster_device: the SNV branch behind that chain (the SNV forms of locus_cluster_flank.hpp).  trgt_hip_snv_cluster_stats:
+                        // cluster loci, counted like FR_SIZE_SNV
+  FR_CLUSTER_DEEP_TAG,  // trgt_hip_set_flank_cluster_deep_device: the tag branch behind the deep cluster chain (locus_cluster_flank_deep.hpp).
+                        // trgt_hip_flank_cluster_deep_stats: deep cluster loci, counted like FR_CLUSTER_TAG
+  FR_N
+};
+struct FlankRouteState { bool on = false; int64_t stats[4] = {0, 0, 0, 0}; };
+
 struct trgt_hip_ctx {
   trgt_knobs knobs;
   int device = -1;
@@ -113,16 +132,7 @@ struct trgt_hip_ctx {
   int32_t cluster_max_reads = 256;  // trgt_hip_set_cluster_max_reads: deepest Genotyper::Cluster locus the device chains take (256 = the one-wave chain only)
   int32_t size_max_reads = 256;     // trgt_hip_set_size_max_reads: deepest Genotyper::Size locus the device genotypers take (256 = the one-wave kernel only)
   int64_t size_deep_stats[4] = {0, 0, 0, 0};  // trgt_hip_size_deep_stats: the deep size loci of the last trgt_locus_batch (genotyped on the device, repaired among them, handed to the host, reserved)
-  bool flank_device = false;  // trgt_hip_set_flank_device: the haplotype-tag branch of genotype_flank runs in the device genotyper (locus_gt.hpp, FLANK forms)
-  int64_t flank_stats[4] = {0, 0, 0, 0};  // trgt_hip_flank_stats: of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, loci sent to the host path for the flank step, reserved)
-  bool snv_split_device = false;  // trgt_hip_set_snv_split_device: the SNV branch of genotype_flank runs in the device genotyper (locus_gt.hpp, SNV forms)
-  int64_t snv_split_stats[4] = {0, 0, 0, 0};  // trgt_hip_snv_split_stats: of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, handed back for room or limits, handed back undecided)
-  bool flank_cluster_device = false;  // trgt_hip_set_flank_cluster_device: the same branch behind the one-wave cluster chain (locus_cluster_flank.hpp)
-  bool snv_cluster_device = false;  // trgt_hip_set_snv_cluster_device: the SNV branch behind that chain (the SNV forms of locus_cluster_flank.hpp)
-  int64_t snv_cluster_stats[4] = {0, 0, 0, 0};  // trgt_hip_snv_cluster_stats: cluster loci of the last trgt_locus_batch, counted like snv_split_stats
-  int64_t flank_cluster_stats[3] = {0, 0, 0};  // trgt_hip_flank_cluster_stats: cluster loci of the last trgt_locus_batch (genotypes replaced on the device, repaired among them, handed back to the host path)
-  bool flank_cluster_deep_device = false;  // trgt_hip_set_flank_cluster_deep_device: the same branch behind the deep cluster chain (locus_cluster_flank_deep.hpp)
-  int64_t flank_cluster_deep_stats[3] = {0, 0, 0};  // trgt_hip_flank_cluster_deep_stats: deep cluster loci of the last trgt_locus_batch, counted like flank_cluster_stats
+  FlankRouteState route[FR_N];  // the opt-in device routes of genotype_flank, indexed by FlankRoute (above)
   int num_cus = 256;
   int band_occ = 0;  // resident workgroups per CU of wfa_band_kernel (wfa_band.hip), asked at its first launch (0: not yet)
   // cached device buffers, indexed by slot

@@ -715,7 +715,7 @@ struct LocusCall {
   const int64_t nl; int64_t nr = 0; int F = 0;
   bool done = false;  // nothing left to do (a call without loci or without reads)
   trgt_locus_batch_in in_expanded; std::vector<uint64_t> expanded_off;  // TRGT_READS_BAM4: the batch with its reads expanded in HBM
-  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, flank_dev = false, snv_dev = false, flank_cl_dev = false, snv_cl_dev = false, flank_cld_dev = false, cf_route = false, cf_snv = false, cfd_route = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
+  bool reads_on_device = false, impure_filter = false, dev_gt = false, presel = false, flank_on = false, use_slots = false, dev_repair = false, split = false, small_gt = false;
   FlankMeta flank_meta{};
   // ---- clean-up state (see the destructor)
   bool zeroed = false;
@@ -781,17 +781,30 @@ struct LocusCall {
   }
 
   bool is_cluster(int64_t l) const { return in->genotyper && in->genotyper[l] == 1; }
+  // ---- the device routes of genotype_flank (FlankRoute, common.hpp).  fits: the context opted in and the batch carries what the route
+  // reads (plan_routes, the one place that decides); ran: a chain enqueued the route's kernels, which then wrote the bytes of its loci
+  bool fits[FR_N] = {}, ran[FR_N] = {};
+  void plan_routes();
+  bool any_route_fits() const { return std::any_of(fits, fits + FR_N, [](bool b) { return b; }); }      // the per-locus byte joins the slab
+  bool cluster_route_fits() const { return fits[FR_CLUSTER_TAG] || fits[FR_CLUSTER_SNV]; }              // one pair of kernels, one count block (o_cfc)
+  bool snv_inputs_up() const { return fits[FR_SIZE_SNV] || fits[FR_CLUSTER_SNV]; }                      // offsets, mismatch lists, the per-read byte
+  bool tags_up() const { return fits[FR_SIZE_TAG] || fits[FR_CLUSTER_TAG] || fits[FR_CLUSTER_DEEP_TAG] || (snv_inputs_up() && in->hp_tag); }  // (the SNV forms read the tags of a batch that has them: tags come first)
+  // the size genotypers' form: one per call, for the one-wave kernels and for the deep size list's
+  enum class GtForm { PLAIN, FLANK, SNV };
+  GtForm gt_form() const { return fits[FR_SIZE_SNV] ? GtForm::SNV : fits[FR_SIZE_TAG] ? GtForm::FLANK : GtForm::PLAIN; }
+  void launch_genotype_kernels(), launch_finish_kernels(const gt::FinishArgs& fa);
+  void tally_route(FlankRoute r, const std::vector<uint32_t>* list, uint8_t snv, const uint8_t* fdone, const uint8_t* need);
   // ga as it stands, with what the FLANK forms read beyond it
   gt::GtFlankArgs flank_args() const { gt::GtFlankArgs fa; static_cast<gt::GtArgs&>(fa) = ga; fa.hp_tag = g.hp; fa.flank_done = (uint8_t*)slab.d(o_fdone); return fa; }
   // ... and with what the SNV forms read beyond that (the three logarithms are the host's: flank_split's own)
   gt::SnvArgs snv_args() const {
     gt::SnvArgs sa; static_cast<gt::GtFlankArgs&>(sa) = flank_args();
     sa.start_offset = g.so; sa.end_offset = g.eo; sa.mismatch_offsets = g.mm; sa.mismatch_off = g.mm_off; sa.snv_read = (uint8_t*)g.snv_read;
-    sa.ln_match = std::log(0.9); sa.ln_mis = std::log(1.0 - 0.9); sa.ln2 = std::log(2.0); sa.tag_route = flank_dev ? 1 : 0;
+    sa.ln_match = std::log(0.9); sa.ln_mis = std::log(1.0 - 0.9); sa.ln2 = std::log(2.0); sa.tag_route = fits[FR_SIZE_TAG] ? 1 : 0;
     return sa;
   }
   gtd::DeepFlankArgs deep_flank_args() const { return gtd::DeepFlankArgs{ds, g.hp, (uint8_t*)slab.d(o_fdone)}; }  // the deep size list's FLANK forms (ds.c.g = ga is the caller's)
-  // ... and its SNV forms (snv_dev with a deep size list): what snv_args() adds, and the route's workspace
+  // ... and its SNV forms (FR_SIZE_SNV with a deep size list): what snv_args() adds, and the route's workspace
   gtd::DeepSnvArgs deep_snv_args() const {
     gtd::DeepSnvArgs da; static_cast<gtd::DeepFlankArgs&>(da) = deep_flank_args();
     const gt::SnvArgs sa = snv_args();
@@ -815,11 +828,7 @@ struct LocusCall {
 int LocusCall::check_args() {
   if (nl < 0) return fail(c, TRGT_ERR_INVALID, "trgt_locus_batch: negative n_loci");
   for (int64_t& v : c->size_deep_stats) v = 0;
-  for (int64_t& v : c->flank_stats) v = 0;
-  for (int64_t& v : c->flank_cluster_stats) v = 0;
-  for (int64_t& v : c->flank_cluster_deep_stats) v = 0;
-  for (int64_t& v : c->snv_split_stats) v = 0;
-  for (int64_t& v : c->snv_cluster_stats) v = 0;
+  for (FlankRouteState& r : c->route) for (int64_t& v : r.stats) v = 0;
   if (nl == 0) { done = true; return TRGT_OK; }
   if (!in->flank_blob || !in->lf_off || !in->lf_len || !in->rf_off || !in->rf_len || !in->tr_blob || !in->tr_off || !in->tr_len ||
       !in->motif_blob || !in->motif_off || !in->set_motif_begin || !in->ploidy || !in->locus_read_begin || !in->read_blob ||
@@ -919,6 +928,18 @@ int LocusCall::host_tables() {
   tl("set-up");
   return TRGT_OK;
 }
+// Which of the context's routes this call runs.  A route fits when the device genotypers run at all, the context opted in and the batch
+// carries what the branch reads: haplotype tags, or mismatch offsets with their table.  Its kernels then read the tags (FLANK / tag forms)
+// or the SNV inputs (SNV forms) and leave one byte per locus.  Where the tag and the SNV route of one genotyper both fit, the SNV forms
+// take the place of the tag forms and the tag route only says whose the tag branch inside them is (tag_route).
+void LocusCall::plan_routes() {
+  const bool tags = in->hp_tag != nullptr, snvs = in->mismatch_offsets != nullptr && in->mismatch_off != nullptr;
+  // (the deep cluster route: the context can have a deep cluster list at all -- plan_device_lists decides which loci it holds; the route
+  //  runs in cluster_chain(1), which is not reached with an empty list)
+  const bool deep_chain = c->cluster_max_reads > gt::GT_MAX_READS && in->genotyper != nullptr && !c->knobs.host_cluster && !c->knobs.split_hmm;
+  const bool batch_has[FR_N] = {tags, snvs, tags, snvs, tags && deep_chain};  // in the order of FlankRoute
+  for (int r = 0; r < FR_N; ++r) fits[r] = dev_gt && c->route[r].on && batch_has[r];
+}
 // The call's modes; stage A's inputs and the device genotyper's on their way up (one batch, flushed by flush_uploads); the result slab
 int LocusCall::upload_tables() {
   reads_on_device = is_device_ptr(in->read_blob);
@@ -932,23 +953,7 @@ int LocusCall::upload_tables() {
   // genotype_flank (tr.rs:69-75) can only change a genotype when reads carry haplotype tags or mismatch offsets
   flank_on = in->hp_tag != nullptr || (in->mismatch_offsets != nullptr && in->mismatch_off != nullptr);
   flank_meta = FlankMeta{in->hp_tag, in->start_offset, in->end_offset, in->mismatch_offsets, in->mismatch_off};
-  // ... and its haplotype-tag branch runs inside the device genotyper on a context that opted in (trgt_hip_set_flank_device): the FLANK
-  // forms of locus_gt.hpp, which read the tags and leave one byte per locus
-  flank_dev = dev_gt && c->flank_device && in->hp_tag != nullptr;
-  // ... and its SNV branch likewise on a context that opted in to that (trgt_hip_set_snv_split_device), for a batch with mismatch offsets:
-  // the SNV forms, which take the place of the FLANK forms of the one-wave kernels and -- where the context also has a deep size list
-  // (trgt_hip_set_size_max_reads) -- of the two deep size kernels; flank_dev then only says whose the tag branch inside them is
-  snv_dev = dev_gt && c->snv_split_device && in->mismatch_offsets != nullptr && in->mismatch_off != nullptr;
-  // ... and, a setting of its own (trgt_hip_set_flank_cluster_device), behind the one-wave cluster chain: locus_cluster_flank.hpp
-  flank_cl_dev = dev_gt && c->flank_cluster_device && in->hp_tag != nullptr;
-  // ... and the SNV branch behind that chain (trgt_hip_set_snv_cluster_device), for a batch with mismatch offsets: the SNV forms of the
-  // same two kernels, which take the place of the tag forms; flank_cl_dev then only says whose the tag branch inside them is
-  snv_cl_dev = dev_gt && c->snv_cluster_device && in->mismatch_offsets != nullptr && in->mismatch_off != nullptr;
-  // ... and the tag branch behind the DEEP cluster chain (trgt_hip_set_flank_cluster_deep_device, a setting of its own again):
-  // locus_cluster_flank_deep.hpp.  Here: the context can have a deep cluster list at all (plan_device_lists decides which loci it holds;
-  // the route runs in cluster_chain(1), which is not reached with an empty list)
-  flank_cld_dev = dev_gt && c->flank_cluster_deep_device && in->hp_tag != nullptr && c->cluster_max_reads > gt::GT_MAX_READS && in->genotyper != nullptr &&
-                  !c->knobs.host_cluster && !c->knobs.split_hmm;
+  plan_routes();  // ... and its branches run on the device where the context opted in
   int rc;
   if (ready) TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, ready, 0));
   if (staged_flank) d_flank = staged_flank;
@@ -971,9 +976,9 @@ int LocusCall::upload_tables() {
     o_nsp = slab.add(2 * (size_t)nl * 4); o_cls = slab.add((size_t)nr * 4); o_rank = slab.add((size_t)nr * 4); o_nspan = slab.add((size_t)nl * 4);
     o_toff = slab.add((2 * (size_t)nl + 1) * 8); o_flip = slab.add((size_t)nl);
     o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
-    if (flank_dev || flank_cl_dev || snv_dev || snv_cl_dev || flank_cld_dev) o_fdone = slab.add((size_t)nl);
-    if (flank_cl_dev || snv_cl_dev) o_cfc = slab.add(clf::CF_WORDS * 4);
-    if (flank_cld_dev) o_cfdc = slab.add(cldf::DF_WORDS * 4);
+    if (any_route_fits()) o_fdone = slab.add((size_t)nl);
+    if (cluster_route_fits()) o_cfc = slab.add(clf::CF_WORDS * 4);
+    if (fits[FR_CLUSTER_DEEP_TAG]) o_cfdc = slab.add(cldf::DF_WORDS * 4);
   }
   if ((rc = dev_get(c, S_LOCUS_4, slab.total, &slab.dev)) || (rc = pin_get(c, P_SPAN_S, slab.total, &slab.host))) return rc;
   d_ss = slab.d(o_ss); d_se = slab.d(o_se); d_hl = slab.d(o_hl); d_hr = slab.d(o_hr);
@@ -984,8 +989,8 @@ int LocusCall::upload_tables() {
         (rc = dev_in(c, S_GT_TRLEN, in->tr_len, (size_t)nl, &g.tr_len, &ub)) || (rc = dev_in(c, S_GT_ALOFF, out->allele_off, 2 * (size_t)nl, &g.al_off, &ub)) ||
         (rc = dev_in(c, S_GT_ALCAP, out->allele_cap, (size_t)nl, &g.al_cap, &ub)) || (in->genotyper && (rc = dev_in(c, S_GT_GENO, in->genotyper, (size_t)nl, &g.geno, &ub))) ||
         (presel && in->read_qual && (rc = dev_in(c, S_PUR_RQ, in->read_qual, (size_t)nr, &g.rq, &ub))) ||
-        ((flank_dev || flank_cl_dev || flank_cld_dev || ((snv_dev || snv_cl_dev) && in->hp_tag)) && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
-        ((snv_dev || snv_cl_dev) && ((in->start_offset && (rc = dev_in(c, S_SNV_SO, in->start_offset, (size_t)nr, &g.so, &ub))) ||
+        (tags_up() && (rc = dev_in(c, S_GT_HP, in->hp_tag, (size_t)nr, &g.hp, &ub))) ||
+        (snv_inputs_up() && ((in->start_offset && (rc = dev_in(c, S_SNV_SO, in->start_offset, (size_t)nr, &g.so, &ub))) ||
                      (in->end_offset && (rc = dev_in(c, S_SNV_EO, in->end_offset, (size_t)nr, &g.eo, &ub))) ||
                      (rc = dev_in(c, S_SNV_MMOFF, in->mismatch_off, (size_t)nr + 1, &g.mm_off, &ub)) ||
                      (rc = dev_in(c, S_SNV_MM, in->mismatch_offsets, (size_t)in->mismatch_off[nr], &g.mm, &ub)) ||
@@ -1038,7 +1043,7 @@ int LocusCall::plan_device_lists() {
       if (n > (uint64_t)gt::GT_MAX_READS && n <= (uint64_t)c->size_max_reads) gsd_list.push_back((uint32_t)l);
     }
     if (!gsd_list.empty() && (rc = dev_in(c, S_GSD_LIST, gsd_list.data(), gsd_list.size(), &d_gsd_list, &ub))) return rc;
-    if (!gsd_list.empty() && snv_dev) {  // the SNV forms' workspace: two masks per read slot, then room for every mismatch offset of the batch
+    if (!gsd_list.empty() && fits[FR_SIZE_SNV]) {  // the SNV forms' workspace: two masks per read slot, then room for every mismatch offset of the batch
       void* ws = nullptr;
       if ((rc = dev_get(c, S_SNV_DEEP, 16 * (size_t)nr + 4 * (size_t)in->mismatch_off[nr] + 16, &ws))) return rc;
       g.snv_prof = ws; g.snv_stage = (uint8_t*)ws + 16 * (size_t)nr;
@@ -1237,20 +1242,53 @@ int LocusCall::purity_chain() {
   ga.sel_read = pa.sel_read; ga.sel_start = pa.sel_start; ga.sel_len = pa.sel_len; ga.n_sel = pa.n_sel;
   return TRGT_OK;
 }
+// The genotype kernels in the call's form: the one-wave genotyper over every locus, then -- behind it: it marked these loci need_host = 1
+// -- the deep size list: selection unless it ran in front of the purity batch, then the workgroup-wide genotyper; its loci without
+// majority support join the repair chain
+void LocusCall::launch_genotype_kernels() {
+  const bool deep = !gsd_list.empty();
+  const dim3 grid((unsigned)nl), dgrid(ds.c.n_list), dblock(cld::DW);
+  if (deep) ds.c.g = ga;
+  auto select = [&] { if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, dgrid, dblock, 0, c->stream, ds); };
+  switch (gt_form()) {
+    case GtForm::SNV:
+      k_genotype_snv.launch(!small_gt, presel, grid, c->stream, snv_args());
+      if (deep) { select(); hipLaunchKernelGGL((gtd::deep_size_genotype_kernel<true, true>), dgrid, dblock, 0, c->stream, deep_snv_args()); }
+      break;
+    case GtForm::FLANK:
+      k_genotype_flank.launch(!small_gt, presel, grid, c->stream, flank_args());
+      if (deep) { select(); hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<true>, dgrid, dblock, 0, c->stream, deep_flank_args()); }
+      break;
+    case GtForm::PLAIN:
+      k_genotype.launch(!small_gt, presel, grid, c->stream, ga);
+      if (deep) { select(); hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<false>, dgrid, dblock, 0, c->stream, ds); }
+      break;
+  }
+}
+// ... and the kernels that finish what the repair chain voted on, in the same form
+void LocusCall::launch_finish_kernels(const gt::FinishArgs& fa) {
+  const bool deep = !gsd_list.empty();
+  const dim3 grid((unsigned)nl), dgrid(ds.c.n_list), dblock(cld::DW);
+  if (deep) ds.c.g = ga;
+  switch (gt_form()) {
+    case GtForm::SNV:
+      k_repair_finish_snv.launch(!small_gt, presel, grid, c->stream, snv_args(), fa);
+      if (deep) hipLaunchKernelGGL((gtd::deep_size_finish_kernel<true, true>), dgrid, dblock, 0, c->stream, deep_snv_args(), fa);
+      break;
+    case GtForm::FLANK:
+      k_repair_finish_flank.launch(!small_gt, presel, grid, c->stream, flank_args(), fa);
+      if (deep) hipLaunchKernelGGL(gtd::deep_size_finish_kernel<true>, dgrid, dblock, 0, c->stream, deep_flank_args(), fa);
+      break;
+    case GtForm::PLAIN:
+      k_repair_finish.launch(!small_gt, presel, grid, c->stream, ga, fa);
+      if (deep) hipLaunchKernelGGL(gtd::deep_size_finish_kernel<false>, dgrid, dblock, 0, c->stream, ds, fa);
+      break;
+  }
+}
 int LocusCall::size_genotyper() {
   if (!dev_gt) return TRGT_OK;
-  if (snv_dev) k_genotype_snv.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, snv_args());
-  else if (flank_dev) k_genotype_flank.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, flank_args());
-  else k_genotype.launch(!small_gt, presel, dim3((unsigned)nl), c->stream, ga);
-  if (!gsd_list.empty()) {
-    // ---- the deep size list, behind the one-wave genotyper (which marked these loci need_host = 1): selection unless it ran in front
-    //      of the purity batch, then the workgroup-wide genotyper; its loci without majority support join the repair chain below
-    ds.c.g = ga;
-    if (!presel) hipLaunchKernelGGL(cld::deep_select_kernel, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
-    if (snv_dev) hipLaunchKernelGGL((gtd::deep_size_genotype_kernel<true, true>), dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_snv_args());
-    else if (flank_dev) hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<true>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_flank_args());
-    else hipLaunchKernelGGL(gtd::deep_size_genotype_kernel<false>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds);
-  }
+  launch_genotype_kernels();
+  ran[FR_SIZE_TAG] = fits[FR_SIZE_TAG]; ran[FR_SIZE_SNV] = fits[FR_SIZE_SNV];  // (the size routes run with the genotyper itself)
   TRGT_HIP_TRY(c, hipGetLastError());
   tl_mark(c, "genotyper launched");
   // Two ways to order the HMM of the settled loci and the repair of the others: one HMM batch behind the repair (default), or -- split_hmm,
@@ -1326,16 +1364,7 @@ int LocusCall::repair_chain() {
                     (uint32_t*)rb.vscr, (uint8_t*)rb.vout, (uint32_t*)rb.vlen};
   hipLaunchKernelGGL(vote::consensus_vote_kernel, dim3((unsigned)rp.cap_groups), dim3(vote::VOTE_THREADS), 0, c->stream, va);
   const gt::FinishArgs fa{(const uint8_t*)rb.vout, (const uint32_t*)rb.vlen};
-  const dim3 fgrid((unsigned)nl);
-  if (snv_dev) k_repair_finish_snv.launch(!small_gt, presel, fgrid, c->stream, snv_args(), fa);
-  else if (flank_dev) k_repair_finish_flank.launch(!small_gt, presel, fgrid, c->stream, flank_args(), fa);
-  else k_repair_finish.launch(!small_gt, presel, fgrid, c->stream, ga, fa);
-  if (!gsd_list.empty()) {
-    ds.c.g = ga;
-    if (snv_dev) hipLaunchKernelGGL((gtd::deep_size_finish_kernel<true, true>), dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_snv_args(), fa);
-    else if (flank_dev) hipLaunchKernelGGL(gtd::deep_size_finish_kernel<true>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, deep_flank_args(), fa);
-    else hipLaunchKernelGGL(gtd::deep_size_finish_kernel<false>, dim3(ds.c.n_list), dim3(cld::DW), 0, c->stream, ds, fa);
-  }
+  launch_finish_kernels(fa);
   TRGT_HIP_TRY(c, hipGetLastError());
   if ((rc = dbg_sync("vote + finish"))) return rc;
   tl_mark(c, "repair chain enqueued");
@@ -1369,13 +1398,12 @@ int LocusCall::cluster_chain(int deep) {
   // opted in; it adds a third consensus round, and only then do the arenas and the job / group / length lists grow from two parts to three
   // ... and its SNV branch (the SNV forms of the same kernels).  The groups of that branch overlap -- a read can be a member of both -- so
   // the third part of the job list (and of the CIGAR lengths beside it) then has room for two jobs per read: a fourth part's worth
-  const bool snv_route = !deep && snv_cl_dev;
-  const bool route = (!deep && flank_cl_dev) || snv_route;
-  if (route) cf_route = true;  // (read by wait_stage_a)
-  if (snv_route) cf_snv = true;
+  const bool snv_route = !deep && fits[FR_CLUSTER_SNV];
+  const bool route = !deep && cluster_route_fits();
   // ... and the tag branch behind the deep chain (locus_cluster_flank_deep.hpp): a third round for the deep list, sized the same way
-  const bool deep_route = deep && flank_cld_dev;
-  if (deep_route) cfd_route = true;  // (read by wait_stage_a)
+  const bool deep_route = deep && fits[FR_CLUSTER_DEEP_TAG];
+  if (deep) ran[FR_CLUSTER_DEEP_TAG] = deep_route;  // (read by wait_stage_a)
+  else { ran[FR_CLUSTER_TAG] = fits[FR_CLUSTER_TAG]; ran[FR_CLUSTER_SNV] = fits[FR_CLUSTER_SNV]; }
   const uint64_t rounds = snv_route ? 4 : (route || deep_route) ? 3 : 2;
   // arenas for the consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
   ca.cap_cigar = std::min<uint64_t>(rounds * cl_reads * (2ull * max_seg + 1), 96ull << 20);   // words
@@ -1455,46 +1483,48 @@ int LocusCall::cluster_chain(int deep) {
   if ((rc = ed_launch(ca.ed2_jobs, 2 * cl_reads, ca.counts + cl::CC_ED2, (const uint8_t*)d_vout, ca.escore2))) return rc;
   step(cld::deep_finish_kernel, k_cluster_finish);
   TRGT_HIP_TRY(c, hipGetLastError());
-  if (route) {
-    // ---- genotype_flank's tag branch for the loci the chain completed with two close alleles: settled at once, or behind a third
-    //      consensus round over the third part of the lists (usually short: the groups without a majority sequence)
+  // ---- genotype_flank for the loci the chain completed with two close alleles: settled at once by the route's kernel, or behind a third
+  //      consensus round over the third part of the lists (usually short: the groups without a majority sequence) by its finish kernel.
+  //      fa: the route's arguments but for the two buffers taken here -- the records of the loci that wait for the round (pend_slot; the
+  //      SNV forms keep pend_hap behind them) and the count block (the call's zero arena, else count_slot cleared by a kernel), whose
+  //      words j3 / g3 count the round's jobs and groups; `words` of it come back with the slab at o_counts.  parts: of the job list
+  auto third_round = [&](auto fa, int pend_slot, int count_slot, uint32_t j3, uint32_t g3, uint32_t words, size_t o_counts, int64_t parts, auto&& route_kernel, auto&& finish_kernel) -> int {
+    constexpr bool snv_forms = std::is_same_v<decltype(fa), clf::ClSnvArgs>;
     void *d_fc = nullptr, *d_fp = nullptr;
-    if ((rc = dev_get(c, S_CLF_PEND, (size_t)n_cl * (sizeof(clf::ClFlankPend) + (snv_route ? 8 : 0)), &d_fp))) return rc;  // (SNV forms: pend_hap behind the records)
-    void* const z_cfc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
-    if (!z_cfc && (rc = dev_get(c, S_CLF_COUNTS, 256, &d_fc))) return rc;
-    clf::ClFlankArgs fa{ca, g.hp, (uint8_t*)slab.d(o_fdone), z_cfc ? (uint32_t*)z_cfc : (uint32_t*)d_fc, (clf::ClFlankPend*)d_fp, 2 * ca.cap_j, 2 * ca.cap_g};
-    if (!z_cfc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, fa.fcounts, (uint32_t)clf::CF_WORDS);
+    if (int r = dev_get(c, pend_slot, (size_t)n_cl * (sizeof(clf::ClFlankPend) + (snv_forms ? 8 : 0)), &d_fp)) return r;
+    void* const z_cfc = zero_take(c, 256);
+    if (!z_cfc) if (int r = dev_get(c, count_slot, 256, &d_fc)) return r;
+    fa.fcounts = z_cfc ? (uint32_t*)z_cfc : (uint32_t*)d_fc; fa.pend = (clf::ClFlankPend*)d_fp;
+    if constexpr (snv_forms) fa.pend_hap = (int32_t*)(fa.pend + n_cl);
+    if (!z_cfc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, fa.fcounts, words);
+    route_kernel(fa);
+    TRGT_HIP_TRY(c, hipGetLastError());
+    if (int r = cons_launch(fa.first_job, fa.fcounts + j3, fa.first_group, fa.fcounts + g3, parts)) return r;
+    finish_kernel(fa);
+    TRGT_HIP_TRY(c, hipGetLastError());
+    TRGT_HIP_TRY(c, hipMemcpyAsync(slab.d(o_counts), fa.fcounts, words * 4, hipMemcpyDeviceToDevice, c->stream));
+    return TRGT_OK;
+  };
+  const clf::ClFlankArgs fa{ca, g.hp, (uint8_t*)slab.d(o_fdone), nullptr, nullptr, 2 * ca.cap_j, 2 * ca.cap_g};
+  if (snv_route) {  // the SNV forms, which also run the tag branch (the three logarithms are the host's: flank_split's own)
     clf::ClSnvArgs sa;
-    if (snv_route) {  // (the three logarithms are the host's: flank_split's own)
-      static_cast<clf::ClFlankArgs&>(sa) = fa;
-      sa.start_offset = g.so; sa.end_offset = g.eo; sa.mismatch_offsets = g.mm; sa.mismatch_off = g.mm_off; sa.snv_read = (uint8_t*)g.snv_read; sa.pend_hap = (int32_t*)((clf::ClFlankPend*)d_fp + n_cl);
-      sa.ln_match = std::log(0.9); sa.ln_mis = std::log(1.0 - 0.9); sa.ln2 = std::log(2.0); sa.tag_route = flank_cl_dev ? 1 : 0;
-      k_cluster_flank_snv.launch(big, presel, cgrid, c->stream, sa);
-    } else k_cluster_flank.launch(big, presel, cgrid, c->stream, fa);
-    TRGT_HIP_TRY(c, hipGetLastError());
-    if ((rc = cons_launch(2 * ca.cap_j, fa.fcounts + clf::CF_J3, 2 * ca.cap_g, fa.fcounts + clf::CF_G3, snv_route ? 2 : 1))) return rc;
-    if (snv_route) k_cluster_flank_finish_snv.launch(big, presel, cgrid, c->stream, sa);
-    else k_cluster_flank_finish.launch(big, presel, cgrid, c->stream, fa);
-    TRGT_HIP_TRY(c, hipGetLastError());
-    TRGT_HIP_TRY(c, hipMemcpyAsync(slab.d(o_cfc), fa.fcounts, clf::CF_WORDS * 4, hipMemcpyDeviceToDevice, c->stream));  // (the counts come back with the slab)
+    static_cast<clf::ClFlankArgs&>(sa) = fa;
+    sa.start_offset = g.so; sa.end_offset = g.eo; sa.mismatch_offsets = g.mm; sa.mismatch_off = g.mm_off; sa.snv_read = (uint8_t*)g.snv_read;
+    sa.ln_match = std::log(0.9); sa.ln_mis = std::log(1.0 - 0.9); sa.ln2 = std::log(2.0); sa.tag_route = fits[FR_CLUSTER_TAG] ? 1 : 0;
+    rc = third_round(sa, S_CLF_PEND, S_CLF_COUNTS, clf::CF_J3, clf::CF_G3, clf::CF_WORDS, o_cfc, 2,
+                     [&](const clf::ClSnvArgs& a) { k_cluster_flank_snv.launch(big, presel, cgrid, c->stream, a); },
+                     [&](const clf::ClSnvArgs& a) { k_cluster_flank_finish_snv.launch(big, presel, cgrid, c->stream, a); });
+  } else if (route) {
+    rc = third_round(fa, S_CLF_PEND, S_CLF_COUNTS, clf::CF_J3, clf::CF_G3, clf::CF_WORDS, o_cfc, 1,
+                     [&](const clf::ClFlankArgs& a) { k_cluster_flank.launch(big, presel, cgrid, c->stream, a); },
+                     [&](const clf::ClFlankArgs& a) { k_cluster_flank_finish.launch(big, presel, cgrid, c->stream, a); });
+  } else if (deep_route) {
+    // (the deep list, one workgroup per locus: its own records and counts -- both lists can be on their route in one call)
+    rc = third_round(cldf::DeepClFlankArgs{da, fa.hp_tag, fa.flank_done, nullptr, nullptr, fa.first_job, fa.first_group}, S_CLDF_PEND, S_CLDF_COUNTS, cldf::DF_J3, cldf::DF_G3, cldf::DF_WORDS, o_cfdc, 1,
+                     [&](const cldf::DeepClFlankArgs& a) { hipLaunchKernelGGL(cldf::deep_cluster_flank_kernel, cgrid, dim3(cld::DW), 0, c->stream, a); tl_mark(c, "deep cluster flank kernel enqueued"); },
+                     [&](const cldf::DeepClFlankArgs& a) { hipLaunchKernelGGL(cldf::deep_cluster_flank_finish_kernel, cgrid, dim3(cld::DW), 0, c->stream, a); });
   }
-  if (deep_route) {
-    // ---- the same branch for the deep list, one workgroup per locus: its own records, its own counts (both lists can be on their route
-    //      in one call), the deep list's arenas and the third part of its job / group lists
-    void *d_fc = nullptr, *d_fp = nullptr;
-    if ((rc = dev_get(c, S_CLDF_PEND, (size_t)n_cl * sizeof(clf::ClFlankPend), &d_fp))) return rc;
-    void* const z_cfc = zero_take(c, 256);  // (cleared with the call's zero arena; else by the kernel below)
-    if (!z_cfc && (rc = dev_get(c, S_CLDF_COUNTS, 256, &d_fc))) return rc;
-    cldf::DeepClFlankArgs fa{da, g.hp, (uint8_t*)slab.d(o_fdone), z_cfc ? (uint32_t*)z_cfc : (uint32_t*)d_fc, (clf::ClFlankPend*)d_fp, 2 * ca.cap_j, 2 * ca.cap_g};
-    if (!z_cfc) hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(64), 0, c->stream, fa.fcounts, (uint32_t)cldf::DF_WORDS);
-    hipLaunchKernelGGL(cldf::deep_cluster_flank_kernel, cgrid, dim3(cld::DW), 0, c->stream, fa);
-    TRGT_HIP_TRY(c, hipGetLastError());
-    tl_mark(c, "deep cluster flank kernel enqueued");
-    if ((rc = cons_launch(2 * ca.cap_j, fa.fcounts + cldf::DF_J3, 2 * ca.cap_g, fa.fcounts + cldf::DF_G3))) return rc;
-    hipLaunchKernelGGL(cldf::deep_cluster_flank_finish_kernel, cgrid, dim3(cld::DW), 0, c->stream, fa);
-    TRGT_HIP_TRY(c, hipGetLastError());
-    TRGT_HIP_TRY(c, hipMemcpyAsync(slab.d(o_cfdc), fa.fcounts, cldf::DF_WORDS * 4, hipMemcpyDeviceToDevice, c->stream));  // (the counts come back with the slab)
-  }
+  if (rc) return rc;
   tl_mark(c, deep ? "deep cluster chain enqueued" : "cluster chain enqueued");
   cl_counts_dev[deep] = ca.counts;
   return TRGT_OK;
@@ -1527,6 +1557,30 @@ int LocusCall::enqueue_results() {
   if ((rc = issue_pending_uploads(c))) return rc;  // the next batch's bytes: behind this call's tables and models, next to stage A
   return TRGT_OK;
 }
+// The statistics of route r from the bytes its kernels left (FL_*, locus_gt.hpp).  list: the loci they wrote (nullptr: every locus that is
+// not a cluster locus); snv: FL_SNV for an SNV branch, 0 for a tag branch -- a byte of the other branch is that route's to count.
+// [0] settled on the device, [1] repaired among them, [2] handed back, [3] handed back undecided (SNV branches); a settled size locus of
+// more than GT_MAX_READS reads is also the deep size list's: [3] of the tag route, which has no undecided loci, and
+// trgt_hip_size_deep_stats[3] for the SNV route.
+// One test serves both branches.  In all four headers that write the byte (locus_gt.hpp, locus_gt_deep.hpp, locus_cluster_flank.hpp,
+// locus_cluster_flank_deep.hpp) FL_UNDECIDED is stored only by the handed() of the SNV forms, together with FL_SNV, and every store of
+// FL_HANDED is `FL_HANDED | mark` (mark = 0 for the tag branch, FL_SNV for the other) or plain FL_HANDED: a tag-branch byte that has
+// FL_HANDED has no other bit set, so `& FL_HANDED` behind the FL_UNDECIDED test counts what `== FL_HANDED` counted.
+void LocusCall::tally_route(FlankRoute r, const std::vector<uint32_t>* list, uint8_t snv, const uint8_t* fdone, const uint8_t* need) {
+  int64_t* const st = c->route[r].stats;
+  const int64_t n = list ? (int64_t)list->size() : nl;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t l = list ? (int64_t)(*list)[(size_t)i] : i;
+    const uint8_t b = fdone[l];
+    if ((!list && is_cluster(l)) || (b & gt::FL_SNV) != snv) continue;
+    if ((b & gt::FL_DONE) && !need[l]) {
+      st[0] += 1; if (b & gt::FL_REPAIRED) st[1] += 1;
+      if (!list && in->locus_read_begin[l + 1] - in->locus_read_begin[l] > (uint64_t)gt::GT_MAX_READS) (snv ? c->size_deep_stats[3] : st[3]) += 1;
+    }
+    else if (b & gt::FL_UNDECIDED) st[3] += 1;
+    else if (b & gt::FL_HANDED) st[2] += 1;
+  }
+}
 int LocusCall::wait_stage_a() {
   { const hipError_t ea = trgt::event_wait(evA);
     if (g_trace_dump && TRGT_DEV_ENV("TRGT_REPAIR_TRACE")) { const uint32_t* h = g_trace_dump; fprintf(stderr, "[repair trace] evA %s counts:", hipGetErrorString(ea)); for (int i = 0; i < 16; ++i) fprintf(stderr, " %u", h[i]);
@@ -1554,19 +1608,19 @@ int LocusCall::wait_stage_a() {
       // (not the loci whose genotype the FLANK forms of the device genotyper already replaced by the tag split)
       const int32_t* nal = (const int32_t*)gh.nal; const uint32_t* alen = (const uint32_t*)gh.alen; const int32_t* rank = (const int32_t*)gh.rank;
       // (the byte of a locus is read only where a kernel wrote it: every locus with the FLANK size kernels, the shallow cluster list with the
-      //  cluster route; a cluster locus has a byte of the cluster route's or none)
       //  cluster route; a cluster locus has a byte of the cluster route's or none.  The SNV forms write every locus' byte as well, and
       //  add FL_NOSPLIT: both branches of flank_split were evaluated on the device and neither splits the reads)
       //  The deep cluster route (locus_cluster_flank_deep.hpp) writes the bytes of the loci admitted to the deep list, and only theirs: a
       //  deep locus beyond the setting or without room in the pair budget never had its byte written.
-      const uint8_t* fdone = flank_dev || snv_dev || cf_route || cfd_route ? (const uint8_t*)slab.h(o_fdone) : nullptr;
+      const bool size_ran = ran[FR_SIZE_TAG] || ran[FR_SIZE_SNV], cluster_ran = ran[FR_CLUSTER_TAG] || ran[FR_CLUSTER_SNV], deep_ran = ran[FR_CLUSTER_DEEP_TAG];
+      const uint8_t* fdone = size_ran || cluster_ran || deep_ran ? (const uint8_t*)slab.h(o_fdone) : nullptr;
       std::vector<uint8_t> on_deep_list;
-      if (cfd_route) { on_deep_list.assign((size_t)nl, 0); for (const uint32_t l : cld_list) on_deep_list[l] = 1; }
+      if (deep_ran) { on_deep_list.assign((size_t)nl, 0); for (const uint32_t l : cld_list) on_deep_list[l] = 1; }
       auto fl_byte = [&](int64_t l) -> uint8_t {
-        if (!is_cluster(l)) return flank_dev || snv_dev ? fdone[l] : (uint8_t)0;
+        if (!is_cluster(l)) return size_ran ? fdone[l] : (uint8_t)0;
         const uint64_t n = in->locus_read_begin[l + 1] - in->locus_read_begin[l];
-        if (n > (uint64_t)gt::GT_MAX_READS) return cfd_route && on_deep_list[(size_t)l] ? fdone[l] : (uint8_t)0;
-        return cf_route && in->ploidy[l] != 0 && n > 0 ? fdone[l] : (uint8_t)0;
+        if (n > (uint64_t)gt::GT_MAX_READS) return deep_ran && on_deep_list[(size_t)l] ? fdone[l] : (uint8_t)0;
+        return cluster_ran && in->ploidy[l] != 0 && n > 0 ? fdone[l] : (uint8_t)0;
       };
       std::atomic<int64_t> sent{0};
       pool->parallel_for(nl, 64, [&](int64_t l, int) {
@@ -1577,54 +1631,22 @@ int LocusCall::wait_stage_a() {
         FlankSplit sp;
         if (flank_split(flank_meta, order.data(), order.size(), sp)) { need[l] = 1; sent += 1; }
       });
-      if (cf_snv) {  // trgt_hip_snv_cluster_stats: the bytes the SNV branch of the route left
-        for (const uint32_t l : cl_list) {
-          const uint8_t b = fdone[l];
-          if (!(b & gt::FL_SNV)) continue;
-          if ((b & gt::FL_DONE) && !need[l]) { c->snv_cluster_stats[0] += 1; if (b & gt::FL_REPAIRED) c->snv_cluster_stats[1] += 1; }
-          else if (b & gt::FL_UNDECIDED) c->snv_cluster_stats[3] += 1;
-          else if (b & gt::FL_HANDED) c->snv_cluster_stats[2] += 1;
-        }
-      }
-      if (cf_route) {  // trgt_hip_flank_cluster_stats (never a locus of the SNV branch)
-        for (const uint32_t l : cl_list) {
-          if (fdone[l] & gt::FL_SNV) continue;  // trgt_hip_snv_cluster_stats'
-          if ((fdone[l] & gt::FL_DONE) && !need[l]) { c->flank_cluster_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_cluster_stats[1] += 1; }
-          else if (fdone[l] == gt::FL_HANDED) c->flank_cluster_stats[2] += 1;
-        }
+      // the statistics: each route counts the bytes of its branch (FL_SNV or not) among the loci its kernels wrote -- the shallow cluster
+      // list, the deep one, every size locus (nullptr)
+      if (ran[FR_CLUSTER_SNV]) tally_route(FR_CLUSTER_SNV, &cl_list, gt::FL_SNV, fdone, need);
+      if (cluster_ran) {  // (whichever of the two settings ran the kernels: they share the third round and its count block)
+        tally_route(FR_CLUSTER_TAG, &cl_list, 0, fdone, need);
         stat_cons_jobs += (int64_t)((const uint32_t*)slab.h(o_cfc))[clf::CF_J3];  // consensus alignments of the third round
       }
-      if (cfd_route) {  // trgt_hip_flank_cluster_deep_stats: the loci of the deep list, which are in no other count
-        for (const uint32_t l : cld_list) {
-          if ((fdone[l] & gt::FL_DONE) && !need[l]) { c->flank_cluster_deep_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_cluster_deep_stats[1] += 1; }
-          else if (fdone[l] == gt::FL_HANDED) c->flank_cluster_deep_stats[2] += 1;
-        }
+      if (deep_ran) {  // (the loci of the deep list, which are in no other count)
+        tally_route(FR_CLUSTER_DEEP_TAG, &cld_list, 0, fdone, need);
         stat_cons_jobs += (int64_t)((const uint32_t*)slab.h(o_cfdc))[cldf::DF_J3];  // consensus alignments of the deep list's third round
       }
-      if (flank_dev) {  // trgt_hip_flank_stats (never a cluster locus in [0], [1], [3])
-        for (int64_t l = 0; l < nl; ++l) {
-          if (is_cluster(l)) continue;
-          if (fdone[l] & gt::FL_SNV) continue;  // trgt_hip_snv_split_stats'
-          if ((fdone[l] & gt::FL_DONE) && !need[l]) {
-            c->flank_stats[0] += 1; if (fdone[l] & gt::FL_REPAIRED) c->flank_stats[1] += 1;
-            if (in->locus_read_begin[l + 1] - in->locus_read_begin[l] > (uint64_t)gt::GT_MAX_READS) c->flank_stats[3] += 1;  // the deep size list's
-          }
-          else if (fdone[l] == gt::FL_HANDED) c->flank_stats[2] += 1;
-        }
-        c->flank_stats[2] += sent.load();
+      if (ran[FR_SIZE_TAG]) {
+        tally_route(FR_SIZE_TAG, nullptr, 0, fdone, need);
+        c->route[FR_SIZE_TAG].stats[2] += sent.load();
       }
-      if (snv_dev) {  // trgt_hip_snv_split_stats: the bytes the SNV branch of the one-wave kernels and of the deep size list's SNV forms left
-        for (int64_t l = 0; l < nl; ++l) {
-          const uint8_t b = fdone[l];
-          if (is_cluster(l) || !(b & gt::FL_SNV)) continue;
-          if ((b & gt::FL_DONE) && !need[l]) {
-            c->snv_split_stats[0] += 1; if (b & gt::FL_REPAIRED) c->snv_split_stats[1] += 1;
-            if (in->locus_read_begin[l + 1] - in->locus_read_begin[l] > (uint64_t)gt::GT_MAX_READS) c->size_deep_stats[3] += 1;  // trgt_hip_size_deep_stats: the deep size list's
-          }
-          else if (b & gt::FL_UNDECIDED) c->snv_split_stats[3] += 1;
-          else if (b & gt::FL_HANDED) c->snv_split_stats[2] += 1;
-        }
-      }
+      if (ran[FR_SIZE_SNV]) tally_route(FR_SIZE_SNV, nullptr, gt::FL_SNV, fdone, need);
     }
     for (int64_t l = 0; l < nl; ++l) if (need[l]) R.push_back(l);
     // an alignment job of a device-built list that the generic kernel refused (longer than the workspace planned from the batch's maxima)
@@ -2273,62 +2295,27 @@ extern "C" int trgt_hip_size_deep_stats(const trgt_hip_ctx* c, int64_t out[4]) {
   return TRGT_OK;
 }
 
-// ---- the haplotype-tag branch of genotype_flank inside the device genotyper is opt-in per context as well (locus_gt.hpp, FLANK forms)
-extern "C" int trgt_hip_set_flank_device(trgt_hip_ctx* c, int on) {
+// ---- the device routes of genotype_flank are opt-in per context as well (FlankRoute, common.hpp): one setter and one statistics call each
+static int route_set(trgt_hip_ctx* c, FlankRoute r, int on) {
   if (!c) return TRGT_ERR_INVALID;
-  c->flank_device = on != 0;
+  c->route[r].on = on != 0;
   return TRGT_OK;
 }
-extern "C" int trgt_hip_flank_stats(const trgt_hip_ctx* c, int64_t out[4]) {
+static int route_stats(const trgt_hip_ctx* c, FlankRoute r, int n, int64_t* out) {
   if (!c || !out) return TRGT_ERR_INVALID;
-  for (int i = 0; i < 4; ++i) out[i] = c->flank_stats[i];
+  for (int i = 0; i < n; ++i) out[i] = c->route[r].stats[i];
   return TRGT_OK;
 }
-
-// ---- ... and the SNV branch of genotype_flank, a setting of its own (locus_gt.hpp, SNV forms)
-extern "C" int trgt_hip_set_snv_split_device(trgt_hip_ctx* c, int on) {
-  if (!c) return TRGT_ERR_INVALID;
-  c->snv_split_device = on != 0;
-  return TRGT_OK;
-}
-extern "C" int trgt_hip_snv_split_stats(const trgt_hip_ctx* c, int64_t out[4]) {
-  if (!c || !out) return TRGT_ERR_INVALID;
-  for (int i = 0; i < 4; ++i) out[i] = c->snv_split_stats[i];
-  return TRGT_OK;
-}
-
-// ---- ... and behind the one-wave cluster chain, a setting of its own (locus_cluster_flank.hpp)
-extern "C" int trgt_hip_set_snv_cluster_device(trgt_hip_ctx* c, int on) {
-  if (!c) return TRGT_ERR_INVALID;
-  c->snv_cluster_device = on != 0;
-  return TRGT_OK;
-}
-extern "C" int trgt_hip_snv_cluster_stats(const trgt_hip_ctx* c, int64_t out[4]) {
-  if (!c) return TRGT_ERR_INVALID;
-  for (int i = 0; i < 4; ++i) out[i] = c->snv_cluster_stats[i];
-  return TRGT_OK;
-}
-extern "C" int trgt_hip_set_flank_cluster_device(trgt_hip_ctx* c, int on) {
-  if (!c) return TRGT_ERR_INVALID;
-  c->flank_cluster_device = on != 0;
-  return TRGT_OK;
-}
-extern "C" int trgt_hip_flank_cluster_stats(const trgt_hip_ctx* c, int64_t out[3]) {
-  if (!c || !out) return TRGT_ERR_INVALID;
-  for (int i = 0; i < 3; ++i) out[i] = c->flank_cluster_stats[i];
-  return TRGT_OK;
-}
-// ---- ... and behind the deep cluster chain, a setting of its own again (locus_cluster_flank_deep.hpp)
-extern "C" int trgt_hip_set_flank_cluster_deep_device(trgt_hip_ctx* c, int on) {
-  if (!c) return TRGT_ERR_INVALID;
-  c->flank_cluster_deep_device = on != 0;
-  return TRGT_OK;
-}
-extern "C" int trgt_hip_flank_cluster_deep_stats(const trgt_hip_ctx* c, int64_t out[3]) {
-  if (!c || !out) return TRGT_ERR_INVALID;
-  for (int i = 0; i < 3; ++i) out[i] = c->flank_cluster_deep_stats[i];
-  return TRGT_OK;
-}
+extern "C" int trgt_hip_set_flank_device(trgt_hip_ctx* c, int on) { return route_set(c, FR_SIZE_TAG, on); }
+extern "C" int trgt_hip_flank_stats(const trgt_hip_ctx* c, int64_t out[4]) { return route_stats(c, FR_SIZE_TAG, 4, out); }
+extern "C" int trgt_hip_set_snv_split_device(trgt_hip_ctx* c, int on) { return route_set(c, FR_SIZE_SNV, on); }
+extern "C" int trgt_hip_snv_split_stats(const trgt_hip_ctx* c, int64_t out[4]) { return route_stats(c, FR_SIZE_SNV, 4, out); }
+extern "C" int trgt_hip_set_flank_cluster_device(trgt_hip_ctx* c, int on) { return route_set(c, FR_CLUSTER_TAG, on); }
+extern "C" int trgt_hip_flank_cluster_stats(const trgt_hip_ctx* c, int64_t out[3]) { return route_stats(c, FR_CLUSTER_TAG, 3, out); }
+extern "C" int trgt_hip_set_snv_cluster_device(trgt_hip_ctx* c, int on) { return route_set(c, FR_CLUSTER_SNV, on); }
+extern "C" int trgt_hip_snv_cluster_stats(const trgt_hip_ctx* c, int64_t out[4]) { return route_stats(c, FR_CLUSTER_SNV, 4, out); }
+extern "C" int trgt_hip_set_flank_cluster_deep_device(trgt_hip_ctx* c, int on) { return route_set(c, FR_CLUSTER_DEEP_TAG, on); }
+extern "C" int trgt_hip_flank_cluster_deep_stats(const trgt_hip_ctx* c, int64_t out[3]) { return route_stats(c, FR_CLUSTER_DEEP_TAG, 3, out); }
 
 extern "C" int trgt_locus_batch(trgt_hip_ctx* c, const trgt_locus_params* p, const trgt_locus_batch_in* in, trgt_locus_batch_out* out) {
   TRGT_ABI_GUARD(c, locus_batch_run(c, p, in, out, nullptr, nullptr, nullptr));

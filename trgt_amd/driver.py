@@ -27,27 +27,10 @@ class ChunkDriver:
         self._run = run_fn or (lambda ctx, chunk, params, kw: locus.run_batch(chunk, params, ctx, **kw))
         self.devices = list(devices)
         self.contexts = [self._make(d) for d in self.devices]
-        if cluster_max_reads is not None:  # deep Genotyper::Cluster loci on the device (Context.set_cluster_max_reads), in every context
-            for c in self.contexts:
-                c.set_cluster_max_reads(cluster_max_reads)
-        if size_max_reads is not None:  # deep Genotyper::Size loci on the device (Context.set_size_max_reads), likewise
-            for c in self.contexts:
-                c.set_size_max_reads(size_max_reads)
-        if flank_device is not None:  # the haplotype-tag branch of genotype_flank inside the device genotyper (Context.set_flank_device), likewise
-            for c in self.contexts:
-                c.set_flank_device(flank_device)
-        if flank_cluster_device is not None:  # ... and behind the one-wave cluster chain (Context.set_flank_cluster_device), likewise
-            for c in self.contexts:
-                c.set_flank_cluster_device(flank_cluster_device)
-        if flank_cluster_deep_device is not None:  # ... and behind the deep cluster chain (Context.set_flank_cluster_deep_device; it follows cluster_max_reads), likewise
-            for c in self.contexts:
-                c.set_flank_cluster_deep_device(flank_cluster_deep_device)
-        if snv_split_device is not None:  # ... and the SNV branch inside the size genotyper (Context.set_snv_split_device: one-wave loci, and with size_max_reads the deep ones), likewise
-            for c in self.contexts:
-                c.set_snv_split_device(snv_split_device)
-        if snv_cluster_device is not None:  # ... and behind the one-wave cluster chain (Context.set_snv_cluster_device), likewise
-            for c in self.contexts:
-                c.set_snv_cluster_device(snv_cluster_device)
+        # the settings, in every context (what each means: the docstrings of the Context methods)
+        _lib.apply_settings(self.contexts, ((cluster_max_reads, "set_cluster_max_reads"), (size_max_reads, "set_size_max_reads"), (flank_device, "set_flank_device"),
+                                            (flank_cluster_device, "set_flank_cluster_device"), (flank_cluster_deep_device, "set_flank_cluster_deep_device"),
+                                            (snv_split_device, "set_snv_split_device"), (snv_cluster_device, "set_snv_cluster_device")))
         self.chunks_by_context = [0] * len(self.contexts)
 
     def close(self):
