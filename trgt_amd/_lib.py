@@ -90,6 +90,8 @@ CLUSTER_FLANK_EXPORTS = ["trgt_hip_set_flank_cluster_device", "trgt_hip_flank_cl
 CLUSTER_SNV_EXPORTS = ["trgt_hip_set_snv_cluster_device", "trgt_hip_snv_cluster_stats"]
 # ... and the two of the tag branch behind the DEEP cluster chain (locus_cluster_flank_deep.hpp), a list of its own for the same reasons
 CLUSTER_DEEP_FLANK_EXPORTS = ["trgt_hip_set_flank_cluster_deep_device", "trgt_hip_flank_cluster_deep_stats"]
+# ... and the two of the SNV branch behind the deep chain (the SNV forms of the same header), checked the same way
+CLUSTER_DEEP_SNV_EXPORTS = ["trgt_hip_set_snv_cluster_deep_device", "trgt_hip_snv_cluster_deep_stats"]
 
 # The opt-in device routes of genotype_flank (FlankRoute, csrc/common.hpp): (name, C setter, C statistics call, its width, docstring of
 # Context.set_<name>_device, docstring of Context.<statistics name without trgt_hip_>).  Context gets the two methods of every row below.
@@ -132,6 +134,20 @@ ROUTES = [
      """trgt_hip_snv_cluster_stats of the context's last trgt_locus_batch: (cluster loci whose genotype the device replaced through the
         SNV branch, those among them with a repaired group, loci handed back for room or limits, loci handed back undecided)."""),
 ]
+# The sixth route, in a table of its own with the same row shape (tests/test_flank_routes_api.py holds ROUTES to its five rows): Context gets
+# the two methods of every row here as well.
+DEEP_SNV_ROUTES = [
+    ("snv_cluster_deep", "trgt_hip_set_snv_cluster_deep_device", "trgt_hip_snv_cluster_deep_stats", 4,
+     """trgt_hip_set_snv_cluster_deep_device: the SNV branch of genotype_flank (genotype_flank.rs:78-138, 171-290) behind the DEEP cluster
+        chain, for the Genotyper::Cluster loci of 257 to set_cluster_max_reads candidate reads of batches that carry mismatch offsets (off,
+        the default: the host redoes a locus whose SNVs split its reads).  It follows the deep chain, so it does nothing on a context
+        without set_cluster_max_reads.  Tags that split the reads come first (set_flank_cluster_deep_device, else the host); a locus whose
+        candidate search is not decided beyond the margin, or that is beyond the route's limits, goes to the host path as before.
+        Independent of the other settings.  Every later call on this context uses it.""",
+     """trgt_hip_snv_cluster_deep_stats of the context's last trgt_locus_batch: (deep cluster loci whose genotype the device replaced
+        through the SNV branch, those among them with a repaired group, loci handed back for room or limits, loci handed back
+        undecided)."""),
+]
 
 
 def apply_settings(contexts, pairs):
@@ -170,6 +186,7 @@ def lib():
             pass
         L = C.CDLL(_SO)
         missing = [n for n in EXPORTS + CLUSTER_FLANK_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_SNV_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_DEEP_FLANK_EXPORTS if not hasattr(L, n)]
+        missing += [n for n in CLUSTER_DEEP_SNV_EXPORTS if not hasattr(L, n)]
         if missing:
             raise TrgtHipError("%s does not export %s (stale build?)" % (_SO, ", ".join(missing)))
         L.trgt_hip_last_error.restype = C.c_char_p
@@ -186,7 +203,7 @@ def lib():
         L.trgt_hip_size_max_reads_limit.restype = C.c_int32
         L.trgt_hip_set_size_max_reads.argtypes = [_VP, C.c_int32]
         L.trgt_hip_size_deep_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
-        for _, setter, stats, _, _, _ in ROUTES:
+        for _, setter, stats, _, _, _ in ROUTES + DEEP_SNV_ROUTES:
             getattr(L, setter).argtypes = [_VP, C.c_int]
             getattr(L, stats).argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_hip_timing_enable.argtypes = [_VP, C.c_int]
@@ -295,14 +312,14 @@ def _route_methods(name, setter, stats, width, set_doc, stats_doc):
         setattr(Context, fname, f)
 
 
-for _row in ROUTES:
+for _row in ROUTES + DEEP_SNV_ROUTES:
     _route_methods(*_row)
 
 
 class Pool:
     """trgt_hip_pool: several contexts (devices[i] = ordinal of context i, ordinals may repeat) behind one queue of batches."""
 
-    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, flank_cluster_deep_device=None, snv_split_device=None, snv_cluster_device=None):
+    def __init__(self, devices, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, flank_cluster_deep_device=None, snv_split_device=None, snv_cluster_deep_device=None, snv_cluster_device=None):
         L = lib()
         L.trgt_hip_pool_create.argtypes = [C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]
         L.trgt_hip_pool_destroy.argtypes = [C.c_void_p]
@@ -328,7 +345,8 @@ class Pool:
             self.contexts.append(c)
         apply_settings(self.contexts, ((cluster_max_reads, "set_cluster_max_reads"), (size_max_reads, "set_size_max_reads"), (flank_device, "set_flank_device"),
                                        (flank_cluster_device, "set_flank_cluster_device"), (flank_cluster_deep_device, "set_flank_cluster_deep_device"),
-                                       (snv_split_device, "set_snv_split_device"), (snv_cluster_device, "set_snv_cluster_device")))
+                                       (snv_split_device, "set_snv_split_device"), (snv_cluster_deep_device, "set_snv_cluster_deep_device"),
+                                       (snv_cluster_device, "set_snv_cluster_device")))
 
     def run_many(self, params_struct, cins, couts, out_per_context=False):
         """cins / couts: lists of LocusBatchIn / LocusBatchOut structures (couts: one per batch, or one per context)"""

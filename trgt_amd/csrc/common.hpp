@@ -116,6 +116,8 @@ enum FlankRoute {
                         // cluster loci, counted like FR_SIZE_SNV
   FR_CLUSTER_DEEP_TAG,  // trgt_hip_set_flank_cluster_deep_device: the tag branch behind the deep cluster chain (locus_cluster_flank_deep.hpp).
                         // trgt_hip_flank_cluster_deep_stats: deep cluster loci, counted like FR_CLUSTER_TAG
+  FR_CLUSTER_DEEP_SNV,  // trgt_hip_set_snv_cluster_deep_device: the SNV branch behind the deep chain (the SNV forms of locus_cluster_flank_deep.hpp).
+                        // trgt_hip_snv_cluster_deep_stats: deep cluster loci, counted like FR_SIZE_SNV
   FR_N
 };
 struct FlankRouteState { bool on = false; int64_t stats[4] = {0, 0, 0, 0}; };
@@ -296,7 +298,7 @@ enum Slot {
   S_GSD_LIST,  // the deep list of the size genotyper (locus_gt_deep.hpp)
   S_GT_HP,     // the reads' haplotype tags for the FLANK forms of the device genotyper (locus_gt.hpp)
   S_SNV_SO, S_SNV_EO, S_SNV_MM, S_SNV_MMOFF, S_SNV_READ,  // the SNV forms' inputs (start / end offsets, mismatch offsets and their table) and per-read byte
-  S_SNV_DEEP,  // the workspace of the deep size list's SNV forms (locus_gt_deep.hpp): per-read masks and staged offsets, one slab
+  S_SNV_DEEP,  // the workspace of the deep lists' SNV forms (locus_gt_deep.hpp, locus_cluster_flank_deep.hpp): per-read masks and staged offsets, one slab
   S_CLF_COUNTS,  // the counters of the tag branch behind the one-wave cluster chain (locus_cluster_flank.hpp)
   S_CLF_PEND,    // ... and its records of the loci that wait for the third consensus round
   S_CLDF_COUNTS, S_CLDF_PEND,  // the same two for the tag branch behind the deep cluster chain (locus_cluster_flank_deep.hpp)

@@ -787,7 +787,8 @@ struct LocusCall {
   void plan_routes();
   bool any_route_fits() const { return std::any_of(fits, fits + FR_N, [](bool b) { return b; }); }      // the per-locus byte joins the slab
   bool cluster_route_fits() const { return fits[FR_CLUSTER_TAG] || fits[FR_CLUSTER_SNV]; }              // one pair of kernels, one count block (o_cfc)
-  bool snv_inputs_up() const { return fits[FR_SIZE_SNV] || fits[FR_CLUSTER_SNV]; }                      // offsets, mismatch lists, the per-read byte
+  bool deep_cluster_route_fits() const { return fits[FR_CLUSTER_DEEP_TAG] || fits[FR_CLUSTER_DEEP_SNV]; }  // likewise for the deep list (o_cfdc)
+  bool snv_inputs_up() const { return fits[FR_SIZE_SNV] || fits[FR_CLUSTER_SNV] || fits[FR_CLUSTER_DEEP_SNV]; }  // offsets, mismatch lists, the per-read byte
   bool tags_up() const { return fits[FR_SIZE_TAG] || fits[FR_CLUSTER_TAG] || fits[FR_CLUSTER_DEEP_TAG] || (snv_inputs_up() && in->hp_tag); }  // (the SNV forms read the tags of a batch that has them: tags come first)
   // the size genotypers' form: one per call, for the one-wave kernels and for the deep size list's
   enum class GtForm { PLAIN, FLANK, SNV };
@@ -937,7 +938,7 @@ void LocusCall::plan_routes() {
   // (the deep cluster route: the context can have a deep cluster list at all -- plan_device_lists decides which loci it holds; the route
   //  runs in cluster_chain(1), which is not reached with an empty list)
   const bool deep_chain = c->cluster_max_reads > gt::GT_MAX_READS && in->genotyper != nullptr && !c->knobs.host_cluster && !c->knobs.split_hmm;
-  const bool batch_has[FR_N] = {tags, snvs, tags, snvs, tags && deep_chain};  // in the order of FlankRoute
+  const bool batch_has[FR_N] = {tags, snvs, tags, snvs, tags && deep_chain, snvs && deep_chain};  // in the order of FlankRoute
   for (int r = 0; r < FR_N; ++r) fits[r] = dev_gt && c->route[r].on && batch_has[r];
 }
 // The call's modes; stage A's inputs and the device genotyper's on their way up (one batch, flushed by flush_uploads); the result slab
@@ -978,7 +979,7 @@ int LocusCall::upload_tables() {
     o_gsz = slab.add(2 * (size_t)nl * 4); o_rpc = slab.add(gt::RC_WORDS * 4); o_skipb = slab.add((size_t)nl); o_clc = slab.add(cl::CC_WORDS * 4); o_cldc = slab.add(cl::CC_WORDS * 4);
     if (any_route_fits()) o_fdone = slab.add((size_t)nl);
     if (cluster_route_fits()) o_cfc = slab.add(clf::CF_WORDS * 4);
-    if (fits[FR_CLUSTER_DEEP_TAG]) o_cfdc = slab.add(cldf::DF_WORDS * 4);
+    if (deep_cluster_route_fits()) o_cfdc = slab.add(cldf::DF_WORDS * 4);
   }
   if ((rc = dev_get(c, S_LOCUS_4, slab.total, &slab.dev)) || (rc = pin_get(c, P_SPAN_S, slab.total, &slab.host))) return rc;
   d_ss = slab.d(o_ss); d_se = slab.d(o_se); d_hl = slab.d(o_hl); d_hr = slab.d(o_hr);
@@ -1043,11 +1044,14 @@ int LocusCall::plan_device_lists() {
       if (n > (uint64_t)gt::GT_MAX_READS && n <= (uint64_t)c->size_max_reads) gsd_list.push_back((uint32_t)l);
     }
     if (!gsd_list.empty() && (rc = dev_in(c, S_GSD_LIST, gsd_list.data(), gsd_list.size(), &d_gsd_list, &ub))) return rc;
-    if (!gsd_list.empty() && fits[FR_SIZE_SNV]) {  // the SNV forms' workspace: two masks per read slot, then room for every mismatch offset of the batch
-      void* ws = nullptr;
-      if ((rc = dev_get(c, S_SNV_DEEP, 16 * (size_t)nr + 4 * (size_t)in->mismatch_off[nr] + 16, &ws))) return rc;
-      g.snv_prof = ws; g.snv_stage = (uint8_t*)ws + 16 * (size_t)nr;
-    }
+  }
+  // the workspace of the deep lists' SNV forms: two masks per read slot, then room for every mismatch offset of the batch.  Taken when either
+  // deep list has a route that reads it, and shared by both in one call: prof, stage and snv_read are indexed by read slot of the batch, the
+  // loci of the two lists are disjoint, and the chains run on one stream
+  if ((!gsd_list.empty() && fits[FR_SIZE_SNV]) || (!cld_list.empty() && fits[FR_CLUSTER_DEEP_SNV])) {
+    void* ws = nullptr;
+    if ((rc = dev_get(c, S_SNV_DEEP, 16 * (size_t)nr + 4 * (size_t)in->mismatch_off[nr] + 16, &ws))) return rc;
+    g.snv_prof = ws; g.snv_stage = (uint8_t*)ws + 16 * (size_t)nr;
   }
   return TRGT_OK;
 }
@@ -1401,10 +1405,12 @@ int LocusCall::cluster_chain(int deep) {
   const bool snv_route = !deep && fits[FR_CLUSTER_SNV];
   const bool route = !deep && cluster_route_fits();
   // ... and the tag branch behind the deep chain (locus_cluster_flank_deep.hpp): a third round for the deep list, sized the same way
-  const bool deep_route = deep && fits[FR_CLUSTER_DEEP_TAG];
-  if (deep) ran[FR_CLUSTER_DEEP_TAG] = deep_route;  // (read by wait_stage_a)
+  // ... and its SNV branch (the SNV forms of those kernels), whose groups overlap in the same way: four parts for the deep list too
+  const bool deep_snv_route = deep && fits[FR_CLUSTER_DEEP_SNV];
+  const bool deep_route = deep && deep_cluster_route_fits();
+  if (deep) { ran[FR_CLUSTER_DEEP_TAG] = fits[FR_CLUSTER_DEEP_TAG]; ran[FR_CLUSTER_DEEP_SNV] = fits[FR_CLUSTER_DEEP_SNV]; }  // (read by wait_stage_a)
   else { ran[FR_CLUSTER_TAG] = fits[FR_CLUSTER_TAG]; ran[FR_CLUSTER_SNV] = fits[FR_CLUSTER_SNV]; }
-  const uint64_t rounds = snv_route ? 4 : (route || deep_route) ? 3 : 2;
+  const uint64_t rounds = (snv_route || deep_snv_route) ? 4 : (route || deep_route) ? 3 : 2;
   // arenas for the consensus rounds at worst-case slots per alignment, bounded: a locus that finds no room takes the host path
   ca.cap_cigar = std::min<uint64_t>(rounds * cl_reads * (2ull * max_seg + 1), 96ull << 20);   // words
   ca.cap_out = std::min<uint64_t>(rounds * (cl_reads + 2ull * n_cl) * ((uint64_t)max_seg + 16) + 64, 256ull << 20);  // bytes
@@ -1489,7 +1495,7 @@ int LocusCall::cluster_chain(int deep) {
   //      SNV forms keep pend_hap behind them) and the count block (the call's zero arena, else count_slot cleared by a kernel), whose
   //      words j3 / g3 count the round's jobs and groups; `words` of it come back with the slab at o_counts.  parts: of the job list
   auto third_round = [&](auto fa, int pend_slot, int count_slot, uint32_t j3, uint32_t g3, uint32_t words, size_t o_counts, int64_t parts, auto&& route_kernel, auto&& finish_kernel) -> int {
-    constexpr bool snv_forms = std::is_same_v<decltype(fa), clf::ClSnvArgs>;
+    constexpr bool snv_forms = std::is_same_v<decltype(fa), clf::ClSnvArgs> || std::is_same_v<decltype(fa), cldf::DeepClSnvArgs>;
     void *d_fc = nullptr, *d_fp = nullptr;
     if (int r = dev_get(c, pend_slot, (size_t)n_cl * (sizeof(clf::ClFlankPend) + (snv_forms ? 8 : 0)), &d_fp)) return r;
     void* const z_cfc = zero_take(c, 256);
@@ -1518,11 +1524,20 @@ int LocusCall::cluster_chain(int deep) {
     rc = third_round(fa, S_CLF_PEND, S_CLF_COUNTS, clf::CF_J3, clf::CF_G3, clf::CF_WORDS, o_cfc, 1,
                      [&](const clf::ClFlankArgs& a) { k_cluster_flank.launch(big, presel, cgrid, c->stream, a); },
                      [&](const clf::ClFlankArgs& a) { k_cluster_flank_finish.launch(big, presel, cgrid, c->stream, a); });
+  } else if (deep_snv_route) {  // (the deep list's SNV forms, which also run its tag branch; the workspace is the one of the deep size list's SNV forms)
+    cldf::DeepClSnvArgs sa;
+    static_cast<cldf::DeepClFlankArgs&>(sa) = cldf::DeepClFlankArgs{da, fa.hp_tag, fa.flank_done, nullptr, nullptr, fa.first_job, fa.first_group};
+    sa.start_offset = g.so; sa.end_offset = g.eo; sa.mismatch_offsets = g.mm; sa.mismatch_off = g.mm_off; sa.snv_read = (uint8_t*)g.snv_read; sa.pend_hap = nullptr;
+    sa.ln_match = std::log(0.9); sa.ln_mis = std::log(1.0 - 0.9); sa.ln2 = std::log(2.0); sa.tag_route = fits[FR_CLUSTER_DEEP_TAG] ? 1 : 0;
+    sa.prof = (uint64_t*)g.snv_prof; sa.stage = (int32_t*)g.snv_stage; sa.stage_cap = in->mismatch_off[nr];
+    rc = third_round(sa, S_CLDF_PEND, S_CLDF_COUNTS, cldf::DF_J3, cldf::DF_G3, cldf::DF_WORDS, o_cfdc, 2,
+                     [&](const cldf::DeepClSnvArgs& a) { hipLaunchKernelGGL(cldf::deep_cluster_flank_kernel<true>, cgrid, dim3(cld::DW), 0, c->stream, a); tl_mark(c, "deep cluster flank kernel enqueued"); },
+                     [&](const cldf::DeepClSnvArgs& a) { hipLaunchKernelGGL(cldf::deep_cluster_flank_finish_kernel<true>, cgrid, dim3(cld::DW), 0, c->stream, a); });
   } else if (deep_route) {
     // (the deep list, one workgroup per locus: its own records and counts -- both lists can be on their route in one call)
     rc = third_round(cldf::DeepClFlankArgs{da, fa.hp_tag, fa.flank_done, nullptr, nullptr, fa.first_job, fa.first_group}, S_CLDF_PEND, S_CLDF_COUNTS, cldf::DF_J3, cldf::DF_G3, cldf::DF_WORDS, o_cfdc, 1,
-                     [&](const cldf::DeepClFlankArgs& a) { hipLaunchKernelGGL(cldf::deep_cluster_flank_kernel, cgrid, dim3(cld::DW), 0, c->stream, a); tl_mark(c, "deep cluster flank kernel enqueued"); },
-                     [&](const cldf::DeepClFlankArgs& a) { hipLaunchKernelGGL(cldf::deep_cluster_flank_finish_kernel, cgrid, dim3(cld::DW), 0, c->stream, a); });
+                     [&](const cldf::DeepClFlankArgs& a) { hipLaunchKernelGGL(cldf::deep_cluster_flank_kernel<false>, cgrid, dim3(cld::DW), 0, c->stream, a); tl_mark(c, "deep cluster flank kernel enqueued"); },
+                     [&](const cldf::DeepClFlankArgs& a) { hipLaunchKernelGGL(cldf::deep_cluster_flank_finish_kernel<false>, cgrid, dim3(cld::DW), 0, c->stream, a); });
   }
   if (rc) return rc;
   tl_mark(c, deep ? "deep cluster chain enqueued" : "cluster chain enqueued");
@@ -1562,7 +1577,7 @@ int LocusCall::enqueue_results() {
 // [0] settled on the device, [1] repaired among them, [2] handed back, [3] handed back undecided (SNV branches); a settled size locus of
 // more than GT_MAX_READS reads is also the deep size list's: [3] of the tag route, which has no undecided loci, and
 // trgt_hip_size_deep_stats[3] for the SNV route.
-// One test serves both branches.  In all four headers that write the byte (locus_gt.hpp, locus_gt_deep.hpp, locus_cluster_flank.hpp,
+// One test serves both branches of all six routes.  In all four headers that write the byte (locus_gt.hpp, locus_gt_deep.hpp, locus_cluster_flank.hpp,
 // locus_cluster_flank_deep.hpp) FL_UNDECIDED is stored only by the handed() of the SNV forms, together with FL_SNV, and every store of
 // FL_HANDED is `FL_HANDED | mark` (mark = 0 for the tag branch, FL_SNV for the other) or plain FL_HANDED: a tag-branch byte that has
 // FL_HANDED has no other bit set, so `& FL_HANDED` behind the FL_UNDECIDED test counts what `== FL_HANDED` counted.
@@ -1612,7 +1627,7 @@ int LocusCall::wait_stage_a() {
       //  add FL_NOSPLIT: both branches of flank_split were evaluated on the device and neither splits the reads)
       //  The deep cluster route (locus_cluster_flank_deep.hpp) writes the bytes of the loci admitted to the deep list, and only theirs: a
       //  deep locus beyond the setting or without room in the pair budget never had its byte written.
-      const bool size_ran = ran[FR_SIZE_TAG] || ran[FR_SIZE_SNV], cluster_ran = ran[FR_CLUSTER_TAG] || ran[FR_CLUSTER_SNV], deep_ran = ran[FR_CLUSTER_DEEP_TAG];
+      const bool size_ran = ran[FR_SIZE_TAG] || ran[FR_SIZE_SNV], cluster_ran = ran[FR_CLUSTER_TAG] || ran[FR_CLUSTER_SNV], deep_ran = ran[FR_CLUSTER_DEEP_TAG] || ran[FR_CLUSTER_DEEP_SNV];
       const uint8_t* fdone = size_ran || cluster_ran || deep_ran ? (const uint8_t*)slab.h(o_fdone) : nullptr;
       std::vector<uint8_t> on_deep_list;
       if (deep_ran) { on_deep_list.assign((size_t)nl, 0); for (const uint32_t l : cld_list) on_deep_list[l] = 1; }
@@ -1638,7 +1653,8 @@ int LocusCall::wait_stage_a() {
         tally_route(FR_CLUSTER_TAG, &cl_list, 0, fdone, need);
         stat_cons_jobs += (int64_t)((const uint32_t*)slab.h(o_cfc))[clf::CF_J3];  // consensus alignments of the third round
       }
-      if (deep_ran) {  // (the loci of the deep list, which are in no other count)
+      if (ran[FR_CLUSTER_DEEP_SNV]) tally_route(FR_CLUSTER_DEEP_SNV, &cld_list, gt::FL_SNV, fdone, need);
+      if (deep_ran) {  // (the loci of the deep list, which are in no other count; whichever of the two settings ran the kernels, as above)
         tally_route(FR_CLUSTER_DEEP_TAG, &cld_list, 0, fdone, need);
         stat_cons_jobs += (int64_t)((const uint32_t*)slab.h(o_cfdc))[cldf::DF_J3];  // consensus alignments of the deep list's third round
       }
@@ -2316,6 +2332,8 @@ extern "C" int trgt_hip_set_snv_cluster_device(trgt_hip_ctx* c, int on) { return
 extern "C" int trgt_hip_snv_cluster_stats(const trgt_hip_ctx* c, int64_t out[4]) { return route_stats(c, FR_CLUSTER_SNV, 4, out); }
 extern "C" int trgt_hip_set_flank_cluster_deep_device(trgt_hip_ctx* c, int on) { return route_set(c, FR_CLUSTER_DEEP_TAG, on); }
 extern "C" int trgt_hip_flank_cluster_deep_stats(const trgt_hip_ctx* c, int64_t out[3]) { return route_stats(c, FR_CLUSTER_DEEP_TAG, 3, out); }
+extern "C" int trgt_hip_set_snv_cluster_deep_device(trgt_hip_ctx* c, int on) { return route_set(c, FR_CLUSTER_DEEP_SNV, on); }
+extern "C" int trgt_hip_snv_cluster_deep_stats(const trgt_hip_ctx* c, int64_t out[4]) { return route_stats(c, FR_CLUSTER_DEEP_SNV, 4, out); }
 
 extern "C" int trgt_locus_batch(trgt_hip_ctx* c, const trgt_locus_params* p, const trgt_locus_batch_in* in, trgt_locus_batch_out* out) {
   TRGT_ABI_GUARD(c, locus_batch_run(c, p, in, out, nullptr, nullptr, nullptr));

@@ -17,6 +17,14 @@
 // A locus whose tags do not split its reads is not touched (the byte stays 0: the host sees it as before and tries the SNV branch); one that
 // finds no room in the arenas, whose vote overflows or whose allele exceeds allele_cap is handed back (need_host = 1, FL_HANDED) and takes
 // the host path.  The kernels of locus_cluster_deep.hpp and locus_cluster_flank.hpp are used as they are.
+// The SNV forms of the two kernels (contexts that opted in with trgt_hip_set_snv_cluster_deep_device, batches that carry mismatch offsets)
+// add the other branch, get_trs_with_clustering (genotype_flank.rs:78-138, 171-290), in the reference's order: tags that split the reads
+// own the locus (this route with both settings on, else the host as before: the byte stays 0), and only without such tags the search of
+// gtd::deep_snv_search runs -- the one of the deep size route, with its limits and its margin rule (locus_gt_deep.hpp).  Its groups
+// overlap as behind the one-wave chain (locus_cluster_flank.hpp): a read that agrees equally with both haplotypes is a member of both
+// while its assignment alternates; multiplicities, medians, the 50 % test, intervals and the third round's members follow the membership,
+// num_spanning and the classification the assignment.  The bytes carry FL_SNV: FL_NOSPLIT (the host need not look again), FL_DONE, or
+// FL_HANDED (limits, FL_UNDECIDED, and the hand-backs of the tag route).
 #pragma once
 #include "locus_cluster_flank.hpp"
 #include "locus_gt_deep.hpp"
@@ -41,11 +49,28 @@ struct DeepClFlankArgs {
   uint32_t first_job, first_group;  // the third part of the deep list's job and group lists
 };
 
+// ... and what the SNV forms read beyond that (a struct of its own: DeepClFlankArgs does not grow): what clf::ClSnvArgs adds to
+// clf::ClFlankArgs, and the workspace of the deep search in HBM -- the one of the deep size list's SNV forms.  Both deep lists can share
+// prof, stage and snv_read in one call: they are indexed by read slot of the batch, the loci of the two lists are disjoint, and the
+// chains run on one stream.
+struct DeepClSnvArgs : DeepClFlankArgs {
+  const int32_t *start_offset, *end_offset;  // per read of the batch (NULL = 0 for every read, as in flank_split)
+  const int32_t* mismatch_offsets; const uint64_t* mismatch_off;  // per read r: its ascending offsets in [mismatch_off[r], mismatch_off[r + 1])
+  uint8_t* snv_read;      // per read slot of the batch, by position in the kept list: gt::SR_* of a locus the search split
+  int32_t* pend_hap;      // [2 n_list] beside pend: the assigned reads of either group (ClFlankPend::cnt holds the members)
+  double ln_match, ln_mis, ln2;  // ln 0.9, ln(1.0 - 0.9), ln 2 as the host's libm rounds them
+  int32_t tag_route;      // 1: tags that split the reads are this route's (trgt_hip_set_flank_cluster_deep_device is on as well); 0: the host's
+  uint64_t* prof;         // [2 x read slots of the batch] kept read i of a locus: its observed mask at 2 (r0 + i), its value mask behind it
+  int32_t* stage;         // [stage_cap = mismatch_off[reads of the batch]] the in-region offsets of a locus' kept reads, packed from mismatch_off[r0] on
+  uint64_t stage_cap;
+};
+template <bool SNV> using DeepClFlankArgsOf = std::conditional_t<SNV, DeepClSnvArgs, DeepClFlankArgs>;
+
 struct DeepClFlank {
   uint32_t ln[MAXR]; uint64_t off[MAXR];  // kept reads in kept order: length and blob offset of the repeat segment
   uint64_t hash[MAXR];                    // of the segment's bytes (equal segments have equal hashes; the bytes decide)
   uint32_t ucnt[MAXR];                    // at a sequence's first read: its multiplicity inside group 0 (low half) and group 1 (high half); 0 elsewhere
-  uint8_t grp[MAXR];                      // the assignment
+  uint8_t grp[MAXR];                      // the assignment (SNV forms, a split by SNVs: bit 0 the assignment, bit 1 set for a read of both groups)
   int32_t cand[DW];                       // per thread: its smallest candidate sequence in byte order
   uint32_t med[2][2];                     // the two middle lengths of either group
   Red red;
@@ -53,10 +78,30 @@ struct DeepClFlank {
 };
 static_assert(sizeof(DeepClFlank) <= 64 * 1024, "static LDS of deep_cluster_flank_kernel");
 static_assert(MAXR < 65536, "two 16-bit multiplicities share a word of DeepClFlank::ucnt");
+// The search of the SNV forms runs before ln / off / hash / ucnt are filled: the offsets whose rank is taken lie over ln, its small lists
+// over hash
+static_assert(sizeof(int32_t) * MAXR <= sizeof(DeepClFlank::ln) && sizeof(gtd::DeepSnv) <= sizeof(DeepClFlank::hash) && offsetof(DeepClFlank, hash) % alignof(gtd::DeepSnv) == 0,
+              "the search's keys and lists lie over ln and hash");
 
-__device__ __forceinline__ void hand_back(const DeepClFlankArgs& a, int64_t l) {
-  if (threadIdx.x == 0) { a.d.c.g.need_host[l] = 1; a.flank_done[l] = gt::FL_HANDED; atomicAdd(a.fcounts + DF_FAILED, 1u); }
+__device__ __forceinline__ void hand_back(const DeepClFlankArgs& a, int64_t l, uint8_t why = 0) {
+  if (threadIdx.x == 0) { a.d.c.g.need_host[l] = 1; a.flank_done[l] = gt::FL_HANDED | why; atomicAdd(a.fcounts + DF_FAILED, 1u); }
 }
+// How gtd::deep_snv_search ends behind the deep cluster chain, clf::ClusterEnd for the workgroup.  true: the reads split, cnt holds the
+// members and hap the assigned reads of either group; false: the byte of the locus says why not
+struct DeepClusterEnd {
+  const DeepClSnvArgs& a; int64_t l; int n; const uint8_t* grp; Red& red;
+  int cnt[2], hap[2];
+  __device__ __forceinline__ bool nosplit() const { if (threadIdx.x == 0) a.flank_done[l] = gt::FL_NOSPLIT | gt::FL_SNV; return false; }
+  __device__ __forceinline__ bool handed(uint8_t why) const { hand_back(a, l, (uint8_t)(gt::FL_SNV | why)); return false; }
+  __device__ __forceinline__ bool split(const int (&members)[2]) {
+    if (members[0] == 0 || members[1] == 0) return nosplit();  // an empty group: no split
+    uint32_t ones = 0;
+    for (int i = threadIdx.x; i < n; i += DW) ones += grp[i] & 1u;
+    ones = cld::block_sum_u32(ones, red);
+    cnt[0] = members[0]; cnt[1] = members[1]; hap[1] = (int)ones; hap[0] = n - (int)ones;
+    return true;
+  }
+};
 
 // 64-bit hash of a byte string anywhere in global memory, by one thread: eight bytes a step, the tail byte by byte
 __device__ __forceinline__ uint64_t hash_seg(const uint8_t* __restrict__ p, uint32_t n) {
@@ -72,9 +117,12 @@ __device__ __forceinline__ uint64_t hash_seg(const uint8_t* __restrict__ p, uint
 
 // The end of both kernels, clf::flank_write for the workgroup: smaller allele first (genotype_flank.rs:33-38: a swap on strict >, the
 // assignment flips with it), the assignment is the classification and its counts are num_spanning, reference allele first (tr.rs:95-101),
-// TrSize::size = allele length.  ap / aln / civ / hap are per tag group, grp holds the assignment of the kept reads.  Uniform arguments.
+// TrSize::size = allele length.  ap / aln / civ / hap are per group -- hap: the reads assigned to it (by tags: its members; by SNVs a read
+// of both groups is assigned to one) --, grp holds the assignment of the kept reads (BY_SNV: in bit 0).  mark: FL_SNV for the SNV branch,
+// 0 for the tags'.  Uniform arguments.
+template <bool BY_SNV = false>
 __device__ __forceinline__ void deep_flank_write(const DeepClFlankArgs& a, const uint8_t* grp, int64_t l, uint64_t r0, int n, const uint8_t* const (&ap)[2], const uint32_t (&aln)[2],
-                                                 const int32_t (&civ)[4], const int32_t (&hap)[2], uint8_t done) {
+                                                 const int32_t (&civ)[4], const int32_t (&hap)[2], uint8_t done, uint8_t mark = 0) {
   const gt::GtArgs& g = a.d.c.g;
   const int tid = threadIdx.x;
   // (constant indices throughout, selections instead of indexed loads: the small per-group arrays stay in registers)
@@ -84,7 +132,7 @@ __device__ __forceinline__ void deep_flank_write(const DeepClFlankArgs& a, const
   const uint8_t* ref = g.tr_blob + g.tr_off[l]; const uint32_t refn = g.tr_len[l];
   // (wave_equal: every wave compares the whole strings, all reach the same answer)
   const bool flip = !gt::wave_equal(p_lo, n_lo, ref, refn) && gt::wave_equal(p_hi, n_hi, ref, refn);
-  if (aln[0] > g.allele_cap[l] || aln[1] > g.allele_cap[l]) { hand_back(a, l); return; }  // the host path reports the error
+  if (aln[0] > g.allele_cap[l] || aln[1] > g.allele_cap[l]) { hand_back(a, l, mark); return; }  // the host path reports the error
   const bool first1 = sw != flip;  // output allele 0 is tag group 1's
 #pragma unroll
   for (int oi = 0; oi < 2; ++oi) {
@@ -102,13 +150,16 @@ __device__ __forceinline__ void deep_flank_write(const DeepClFlankArgs& a, const
   const uint8_t first_group = first1 ? 1 : 0;
   for (int i = tid; i < n; i += DW) {
     const uint32_t rd = a.d.sel_read[r0 + i];
-    g.classification[r0 + rd] = grp[i] == first_group ? 0 : 1;
+    if constexpr (BY_SNV) g.classification[r0 + rd] = (grp[i] & 1u) == first_group ? 0 : 1;
+    else g.classification[r0 + rd] = grp[i] == first_group ? 0 : 1;
     g.read_rank[r0 + rd] = i;
   }
-  if (tid == 0) { g.n_alleles[l] = 2; g.n_spanning_reads[l] = (uint32_t)n; g.flipped[l] = (uint8_t)flip; a.flank_done[l] = done; }
+  if (tid == 0) { g.n_alleles[l] = 2; g.n_spanning_reads[l] = (uint32_t)n; g.flipped[l] = (uint8_t)flip; a.flank_done[l] = done | mark; }
 }
 
-__global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlankArgs a) {
+template <bool SNV = false>
+__global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlankArgsOf<SNV> a) {
+  using MEM = gtd::DeepSnvMembers;  // (SNV forms, a split by SNVs) who belongs to a group, from the byte in grp
   __shared__ DeepClFlank sh;
   const uint32_t k = blockIdx.x;
   if (k >= a.d.c.n_list) return;
@@ -125,7 +176,31 @@ __global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlan
   const int n = rec.n;
   if (n <= 0 || n > MAXR) return;
   int cnt[2];  // members of either group
-  if (!gtd::deep_flank_assign(sh.grp, a.d, a.hp_tag, r0, n, cnt, sh.red)) return;  // the tags do not split the reads: the host tries the SNV branch as before
+  int hap[2] = {0, 0};  // (SNV forms) the reads assigned to it: by tags its members, by SNVs a read of both groups is assigned to one
+  bool snv = false;     // (SNV forms) the split is the SNV branch's: its groups overlap
+  if constexpr (!SNV) {
+    if (!gtd::deep_flank_assign(sh.grp, a.d, a.hp_tag, r0, n, cnt, sh.red)) return;  // the tags do not split the reads: the host tries the SNV branch as before
+  } else {
+    if (a.hp_tag && gtd::deep_flank_assign(sh.grp, a.d, a.hp_tag, r0, n, cnt, sh.red)) {
+      if (!a.tag_route) return;  // the tags own the locus and the host finds their split as before: the byte stays 0
+      hap[0] = cnt[0]; hap[1] = cnt[1];
+    } else {
+      // the search, before ln / off / hash / ucnt are filled: its keys over ln, its lists over hash (kept read i is read r0 + sel_read[r0 + i]
+      // of the batch, as in the deep size route)
+      DeepClusterEnd end{a, l, n, sh.grp, sh.red, {0, 0}, {0, 0}};
+      if (!gtd::deep_snv_search(*reinterpret_cast<gtd::DeepSnv*>(static_cast<void*>(sh.hash)), reinterpret_cast<int32_t*>(sh.ln), sh.grp, sh.red, a, r0, n,
+                                [&](int i) { return r0 + a.d.sel_read[r0 + i]; }, end))
+        return;  // no split, or handed back: the byte says which
+      cnt[0] = end.cnt[0]; cnt[1] = end.cnt[1]; hap[0] = end.hap[0]; hap[1] = end.hap[1];
+      snv = true;
+    }
+  }
+  const uint8_t mark = snv ? (uint8_t)gt::FL_SNV : (uint8_t)0;
+  // (the tag forms keep the statements they had, here and below: their resource figures stay; profiles/snv_cluster_deep_resource_usage.txt)
+  auto in = [&](uint32_t b, int q) {  // a read whose byte in grp is b is a member of group q
+    if constexpr (SNV) return snv ? MEM::in(b, q) : b == (uint32_t)q;
+    else return b == (uint32_t)q;
+  };
   // ---- every thread reads the segments of its reads once: length, offset, hash
   for (int i = tid; i < n; i += DW) {
     const uint32_t li = a.d.sel_len[r0 + i];
@@ -139,20 +214,26 @@ __global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlan
     // ---- all pairs, on LDS: thread t owns reads t, t + DW, ...; against every read j in kept order
     //      first[x]: the first kept read with the sequence of read x (bytes compared where length and hash agree, until one is found)
     //      rk[x]:    the rank of read x among the lengths of its group, #{shorter} + #{equal and earlier}
+    //      (SNV forms: a read of both groups has a rank in either -- rk among the members of group 0, rk1 among those of group 1)
     uint32_t li[DT]; uint64_t hi[DT]; uint32_t gi[DT]; int rk[DT], first[DT];
+    int rk1[SNV ? DT : 1]; (void)rk1;
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
       const int i = tid + DW * t;
       const bool valid = i < n;
       li[t] = valid ? sh.ln[i] : 0xFFFFFFFFu; hi[t] = valid ? sh.hash[i] : 0ull; gi[t] = valid ? (uint32_t)sh.grp[i] : 2u;
       rk[t] = 0; first[t] = i;
+      if constexpr (SNV) rk1[t] = 0;
     }
     for (int j = 0; j < n; ++j) {
       const uint32_t lj = sh.ln[j]; const uint64_t hj = sh.hash[j]; const uint32_t gj = sh.grp[j];
 #pragma unroll
       for (int t = 0; t < DT; ++t) {
         const int i = tid + DW * t;
-        rk[t] += gj == gi[t] && (lj < li[t] || (lj == li[t] && j < i));
+        if constexpr (SNV) {
+          const bool before = lj < li[t] || (lj == li[t] && j < i);
+          rk[t] += in(gj, 0) && before; rk1[t] += in(gj, 1) && before;
+        } else rk[t] += gj == gi[t] && (lj < li[t] || (lj == li[t] && j < i));
         if (lj == li[t] && hj == hi[t] && j < i && first[t] == i && gtd::cmp_seg_thread(seg_ptr(j), lj, seg_ptr(i), lj) == 0) first[t] = j;
       }
     }
@@ -161,10 +242,19 @@ __global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlan
 #pragma unroll
     for (int t = 0; t < DT; ++t) {
       if (tid + DW * t >= n) continue;
-      const int q = (int)gi[t];
-      atomicAdd(&sh.ucnt[first[t]], q ? 0x10000u : 1u);
-      if (rk[t] == cnt[q] / 2) sh.med[q][1] = li[t];
-      if (rk[t] == cnt[q] / 2 - 1) sh.med[q][0] = li[t];
+      if constexpr (SNV) {  // a read of both groups counts in both halves, and can be a middle element of either
+        const bool in0 = in(gi[t], 0), in1 = in(gi[t], 1);
+        atomicAdd(&sh.ucnt[first[t]], (in0 ? 1u : 0u) + (in1 ? 0x10000u : 0u));
+        if (in0 && rk[t] == cnt[0] / 2) sh.med[0][1] = li[t];
+        if (in0 && rk[t] == cnt[0] / 2 - 1) sh.med[0][0] = li[t];
+        if (in1 && rk1[t] == cnt[1] / 2) sh.med[1][1] = li[t];
+        if (in1 && rk1[t] == cnt[1] / 2 - 1) sh.med[1][0] = li[t];
+      } else {
+        const int q = (int)gi[t];
+        atomicAdd(&sh.ucnt[first[t]], q ? 0x10000u : 1u);
+        if (rk[t] == cnt[q] / 2) sh.med[q][1] = li[t];
+        if (rk[t] == cnt[q] / 2 - 1) sh.med[q][0] = li[t];
+      }
     }
   }
   __syncthreads();
@@ -197,15 +287,16 @@ __global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlan
       __syncthreads();
     }
     best = sh.cand[0];  // (the group is not empty: some thread had a candidate)
-    if (best < 0) { hand_back(a, l); return; }  // (cannot happen; uniform, and no index below is taken from a value that was never set)
-    for (int i = tid; i < n; i += DW) if (sh.grp[i] == q) { const uint32_t v = sh.ln[i]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
+    if (best < 0) { hand_back(a, l, mark); return; }  // (cannot happen; uniform, and no index below is taken from a value that was never set)
+    for (int i = tid; i < n; i += DW) if (in(sh.grp[i], q)) { const uint32_t v = sh.ln[i]; mn = v < mn ? v : mn; mx = v > mx ? v : mx; }
     civ[2 * q] = (int32_t)gtd::block_min_u32(mn, sh.red); civ[2 * q + 1] = (int32_t)gtd::block_max_u32(mx, sh.red);  // (their barriers: cand is free again)
     rep[q] = best; aln[q] = sh.ln[best];
     lacks[q] = (double)top / (double)cnt[q] < 0.5;
   }
   if (!lacks[0] && !lacks[1]) {
     const uint8_t* const ap[2] = {seg_ptr(rep[0]), seg_ptr(rep[1])};
-    deep_flank_write(a, sh.grp, l, r0, n, ap, aln, civ, cnt, (uint8_t)gt::FL_DONE);
+    if constexpr (SNV) deep_flank_write<true>(a, sh.grp, l, r0, n, ap, aln, civ, hap, (uint8_t)gt::FL_DONE, mark);
+    else deep_flank_write(a, sh.grp, l, r0, n, ap, aln, civ, cnt, (uint8_t)gt::FL_DONE);
     return;
   }
   // ---- a group below 50 %: backbone = its sequence, one member per read of the group in kept order, duplicates included.  The arenas
@@ -215,7 +306,7 @@ __global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlan
   for (int q = 0; q < 2; ++q) {
     if (!lacks[q]) continue;
     uint32_t bytes = 0;
-    for (int i = tid; i < n; i += DW) if (sh.grp[i] == q) bytes += sh.ln[i];
+    for (int i = tid; i < n; i += DW) if (in(sh.grp[i], q)) bytes += sh.ln[i];
     nm[q] = (uint32_t)cnt[q]; mbytes[q] = cld::block_sum_u32(bytes, sh.red);
   }
   gt::GroupNeeds nd[2] = {};
@@ -225,14 +316,15 @@ __global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlan
     gt::Reserved r;
     r.g0 = r.j0 = 0;
     if (gt::reserve_arenas(a.d.c.counts + cl::CC_CIGAR, a.d.c.counts + cl::CC_OUT, a.d.c.counts + cl::CC_SCRATCH, a.d.c.cap_cigar, a.d.c.cap_out, a.d.c.cap_scratch, nd, r)) {
-      // (room in the third part of the lists: a read is a member of one tag group -- at most cap_j jobs and 2 groups per locus)
+      // (room in the third part of the lists: a read is a member of one tag group, of at most two SNV groups -- cap_j jobs for the launch
+      //  of the tag forms, 2 cap_j for that of the SNV forms, which is how cluster_chain sizes the lists; 2 groups per locus)
       r.j0 = a.first_job + atomicAdd(a.fcounts + DF_J3, nm[0] + nm[1]);
       r.g0 = a.first_group + atomicAdd(a.fcounts + DF_G3, (uint32_t)lacks[0] + (uint32_t)lacks[1]);
     }
     sh.rsv = r;
   }
   __syncthreads();
-  if (!sh.rsv.ok) { hand_back(a, l); return; }
+  if (!sh.rsv.ok) { hand_back(a, l, mark); return; }
   gt::Reserved at = sh.rsv;
   clf::ClFlankPend pd;
 #pragma unroll
@@ -242,26 +334,45 @@ __global__ void __launch_bounds__(DW) deep_cluster_flank_kernel(const DeepClFlan
   }
 #pragma unroll
   for (int q = 0; q < 2; ++q)
-    if (lacks[q]) pd.grp[q] = (int32_t)gt::queue_group<DW>(a.d.c.groups, a.d.c.jobs, at, seg_of(rep[q]), nm[q], nd[q], n, [&, q](int i) { return sh.grp[i] == q; }, seg_of);
-  if (tid == 0) { a.pend[k] = pd; a.flank_done[l] = gt::FL_REPAIRED; }  // the locus waits for deep_cluster_flank_finish_kernel
+    if (lacks[q]) pd.grp[q] = (int32_t)gt::queue_group<DW>(a.d.c.groups, a.d.c.jobs, at, seg_of(rep[q]), nm[q], nd[q], n, [&, q](int i) { return in(sh.grp[i], q); }, seg_of);
+  // (SNV forms: a waiting locus of the SNV branch has its split in snv_read, where the search left it; the finish kernel reads it and does not
+  //  repeat the search)
+  if constexpr (SNV) { if (snv && tid == 0) { a.pend_hap[2 * k] = hap[0]; a.pend_hap[2 * k + 1] = hap[1]; } }
+  if (tid == 0) { a.pend[k] = pd; a.flank_done[l] = gt::FL_REPAIRED | mark; }  // the locus waits for deep_cluster_flank_finish_kernel
 }
 
 // ---- behind the third consensus round: the loci that waited.  The assignment is recomputed from the tags (deterministic from the same
 // list of kept reads); each allele is the voted consensus of a repaired group or the backbone of a group that needed none.
+// (SNV forms: a locus of the SNV branch waits with FL_REPAIRED | FL_SNV; its assignment is read back from snv_read, its counts from pend
+// and pend_hap)
 struct DeepClFlankFin { uint8_t grp[MAXR]; Red red; };
-__global__ void __launch_bounds__(DW) deep_cluster_flank_finish_kernel(const DeepClFlankArgs a) {
+template <bool SNV = false>
+__global__ void __launch_bounds__(DW) deep_cluster_flank_finish_kernel(const DeepClFlankArgsOf<SNV> a) {
   __shared__ DeepClFlankFin sh;
   const uint32_t k = blockIdx.x;
   if (k >= a.d.c.n_list) return;
   const gt::GtArgs& g = a.d.c.g;
   const int64_t l = a.d.c.list[k];
-  if (a.flank_done[l] != gt::FL_REPAIRED) return;  // (thread 0 writes the byte behind the barriers of the assignment: every thread has read it by then)
+  bool snv = false;
+  if constexpr (SNV) snv = a.flank_done[l] == (gt::FL_REPAIRED | gt::FL_SNV);
+  if (a.flank_done[l] != gt::FL_REPAIRED && !snv) return;  // (thread 0 writes the byte behind the barriers of the assignment: every thread has read it by then)
   const uint64_t r0 = g.locus_read_begin[l];
   const int n = a.d.c.rec[k].n;
   const clf::ClFlankPend pd = a.pend[k];
   int cnt[2] = {0, 0};
+  int32_t hap[2] = {0, 0};  // (SNV forms) the assigned reads of either group of a locus of the SNV branch
   bool fail = n <= 0 || n > MAXR;
-  if (!fail) fail = !gtd::deep_flank_assign(sh.grp, a.d, a.hp_tag, r0, n, cnt, sh.red) || cnt[0] != pd.cnt[0] || cnt[1] != pd.cnt[1];
+  if constexpr (SNV) {
+    if (snv) {
+      if (!fail) for (int i = threadIdx.x; i < n; i += DW) sh.grp[i] = (uint8_t)(a.snv_read[r0 + i] & gt::SR_ASSIGN);
+      hap[0] = a.pend_hap[2 * k]; hap[1] = a.pend_hap[2 * k + 1];
+      __syncthreads();  // (grp is visible, and every thread has read the byte)
+      if (!fail) fail = n != hap[0] + hap[1];
+    } else if (!fail) fail = !gtd::deep_flank_assign(sh.grp, a.d, a.hp_tag, r0, n, cnt, sh.red) || cnt[0] != pd.cnt[0] || cnt[1] != pd.cnt[1];
+  } else {
+    if (!fail) fail = !gtd::deep_flank_assign(sh.grp, a.d, a.hp_tag, r0, n, cnt, sh.red) || cnt[0] != pd.cnt[0] || cnt[1] != pd.cnt[1];
+  }
+  const uint8_t mark = snv ? (uint8_t)gt::FL_SNV : (uint8_t)0;
   const uint8_t* ap[2] = {nullptr, nullptr}; uint32_t aln[2] = {0, 0};
   for (int q = 0; q < 2 && !fail; ++q) {
     if (pd.grp[q] >= 0) {
@@ -270,9 +381,12 @@ __global__ void __launch_bounds__(DW) deep_cluster_flank_finish_kernel(const Dee
       ap[q] = a.d.c.vote_out + a.d.c.groups[pd.grp[q]].out_off; aln[q] = voted;
     } else { ap[q] = g.reads + pd.bb_off[q]; aln[q] = pd.bb_len[q]; }
   }
-  if (fail) { hand_back(a, l); return; }
+  if (fail) { hand_back(a, l, mark); return; }
   const uint8_t* const apc[2] = {ap[0], ap[1]};
-  deep_flank_write(a, sh.grp, l, r0, n, apc, aln, pd.civ, pd.cnt, (uint8_t)(gt::FL_DONE | gt::FL_REPAIRED));
+  if constexpr (SNV) {
+    if (snv) deep_flank_write<true>(a, sh.grp, l, r0, n, apc, aln, pd.civ, hap, (uint8_t)(gt::FL_DONE | gt::FL_REPAIRED), mark);
+    else deep_flank_write<true>(a, sh.grp, l, r0, n, apc, aln, pd.civ, pd.cnt, (uint8_t)(gt::FL_DONE | gt::FL_REPAIRED));
+  } else deep_flank_write(a, sh.grp, l, r0, n, apc, aln, pd.civ, pd.cnt, (uint8_t)(gt::FL_DONE | gt::FL_REPAIRED));
 }
 
 }  // namespace cldf

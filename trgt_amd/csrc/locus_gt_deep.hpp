@@ -20,7 +20,8 @@
 // genotype_flank::genotype for a deep locus whose two sizes are at most 10 apart: flank_route / flank_finish of locus_gt.hpp restated for
 // the workgroup, see deep_flank_route.  The SNV forms (contexts that opted in to trgt_hip_set_snv_split_device as well, batches that carry
 // mismatch offsets) add the other branch, the split by heterozygous SNVs of the flanks (genotype_flank.rs:78-138, 171-290): snv_route of
-// locus_gt.hpp restated for the workgroup, see deep_snv_route.
+// locus_gt.hpp restated for the workgroup, see deep_snv_route.  The search of that branch, up to and including the assignment, is
+// deep_snv_search: stated once, and also called by the SNV forms behind the deep cluster chain (locus_cluster_flank_deep.hpp).
 #pragma once
 #include <cstddef>
 #include "locus_cluster_deep.hpp"
@@ -361,8 +362,9 @@ __device__ __forceinline__ bool deep_flank_route(DeepSize& sh, const DeepFlankAr
 // route decides, when it decides (the margin rule) and why that is safe are snv_route's, see there; the bound on the difference between
 // the host's and the device's sum of one candidate grows with the reads of a locus, and for n <= 2 048 its three terms give
 // n * 2^-49 + 2^-51 * (|M| + 1.4 n) + n * 2^-52 * |M| < 5e-12 * (1 + |M|), of which the margin 2^-30 * (1 + |M|) is still about 180 times.
-// The small lists of the route lie over DeepFlank::cnt, which the tail fills only after them; the offsets whose rank is taken over
-// DeepSize::tmp; masks and staged offsets in DeepSnvArgs::prof / stage.
+// In the deep size kernels the small lists of the search lie over DeepFlank::cnt, which the tail fills only after them, and the offsets
+// whose rank is taken over DeepSize::tmp (deep_snv_route, below the search); masks and staged offsets in DeepSnvArgs::prof / stage.
+// The limits are shared by both callers: gt::SNV_MAX_SNVS, gt::SNV_MAX_HAPS, SNV_DEEP_CAP.
 // false: no split (FL_NOSPLIT | FL_SNV: neither branch splits the reads, the host need not look) and the locus continues with the length
 // genotype.  true: settled by deep_flank_tail, or handed to the host path (need_host = 1, FL_HANDED | FL_SNV).
 struct DeepSnv {
@@ -375,16 +377,18 @@ static_assert(sizeof(DeepSnv) <= sizeof(DeepFlank::cnt) && offsetof(DeepFlank, c
 constexpr int SNV_DEEP_CAP = gt::SNV_OFFS_PER_READ * MAXR;  // in-region occurrences of a locus: 8 per read slot of the kernel
 static_assert(SNV_DEEP_CAP / DW <= 64, "one bit per owned entry in `called`");
 
-__device__ __forceinline__ bool deep_snv_route(DeepSize& sh, const DeepSnvArgs& sa, int64_t l, uint64_t r0, int n, int nu) {
-  const DeepArgs& a = sa.d;
-  const gt::GtArgs& g = a.c.g;
-  DeepFlank& fl = deep_flank_lds(sh);
-  DeepSnv& sv = *reinterpret_cast<DeepSnv*>(static_cast<void*>(fl.cnt));
-  int32_t* const key = reinterpret_cast<int32_t*>(sh.tmp);
+// The search itself, up to and including the assignment, stated once for both deep lists (the size route below and the SNV forms of
+// locus_cluster_flank_deep.hpp).  sv / key: where its small lists and the offsets whose rank is taken live in LDS (key: n words); grp: per
+// kept read, bit 0 the assignment, bit 1 set for a read of both groups; read_of(i): the read of the batch that kept read i is; sa: the
+// route's arguments (the fields DeepSnvArgs adds to DeepFlankArgs, under these names); end: how it ends, like clf::ClusterEnd --
+//   end.nosplit()     no split          end.handed(why)   beyond a limit (why = 0) or undecided (FL_UNDECIDED)
+//   end.split(cnt)    the assignment is in grp and in sa.snv_read (SR_*), cnt[t] members of either group (a group may be empty)
+// and the result is what they return.  Every thread is done with sv and key when end.split is called.  Uniform arguments and result.
+template <class A, class ReadOf, class End>
+__device__ __forceinline__ bool deep_snv_search(DeepSnv& sv, int32_t* const key, uint8_t* const grp, Red& red, const A& sa, uint64_t r0, int n, ReadOf read_of, End& end) {
   const int tid = threadIdx.x;
-  auto nosplit = [&]() { if (tid == 0) sa.flank_done[l] = gt::FL_NOSPLIT | gt::FL_SNV; return false; };
-  auto handed = [&](uint8_t why) { if (tid == 0) { g.need_host[l] = 1; sa.flank_done[l] = (uint8_t)(gt::FL_HANDED | gt::FL_SNV | why); } return true; };
-  auto read_of = [&](int i) { return r0 + a.sel_read[r0 + i]; };
+  auto nosplit = [&]() { return end.nosplit(); };
+  auto handed = [&](uint8_t why) { return end.handed(why); };
   // ---- get_analysis_region (:206-226): the skip-th largest start offset, the skip-th smallest end offset, by (value, index) rank
   const int skip = (int)round((double)n * (1.0 - 0.85));
   if (skip >= n) return nosplit();
@@ -417,7 +421,7 @@ __device__ __forceinline__ bool deep_snv_route(DeepSize& sh, const DeepSnvArgs& 
     uint32_t c = 0;
     for (uint64_t k = m0; k < m1; ++k) { const int32_t o = sa.mismatch_offsets[k]; c += reg0 <= o && o <= reg1; }
     uint32_t tot;
-    uint32_t at = total + block_excl_scan_u32(c, tot, sh.red);
+    uint32_t at = total + block_excl_scan_u32(c, tot, red);
     for (uint64_t k = m0; k < m1; ++k) { const int32_t o = sa.mismatch_offsets[k]; if (reg0 <= o && o <= reg1) { if (at < room) stage[at] = o; ++at; } }
     total += tot;
   }
@@ -439,7 +443,7 @@ __device__ __forceinline__ bool deep_snv_route(DeepSize& sh, const DeepSnvArgs& 
     if ((uint32_t)DW * (uint32_t)t >= total) break;
     const bool mine = (called >> t) & 1ull;
     uint32_t tot;
-    const uint32_t at = (uint32_t)ns + cld::block_rank(mine, tot, sh.red);
+    const uint32_t at = (uint32_t)ns + cld::block_rank(mine, tot, red);
     if (mine && at < (uint32_t)gt::SNV_MAX_SNVS) sv.v_tmp[at] = stage[(uint32_t)tid + (uint32_t)DW * (uint32_t)t];
     ns += (int)tot;
   }
@@ -474,7 +478,7 @@ __device__ __forceinline__ bool deep_snv_route(DeepSize& sh, const DeepSnvArgs& 
     prof[2 * i] = obs; prof[2 * i + 1] = val;
     full += obs == all;
   }
-  full = cld::block_sum_u32(full, sh.red);  // (its barriers also publish the masks to the workgroup)
+  full = cld::block_sum_u32(full, red);  // (its barriers also publish the masks to the workgroup)
   // ---- candidate genotypes (:228-248): the distinct fully observed profiles in the derived order of Option<bool> -- first SNV most
   //      significant, false before true: the bit-reversed value mask -- and their pairs a <= b, a outer
   if ((double)full / (double)n < 0.40) return nosplit();
@@ -485,7 +489,7 @@ __device__ __forceinline__ bool deep_snv_route(DeepSize& sh, const DeepSnvArgs& 
     uint64_t v = 0;
     if (first) { v = prof[2 * i + 1]; for (int j = 0; j < i; ++j) first = first && !(prof[2 * j] == all && prof[2 * j + 1] == v); }
     uint32_t tot;
-    const uint32_t q = (uint32_t)nh + cld::block_rank(first, tot, sh.red);
+    const uint32_t q = (uint32_t)nh + cld::block_rank(first, tot, red);
     if (first && q < (uint32_t)gt::SNV_MAX_HAPS) sv.v_htmp[q] = v;
     nh += (int)tot;
   }
@@ -528,20 +532,37 @@ __device__ __forceinline__ bool deep_snv_route(DeepSize& sh, const DeepSnvArgs& 
     if (valid) { const uint64_t obs = prof[2 * i], val = prof[2 * i + 1]; d1 = __popcll(obs & ~(val ^ top1)); d2 = __popcll(obs & ~(val ^ top2)); }
     const bool tie = valid && d1 == d2;
     uint32_t tot;
-    const uint32_t k = ties + cld::block_rank(tie, tot, sh.red);
+    const uint32_t k = ties + cld::block_rank(tie, tot, red);
     if (valid) {
       const uint32_t gi = tie ? (k & 1u) : (d1 < d2 ? 0u : 1u);
       const bool in0 = gi == 0 || tie, in1 = gi == 1 || tie;
-      fl.grp[i] = (uint8_t)(gi | (tie ? 2u : 0u));
+      grp[i] = (uint8_t)(gi | (tie ? 2u : 0u));
       sa.snv_read[r0 + i] = (uint8_t)((gi ? gt::SR_ASSIGN : 0) | (in0 ? gt::SR_IN0 : 0) | (in1 ? gt::SR_IN1 : 0));
       c0 += in0; c1 += in1;
     }
     ties += tot;
   }
-  // (the barriers of the sums: every thread is done with the route's lists, whose bytes the tail fills next, and sees grp and the bytes)
-  const int cnt[2] = {(int)cld::block_sum_u32(c0, sh.red), (int)cld::block_sum_u32(c1, sh.red)};
-  if (!deep_flank_tail<DeepSnvMembers>(sh, sa, l, r0, n, nu, cnt, sa.snv_read)) return nosplit();
-  return true;
+  // (the barriers of the sums: every thread is done with the search's lists and sees grp and the bytes)
+  const int cnt[2] = {(int)cld::block_sum_u32(c0, red), (int)cld::block_sum_u32(c1, red)};
+  return end.split(cnt);
+}
+
+// How the search ends inside the deep size genotyper: the byte of the locus; a split goes on with deep_flank_tail, which fills the bytes
+// of the search's lists next
+struct DeepSizeEnd {
+  DeepSize& sh; const DeepSnvArgs& sa; int64_t l; uint64_t r0; int n, nu;
+  __device__ __forceinline__ bool nosplit() const { if (threadIdx.x == 0) sa.flank_done[l] = gt::FL_NOSPLIT | gt::FL_SNV; return false; }
+  __device__ __forceinline__ bool handed(uint8_t why) const { if (threadIdx.x == 0) { sa.d.c.g.need_host[l] = 1; sa.flank_done[l] = (uint8_t)(gt::FL_HANDED | gt::FL_SNV | why); } return true; }
+  __device__ __forceinline__ bool split(const int (&cnt)[2]) const {
+    if (!deep_flank_tail<DeepSnvMembers>(sh, sa, l, r0, n, nu, cnt, sa.snv_read)) return nosplit();
+    return true;
+  }
+};
+__device__ __forceinline__ bool deep_snv_route(DeepSize& sh, const DeepSnvArgs& sa, int64_t l, uint64_t r0, int n, int nu) {
+  DeepFlank& fl = deep_flank_lds(sh);
+  DeepSizeEnd end{sh, sa, l, r0, n, nu};
+  return deep_snv_search(*reinterpret_cast<DeepSnv*>(static_cast<void*>(fl.cnt)), reinterpret_cast<int32_t*>(sh.tmp), fl.grp, sh.red, sa, r0, n,
+                         [&](int i) { return r0 + sa.d.sel_read[r0 + i]; }, end);
 }
 
 template <bool FLANK = false, bool SNV = false>

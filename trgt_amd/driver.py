@@ -17,11 +17,11 @@ from . import _lib, locus
 
 
 class ChunkDriver:
-    """devices: one entry per context (ordinals may repeat: several contexts on one GPU).  cluster_max_reads, size_max_reads, flank_device, flank_cluster_device, flank_cluster_deep_device, snv_split_device, snv_cluster_device: passed to every context
+    """devices: one entry per context (ordinals may repeat: several contexts on one GPU).  cluster_max_reads, size_max_reads, flank_device, flank_cluster_device, flank_cluster_deep_device, snv_split_device, snv_cluster_deep_device, snv_cluster_device: passed to every context
     (size_max_reads and flank_device combine: deep size loci of a haplotagged batch then run the tag branch of genotype_flank on the device;
     size_max_reads and snv_split_device combine likewise: deep size loci of a batch with mismatch offsets then run its SNV branch there)."""
 
-    def __init__(self, devices=(0,), params=None, context_factory=None, run_fn=None, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, flank_cluster_deep_device=None, snv_split_device=None, snv_cluster_device=None):
+    def __init__(self, devices=(0,), params=None, context_factory=None, run_fn=None, cluster_max_reads=None, size_max_reads=None, flank_device=None, flank_cluster_device=None, flank_cluster_deep_device=None, snv_split_device=None, snv_cluster_deep_device=None, snv_cluster_device=None):
         self.params = params or locus.Params()
         self._make = context_factory or (lambda dev: _lib.Context(dev))
         self._run = run_fn or (lambda ctx, chunk, params, kw: locus.run_batch(chunk, params, ctx, **kw))
@@ -30,7 +30,7 @@ class ChunkDriver:
         # the settings, in every context (what each means: the docstrings of the Context methods)
         _lib.apply_settings(self.contexts, ((cluster_max_reads, "set_cluster_max_reads"), (size_max_reads, "set_size_max_reads"), (flank_device, "set_flank_device"),
                                             (flank_cluster_device, "set_flank_cluster_device"), (flank_cluster_deep_device, "set_flank_cluster_deep_device"),
-                                            (snv_split_device, "set_snv_split_device"), (snv_cluster_device, "set_snv_cluster_device")))
+                                            (snv_split_device, "set_snv_split_device"), (snv_cluster_deep_device, "set_snv_cluster_deep_device"), (snv_cluster_device, "set_snv_cluster_device")))
         self.chunks_by_context = [0] * len(self.contexts)
 
     def close(self):
