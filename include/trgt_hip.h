@@ -370,6 +370,30 @@ typedef struct trgt_locus_batch_out {  /* LocusResult (locus_result.rs:16-22) x 
 int trgt_locus_batch(trgt_hip_ctx* ctx, const trgt_locus_params* p, const trgt_locus_batch_in* in,
                      trgt_locus_batch_out* out);
 
+/* Allele::meth, the one field of LocusResult trgt_locus_batch_out has no slot for (additive to ABI 11):
+ * get_meth (tr.rs:198-230) with assign_read (:239-266) and get_tr_meth (:363-398) for the loci of a finished trgt_locus_batch call.
+ * in:  n_loci, locus_read_begin, read_blob (host or device, ASCII or TRGT_READS_BAM4 per read_encoding), read_off, read_len
+ * res: span_start, span_end, read_rank, n_alleles, ci, allele_len, and -- when not NULL -- gt_size, flipped (as the writer reads them)
+ * meth: HiFiRead::meth of every read, one byte per CpG of the clipped read (host or device); meth_off [n_reads + 1], has_meth [n_reads] (host)
+ * allele_meth [2 per locus]: Allele::meth in OUTPUT order (after "reference allele first"), NaN = None; slots >= n_alleles are NaN
+ * meth_reads  [2 per locus], optional: how many reads were averaged;  read_meth [n_reads], optional: get_tr_meth per read, NaN = None
+ * (the three outputs host or device).  A read takes part when read_rank >= 0, has_meth is set and its meth range is not empty; its level is
+ * the mean of meth[cpg_index] / 255.0 over the CpGs ('C' at pos, 'G' at pos + 1) with span_start <= pos < span_end, cpg_index counting every CpG
+ * of the read from its start, summed in increasing pos; assign_read works on the genotype's own order (gt_size, or allele_len when NULL,
+ * and ci, un-flipped where flipped[l] is set and n_alleles == 2); per allele the levels are summed by increasing read_rank.  All f64, bit for
+ * bit the reference's.  Two kernels (trgt_amd/csrc/locus_meth.hip): one wave per kept read streams the bases up to span_end + 1 -- 4-bit
+ * reads as nibbles, not expanded -- and one wave per locus averages.  Synchronous on the context's stream.
+ * TRGT_ERR_INVALID with a message, before any launch: NULL among the required arrays, a non-monotone meth_off or locus_read_begin, a ranked
+ * read whose span is not 0 <= start <= end <= read_len, ranks of a locus that are not 0 .. kept - 1.  TRGT_ERR_INVALID after the kernels: a CpG
+ * inside a span with cpg_index >= the read's number of calls (the reference's "malformed methylation profile"; the message names the lowest
+ * such read index, the outputs are unspecified).  Calls missing only beyond span_end are not an error: nothing is read there. */
+int trgt_locus_meth_batch(trgt_hip_ctx* ctx, const trgt_locus_batch_in* in, const trgt_locus_batch_out* res,
+                          const uint8_t* meth, const uint64_t* meth_off, const uint8_t* has_meth,
+                          double* allele_meth, int32_t* meth_reads, double* read_meth);
+/* With trgt_hip_timing_enable on: HIP-event time (ms) of the two kernels of the context's last trgt_locus_meth_batch --
+ * out[0] tr_meth_kernel, out[1] allele_meth_kernel (tools/locus_meth_timing.py). */
+int trgt_locus_meth_kernel_ms(const trgt_hip_ctx* ctx, double out[2]);
+
 /* Host helper for callers that hold ASCII reads and want TRGT_READS_BAM4 (a BAM reader has the codes already: trgt_ingest_params.
  * keep_bam4): packs read r (ascii + read_off[r], read_len[r] bases) to packed + packed_off[r], where packed_off[r] is written as the
  * running sum of ceil(read_len / 2).  Letters outside "=ACMGRSVTWYHKDBN" become N, as in htslib.  packed needs
@@ -529,6 +553,10 @@ void trgt_writer_default_params(trgt_writer_params* p);
 int trgt_writer_open(const trgt_ingest* src, const trgt_writer_params* p, const char* vcf_path, const char* bam_path, trgt_writer** out);
 /* the loci of one ingested batch with the results trgt_locus_batch filled for it (gt_size / flipped wanted for an exact AM) */
 int trgt_writer_write(trgt_writer* w, const trgt_ingest_batch* b, const trgt_locus_batch_out* out);
+/* trgt_writer_write with the AM field taken from the caller instead of computed: the host scan of every kept read's bases for CpGs is skipped.
+ * allele_meth / meth_reads [2 per locus], HOST, both required: what trgt_locus_meth_batch returned for the batch.  AM is "%.2f" of
+ * allele_meth[2l + a], "." for NaN.  Every mode of the writer (threads, write_behind, records_device) works as with trgt_writer_write. */
+int trgt_writer_write_meth(trgt_writer* w, const trgt_ingest_batch* b, const trgt_locus_batch_out* out, const double* allele_meth, const int32_t* meth_reads);
 int trgt_writer_close(trgt_writer* w);   /* flushes, writes the BGZF end-of-file blocks, frees the handle */
 const char* trgt_writer_last_error(const trgt_writer* w);
 /* ABI 10: BGZF blocks of the spanning BAM so far: out[0] deflated on the device (deflate_device), [1] declined by it (zlib took them), [2] by

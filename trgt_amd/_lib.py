@@ -75,6 +75,7 @@ EXPORTS = [
     "trgt_hip_set_workspace_limit", "trgt_hip_cluster_max_reads_limit", "trgt_hip_set_cluster_max_reads", "trgt_hip_size_max_reads_limit", "trgt_hip_set_size_max_reads", "trgt_hip_size_deep_stats", "trgt_hip_set_flank_device", "trgt_hip_flank_stats", "trgt_hip_set_snv_split_device", "trgt_hip_snv_split_stats", "trgt_hip_timing_enable", "trgt_hip_timing_reset", "trgt_hip_timing_get",
     "trgt_wfa_default_params", "trgt_wfa_batch", "trgt_flank_filter_batch", "trgt_find_spans_batch", "trgt_hmm_batch", "trgt_hmm_path_capacity", "trgt_hmm_models_check",
     "trgt_locus_batch", "trgt_locus_batch_submit", "trgt_locus_batch_wait", "trgt_locus_default_params", "trgt_reads_pack_bam4",
+    "trgt_locus_meth_batch", "trgt_locus_meth_kernel_ms", "trgt_writer_write_meth",
     "trgt_hip_pool_create", "trgt_hip_pool_destroy", "trgt_hip_pool_size", "trgt_hip_pool_context", "trgt_hip_pool_last_error", "trgt_locus_batch_many",
     "trgt_ingest_open", "trgt_ingest_close", "trgt_ingest_last_error", "trgt_ingest_default_params", "trgt_ingest_batch_from_catalog", "trgt_ingest_free", "trgt_ingest_device_stats", "trgt_writer_device_stats", "trgt_writer_set_records_device", "trgt_writer_records_stats",
     "trgt_ingest_header_text", "trgt_ingest_n_contigs", "trgt_ingest_contig_name", "trgt_ingest_contig_length",
@@ -217,6 +218,8 @@ def lib():
         L.trgt_flank_filter_batch.argtypes = [_VP, _VP, C.c_int64] + [_VP] * 5 + [C.c_int32, C.c_int32] + [_VP] * 4
         L.trgt_find_spans_batch.argtypes = [_VP, _VP, C.c_int64] + [_VP] * 13
         L.trgt_locus_batch.argtypes = [_VP, _VP, _VP, _VP]
+        L.trgt_locus_meth_batch.argtypes = [_VP] * 9
+        L.trgt_locus_meth_kernel_ms.argtypes = [_VP, C.POINTER(C.c_double)]
         L.trgt_reads_pack_bam4.argtypes = [_VP, C.c_int64, _VP, _VP, _VP, _VP]
         L.trgt_reads_pack_bam4.restype = C.c_int64
         L.trgt_locus_batch_submit.argtypes = [_VP, _VP, _VP, _VP, C.POINTER(C.c_int64)]

@@ -135,6 +135,7 @@ struct trgt_hip_ctx {
   int32_t size_max_reads = 256;     // trgt_hip_set_size_max_reads: deepest Genotyper::Size locus the device genotypers take (256 = the one-wave kernel only)
   int64_t size_deep_stats[4] = {0, 0, 0, 0};  // trgt_hip_size_deep_stats: the deep size loci of the last trgt_locus_batch (genotyped on the device, repaired among them, handed to the host, reserved)
   FlankRouteState route[FR_N];  // the opt-in device routes of genotype_flank, indexed by FlankRoute (above)
+  double meth_ms[2] = {0, 0};   // trgt_locus_meth_kernel_ms: tr_meth_kernel and allele_meth_kernel of the last timed trgt_locus_meth_batch
   int num_cus = 256;
   int band_occ = 0;  // resident workgroups per CU of wfa_band_kernel (wfa_band.hip), asked at its first launch (0: not yet)
   // cached device buffers, indexed by slot
@@ -304,6 +305,7 @@ enum Slot {
   S_CLDF_COUNTS, S_CLDF_PEND,  // the same two for the tag branch behind the deep cluster chain (locus_cluster_flank_deep.hpp)
   S_FS_SETTLED, S_FS_FILTERJOBS,  // flank location: the marks of what the seed search's shortcuts settled, and the pre-filter's list behind the settled-sibling rule (spans.hip)
   S_FS_BANDFALL, S_LW_BANDFALL,  // flank location: the banded jobs the one-wave forward kernel leaves to the LDS launch (wfa_band.hip), short and long reads
+  S_METH_READS, S_METH_CALLS, S_METH_JOBS, S_METH_LOCI, S_METH_LEVEL, S_METH_LEN, S_METH_FLAG, S_METH_OUT, S_METH_NREADS, S_METH_PERREAD,  // trgt_locus_meth_batch (locus_meth.hip)
   S_COUNT
 };
 // pinned host buffer slots

@@ -283,7 +283,8 @@ static int writer_open_impl(const trgt_ingest* src, const trgt_writer_params* p,
   return TRGT_OK;
 }
 
-static int writer_write_impl(trgt_writer* w, const trgt_ingest_batch* b, const trgt_locus_batch_out* o) {
+// given_meth (trgt_writer_write_meth): Allele::meth per output slot, NaN = None, in place of the host's own get_meth over the reads' bases
+static int writer_write_impl(trgt_writer* w, const trgt_ingest_batch* b, const trgt_locus_batch_out* o, const double* given_meth = nullptr) {
   if (!w || !b || !o) return TRGT_ERR_INVALID;
   auto bad = [&](const std::string& m) { w->err = m; return TRGT_ERR_INVALID; };
   if (!o->n_alleles || !o->allele_blob || !o->allele_off || !o->allele_len || !o->ci || !o->num_spanning || !o->classification || !o->read_rank ||
@@ -339,7 +340,7 @@ static int writer_write_impl(trgt_writer* w, const trgt_ingest_batch* b, const t
       // get_meth (tr.rs:196-229) in the genotype's own order (before "reference allele first")
       const bool flipped = o->flipped && o->flipped[l] && n_al == 2;
       double meth_sum[2] = {0, 0}; size_t meth_n[2] = {0, 0};
-      if (b->has_meth && b->meth && b->meth_off) {
+      if (!given_meth && b->has_meth && b->meth && b->meth_off) {
         auto pre = [&](int a) { return flipped ? 1 - a : a; };  // allele of the original order -> output slot
         const size_t sz[2] = {(size_t)(o->gt_size ? o->gt_size[2 * l + pre(0)] : (int32_t)o->allele_len[2 * l + pre(0)]),
                               n_al == 2 ? (size_t)(o->gt_size ? o->gt_size[2 * l + pre(1)] : (int32_t)o->allele_len[2 * l + pre(1)]) : 0};
@@ -387,7 +388,8 @@ static int writer_write_impl(trgt_writer* w, const trgt_ingest_batch* b, const t
         if (std::isnan(o->purity[2 * l + a])) f_ap += "."; else { std::snprintf(num, sizeof num, "%.6f", o->purity[2 * l + a]); f_ap += num; }
         f_am += sep;
         const int src = flipped ? 1 - a : a;  // the allele's slot in the original order
-        if (meth_n[src]) { std::snprintf(num, sizeof num, "%.2f", meth_sum[src] / (double)meth_n[src]); f_am += num; } else f_am += ".";
+        if (given_meth) { if (std::isnan(given_meth[2 * l + a])) f_am += "."; else { std::snprintf(num, sizeof num, "%.2f", given_meth[2 * l + a]); f_am += num; } }
+        else if (meth_n[src]) { std::snprintf(num, sizeof num, "%.2f", meth_sum[src] / (double)meth_n[src]); f_am += num; } else f_am += ".";
       }
       line += ":" + f_al + ":" + f_allr + ":" + f_sd + ":" + f_mc + ":" + f_ms + ":" + f_ap + ":" + f_am + "\n";
     }
@@ -618,6 +620,11 @@ int trgt_writer_open(const trgt_ingest* src, const trgt_writer_params* p, const 
 }
 int trgt_writer_write(trgt_writer* w, const trgt_ingest_batch* b, const trgt_locus_batch_out* o) {
   try { return writer_write_impl(w, b, o); } catch (const std::exception& e) { if (w) w->err = std::string("trgt_writer_write: ") + e.what(); return TRGT_ERR_NOMEM; }
+}
+int trgt_writer_write_meth(trgt_writer* w, const trgt_ingest_batch* b, const trgt_locus_batch_out* o, const double* allele_meth, const int32_t* meth_reads) {
+  if (!w) return TRGT_ERR_INVALID;
+  if (!allele_meth || !meth_reads) { w->err = "trgt_writer_write_meth: allele_meth and meth_reads are both required"; return TRGT_ERR_INVALID; }
+  try { return writer_write_impl(w, b, o, allele_meth); } catch (const std::exception& e) { w->err = std::string("trgt_writer_write_meth: ") + e.what(); return TRGT_ERR_NOMEM; }
 }
 
 int trgt_writer_close(trgt_writer* w) {

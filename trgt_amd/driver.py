@@ -114,6 +114,13 @@ def split_batch(batch, chunk_loci):
             m0o, m1o = int(mo[r0]), int(mo[r1])
             c["mismatch_off"] = np.ascontiguousarray(mo[r0:r1 + 1] - np.uint64(m0o))
             c["mismatch_offsets"] = np.ascontiguousarray(np.concatenate([batch["mismatch_offsets"][m0o:m1o], np.zeros(1, np.int32)]).astype(np.int32))
+        # what get_meth reads (locus.allele_meth): the calls re-based like the mismatch offsets, one spare byte behind an empty range
+        if all(batch.get(k) is not None for k in ("meth", "meth_off", "has_meth")):
+            eo = batch["meth_off"]
+            e0, e1 = int(eo[r0]), int(eo[r1])
+            c["meth_off"] = np.ascontiguousarray(eo[r0:r1 + 1] - np.uint64(e0))
+            c["meth"] = np.ascontiguousarray(np.concatenate([batch["meth"][e0:e1], np.zeros(1, np.uint8)]).astype(np.uint8))
+            c["has_meth"] = np.ascontiguousarray(np.concatenate([batch["has_meth"][r0:r1], np.zeros(1, np.uint8)])[:max(r1 - r0, 1)].astype(np.uint8))
         # (4-bit reads: the chunk's read_off still points into the parent's PACKED blob)
         if batch.get("read_encoding"):
             c["read_encoding"] = int(batch["read_encoding"])

@@ -54,7 +54,8 @@ class LocusResult:  # locus_result.rs:16-22
 
 def pack(loci):
     """loci: list of dict(left_flank, right_flank, tr, motifs, ploidy, reads[, genotyper ("size" | "cluster"), read_qual, and -- what
-    genotype_flank reads -- hp_tag (None / 1 / 2 per read), start_offset, end_offset, mismatch_offsets (a list per read)]).
+    genotype_flank reads -- hp_tag (None / 1 / 2 per read), start_offset, end_offset, mismatch_offsets (a list per read); and -- what
+    get_meth reads -- meth: per read None or a byte sequence, HiFiRead::meth, one call per CpG of the read]).
     Returns the ABI arrays (host)."""
     flank, tr, motifs, reads = bytearray(), bytearray(), bytearray(), bytearray()
     lf_off, lf_len, rf_off, rf_len, tr_off, tr_len, motif_off, set_begin, ploidy, lrb, read_off, read_len = ([] for _ in range(12))
@@ -64,7 +65,14 @@ def pack(loci):
     genotyper, read_qual = [], []
     has_meta = any(L.get("hp_tag") is not None or L.get("mismatch_offsets") is not None for L in loci)
     hp, so, eo, mm, mm_off = [], [], [], [], [0]
+    has_meth_key = any(L.get("meth") is not None for L in loci)
+    calls, calls_off, has_meth = bytearray(), [0], []
     for L in loci:
+        if has_meth_key:
+            for v in (L.get("meth") if L.get("meth") is not None else [None] * len(L["reads"])):
+                has_meth.append(0 if v is None else 1)
+                calls += b"" if v is None else bytes(v)
+                calls_off.append(len(calls))
         if has_meta:
             n = len(L["reads"])
             hp += [-1 if v is None else int(v) for v in (L.get("hp_tag") if L.get("hp_tag") is not None else [None] * n)]
@@ -96,7 +104,9 @@ def pack(loci):
                 read_off=np.array(read_off, np.uint64), read_len=np.array(read_len, np.uint32),
                 genotyper=np.array(genotyper, np.uint8), read_qual=np.array(read_qual, np.float64),
                 **(dict(hp_tag=np.array(hp, np.int16), start_offset=np.array(so, np.int32), end_offset=np.array(eo, np.int32),
-                        mismatch_offsets=np.array(mm + [0], np.int32), mismatch_off=np.array(mm_off, np.uint64)) if has_meta else {}))
+                        mismatch_offsets=np.array(mm + [0], np.int32), mismatch_off=np.array(mm_off, np.uint64)) if has_meta else {}),
+                **(dict(meth=u8(calls), meth_off=np.array(calls_off, np.uint64), has_meth=np.array(has_meth or [0], np.uint8))
+                   if has_meth_key else {}))
 
 
 def find_tr_spans_batch(batch, params=Params(), ctx=None, flank_dev=None, reads_dev=None):
@@ -278,8 +288,27 @@ def submit_batch(batch, params=Params(), ctx=None, outputs=None, flank=None, rea
     return Ticket(ctx, batch, out, cin, lp, (fl, rd) + tuple(batch.get(k) for k in _CIN_KEYS), t.value)
 
 
-def locus_result(batch, out, l):
-    """Unpack locus l of a finished batch into the reference's LocusResult shape."""
+def allele_meth(batch, out, ctx=None, reads_dev=None, meth_dev=None):
+    """trgt_locus_meth_batch -- get_meth / assign_read / get_tr_meth (tr.rs:198-266, 363-398) -- for a finished batch that carries meth,
+    meth_off and has_meth (pack(): the per-locus "meth" lists; ingest: the reader's arrays).  out: the BatchOutputs trgt_locus_batch filled.
+    Returns (allele_meth [2 per locus, output order, NaN = None], meth_reads [2 per locus], read_meth [per input read, NaN = None]).
+    *_dev: optional HBM copies of read_blob / meth (torch tensors or _lib.DevPtr)."""
+    ctx = ctx or _lib.context()
+    for k in ("meth", "meth_off", "has_meth"):
+        if batch.get(k) is None:
+            raise KeyError("allele_meth: the batch carries no %r" % k)
+    nl, nr = int(batch["n_loci"]), int(batch["locus_read_begin"][int(batch["n_loci"])])
+    am, n, rm = np.full(2 * nl, np.nan), np.zeros(2 * nl, np.int32), np.full(max(nr, 1), np.nan)
+    reads = reads_dev if reads_dev is not None else batch["read_blob"]
+    cin = _batch_in(batch, batch["flank_blob"], reads)
+    p = _lib.ptr
+    ctx.check(_lib.lib().trgt_locus_meth_batch(ctx.handle, C.addressof(cin), C.addressof(out.c_out), p(meth_dev if meth_dev is not None else batch["meth"]),
+                                               p(batch["meth_off"]), p(batch["has_meth"]), p(am), p(n), p(rm)))
+    return am, n, rm[:nr]
+
+
+def locus_result(batch, out, l, meth=None):
+    """Unpack locus l of a finished batch into the reference's LocusResult shape.  meth: allele_meth()'s first array, for Allele.meth."""
     a0, a1 = int(batch["locus_read_begin"][l]), int(batch["locus_read_begin"][l + 1])
     geno = []
     for a in range(int(out.n_alleles[l])):
@@ -290,7 +319,7 @@ def locus_result(batch, out, l):
         co = int(out.count_off[s])
         counts = [int(v) for v in out.motif_counts[co:co + int(out.n_motifs[l])]]
         geno.append(Allele(seq, Annotation(labels, counts, float(out.purity[s])), (int(out.ci[4 * l + 2 * a]), int(out.ci[4 * l + 2 * a + 1])),
-                           int(out.num_spanning[2 * l + a])))
+                           int(out.num_spanning[2 * l + a]), None if meth is None or math.isnan(meth[s]) else float(meth[s])))
     rank = out.read_rank[a0:a1]
     kept = [int(i) for i in np.argsort(np.where(rank >= 0, rank, 1 << 30), kind="stable")[:int((rank >= 0).sum())]]
     return LocusResult(geno, kept, [(int(out.span_start[a0 + i]), int(out.span_end[a0 + i])) for i in kept],
@@ -301,4 +330,5 @@ def analyze_batch(loci, params=Params(), ctx=None):
     """analyze() for a list of loci (dicts, see pack) -> list of LocusResult."""
     batch = pack(loci)
     out = run_batch(batch, params, ctx)
-    return [locus_result(batch, out, l) for l in range(len(loci))]
+    meth = allele_meth(batch, out, ctx)[0] if batch.get("meth") is not None else None
+    return [locus_result(batch, out, l, meth) for l in range(len(loci))]

@@ -44,11 +44,22 @@ class Writer:
                 self.handle = C.c_void_p()
                 raise _lib.TrgtHipError("trgt_writer_set_records_device: %s" % msg)
 
-    def write(self, batch, outputs):
-        """batch: a dict of ingest.Reader.batch(..., keep_native=True); outputs: the locus.BatchOutputs trgt_locus_batch filled for it"""
-        rc = self._L.trgt_writer_write(self.handle, batch["_native"].handle, C.addressof(outputs.c_out))
+    def write(self, batch, outputs, allele_meth=None, meth_reads=None):
+        """batch: a dict of ingest.Reader.batch(..., keep_native=True); outputs: the locus.BatchOutputs trgt_locus_batch filled for it.
+        allele_meth / meth_reads (both or neither): what locus.allele_meth returned for the batch -- trgt_writer_write_meth then prints the
+        AM field from them and the host's own scan of the reads for CpGs is skipped."""
+        if (allele_meth is None) != (meth_reads is None):
+            raise ValueError("Writer.write: allele_meth and meth_reads go together")
+        if allele_meth is None:
+            name, rc = "trgt_writer_write", self._L.trgt_writer_write(self.handle, batch["_native"].handle, C.addressof(outputs.c_out))
+        else:
+            am, n = np.ascontiguousarray(allele_meth, np.float64), np.ascontiguousarray(meth_reads, np.int32)
+            if len(am) != 2 * int(batch["n_loci"]) or len(n) != len(am):
+                raise ValueError("Writer.write: allele_meth and meth_reads hold two values per locus")
+            self._L.trgt_writer_write_meth.argtypes = [C.c_void_p, C.POINTER(IngestBatch), C.c_void_p, C.c_void_p, C.c_void_p]
+            name, rc = "trgt_writer_write_meth", self._L.trgt_writer_write_meth(self.handle, batch["_native"].handle, C.addressof(outputs.c_out), _lib.ptr(am), _lib.ptr(n))
         if rc != 0:
-            raise _lib.TrgtHipError("trgt_writer_write: %s" % self._L.trgt_writer_last_error(self.handle).decode())
+            raise _lib.TrgtHipError("%s: %s" % (name, self._L.trgt_writer_last_error(self.handle).decode()))
 
     def device_stats(self):
         """trgt_writer_device_stats: BGZF blocks of the spanning BAM deflated on the device / declined by it / deflated by zlib for lack of a
