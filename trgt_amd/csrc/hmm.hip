@@ -1654,909 +1654,16 @@ __global__ void __launch_bounds__(1024) hmm_span_prefix_kernel(const uint32_t* _
 }
 
 
-// ---- host side of the long trace-back: room for the chunk maps of a job that may be long, and the launch behind a class's fill kernel
-// From how many columns on an allele's trace-back goes to the many-wave kernel: 1 536 in a class of thousands of jobs (every long job
-// costs that kernel three launches' worth of chunk maps: the hundreds of 0.5-2 kb VNTR alleles of a catalog step were 27 % slower
-// through it), 512 in a small class (a pathogenic catalog: the one lane of the fill kernel chasing 1 500 columns was 1.2 ms of a call).
-static inline uint32_t hmm_long_min(uint64_t class_jobs) { return class_jobs <= 256 ? 512u : (uint32_t)HMM_LONG_MIN; }  // (2 048 was too many: the 2 000 VNTR candidates of a cfg4 step, 9.2 -> 10.6 ms)
-static inline uint64_t hmm_map_words(uint32_t S, uint64_t max_len, uint32_t long_min) {
-  const uint64_t L = max_len + 2;
-  if (L < (uint64_t)long_min) return 0;
-  const uint64_t n_chunks = (L + HMM_LONG_CHUNK - 1) / HMM_LONG_CHUNK;
-  return n_chunks * (3ull * S + 8ull) + 8;
-}
-static size_t hmm_long_lds_bytes(uint32_t S, uint32_t nb) {
-  size_t o = 64 + (size_t)20 * S + (size_t)20 * nb + ((S + 3) & ~3u) + (((size_t)S / 3 + 15) & ~(size_t)15) + 32;
-  return ((o + 15) & ~(size_t)15) + (size_t)(HMM_LONG_THREADS / 64) * (HMM_LONG_STG + 512) + HMM_LONG_MAP_LDS;
-}
-static size_t hmm_lds_bytes(uint32_t S, uint32_t nb) {
-  size_t o = 64 + (((size_t)HMM_LDS_PER_STATE * S + 15) & ~(size_t)15) + (((size_t)16 * nb + 15) & ~(size_t)15) + (size_t)hmm_stage_bytes((int)((S + 15) & ~15u));
-  o += HMM_CODE_WINDOW + HMM_CODE_PAD + (((size_t)S / 3 + 15) & ~(size_t)15) + 12 * (size_t)HMM_VIS_LDS + 4 * (size_t)nb;
-  o += 8 + 8 * 64;  // the steps of a trace-back round (l_rec)
-  return o + 64;
-}
-
-
-// Launch class of a motif set: 0 = at most 32 states (two alleles per wave of hmm_viterbi_kernel), w = 1 .. max_waves: its workgroup
-// of w waves (a thread per lane), above that HMM_CLASS_BIG: hmm_viterbi_big_kernel (hmm_big.hpp; the lanes tiled over 1 024 threads).
-// trgt_hmm_batch launches hmm_viterbi_kernel with up to 16 waves, the locus path (hmm_enqueue_slots) with up to 7.
-constexpr uint32_t HMM_BATCH_MAX_WAVES = 16, HMM_SLOT_MAX_WAVES = 7, HMM_CLASS_BIG = 17;
-static inline uint32_t hmm_set_class(const HmmSetDev& sd, uint32_t max_waves) {
-  if (sd.S <= 32) return 0u;
-  const uint32_t w = (std::max(sd.S, sd.n_lanes) + 63) / 64;
-  return w <= max_waves ? w : HMM_CLASS_BIG;
-}
-// One class of large models behind the resolved job list [jobs, jobs + nj) (n_jobs_dev: its length on the device, or null)
-static int hmm_launch_big(trgt_hip_ctx* c, hipStream_t ls, uint32_t maxS, uint32_t maxnb, uint32_t nj, const HmmJobDev* d_jobs, const HmmSetDev* d_sets, const uint8_t* d_model,
-                          const uint8_t* d_seq, uint8_t* d_bp, uint32_t* d_visits, uint16_t* path, uint32_t* plen, int32_t* spans, uint32_t* nsp, uint32_t* cnt, double* pur,
-                          int32_t* edit, int32_t* maxd, const uint32_t* n_jobs_dev) {
-  const size_t lds = hmm_big_lds(maxS, maxnb).total;
-  if (lds > 160 * 1024) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: LDS need %zu B", lds);
-  if (lds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)hmm_viterbi_big_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipLaunchKernelGGL(hmm_viterbi_big_kernel, dim3(nj), dim3(HMM_BIG_THREADS), lds, ls, d_jobs, d_sets, d_model, d_seq, d_bp, d_visits, path, plen, spans, nsp, cnt, pur, edit, maxd, nj, n_jobs_dev);
-  TRGT_HIP_TRY(c, hipGetLastError());
-  return TRGT_OK;
-}
-
-// The position-per-lane fill (hmm_ppl.hpp) of one class's job list, in front of the class's trace-back launch on the same stream: one
-// launch per group width the class's sets need (lanes_mask: bit 0 = 8 lanes, 1 = 16, 2 = 32, 3 = 64); a launch walks the whole list
-// and takes the jobs of its width (groups of other widths idle: a wave without a job of its own returns at once).
-static int hmm_launch_ppl(trgt_hip_ctx* c, int bset, int class_slot, hipStream_t ls, unsigned lanes_mask, const HmmJobDev* d_jobs, const HmmSetDev* d_sets, const uint8_t* d_model,
-                          const uint8_t* d_seq, uint8_t* d_bp, const ppl::PplSegs& segs) {
-  if (!segs.begin[segs.n_seg]) return TRGT_OK;
-  auto launch = [&](int g, hipStream_t s) {
-    const uint32_t nj = segs.end_slot[g] > segs.first_slot[g] ? segs.end_slot[g] - segs.first_slot[g] : 0u;  // job slots this width looks at
-    if (!nj) return;
-    // (rows of one byte per lane; TRGT_HMM_PPL_WIDE in `make DEV=1` builds: the round-5 rows of one byte per state)
-#define TRGT_PPL_LAUNCH(GG, NB)                                                                                                                         \
-    do { if (c->knobs.hmm_ppl_wide) hipLaunchKernelGGL((ppl::hmm_fill_ppl_kernel<GG, false>), dim3(NB), dim3(64), 0, s, d_jobs, d_sets, d_model, d_seq, d_bp, segs); \
-         else hipLaunchKernelGGL((ppl::hmm_fill_ppl_kernel<GG, true>), dim3(NB), dim3(64), 0, s, d_jobs, d_sets, d_model, d_seq, d_bp, segs); } while (0)
-    if (g == 0) TRGT_PPL_LAUNCH(8, (nj + 7) / 8);
-    else if (g == 1) TRGT_PPL_LAUNCH(16, (nj + 3) / 4);
-    else if (g == 2) TRGT_PPL_LAUNCH(32, (nj + 1) / 2);
-    else TRGT_PPL_LAUNCH(64, nj);
-#undef TRGT_PPL_LAUNCH
-  };
-  // the widest groups on the class's own stream; the other widths (disjoint jobs) next to it on side streams forked off that stream and
-  // joined back into it: one behind the other they added up their tails (a cfg4 class with 32- and 64-lane sets: 0.53 + 0.47 ms in
-  // front of its trace-back)
-  const bool side_ok = !c->knobs.hmm_ppl_serial && class_slot >= 0 && class_slot < 4 && (lanes_mask & (lanes_mask - 1u)) != 0u;
-  if (!side_ok) {
-    for (int g = 3; g >= 0; --g) if (lanes_mask & (1u << g)) launch(g, ls);
-    return TRGT_OK;
-  }
-  hipEvent_t& f = c->hmm_ppl_fork[bset][class_slot];
-  if (!f) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&f, hipEventDisableTiming));
-  TRGT_HIP_TRY(c, hipEventRecord(f, ls));
-  int n_side = 0;
-  bool first = true;
-  for (int g = 3; g >= 0; --g) {
-    if (!(lanes_mask & (1u << g))) continue;
-    if (first || n_side >= 3) { launch(g, ls); first = false; continue; }
-    hipStream_t& s = c->hmm_ppl_side[bset][class_slot][n_side];
-    hipEvent_t& j = c->hmm_ppl_join[bset][class_slot][n_side];
-    if (!s) TRGT_HIP_TRY(c, trgt::make_side_stream(c, &s));
-    if (!j) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&j, hipEventDisableTiming));
-    TRGT_HIP_TRY(c, hipStreamWaitEvent(s, f, 0));
-    launch(g, s);
-    TRGT_HIP_TRY(c, hipEventRecord(j, s));
-    ++n_side;
-  }
-  for (int i = 0; i < n_side; ++i) TRGT_HIP_TRY(c, hipStreamWaitEvent(ls, c->hmm_ppl_join[bset][class_slot][i], 0));
-  return TRGT_OK;
-}
-static inline ppl::PplSegs hmm_ppl_one_segment(uint32_t nj, const uint32_t* n_jobs_dev) { ppl::PplSegs g{}; g.begin[1] = nj; g.n_seg = 1; g.counts = n_jobs_dev; for (int w = 0; w < 4; ++w) { g.first_slot[w] = 0; g.end_slot[w] = nj; } return g; }
-static inline unsigned hmm_ppl_bit(const HmmSetDev& sd) { const int g = ppl::lanes_for(sd.ppl_lanes); return g == 8 ? 1u : g == 16 ? 2u : g == 32 ? 4u : g == 64 ? 8u : 0u; }
-
-// ---- the launches of one class (jobs of one workgroup size), for a host-built job list (hmm_enqueue) and a device-resolved one
-//      (hmm_enqueue_slots) alike.
-// The buffers every kernel of a batch gets:
-struct HmmLaunchBufs {
-  const HmmSetDev* sets; const uint8_t* model; const uint8_t* seq; uint8_t* bp; uint32_t* visits;
-  uint16_t* path; uint32_t* plen; int32_t* spans; uint32_t* nsp; uint32_t* cnt; double* pur; int32_t* edit; int32_t* maxd;
-};
-struct HmmClassLaunch {
-  uint32_t cls;                // hmm_set_class of the class's sets (HMM_CLASS_BIG: hmm_viterbi_big_kernel)
-  int ordinal;                 // how many classes of this batch were launched before (0: on the batch's stream, else on a side stream)
-  int buffer_set;
-  const HmmJobDev* jobs;       // the class's jobs (device) ...
-  uint32_t nj;                 // ... how many there are (a device-resolved list: at most) ...
-  const uint32_t* n_jobs_dev;  // ... and, for a device-resolved list, where the device counted them (else null)
-  uint32_t maxS, maxnb;        // largest model of the class
-  uint64_t max_len;            // longest allele the class can have
-  unsigned ppl_mask;           // group widths of the class's position-per-lane fills (hmm_ppl_bit)
-  bool ppl_launched;           // those fills were launched in front, merged over all classes
-  size_t first_job, n_listed;  // where the class's jobs begin in the batch's list, and that list's length (S_HMM_LONG fallback, below)
-  int64_t cells;               // for the timer
-  unsigned* side_used;         // the batch's side streams in use so far (hmm_join_classes)
-  HmmLaunchBufs b;
-};
-constexpr size_t HMM_LONG_PIECE_PAD = 16;
-
-// The `lds_per_job` word of hmm_viterbi_kernel, as its first lines decode it:
-//   bits  0-22  LDS bytes of one job (a multiple of 16)
-//   bit   23    the position-per-lane fill wrote rows of one byte per lane (hmm_fill_ppl_kernel<G, true>), not one per state
-//   bits 24-29  columns from which an allele goes to hmm_traceback_long_kernel, / 256 (0: HMM_LONG_MIN)
-//   bit   30    the back-pointers of sets with ppl_lanes are there already (hmm_fill_ppl_kernel ran in front)
-//   bit   31    TRGT_HMM_FOUR_ROUNDS
-static uint32_t hmm_viterbi_flags(const trgt_hip_ctx* c, size_t lds_job, unsigned ppl_mask, uint32_t long_min) {
-  return (uint32_t)lds_job | (c->knobs.hmm_four_rounds ? 0x80000000u : 0u) | (ppl_mask ? 0x40000000u : 0u) | (ppl_mask && !c->knobs.hmm_ppl_wide ? 0x00800000u : 0u) | ((long_min / 256u) << 24);
-}
-// The four instantiations of hmm_viterbi_kernel: two alleles per wave or one, score columns in registers (one-wave classes) or in LDS
-struct HmmViterbiFn {
-  const void* fn;
-  void (*launch)(dim3 grid, dim3 block, size_t lds, hipStream_t ls, const HmmClassLaunch& a, uint32_t flags, uint32_t* d_long);
-};
-template <int SUB, bool ONE_WAVE>
-static void hmm_launch_viterbi(dim3 grid, dim3 block, size_t lds, hipStream_t ls, const HmmClassLaunch& a, uint32_t flags, uint32_t* d_long) {
-  hipLaunchKernelGGL((hmm_viterbi_kernel<SUB, ONE_WAVE>), grid, block, lds, ls, a.jobs, a.b.sets, a.b.model, a.b.seq, a.b.bp, a.b.visits, a.b.path, a.b.plen, a.b.spans,
-                     a.b.nsp, a.b.cnt, a.b.pur, a.b.edit, a.b.maxd, a.nj, flags, a.n_jobs_dev, d_long);
-}
-template <int SUB, bool ONE_WAVE>
-static HmmViterbiFn hmm_viterbi_fn() { return {(const void*)hmm_viterbi_kernel<SUB, ONE_WAVE>, hmm_launch_viterbi<SUB, ONE_WAVE>}; }
-
-// The classes of a batch run next to each other: the first on the batch's stream, the others on side streams forked off it (three per
-// buffer set, in rotation) and joined back into it.  A class is bounded by its longest allele: one behind the other they add up their tails.
-static int hmm_fork_record(trgt_hip_ctx* c, int buffer_set) {  // where the side streams fork off: in front of the first class's launch
-  hipEvent_t& ev = c->hmm_fork[buffer_set ? 1 : 0];
-  if (!ev) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  TRGT_HIP_TRY(c, hipEventRecord(ev, c->stream));
-  return TRGT_OK;
-}
-static int hmm_class_stream(trgt_hip_ctx* c, int buffer_set, int ordinal, unsigned& side_used, hipStream_t* ls) {
-  *ls = c->stream;
-  if (ordinal == 0) return TRGT_OK;
-  const int sidx = (ordinal - 1) % 3 + (buffer_set ? 3 : 0);
-  if (!c->hmm_side[sidx]) TRGT_HIP_TRY(c, trgt::make_side_stream(c, &c->hmm_side[sidx]));
-  if (!c->hmm_join[sidx]) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->hmm_join[sidx], hipEventDisableTiming));
-  *ls = c->hmm_side[sidx];
-  TRGT_HIP_TRY(c, hipStreamWaitEvent(*ls, c->hmm_fork[buffer_set ? 1 : 0], 0));
-  side_used |= 1u << sidx;
-  return TRGT_OK;
-}
-static int hmm_join_classes(trgt_hip_ctx* c, unsigned side_used) {
-  for (int sidx = 0; sidx < 6; ++sidx)
-    if (side_used & (1u << sidx)) {
-      TRGT_HIP_TRY(c, hipEventRecord(c->hmm_join[sidx], c->hmm_side[sidx]));
-      TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->hmm_join[sidx], 0));
-    }
-  return TRGT_OK;
-}
-
-static int hmm_launch_class(trgt_hip_ctx* c, const HmmClassLaunch& a) {
-  int rc;
-  const bool half = a.cls == 0;             // two alleles per wave
-  const bool big = a.cls == HMM_CLASS_BIG;  // (hmm_viterbi_big_kernel: no position-per-lane fill, its own trace-back for every length)
-  const size_t lds_job = big ? 0 : (hmm_lds_bytes(a.maxS, a.maxnb) + 15) & ~(size_t)15;
-  const size_t lds = half ? 2 * lds_job : lds_job;
-  if (lds > 160 * 1024) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_hmm_batch: LDS need %zu B", lds);
-  const bool regs = !c->knobs.hmm_lds_fill;  // one-wave classes keep the score columns in registers (TRGT_HMM_LDS_FILL=1: in LDS like the others)
-  const HmmViterbiFn k = half ? (regs ? hmm_viterbi_fn<32, true>() : hmm_viterbi_fn<32, false>())
-                              : (regs && a.cls == 1 ? hmm_viterbi_fn<64, true>() : hmm_viterbi_fn<64, false>());
-  if (lds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  hipStream_t ls;
-  if ((rc = hmm_class_stream(c, a.buffer_set, a.ordinal, *a.side_used, &ls))) return rc;
-  KTimer t(c, TRGT_K_HMM, ls);
-  const HmmLaunchBufs& b = a.b;
-  if (big) {
-    if ((rc = hmm_launch_big(c, ls, a.maxS, a.maxnb, a.nj, a.jobs, b.sets, b.model, b.seq, b.bp, b.visits, b.path, b.plen, b.spans, b.nsp, b.cnt, b.pur, b.edit, b.maxd, a.n_jobs_dev))) return rc;
-    t.stop(a.cells);
-    return TRGT_OK;
-  }
-  // (the class's list of long alleles: filled by the fill kernel, worked off by the trace-back kernel right behind it)
-  uint32_t* d_long_cls = nullptr;
-  const uint32_t long_min_cls = hmm_long_min(a.nj);
-  if (!c->knobs.hmm_no_long_tb && a.max_len + 2 >= (uint64_t)long_min_cls) {
-    if (void* z = zero_take(c, ((size_t)a.nj + 16) * 4)) d_long_cls = (uint32_t*)z;  // [count | job indices] of this class, the count cleared
-    else {
-      // no zero arena: S_HMM_LONG, n_listed + HMM_LONG_PIECE_PAD * (HMM_CLASS_BIG + 1) words.  The class with `ordinal` classes in
-      // front of it, whose jobs are [first_job, first_job + nj) of the batch's list, has the nj + HMM_LONG_PIECE_PAD words from
-      // first_job + HMM_LONG_PIECE_PAD * ordinal on: the pieces follow each other without overlap, whatever the classes' sizes.
-      void* dl = nullptr;
-      const int so = a.buffer_set ? (int)S_HMM_B_BASE - (int)S_HMM_SEQ : 0;
-      if ((rc = dev_get(c, S_HMM_LONG + so, (a.n_listed + HMM_LONG_PIECE_PAD * (HMM_CLASS_BIG + 1)) * 4, &dl))) return rc;
-      d_long_cls = (uint32_t*)dl + a.first_job + HMM_LONG_PIECE_PAD * (size_t)a.ordinal;
-      TRGT_HIP_TRY(c, hipMemsetAsync(d_long_cls, 0, 4, ls));
-    }
-  }
-  if (a.ppl_mask && !a.ppl_launched &&
-      (rc = hmm_launch_ppl(c, a.buffer_set ? 1 : 0, a.ordinal & 3, ls, a.ppl_mask, a.jobs, b.sets, b.model, b.seq, b.bp, hmm_ppl_one_segment(a.nj, a.n_jobs_dev)))) return rc;
-  k.launch(dim3(half ? (a.nj + 1) / 2 : a.nj), dim3(half ? 64 : 64 * a.cls), lds, ls, a, hmm_viterbi_flags(c, lds_job, a.ppl_mask, long_min_cls), d_long_cls);
-  TRGT_HIP_TRY(c, hipGetLastError());
-  if (d_long_cls) {
-    const size_t llds = hmm_long_lds_bytes(a.maxS, a.maxnb);
-    if (llds > 64 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)hmm_traceback_long_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)llds));
-    const int G = c->knobs.hmm_long_wgs;  // workgroups per long allele (1: one launch, the whole trace-back by one workgroup; else the phases 1 / 2 / 3)
-    for (int ph = G > 1 ? 1 : 0; ph <= (G > 1 ? 3 : 0); ++ph) {
-      const int g = ph == 1 || ph == 3 ? G : 1;
-      hipLaunchKernelGGL(hmm_traceback_long_kernel, dim3((unsigned)std::min<uint32_t>(a.nj, 64u) * (unsigned)g), dim3(HMM_LONG_THREADS), llds, ls, a.jobs, b.sets, b.model, b.seq,
-                         (const uint8_t*)b.bp, b.visits, b.path, b.plen, b.spans, b.nsp, b.cnt, b.pur, b.edit, b.maxd, (const uint32_t*)d_long_cls,
-                         ph | (a.ppl_mask && !c->knobs.hmm_ppl_wide ? 0x100 : 0), g);  // (bit 8: rows of one byte per lane, as bit 23 above)
-    }
-    TRGT_HIP_TRY(c, hipGetLastError());
-  }
-  t.stop(a.cells);
-  return TRGT_OK;
-}
-
-// All motif-set models of a batch (host side).  Thread-safe: touches no ctx state.
-int hmm_build_models(int32_t n_sets, const uint8_t* motif_blob, const uint32_t* motif_off, const uint32_t* set_motif_begin, HmmModels& out) {
-  char msg[160];
-  out.rc = 0;
-  std::vector<HmmSetDev>& sets = out.sets;
-  sets.assign((size_t)n_sets, HmmSetDev());
-  std::vector<std::vector<uint8_t>> blobs((size_t)n_sets);
-  std::vector<int> set_err((size_t)n_sets, 0);
-  {
-    const int nthr = (int)std::min<int64_t>(std::max(1u, std::min(32u, std::thread::hardware_concurrency())), std::max(1, n_sets / 64));
-    auto work = [&](int t) {
-      for (int s = t; s < n_sets; s += nthr) {
-        std::vector<std::string> motifs;
-        for (uint32_t m = set_motif_begin[s]; m < set_motif_begin[s + 1]; ++m) {
-          std::string mot((const char*)motif_blob + motif_off[m], motif_off[m + 1] - motif_off[m]);
-          if (mot.empty()) { set_err[s] = 1; break; }
-          static const char allowed[] = "ATCGN";  // replace_invalid_bases(m, ATCGN)
-          for (size_t i = 0; i < mot.size(); ++i)
-            if (mot[i] == 0 || !std::strchr("ATCGN", mot[i])) mot[i] = allowed[i % 5];
-          motifs.push_back(mot);
-        }
-        if (set_err[s]) continue;
-        if (motifs.empty()) { set_err[s] = 2; continue; }
-        build_set(motifs, blobs[s], sets[s]);
-        if (sets[s].S > HMM_BIG_MAX_STATES || sets[s].n_lanes > HMM_BIG_MAX_STATES) set_err[s] = 3;
-        else if (sets[s].n_blocks > 254) set_err[s] = 4;
-      }
-    };
-    if (nthr <= 1) work(0);
-    else {
-      std::vector<std::thread> th;
-      for (int t = 0; t < nthr; ++t) th.emplace_back(work, t);
-      for (auto& x : th) x.join();
-    }
-  }
-  std::vector<uint8_t>& blob = out.blob;
-  {
-    uint64_t total = 0;
-    for (int s = 0; s < n_sets; ++s) {
-      if (set_err[s] == 1) { snprintf(msg, sizeof msg, "trgt_hmm_batch: empty motif in set %d", s); out.err = msg; return out.rc = TRGT_ERR_INVALID; }
-      if (set_err[s] == 2) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has no motif", s); out.err = msg; return out.rc = TRGT_ERR_INVALID; }
-      if (set_err[s] == 3) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has %u HMM states on %u lanes (kernel limit %u)", s, sets[s].S, sets[s].n_lanes, HMM_BIG_MAX_STATES); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
-      if (set_err[s] == 4) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has too many motifs", s); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
-      total += blobs[s].size();
-    }
-    blob.resize((size_t)total);
-    uint64_t pos = 0;
-    for (int s = 0; s < n_sets; ++s) {
-      std::memcpy(blob.data() + pos, blobs[s].data(), blobs[s].size());
-      HmmSetDev& d = sets[s];
-      d.off_inlp += pos; d.off_em += pos; d.off_inst += pos; d.off_block += pos; d.off_nin += pos; d.off_level += pos;
-      d.off_flags += pos; d.off_blocks += pos; d.off_motifs += pos; d.off_perm += pos;
-      pos += blobs[s].size();
-      std::vector<uint8_t>().swap(blobs[s]);
-    }
-  }
-  return 0;
-}
-
-
-// All motif-set models of a batch, built ON THE DEVICE (hmm_model_build_kernel): the host lays the sets out (sizes, offsets, lane
-// tables: a few microseconds per thousand sets), uploads the motifs and the logarithm table (kilobytes) and launches one workgroup per
-// set -- instead of building ~2 KB of tables per set on host threads and uploading them (6 ms + 22 MB for a 10k-locus batch: it had
-// become the critical path of stage C).  Uploads and the kernel go to `up` (a stream with nothing in front of it); `done` is recorded
-// behind them.  out.sets / out.d_sets / out.d_blob are valid on return (the device side once `done` has fired).
-int hmm_models_on_device(trgt_hip_ctx* c, int32_t n_sets, const uint8_t* motif_blob, const uint32_t* motif_off, const uint32_t* set_motif_begin,
-                         HmmModels& out, hipStream_t up, hipEvent_t done) {
-  out.rc = 0; out.blob.clear(); out.d_sets = out.d_blob = nullptr;
-  std::vector<HmmSetDev>& sets = out.sets;
-  sets.assign((size_t)n_sets, HmmSetDev());
-  if (n_sets <= 0) return TRGT_OK;
-  const uint32_t m_total = set_motif_begin[n_sets];
-  const uint32_t byte0 = motif_off[0], bytes_total = motif_off[m_total] - byte0;
-  // layout: per set
-  std::vector<uint16_t> perm_all, perm;
-  std::vector<uint64_t> perm_src((size_t)n_sets, 0);
-  std::vector<uint32_t> mlens, blocks, seed_row((size_t)m_total, 0);
-  std::vector<double> seed_tab;
-  std::vector<int64_t> row_of_len;  // motif length -> first entry of its row (-1: none yet)
-  uint64_t pos = 0;
-  char msg[160];
-  for (int s = 0; s < n_sets; ++s) {
-    const uint32_t m0 = set_motif_begin[s], m1 = set_motif_begin[s + 1];
-    if (m1 <= m0) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has no motif", s); out.err = msg; return out.rc = TRGT_ERR_INVALID; }
-    if (m1 - m0 + 1 > 254) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has too many motifs", s); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
-    mlens.clear();
-    for (uint32_t m = m0; m < m1; ++m) {
-      const uint32_t n = motif_off[m + 1] - motif_off[m];
-      if (n == 0) { snprintf(msg, sizeof msg, "trgt_hmm_batch: empty motif in set %d", s); out.err = msg; return out.rc = TRGT_ERR_INVALID; }
-      mlens.push_back(n);
-      if (row_of_len.size() <= n) row_of_len.resize((size_t)n + 1, -1);
-      if (row_of_len[n] < 0) {  // ln(seed * (n - k)), k = 1 .. n - 1 (builder.rs:80-173), entry 0 unused
-        row_of_len[n] = (int64_t)seed_tab.size();
-        const double seed = 2.00 * (1.00 - 0.90) / (double)((size_t)n * (size_t)(n - 1));
-        seed_tab.push_back(0.0);
-        for (uint32_t k = 1; k < n; ++k) seed_tab.push_back(std::log(seed * (double)(n - k)));
-      }
-      seed_row[m] = (uint32_t)row_of_len[n];
-    }
-    HmmSetDev& d = sets[(size_t)s];
-    const uint64_t bytes = layout_set(mlens.data(), (uint32_t)mlens.size(), d, blocks, perm);
-    if (d.S > HMM_BIG_MAX_STATES || d.n_lanes > HMM_BIG_MAX_STATES) { snprintf(msg, sizeof msg, "trgt_hmm_batch: set %d has %u HMM states on %u lanes (kernel limit %u)", s, d.S, d.n_lanes, HMM_BIG_MAX_STATES); out.err = msg; return out.rc = TRGT_ERR_UNSUPPORTED; }
-    d.off_inlp += pos; d.off_em += pos; d.off_inst += pos; d.off_block += pos; d.off_nin += pos; d.off_level += pos;
-    d.off_flags += pos; d.off_blocks += pos; d.off_motifs += pos; d.off_perm += pos;
-    pos += bytes;
-    if (!perm.empty()) { perm_src[(size_t)s] = perm_all.size(); perm_all.insert(perm_all.end(), perm.begin(), perm.end()); }
-  }
-  out.blob_bytes = pos;
-  // one pinned slab -> one device slab: sets | motif_off (rebased) | set_motif_begin | seed_row | perm_src | seed_tab | perm_all | motif bytes
-  struct Lay { size_t total = 0; size_t add(size_t b) { const size_t o = total; total += (b + 15) & ~(size_t)15; return o; } } lay;
-  const size_t o_sets = lay.add(sizeof(HmmSetDev) * (size_t)n_sets), o_moff = lay.add(4 * ((size_t)m_total + 1)), o_smb = lay.add(4 * ((size_t)n_sets + 1)),
-               o_srow = lay.add(4 * (size_t)m_total), o_psrc = lay.add(8 * (size_t)n_sets), o_stab = lay.add(8 * seed_tab.size()),
-               o_perm = lay.add(2 * perm_all.size()), o_mot = lay.add(bytes_total);
-  void *h = nullptr, *dv = nullptr, *d_blob = nullptr, *d_sets = nullptr;
-  int rc;
-  if ((rc = pin_get(c, P_HMM_BUILD, lay.total, &h)) || (rc = dev_get(c, S_HMM_BUILD, lay.total, &dv)) ||
-      (rc = dev_get(c, S_HMM_MODEL, (size_t)pos + 16, &d_blob)))
-    return out.rc = rc;
-  uint8_t* hb = (uint8_t*)h;
-  std::memcpy(hb + o_sets, sets.data(), sizeof(HmmSetDev) * (size_t)n_sets);
-  { uint32_t* q = (uint32_t*)(hb + o_moff); for (uint32_t m = 0; m <= m_total; ++m) q[m] = motif_off[m] - byte0; }
-  std::memcpy(hb + o_smb, set_motif_begin, 4 * ((size_t)n_sets + 1));
-  std::memcpy(hb + o_srow, seed_row.data(), 4 * (size_t)m_total);
-  std::memcpy(hb + o_psrc, perm_src.data(), 8 * (size_t)n_sets);
-  std::memcpy(hb + o_stab, seed_tab.data(), 8 * seed_tab.size());
-  if (!perm_all.empty()) std::memcpy(hb + o_perm, perm_all.data(), 2 * perm_all.size());
-  {  // replace_invalid_bases(m, ATCGN) (utils.rs:29-42), position inside the motif
-    uint8_t* q = hb + o_mot;
-    static const char allowed[] = "ATCGN";
-    for (uint32_t m = 0; m < m_total; ++m) {
-      const uint8_t* src = motif_blob + motif_off[m];
-      const uint32_t n = motif_off[m + 1] - motif_off[m];
-      uint8_t* dst = q + (motif_off[m] - byte0);
-      for (uint32_t i = 0; i < n; ++i) { const uint8_t ch = src[i]; dst[i] = (ch == 'A' || ch == 'T' || ch == 'C' || ch == 'G' || ch == 'N') ? ch : (uint8_t)allowed[i % 5]; }
-    }
-  }
-  TRGT_HIP_TRY(c, hipSetDevice(c->device));
-  if ((rc = h2d_small(c, dv, h, lay.total, up, -1))) return out.rc = rc;  // (pinned source; a kernel copy: not queued behind bulk uploads)
-  // (the descriptors stay where they were uploaded -- the build slab lives as long as the models; the padding between a set's tables is
-  //  cleared by the build kernel itself, so that the blob compares equal to the host builder's: a D2D copy and a 20-MB fill per call less)
-  d_sets = (uint8_t*)dv + o_sets;
-  HmmBuildArgs a;
-  const uint8_t* db = (const uint8_t*)dv;
-  a.sets = (const HmmSetDev*)(db + o_sets); a.blob = (uint8_t*)d_blob; a.motif_bytes = db + o_mot; a.motif_off = (const uint32_t*)(db + o_moff);
-  a.set_motif_begin = (const uint32_t*)(db + o_smb); a.seed_row = (const uint32_t*)(db + o_srow); a.seed_tab = (const double*)(db + o_stab);
-  a.perm_all = (const uint16_t*)(db + o_perm); a.perm_src = (const uint64_t*)(db + o_psrc); a.blob_bytes = pos; a.k = hmm_build_consts();
-  hipLaunchKernelGGL(hmm_model_build_kernel, dim3((unsigned)n_sets), dim3(64), 0, up, a);
-  TRGT_HIP_TRY(c, hipGetLastError());
-  if (done) TRGT_HIP_TRY(c, hipEventRecord(done, up));
-  out.d_sets = d_sets; out.d_blob = d_blob;
-  return TRGT_OK;
-}
+#include "hmm_batch.hpp"  // the host side of a batch
 
 }  // namespace trgt
 
 using namespace trgt;
 
+// ---- C entry points
 extern "C" uint64_t trgt_hmm_path_capacity(uint32_t seq_len, uint32_t max_motif_len) {
   if (seq_len == 0) return 1;
   return (uint64_t)(seq_len + 2) * (max_motif_len + 4) + 8;
-}
-
-// State of an enqueued HMM batch between hmm_enqueue (uploads + kernel launches, no host wait for the kernels) and
-// hmm_collect (result copies).  One batch per ctx may be pending: the device buffers are the ctx's pool slots.
-struct trgt::HmmPending {
-  int64_t n_jobs = 0;
-  int set = 0; hipStream_t stream = nullptr;  // scratch-buffer set and stream of this batch
-  std::vector<uint64_t> cnt_off; std::vector<uint32_t> cnt_n; uint32_t* cnt_user = nullptr; uint64_t cnt_total = 0;  // motif counts go back job by job
-  bool spans_on_host = false;
-  // the packed copy of the spans is made behind the kernels at enqueue time (pack_behind_kernels): collect only copies
-  const int32_t* d_packed = nullptr; const uint64_t* d_poff = nullptr; uint64_t packed_cap_bytes = 0;
-  std::vector<uint64_t> tight_off;
-  std::vector<uint32_t> slot_nm;  // hmm_enqueue_slots: motifs of every slot's set (the job list is only known once the genotyper is back)
-  std::vector<uint64_t> slot_cnt_off;
-  std::vector<HmmJobDev> jobs;   // upload sources stay alive until the batch is collected
-  HmmModels local_models;
-  int32_t* spans3 = nullptr; const uint64_t* span_off = nullptr;
-  DevOut<uint16_t> o_path; DevOut<uint32_t> o_plen, o_nsp, o_cnt; DevOut<int32_t> o_spans, o_edit, o_maxd; DevOut<double> o_pur;
-};
-
-void trgt::hmm_pending_free(HmmPending* p) { delete p; }
-
-// Behind the kernels of a batch whose spans go to host memory: prefix of the span counts + compaction of the per-job span lists into
-// the back-pointer workspace (free once the kernels are through; at least 16 B per (base, state-row) >= 12 B per possible span).
-// hmm_collect then copies counts, total and the first HMM_PACKED_FIRST bytes of the packed spans in ONE go -- the host used to wait for
-// the counts, build the offsets, upload them, launch the compaction and wait again (0.5 ms of a 10k-locus call's tail).
-constexpr size_t HMM_PACKED_FIRST = 1u << 20;
-// (the offsets of the per-job span lists go up on `up` BEFORE the kernels are enqueued -- with the job list, on the copy stream in the
-//  slots path -- and not behind them on the batch's stream, where that upload sat on the critical path of every call's tail: round 5)
-static int pack_tables_upload(trgt_hip_ctx* c, const uint64_t* tight_off_host, int64_t n_jobs, int so, hipStream_t up, void** d_tabs) {
-  int rc;
-  if ((rc = dev_get(c, S_HMM_MOTIFS + so, (size_t)n_jobs * 16 + 16, d_tabs))) return rc;
-  uint64_t* d_toff = (uint64_t*)*d_tabs + (n_jobs + 1);
-  return h2d_small(c, d_toff, tight_off_host, (size_t)n_jobs * 8, up, S_HMM_MOTIFS + so);
-}
-static int pack_behind_kernels(trgt_hip_ctx* c, trgt::HmmPending* P, void* d_tabs, int64_t n_jobs, void* d_bp, uint64_t bp_bytes,
-                               const int32_t* d_spans, const uint32_t* d_nsp, int so) {
-  uint64_t* d_poff = (uint64_t*)d_tabs; uint64_t* d_toff = d_poff + (n_jobs + 1);
-  hipLaunchKernelGGL(hmm_span_prefix_kernel, dim3(1), dim3(1024), 0, c->stream, d_nsp, d_poff, (uint64_t)n_jobs);
-  hipLaunchKernelGGL(hmm_pack_spans_kernel, dim3((unsigned)((n_jobs + 255) / 256)), dim3(256), 0, c->stream, d_spans, (const uint64_t*)d_toff, d_nsp,
-                     (const uint64_t*)d_poff, (int32_t*)d_bp, (uint64_t)n_jobs);
-  TRGT_HIP_TRY(c, hipGetLastError());
-  P->d_packed = (const int32_t*)d_bp; P->d_poff = d_poff; P->packed_cap_bytes = bp_bytes;
-  return TRGT_OK;
-}
-
-int trgt::hmm_batch_impl(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets, const uint8_t* motif_blob, const uint32_t* motif_off,
-                         const uint32_t* set_motif_begin, int64_t n_jobs, const uint32_t* job_set,
-                         const uint8_t* seq_blob, const uint64_t* seq_off, const uint32_t* seq_len, uint16_t* path,
-                         const uint64_t* path_off, uint32_t* path_len, int32_t* spans3, const uint64_t* span_off,
-                         uint32_t* n_spans, uint32_t* motif_counts, const uint64_t* count_off, double* purity,
-                         int32_t* edit_dist, int32_t* max_dist) {
-  HmmPending* pend = nullptr;
-  int rc = hmm_enqueue(c, premade, n_sets, motif_blob, motif_off, set_motif_begin, n_jobs, job_set, seq_blob, seq_off, seq_len, path, path_off,
-                       path_len, spans3, span_off, n_spans, motif_counts, count_off, purity, edit_dist, max_dist, &pend);
-  if (rc) return rc;
-  return hmm_collect(c, pend);
-}
-
-int trgt::hmm_enqueue(trgt_hip_ctx* c, const HmmModels* premade, int32_t n_sets, const uint8_t* motif_blob, const uint32_t* motif_off,
-                      const uint32_t* set_motif_begin, int64_t n_jobs, const uint32_t* job_set,
-                      const uint8_t* seq_blob, const uint64_t* seq_off, const uint32_t* seq_len, uint16_t* path,
-                      const uint64_t* path_off, uint32_t* path_len, int32_t* spans3, const uint64_t* span_off,
-                      uint32_t* n_spans, uint32_t* motif_counts, const uint64_t* count_off, double* purity,
-                      int32_t* edit_dist, int32_t* max_dist, HmmPending** out_pending, int buffer_set) {
-  *out_pending = nullptr;
-  const int so = buffer_set ? (int)S_HMM_B_BASE - (int)S_HMM_SEQ : 0;  // slot offset of the buffer set
-  if (!c) return TRGT_ERR_INVALID;
-  if (n_sets < 0 || n_jobs < 0 || (n_jobs > 0 && (!motif_blob || !motif_off || !set_motif_begin || !job_set || !seq_off ||
-                                                    !seq_len || (spans3 && !span_off) || !n_spans || !motif_counts ||
-                                                    !count_off || !purity)))
-    return fail(c, TRGT_ERR_INVALID, "trgt_hmm_batch: null argument");
-  if (path && !path_off) return fail(c, TRGT_ERR_INVALID, "trgt_hmm_batch: path without path_off");
-  if (n_jobs == 0) return TRGT_OK;
-  TRGT_HIP_TRY(c, hipSetDevice(c->device));
-  std::unique_ptr<HmmPending> P(new HmmPending());
-  P->n_jobs = n_jobs; P->spans3 = spans3; P->span_off = span_off; P->set = buffer_set; P->stream = c->stream;
-  // ---- models (host libm ln tables): built here unless the caller prepared them ahead of time (trgt_locus_batch does,
-  //      concurrently with the flank-location stage)
-  HmmModels& local_models = P->local_models;
-  const HmmModels* mp = premade;
-  if (!mp) {
-    const int mrc = hmm_models_on_device(c, n_sets, motif_blob, motif_off, set_motif_begin, local_models, c->stream, nullptr);
-    if (mrc) return fail(c, mrc, "%s", local_models.err.empty() ? trgt_hip_last_error(c) : local_models.err.c_str());
-    mp = &local_models;
-  } else if (mp->rc) return fail(c, mp->rc, "%s", mp->err.c_str());
-  const std::vector<HmmSetDev>& sets = mp->sets;
-  const std::vector<uint8_t>& blob = mp->blob;
-  // ---- jobs, grouped by workgroup size (64 * ceil(S/64))
-  std::vector<HmmJobDev>& jobs = P->jobs;
-  jobs.resize((size_t)n_jobs);
-  uint64_t bp_total = 0, visit_total = 0, seq_total = 0, span_total = 0, count_total = 0, path_total = 0;
-  int64_t cells = 0;
-  auto set_class_of = [&](const HmmSetDev& sd_) { return hmm_set_class(sd_, HMM_BATCH_MAX_WAVES); };
-  uint64_t class_jobs[32] = {};
-  for (int64_t j = 0; j < n_jobs; ++j) {
-    if ((int32_t)job_set[j] >= n_sets) return fail(c, TRGT_ERR_INVALID, "trgt_hmm_batch: job %lld bad set", (long long)j);
-    class_jobs[std::min<uint32_t>(set_class_of(sets[job_set[j]]), 31u)] += 1;
-  }
-  for (int64_t j = 0; j < n_jobs; ++j) {
-    const HmmSetDev& sd = sets[job_set[j]];
-    HmmJobDev& jd = jobs[(size_t)j];
-    jd.set = job_set[j]; jd.seq_len = seq_len[j]; jd.job_index = (uint32_t)j;
-    jd.seq_off = seq_off[j]; jd.span_off = spans3 ? span_off[j] : 0; jd.count_off = count_off[j];
-    jd.path_off = path ? path_off[j] : 0;
-    jd.path_cap = (uint32_t)std::min<uint64_t>(trgt_hmm_path_capacity(seq_len[j], sd.max_mlen), 0xFFFFFFFFull);
-    const uint64_t spad = (sd.S + 15) & ~15u;
-    // Invariant (hmm_ppl.hpp): every job's rows start 16 bytes into its piece -- bytes [bp_off - 16, bp_off) take the stores of roles a lane of the
-    // position-per-lane fill does not have, and a wave's lanes without a job store to bytes 0..15 of the workspace through the fake
-    // bp_off = 16; no row of any job may ever start below 16 (tests/test_hmm_gpu.py compares both fills on long alleles)
-    jd.bp_off = bp_total + 16; bp_total += 16 + align_up(spad * ((uint64_t)seq_len[j] + 2), 16);
-    jd.visit_off = visit_total; visit_total += 3ull * ((uint64_t)seq_len[j] + 2);
-    { const uint64_t mw = c->knobs.hmm_no_long_tb || set_class_of(sd) == HMM_CLASS_BIG ? 0 : hmm_map_words(sd.S, seq_len[j], hmm_long_min(class_jobs[std::min<uint32_t>(set_class_of(sd), 31u)])); jd.map_off = mw ? visit_total + 4 : 0; visit_total += mw ? mw + 4 : 0; }
-    seq_total = std::max<uint64_t>(seq_total, seq_off[j] + seq_len[j]);
-    if (spans3) span_total = std::max<uint64_t>(span_total, span_off[j] + seq_len[j] + 1);
-    count_total = std::max<uint64_t>(count_total, count_off[j] + (sd.n_blocks - 1));
-    P->cnt_off.push_back(count_off[j]); P->cnt_n.push_back(sd.n_blocks - 1);
-    if (path) path_total = std::max<uint64_t>(path_total, path_off[j] + jd.path_cap);
-    cells += (int64_t)sd.S * ((int64_t)seq_len[j] + 2);
-  }
-  if (bp_total > c->ws_limit) return fail(c, TRGT_ERR_NOMEM, "trgt_hmm_batch: back-pointer workspace %llu B exceeds limit", (unsigned long long)bp_total);
-  // class 0: at most 32 states (two alleles per wave); else the number of waves per allele
-  auto job_class = [&](const HmmJobDev& j) { return hmm_set_class(sets[j.set], HMM_BATCH_MAX_WAVES); };
-  {  // (usually one class: skip the sort then)
-    bool mixed = false;
-    const uint32_t c0 = job_class(jobs[0]);
-    for (const auto& jd : jobs) if (job_class(jd) != c0) { mixed = true; break; }
-    if (mixed) std::stable_sort(jobs.begin(), jobs.end(), [&](const HmmJobDev& a, const HmmJobDev& b) { return job_class(a) < job_class(b); });
-    // Inside a class the longest alleles go first: workgroups start in list order, and a launch ends with its last allele -- a 10-kb
-    // allele started behind a thousand short ones is pure tail.  (Classes of many alleles of similar length -- the single STR motif
-    // of a whole-genome catalog -- are left alone: sorting twenty thousand jobs costs more than it saves.)
-    size_t b0 = 0;
-    while (b0 < jobs.size()) {
-      size_t b1 = b0; uint32_t mx = 0; uint64_t sum = 0;
-      const uint32_t jc = job_class(jobs[b0]);
-      while (b1 < jobs.size() && job_class(jobs[b1]) == jc) { mx = std::max(mx, jobs[b1].seq_len); sum += jobs[b1].seq_len; ++b1; }
-      const size_t n = b1 - b0;
-      if (n > 1 && (n <= 4096 || (uint64_t)mx * n > 4 * sum))
-        std::stable_sort(jobs.begin() + (ptrdiff_t)b0, jobs.begin() + (ptrdiff_t)b1, [](const HmmJobDev& a, const HmmJobDev& b) { return a.seq_len > b.seq_len; });
-      b0 = b1;
-    }
-  }
-  // ---- device buffers
-  const uint8_t* d_seq = nullptr;
-  int rc;
-  if (is_device_ptr(seq_blob)) d_seq = seq_blob;
-  else {
-    // host sequences: upload them packed (the caller's blob is usually sparse: one max-length slot per allele)
-    uint64_t tight = 0;
-    for (int64_t j = 0; j < n_jobs; ++j) tight += seq_len[j];
-    void *h_tight = nullptr, *d_tight = nullptr;
-    if ((rc = pin_get(c, buffer_set ? P_HMM_SEQ_B : P_HMM_SEQ, (size_t)tight + 16, &h_tight)) || (rc = dev_get(c, S_HMM_SEQ + so, (size_t)tight + 16, &d_tight))) return rc;
-    std::vector<uint64_t> toff((size_t)n_jobs);
-    uint64_t o = 0;
-    for (int64_t j = 0; j < n_jobs; ++j) { toff[(size_t)j] = o; std::memcpy((uint8_t*)h_tight + o, seq_blob + seq_off[j], seq_len[j]); o += seq_len[j]; }
-    for (auto& jd : jobs) jd.seq_off = toff[jd.job_index];
-    if ((rc = h2d_small(c, d_tight, h_tight, (size_t)tight, c->stream, -1))) return rc;
-    d_seq = (const uint8_t*)d_tight;
-  }
-  void *d_sets = nullptr, *d_model = nullptr, *d_jobs = nullptr, *d_bp = nullptr, *d_visits = nullptr;
-  if (mp->d_sets && mp->d_blob) { d_sets = const_cast<void*>(mp->d_sets); d_model = const_cast<void*>(mp->d_blob); }
-  else {
-    if ((rc = dev_get(c, S_HMM_DESC, sets.size() * sizeof(HmmSetDev), &d_sets))) return rc;
-    if ((rc = dev_get(c, S_HMM_MODEL, blob.size(), &d_model))) return rc;
-    TRGT_HIP_TRY(c, hipMemcpyAsync(d_sets, sets.data(), sets.size() * sizeof(HmmSetDev), hipMemcpyHostToDevice, c->stream));
-    TRGT_HIP_TRY(c, hipMemcpyAsync(d_model, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
-  }
-  if ((rc = dev_get(c, S_HMM_JOBS + so, jobs.size() * sizeof(HmmJobDev), &d_jobs))) return rc;
-  if ((rc = dev_get(c, S_HMM_BP + so, (size_t)bp_total, &d_bp))) return rc;
-  if ((rc = dev_get(c, S_HMM_VISITS + so, (size_t)visit_total * 4, &d_visits))) return rc;
-  auto &o_path = P->o_path; auto &o_plen = P->o_plen, &o_nsp = P->o_nsp, &o_cnt = P->o_cnt; auto &o_spans = P->o_spans, &o_edit = P->o_edit, &o_maxd = P->o_maxd; auto& o_pur = P->o_pur;
-  // Spans: when the caller's buffer is host memory the kernel writes a tight per-job layout on the device and only the
-  // spans actually produced are copied back (packed); a device buffer is written in the caller's layout directly.
-  // spans3 == NULL: the caller only wants purity / counts (filter_impure_trs); the spans stay in the tight device layout
-  const bool discard_spans = spans3 == nullptr;
-  const bool spans_on_host = discard_spans || !is_device_ptr(spans3);
-  P->spans_on_host = spans_on_host && !discard_spans;
-  std::vector<uint64_t>& tight_off = P->tight_off;
-  uint64_t tight_total = 0;
-  if (spans_on_host) {
-    tight_off.resize((size_t)n_jobs);
-    for (int64_t j = 0; j < n_jobs; ++j) { tight_off[(size_t)j] = tight_total; tight_total += (uint64_t)seq_len[j] + 1; }
-    for (auto& jd : jobs) jd.span_off = tight_off[jd.job_index];
-  }
-  {  // the job list goes up once, from pinned memory (a pageable source makes the "async" copy a blocking staged one)
-    void* h_jobs = nullptr;
-    if ((rc = pin_get(c, buffer_set ? P_HMM_JOBS_B : P_HMM_JOBS, jobs.size() * sizeof(HmmJobDev), &h_jobs))) return rc;
-    std::memcpy(h_jobs, jobs.data(), jobs.size() * sizeof(HmmJobDev));
-    if ((rc = h2d_small(c, d_jobs, h_jobs, jobs.size() * sizeof(HmmJobDev), c->stream, -1))) return rc;
-  }
-  void* d_pack_tabs = nullptr;
-  if (P->spans_on_host && (rc = pack_tables_upload(c, tight_off.data(), n_jobs, so, c->stream, &d_pack_tabs))) return rc;
-  if ((rc = o_path.init(c, S_HMM_PATH + so, path, (size_t)path_total))) return rc;
-  if ((rc = o_plen.init(c, S_HMM_PLEN + so, path_len, (size_t)n_jobs))) return rc;
-  if (spans_on_host) {
-    void* d = nullptr;
-    if ((rc = dev_get(c, S_HMM_SPANS + so, (size_t)tight_total * 12, &d))) return rc;
-    o_spans.user = spans3; o_spans.dev = (int32_t*)d; o_spans.count = 0; o_spans.staged = false;  // copied back packed, below
-  } else if ((rc = o_spans.init(c, S_HMM_SPANS + so, spans3, (size_t)span_total * 3))) return rc;
-  if ((rc = o_nsp.init(c, S_HMM_NSP + so, n_spans, (size_t)n_jobs))) return rc;
-  if ((rc = o_cnt.init(c, S_HMM_CNT + so, motif_counts, (size_t)count_total))) return rc;
-  if (o_cnt.staged) {  // host array shared with other batches: only the ranges of this batch's jobs may be written back (hmm_collect)
-    P->cnt_user = motif_counts; P->cnt_total = count_total; o_cnt.staged = false;
-  }
-  if ((rc = o_pur.init(c, S_HMM_PUR + so, purity, (size_t)n_jobs))) return rc;
-  if ((rc = o_edit.init(c, S_HMM_EDIT + so, edit_dist, (size_t)n_jobs))) return rc;
-  if ((rc = o_maxd.init(c, S_HMM_MAXD + so, max_dist, (size_t)n_jobs))) return rc;
-  // ---- one launch per workgroup-size class; the first on the batch's stream, the others on side streams forked off it, so that
-  //      the classes run next to each other (a class is bounded by its longest allele: one behind the other they add up their tails)
-  // the fork event sits behind the uploads and IN FRONT of the first launch: recorded behind it (as it was until the cfg3 trace showed
-  // it), every other class waited for the first class to finish -- 17.6 + 15.2 ms instead of 17.6 for the 10-kb alleles of cfg3
-  if ((rc = hmm_fork_record(c, buffer_set))) return rc;
-  HmmClassLaunch cl{};
-  cl.buffer_set = buffer_set; cl.n_listed = jobs.size();
-  cl.b = HmmLaunchBufs{(const HmmSetDev*)d_sets, (const uint8_t*)d_model, d_seq, (uint8_t*)d_bp, (uint32_t*)d_visits,
-                       o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev};
-  unsigned side_used = 0;
-  cl.side_used = &side_used;
-  for (size_t i = 0, e; i < jobs.size(); i = e, ++cl.ordinal) {
-    cl.cls = job_class(jobs[i]);
-    uint32_t maxq = 0;
-    cl.maxS = cl.maxnb = 0; cl.ppl_mask = 0;
-    for (e = i; e < jobs.size() && job_class(jobs[e]) == cl.cls; ++e) {
-      const HmmSetDev& sd = sets[jobs[e].set];
-      cl.maxS = std::max(cl.maxS, sd.S); cl.maxnb = std::max(cl.maxnb, sd.n_blocks); maxq = std::max(maxq, jobs[e].seq_len);
-      cl.ppl_mask |= hmm_ppl_bit(sd);
-    }
-    if (c->knobs.hmm_no_ppl) cl.ppl_mask = 0;
-    cl.jobs = (const HmmJobDev*)d_jobs + i; cl.nj = (uint32_t)(e - i); cl.first_job = i; cl.max_len = maxq;
-    cl.cells = i == 0 ? cells : 0;
-    if ((rc = hmm_launch_class(c, cl))) return rc;
-  }
-  if ((rc = hmm_join_classes(c, side_used))) return rc;
-  if (P->spans_on_host && (rc = pack_behind_kernels(c, P.get(), d_pack_tabs, n_jobs, d_bp, bp_total, o_spans.dev, o_nsp.dev, so))) return rc;
-  *out_pending = P.release();
-  return TRGT_OK;
-}
-
-
-// ---- stage C behind a device-side genotyper: the kernels are enqueued before the host knows which alleles exist (see
-//      hmm_resolve_kernel); hmm_slots_resolved tells the pending batch afterwards, hmm_collect is the same as for a host-built list.
-int trgt::hmm_enqueue_slots(trgt_hip_ctx* c, const HmmModels* mp, const HmmSlots& in, int32_t* spans3, const uint64_t* span_off,
-                            uint32_t* n_spans, uint32_t* motif_counts, const uint64_t* count_off, double* purity,
-                            HmmPending** out_pending, int buffer_set) {
-  *out_pending = nullptr;
-  const int so = buffer_set ? (int)S_HMM_B_BASE - (int)S_HMM_SEQ : 0;
-  if (!c) return TRGT_ERR_INVALID;
-  if (!mp || mp->rc) return fail(c, mp ? mp->rc : TRGT_ERR_INVALID, "%s", mp ? mp->err.c_str() : "no models");
-  const int64_t nl = in.n_loci, n_slots = 2 * nl;
-  if (nl <= 0) return TRGT_OK;
-  if (!mp->d_sets || !mp->d_blob) return fail(c, TRGT_ERR_INVALID, "hmm_enqueue_slots: the models must be in device memory");
-  if (!is_device_ptr(in.seq_blob_dev) || (spans3 && is_device_ptr(spans3))) return fail(c, TRGT_ERR_INVALID, "hmm_enqueue_slots: device alleles, host results");
-  TRGT_HIP_TRY(c, hipSetDevice(c->device));
-  const std::vector<HmmSetDev>& sets = mp->sets;
-  std::unique_ptr<HmmPending> P(new HmmPending());
-  P->n_jobs = n_slots; P->spans3 = spans3; P->span_off = span_off; P->set = buffer_set; P->stream = c->stream;
-  constexpr int NC = HMM_SLOT_CLASSES, BIG = HMM_SLOT_CLASSES - 1;  // (the classes of hmm_viterbi_kernel keep their numbers and launch shapes)
-  auto set_class = [&](const HmmSetDev& sd) { const uint32_t k = hmm_set_class(sd, HMM_SLOT_MAX_WAVES); return k == HMM_CLASS_BIG ? (uint32_t)BIG : k; };
-  // candidates by class (a counting sort: loci keep their order inside a class)
-  uint32_t class_n[NC] = {}, class_begin[NC + 1];
-  for (int64_t l = 0; l < nl; ++l) {
-    if (in.host_skip && in.host_skip[l]) continue;
-    class_n[set_class(sets[(size_t)l])] += 2;
-  }
-  class_begin[0] = 0;
-  for (int k = 0; k < NC; ++k) class_begin[k + 1] = class_begin[k] + class_n[k];
-  const uint32_t n_cand = class_begin[NC];
-  P->slot_nm.assign((size_t)n_slots, 0); P->slot_cnt_off.assign(count_off, count_off + n_slots);
-  P->tight_off.assign(span_off, span_off + n_slots);
-  P->spans_on_host = spans3 != nullptr;
-  uint64_t count_total = 0, span_total = 0;
-  for (int64_t sl = 0; sl < n_slots; ++sl) {
-    const HmmSetDev& sd = sets[(size_t)(sl >> 1)];
-    P->slot_nm[(size_t)sl] = sd.n_blocks - 1;
-    count_total = std::max<uint64_t>(count_total, count_off[sl] + (sd.n_blocks - 1));
-    span_total = std::max<uint64_t>(span_total, span_off[sl] + in.cap[sl >> 1] + 1);
-  }
-  tl_mark(c, "hmm slots: counted");
-  if (n_cand == 0) { P->n_jobs = 0; return TRGT_OK; }
-  void* h_cand = nullptr;
-  int rc;
-  if ((rc = pin_get(c, buffer_set ? P_HMM_JOBS_B : P_HMM_JOBS, (size_t)n_cand * sizeof(HmmJobDev), &h_cand))) return rc;
-  HmmJobDev* cand = (HmmJobDev*)h_cand;
-  uint64_t bp_total = 0, visit_total = 0;
-  {
-    uint32_t at[NC];
-    for (int k = 0; k < NC; ++k) at[k] = class_begin[k];
-    for (int64_t l = 0; l < nl; ++l) {
-      if (in.host_skip && in.host_skip[l]) continue;
-      const HmmSetDev& sd = sets[(size_t)l];
-      const uint32_t k = set_class(sd);
-      const uint64_t spad = (sd.S + 15) & ~15u;
-      for (int a = 0; a < 2; ++a) {
-        HmmJobDev& jd = cand[at[k]++];
-        const int64_t sl = 2 * l + a;
-        jd.set = (uint32_t)l; jd.seq_len = 0; jd.job_index = (uint32_t)sl; jd.path_cap = 0;
-        jd.seq_off = in.seq_off[sl]; jd.path_off = 0; jd.span_off = span_off[sl]; jd.count_off = count_off[sl];
-        jd.bp_off = bp_total + 16; bp_total += 16 + align_up(spad * ((uint64_t)in.cap[l] + 2), 16);  // room for the longest allele the locus can have (+ the dump slot of hmm_fill_ppl_kernel)
-        jd.visit_off = visit_total; visit_total += 3ull * ((uint64_t)in.cap[l] + 2);
-        { const uint64_t mw = c->knobs.hmm_no_long_tb || k == (uint32_t)BIG ? 0 : hmm_map_words(sd.S, in.cap[l], hmm_long_min(class_n[k])); jd.map_off = mw ? visit_total + 4 : 0; visit_total += mw ? mw + 4 : 0; }
-      }
-    }
-  }
-  tl_mark(c, "hmm slots: candidates");
-  if (bp_total > c->ws_limit) return fail(c, TRGT_ERR_NOMEM, "trgt_hmm_batch: back-pointer workspace %llu B exceeds limit", (unsigned long long)bp_total);
-  void *d_jobs = nullptr, *d_bp = nullptr, *d_visits = nullptr;
-  const size_t jobs_bytes = (size_t)n_cand * sizeof(HmmJobDev);
-  // (S_HMM_JOBS: candidates | job lists | counts per class (16 words) | 2 x HMM_RESOLVE_KEYS resolve counters | verdicts)
-  constexpr size_t count_bytes = 64 + 8 * (size_t)HMM_RESOLVE_KEYS;
-  if ((rc = dev_get(c, S_HMM_JOBS + so, 2 * jobs_bytes + count_bytes + 4 * (size_t)n_cand + (size_t)n_cand + 16, &d_jobs)) || (rc = dev_get(c, S_HMM_BP + so, (size_t)bp_total, &d_bp)) ||
-      (rc = dev_get(c, S_HMM_VISITS + so, (size_t)visit_total * 4, &d_visits)))
-    return rc;
-  HmmJobDev* const d_cand = (HmmJobDev*)d_jobs;
-  void* d_pack_tabs = nullptr;
-  HmmJobDev* const d_list = d_cand + n_cand;
-  // counts | histogram | places taken (cleared): a piece of the call's zero arena when there is one
-  void* const z_count = zero_take(c, count_bytes);
-  uint32_t* const d_count = z_count ? (uint32_t*)z_count : (uint32_t*)((uint8_t*)d_jobs + 2 * jobs_bytes);
-  uint32_t* const d_verdict = (uint32_t*)((uint8_t*)d_jobs + 2 * jobs_bytes + count_bytes);
-  {  // on the copy stream: a copy queued on the batch's stream would sit in the copy engine's queue until the genotyper in front of it
-     // has run, and hold up every copy issued after it (the next batch's reads)
-    hipStream_t us = c->stream_copy ? c->stream_copy : c->stream;
-    if ((rc = h2d_small(c, d_cand, h_cand, jobs_bytes, us, -1))) return rc;
-    if (P->spans_on_host && (rc = pack_tables_upload(c, P->tight_off.data(), n_slots, so, us, &d_pack_tabs))) return rc;
-    if (us != c->stream) {
-      if (!c->ev_upload) TRGT_HIP_TRY(c, hipEventCreateWithFlags(&c->ev_upload, hipEventDisableTiming));
-      TRGT_HIP_TRY(c, hipEventRecord(c->ev_upload, us));
-      TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_upload, 0));
-    }
-  }
-  auto &o_path = P->o_path; auto &o_plen = P->o_plen, &o_nsp = P->o_nsp, &o_cnt = P->o_cnt; auto &o_spans = P->o_spans, &o_edit = P->o_edit, &o_maxd = P->o_maxd; auto& o_pur = P->o_pur;
-  if ((rc = o_path.init(c, S_HMM_PATH + so, (uint16_t*)nullptr, 0)) || (rc = o_plen.init(c, S_HMM_PLEN + so, (uint32_t*)nullptr, 0))) return rc;
-  {
-    void* d = nullptr;
-    if ((rc = dev_get(c, S_HMM_SPANS + so, (size_t)span_total * 12 + 16, &d))) return rc;
-    o_spans.user = spans3; o_spans.dev = (int32_t*)d; o_spans.count = 0; o_spans.staged = false;  // copied back packed (hmm_collect)
-  }
-  if ((rc = o_nsp.init(c, S_HMM_NSP + so, n_spans, (size_t)n_slots)) || (rc = o_cnt.init(c, S_HMM_CNT + so, motif_counts, (size_t)count_total)) ||
-      (rc = o_pur.init(c, S_HMM_PUR + so, purity, (size_t)n_slots)) || (rc = o_edit.init(c, S_HMM_EDIT + so, (int32_t*)nullptr, 0)) ||
-      (rc = o_maxd.init(c, S_HMM_MAXD + so, (int32_t*)nullptr, 0)))
-    return rc;
-  if (o_cnt.staged) { P->cnt_user = motif_counts; P->cnt_total = count_total; o_cnt.staged = false; }
-  uint32_t max_cap = 1, len_shift = 0;
-  for (int64_t l = 0; l < nl; ++l) max_cap = std::max(max_cap, in.cap[l]);
-  while ((max_cap >> len_shift) >= 64) ++len_shift;
-  // slots that are no candidates at all (loci left to the host path) hold "no allele" too
-  if (void* z = o_nsp.staged && (size_t)n_slots * 4 <= (512u << 10) ? zero_take(c, (size_t)n_slots * 4) : nullptr) o_nsp.dev = (uint32_t*)z;
-  else TRGT_HIP_TRY(c, hipMemsetAsync(o_nsp.dev, 0, (size_t)n_slots * 4, c->stream));
-  const uint8_t* d_dup = nullptr;
-  if (c->knobs.hmm_resolve_one_wg) {
-    for (int k = 0; k < NC; ++k) {
-      if (!class_n[k]) continue;
-      HmmResolveArgs ra{d_cand + class_begin[k], class_n[k], in.d_skip, in.d_n_alleles, in.d_allele_len, d_list + class_begin[k], d_count + k, o_nsp.dev, o_pur.dev, len_shift};
-      hipLaunchKernelGGL(hmm_resolve_kernel, dim3(1), dim3(1024), 0, c->stream, ra);
-    }
-  } else {
-    HmmResolveAllArgs ra;
-    ra.cand = d_cand; ra.n = (uint32_t)n_cand;
-    for (int k = 0; k <= NC; ++k) ra.class_begin[k] = (uint32_t)class_begin[k];
-    ra.skip_locus = in.d_skip; ra.n_alleles = in.d_n_alleles; ra.allele_len = in.d_allele_len;
-    ra.jobs = d_list; ra.n_jobs = d_count; ra.n_spans = o_nsp.dev; ra.purity = o_pur.dev;
-    ra.hist = d_count + 16; ra.taken = ra.hist + HMM_RESOLVE_KEYS; ra.verdict = d_verdict; ra.len_shift = len_shift;
-    ra.seq_blob = in.seq_blob_dev; ra.dup = c->knobs.hmm_no_dedupe ? nullptr : reinterpret_cast<uint8_t*>(ra.verdict + n_cand);
-    d_dup = ra.dup;
-    if (!z_count) TRGT_HIP_TRY(c, hipMemsetAsync(d_count, 0, count_bytes, c->stream));
-    const dim3 rg((unsigned)((n_cand + 255) / 256));
-    hipLaunchKernelGGL(hmm_resolve_count_kernel, rg, dim3(256), 0, c->stream, ra);
-    hipLaunchKernelGGL(hmm_resolve_scatter_kernel, rg, dim3(256), 0, c->stream, ra);
-  }
-  TRGT_HIP_TRY(c, hipGetLastError());
-  tl_mark(c, "hmm slots: resolve launched");
-  // ---- the position-per-lane fills of ALL classes: one launch per group width over the whole list (a segment per class), the widths next
-  //      to each other (hmm_launch_ppl), the classes' trace-backs behind them.  Per class -- up to four launches on as many streams for
-  //      each of up to four classes -- the stage had more streams than HIP has hardware queues, and what shares a queue runs one after
-  //      the other: in a cfg4 trace the second 64-lane fill began 0.7 ms after the stage did (1.47 ms for the stage; 0.57 + 0.3 are its
-  //      longest fill and trace-back).  TRGT_HMM_PPL_PER_CLASS=1: as before.
-  unsigned class_ppl_mask[HMM_PPL_CLASSES] = {}, all_ppl_mask = 0;
-  if (!c->knobs.hmm_no_ppl)
-    for (uint32_t k = 0; k < (uint32_t)HMM_PPL_CLASSES; ++k) {
-      for (uint32_t i = class_begin[k]; i < class_begin[k + 1]; i += 2) class_ppl_mask[k] |= hmm_ppl_bit(sets[cand[i].set]);
-      all_ppl_mask |= class_ppl_mask[k];
-    }
-  const bool ppl_merged = all_ppl_mask != 0 && !c->knobs.hmm_ppl_per_class;
-  if (ppl_merged) {
-    ppl::PplSegs segs{};
-    static_assert(sizeof(segs.begin) / sizeof(segs.begin[0]) == HMM_PPL_CLASSES + 1, "a segment per class that can have such a fill");
-    for (int k = 0; k <= HMM_PPL_CLASSES; ++k) segs.begin[k] = (uint32_t)class_begin[k];  // (the large models behind them have no such fill)
-    segs.n_seg = HMM_PPL_CLASSES; segs.counts = (const uint32_t*)d_count;
-    // a width's launch spans the classes that hold sets of that width, not the whole list: a workgroup that finds no job of its width
-    // ends at once, but 17 000 of them in front of 3 000 that work made the 64-lane launch of cfg4 0.73 ms instead of 0.54
-    for (int w = 0; w < 4; ++w) {
-      segs.first_slot[w] = segs.end_slot[w] = 0;
-      bool any = false;
-      for (int k = 0; k < HMM_PPL_CLASSES; ++k)
-        if (class_ppl_mask[k] & (1u << w)) { if (!any) segs.first_slot[w] = segs.begin[k]; segs.end_slot[w] = segs.begin[k + 1]; any = true; }
-    }
-    KTimer tf(c, TRGT_K_HMM, c->stream);
-    if ((rc = hmm_launch_ppl(c, buffer_set ? 1 : 0, 0, c->stream, all_ppl_mask, (const HmmJobDev*)d_list, (const HmmSetDev*)mp->d_sets, (const uint8_t*)mp->d_blob, in.seq_blob_dev, (uint8_t*)d_bp, segs))) return rc;
-    TRGT_HIP_TRY(c, hipGetLastError());
-    tf.stop(0);
-  }
-  if ((rc = hmm_fork_record(c, buffer_set))) return rc;  // (behind the resolve kernel and the merged fills, in front of the first class launch)
-  HmmClassLaunch cl{};
-  cl.buffer_set = buffer_set; cl.n_listed = n_cand; cl.ppl_launched = ppl_merged;
-  cl.b = HmmLaunchBufs{(const HmmSetDev*)mp->d_sets, (const uint8_t*)mp->d_blob, in.seq_blob_dev, (uint8_t*)d_bp, (uint32_t*)d_visits,
-                       o_path.dev, o_plen.dev, o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev, o_edit.dev, o_maxd.dev};
-  unsigned side_used = 0;
-  cl.side_used = &side_used;
-  for (uint32_t k = 0; k < (uint32_t)NC; ++k) {
-    if (!class_n[k]) continue;
-    uint32_t max_cap_cls = 0;
-    cl.maxS = cl.maxnb = 0;
-    for (uint32_t i = class_begin[k]; i < class_begin[k + 1]; i += 2) {
-      const HmmSetDev& sd = sets[cand[i].set];
-      cl.maxS = std::max(cl.maxS, sd.S); cl.maxnb = std::max(cl.maxnb, sd.n_blocks); max_cap_cls = std::max(max_cap_cls, in.cap[cand[i].set]);
-    }
-    cl.cls = k == (uint32_t)BIG ? HMM_CLASS_BIG : k;
-    cl.ppl_mask = k < (uint32_t)HMM_PPL_CLASSES ? class_ppl_mask[k] : 0u;
-    cl.jobs = (const HmmJobDev*)d_list + class_begin[k]; cl.nj = class_n[k]; cl.n_jobs_dev = d_count + k; cl.first_job = class_begin[k]; cl.max_len = max_cap_cls;
-    if ((rc = hmm_launch_class(c, cl))) return rc;  // (cells: counted when the genotyper's results are known, hmm_slots_resolved)
-    ++cl.ordinal;
-  }
-  if ((rc = hmm_join_classes(c, side_used))) return rc;
-  if (d_dup) {  // homozygous loci: the second allele's results are the first one's
-    hipLaunchKernelGGL(hmm_dup_copy_kernel, dim3((unsigned)((n_cand + 255) / 256)), dim3(256), 0, c->stream, (const HmmJobDev*)d_cand, (uint32_t)n_cand, d_dup, (const HmmSetDev*)mp->d_sets,
-                       o_spans.dev, o_nsp.dev, o_cnt.dev, o_pur.dev);
-    TRGT_HIP_TRY(c, hipGetLastError());
-  }
-  tl_mark(c, "hmm slots: classes launched");
-  if (P->spans_on_host && (rc = pack_behind_kernels(c, P.get(), d_pack_tabs, n_slots, d_bp, bp_total, o_spans.dev, o_nsp.dev, so))) return rc;
-  *out_pending = P.release();
-  return TRGT_OK;
-}
-
-int64_t trgt::hmm_slots_resolved(trgt_hip_ctx* c, HmmPending* P, const HmmModels* mp, const uint8_t* skip, const int32_t* n_alleles, const uint32_t* allele_len) {
-  if (!P) return 0;
-  int64_t jobs = 0, cells = 0;
-  P->cnt_off.clear(); P->cnt_n.clear();
-  for (int64_t sl = 0; sl < P->n_jobs; ++sl) {
-    const int64_t l = sl >> 1;
-    if (skip[l] || (int32_t)(sl & 1) >= n_alleles[l]) continue;
-    P->cnt_off.push_back(P->slot_cnt_off[(size_t)sl]); P->cnt_n.push_back(P->slot_nm[(size_t)sl]);
-    cells += (int64_t)mp->sets[(size_t)l].S * ((int64_t)allele_len[sl] + 2);
-    ++jobs;
-  }
-  if (c->timing) c->k_cells[TRGT_K_HMM] += cells;
-  return jobs;
-}
-
-int trgt::hmm_collect(trgt_hip_ctx* c, HmmPending* pend) {
-  if (!pend) return TRGT_OK;  // an empty batch
-  std::unique_ptr<HmmPending> P(pend);
-  struct StreamSwap { trgt_hip_ctx* c; hipStream_t saved; ~StreamSwap() { c->stream = saved; } } stream_swap{c, c->stream};
-  c->stream = P->stream;
-  const int64_t n_jobs = P->n_jobs;
-  const bool spans_on_host = P->spans_on_host;
-  std::vector<uint64_t>& tight_off = P->tight_off;
-  int32_t* spans3 = P->spans3; const uint64_t* span_off = P->span_off;
-  auto &o_path = P->o_path; auto &o_plen = P->o_plen, &o_nsp = P->o_nsp, &o_cnt = P->o_cnt; auto &o_spans = P->o_spans, &o_edit = P->o_edit, &o_maxd = P->o_maxd; auto& o_pur = P->o_pur;
-  int rc;
-  const bool tl_on = c->knobs.timeline;
-  const auto tl0 = std::chrono::steady_clock::now();
-  auto HTL = [&](const char* name, double mb) { if (tl_on) fprintf(stderr, "[tl]   hmm collect %-22s +%6.2f ms  (%.2f MB)\n", name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count(), mb); };
-  if (spans_on_host) {
-    // counts, total and the head of the packed spans in one round trip (the compaction ran behind the kernels: pack_behind_kernels)
-    std::vector<uint32_t> h_nsp((size_t)n_jobs);
-    uint64_t ptotal = 0;
-    const size_t first = (size_t)std::min<uint64_t>(HMM_PACKED_FIRST, P->packed_cap_bytes);
-    std::vector<int32_t> h_packed(first / 4 + 4);
-    { const int d2h_rc = trgt::d2h(c, h_nsp.data(), o_nsp.dev, (size_t)n_jobs * 4, c->stream); if (d2h_rc) return d2h_rc; }
-    { const int d2h_rc = trgt::d2h(c, &ptotal, P->d_poff + n_jobs, 8, c->stream); if (d2h_rc) return d2h_rc; }
-    { const int d2h_rc = trgt::d2h(c, h_packed.data(), P->d_packed, first, c->stream); if (d2h_rc) return d2h_rc; }
-    TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
-    HTL("counts + packed spans on host", (double)((size_t)n_jobs * 4 + first) / 1e6);
-    if (ptotal * 12 > P->packed_cap_bytes) return fail(c, TRGT_ERR_INVALID, "trgt_hmm_batch: %llu spans do not fit the packing workspace", (unsigned long long)ptotal);
-    if (ptotal * 12 > first) {  // the rest (many spans: long alleles of interrupted repeats)
-      h_packed.resize((size_t)ptotal * 3 + 4);
-      { const int d2h_rc = trgt::d2h(c, (uint8_t*)h_packed.data() + first, (const uint8_t*)P->d_packed + first, (size_t)ptotal * 12 - first, c->stream); if (d2h_rc) return d2h_rc; }
-      TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
-      HTL("rest of the packed spans", (double)(ptotal * 12 - first) / 1e6);
-    }
-    uint64_t at = 0;
-    for (int64_t j = 0; j < n_jobs; ++j) {
-      std::memcpy(spans3 + 3 * span_off[j], h_packed.data() + 3 * at, (size_t)h_nsp[(size_t)j] * 12);
-      at += h_nsp[(size_t)j];
-    }
-    (void)tight_off; (void)rc;
-  }
-  std::vector<uint32_t> h_cnt;
-  if (P->cnt_user && P->cnt_total) {
-    h_cnt.resize((size_t)P->cnt_total);
-    { const int d2h_rc = trgt::d2h(c, h_cnt.data(), o_cnt.dev, (size_t)P->cnt_total * 4, c->stream); if (d2h_rc) return d2h_rc; }
-  }
-  if ((rc = o_path.finish(c)) || (rc = o_plen.finish(c)) || (rc = o_spans.finish(c)) || (rc = o_nsp.finish(c)) ||
-      (rc = o_cnt.finish(c)) || (rc = o_pur.finish(c)) || (rc = o_edit.finish(c)) || (rc = o_maxd.finish(c)))
-    return rc;
-  HTL("copies enqueued", (double)((o_path.staged ? o_path.count * 2 : 0) + (o_plen.staged ? o_plen.count * 4 : 0) + (o_spans.staged ? o_spans.count * 4 : 0) + (o_nsp.staged ? o_nsp.count * 4 : 0) +
-                                  (o_cnt.staged ? o_cnt.count * 4 : 0) + (o_pur.staged ? o_pur.count * 8 : 0) + (o_edit.staged ? o_edit.count * 4 : 0) + (o_maxd.staged ? o_maxd.count * 4 : 0)) / 1e6);
-  TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
-  HTL("synced", 0.0);
-#ifdef TRGT_HMM_PROF
-  {
-    unsigned long long h[16], z[16] = {0};
-    TRGT_HIP_TRY(c, hipMemcpyFromSymbol(h, HIP_SYMBOL(g_hmm_prof), sizeof h));
-    TRGT_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(g_hmm_prof), z, sizeof h));
-    const double t = (double)(h[0] + h[1] + h[2] + h[3]) + 1e-9;
-    fprintf(stderr, "[hmm prof] jobs=%lld | setup %.1f%% fill %.1f%% traceback %.1f%% path+decode %.1f%% | kcycles/job %.1f\n", (long long)n_jobs,
-            100 * h[0] / t, 100 * h[1] / t, 100 * h[2] / t, 100 * h[3] / t, t / 1e3 / (double)n_jobs);
-    const double f = (double)(h[8] + h[9] + h[10] + h[11] + h[12] + h[13]) + 1e-9;
-    fprintf(stderr, "[hmm prof]   long trace-back (kcycles of thread 0 over all alleles): chunk maps %.0f, stringing %.0f, re-walk %.0f, path order + visits %.0f\n", h[4] / 1e3, h[5] / 1e3, h[6] / 1e3, h[7] / 1e3);
-    fprintf(stderr, "[hmm prof]   fill (%.0f kcycles on the profiled lanes): symbol %.1f%% emitting+sync %.1f%% chains+ends+sync %.1f%% run end+sync %.1f%% block starts+sync %.1f%% store %.1f%%\n",
-            f / 1e3, 100 * h[8] / f, 100 * h[9] / f, 100 * h[10] / f, 100 * h[11] / f, 100 * h[12] / f, 100 * h[13] / f);
-  }
-#endif
-  if (!h_cnt.empty())
-    for (size_t j = 0; j < P->cnt_off.size(); ++j)
-      std::memcpy(P->cnt_user + P->cnt_off[j], h_cnt.data() + P->cnt_off[j], (size_t)P->cnt_n[j] * 4);
-  return TRGT_OK;
 }
 
 // Developer / test entry: builds the models of the motif sets both ways -- on the device (what every other entry point uses) and with
@@ -2588,6 +1695,10 @@ extern "C" int trgt_hmm_batch(trgt_hip_ctx* c, int32_t n_sets, const uint8_t* mo
                               const uint64_t* path_off, uint32_t* path_len, int32_t* spans3, const uint64_t* span_off,
                               uint32_t* n_spans, uint32_t* motif_counts, const uint64_t* count_off, double* purity,
                               int32_t* edit_dist, int32_t* max_dist) {
-  return hmm_batch_impl(c, nullptr, n_sets, motif_blob, motif_off, set_motif_begin, n_jobs, job_set, seq_blob, seq_off, seq_len, path,
-                        path_off, path_len, spans3, span_off, n_spans, motif_counts, count_off, purity, edit_dist, max_dist);
+  HmmBatchIO io;
+  io.n_sets = n_sets; io.motif_blob = motif_blob; io.motif_off = motif_off; io.set_motif_begin = set_motif_begin;
+  io.n_jobs = n_jobs; io.job_set = job_set; io.seq_blob = seq_blob; io.seq_off = seq_off; io.seq_len = seq_len;
+  io.path = path; io.path_off = path_off; io.path_len = path_len; io.spans3 = spans3; io.span_off = span_off; io.n_spans = n_spans;
+  io.motif_counts = motif_counts; io.count_off = count_off; io.purity = purity; io.edit_dist = edit_dist; io.max_dist = max_dist;
+  return hmm_batch_impl(c, nullptr, io);
 }

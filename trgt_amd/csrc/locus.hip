@@ -748,6 +748,19 @@ struct LocusCall {
   cld::DeepArgs da, ds;  // (ds: the deep size list -- the same per-read lists, the loci of the two lists being different ones; its own counts)
   // ---- stage C.  The motif-HMM tables depend only on the catalog: built on the device, behind stage A's launches
   HmmModels models; HmmSlots hs;
+  // the arguments of the call's HMM batches: its motif sets and result arrays; a call site adds its job list and what it keeps apart
+  HmmBatchIO hmm_io(uint32_t* n_spans, double* purity) const {
+    HmmBatchIO io;
+    io.n_sets = (int32_t)nl; io.motif_blob = in->motif_blob; io.motif_off = in->motif_off; io.set_motif_begin = in->set_motif_begin;
+    io.spans3 = out->spans3; io.span_off = out->span_off; io.n_spans = n_spans; io.motif_counts = out->motif_counts; io.count_off = out->count_off; io.purity = purity;
+    return io;
+  }
+  // ... with a host-built job list; the site names where the list's spans and counts go (span_off, count_off), or takes the spans out
+  HmmBatchIO hmm_list_io(const std::vector<uint32_t>& set, const void* blob, const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, uint32_t* n_spans, double* purity) const {
+    HmmBatchIO io = hmm_io(n_spans, purity);
+    io.n_jobs = (int64_t)set.size(); io.job_set = set.data(); io.seq_blob = (const uint8_t*)blob; io.seq_off = off.data(); io.seq_len = len.data();
+    return io;
+  }
   hipStream_t upload_stream = nullptr;
   std::vector<uint8_t> slot_skip;
   std::vector<uint32_t> nsB; std::vector<double> puB;  // n_spans / purity of the second batch (merged into the outputs slot by slot)
@@ -1232,8 +1245,9 @@ int LocusCall::purity_chain() {
     if ((rc = dev_get(c, S_PUR_CNT, ((size_t)cnt_total + 1) * 4, &d_pcnt))) return rc;
     const int64_t tc0 = now_ns();
     // (device pointers for every result: nothing is copied back, the call returns when the kernels are through)
-    rc = hmm_batch_impl(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, n_pj, pj_set.data(), d_reads, pj_off.data(), pj_len.data(),
-                        nullptr, nullptr, nullptr, nullptr, nullptr, (uint32_t*)ps.d(po_nsp), (uint32_t*)d_pcnt, pj_cnt_off.data(), (double*)ps.d(po_pur), nullptr, nullptr);
+    HmmBatchIO io = hmm_list_io(pj_set, d_reads, pj_off, pj_len, (uint32_t*)ps.d(po_nsp), (double*)ps.d(po_pur));
+    io.spans3 = nullptr; io.span_off = nullptr; io.motif_counts = (uint32_t*)d_pcnt; io.count_off = pj_cnt_off.data();
+    rc = hmm_batch_impl(c, &models, io);
     if (rc) return rc;
     tC += now_ns() - tc0;
     stat_hmm_jobs += n_pj;
@@ -1315,7 +1329,7 @@ int LocusCall::size_genotyper() {
       TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream_hmm, c->ev_gt, 0)); TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream_hmm, c->ev_upload, 0)); c->stream = c->stream_hmm;
       hs.d_skip = (const uint8_t*)g.need;
       tc0 = now_ns();
-      rc = hmm_enqueue_slots(c, &models, hs, out->spans3, out->span_off, out->n_spans, out->motif_counts, out->count_off, out->purity, &hmm_pending);
+      rc = hmm_enqueue_slots(c, &models, hs, hmm_io(out->n_spans, out->purity), &hmm_pending);
     }
     if (rc) return rc;
     tC += now_ns() - tc0;
@@ -1377,7 +1391,7 @@ int LocusCall::repair_chain() {
     hs.d_skip = (const uint8_t*)slab.d(o_skipb);
     nsB.assign(2 * (size_t)nl, 0); puB.assign(2 * (size_t)nl, 0.0);
     const int64_t tc0 = now_ns();
-    if ((rc = hmm_enqueue_slots(c, &models, hs, out->spans3, out->span_off, nsB.data(), out->motif_counts, out->count_off, puB.data(), &hmm_pendingB, 1))) return rc;
+    if ((rc = hmm_enqueue_slots(c, &models, hs, hmm_io(nsB.data(), puB.data()), &hmm_pendingB, 1))) return rc;
     tC += now_ns() - tc0;
     std::swap(c->stream, c->stream2);
     TRGT_HIP_TRY(c, hipStreamWaitEvent(c->stream, c->ev_rp, 0));
@@ -1565,7 +1579,7 @@ int LocusCall::enqueue_results() {
   if (use_slots && !hmm_pending && !hmm_pendingB) {  // one HMM batch behind the genotyper and the repair (need_host is final by then)
     hs.d_skip = (const uint8_t*)g.need;
     const int64_t tc0 = now_ns();
-    if ((rc = hmm_enqueue_slots(c, &models, hs, out->spans3, out->span_off, out->n_spans, out->motif_counts, out->count_off, out->purity, &hmm_pending))) return rc;
+    if ((rc = hmm_enqueue_slots(c, &models, hs, hmm_io(out->n_spans, out->purity), &hmm_pending))) return rc;
     tC += now_ns() - tc0;
     tl("hmm1 enqueued (device-resolved job list)");
   }
@@ -1800,9 +1814,9 @@ int LocusCall::gather_host_segments() {
       if ((rc = collect_ab()) || (rc = collect_hmm1())) return rc;
       pj_nsp.resize(pj_set.size()); pj_pur.resize(pj_set.size());
       std::vector<uint32_t> pj_counts((size_t)cnt_total + 1);
-      rc = hmm_batch_impl(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, (int64_t)pj_set.size(), pj_set.data(),
-                          reads_on_device ? d_reads : in->read_blob, pj_off.data(), pj_len.data(), nullptr, nullptr, nullptr, nullptr, nullptr,
-                          pj_nsp.data(), pj_counts.data(), pj_cnt_off.data(), pj_pur.data(), nullptr, nullptr);
+      HmmBatchIO io = hmm_list_io(pj_set, reads_on_device ? d_reads : in->read_blob, pj_off, pj_len, pj_nsp.data(), pj_pur.data());
+      io.spans3 = nullptr; io.span_off = nullptr; io.motif_counts = pj_counts.data(); io.count_off = pj_cnt_off.data();
+      rc = hmm_batch_impl(c, &models, io);
       if (rc) return rc;
       stat_hmm_jobs += (int64_t)pj_set.size();
     }
@@ -1883,9 +1897,9 @@ int LocusCall::hmm1_enqueue() {
     if (!job_set.empty()) {
       nsp.resize(job_set.size()); pur.resize(job_set.size());
       const int64_t tc0 = now_ns();
-      rc = hmm_enqueue(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, (int64_t)job_set.size(), job_set.data(),
-                       (const uint8_t*)g.blob, seq_off.data(), seq_len.data(), nullptr, nullptr, nullptr, out->spans3, span_off.data(), nsp.data(),
-                       out->motif_counts, count_off.data(), pur.data(), nullptr, nullptr, &hmm_pending);
+      HmmBatchIO io = hmm_list_io(job_set, g.blob, seq_off, seq_len, nsp.data(), pur.data());
+      io.span_off = span_off.data(); io.count_off = count_off.data();
+      rc = hmm_enqueue(c, &models, io, &hmm_pending);
       if (rc) return rc;
       tC += now_ns() - tc0;
       tl("hmm1 enqueued");
@@ -2184,9 +2198,9 @@ int LocusCall::host_stage_c() {
     // (the two batches are independent; queued on the same streams the second one waited for the first -- config 3: 65 -> 5x ms per call)
     StreamGuard keep(c);
     if (hmm_pending) c->stream = c->stream2;
-    rc = hmm_enqueue(c, &models, (int32_t)nl, in->motif_blob, in->motif_off, in->set_motif_begin, (int64_t)js2.size(), js2.data(),
-                     out->allele_blob, so2.data(), sl2.data(), nullptr, nullptr, nullptr, out->spans3, spo2.data(), ns2.data(),
-                     out->motif_counts, co2.data(), pu2.data(), nullptr, nullptr, &hmm_pending2, hmm_pending ? 1 : 0);
+    HmmBatchIO io = hmm_list_io(js2, out->allele_blob, so2, sl2, ns2.data(), pu2.data());
+    io.span_off = spo2.data(); io.count_off = co2.data();
+    rc = hmm_enqueue(c, &models, io, &hmm_pending2, hmm_pending ? 1 : 0);
     if (rc) return rc;
     stat_hmm_jobs += (int64_t)js2.size();
   }
