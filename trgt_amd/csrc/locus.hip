@@ -371,8 +371,10 @@ int consensus_repair_batch(trgt_hip_ctx* c, int64_t n_jobs, const uint8_t* seqs,
   const bool tl_on = c->knobs.timeline;
   const int64_t tl0 = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
   WfaOnDevice dev;
-  int rc = wfa_batch_impl(c, &wp, n_jobs, seqs, po, pl, to, tl, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                          nullptr, nullptr, while_running, &dev);
+  WfaBatchIO io;
+  io.n_jobs = n_jobs; io.seqs = seqs; io.pat_off = po; io.pat_len = pl; io.txt_off = to; io.txt_len = tl;
+  io.while_running = while_running; io.on_device = &dev;
+  int rc = wfa_batch_impl(c, &wp, io);
   if (rc) return rc;
   RTL("alignments done");
   std::vector<vote::Group> groups;

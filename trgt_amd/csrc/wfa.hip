@@ -9,6 +9,7 @@
 #include <chrono>
 
 #include "wfa_engine.hpp"
+#include "wfa_plan.hpp"
 
 namespace trgt {
 namespace wfa {
@@ -533,267 +534,226 @@ __device__ __forceinline__ void wfa_kernel_body(const KArgs& a) {
 
 namespace trgt {
 
-// ------------------------------------------------------------------ host planner
-static int gap_cost(const trgt_wfa_params& p, int64_t len) {
-  if (len <= 0) return 0;
-  int64_t c;
-  switch (p.metric) {
-    case 0: case 1: c = len; break;
-    case 2: c = (int64_t)p.gap_ext1 * len; break;
-    case 3: c = p.gap_open1 + (int64_t)p.gap_ext1 * len; break;
-    default: c = std::min<int64_t>(p.gap_open1 + (int64_t)p.gap_ext1 * len, p.gap_open2 + (int64_t)p.gap_ext2 * len); break;
-  }
-  return (int)std::min<int64_t>(c, 1 << 28);
+// ------------------------------------------------------------------ host launcher
+// Everything wfa_launch decides -- penalties, score bound, workspace layout, which kernels run, their LDS -- is wfa_plan (wfa_plan.hpp), a
+// pure function of plain values that is checked without a GPU.  WfaCall is one launch: the plan, then the stages that act on it, in the
+// order wfa_launch lists them.
+namespace {
+
+typedef void (*WfaKernelFn)(const wfa::KArgs);
+// the pool slots of a buffer set (WfaLaunch::buffer_set)
+struct WfaSlots { int ws, counter, cells, retry, mid; };
+constexpr WfaSlots WFA_SLOTS[3] = {{S_WFA_WS, S_WFA_COUNTER, S_WFA_CELLS, S_WFA_RETRY, S_WFA_MID},
+                                   {S_WFA_WS_B, S_WFA_COUNTER_B, S_WFA_CELLS_B, S_WFA_RETRY_B, S_WFA_MID_B},
+                                   {S_WFA_WS_C, S_WFA_COUNTER_C, S_WFA_CELLS_C, S_WFA_RETRY_C, S_WFA_MID_C}};
+
+// the dedicated kernel by WfaFastId
+WfaKernelFn wfa_fast_fn(int id) {
+  using wfa::wfa_fast_kernel;
+  static const WfaKernelFn fn[WFA_FAST_IDS] = {wfa_fast_kernel<256, 0>, wfa_fast_kernel<256, 1>, wfa_fast_kernel<256, 2>, wfa_fast_kernel<192, 0>, wfa_fast_kernel<192, 1>,
+                                               wfa_fast_kernel<192, 2>, wfa_fast_kernel<0, 0>,   wfa_fast_kernel<0, 1>,   wfa_fast_kernel<0, 2>,   wfa_fast_kernel<256, 3>,
+                                               wfa_fast_kernel<128, 3>, wfa_fast_kernel<64, 3>,  wfa_fast_kernel<64, 2>};
+  return fn[id];
+}
+// the generic kernel by wfa_generic_id: the workgroup build of every metric, then the one-wave builds
+WfaKernelFn wfa_generic_fn(int id) {
+  using namespace wfa;
+  static const WfaKernelFn fn[WFA_GENERIC_IDS] = {wfa_kernel<0, false>, wfa_kernel<1, false>, wfa_kernel<2, false>, wfa_kernel<3, false>, wfa_kernel<4, false>,
+                                                  wfa_kernel_wave<1>, wfa_kernel_wave<3>};
+  return fn[id];
+}
+// its LDS-arena variant by wfa_arena_id
+WfaKernelFn wfa_arena_fn(int id) {
+  using namespace wfa;
+  static const WfaKernelFn fn[4] = {wfa_kernel<1, true>, wfa_kernel<3, true>, wfa_kernel_wave_la<1>, wfa_kernel_wave_la<3>};
+  return fn[id];
 }
 
-int wfa_launch(trgt_hip_ctx* c, const trgt_wfa_params& p, const WfaLaunch& L) {
-  using namespace wfa;
-  if (p.metric < 0 || p.metric > 4) return fail(c, TRGT_ERR_INVALID, "wfa: bad metric %d", p.metric);
-  if (p.heuristic != 0 && p.heuristic != 1) return fail(c, TRGT_ERR_UNSUPPORTED, "wfa: only Heuristic::None and WFadaptive are implemented");
-  if (p.memory_mode == 3 && p.span != 0) return fail(c, TRGT_ERR_UNSUPPORTED, "wfa: BiWFA is end-to-end only (as used by TRGT)");
-  if (p.metric >= 2 && (p.mismatch <= 0 || p.gap_ext1 <= 0 || (p.metric >= 3 && p.gap_open1 < 0)))
-    return fail(c, TRGT_ERR_INVALID, "wfa: penalties must be positive");
-  KArgs a;
-  std::memset(&a, 0, sizeof a);
-  Pen& pen = a.kp.pen;
-  pen.metric = p.metric;
-  switch (p.metric) {
-    case 0: pen.x = -1; pen.o1 = 1; pen.e1 = -1; pen.o2 = pen.e2 = -1; pen.scope = 2; pen.ncomp = 1; break;
-    case 1: pen.x = 1; pen.o1 = 1; pen.e1 = -1; pen.o2 = pen.e2 = -1; pen.scope = 2; pen.ncomp = 1; break;
-    case 2: pen.x = p.mismatch; pen.o1 = p.gap_ext1; pen.e1 = -1; pen.o2 = pen.e2 = -1; pen.scope = std::max(pen.x, pen.o1) + 1; pen.ncomp = 1; break;
-    case 3: pen.x = p.mismatch; pen.o1 = p.gap_open1; pen.e1 = p.gap_ext1; pen.o2 = pen.e2 = -1; pen.scope = std::max(pen.x, pen.o1 + pen.e1) + 1; pen.ncomp = 3; break;
-    default: pen.x = p.mismatch; pen.o1 = p.gap_open1; pen.e1 = p.gap_ext1; pen.o2 = p.gap_open2; pen.e2 = p.gap_ext2;
-      pen.scope = std::max(pen.x, std::max(pen.o1 + pen.e1, pen.o2 + pen.e2)) + 1; pen.ncomp = 5; break;
+struct WfaCall {
+  trgt_hip_ctx* const c; const trgt_wfa_params& p; const WfaLaunch& L;
+  const int bset;
+  WfaPlan plan;
+  wfa::KArgs a;
+  void *d_ws = nullptr, *d_counter = nullptr, *d_cells = nullptr;
+  WfaKernelFn main_fn = nullptr;
+  int64_t grid_blocks = 0;
+
+  WfaCall(trgt_hip_ctx* c_, const trgt_wfa_params& p_, const WfaLaunch& L_) : c(c_), p(p_), L(L_), bset(L_.buffer_set == 2 ? 2 : L_.buffer_set ? 1 : 0) {}
+
+  int make_plan() {
+    WfaPlanIn in;
+    in.p = p;
+    in.n_jobs_host = L.n_jobs_host; in.jobs_bound = L.jobs_bound; in.max_plen = L.max_plen; in.max_tlen = L.max_tlen; in.max_sum = L.max_sum;
+    in.threads = L.threads; in.max_score = L.max_score;
+    in.tag = L.kernel_tag >= 0 ? L.kernel_tag : (L.timer_slot == TRGT_K_WFA_FLANK_REST ? 1 : 0);
+    in.ws_budget = L.ws_budget; in.buffer_set = bset;
+    in.has_ops = L.ops != nullptr; in.has_n_jobs_dev = L.n_jobs_dev != nullptr; in.has_jobs2 = L.n_jobs2_dev != nullptr;
+    in.num_cus = c->num_cus; in.ws_limit = c->ws_limit;
+    const trgt_knobs& k = c->knobs;
+    in.no_spec = k.no_spec; in.no_lean = k.no_lean; in.no_lds_wfa = k.no_lds_wfa; in.wfa_no_wave_variant = k.wfa_no_wave_variant;
+    in.wfa_no_stage = k.wfa_no_stage; in.skip_bt = k.skip_bt; in.lds_wfa_seq = k.lds_wfa_seq; in.lds_wfa_kb = k.lds_wfa_kb;
+    const char* why = "";
+    if (const int rc = wfa_plan(in, &plan, &why)) return fail(c, rc, "%s", why);
+    main_fn = plan.main == WFA_MAIN_FAST ? wfa_fast_fn(plan.main_id) : wfa_generic_fn(plan.main_id);
+    return TRGT_OK;
   }
-  if (pen.scope > RING) return fail(c, TRGT_ERR_UNSUPPORTED, "wfa: penalties need a score scope of %d (> %d)", pen.scope, RING);
-  a.kp.span = p.span; a.kp.pbf = p.pattern_begin_free; a.kp.pef = p.pattern_end_free; a.kp.tbf = p.text_begin_free; a.kp.tef = p.text_end_free;
-  a.kp.scope_alignment = p.scope != 0; a.kp.biwfa = p.memory_mode == 3; a.kp.heuristic = p.heuristic;
-  a.kp.h_min_len = p.h_min_wavefront_length; a.kp.h_max_dist = p.h_max_distance_threshold; a.kp.h_steps = p.h_steps_between_cutoffs;
-  a.kp.bi_min_score = p.bialign_min_score; a.kp.bi_min_length = p.bialign_min_length;
-  // ---- workspace plan from the batch maxima
-  const int64_t mp = L.max_plen, mt = L.max_tlen, msum = L.max_sum;
-  int64_t score_bound;
-  const bool text_free = p.span == 1 && (p.text_begin_free < 0) && (p.text_end_free < 0);
-  if (text_free) score_bound = gap_cost(p, mp) + 2;          // delete the whole pattern anywhere in the free text
-  else score_bound = (int64_t)gap_cost(p, mp) + gap_cost(p, mt) + 2;
-  if (a.kp.biwfa && a.kp.scope_alignment) {                   // base cases: score <= 250 unless the heuristic misleads; min-length fallback
-    const int64_t small = (int64_t)gap_cost(p, std::min<int64_t>(mp, p.bialign_min_length)) + gap_cost(p, std::min<int64_t>(mt, p.bialign_min_length)) + 2;
-    score_bound = std::min<int64_t>(score_bound, std::max<int64_t>(small, 4 * (int64_t)p.bialign_min_score + 64));
+
+  // workspace, then the counter block, then the offset counter
+  int take_buffers() {
+    int rc;
+    if ((rc = dev_get(c, WFA_SLOTS[bset].ws, (size_t)(plan.ws_per_block * (uint64_t)plan.blocks), &d_ws))) return rc;
+    // job counters | slot flags | 40 words of the lean kernels (statistics, their counters); the offset counter of the batch.  Cleared
+    // pieces of the call's zero arena (inside trgt_locus_batch: no hipMemsetAsync per launch), else pool slots cleared here
+    if ((rc = dev_get_zeroed(c, WFA_SLOTS[bset].counter, (size_t)plan.counter_bytes, &d_counter, c->stream))) return rc;
+    // (buffer set 2 = the device-side chains of a locus call -- consensus repair, cluster genotyper: their launches count into one piece,
+    //  read back once per call for the roofline block of the consensus alignments)
+    const bool chain_keep = bset == 2 && c->zero_on && c->wfa_cells_cur[2] != nullptr;
+    if (!L.keep_cells && !chain_keep) {
+      if ((rc = dev_get_zeroed(c, WFA_SLOTS[bset].cells, 32, &d_cells, c->stream))) return rc;
+      c->wfa_cells_cur[bset] = d_cells;
+    } else if (c->wfa_cells_cur[bset]) d_cells = c->wfa_cells_cur[bset];  // a later launch of the same logical batch: keeps counting where the first one did
+    else if ((rc = dev_get(c, WFA_SLOTS[bset].cells, 32, &d_cells))) return rc;
+    return TRGT_OK;
   }
-  score_bound = std::min<int64_t>(score_bound, 1 << 20);
-  const bool capped = L.max_score > 0 && p.span == 1 && p.pattern_begin_free == 0 && p.text_begin_free >= 0;
-  if (capped) score_bound = std::min<int64_t>(score_bound, L.max_score + 1);
-  const uint64_t per_level = (uint64_t)pen.ncomp * (uint64_t)std::min<int64_t>(msum + 3, 2 * score_bound + 3 + (p.span ? msum : 0));
-  uint64_t arena_ints = std::min<uint64_t>((uint64_t)(score_bound + 1) * per_level + 64, (1ull << 30) / 4);  // <= 1 GiB per workgroup
-  const uint64_t ring_stride = (uint64_t)msum + 4;
-  const uint64_t ring_ints = a.kp.biwfa ? (uint64_t)pen.scope * pen.ncomp * ring_stride : 0;
-  auto al = [](uint64_t v) { return (v + 255) & ~255ull; };
-  uint64_t off = 0;
-  a.uni_slots = (uint32_t)(score_bound + 1);
-  a.off_gdesc = off; off = al(off + (uint64_t)a.uni_slots * 5 * sizeof(WfDesc));
-  a.off_arena_u = off; off = al(off + arena_ints * 4);
-  a.off_arena_f = off; off = al(off + ring_ints * 4);
-  a.off_arena_r = off; off = al(off + ring_ints * 4);
-  a.rle_cap = (uint32_t)(msum + 4);
-  a.off_rle_tmp = off; off = al(off + (uint64_t)a.rle_cap * 4);
-  a.off_rle_out = off; off = al(off + (uint64_t)a.rle_cap * 4);
-  a.off_run_start = off; off = al(off + (uint64_t)a.rle_cap * 4);
-  a.ws_per_block = off;
-  a.arena_uni_cap = (uint32_t)std::min<uint64_t>(arena_ints, 0xFFFFFFF0ull);
-  a.ring_stride = (uint32_t)ring_stride;
-  const int threads = L.threads > 0 ? L.threads : (p.span == 1 ? 256 : 64);
-  int64_t blocks = std::min<int64_t>(L.n_jobs_host, (int64_t)c->num_cus * (threads >= 512 ? 4 : threads >= 256 ? 8 : 16));
-  blocks = std::min<int64_t>(blocks, (int64_t)(c->ws_limit / std::max<uint64_t>(a.ws_per_block, 1)));
-  if (L.ws_budget > 0 && blocks > 1) blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, (int64_t)(L.ws_budget / std::max<uint64_t>(a.ws_per_block, 1))));
-  if (blocks < 1) {
-    // shrink the per-workgroup arena to what the limit allows; overflowing jobs report TRGT_WF_OOM
-    const uint64_t fixed = a.ws_per_block - al(arena_ints * 4);
-    if (c->ws_limit <= fixed + 4096) return fail(c, TRGT_ERR_NOMEM, "wfa: workspace limit %llu B too small", (unsigned long long)c->ws_limit);
-    arena_ints = (c->ws_limit - fixed - 4096) / 4;
-    return fail(c, TRGT_ERR_NOMEM, "wfa: one workgroup needs %llu B of workspace, limit is %llu B", (unsigned long long)a.ws_per_block,
-                (unsigned long long)c->ws_limit);
+
+  void fill_args() {
+    std::memset(&a, 0, sizeof a);
+    wfa::KParams& kp = a.kp;
+    kp.pen = plan.pen;
+    kp.span = p.span; kp.pbf = p.pattern_begin_free; kp.pef = p.pattern_end_free; kp.tbf = p.text_begin_free; kp.tef = p.text_end_free;
+    kp.scope_alignment = p.scope != 0; kp.biwfa = p.memory_mode == 3; kp.heuristic = p.heuristic;
+    kp.h_min_len = p.h_min_wavefront_length; kp.h_max_dist = p.h_max_distance_threshold; kp.h_steps = p.h_steps_between_cutoffs;
+    kp.bi_min_score = p.bialign_min_score; kp.bi_min_length = p.bialign_min_length;
+    a.uni_slots = plan.uni_slots; a.arena_uni_cap = plan.arena_uni_cap; a.ring_stride = plan.ring_stride; a.rle_cap = plan.rle_cap;
+    a.off_gdesc = plan.off_gdesc; a.off_arena_u = plan.off_arena_u; a.off_arena_f = plan.off_arena_f; a.off_arena_r = plan.off_arena_r;
+    a.off_rle_tmp = plan.off_rle_tmp; a.off_rle_out = plan.off_rle_out; a.off_run_start = plan.off_run_start; a.ws_per_block = plan.ws_per_block;
+    a.slot_flags = (unsigned int*)d_counter + 4; a.n_slots_ws = (uint32_t)plan.blocks; a.jobs_per_block = 0xFFFFFFFFu;  // persistent workgroups: measured 15-45 % faster than short-lived ones
+    a.ws = (uint8_t*)d_ws; a.counter = (unsigned int*)d_counter; a.cells_out = (unsigned long long*)d_cells; a.refused = L.refused;
+    a.jobs = L.jobs_dev; a.n_jobs = (uint32_t)L.n_jobs_host; a.n_jobs_dev = L.n_jobs_dev;
+    a.n_jobs2_dev = L.n_jobs2_dev; a.jobs_cap = L.jobs_cap;
+    a.pat_base = L.pat_base; a.txt_base = L.txt_base;
+    a.status = L.status; a.score = L.score; a.n_match = L.n_match; a.span4 = L.span4; a.cigar = L.cigar; a.cigar_len = L.cigar_len;
+    a.ops = L.ops; a.ops_len = L.ops_len;
+    a.lds_seq_cap = plan.lds_seq_cap; a.fast_wcap = plan.fast_wcap; a.fast_ring_bytes = plan.fast_ring_bytes; a.fast_koff = plan.fast_koff;
+    a.fast_dbg = plan.fast_dbg; a.ring_off = plan.ring_off; a.ring_mask = plan.ring_mask;
   }
-  void* d_ws = nullptr; void* d_counter = nullptr; void* d_cells = nullptr;
-  int rc;
-  if ((rc = dev_get(c, L.buffer_set == 2 ? S_WFA_WS_C : L.buffer_set ? S_WFA_WS_B : S_WFA_WS, (size_t)(a.ws_per_block * (uint64_t)blocks), &d_ws))) return rc;
-  // job counters | slot flags | 24 words of the lean kernels (statistics, their counters); the offset counter of the batch.  Cleared
-  // pieces of the call's zero arena (inside trgt_locus_batch: no hipMemsetAsync per launch), else pool slots cleared here
-  const size_t counter_bytes = 16 + 4 * (size_t)blocks + 160;  // (+ 40 words of the lean kernels: 3 x 8 statistics, 5 counters)
-  const int bset = L.buffer_set == 2 ? 2 : L.buffer_set ? 1 : 0;
-  if ((rc = dev_get_zeroed(c, bset == 2 ? S_WFA_COUNTER_C : bset ? S_WFA_COUNTER_B : S_WFA_COUNTER, counter_bytes, &d_counter, c->stream))) return rc;
-  // (buffer set 2 = the device-side chains of a locus call -- consensus repair, cluster genotyper: their launches count into one piece,
-  //  read back once per call for the roofline block of the consensus alignments)
-  const bool chain_keep = bset == 2 && c->zero_on && c->wfa_cells_cur[2] != nullptr;
-  if (!L.keep_cells && !chain_keep) {
-    if ((rc = dev_get_zeroed(c, bset == 2 ? S_WFA_CELLS_C : bset ? S_WFA_CELLS_B : S_WFA_CELLS, 32, &d_cells, c->stream))) return rc;
-    c->wfa_cells_cur[bset] = d_cells;
-  } else if (c->wfa_cells_cur[bset]) d_cells = c->wfa_cells_cur[bset];  // a later launch of the same logical batch: keeps counting where the first one did
-  else if ((rc = dev_get(c, bset == 2 ? S_WFA_CELLS_C : bset ? S_WFA_CELLS_B : S_WFA_CELLS, 32, &d_cells))) return rc;
-  a.slot_flags = (unsigned int*)d_counter + 4; a.n_slots_ws = (uint32_t)blocks; a.jobs_per_block = 0xFFFFFFFFu;  // persistent workgroups: measured 15-45 % faster than short-lived ones
-  a.ws = (uint8_t*)d_ws; a.counter = (unsigned int*)d_counter; a.cells_out = (unsigned long long*)d_cells; a.refused = L.refused;
-  a.jobs = L.jobs_dev; a.n_jobs = (uint32_t)L.n_jobs_host; a.n_jobs_dev = L.n_jobs_dev;
-  a.n_jobs2_dev = L.n_jobs2_dev; a.jobs_cap = L.jobs_cap;
-  a.pat_base = L.pat_base; a.txt_base = L.txt_base;
-  a.status = L.status; a.score = L.score; a.n_match = L.n_match; a.span4 = L.span4; a.cigar = L.cigar; a.cigar_len = L.cigar_len;
-  a.ops = L.ops; a.ops_len = L.ops_len;
-  a.retry_jobs = nullptr; a.retry_count = nullptr;
-  const uint64_t seq_need = ((uint64_t)mp + 15) / 16 * 16 + (uint64_t)mt + 16;
-  a.lds_seq_cap = (uint32_t)((std::min<uint64_t>(seq_need, 32 * 1024) + 15) & ~15ull);
-  if (seq_need > 32 * 1024 || c->knobs.wfa_no_stage) a.lds_seq_cap = 0;  // too long: extend straight from global memory (L1/L2 cached)
-  size_t lds = a.lds_seq_cap;
-  a.fast_wcap = 0; a.fast_ring_bytes = 0; a.fast_koff = 0;
-  a.fast_dbg = c->knobs.skip_bt ? 1 : 0;
-  if (p.metric == 3 && p.heuristic == 0 && !a.kp.biwfa && a.lds_seq_cap > 0 && mt + score_bound < 65000 && threads % 64 == 0 && threads <= 256) {
-    // LDS fast path (wfa_fast.hpp): ring of the live wavefronts as 16-bit offsets
-    uint64_t wcap = ((uint64_t)msum + 8 + 7) & ~7ull;
-    if (capped) {  // levels 0 .. max_score + 1: diagonals -(max_score + 1) .. text_begin_free + max_score + 1
-      a.fast_koff = (uint32_t)(L.max_score + 4);
-      wcap = std::min<uint64_t>(wcap, ((uint64_t)a.fast_koff + (uint64_t)p.text_begin_free + (uint64_t)L.max_score + 12 + 7) & ~7ull);
-    }
-    const uint64_t ring_bytes = (uint64_t)(std::max(pen.x, pen.o1 + pen.e1) + 1 + 2 * (pen.e1 + 1)) * wcap * 2;
-    const uint64_t win_bytes = 4ull * (uint64_t)(mp + mt + 8);
-    // (the byte copies of the two sequences are staged in the ring area, which is idle until level 0 is written)
-    if (ring_bytes + win_bytes <= 96 * 1024 && (seq_need <= ring_bytes || capped)) { a.fast_wcap = (uint32_t)wcap; a.fast_ring_bytes = (uint32_t)((ring_bytes + 15) & ~15ull); lds = (size_t)a.fast_ring_bytes + (size_t)win_bytes; }
-  }
-  // TRGT's flank-location configuration has an instantiation of its own (wfa_fast.hpp, SPEC)
-  const int tag = L.kernel_tag >= 0 ? L.kernel_tag : (L.timer_slot == TRGT_K_WFA_FLANK_REST ? 1 : 0);
-  const bool flank_pen = pen.x == 2 && pen.o1 == 5 && pen.e1 == 1 && a.kp.span == 1 && a.kp.pbf == 0 && a.kp.pef == 0 && a.kp.tef < 0 && !c->knobs.no_spec;
-  const bool fast_spec = flank_pen && a.fast_koff == 0 && a.kp.tbf < 0 && (threads == 256 || threads == 192);
-  const bool win_spec = flank_pen && a.fast_koff != 0 && (tag == 2 || tag == 3) && threads == 64;  // the windowed launches of trgt_find_spans_batch
-  // (TRGT_BAND_THREADS=256 / 128: the banded back-trace of what the pre-filter keeps with four / two waves per alignment -- its launch is as
-  //  long as its slowest alignment, and a band of 2 s* + 2 s + 1 diagonals is several strips of a wave)
-  const bool band_wide = flank_pen && a.fast_koff != 0 && tag == 3 && (threads == 256 || threads == 128);
-  if (tag == 3 && !win_spec && !band_wide) return fail(c, TRGT_ERR_INVALID, "wfa: the banded launch exists for the flank configuration only");
-  void (*const spec_fn[2][3])(const KArgs) = {{wfa_fast_kernel<256, 0>, wfa_fast_kernel<256, 1>, wfa_fast_kernel<256, 2>},
-                                              {wfa_fast_kernel<192, 0>, wfa_fast_kernel<192, 1>, wfa_fast_kernel<192, 2>}};
-  void (*const gen_fn[3])(const KArgs) = {wfa_fast_kernel<0, 0>, wfa_fast_kernel<0, 1>, wfa_fast_kernel<0, 2>};
-  void (*const fast_fn)(const KArgs) = band_wide ? (threads == 256 ? wfa_fast_kernel<256, 3> : wfa_fast_kernel<128, 3>) : win_spec ? (tag == 3 ? wfa_fast_kernel<64, 3> : wfa_fast_kernel<64, 2>) : fast_spec ? spec_fn[threads == 192 ? 1 : 0][tag] : gen_fn[tag];
-  KTimer t(c, L.timer_slot);
+
   // `blocks` bounds how many workgroups can be resident (one workspace slot each); the grid covers all jobs
-  int64_t grid_blocks = std::max<int64_t>(1, std::min<int64_t>(blocks, L.n_jobs_host));
-  if (a.fast_wcap > 0) {
-    // Persistent workgroups: launch exactly as many as can be resident (LDS- and register-bound, 4 per CU at most).  Workgroups
-    // waiting for dispatch would do no work anyway, and while they wait the dispatcher keeps kernels of other streams (the
-    // gather / HMM kernels of an earlier chunk) from starting.
-    int occ = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fast_fn, threads, lds) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 4; }
-    int64_t per_cu = occ;
-    if (c->knobs.grid_per_cu > 0) per_cu = c->knobs.grid_per_cu;
-    if (c->knobs.debug) fprintf(stderr, "[wfa] fast kernel lds=%zu occupancy=%d per_cu=%lld threads=%d\n", lds, occ, (long long)per_cu, threads);
-    grid_blocks = std::min<int64_t>(grid_blocks, (int64_t)c->num_cus * per_cu);
+  int size_main_grid() {
+    grid_blocks = std::max<int64_t>(1, std::min<int64_t>(plan.blocks, L.n_jobs_host));
+    if (plan.main == WFA_MAIN_FAST) {
+      // Persistent workgroups: launch exactly as many as can be resident (LDS- and register-bound, 4 per CU at most).  Workgroups
+      // waiting for dispatch would do no work anyway, and while they wait the dispatcher keeps kernels of other streams (the
+      // gather / HMM kernels of an earlier chunk) from starting.
+      int occ = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, main_fn, plan.threads, (size_t)plan.lds) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 4; }
+      int64_t per_cu = occ;
+      if (c->knobs.grid_per_cu > 0) per_cu = c->knobs.grid_per_cu;
+      if (c->knobs.debug) fprintf(stderr, "[wfa] fast kernel lds=%zu occupancy=%d per_cu=%lld threads=%d\n", (size_t)plan.lds, occ, (long long)per_cu, plan.threads);
+      grid_blocks = std::min<int64_t>(grid_blocks, (int64_t)c->num_cus * per_cu);
+    } else if (plan.lds > 48 * 1024) {
+      for (int id = 0; id < WFA_GENERIC_IDS; ++id)
+        TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)wfa_generic_fn(id), hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds));
+    }
+    return TRGT_OK;
   }
-  const dim3 grid((unsigned)grid_blocks), block((unsigned)threads);
-  if (a.fast_wcap == 0) {  // the generic kernel keeps the descriptor rings of its three instances behind the staged sequences
-    a.ring_mask = RING - 1; a.ring_off = (a.lds_seq_cap + 15u) & ~15u;
-    lds = (size_t)a.ring_off + 3 * RING * 5 * sizeof(WfDesc);
-    if (lds > 48 * 1024)
-      for (const void* fn : {(const void*)wfa_kernel<0, false>, (const void*)wfa_kernel<1, false>, (const void*)wfa_kernel<2, false>, (const void*)wfa_kernel<3, false>, (const void*)wfa_kernel<4, false>,
-                             (const void*)wfa_kernel_wave<1>, (const void*)wfa_kernel_wave<3>})
-        TRGT_HIP_TRY(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  }
-  // ---- BiWFA batches of one wave per alignment (consensus alignments, edit distances): first the LDS-arena variant over the whole list,
-  //      then the HBM variant over what did not fit (its job list and count are written by the first launch)
-  // ---- BiWFA batches of one wave per alignment (consensus alignments, edit distances): first the register-resident kernel (wfa_lean.hip) over
-  //      the whole list, then this kernel over what it did not take (job list and count written by the first launch)
-  const int64_t jobs_bound = L.jobs_bound > 0 ? L.jobs_bound : L.n_jobs_host;  // (n_jobs_host may only bound the workgroups: the retry list holds every job)
-  const bool one_wave_biwfa = a.kp.biwfa && p.span == 0 && threads == 64 && !L.ops && a.fast_wcap == 0 && !L.n_jobs2_dev;
-  const bool lean_ok = one_wave_biwfa && !c->knobs.no_lean && (p.metric == 1 || (p.metric == 3 && pen.x == 2 && pen.o1 == 5 && pen.e1 == 1));
-  if (lean_ok) {
-    // (with a device-side job count the retry list must hold every job the lean kernels may hand on -- n_jobs_host only
-    //  bounds the workgroups then -- so the caller has to say how many there can be; a list that is too short would drop alignments)
-    if (L.n_jobs_dev && L.jobs_bound <= 0) return fail(c, TRGT_ERR_INVALID, "wfa: a launch with a device-side job count needs jobs_bound (the capacity of the hand-over lists)");
-    void* d_retry = nullptr;
-    if ((rc = dev_get(c, L.buffer_set == 2 ? S_WFA_RETRY_C : L.buffer_set ? S_WFA_RETRY_B : S_WFA_RETRY, (size_t)jobs_bound * sizeof(JobDev), &d_retry))) return rc;
-    void* d_mid = nullptr;
-    if ((rc = dev_get(c, L.buffer_set == 2 ? S_WFA_MID_C : L.buffer_set ? S_WFA_MID_B : S_WFA_MID, 2 * (size_t)jobs_bound * sizeof(JobDev), &d_mid))) return rc;  // (two lists: between tiers one / two and two / three)
-    unsigned int* const lean_words = (unsigned int*)d_counter + 4 + blocks;  // [0..23] statistics of the three tiers, [24..28] their counters
-    if ((rc = wfa_lean_launch(c, p, L, (JobDev*)d_mid, (JobDev*)d_retry, (unsigned int*)d_counter + 1, (uint32_t)std::min<int64_t>(jobs_bound, 0xFFFFFFF0ll), (unsigned int*)d_counter + 3,
-                              lean_words + 24, (unsigned long long*)d_cells, c->knobs.debug ? lean_words : nullptr)))
-      return rc;
+
+  // a front launch has handed on what it did not take: the main kernel runs over the retry list, counted at word 1 of the counter block
+  void main_from_retry_list(void* d_retry) {
     a.jobs = (const JobDev*)d_retry; a.n_jobs_dev = (const uint32_t*)d_counter + 1; a.n_jobs2_dev = nullptr; a.jobs_cap = 0;
     a.counter = (unsigned int*)d_counter + 2;
   }
-  const bool la_ok = !lean_ok && one_wave_biwfa && (p.metric == 1 || p.metric == 3) && !c->knobs.no_lds_wfa;
-  if (la_ok) {
+
+  // the register-resident kernels (wfa_lean.hip) over the whole list, then the generic kernel over what they did not take
+  int lean_front() {
+    if (plan.front != WFA_FRONT_LEAN) return TRGT_OK;
+    int rc;
+    void *d_retry = nullptr, *d_mid = nullptr;
+    if ((rc = dev_get(c, WFA_SLOTS[bset].retry, (size_t)plan.jobs_bound * sizeof(JobDev), &d_retry))) return rc;
+    if ((rc = dev_get(c, WFA_SLOTS[bset].mid, 2 * (size_t)plan.jobs_bound * sizeof(JobDev), &d_mid))) return rc;  // (two lists: between tiers one / two and two / three)
+    unsigned int* const lean_words = (unsigned int*)d_counter + 4 + plan.blocks;  // [0..23] statistics of the three tiers, [24..28] their counters
+    if ((rc = wfa_lean_launch(c, p, L, (JobDev*)d_mid, (JobDev*)d_retry, (unsigned int*)d_counter + 1, (uint32_t)std::min<int64_t>(plan.jobs_bound, 0xFFFFFFF0ll), (unsigned int*)d_counter + 3,
+                              lean_words + 24, (unsigned long long*)d_cells, c->knobs.debug ? lean_words : nullptr)))
+      return rc;
+    main_from_retry_list(d_retry);
+    return TRGT_OK;
+  }
+
+  // the LDS-arena variant of the generic kernel over the whole list, then the HBM variant over what did not fit
+  int arena_front() {
+    if (plan.front != WFA_FRONT_ARENA) return TRGT_OK;
     void* d_retry = nullptr;
-    if ((rc = dev_get(c, L.buffer_set == 2 ? S_WFA_RETRY_C : L.buffer_set ? S_WFA_RETRY_B : S_WFA_RETRY, (size_t)jobs_bound * sizeof(JobDev), &d_retry))) return rc;
-    KArgs la = a;
-    // dynamic LDS of a workgroup: sequences | two run-length buffers | descriptor rings (as many levels as the score scope needs) | the
-    // region of the wavefronts.  Defaults sized for 12 workgroups per CU (one wave each; the registers allow no more): this kernel is all
-    // latency, and the alignments that do not fit are few and go to the HBM variant.
-    const uint32_t seq_cap = (uint32_t)std::max(256, c->knobs.lds_wfa_seq), rle_cap = 96, region = (uint32_t)std::max(2, c->knobs.lds_wfa_kb) * 1024u;
-    uint32_t ring_levels = 2;
-    while ((int)ring_levels < pen.scope) ring_levels *= 2;
-    la.lds_seq_cap = seq_cap; la.la_rle_cap = rle_cap; la.la_rle_tmp = seq_cap; la.la_rle_out = seq_cap + 4 * rle_cap;
-    la.ring_off = seq_cap + 8 * rle_cap; la.ring_mask = ring_levels - 1;
-    la.la_region = la.ring_off + 3 * ring_levels * 5 * (uint32_t)sizeof(WfDesc); la.la_region_bytes = region;
-    la.la_gdesc_slots = std::min<uint32_t>(40, (region / 3) / (5 * (uint32_t)sizeof(WfDesc)));
+    if (const int rc = dev_get(c, WFA_SLOTS[bset].retry, (size_t)plan.jobs_bound * sizeof(JobDev), &d_retry)) return rc;
+    wfa::KArgs la = a;
+    la.lds_seq_cap = plan.la_seq_cap; la.la_rle_cap = plan.la_rle_cap; la.la_rle_tmp = plan.la_rle_tmp; la.la_rle_out = plan.la_rle_out;
+    la.ring_off = plan.la_ring_off; la.ring_mask = plan.la_ring_mask;
+    la.la_region = plan.la_region; la.la_region_bytes = plan.la_region_bytes; la.la_gdesc_slots = plan.la_gdesc_slots;
     la.retry_jobs = (JobDev*)d_retry; la.retry_count = (unsigned int*)d_counter + 1;
-    const size_t la_lds = (size_t)la.la_region + region;
-    void (*const la_fn)(const KArgs) = c->knobs.wfa_no_wave_variant ? (p.metric == 1 ? wfa_kernel<1, true> : wfa_kernel<3, true>) : (p.metric == 1 ? wfa_kernel_wave_la<1> : wfa_kernel_wave_la<3>);
+    const size_t la_lds = (size_t)plan.la_lds;
+    const WfaKernelFn la_fn = wfa_arena_fn(plan.arena_id);
     int occ = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, la_fn, 64, la_lds) != hipSuccess || occ < 1) { (void)hipGetLastError(); occ = 4; }
     const int64_t la_grid = std::max<int64_t>(1, std::min<int64_t>(L.n_jobs_host, (int64_t)c->num_cus * occ));
-    if (c->knobs.debug) fprintf(stderr, "[wfa] LDS-arena variant: lds=%zu (+ static) occupancy=%d grid=%lld ring levels %u gdesc slots %u\n", la_lds, occ, (long long)la_grid, ring_levels, la.la_gdesc_slots);
+    if (c->knobs.debug) fprintf(stderr, "[wfa] LDS-arena variant: lds=%zu (+ static) occupancy=%d grid=%lld ring levels %u gdesc slots %u\n", la_lds, occ, (long long)la_grid, plan.la_ring_mask + 1, la.la_gdesc_slots);
     hipLaunchKernelGGL(la_fn, dim3((unsigned)la_grid), dim3(64), la_lds, c->stream, la);
     TRGT_HIP_TRY(c, hipGetLastError());
-    a.jobs = (const JobDev*)d_retry; a.n_jobs_dev = (const uint32_t*)d_counter + 1; a.n_jobs2_dev = nullptr; a.jobs_cap = 0;
-    a.counter = (unsigned int*)d_counter + 2;
+    main_from_retry_list(d_retry);
+    return TRGT_OK;
   }
-  const bool wave_variant = threads == 64 && !c->knobs.wfa_no_wave_variant;  // (edit and gap-affine have one: what the locus path uses)
-  if (a.fast_wcap > 0) {
-    // every job of this batch qualifies for the dedicated LDS-resident kernel (wfa_fast.hpp)
-    if (lds > 48 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)fast_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(fast_fn, grid, block, lds, c->stream, a);
-  } else
-  switch (p.metric) {
-    case 0: hipLaunchKernelGGL((wfa_kernel<0, false>), grid, block, lds, c->stream, a); break;
-    case 1: if (wave_variant) hipLaunchKernelGGL((wfa_kernel_wave<1>), grid, block, lds, c->stream, a); else hipLaunchKernelGGL((wfa_kernel<1, false>), grid, block, lds, c->stream, a); break;
-    case 2: hipLaunchKernelGGL((wfa_kernel<2, false>), grid, block, lds, c->stream, a); break;
-    case 3: if (wave_variant) hipLaunchKernelGGL((wfa_kernel_wave<3>), grid, block, lds, c->stream, a); else hipLaunchKernelGGL((wfa_kernel<3, false>), grid, block, lds, c->stream, a); break;
-    default: hipLaunchKernelGGL((wfa_kernel<4, false>), grid, block, lds, c->stream, a); break;
-  }
-  { const hipError_t le = hipGetLastError();
+
+  int launch_main() {
+    const size_t lds = (size_t)plan.lds;
+    // (dedicated kernel: every job of this batch qualifies for it, wfa_fast.hpp)
+    if (plan.main == WFA_MAIN_FAST && lds > 48 * 1024) TRGT_HIP_TRY(c, hipFuncSetAttribute((const void*)main_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(main_fn, dim3((unsigned)grid_blocks), dim3((unsigned)plan.threads), lds, c->stream, a);
+    const hipError_t le = hipGetLastError();
     if (le != hipSuccess) return fail(c, TRGT_ERR_HIP, "alignment kernel launch failed: %s (buffer set %d, at most %lld jobs, metric %d, %s, lds %zu, grid %lld x %d)", hipGetErrorString(le),
-                                      L.buffer_set, (long long)L.n_jobs_host, p.metric, a.fast_wcap ? "dedicated kernel" : "generic kernel", lds, (long long)grid_blocks, threads); }
-  t.stop(0);
-  if (lean_ok && c->knobs.debug) {  // (synchronises: developer output only)
+                                      L.buffer_set, (long long)L.n_jobs_host, p.metric, plan.main == WFA_MAIN_FAST ? "dedicated kernel" : "generic kernel", lds, (long long)grid_blocks, plan.threads);
+    return TRGT_OK;
+  }
+
+  // TRGT_WFA_DEBUG: what the front launch handed on (synchronises: developer output only)
+  int debug_report() {
+    if (!c->knobs.debug || plan.front == WFA_FRONT_NONE) return TRGT_OK;
     unsigned int h[4] = {0, 0, 0, 0};
     TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
     TRGT_HIP_TRY(c, hipMemcpy(h, d_counter, 16, hipMemcpyDeviceToHost));
+    if (plan.front == WFA_FRONT_ARENA) {
+      fprintf(stderr, "[wfa] LDS-arena variant: metric %d, %lld jobs at most, %u went on to the HBM variant\n", p.metric, (long long)L.n_jobs_host, h[1]);
+      return TRGT_OK;
+    }
     unsigned int w[40];
-    TRGT_HIP_TRY(c, hipMemcpy(w, (unsigned int*)d_counter + 4 + blocks, 160, hipMemcpyDeviceToHost));
-    fprintf(stderr, "[wfa] lean kernels: metric %d, %lld jobs at most, %u went on to the second tier, %u to the third, %u to the generic kernel (%u lost)\n", p.metric, (long long)jobs_bound, w[25], w[27], h[1], h[3]);
+    TRGT_HIP_TRY(c, hipMemcpy(w, (unsigned int*)d_counter + 4 + plan.blocks, 160, hipMemcpyDeviceToHost));
+    fprintf(stderr, "[wfa] lean kernels: metric %d, %lld jobs at most, %u went on to the second tier, %u to the third, %u to the generic kernel (%u lost)\n", p.metric, (long long)plan.jobs_bound, w[25], w[27], h[1], h[3]);
     for (int t = 0; t < 3; ++t)
       fprintf(stderr, "[wfa]   tier %d handed on: lengths %u, window %u, range %u, history levels %u, history cells %u, runs %u, stack %u, status %u\n", t + 1,
               w[8 * t + 0], w[8 * t + 1], w[8 * t + 2], w[8 * t + 3], w[8 * t + 4], w[8 * t + 5], w[8 * t + 6], w[8 * t + 7]);
+    return TRGT_OK;
   }
-  if (la_ok && c->knobs.debug) {  // (synchronises: developer output only)
-    unsigned int h[4] = {0, 0, 0, 0};
-    TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
-    TRGT_HIP_TRY(c, hipMemcpy(h, d_counter, 16, hipMemcpyDeviceToHost));
-    fprintf(stderr, "[wfa] LDS-arena variant: metric %d, %lld jobs at most, %u went on to the HBM variant\n", p.metric, (long long)L.n_jobs_host, h[1]);
-  }
+
+  // make PROF=1: the clocks the kernels of the main launch left in their profile symbols, read and cleared
+  int prof_readback() {
 #ifdef TRGT_WFA_PROF
-  if (a.fast_wcap == 0) {
-    unsigned long long h[8], z[8] = {0};
-    TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
-    TRGT_HIP_TRY(c, hipMemcpyFromSymbol(h, HIP_SYMBOL(wfa::g_wfa_gprof), sizeof h));
-    TRGT_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(wfa::g_wfa_gprof), z, sizeof h));
-    const double tot = (double)(h[0] + h[1] + h[2] + h[3]) + 1e-9;
-    fprintf(stderr, "[wfa gprof] jobs=%lld grid=%lld thr=%d | claim+stage %.1f%% breakpoint %.1f%% base %.1f%% other %.1f%% | Mcycles total %.1f\n",
-            (long long)L.n_jobs_host, (long long)grid_blocks, threads, 100 * h[0] / tot, 100 * h[1] / tot, 100 * h[2] / tot, 100 * h[3] / tot, tot / 1e6);
-    unsigned long long e[16], ze[16] = {0};
-    TRGT_HIP_TRY(c, hipMemcpyFromSymbol(e, HIP_SYMBOL(wfa::g_wfa_eprof), sizeof e));
-    TRGT_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(wfa::g_wfa_eprof), ze, sizeof e));
-    const double lv = (double)e[10] + 1e-9;
-    fprintf(stderr, "[wfa eprof] levels %llu (%.1f per job) | cycles per level: fetch %.0f alloc %.0f strips %.0f close %.0f post %.0f heuristic %.0f | per job: init %.0f extend_only %.0f\n",
-            e[10], lv / (double)std::max<int64_t>(1, L.n_jobs_host), e[0] / lv, e[1] / lv, e[2] / lv, e[3] / lv, e[4] / lv, e[5] / lv,
-            (double)e[7] / (double)std::max<int64_t>(1, L.n_jobs_host), (double)e[8] / (double)std::max<int64_t>(1, L.n_jobs_host));
-    fprintf(stderr, "[wfa eprof] inside the strips, cycles per level: loads + recurrences %.0f, extension %.0f, termination / antidiagonal atomics %.0f, stores + range reductions %.0f\n",
-            e[11] / lv, e[12] / lv, e[13] / lv, e[14] / lv);
-  }
-  if (a.fast_wcap > 0) {
+    const int threads = plan.threads;
+    if (plan.main == WFA_MAIN_GENERIC) {
+      unsigned long long h[8], z[8] = {0};
+      TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
+      TRGT_HIP_TRY(c, hipMemcpyFromSymbol(h, HIP_SYMBOL(wfa::g_wfa_gprof), sizeof h));
+      TRGT_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(wfa::g_wfa_gprof), z, sizeof h));
+      const double tot = (double)(h[0] + h[1] + h[2] + h[3]) + 1e-9;
+      fprintf(stderr, "[wfa gprof] jobs=%lld grid=%lld thr=%d | claim+stage %.1f%% breakpoint %.1f%% base %.1f%% other %.1f%% | Mcycles total %.1f\n",
+              (long long)L.n_jobs_host, (long long)grid_blocks, threads, 100 * h[0] / tot, 100 * h[1] / tot, 100 * h[2] / tot, 100 * h[3] / tot, tot / 1e6);
+      unsigned long long e[16], ze[16] = {0};
+      TRGT_HIP_TRY(c, hipMemcpyFromSymbol(e, HIP_SYMBOL(wfa::g_wfa_eprof), sizeof e));
+      TRGT_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(wfa::g_wfa_eprof), ze, sizeof e));
+      const double lv = (double)e[10] + 1e-9;
+      fprintf(stderr, "[wfa eprof] levels %llu (%.1f per job) | cycles per level: fetch %.0f alloc %.0f strips %.0f close %.0f post %.0f heuristic %.0f | per job: init %.0f extend_only %.0f\n",
+              e[10], lv / (double)std::max<int64_t>(1, L.n_jobs_host), e[0] / lv, e[1] / lv, e[2] / lv, e[3] / lv, e[4] / lv, e[5] / lv,
+              (double)e[7] / (double)std::max<int64_t>(1, L.n_jobs_host), (double)e[8] / (double)std::max<int64_t>(1, L.n_jobs_host));
+      fprintf(stderr, "[wfa eprof] inside the strips, cycles per level: loads + recurrences %.0f, extension %.0f, termination / antidiagonal atomics %.0f, stores + range reductions %.0f\n",
+              e[11] / lv, e[12] / lv, e[13] / lv, e[14] / lv);
+      return TRGT_OK;
+    }
     unsigned long long h[32], lv[32], z[32] = {0};
     TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
     TRGT_HIP_TRY(c, hipMemcpyFromSymbol(h, HIP_SYMBOL(wfa::g_wfa_prof), sizeof h));
@@ -813,9 +773,31 @@ int wfa_launch(trgt_hip_ctx* c, const trgt_wfa_params& p, const WfaLaunch& L) {
       const double t = (double)(q[0] + q[1] + q[2] + q[3]) + 1e-9;
       fprintf(stderr, "[wfa prof]   wave %d: barrier %.1f%% prologue %.1f%% strips %.1f%% record %.1f%%\n", w, 100 * q[0] / t, 100 * q[1] / t, 100 * q[2] / t, 100 * q[3] / t);
     }
-  }
 #endif
-  c->last_wfa_cells_dev = d_cells;
+    return TRGT_OK;
+  }
+};
+
+}  // namespace
+
+int wfa_launch(trgt_hip_ctx* c, const trgt_wfa_params& p, const WfaLaunch& L) {
+  WfaCall w(c, p, L);
+  int rc;
+  if ((rc = w.make_plan()) ||
+      (rc = w.take_buffers()))
+    return rc;
+  w.fill_args();
+  KTimer t(c, L.timer_slot);
+  if ((rc = w.size_main_grid()) ||
+      (rc = w.lean_front()) ||
+      (rc = w.arena_front()) ||
+      (rc = w.launch_main()))
+    return rc;
+  t.stop(0);
+  if ((rc = w.debug_report()) ||
+      (rc = w.prof_readback()))
+    return rc;
+  c->last_wfa_cells_dev = w.d_cells;
   return TRGT_OK;
 }
 
@@ -836,69 +818,66 @@ __global__ void cigar_pack_kernel(const uint32_t* __restrict__ cigar, const JobD
 }
 }  // namespace
 
-// trgt_wfa_batch proper.  packed != nullptr: the caller wants the run-length CIGARs as one dense array (job j =
+// trgt_wfa_batch proper.  io.packed != nullptr: the caller wants the run-length CIGARs as one dense array (job j =
 // packed->data[packed->off[j] .. packed->off[j + 1])) instead of the worst-case-sized slots of the public ABI -- the internal
 // callers (consensus alignments of trgt_locus_batch) read a few runs per job, not plen + tlen + 1.
-int wfa_batch_impl(trgt_hip_ctx* c, const trgt_wfa_params* p, int64_t n_jobs, const uint8_t* seqs, const uint64_t* pat_off,
-                   const uint32_t* pat_len, const uint64_t* txt_off, const uint32_t* txt_len, int32_t* status, int32_t* score,
-                   int32_t* n_match, uint32_t* span4, uint32_t* cigar, const uint64_t* cigar_off, uint32_t* cigar_len, uint8_t* ops,
-                   const uint64_t* ops_off, uint32_t* ops_len, PackedCigars* packed, const std::function<int()>* while_running,
-                   WfaOnDevice* on_device) {
+int wfa_batch_impl(trgt_hip_ctx* c, const trgt_wfa_params* p, const WfaBatchIO& io) {
   if (!c) return TRGT_ERR_INVALID;
-  if (!p || n_jobs < 0 || (n_jobs > 0 && (!seqs || !pat_off || !pat_len || !txt_off || !txt_len)))
+  uint32_t* cigar_len = io.cigar_len;  // (a packed result reads the lengths into a vector of its own)
+  if (!p || io.n_jobs < 0 || (io.n_jobs > 0 && (!io.seqs || !io.pat_off || !io.pat_len || !io.txt_off || !io.txt_len)))
     return fail(c, TRGT_ERR_INVALID, "trgt_wfa_batch: null argument");
-  if ((cigar && (!cigar_off || !cigar_len)) || (ops && (!ops_off || !ops_len)))
+  if ((io.cigar && (!io.cigar_off || !cigar_len)) || (io.ops && (!io.ops_off || !io.ops_len)))
     return fail(c, TRGT_ERR_INVALID, "trgt_wfa_batch: cigar/ops need their offset and length arrays");
-  if (packed) { packed->data.clear(); packed->off.assign((size_t)n_jobs + 1, 0); }
-  if (n_jobs == 0) return TRGT_OK;
+  if (io.packed) { io.packed->data.clear(); io.packed->off.assign((size_t)io.n_jobs + 1, 0); }
+  if (io.n_jobs == 0) return TRGT_OK;
   const bool tl_on = c->knobs.timeline;
   const auto tl0 = std::chrono::steady_clock::now();
 #define WTL(name) do { if (tl_on) fprintf(stderr, "[tl]   wfa_batch %-18s +%6.2f ms\n", name, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count()); } while (0)
-  if (n_jobs > 0xFFFFFFF0ll) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_wfa_batch: too many jobs");
+  if (io.n_jobs > 0xFFFFFFF0ll) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_wfa_batch: too many jobs");
   TRGT_HIP_TRY(c, hipSetDevice(c->device));
-  std::vector<JobDev> jobs((size_t)n_jobs);
+  std::vector<JobDev> jobs((size_t)io.n_jobs);
   WfaLaunch L;
   uint64_t seq_total = 0, cigar_total = 0, ops_total = 0;
-  for (int64_t j = 0; j < n_jobs; ++j) {
+  for (int64_t j = 0; j < io.n_jobs; ++j) {
     JobDev& jd = jobs[(size_t)j];
-    jd.pat_off = pat_off[j]; jd.txt_off = txt_off[j]; jd.pat_len = pat_len[j]; jd.txt_len = txt_len[j]; jd.out_index = (uint32_t)j;
-    jd.cigar_off = cigar ? cigar_off[j] : 0; jd.ops_off = ops ? ops_off[j] : 0;
-    if (packed || on_device) { jd.cigar_off = cigar_total; cigar_total += (uint64_t)pat_len[j] + txt_len[j] + 1; }
-    L.max_plen = std::max<int64_t>(L.max_plen, pat_len[j]); L.max_tlen = std::max<int64_t>(L.max_tlen, txt_len[j]);
-    L.max_sum = std::max<int64_t>(L.max_sum, (int64_t)pat_len[j] + txt_len[j]);
-    seq_total = std::max<uint64_t>(seq_total, std::max(pat_off[j] + pat_len[j], txt_off[j] + txt_len[j]));
-    if (cigar) cigar_total = std::max<uint64_t>(cigar_total, cigar_off[j] + pat_len[j] + txt_len[j] + 1);
-    if (ops) ops_total = std::max<uint64_t>(ops_total, ops_off[j] + pat_len[j] + txt_len[j]);
+    jd.pat_off = io.pat_off[j]; jd.txt_off = io.txt_off[j]; jd.pat_len = io.pat_len[j]; jd.txt_len = io.txt_len[j]; jd.out_index = (uint32_t)j;
+    jd.cigar_off = io.cigar ? io.cigar_off[j] : 0; jd.ops_off = io.ops ? io.ops_off[j] : 0;
+    if (io.packed || io.on_device) { jd.cigar_off = cigar_total; cigar_total += (uint64_t)io.pat_len[j] + io.txt_len[j] + 1; }
+    L.max_plen = std::max<int64_t>(L.max_plen, io.pat_len[j]); L.max_tlen = std::max<int64_t>(L.max_tlen, io.txt_len[j]);
+    L.max_sum = std::max<int64_t>(L.max_sum, (int64_t)io.pat_len[j] + io.txt_len[j]);
+    seq_total = std::max<uint64_t>(seq_total, std::max(io.pat_off[j] + io.pat_len[j], io.txt_off[j] + io.txt_len[j]));
+    if (io.cigar) cigar_total = std::max<uint64_t>(cigar_total, io.cigar_off[j] + io.pat_len[j] + io.txt_len[j] + 1);
+    if (io.ops) ops_total = std::max<uint64_t>(ops_total, io.ops_off[j] + io.pat_len[j] + io.txt_len[j]);
   }
   if (L.max_sum > (1 << 27)) return fail(c, TRGT_ERR_UNSUPPORTED, "trgt_wfa_batch: sequences too long");
   int rc;
   const uint8_t* d_seq = nullptr;
   WTL("jobs built");
-  if ((rc = dev_in(c, S_WFA_SEQ, seqs, (size_t)seq_total, &d_seq))) return rc;
+  if ((rc = dev_in(c, S_WFA_SEQ, io.seqs, (size_t)seq_total, &d_seq))) return rc;
   WTL("sequences uploaded");
   void* d_jobs = nullptr;
   if ((rc = dev_get(c, S_WFA_JOBS, jobs.size() * sizeof(JobDev), &d_jobs))) return rc;
   if ((rc = h2d_small(c, d_jobs, jobs.data(), jobs.size() * sizeof(JobDev), c->stream, S_WFA_JOBS))) return rc;
   DevOut<int32_t> o_status, o_score, o_nm; DevOut<uint32_t> o_span, o_cigar, o_clen, o_olen; DevOut<uint8_t> o_ops;
   std::vector<uint32_t> h_clen;
-  if (packed || on_device) {  // device-only CIGAR slots; the lengths come back first (packed) or not at all (on_device)
+  if (io.packed || io.on_device) {  // device-only CIGAR slots; the lengths come back first (packed) or not at all (on_device)
     void* d = nullptr;
     if ((rc = dev_get(c, S_WFA_CIGAR, (size_t)cigar_total * 4, &d))) return rc;
     o_cigar.dev = (uint32_t*)d;
-    if (packed) { h_clen.resize((size_t)n_jobs); cigar_len = h_clen.data(); }
+    if (io.packed) { h_clen.resize((size_t)io.n_jobs); cigar_len = h_clen.data(); }
   }
-  if ((rc = o_status.init(c, S_WFA_STATUS, status, (size_t)n_jobs)) || (rc = o_score.init(c, S_WFA_SCORE, score, (size_t)n_jobs)) ||
-      (rc = o_nm.init(c, S_WFA_NMATCH, n_match, (size_t)n_jobs)) || (rc = o_span.init(c, S_WFA_SPAN, span4, (size_t)n_jobs * 4)) ||
-      (!packed && !on_device && (rc = o_cigar.init(c, S_WFA_CIGAR, cigar, (size_t)cigar_total))) || (rc = o_clen.init(c, S_WFA_CLEN, cigar_len, (size_t)n_jobs)) ||
-      (rc = o_ops.init(c, S_WFA_OPS, ops, (size_t)ops_total)) || (rc = o_olen.init(c, S_WFA_OLEN, ops_len, (size_t)n_jobs)))
+  if ((rc = o_status.init(c, S_WFA_STATUS, io.status, (size_t)io.n_jobs)) || (rc = o_score.init(c, S_WFA_SCORE, io.score, (size_t)io.n_jobs)) ||
+      (rc = o_nm.init(c, S_WFA_NMATCH, io.n_match, (size_t)io.n_jobs)) || (rc = o_span.init(c, S_WFA_SPAN, io.span4, (size_t)io.n_jobs * 4)) ||
+      (!io.packed && !io.on_device && (rc = o_cigar.init(c, S_WFA_CIGAR, io.cigar, (size_t)cigar_total))) || (rc = o_clen.init(c, S_WFA_CLEN, cigar_len, (size_t)io.n_jobs)) ||
+      (rc = o_ops.init(c, S_WFA_OPS, io.ops, (size_t)ops_total)) || (rc = o_olen.init(c, S_WFA_OLEN, io.ops_len, (size_t)io.n_jobs)))
     return rc;
-  if (on_device && !o_clen.dev) {  // (no host destination: a device-only array)
+  if (io.on_device && !o_clen.dev) {  // (no host destination: a device-only array)
     void* d = nullptr;
-    if ((rc = dev_get(c, S_WFA_CLEN, (size_t)n_jobs * 4, &d))) return rc;
+    if ((rc = dev_get(c, S_WFA_CLEN, (size_t)io.n_jobs * 4, &d))) return rc;
     o_clen.dev = (uint32_t*)d;
   }
-  if (on_device) { on_device->jobs = (const JobDev*)d_jobs; on_device->cigar = o_cigar.dev; on_device->cigar_len = o_clen.dev; on_device->seqs = d_seq; }
-  L.jobs_dev = (const JobDev*)d_jobs; L.n_jobs_host = n_jobs; L.n_jobs_dev = nullptr;
+  if (io.on_device) { io.on_device->jobs = (const JobDev*)d_jobs; io.on_device->cigar = o_cigar.dev; io.on_device->cigar_len = o_clen.dev; io.on_device->seqs = d_seq; }
+  L.jobs_dev = (const JobDev*)d_jobs; L.n_jobs_host = io.n_jobs; L.n_jobs_dev = nullptr;
   L.buffer_set = 1;  // trgt_locus_batch runs consensus alignments next to a flank-location launch (set 0) of a later chunk
   L.pat_base = d_seq; L.txt_base = d_seq;
   L.status = o_status.dev; L.score = o_score.dev; L.n_match = o_nm.dev; L.span4 = o_span.dev; L.cigar = o_cigar.dev;
@@ -907,7 +886,7 @@ int wfa_batch_impl(trgt_hip_ctx* c, const trgt_wfa_params* p, int64_t n_jobs, co
   if ((rc = wfa_launch(c, *p, L))) return rc;
   WTL("launched");
   // host work of the caller goes here: the copies below end in pageable memory, i.e. they block until the kernel is done
-  if (while_running && *while_running) { const int wrc = (*while_running)(); if (wrc) { (void)trgt::stream_wait(c, c->stream); return wrc; } }
+  if (io.while_running && *io.while_running) { const int wrc = (*io.while_running)(); if (wrc) { (void)trgt::stream_wait(c, c->stream); return wrc; } }
   if ((rc = o_status.finish(c)) || (rc = o_score.finish(c)) || (rc = o_nm.finish(c)) || (rc = o_span.finish(c)) ||
       (rc = o_cigar.finish(c)) || (rc = o_clen.finish(c)) || (rc = o_ops.finish(c)) || (rc = o_olen.finish(c)))
     return rc;
@@ -917,19 +896,19 @@ int wfa_batch_impl(trgt_hip_ctx* c, const trgt_wfa_params* p, int64_t n_jobs, co
   { const int d2h_rc = trgt::d2h(c, &cells, cells_dev, 8, my_stream); if (d2h_rc) return d2h_rc; }
   TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
   if (c->timing) c->k_cells[TRGT_K_WFA] += (int64_t)cells;
-  if (packed) {
+  if (io.packed) {
     uint64_t total = 0;
-    for (int64_t j = 0; j < n_jobs; ++j) { packed->off[(size_t)j] = total; total += h_clen[(size_t)j]; }
-    packed->off[(size_t)n_jobs] = total;
-    packed->data.resize((size_t)total);
+    for (int64_t j = 0; j < io.n_jobs; ++j) { io.packed->off[(size_t)j] = total; total += h_clen[(size_t)j]; }
+    io.packed->off[(size_t)io.n_jobs] = total;
+    io.packed->data.resize((size_t)total);
     if (total) {
       void *d_poff = nullptr, *d_packed = nullptr;
-      if ((rc = dev_get(c, S_WFA_POFF, (size_t)n_jobs * 8, &d_poff)) || (rc = dev_get(c, S_WFA_PACKED, (size_t)total * 4, &d_packed))) return rc;
-      if ((rc = h2d_small(c, d_poff, packed->off.data(), (size_t)n_jobs * 8, c->stream, S_WFA_POFF))) return rc;
-      hipLaunchKernelGGL(cigar_pack_kernel, dim3((unsigned)((n_jobs + 3) / 4)), dim3(256), 0, c->stream, (const uint32_t*)o_cigar.dev,
-                         (const JobDev*)d_jobs, (const uint32_t*)o_clen.dev, (const uint64_t*)d_poff, (uint32_t*)d_packed, (uint64_t)n_jobs);
+      if ((rc = dev_get(c, S_WFA_POFF, (size_t)io.n_jobs * 8, &d_poff)) || (rc = dev_get(c, S_WFA_PACKED, (size_t)total * 4, &d_packed))) return rc;
+      if ((rc = h2d_small(c, d_poff, io.packed->off.data(), (size_t)io.n_jobs * 8, c->stream, S_WFA_POFF))) return rc;
+      hipLaunchKernelGGL(cigar_pack_kernel, dim3((unsigned)((io.n_jobs + 3) / 4)), dim3(256), 0, c->stream, (const uint32_t*)o_cigar.dev,
+                         (const JobDev*)d_jobs, (const uint32_t*)o_clen.dev, (const uint64_t*)d_poff, (uint32_t*)d_packed, (uint64_t)io.n_jobs);
       TRGT_HIP_TRY(c, hipGetLastError());
-      { const int d2h_rc = trgt::d2h(c, packed->data.data(), d_packed, (size_t)total * 4, c->stream); if (d2h_rc) return d2h_rc; }
+      { const int d2h_rc = trgt::d2h(c, io.packed->data.data(), d_packed, (size_t)total * 4, c->stream); if (d2h_rc) return d2h_rc; }
       TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
     }
   }
@@ -942,6 +921,9 @@ extern "C" int trgt_wfa_batch(trgt_hip_ctx* c, const trgt_wfa_params* p, int64_t
                               const uint32_t* txt_len, int32_t* status, int32_t* score, int32_t* n_match, uint32_t* span4,
                               uint32_t* cigar, const uint64_t* cigar_off, uint32_t* cigar_len, uint8_t* ops,
                               const uint64_t* ops_off, uint32_t* ops_len) {
-  return trgt::wfa_batch_impl(c, p, n_jobs, seqs, pat_off, pat_len, txt_off, txt_len, status, score, n_match, span4, cigar, cigar_off,
-                              cigar_len, ops, ops_off, ops_len, nullptr);
+  trgt::WfaBatchIO io;
+  io.n_jobs = n_jobs; io.seqs = seqs; io.pat_off = pat_off; io.pat_len = pat_len; io.txt_off = txt_off; io.txt_len = txt_len;
+  io.status = status; io.score = score; io.n_match = n_match; io.span4 = span4;
+  io.cigar = cigar; io.cigar_off = cigar_off; io.cigar_len = cigar_len; io.ops = ops; io.ops_off = ops_off; io.ops_len = ops_len;
+  return trgt::wfa_batch_impl(c, p, io);
 }

@@ -22,16 +22,11 @@ namespace wfa {
 
 constexpr int32_t OFF_NULL = INT32_MIN / 2;  // WAVEFRONT_OFFSET_NULL
 constexpr uint32_t NOBASE = 0xFFFFFFFFu;
-constexpr int RING = 32;                      // LDS mirror depth of wavefront descriptors (>= max_score_scope)
-constexpr int KBIAS = 1 << 30;
+constexpr int KBIAS = 1 << 30;  // (RING, WfDesc and Pen: wfa_types.hpp, shared with the launch plan)
 enum { CM = 0, CI1 = 1, CI2 = 2, CD1 = 3, CD2 = 4 };
 enum { ST_OK = 0, ST_END_REACHED = 1, ST_END_UNREACHABLE = 2, ST_OOM = 3 };
 enum { M_INDEL = 0, M_EDIT = 1, M_LINEAR = 2, M_AFFINE = 3, M_AFFINE2P = 4 };
 enum { I_FWD = 0, I_REV = 1, I_UNI = 2 };
-
-struct WfDesc { int lo, hi, lo_alloc; uint32_t base; };  // base == NOBASE: wavefront pointer is NULL; lo > hi: ->null
-
-struct Pen { int metric, x, o1, e1, o2, e2, scope, ncomp; };
 
 struct KParams {  // by-value kernel argument
   Pen pen;

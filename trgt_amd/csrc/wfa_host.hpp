@@ -3,14 +3,9 @@
 #include <functional>
 #include <vector>
 #include "common.hpp"
+#include "wfa_types.hpp"  // JobDev
 
 namespace trgt {
-
-struct JobDev {  // one alignment: pattern / text inside pat_base / txt_base, output slots
-  uint64_t pat_off, txt_off, cigar_off, ops_off;
-  uint32_t pat_len, txt_len, out_index, pad;
-};
-
 
 // A read shorter than this cannot contain the repeat of its locus with both flanks around it (the longest read of the locus is
 // the yardstick): at least one of its flank alignments ends with a long gap, i.e. runs through many score levels.
@@ -135,12 +130,18 @@ struct PackedCigars { std::vector<uint32_t> data; std::vector<uint64_t> off; };
 // ... or left in HBM for a kernel of the caller (the consensus column voting): job list, CIGAR slots (job j at cigar[jobs[j].cigar_off ..],
 // cigar_len[jobs[j].out_index] entries) and the sequence blob, valid until the next alignment batch of the context
 struct WfaOnDevice { const JobDev* jobs = nullptr; const uint32_t* cigar = nullptr; const uint32_t* cigar_len = nullptr; const uint8_t* seqs = nullptr; };
-// trgt_wfa_batch with an optional dense CIGAR result (packed != nullptr replaces cigar / cigar_off / cigar_len).
-int wfa_batch_impl(trgt_hip_ctx* c, const trgt_wfa_params* p, int64_t n_jobs, const uint8_t* seqs, const uint64_t* pat_off,
-                   const uint32_t* pat_len, const uint64_t* txt_off, const uint32_t* txt_len, int32_t* status, int32_t* score,
-                   int32_t* n_match, uint32_t* span4, uint32_t* cigar, const uint64_t* cigar_off, uint32_t* cigar_len, uint8_t* ops,
-                   const uint64_t* ops_off, uint32_t* ops_len, PackedCigars* packed,
-                   const std::function<int()>* while_running = nullptr,  // host work to do between the launch and the wait
-                   WfaOnDevice* on_device = nullptr);  // != nullptr: run-length CIGARs are produced but stay on the device
+// The caller's arrays of an alignment batch, as trgt_wfa_batch (include/trgt_hip.h) documents them, and what the internal callers add.
+struct WfaBatchIO {
+  int64_t n_jobs = 0; const uint8_t* seqs = nullptr;
+  const uint64_t* pat_off = nullptr; const uint32_t* pat_len = nullptr; const uint64_t* txt_off = nullptr; const uint32_t* txt_len = nullptr;
+  int32_t* status = nullptr; int32_t* score = nullptr; int32_t* n_match = nullptr; uint32_t* span4 = nullptr;
+  uint32_t* cigar = nullptr; const uint64_t* cigar_off = nullptr; uint32_t* cigar_len = nullptr;
+  uint8_t* ops = nullptr; const uint64_t* ops_off = nullptr; uint32_t* ops_len = nullptr;
+  PackedCigars* packed = nullptr;                        // the run-length CIGARs as one dense array (replaces cigar / cigar_off / cigar_len)
+  const std::function<int()>* while_running = nullptr;  // host work to do between the launch and the wait
+  WfaOnDevice* on_device = nullptr;                      // run-length CIGARs are produced but stay on the device
+};
+// trgt_wfa_batch proper
+int wfa_batch_impl(trgt_hip_ctx* c, const trgt_wfa_params* p, const WfaBatchIO& io);
 
 }  // namespace trgt
