@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from bamtools import read_bam_records, write_bam, write_fasta
+from writer_results import handmade as _handmade
 
 pytestmark = pytest.mark.gpu
 
@@ -43,34 +44,6 @@ def _same_files(a, b):
             for k in p:
                 assert p[k] == q[k], (i, p["name"], k, p[k], q[k])
     assert x == y, "the records agree, the BGZF blocks do not"
-
-
-def _handmade(b, rng, F, keep=0.85, bad=0.0):
-    """Results as a caller may hand them over: per locus a random subset of the reads ranked in random order, spans that leave F bases on
-    both sides; a share `bad` of them gets a span the host path skips (span_start < F, span_end + F > read_len, span_end > read_len)."""
-    from trgt_amd import locus
-    out = locus.BatchOutputs(b)
-    out.span_start[:] = -1; out.span_end[:] = -1; out.read_rank[:] = -1; out.classification[:] = -1
-    lrb = b["locus_read_begin"]
-    n_bad = 0
-    for l in range(b["n_loci"]):
-        rs = [r for r in range(int(lrb[l]), int(lrb[l + 1])) if rng.random() < keep]
-        rng.shuffle(rs)
-        for rank, r in enumerate(rs):
-            n = int(b["read_len"][r])
-            s = int(rng.integers(F, max(F, n - F) + 1))
-            e = int(rng.integers(s, max(s, n - F) + 1))
-            if rng.random() < bad:
-                n_bad += 1
-                kind = int(rng.integers(0, 3))
-                if kind == 0 and F > 0:
-                    s = int(rng.integers(0, F))
-                elif kind == 1:
-                    e = max(s, n - F + 1 + int(rng.integers(0, max(1, F))))
-                else:
-                    e = n + 1 + int(rng.integers(0, 5000))
-            out.span_start[r], out.span_end[r], out.read_rank[r], out.classification[r] = s, e, rank, int(rng.integers(0, 2))
-    return out, n_bad
 
 
 @pytest.fixture(scope="module")

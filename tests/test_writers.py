@@ -158,6 +158,45 @@ def test_vcf_and_spanning_bam_from_handmade_results(tmp_path):
     assert len([l for l in open(tmp_path / "wb1_6.vcf").read().splitlines() if not l.startswith("#")]) == 6
 
 
+def test_pieces_of_several_workers_come_out_in_locus_order(tmp_path):
+    """64 loci: a writer with four threads formats them on four workers (one per 16 loci), one with a single thread on one.  The files are
+    the same byte for byte, with and without write-behind, and the records are the kept reads the skip rules leave, locus by locus in
+    rank order."""
+    from trgt_amd import ingest, synth_bam, writers
+    from writer_results import handmade, two_alleles
+    ds = synth_bam.write_dataset(str(tmp_path / "ds"), n_loci=64, read_len=1500, reads_per_locus=8)
+    rd = ingest.Reader(ds["bam"], ds["fasta"])
+    b = rd.batch(ds["bed"], keep_native=True)
+    assert b["n_loci"] == 64 and not b.get("read_blob_dev")
+    F = 50
+    out, n_bad = handmade(b, np.random.default_rng(64), F, bad=0.2)
+    assert n_bad > 20
+    two_alleles(b, out)
+    lrb, names = b["locus_read_begin"], b["read_name"]
+    files = {}
+    for threads in (1, 4):
+        for wb in (0, 1):
+            vcf, bam = tmp_path / ("t%d_%d.vcf" % (threads, wb)), tmp_path / ("t%d_%d.bam" % (threads, wb))
+            w = writers.Writer(rd, vcf, bam, output_flank_len=F, threads=threads, write_behind=wb)
+            for _ in range(2):
+                w.write(b, out)
+            w.close()
+            files[threads, wb] = (open(vcf, "rb").read(), open(bam, "rb").read())
+    assert files[1, 0] == files[1, 1] == files[4, 0] == files[4, 1]
+    lines = [l for l in files[4, 1][0].decode().splitlines() if not l.startswith("#")]
+    ids = [l.split("\t")[7].split(";")[0] for l in lines]
+    assert len(lines) == 128 and ids[:64] == ids[64:] and len(set(ids)) == 64 and all(l.split("\t")[9].count("/") == 1 for l in lines)
+    want = []
+    for l in range(64):
+        ranked = sorted((int(out.read_rank[r]), r) for r in range(int(lrb[l]), int(lrb[l + 1])) if out.read_rank[r] >= 0)
+        for _, r in ranked:
+            s, e, n = int(out.span_start[r]), int(out.span_end[r]), int(b["read_len"][r])
+            if s >= F and n >= e + F and e - s + 2 * F > 0:   # write_bam.rs' flank rule and clip_bases' None
+                want.append((names[r], ids[l].split("=")[1], e - s + 2 * F))
+    got = [(g["name"], g["tags"]["TR"][1], len(g["seq"])) for g in read_bam_records(str(tmp_path / "t4_1.bam"))[2]]
+    assert got == want + want and 250 < len(want) < int((out.read_rank >= 0).sum())
+
+
 def test_write_behind_reports_a_failed_write_at_the_next_call_or_the_close(tmp_path):
     """trgt_writer_params.write_behind: what the writer's own thread runs into (here: /dev/full, every flush fails) comes back from the
     next trgt_writer_write or from trgt_writer_close, never silently"""

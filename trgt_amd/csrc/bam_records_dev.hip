@@ -9,14 +9,15 @@
 //   fill_kernel    one workgroup (a wave) per record writes it: dword stores wherever four bytes of the stream are aligned, byte stores at the edges
 // The stream is the writer's carried tail (less than one BGZF block, uploaded) followed by the records; finish() has its full 0xFF00-byte
 // blocks checksummed (crc32_blocks_kernel of ingest_dev.hip) and deflated (deflate_dev.hip) where they lie and brings back payloads,
-// lengths, CRCs and the tail -- or, without a deflate device, the stream itself for zlib.  The record bytes are what writers.hip's
-// format_locus produces, byte for byte; the three errors it reports are flags here and the host path redoes such a batch.
+// lengths, CRCs and the tail -- or, without a deflate device, the stream itself for zlib.  The record bytes are what writer_format.hpp's
+// bam_record produces, byte for byte; the three errors it reports are flags here and the host path redoes such a batch.
 #include <cmath>
 #include <cstring>
 #include <memory>
 
 #include "common.hpp"
 #include "bam_records_dev.hpp"
+#include "bgzf_block.hpp"
 #include "ingest_dev.hpp"
 
 namespace trgt {
@@ -436,7 +437,7 @@ int finish(Engine* e, trgt_hip_ctx* defl, uint64_t min_dev_blocks, Finished& out
   // ---- the blocks the device declined go to zlib: their bytes come back
   e->raw_at.assign(nb, ~0ull);
   uint64_t n_raw = 0, pay = 0;
-  for (uint64_t k = 0; k < nb; ++k) { if (len[k] > 0 && len[k] + 26u <= 0x10000u) pay += len[k]; else e->raw_at[k] = n_raw++ * BLOCK; }
+  for (uint64_t k = 0; k < nb; ++k) { if (bgzf_payload_fits(len[k])) pay += len[k]; else e->raw_at[k] = n_raw++ * BLOCK; }
   if (n_raw) {
     // (dn_pin may move: everything read so far is re-established from the new pointer only when it did not grow -- so the room is asked for up front)
     if (e->dn_pin.cap < a_raw + n_raw * BLOCK + 64) {
