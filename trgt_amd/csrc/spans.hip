@@ -147,7 +147,7 @@ __global__ void __launch_bounds__(256) flank_scan_kernel(const ScanArgs a) {
 // full run's termination test and back-trace would read -- bit for bit -- PROVIDED its penalty turns out <= S0 (window_check_kernel;
 // otherwise, or when the occurrences are spread too widely or there are none, the whole read is aligned as before).  Offsets of a
 // windowed run never exceed those of the full run (fewer sources under the max), so it cannot end early either.
-// One wavefront; every lane returns the same kmin / kmax (kmin > kmax: no occurrence).
+// One wavefront; kmin / kmax are wave-uniform scalars (kmin > kmax: no occurrence).
 constexpr int WIN_SEGMENTS_DEFAULT = 8;  // (4, 6 and 8 are instantiated; TRGT_WIN_SEGMENTS picks another one.  Measured on the 10k-locus
                                          // batch, search + alignments: 4 -> 3.19 ms, 6 -> 3.00, 8 -> 2.90, 10 -> 2.97, 12 -> 3.02)
 // An "occurrence" is a match of the first TWELVE bases of a segment (all from registers: no memory round trip per candidate).  That
@@ -199,40 +199,45 @@ __device__ __forceinline__ void piece_window_heads(const uint8_t* __restrict__ r
         }
       }
     }
-    // The first FOUR bytes at every candidate start decide whether a segment is looked at more closely in this round (a 32-bit
-    // compare per position and segment; the other eight bytes are formed only then).  This kernel is bound by instruction issue:
-    // twelve bytes at every position and 64-bit compares were 48 byte-aligns and 128 double-width compares per round.
-    uint32_t lo[16];
+    // The first FOUR bytes at every candidate start decide whether a segment is looked at more closely in this round: a 32-bit
+    // compare per position and segment, kept as a BALLOT (the compares land in SGPR pairs anyway).  Everything behind it is uniform
+    // over the wave: the segment is skipped when no lane has a candidate, and of its sixteen positions only those where some lane
+    // has one are verified -- a scalar compare and branch each -- against the other eight bytes, lo[s16 + 4] and lo[s16 + 8] of the
+    // 24 candidate dwords formed once per round.  The verified matches are balloted again; their lowest and highest lane give the
+    // smallest and largest position of that s16 (a flank of period 16, 8, 4, 2 or 1 has several lanes there, one ballot takes them
+    // all), so kmin / kmax are scalars and nothing is reduced across lanes at the end.  With per-lane branches every seeded
+    // segment verified all sixteen positions in every lane (about 75 vector instructions, four of the bodies if-converted and
+    // unconditional), and a six-step butterfly over kmin / kmax followed (46 more, twelve LDS round trips per job): 1 234 vector
+    // instructions per job then, 659 now -- for 9 % of the kernel's time, the rest is the job's chain of loads and scalar work
+    // (DESIGN.md section 5).  The compiler flattens a uniform `if` whose body it can speculate -- a plain `if (m[s16] != 0)` had
+    // all sixteen bodies if-converted, 175 vector instructions per segment -- so each body begins with an empty `asm volatile`,
+    // which keeps the branch (as in wfa_band.hip; read the listing after a change: about 22 vector instructions per seeded segment).
+    uint32_t lo[24];
 #pragma unroll
-    for (int s16 = 0; s16 < 16; ++s16) {
-      const int d = s16 >> 2, sh = s16 & 3;
-      lo[s16] = sh == 0 ? w[d] : __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
+    for (int j = 0; j < 24; ++j) {
+      const int d = j >> 2, sh = j & 3;
+      lo[j] = sh == 0 ? w[d] : __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
     }
 #pragma unroll
     for (int i = 0; i < WIN_SEGMENTS; ++i) {
       const uint32_t h_lo = (uint32_t)h[i], h_hi = (uint32_t)(h[i] >> 32);
-      bool any = false;
+      unsigned long long m[16], any = 0ull;
 #pragma unroll
-      for (int s16 = 0; s16 < 16; ++s16) any |= lo[s16] == h_lo;
-      if (__ballot(any) == 0ull) continue;  // (uniform; taken but for the round that holds an occurrence of this segment, or four of its bases by chance)
+      for (int s16 = 0; s16 < 16; ++s16) { m[s16] = __ballot(lo[s16] == h_lo); any |= m[s16]; }
+      if (any == 0ull) continue;  // (taken but for the round that holds an occurrence of this segment, or four of its bases by chance)
 #pragma unroll
       for (int s16 = 0; s16 < 16; ++s16) {
-        if (lo[s16] == h_lo) {
-          const int d = s16 >> 2, sh = s16 & 3;
-          const uint32_t hi = sh == 0 ? w[d + 1] : __builtin_amdgcn_alignbyte(w[d + 2], w[d + 1], sh);
-          const uint32_t w3 = sh == 0 ? w[d + 2] : __builtin_amdgcn_alignbyte(w[d + 3], w[d + 2], sh);
-          if (hi == h_hi && w3 == h3[i] && off + s16 <= last) {
-            const int k = off + s16 - i * q;
-            kmin = k < kmin ? k : kmin; kmax = k > kmax ? k : kmax;
+        if (m[s16] != 0ull) {
+          asm volatile("" ::: "memory");  // (not speculatable: the branch stays a branch)
+          const unsigned long long full = m[s16] & __ballot(lo[s16 + 4] == h_hi && lo[s16 + 8] == h3[i] && off + s16 <= last);
+          if (full != 0ull) {
+            const int k0 = base + s16 - i * q;
+            const int k_lo = k0 + 16 * (int)__builtin_ctzll(full), k_hi = k0 + 16 * (63 - (int)__builtin_clzll(full));
+            kmin = k_lo < kmin ? k_lo : kmin; kmax = k_hi > kmax ? k_hi : kmax;
           }
         }
       }
     }
-  }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const int a = __shfl_xor(kmin, d), b = __shfl_xor(kmax, d);
-    kmin = a < kmin ? a : kmin; kmax = b > kmax ? b : kmax;
   }
   kmin_out = kmin; kmax_out = kmax;
 }
