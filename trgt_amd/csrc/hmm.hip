@@ -569,22 +569,7 @@ __global__ void hmm_viterbi_kernel(const HmmJobDev* __restrict__ jobs, const Hmm
   hmm_sync_mem(sync_n);  // (also orders the zeroing of the motif counts above before thread 0 counts into them)
   // traceback word of my state: kind (0 outside any block, 1 block start, 2 block end, 3 skip state, 4 match, 5 insertion,
   // 6 deletion) | emits << 3 | block << 8 | expected motif base << 16 (match states)
-  if (act) {
-    const int blk = (int)l_block[st];
-    uint32_t kind = 0, expected = 0;
-    if (blk >= 0) {
-      const int bstart = (int)l_blocks[0 * nb + blk], bend = (int)l_blocks[1 * nb + blk];
-      if (st == bstart) kind = 1;
-      else if (st == bend) kind = 2;
-      else if (blk == nb - 1) kind = 3;
-      else {
-        const int mlen = (int)l_blocks[2 * nb + blk], off = st - bstart - 1, k = off / mlen;
-        kind = 4u + (uint32_t)k;
-        if (k == 0) expected = motif_bytes[l_blocks[3 * nb + blk] + off];
-      }
-    }
-    l_info[st] = kind | ((uint32_t)(l_flags[st] & 1) << 3) | ((uint32_t)(blk & 0xFF) << 8) | (expected << 16);
-  }
+  if (act) l_info[st] = hmm_state_info(st, (int)l_block[st], nb, l_blocks, motif_bytes, l_flags[st]);
   // roles in the evaluation of the silent states of a column (see the fill loop)
   const int my_blk = act ? (int)l_block[st] : -1;
   const bool role_end = act && my_blk >= 0 && st == (int)l_blocks[1 * nb + my_blk];
@@ -1128,6 +1113,7 @@ __global__ void hmm_viterbi_kernel(const HmmJobDev* __restrict__ jobs, const Hmm
 }
 
 #include "hmm_ppl.hpp"
+#include "hmm_trace_ppl.hpp"
 #include "hmm_big.hpp"
 
 // ---- trace-back of LONG alleles on many waves (DESIGN_HISTORY 7.3: "block-wise composed trace-back").  The chase of the back-pointers

@@ -144,6 +144,28 @@ static void hmm_launch_viterbi(dim3 grid, dim3 block, size_t lds, hipStream_t ls
 template <int SUB, bool ONE_WAVE>
 static HmmViterbiFn hmm_viterbi_fn() { return {(const void*)hmm_viterbi_kernel<SUB, ONE_WAVE>, hmm_launch_viterbi<SUB, ONE_WAVE>}; }
 
+// The trace-back of a class 0 whose alleles were all filled in packed rows of 8 / 16 lanes: hmm_trace_ppl_kernel<G>, 64 / G alleles per
+// wave; a class with both widths takes hmm_trace_ppl_both_kernel, one launch whose workgroups walk the list once per width (each pass
+// skips the other's jobs, as the fills do).
+// TRGT_HMM_TRACE_WIDE=1 (developer builds): hmm_viterbi_kernel<32, .> with its fill skipped, two alleles per wave, as before.
+static inline bool hmm_trace_packed(const trgt_hip_ctx* c, const HmmClassLaunch& a) {
+  return a.cls == 0 && a.ppl_mask != 0 && (a.ppl_mask & ~3u) == 0 && !c->knobs.hmm_ppl_wide && !c->knobs.hmm_no_ppl && !c->knobs.hmm_trace_wide &&
+         a.maxS <= (uint32_t)HMM_TP_MAX_STATES && a.maxnb <= (uint32_t)HMM_TP_MAX_BLOCKS;
+}
+static void hmm_launch_trace_ppl(hipStream_t ls, const HmmClassLaunch& a, uint32_t long_min, uint32_t* d_long) {
+  HmmTracePplArgs t{a.jobs, a.b.sets, a.b.model, a.b.seq, (const uint8_t*)a.b.bp, a.b.visits, a.b.path, a.b.plen, a.b.spans, a.b.nsp, a.b.cnt, a.b.pur, a.b.edit, a.b.maxd,
+                    a.nj, a.n_jobs_dev, {0u, 0u}, (int)long_min, d_long, 0u};
+  t.lds_per_job[0] = (uint32_t)hmm_trace_ppl_lds(8, (int)a.maxS, (int)a.maxnb).total;
+  t.lds_per_job[1] = (uint32_t)hmm_trace_ppl_lds(16, (int)a.maxS, (int)a.maxnb).total;
+  const uint32_t blocks8 = (a.nj + 7) / 8, blocks16 = (a.nj + 3) / 4;
+  const size_t lds8 = 8 * (size_t)t.lds_per_job[0], lds16 = 4 * (size_t)t.lds_per_job[1];
+  if ((a.ppl_mask & 3u) == 3u) {
+    t.n_blocks8 = blocks8;
+    hipLaunchKernelGGL(hmm_trace_ppl_both_kernel, dim3(blocks8 + blocks16), dim3(64), std::max(lds8, lds16), ls, t);
+  } else if (a.ppl_mask & 1u) hipLaunchKernelGGL((hmm_trace_ppl_kernel<8>), dim3(blocks8), dim3(64), lds8, ls, t);
+  else hipLaunchKernelGGL((hmm_trace_ppl_kernel<16>), dim3(blocks16), dim3(64), lds16, ls, t);
+}
+
 // The classes of a batch run next to each other: the first on the batch's stream, the others on side streams forked off it (three per
 // buffer set, in rotation) and joined back into it.  A class is bounded by its longest allele: one behind the other they add up their tails.
 static int hmm_fork_record(trgt_hip_ctx* c, int buffer_set) {  // where the side streams fork off: in front of the first class's launch
@@ -210,7 +232,11 @@ static int hmm_launch_class(trgt_hip_ctx* c, const HmmClassLaunch& a) {
   }
   if (a.ppl_mask && !a.ppl_launched &&
       (rc = hmm_launch_ppl(c, a.buffer_set ? 1 : 0, a.ordinal & 3, ls, a.ppl_mask, a.jobs, b.sets, b.model, b.seq, b.bp, hmm_ppl_one_segment(a.nj, a.n_jobs_dev)))) return rc;
-  k.launch(dim3(half ? (a.nj + 1) / 2 : a.nj), dim3(half ? 64 : 64 * a.cls), lds, ls, a, hmm_viterbi_flags(c, lds_job, a.ppl_mask, long_min_cls), d_long_cls);
+  const bool packed_trace = hmm_trace_packed(c, a);
+  if (c->knobs.debug) fprintf(stderr, "[hmm] class %u: %u jobs, trace-back by %s\n", a.cls, a.nj, packed_trace ? "hmm_trace_ppl_kernel" : "hmm_viterbi_kernel");
+  if (packed_trace) {
+    hmm_launch_trace_ppl(ls, a, long_min_cls, d_long_cls);
+  } else k.launch(dim3(half ? (a.nj + 1) / 2 : a.nj), dim3(half ? 64 : 64 * a.cls), lds, ls, a, hmm_viterbi_flags(c, lds_job, a.ppl_mask, long_min_cls), d_long_cls);
   TRGT_HIP_TRY(c, hipGetLastError());
   if (d_long_cls) {
     const size_t llds = hmm_long_lds_bytes(a.maxS, a.maxnb);

@@ -1,10 +1,12 @@
-// trgt_amd/csrc/hmm_traceback.hpp -- the trace-back code shared by hmm_viterbi_kernel, hmm_viterbi_big_kernel (hmm_big.hpp) and
-// hmm_traceback_long_kernel (included by hmm.hip ahead of the kernels; everything here is inlined into them).
+// trgt_amd/csrc/hmm_traceback.hpp -- the trace-back code shared by hmm_viterbi_kernel, hmm_trace_ppl_kernel (hmm_trace_ppl.hpp),
+// hmm_viterbi_big_kernel (hmm_big.hpp) and hmm_traceback_long_kernel (included by hmm.hip ahead of the kernels; everything here is
+// inlined into them).
 //
 // hmm_decode_steps   what up to REC noted steps of the walk mean, one lane per step: all three kernels
 // hmm_path_to_front, hmm_store_purity   the end of a job's trace-back: all three kernels
 // hmm_trace_rounds, hmm_decode_visits   the serial chase (thread 0 follows the back-pointers through LDS-staged columns, the lanes of
-//                    the job's first wave decode the noted steps) and the decode of the motif visits by thread 0: the two fill kernels.
+//                    the job's first wave decode the noted steps) and the decode of the motif visits by thread 0: the two fill kernels
+//                    and hmm_trace_ppl_kernel, whose "threads" are the G lanes of a job's group.
 //                    (The long kernel chases on wave-uniform values and decodes the visits on all its threads.)
 #pragma once
 
@@ -110,7 +112,25 @@ __device__ __forceinline__ void hmm_store_purity(const uint32_t job_index, const
   if (maxd_out) maxd_out[job_index] = mx;
 }
 
-// ---- the serial trace-back of the two fill kernels.  LDS of a job as they carve it up:
+// ---- the trace-back word of state st (l.info): kind (0 outside any block, 1 block start, 2 block end, 3 skip state, 4 match, 5 insertion,
+// 6 deletion) | emits << 3 | block << 8 | expected motif base << 16 (match states).  blk: the state's block (-1: none); blocks: [4][nb]
+__device__ __forceinline__ uint32_t hmm_state_info(const int st, const int blk, const int nb, const uint32_t* blocks, const uint8_t* motif_bytes, const uint32_t flags_st) {
+  uint32_t kind = 0, expected = 0;
+  if (blk >= 0) {
+    const int bstart = (int)blocks[0 * nb + blk], bend = (int)blocks[1 * nb + blk];
+    if (st == bstart) kind = 1;
+    else if (st == bend) kind = 2;
+    else if (blk == nb - 1) kind = 3;
+    else {
+      const int mlen = (int)blocks[2 * nb + blk], off = st - bstart - 1, k = off / mlen;
+      kind = 4u + (uint32_t)k;
+      if (k == 0) expected = motif_bytes[blocks[3 * nb + blk] + off];
+    }
+  }
+  return kind | ((flags_st & 1u) << 3) | ((uint32_t)(blk & 0xFF) << 8) | (expected << 16);
+}
+
+// ---- the serial trace-back of the fill kernels and of hmm_trace_ppl_kernel.  LDS of a job as they carve it up:
 struct HmmTraceLds {
   int* tb;                  // the walk's state, shared between the walker (thread 0) and the stagers: the words TB_*
   const uint32_t* inst;     // [S][4] hmm_pred_entry
@@ -142,7 +162,10 @@ __device__ __forceinline__ void hmm_trace_init(int* tb, const int S, const int L
 // bases of the visit a block start closes): a lane shift and a ballot.
 // PPL: the rows may be those of the position-per-lane fill, one byte per lane of the job's group (`packed`; TB_LOC is carried then);
 // else they are one byte per state, `packed` is ignored, and the run end's back-pointer is guarded against a column no path goes through.
-template <int REC, bool PPL, class Sync>
+// VIS: motif visits the job keeps in LDS (l.vis); the others go to its workspace at their own index.
+// CHUNK: 0, or (a job of REC lanes with packed rows of REC bytes) the most cols_per_chunk can be: a chunk is then staged with a fixed
+// number of pieces per lane, every one loaded before the first is stored.
+template <int REC, bool PPL, int VIS = HMM_VIS_LDS, int CHUNK = 0, class Sync>
 __device__ __forceinline__ void hmm_trace_rounds(const Sync sync, const int tid, const int nthr, const HmmTraceLds l, const bool packed_arg, const int rstride,
                                                  const int cols_per_chunk, const int S, const int nb, const int L, const uint8_t* __restrict__ seq,
                                                  const uint8_t* bp, uint32_t* g_vis, uint16_t* pbuf, const int pcap, const unsigned long long gmask) {
@@ -151,13 +174,30 @@ __device__ __forceinline__ void hmm_trace_rounds(const Sync sync, const int tid,
   while (true) {
     if (tb[TB_DONE]) break;
     const int c1 = tb[TB_IDX] + 1, c0 = packed ? (max(0, c1 - cols_per_chunk) & ~1) : max(0, c1 - cols_per_chunk);  // (rows of 8 bytes: an even column starts a 16-byte piece)
-    {
+    if constexpr (CHUNK == 0) {
       const uint4* src = reinterpret_cast<const uint4*>(bp + (size_t)c0 * rstride);
       uint4* dst = reinterpret_cast<uint4*>(l.stage);
       const int n16 = ((c1 - c0) * rstride + 15) / 16;
       for (int i = tid; i < n16; i += nthr) dst[i] = src[i];
       // ... and the symbol codes of the same columns, plus those a motif copy starting in the last of them reaches into
       for (int k = tid; k < c1 - c0 + HMM_CODE_PAD && c0 + k < L; k += nthr) l.seq[k] = (uint8_t)hmm_code(seq, c0 + k, L);
+    } else {
+      // (the same copies with REC lanes: loops of one global round trip per pass were eleven passes for the codes of 64 columns and five
+      //  for their rows; here the loads of a chunk are all in flight at once)
+      constexpr int U16 = (((CHUNK + 1) * REC + 15) / 16 + REC - 1) / REC, UC = (CHUNK + 1 + HMM_CODE_PAD + REC - 1) / REC;
+      const uint4* src = reinterpret_cast<const uint4*>(bp + (size_t)c0 * REC);
+      uint4* dst = reinterpret_cast<uint4*>(l.stage);
+      const int n16 = ((c1 - c0) * REC + 15) / 16, nc = min(c1 - c0 + HMM_CODE_PAD, L - c0);
+      uint4 r16[U16];
+      int rc[UC];
+#pragma unroll
+      for (int u = 0; u < U16; ++u) r16[u] = tid + u * REC < n16 ? src[tid + u * REC] : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+      for (int u = 0; u < UC; ++u) rc[u] = tid + u * REC < nc ? hmm_code(seq, c0 + tid + u * REC, L) : 0;
+#pragma unroll
+      for (int u = 0; u < U16; ++u) if (tid + u * REC < n16) dst[tid + u * REC] = r16[u];
+#pragma unroll
+      for (int u = 0; u < UC; ++u) if (tid + u * REC < nc) l.seq[tid + u * REC] = (uint8_t)rc[u];
     }
     auto code_at = [&](int i) -> int { return (int)l.seq[i - c0]; };
     sync.lds();
@@ -196,9 +236,9 @@ __device__ __forceinline__ void hmm_trace_rounds(const Sync sync, const int tid,
       if (tid < REC) {
         const int n = tb[TB_NREC];
         const HmmStepCarry cy{tb[TB_NPATH], tb[TB_NVISIT], tb[TB_NEXT], tb[TB_VB1]};
-        // (the first HMM_VIS_LDS visits in LDS, the others in the job's workspace at their own index)
+        // (the first VIS visits in LDS, the others in the job's workspace at their own index)
         const HmmStepSums r = hmm_decode_steps<REC>(tid, n, cy, gmask, l.rec, l.info, l.blocks, nb, l.mot, pbuf, pcap, code_at,
-                                                    [&](int nv) -> uint32_t* { return nv < HMM_VIS_LDS ? l.vis + 3 * nv : g_vis + 3 * (size_t)nv; });
+                                                    [&](int nv) -> uint32_t* { return nv < VIS ? l.vis + 3 * nv : g_vis + 3 * (size_t)nv; });
         if (tid == 0) {
           int np = cy.np + n;
           if (more == 2) { if (pbuf && np < pcap) pbuf[pcap - 1 - np] = 0; ++np; tb[TB_DONE] = 1; }
@@ -214,8 +254,9 @@ __device__ __forceinline__ void hmm_trace_rounds(const Sync sync, const int tid,
 }
 
 // ---- decode (thread 0): label_motifs over the kept copies, skip filter, counts, collapse.  Visits were recorded back to front: the
-//      last ones recorded (the first of the allele) sit in global memory and come through LDS in chunks.
-template <class Sync>
+//      last ones recorded (the first of the allele) sit in global memory and come through LDS in chunks.  VIS: visits kept in LDS;
+//      STAGE: bytes of the staging window l.stage, which takes the chunks.
+template <int VIS = HMM_VIS_LDS, int STAGE = HMM_STAGE_BYTES, class Sync>
 __device__ __forceinline__ void hmm_decode_visits(const Sync sync, const int tid, const int nthr, const HmmTraceLds l, const int nb, const uint32_t* g_vis,
                                                   int32_t* const sp, uint32_t* n_spans_job, uint32_t* counts_job) {
   const int n_motifs = nb - 1;
@@ -235,10 +276,10 @@ __device__ __forceinline__ void hmm_decode_visits(const Sync sync, const int tid
     }
   };
   int v = l.tb[TB_NVISIT] - 1;
-  constexpr int VIS_CHUNK = HMM_STAGE_BYTES / 12;
+  constexpr int VIS_CHUNK = STAGE / 12;
   uint32_t* const l_vchunk = reinterpret_cast<uint32_t*>(l.stage);  // (the staging window of the back-pointers is free now)
-  while (v >= HMM_VIS_LDS) {
-    const int n = min(v - HMM_VIS_LDS + 1, VIS_CHUNK), v0 = v - n + 1;
+  while (v >= VIS) {
+    const int n = min(v - VIS + 1, VIS_CHUNK), v0 = v - n + 1;
     sync.mem();  // (the visits were written by the decoding lanes; the chunk before has been consumed)
     for (int k = tid; k < 3 * n; k += nthr) l_vchunk[k] = g_vis[3 * (size_t)v0 + k];
     sync.lds();
