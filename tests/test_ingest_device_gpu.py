@@ -253,6 +253,87 @@ def test_an_unusable_ingest_device_fails_the_call(tmp_path):
     _same_batches(a, b)
 
 
+# ---- branches of the plan (trgt_amd/csrc/ingest_plan.hpp; its values are pinned by tests/tools/ingest_plan_check.cpp) on the device ---------
+@pytest.fixture(scope="module")
+def far_apart(tmp_path_factory):
+    """chr1 with reads over loci A (3000) and A2 (3400), then 165 random 3 kb reads that no locus wants, then reads over locus B (200000); chr2
+    is in the FASTA only.  The filler is about 120 kB of compressed BAM (a quarter of a byte per random base), twice the 64 KiB below which two compressed
+    ranges merge, and none of its reads crosses a 16 kb boundary (it would land in a bin that the windows of A and B both look into)."""
+    d = tmp_path_factory.mktemp("far")
+    rng = np.random.default_rng(23)
+    n = 230000
+    genome = "".join(rng.choice(list("ACGT"), n))
+    fa, bam = str(d / "g.fa"), str(d / "r.bam")
+    write_fasta(fa, [("chr1", genome), ("chr2", genome[:20000])])
+
+    def rec(name, pos, length):
+        return dict(name=name, tid=0, pos=pos, cigar=[("=", length)], seq="".join(rng.choice(list("ACGT"), length)), tags={"rq": ("f", 0.999)})
+    recs = [rec("a%d" % i, 2600 + 10 * i, 1000) for i in range(6)]
+    recs += [rec("f%d_%d_%d" % (w, k, c), 16384 * w + 100 + 3200 * k, 3000) for w in range(1, 12) for k in range(5) for c in range(3)]
+    recs += [rec("b%d" % i, 199600 + 10 * i, 1000) for i in range(4)]
+    write_bam(bam, [("chr1", n)], recs)
+    beds = {}
+    for tag, lines in (("three", [("chr1", 3000, "A"), ("chr1", 3400, "A2"), ("chr1", 200000, "B")]), ("empty", [("chr2", 1000, "N"), ("chr1", 8000, "E")])):
+        beds[tag] = str(d / (tag + ".bed"))
+        open(beds[tag], "w").write("".join("%s\t%d\t%d\tID=%s;MOTIFS=CAG;STRUC=(CAG)n\n" % (c, s, s + 30, i) for c, s, i in lines))
+    return bam, fa, beds
+
+
+def test_two_compressed_ranges_in_one_call_and_one_range_for_two_loci(far_apart, monkeypatch, capfd):
+    from trgt_amd import ingest
+    bam, fa, beds = far_apart
+    rd = ingest.Reader(bam, fa)
+    monkeypatch.setenv("TRGT_INGEST_TRACE", "1")
+    host, dev, fell_back, st = _both(rd, beds["three"], keep_bam4=1)
+    monkeypatch.delenv("TRGT_INGEST_TRACE")
+    assert not fell_back and st["blocks_by_zlib"] == 0
+    _same_batches(host, dev)
+    assert [int(v) for v in np.diff(host["locus_read_begin"])] == [6, 6, 4]
+    # the call's own account: A and A2 share the first range, the filler is not read, B is the second range
+    m = re.search(r"device: (\d+) ranges, (\d+) blocks", capfd.readouterr().err)
+    assert m and int(m.group(1)) == 2, m
+    raw, off, n_blocks = open(bam, "rb").read(), 0, 0
+    while off < len(raw):
+        off += (raw[off + 16] | (raw[off + 17] << 8)) + 1
+        n_blocks += 1
+    assert len(raw) > 2 * 0x10000 and n_blocks >= 12 and int(m.group(2)) <= n_blocks // 2
+
+
+@pytest.mark.parametrize("keep_bam4", [0, 1])
+def test_a_batch_without_any_read(far_apart, keep_bam4):
+    # a locus on a contig the BAM header lacks (tid -1: no chunks) and one no record overlaps (its chunk is walked, nothing is kept).  A batch
+    # with reads goes first and is freed: the empty one gets that slab back, so what it hands out is what it wrote
+    from trgt_amd import ingest
+    bam, fa, beds = far_apart
+    rd = ingest.Reader(bam, fa)
+    assert rd.batch(beds["three"], ingest_device=0, keep_bam4=keep_bam4)["n_reads"] == 16
+    host, dev, fell_back, _ = _both(rd, beds["empty"], keep_bam4=keep_bam4)
+    assert not fell_back and host["n_loci"] == 2 and host["skipped"] == []
+    assert dev["n_reads"] == 0 and host["n_reads"] == 0
+    _same_batches(host, dev)
+    for k in ("mismatch_off", "meth_off", "cigar_off"):
+        assert list(dev[k]) == [0], k
+    assert list(dev["locus_read_begin"]) == [0, 0, 0] and list(dev["n_reads_seen"]) == [0, 0]
+    assert len(dev["read_blob"]) == len(host["read_blob"]) == 1 and int(dev["read_blob"][0]) == 0   # read_bytes: the one NUL of an empty blob
+    assert ("read_bam4" in dev) == bool(keep_bam4)
+    if keep_bam4:
+        assert list(dev["read_bam4"]) == [0] and list(dev["read_bam4_off"]) == [0]
+
+
+def test_a_freed_batch_gives_its_slab_to_the_next_one(far_apart):
+    from trgt_amd import ingest
+    bam, fa, beds = far_apart
+    rd = ingest.Reader(bam, fa)
+    host = rd.batch(beds["three"])
+    first = rd.batch(beds["three"], ingest_device=0, keep_native=True)
+    _same_batches(host, first)
+    slab = first["read_blob_dev"]
+    del first["_native"]   # trgt_ingest_free: the lease returns the slab to the reader's pool
+    second = rd.batch(beds["three"], ingest_device=0, keep_native=True)
+    _same_batches(host, second)
+    assert second["read_blob_dev"] == slab and rd.device_stats()["fallbacks"] == 0   # the same piece of the same slab
+
+
 # ---- the reference's unit-test vectors as BAM records -----------------------------------------------------------------------------------
 def _ops(cigar):
     return [(c, int(n)) for n, c in re.findall(r"(\d+)([MIDNSHP=X])", cigar)]

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <limits>
 #include <map>
 #include <memory>
@@ -25,7 +26,6 @@
 #include <new>
 #include <sstream>
 #include <string>
-#include <chrono>
 #include <thread>
 #include <vector>
 
@@ -576,156 +576,123 @@ struct trgt_ingest {
   }
 };
 
-// ---- trgt_ingest_params.ingest_device: the reads of a batch of loci through the kernels of ingest_dev.hip.  Host work: the .bai chunks of
-// every locus, the compressed ranges they span read into pinned memory (a few threads), the BGZF headers walked (block table, footers'
-// CRC-32 / ISIZE; the blocks of a range are laid end to end in the inflated buffer, so a record may run across blocks as in the file),
-// every chunk's virtual offsets turned into positions in that buffer.
+// a worker on n threads, or inline when one is enough (the worker claims its share of the work from a counter the threads share)
+template <class F>
+static void run_on_threads(int n, F&& worker) {
+  if (n <= 1) { worker(); return; }
+  std::vector<std::thread> th;
+  for (int t = 0; t < n; ++t) th.emplace_back(std::ref(worker));
+  for (auto& t : th) t.join();
+}
+
+// ---- trgt_ingest_params.ingest_device: the reads of a batch of loci through the kernels of ingest_dev.hip.  What the host decides is
+// ingest_plan.hpp (pure functions: windows, compressed ranges and their place in the staging buffer, the block table off the BGZF headers,
+// the chunks as positions in the inflated bytes); a DeviceReads acts on it in the stages of run(): take_slot, windows_and_chunks (.bai),
+// plan_file_ranges, read_pieces (a few threads, into the slot's pinned staging), walk_headers, place_chunks -- each may send the call to
+// the host path (res.fallback) -- then run_slot (ingest_dev.hip) and account_and_trace.  Leaving gives the slot back and closes the file;
+// `res` owns the slab of the batch (its lease), so every way out that does not hand it on returns the slab to the pool.
 // rc TRGT_OK: res.fallback == 0 -> the arrays of `res` are the batch's; != 0 -> the host path runs (and reports what is wrong); < 0: error
 struct DevLocusIn { int tid; int64_t start, end; };
-static int device_reads(trgt_ingest* h, const trgt_ingest_params* p, const std::vector<DevLocusIn>& dl, trgt::ingd::RunOut& res, std::string& err, bool trace) {
-  namespace ingd = trgt::ingd;
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
-  auto bad = [&](const std::string& m) { err = m; return TRGT_ERR_INVALID; };
-  // a free slot of device state
-  int si = -1;
-  {
+struct DeviceReads {
+  trgt_ingest* h; const trgt_ingest_params* p; const std::vector<DevLocusIn>& dl; trgt::ingd::RunOut& res; std::string& err; bool trace;
+  trgt::ingd::Slot* slot = nullptr; int si = -1;  // (slot: set once dev_slots[si] is marked busy)
+  int fd = -1;
+  std::vector<trgt::ingd::LocusDesc> ld;
+  std::vector<trgt::ingd::VoffPair> cv;     // the chunks' virtual offsets
+  trgt::ingd::RangePlan rp; uint8_t* src = nullptr;
+  trgt::ingd::BlockWalk bw;
+  std::vector<trgt::ingd::ChunkDesc> cd;
+  double t0 = 0, t_read = 0, t_walk = 0;
+
+  ~DeviceReads() {
+    if (fd >= 0) ::close(fd);
+    if (slot) { { std::lock_guard<std::mutex> g(h->dev_mu); h->dev_slots[si].busy = false; } h->dev_cv.notify_all(); }
+  }
+  int bad(const std::string& m) { err = m; return TRGT_ERR_INVALID; }
+
+  int take_slot() {  // a free slot of device state
+    t0 = trgt::ingd::now_ms();
     std::unique_lock<std::mutex> g(h->dev_mu);
     if (h->dev_device != p->ingest_device) {
       h->dev_cv.wait(g, [&] { for (auto& d : h->dev_slots) if (d.busy) return false; return true; });
-      for (auto& d : h->dev_slots) if (d.s) { ingd::slot_destroy(d.s); d.s = nullptr; }
+      for (auto& d : h->dev_slots) if (d.s) { trgt::ingd::slot_destroy(d.s); d.s = nullptr; }
       h->dev_device = p->ingest_device;
     }
     h->dev_cv.wait(g, [&] { for (int i = 0; i < trgt_ingest::DEV_SLOTS; ++i) if (!h->dev_slots[i].busy) { si = i; return true; } return false; });
-    if (!h->dev_slots[si].s && !(h->dev_slots[si].s = ingd::slot_create(p->ingest_device, err))) return TRGT_ERR_NO_DEVICE;
+    if (!h->dev_slots[si].s && !(h->dev_slots[si].s = trgt::ingd::slot_create(p->ingest_device, err))) return TRGT_ERR_NO_DEVICE;
     h->dev_slots[si].busy = true;
+    slot = h->dev_slots[si].s;
+    return TRGT_OK;
   }
-  struct Release { trgt_ingest* h; int si; ~Release() { { std::lock_guard<std::mutex> g(h->dev_mu); h->dev_slots[si].busy = false; } h->dev_cv.notify_all(); } } release{h, si};
-  ingd::Slot* slot = h->dev_slots[si].s;
-  const size_t nl = dl.size();
-  std::vector<ingd::LocusDesc> ld(nl);
-  std::vector<std::pair<uint64_t, uint64_t>> cv;  // the chunks' virtual offsets
-  for (size_t li = 0; li < nl; ++li) {
-    ingd::LocusDesc& d = ld[li];
-    d.tid = dl[li].tid; d.pad = 0;
-    d.beg = std::max<int64_t>(0, dl[li].start - p->flank_len); d.end = dl[li].end + p->flank_len;
-    d.region_start = dl[li].start; d.region_end = dl[li].end;
-    d.clip_start = dl[li].start - 2ll * p->flank_len; d.clip_end = dl[li].end + 2ll * p->flank_len;
-    d.chunk_begin = (int32_t)cv.size();
-    if (d.tid >= 0) for (auto& ch : h->bai.query(d.tid, d.beg, d.end)) cv.push_back(ch);
-    d.chunk_end = (int32_t)cv.size();
+  int windows_and_chunks() {
+    for (auto& l : dl) ld.push_back(trgt::ingd::locus_windows(l.tid, l.start, l.end, p->flank_len));
+    cv = trgt::ingd::locus_chunks(ld, [&](int tid, int64_t beg, int64_t end) { return h->bai.query(tid, beg, end); });
+    return TRGT_OK;
   }
-  std::vector<std::pair<uint64_t, uint64_t>> ranges, merged;
-  for (auto& c : cv) ranges.emplace_back(c.first >> 16, c.second >> 16);
-  std::sort(ranges.begin(), ranges.end());
-  for (auto& r : ranges) {
-    if (!merged.empty() && r.first <= merged.back().second + 0x10000) merged.back().second = std::max(merged.back().second, r.second);
-    else merged.push_back(r);
+  int plan_file_ranges() {
+    fd = ::open(h->bam_path.c_str(), O_RDONLY);
+    if (fd < 0) return bad("cannot open " + h->bam_path);
+    struct stat st;
+    if (::fstat(fd, &st) != 0) return bad("cannot stat " + h->bam_path);
+    rp = trgt::ingd::plan_ranges(cv, (uint64_t)st.st_size);
+    src = trgt::ingd::slot_src(slot, (size_t)rp.src_total + 64, err);
+    return src ? TRGT_OK : TRGT_ERR_NOMEM;
   }
-  const int fd = ::open(h->bam_path.c_str(), O_RDONLY);
-  if (fd < 0) return bad("cannot open " + h->bam_path);
-  struct Fd { int fd; ~Fd() { ::close(fd); } } fdg{fd};
-  struct stat st;
-  if (::fstat(fd, &st) != 0) return bad("cannot stat " + h->bam_path);
-  const uint64_t fsize = (uint64_t)st.st_size;
-  uint64_t src_total = 0;
-  std::vector<uint64_t> src_at(merged.size());
-  for (size_t i = 0; i < merged.size(); ++i) {
-    const uint64_t c0 = merged[i].first, c1 = std::min<uint64_t>(fsize, merged[i].second + 0x10000 + 64);
-    src_at[i] = src_total;
-    if (c1 > c0) src_total += ((c1 - c0) + 63) & ~63ull;
-  }
-  uint8_t* const src = ingd::slot_src(slot, (size_t)src_total + 64, err);
-  if (!src) return TRGT_ERR_NOMEM;
-  {  // the compressed ranges, read by a few threads (page cache or disk), in pieces
-    struct Piece { uint64_t off; uint8_t* dst; size_t n; };
-    std::vector<Piece> pieces;
-    for (size_t i = 0; i < merged.size(); ++i) {
-      const uint64_t c0 = merged[i].first, c1 = std::min<uint64_t>(fsize, merged[i].second + 0x10000 + 64);
-      for (uint64_t o = c0; o < c1; o += 4u << 20) pieces.push_back({o, src + src_at[i] + (o - c0), (size_t)std::min<uint64_t>(c1 - o, 4u << 20)});
-    }
+  int read_pieces() {  // the compressed ranges, read by a few threads (page cache or disk), in pieces
+    const auto& pieces = rp.pieces;
     std::atomic<size_t> next{0}; std::atomic<int> failed{0};
     auto rd = [&]() {
       for (;;) {
         const size_t i = next.fetch_add(1);
         if (i >= pieces.size()) break;
         for (size_t done = 0; done < pieces[i].n;) {
-          const ssize_t g = ::pread(fd, pieces[i].dst + done, pieces[i].n - done, (off_t)(pieces[i].off + done));
+          const ssize_t g = ::pread(fd, src + pieces[i].src_off + done, pieces[i].n - done, (off_t)(pieces[i].file_off + done));
           if (g <= 0) { failed = 1; return; }
           done += (size_t)g;
         }
       }
     };
     const int want = p->threads > 0 ? p->threads : 8;
-    const int nt = (int)std::min<size_t>((size_t)std::max(1, std::min(want, 8)), pieces.size());
-    if (nt <= 1) rd();
-    else { std::vector<std::thread> th; for (int t = 0; t < nt; ++t) th.emplace_back(rd); for (auto& t : th) t.join(); }
+    run_on_threads((int)std::min<size_t>((size_t)std::max(1, std::min(want, 8)), pieces.size()), rd);
     if (failed) return bad("trgt_ingest: reading the compressed blocks failed");
+    t_read = trgt::ingd::now_ms();
+    return TRGT_OK;
   }
-  const double t_read = now();
-  // ---- block table: payloads, where they inflate to, the footers
-  std::vector<trgt::infl::BlockDesc> blocks; std::vector<uint32_t> crcs;
-  struct Known { uint64_t coff, lin; uint32_t isize, range; };
-  std::vector<Known> known;  // every block met (also empty ones), sorted by coff
-  std::vector<uint64_t> lin_end(merged.size());
-  uint64_t lin = 0;
-  auto fall = [&](int why) { res = ingd::RunOut(); res.fallback = why; return TRGT_OK; };
-  for (size_t i = 0; i < merged.size(); ++i) {
-    const uint64_t c0 = merged[i].first, cend = std::min<uint64_t>(fsize, merged[i].second + 0x10000 + 64);
-    uint64_t coff = c0;
-    while (coff <= merged[i].second && coff < fsize) {
-      if (coff + 18 > cend) return fall(ingd::FB_BLOCK);
-      const uint8_t* hp = src + src_at[i] + (coff - c0);
-      if (hp[0] != 31 || hp[1] != 139 || hp[2] != 8 || !(hp[3] & 4)) return fall(ingd::FB_BLOCK);  // (the host path says what is wrong)
-      const uint32_t xlen = hp[10] | (hp[11] << 8);
-      if (coff + 12 + xlen > cend) return fall(ingd::FB_BLOCK);
-      uint32_t bsize = 0; bool found = false;
-      for (uint32_t k = 0; k + 4 <= xlen;) {
-        const uint32_t slen = hp[12 + k + 2] | (hp[12 + k + 3] << 8);
-        if (hp[12 + k] == 'B' && hp[12 + k + 1] == 'C' && slen == 2 && k + 6 <= xlen) { bsize = hp[12 + k + 4] | (hp[12 + k + 5] << 8); found = true; break; }
-        k += 4 + slen;
-      }
-      if (!found) return fall(ingd::FB_BLOCK);
-      const uint32_t total = bsize + 1, hdr = 12 + xlen;
-      if (total < hdr + 8 || coff + total > cend) return fall(ingd::FB_BLOCK);
-      const uint32_t isize = le32(hp + total - 4);
-      if (isize > 0x10000) return fall(ingd::FB_BLOCK);
-      known.push_back(Known{coff, lin, isize, (uint32_t)i});
-      if (isize) {
-        blocks.push_back(trgt::infl::BlockDesc{src_at[i] + (coff - c0) + hdr, lin, total - hdr - 8, isize});
-        crcs.push_back(le32(hp + total - 8));
-        lin += isize;
-      }
-      coff += total;
-    }
-    lin_end[i] = lin;
-    lin = ((lin + 63) & ~63ull) + 64;  // (a gap between the ranges: nothing of one is read as the other's)
+  int fall(int why) { res = trgt::ingd::RunOut(); res.fallback = why; return TRGT_OK; }
+  int walk_headers() {  // block table: payloads, where they inflate to, the footers
+    bw = trgt::ingd::walk_block_headers(src, rp.src_total, rp);
+    if (bw.fallback) return fall(bw.fallback);
+    t_walk = trgt::ingd::now_ms();
+    return TRGT_OK;
   }
-  const double t_walk = now();
-  // ---- the chunks as positions in the inflated bytes
-  std::vector<ingd::ChunkDesc> cd(cv.size());
-  auto find = [&](uint64_t coff) -> const Known* {
-    auto it = std::lower_bound(known.begin(), known.end(), coff, [](const Known& k, uint64_t c) { return k.coff < c; });
-    return it != known.end() && it->coff == coff ? &*it : nullptr;
-  };
-  for (size_t c = 0; c < cv.size(); ++c) {
-    const Known* a = find(cv[c].first >> 16);
-    if (!a || (cv[c].first & 0xFFFF) > a->isize) return fall(ingd::FB_WALK);
-    const Known* b = find(cv[c].second >> 16);
-    cd[c].lin0 = a->lin + (cv[c].first & 0xFFFF);
-    cd[c].lin_limit = lin_end[a->range];
-    cd[c].lin1 = b && b->range == a->range ? std::min<uint64_t>(b->lin + std::min<uint64_t>(cv[c].second & 0xFFFF, b->isize), cd[c].lin_limit) : cd[c].lin_limit;
+  int place_chunks() {
+    const int why = trgt::ingd::place_chunks(cv, bw, cd);
+    return why ? fall(why) : TRGT_OK;
   }
-  ingd::RunIn in;
-  in.src_bytes = src_total; in.n_blocks = (int64_t)blocks.size(); in.blocks = blocks.data(); in.crc = crcs.data(); in.infl_bytes = lin;
-  in.n_loci = (int64_t)nl; in.loci = ld.data(); in.n_chunks = (int64_t)cd.size(); in.chunks = cd.data();
-  in.reservoir = (uint32_t)(3ll * p->max_depth); in.min_rq = p->min_read_qual; in.keep_bam4 = p->keep_bam4 != 0; in.waves_per_cu = p->inflate_waves_per_cu;
-  const int rc = ingd::slot_run(slot, in, *h->slab_pool, res, err);
-  if (rc) return rc;
-  h->dev_blocks += (int64_t)blocks.size(); h->dev_blocks_host += (int64_t)res.blocks_host_inflated;
-  if (trace) std::fprintf(stderr, "[ingest]   device: %zu ranges, %zu blocks (%.1f MB -> %.1f MB), file %.1f ms, headers %.1f ms, upload+inflate+crc %.1f ms (%llu blocks by zlib), walk %.1f ms, read sizes %.1f ms, slab + fill launch %.1f ms, fill + download %.1f ms, fallback %d\n",
-                          merged.size(), blocks.size(), (double)src_total / 1e6, (double)lin / 1e6, t_read - t0, t_walk - t_read, res.ms_inflate, (unsigned long long)res.blocks_host_inflated, res.ms_walk, res.ms_reads, res.ms_upload, res.ms_download, res.fallback);
-  return TRGT_OK;
+  int run_slot() {
+    trgt::ingd::RunIn in;
+    in.src_bytes = rp.src_total; in.n_blocks = (int64_t)bw.blocks.size(); in.blocks = bw.blocks.data(); in.crc = bw.crcs.data(); in.infl_bytes = bw.infl_bytes;
+    in.n_loci = (int64_t)ld.size(); in.loci = ld.data(); in.n_chunks = (int64_t)cd.size(); in.chunks = cd.data();
+    in.reservoir = (uint32_t)(3ll * p->max_depth); in.min_rq = p->min_read_qual; in.keep_bam4 = p->keep_bam4 != 0; in.waves_per_cu = p->inflate_waves_per_cu;
+    return trgt::ingd::slot_run(slot, in, h->slab_pool, res, err);
+  }
+  void account_and_trace() {
+    h->dev_blocks += (int64_t)bw.blocks.size(); h->dev_blocks_host += (int64_t)res.blocks_host_inflated;
+    if (trace) std::fprintf(stderr, "[ingest]   device: %zu ranges, %zu blocks (%.1f MB -> %.1f MB), file %.1f ms, headers %.1f ms, upload+inflate+crc %.1f ms (%llu blocks by zlib), walk %.1f ms, read sizes %.1f ms, slab + fill launch %.1f ms, fill + download %.1f ms, fallback %d\n",
+                            rp.ranges.size(), bw.blocks.size(), (double)rp.src_total / 1e6, (double)bw.infl_bytes / 1e6, t_read - t0, t_walk - t_read, res.ms_inflate, (unsigned long long)res.blocks_host_inflated, res.ms_walk, res.ms_reads, res.ms_upload, res.ms_download, res.fallback);
+  }
+  int run() {
+    using Stage = int (DeviceReads::*)();
+    static constexpr Stage plan_stages[] = {&DeviceReads::take_slot, &DeviceReads::windows_and_chunks, &DeviceReads::plan_file_ranges, &DeviceReads::read_pieces,
+                                            &DeviceReads::walk_headers, &DeviceReads::place_chunks};
+    for (const Stage stage : plan_stages) { const int rc = (this->*stage)(); if (rc || res.fallback) return rc; }
+    if (const int rc = run_slot()) return rc;
+    account_and_trace();
+    return TRGT_OK;
+  }
+};
+static int device_reads(trgt_ingest* h, const trgt_ingest_params* p, const std::vector<DevLocusIn>& dl, trgt::ingd::RunOut& res, std::string& err, bool trace) {
+  return DeviceReads{h, p, dl, res, err, trace}.run();
 }
 
 struct BatchStore {  // owner of the arrays a trgt_ingest_batch points to
@@ -744,8 +711,7 @@ struct BatchStore {  // owner of the arrays a trgt_ingest_batch points to
   std::vector<uint64_t> bam4_off;
   std::string skipped; std::vector<uint64_t> skipped_off;
   // ingest_device: the per-read arrays are pieces of one device slab + its pinned mirror (back to the reader's pool when the batch is freed)
-  trgt::ingd::Slab slab; std::shared_ptr<trgt::ingd::SlabPool> slab_pool;
-  ~BatchStore() { if (slab_pool) slab_pool->give(slab); }
+  trgt::ingd::SlabLease lease;
   trgt_ingest_batch pub;
 };
 
@@ -755,8 +721,9 @@ namespace trgt {
 bool ingest_batch_slab(const trgt_ingest_batch* b, const void** dev, const void** pin, size_t* bytes, int* device) {
   if (!b || !b->owner || !b->read_blob_dev) return false;
   const BatchStore* S = reinterpret_cast<const BatchStore*>(b->owner);
-  if (&S->pub != b || !S->slab.dev || !S->slab.pin) return false;
-  *dev = S->slab.dev; *pin = S->slab.pin; *bytes = S->slab.cap; *device = S->slab.device;
+  const trgt::ingd::Slab& slab = S->lease.slab();
+  if (&S->pub != b || !slab.dev || !slab.pin) return false;
+  *dev = slab.dev; *pin = slab.pin; *bytes = slab.cap; *device = slab.device;
   return true;
 }
 }  // namespace trgt
@@ -893,31 +860,42 @@ static bool parse_bed_info(const std::string& info, std::string& id, std::vector
   return true;
 }
 
-static int ingest_batch_impl(trgt_ingest* h, const trgt_ingest_params* p, const char* bed_path, int64_t first_locus, int64_t max_loci,
-                             trgt_ingest_batch** out) {
-  if (!h || !p || !bed_path || !out) return TRGT_ERR_INVALID;
-  *out = nullptr;
-  auto bad = [&](const std::string& m) { h->err = m; return TRGT_ERR_INVALID; };
-  if (p->flank_len <= 0 || p->max_depth <= 0) return bad("trgt_ingest: flank_len and max_depth must be positive");
-  std::ifstream bed(bed_path);
-  if (!bed) return bad(std::string("cannot open ") + bed_path);
+// One call of trgt_ingest_batch_from_catalog: the stages of ingest_batch_impl, in its order.  A stage returns TRGT_OK or a TRGT_ERR_* code
+// (with h->err).  `dev` owns the slab of a device-ingested batch until publish hands it to the BatchStore.
+struct CatalogLocus {
+  std::string contig, id, struc; int64_t start, end; std::vector<std::string> motifs; std::string lf, tr, rf;
+  std::vector<Read> reads; int32_t n_filt = 0; int64_t n_seen = 0; std::string err;
+};
+struct BatchAt { uint64_t read = 0, bytes = 0, name = 0, snp = 0, meth = 0, cig = 0, bam4 = 0; };  // where a locus starts in the per-read arrays
+struct BatchCall {
+  trgt_ingest* h; const trgt_ingest_params* p;
   const bool trace = std::getenv("TRGT_INGEST_TRACE") != nullptr;  // phase times on stderr
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double t0 = now();
-  struct L { std::string contig, id, struc; int64_t start, end; std::vector<std::string> motifs; std::string lf, tr, rf; std::vector<Read> reads; int32_t n_filt = 0; int64_t n_seen = 0; std::string err; };
-  std::vector<L> loci;
-  std::vector<std::string> skipped;  // one message per catalog line that gave no locus
-  {
-    // stream_loci_into_channel (locus.rs:93-137): a line that does not give a Locus is reported ("Error at BED line N: ...") and the
-    // next line is read; blank lines are lines like any other ("Expected 4 fields ..., found 0").  first_locus / max_loci count
-    // catalog LINES.
+  std::vector<CatalogLocus> loci; int64_t nl = 0;
+  std::vector<std::string> skipped;         // one message per catalog line that gave no locus
+  trgt::ingd::RunOut dev; bool from_device = false;
+  int nthr = 1; int64_t run = 1;
+  std::atomic<uint64_t> n_inflated{0}, n_cache_hits{0};
+  std::unique_ptr<BatchStore> S;
+  std::vector<BatchAt> at; BatchAt tot;
+  double t0 = 0, t1 = 0, t2 = 0;
+
+  int bad(const std::string& m) { h->err = m; return TRGT_ERR_INVALID; }
+
+  // stream_loci_into_channel (locus.rs:93-137): a line that does not give a Locus is reported ("Error at BED line N: ...") and the
+  // next line is read; blank lines are lines like any other ("Expected 4 fields ..., found 0").  first_locus / max_loci count
+  // catalog LINES.
+  int read_catalog(const char* bed_path, int64_t first_locus, int64_t max_loci) {
+    if (p->flank_len <= 0 || p->max_depth <= 0) return bad("trgt_ingest: flank_len and max_depth must be positive");
+    std::ifstream bed(bed_path);
+    if (!bed) return bad(std::string("cannot open ") + bed_path);
+    t0 = trgt::ingd::now_ms();
     std::string line; int64_t line_no = 0;
     while (std::getline(bed, line)) {
       ++line_no;
       if (line_no - 1 < first_locus) continue;
       if (max_loci >= 0 && line_no - 1 >= first_locus + max_loci) break;
       if (!line.empty() && line.back() == '\r') line.pop_back();
-      L l; std::string e;
+      CatalogLocus l; std::string e;
       auto skip = [&](const std::string& m) { skipped.push_back("Error at BED line " + std::to_string(line_no) + ": " + m); };
       std::string info;
       if (!parse_bed_region(line, l.contig, l.start, l.end, info, e)) { skip(e); continue; }
@@ -933,14 +911,14 @@ static int ingest_batch_impl(trgt_ingest* h, const trgt_ingest_params* p, const 
           !h->fasta.fetch(l.contig, l.end, l.end + p->flank_len, l.rf, e)) { skip(e); continue; }
       loci.push_back(std::move(l));
     }
+    nl = (int64_t)loci.size();
+    t1 = trgt::ingd::now_ms();
+    return TRGT_OK;
   }
-  const int64_t nl = (int64_t)loci.size();
-  const double t1 = now();
-  // ---- trgt_ingest_params.ingest_device: the reads of these loci through the kernels of ingest_dev.hip; what they do not take (res.fallback)
-  // goes through the host path below, which yields the data or the error message
-  trgt::ingd::RunOut dev;
-  bool from_device = false;
-  if (p->ingest_device >= 0 && nl > 0) {
+  // trgt_ingest_params.ingest_device: the reads of these loci through the kernels of ingest_dev.hip; what they do not take (dev.fallback)
+  // goes through the host path, which yields the data or the error message
+  int device_attempt() {
+    if (p->ingest_device < 0 || nl <= 0) return TRGT_OK;
     std::vector<DevLocusIn> dl((size_t)nl);
     for (int64_t li = 0; li < nl; ++li) { auto it = h->ref_id.find(loci[(size_t)li].contig); dl[(size_t)li] = DevLocusIn{it == h->ref_id.end() ? -1 : it->second, loci[(size_t)li].start, loci[(size_t)li].end}; }
     std::string derr;
@@ -949,205 +927,235 @@ static int ingest_batch_impl(trgt_ingest* h, const trgt_ingest_params* p, const 
     ++h->dev_calls;
     if (dev.fallback) { ++h->dev_fallbacks; h->dev_last_reason = dev.fallback; }
     else from_device = true;
+    return TRGT_OK;
   }
-  // ---- reads: extract_reads + clip_reads per locus, loci spread over threads (one file handle each)
-  int nthr = p->threads > 0 ? p->threads : (int)std::max(1u, std::min(32u, std::thread::hardware_concurrency()));  // (more than 32 workers lose: tools/ingest_scaling.py)
-  nthr = (int)std::max<int64_t>(1, std::min<int64_t>(nthr, nl));
-  std::atomic<int64_t> next{0};
-  std::atomic<uint64_t> n_inflated{0}, n_cache_hits{0};
-  // a worker takes a run of consecutive catalog lines (sorted catalogs: neighbours share BGZF blocks, see Bgzf), short enough that
-  // every thread still gets several runs
-  const int64_t run = std::max<int64_t>(1, std::min<int64_t>(8, nl / (4ll * nthr)));
-  auto work_body = [&]() {
-    std::unique_ptr<Bgzf> zp;
-    { std::lock_guard<std::mutex> g(h->idle_mu); if (!h->idle_readers.empty()) { zp = std::move(h->idle_readers.back()); h->idle_readers.pop_back(); } }
-    if (!zp) {
-      zp.reset(new Bgzf(48));
-      if (!zp->open(h->bam_path.c_str())) { for (auto& l : loci) if (l.err.empty()) { l.err = zp->err; break; } return; }
-    }
-    struct Back { trgt_ingest* h; std::unique_ptr<Bgzf>& z; ~Back() { if (z && z->err.empty()) { std::lock_guard<std::mutex> g(h->idle_mu); h->idle_readers.push_back(std::move(z)); } } } back{h, zp};
-    Bgzf& z = *zp;
-    z.block_coff = ~0ull; z.block_csize = 0; z.cur_data = nullptr; z.cur_size = 0; z.pos = 0;
-    const uint64_t inflated0 = z.n_inflated, hits0 = z.n_hits;
-    RawRec rec;
-    for (;;) {
-      const int64_t l0 = next.fetch_add(run);
-      if (l0 >= nl) break;
-     for (int64_t li = l0; li < std::min(nl, l0 + run); ++li) {
-      L& l = loci[(size_t)li];
-      auto it = h->ref_id.find(l.contig);
-      if (it == h->ref_id.end()) continue;  // "Fetch error" is a warning in the reference: the locus gets no reads
-      const int tid = it->second;
-      const int64_t beg = std::max<int64_t>(0, l.start - p->flank_len), end = l.end + p->flank_len;
-      const int64_t reservoir = 3ll * p->max_depth;
-      std::unique_ptr<StdRng> rng;
-      int64_t n_reads = 0;
-      bool stop = false;
-      for (auto& ch : h->bai.query(tid, beg, end)) {
-        if (stop) break;
-        if (!z.seek(ch.first)) { l.err = z.err; break; }
-        while (z.tell() < ch.second) {
-          uint8_t b4[4];
-          const int g = z.read(b4, 4);
-          if (g == 0) break;
-          if (g < 0) { l.err = z.err; stop = true; break; }
-          { const uint32_t bs = le32(b4); if (bs < 32 || bs > (1u << 29)) { l.err = "corrupt BAM record"; stop = true; break; } rec.d.resize(bs); }
-          if (z.read(rec.d.data(), rec.d.size()) != 1 || !parse_rec(rec)) { l.err = z.err.empty() ? "corrupt BAM record" : z.err; stop = true; break; }
-          if (rec.ref_id != tid || rec.pos >= end) { stop = true; break; }  // sorted: nothing further overlaps
-          int64_t rend = rec_ref_end(rec);
-          if (rend == rec.pos) rend = rec.pos + 1;
-          if (rend <= beg) continue;
-          if (rec.flag & (0x800 | 0x100)) continue;  // supplementary / secondary
-          { const uint8_t* a = find_aux(rec, "rq"); float f = 1.0f; if (a && a[0] == 'f') std::memcpy(&f, a + 1, 4);
-            if ((a && a[0] == 'f' ? (double)f : 1.0) < p->min_read_qual) { ++l.n_filt; continue; } }
-          if (n_reads < reservoir) { l.reads.emplace_back(); make_read(rec, l.start, l.end, l.reads.back()); }
-          else {  // the reservoir is full: every further read replaces a random one with probability reservoir / (n + 1)
-            if (!rng) rng.reset(new StdRng(42));
-            const uint64_t j = rng->range((uint64_t)n_reads);
-            if ((int64_t)j < reservoir) make_read(rec, l.start, l.end, l.reads[(size_t)j]);
-          }
-          ++n_reads;
-        }
-      }
-      l.n_seen = n_reads;
-      // clip_reads (tr.rs:186-196): radius 2 * flank_len
-      const int64_t rs = l.start - 2ll * p->flank_len, re = l.end + 2ll * p->flank_len;
-      std::vector<Read> clipped;
-      for (auto& r : l.reads) { Read c; if (clip_to_region(r, rs, re, c)) clipped.push_back(std::move(c)); }
-      l.reads.swap(clipped);
-     }
-    }
-    n_inflated += z.n_inflated - inflated0; n_cache_hits += z.n_hits - hits0;
-  };
-  std::atomic<int> worker_failed{0};
-  auto work = [&]() {  // (an exception must not leave a thread, nor cross the C ABI)
-    try { work_body(); } catch (const std::exception& e) { worker_failed = 1; for (auto& l : loci) if (l.err.empty()) { l.err = std::string("reading the BAM: ") + e.what(); break; } }
-  };
-  if (from_device) {}
-  else if (nthr <= 1) work();
-  else { std::vector<std::thread> th; for (int t = 0; t < nthr; ++t) th.emplace_back(work); for (auto& t : th) t.join(); }
-  for (auto& l : loci) if (!l.err.empty()) return bad(l.id + ": " + l.err);
-  const double t2 = now();
-  // ---- the arrays of trgt_locus_batch_in (+ what the writers need per read)
-  std::unique_ptr<BatchStore> S(new BatchStore());
-  S->lrb.push_back(0); S->motif_off.push_back(0); S->set_begin.push_back(0);
-  S->contig_off.push_back(0); S->id_off.push_back(0); S->struc_off.push_back(0);
-  // per locus: the catalog fields, and where its reads go in the per-read arrays (sizes first, then the loci are copied in by the workers)
-  struct At { uint64_t read = 0, bytes = 0, name = 0, snp = 0, meth = 0, cig = 0, bam4 = 0; };
-  std::vector<At> at((size_t)nl + 1);
-  for (int64_t li = 0; li < nl; ++li) {
-    L& l = loci[(size_t)li];
-    S->lf_off.push_back(S->flank.size()); S->lf_len.push_back((uint32_t)l.lf.size()); S->flank += l.lf;
-    S->rf_off.push_back(S->flank.size()); S->rf_len.push_back((uint32_t)l.rf.size()); S->flank += l.rf;
-    S->tr_off.push_back(S->tr.size()); S->tr_len.push_back((uint32_t)l.tr.size()); S->tr += l.tr;
-    for (auto& m : l.motifs) { S->motifs += m; S->motif_off.push_back((uint32_t)S->motifs.size()); }
-    S->set_begin.push_back((uint32_t)S->motif_off.size() - 1);
-    S->ploidy.push_back((uint8_t)p->default_ploidy); S->genotyper.push_back((uint8_t)p->genotyper);
-    S->contigs += l.contig; S->contig_off.push_back(S->contigs.size()); S->ids += l.id; S->id_off.push_back(S->ids.size());
-    S->strucs += l.struc; S->struc_off.push_back(S->strucs.size());
-    S->region_start.push_back(l.start); S->region_end.push_back(l.end);
-    S->n_filtered.push_back(from_device ? dev.out.n_filt[li] : l.n_filt); S->n_seen.push_back(from_device ? dev.out.n_seen[li] : l.n_seen);
-    At n = at[(size_t)li];
-    for (auto& r : l.reads) {
-      ++n.read; n.bytes += r.bases.size(); n.name += r.id.size(); n.snp += r.mismatch_offsets.size(); n.meth += r.has_meth ? r.meth.size() : 0;
-      n.cig += r.cigar.size(); n.bam4 += (r.bases.size() + 1) / 2;
-    }
-    at[(size_t)li + 1] = n;
-    S->lrb.push_back(from_device ? dev.out.lrb[li + 1] : n.read);
+  void size_workers() {
+    nthr = p->threads > 0 ? p->threads : (int)std::max(1u, std::min(32u, std::thread::hardware_concurrency()));  // (more than 32 workers lose: tools/ingest_scaling.py)
+    nthr = (int)std::max<int64_t>(1, std::min<int64_t>(nthr, nl));
+    // a worker takes a run of consecutive catalog lines (sorted catalogs: neighbours share BGZF blocks, see Bgzf), short enough that
+    // every thread still gets several runs
+    run = std::max<int64_t>(1, std::min<int64_t>(8, nl / (4ll * nthr)));
   }
-  const At tot = at[(size_t)nl];
-  const size_t nr = (size_t)tot.read;
-  S->read_off.resize(nr); S->read_len.resize(nr); S->reads.resize((size_t)tot.bytes); S->quals.resize((size_t)tot.bytes);
-  S->names.resize((size_t)tot.name); S->name_off.assign(nr + 1, 0); S->rq.resize(nr); S->is_reverse.resize(nr); S->mapq.resize(nr); S->hp.resize(nr);
-  S->start_offset.resize(nr); S->end_offset.resize(nr); S->snp.resize((size_t)tot.snp); S->snp_off.assign(nr + 1, 0);
-  S->meth.resize((size_t)tot.meth); S->moff.assign(nr + 1, 0); S->has_meth.resize(nr);
-  S->cig.resize((size_t)tot.cig); S->cig_off.assign(nr + 1, 0); S->cig_ref_pos.resize(nr);
-  if (p->keep_bam4) { S->bam4.assign((size_t)tot.bam4 + 1, 0); S->bam4_off.assign(nr + 1, 0); }  // the reads once more, two bases per byte (half the bytes to move to the GPU)
-  std::atomic<int64_t> next_fill{0};
-  std::atomic<int> fill_failed{0};
-  auto fill = [&]() {
-    for (;;) {
-      const int64_t l0 = next_fill.fetch_add(16);
-      if (l0 >= nl) break;
-      for (int64_t li = l0; li < std::min(nl, l0 + 16); ++li) {
-        At n = at[(size_t)li];
-        const size_t r0 = (size_t)n.read;
-        for (auto& r : loci[(size_t)li].reads) {
-          const size_t k = (size_t)n.read;
-          S->read_off[k] = n.bytes; S->read_len[k] = (uint32_t)r.bases.size();
-          std::memcpy(&S->reads[0] + n.bytes, r.bases.data(), r.bases.size());
-          std::memcpy(&S->quals[0] + n.bytes, r.quals.data(), std::min(r.quals.size(), r.bases.size()));
-          std::memcpy(&S->names[0] + n.name, r.id.data(), r.id.size());
-          S->rq[k] = r.rq; S->is_reverse[k] = r.is_reverse ? 1 : 0; S->mapq[k] = r.mapq; S->hp[k] = (int16_t)r.hp;
-          S->start_offset[k] = r.start_offset; S->end_offset[k] = r.end_offset;
-          std::copy(r.mismatch_offsets.begin(), r.mismatch_offsets.end(), S->snp.begin() + (ptrdiff_t)n.snp);
-          S->has_meth[k] = r.has_meth ? 1 : 0;
-          if (r.has_meth) std::copy(r.meth.begin(), r.meth.end(), S->meth.begin() + (ptrdiff_t)n.meth);
-          std::copy(r.cigar.begin(), r.cigar.end(), S->cig.begin() + (ptrdiff_t)n.cig); S->cig_ref_pos[k] = r.ref_pos;
-          ++n.read; n.bytes += r.bases.size(); n.name += r.id.size(); n.snp += r.mismatch_offsets.size(); n.meth += r.has_meth ? r.meth.size() : 0; n.cig += r.cigar.size();
-          S->name_off[k + 1] = n.name; S->snp_off[k + 1] = n.snp; S->moff[k + 1] = n.meth; S->cig_off[k + 1] = n.cig;
+  // extract_reads of one locus (tr.rs:268-361): the .bai query, the record loop with its filters, the reservoir of 3 * max_depth reads
+  void read_locus(Bgzf& z, RawRec& rec, CatalogLocus& l) const {
+    auto it = h->ref_id.find(l.contig);
+    if (it == h->ref_id.end()) return;  // "Fetch error" is a warning in the reference: the locus gets no reads
+    const int tid = it->second;
+    const int64_t beg = std::max<int64_t>(0, l.start - p->flank_len), end = l.end + p->flank_len;
+    const int64_t reservoir = 3ll * p->max_depth;
+    std::unique_ptr<StdRng> rng;
+    int64_t n_reads = 0;
+    bool stop = false;
+    for (auto& ch : h->bai.query(tid, beg, end)) {
+      if (stop) break;
+      if (!z.seek(ch.first)) { l.err = z.err; break; }
+      while (z.tell() < ch.second) {
+        uint8_t b4[4];
+        const int g = z.read(b4, 4);
+        if (g == 0) break;
+        if (g < 0) { l.err = z.err; stop = true; break; }
+        { const uint32_t bs = le32(b4); if (bs < 32 || bs > (1u << 29)) { l.err = "corrupt BAM record"; stop = true; break; } rec.d.resize(bs); }
+        if (z.read(rec.d.data(), rec.d.size()) != 1 || !parse_rec(rec)) { l.err = z.err.empty() ? "corrupt BAM record" : z.err; stop = true; break; }
+        if (rec.ref_id != tid || rec.pos >= end) { stop = true; break; }  // sorted: nothing further overlaps
+        int64_t rend = rec_ref_end(rec);
+        if (rend == rec.pos) rend = rec.pos + 1;
+        if (rend <= beg) continue;
+        if (rec.flag & (0x800 | 0x100)) continue;  // supplementary / secondary
+        { const uint8_t* a = find_aux(rec, "rq"); float f = 1.0f; if (a && a[0] == 'f') std::memcpy(&f, a + 1, 4);
+          if ((a && a[0] == 'f' ? (double)f : 1.0) < p->min_read_qual) { ++l.n_filt; continue; } }
+        if (n_reads < reservoir) { l.reads.emplace_back(); make_read(rec, l.start, l.end, l.reads.back()); }
+        else {  // the reservoir is full: every further read replaces a random one with probability reservoir / (n + 1)
+          if (!rng) rng.reset(new StdRng(42));
+          const uint64_t j = rng->range((uint64_t)n_reads);
+          if ((int64_t)j < reservoir) make_read(rec, l.start, l.end, l.reads[(size_t)j]);
         }
-        if (p->keep_bam4 && n.read > r0) {
-          const uint64_t base = at[(size_t)li].bam4;
-          const int64_t got = trgt_reads_pack_bam4((const uint8_t*)S->reads.data(), (int64_t)(n.read - r0), S->read_off.data() + r0, S->read_len.data() + r0, S->bam4.data() + base, S->bam4_off.data() + r0);
-          if (got != (int64_t)(at[(size_t)li + 1].bam4 - base)) fill_failed = 1;
-          for (size_t k = r0; k < (size_t)n.read; ++k) S->bam4_off[k] += base;
-        }
-        std::vector<Read>().swap(loci[(size_t)li].reads);  // (freed by the worker, not by the caller's thread at the end)
+        ++n_reads;
       }
     }
-  };
-  {
-    auto guarded = [&]() { try { fill(); } catch (const std::exception&) { fill_failed = 1; } };
-    if (from_device) {}
-    else if (nthr <= 1) guarded();
-    else { std::vector<std::thread> th; for (int t = 0; t < nthr; ++t) th.emplace_back(guarded); for (auto& t : th) t.join(); }
+    l.n_seen = n_reads;
   }
-  if (fill_failed) return bad("trgt_ingest: assembling the batch failed");
-  trgt_ingest_batch& B = S->pub;
-  std::memset(&B, 0, sizeof B);
-  B.read_blob_device = -1;
-  auto u8 = [](const std::string& s) { return (const uint8_t*)s.data(); };
-  if (S->flank.empty()) S->flank.push_back('\0');
-  if (S->tr.empty()) S->tr.push_back('\0');
-  if (S->reads.empty()) S->reads.push_back('\0');
-  B.n_loci = nl; B.n_reads = (int64_t)S->read_off.size(); B.n_motifs = (int64_t)S->motif_off.size() - 1;
-  B.flank_bytes = S->flank.size(); B.tr_bytes = S->tr.size(); B.motif_bytes = S->motifs.size(); B.read_bytes = S->reads.size();
-  B.flank_blob = u8(S->flank); B.lf_off = S->lf_off.data(); B.lf_len = S->lf_len.data(); B.rf_off = S->rf_off.data(); B.rf_len = S->rf_len.data();
-  B.tr_blob = u8(S->tr); B.tr_off = S->tr_off.data(); B.tr_len = S->tr_len.data();
-  B.motif_blob = u8(S->motifs); B.motif_off = S->motif_off.data(); B.set_motif_begin = S->set_begin.data();
-  B.ploidy = S->ploidy.data(); B.genotyper = S->genotyper.data(); B.locus_read_begin = S->lrb.data();
-  B.read_blob = u8(S->reads); B.read_off = S->read_off.data(); B.read_len = S->read_len.data(); B.read_qual = S->rq.data();
-  B.qual_blob = u8(S->quals); B.name_blob = S->names.data(); B.name_off = S->name_off.data();
-  B.is_reverse = S->is_reverse.data(); B.mapq = S->mapq.data(); B.hp_tag = S->hp.data(); B.has_meth = S->has_meth.data();
-  B.start_offset = S->start_offset.data(); B.end_offset = S->end_offset.data();
-  B.mismatch_offsets = S->snp.data(); B.mismatch_off = S->snp_off.data();
-  B.meth = S->meth.data(); B.meth_off = S->moff.data();
-  B.n_quality_filtered = S->n_filtered.data(); B.n_reads_seen = S->n_seen.data();
-  B.contig_blob = S->contigs.data(); B.contig_off = S->contig_off.data(); B.id_blob = S->ids.data(); B.id_off = S->id_off.data();
-  B.struc_blob = S->strucs.data(); B.struc_off = S->struc_off.data(); B.region_start = S->region_start.data(); B.region_end = S->region_end.data();
-  B.cigar = S->cig.data(); B.cigar_off = S->cig_off.data(); B.cigar_ref_pos = S->cig_ref_pos.data();
-  S->skipped_off.push_back(0);
-  for (auto& m : skipped) { S->skipped += m; S->skipped_off.push_back(S->skipped.size()); }
-  B.n_skipped = (int64_t)skipped.size(); B.skipped_blob = S->skipped.data(); B.skipped_off = S->skipped_off.data();
-  if (p->keep_bam4) { B.read_bam4 = S->bam4.data(); B.read_bam4_off = S->bam4_off.data(); B.read_bam4_bytes = tot.bam4; }
-  if (from_device) {  // the per-read arrays are pieces of the slab the kernels filled (pinned mirror); the ASCII reads stay in HBM as well
-    const trgt::ingd::HostOut& D = dev.out;
-    S->slab = dev.slab; dev.slab = trgt::ingd::Slab(); S->slab_pool = h->slab_pool;
-    B.n_reads = D.n_reads; B.read_bytes = std::max<uint64_t>(1, D.read_bytes);
-    B.read_blob = D.reads; B.read_off = D.read_off; B.read_len = D.read_len; B.read_qual = D.rq;
-    B.qual_blob = D.quals; B.name_blob = D.names; B.name_off = D.name_off;
-    B.is_reverse = D.is_reverse; B.mapq = D.mapq; B.hp_tag = D.hp; B.has_meth = D.has_meth;
-    B.start_offset = D.start_offset; B.end_offset = D.end_offset;
-    B.mismatch_offsets = D.snp; B.mismatch_off = D.snp_off; B.meth = D.meth; B.meth_off = D.meth_off;
-    B.cigar = D.cig; B.cigar_off = D.cig_off; B.cigar_ref_pos = D.cig_ref_pos;
-    if (p->keep_bam4) { B.read_bam4 = D.bam4; B.read_bam4_off = D.bam4_off; B.read_bam4_bytes = D.bam4_bytes; }
-    B.read_blob_dev = D.dev_reads; B.read_blob_device = p->ingest_device;
+  // clip_reads (tr.rs:186-196): radius 2 * flank_len
+  void clip(CatalogLocus& l) const {
+    const int64_t rs = l.start - 2ll * p->flank_len, re = l.end + 2ll * p->flank_len;
+    std::vector<Read> clipped;
+    for (auto& r : l.reads) { Read c; if (clip_to_region(r, rs, re, c)) clipped.push_back(std::move(c)); }
+    l.reads.swap(clipped);
   }
-  if (trace) std::fprintf(stderr, "[ingest] %lld loci, %d threads (runs of %lld): catalog+genome %.1f ms, reads %.1f ms (%s; %llu blocks inflated by the workers, %llu found in their caches), arrays %.1f ms\n", (long long)nl, nthr, (long long)run, t1 - t0, t2 - t1, from_device ? "on the device" : "host workers", (unsigned long long)n_inflated.load(), (unsigned long long)n_cache_hits.load(), now() - t2);
-  B.owner = S.release();
-  *out = &reinterpret_cast<BatchStore*>(B.owner)->pub;
-  return TRGT_OK;
+  // extract_reads + clip_reads per locus, loci spread over threads (one file handle each)
+  int host_reads() {
+    std::atomic<int64_t> next{0};
+    auto work_body = [&]() {
+      std::unique_ptr<Bgzf> zp;
+      { std::lock_guard<std::mutex> g(h->idle_mu); if (!h->idle_readers.empty()) { zp = std::move(h->idle_readers.back()); h->idle_readers.pop_back(); } }
+      if (!zp) {
+        zp.reset(new Bgzf(48));
+        if (!zp->open(h->bam_path.c_str())) { for (auto& l : loci) if (l.err.empty()) { l.err = zp->err; break; } return; }
+      }
+      struct Back { trgt_ingest* h; std::unique_ptr<Bgzf>& z; ~Back() { if (z && z->err.empty()) { std::lock_guard<std::mutex> g(h->idle_mu); h->idle_readers.push_back(std::move(z)); } } } back{h, zp};
+      Bgzf& z = *zp;
+      z.block_coff = ~0ull; z.block_csize = 0; z.cur_data = nullptr; z.cur_size = 0; z.pos = 0;
+      const uint64_t inflated0 = z.n_inflated, hits0 = z.n_hits;
+      RawRec rec;
+      for (;;) {
+        const int64_t l0 = next.fetch_add(run);
+        if (l0 >= nl) break;
+        for (int64_t li = l0; li < std::min(nl, l0 + run); ++li) { read_locus(z, rec, loci[(size_t)li]); clip(loci[(size_t)li]); }
+      }
+      n_inflated += z.n_inflated - inflated0; n_cache_hits += z.n_hits - hits0;
+    };
+    auto work = [&]() {  // (an exception must not leave a thread, nor cross the C ABI)
+      try { work_body(); } catch (const std::exception& e) { for (auto& l : loci) if (l.err.empty()) { l.err = std::string("reading the BAM: ") + e.what(); break; } }
+    };
+    run_on_threads(nthr, work);
+    for (auto& l : loci) if (!l.err.empty()) return bad(l.id + ": " + l.err);
+    return TRGT_OK;
+  }
+  // the arrays of trgt_locus_batch_in (+ what the writers need per read): per locus the catalog fields, and where its reads go in the
+  // per-read arrays (sizes here; fill_arrays copies the loci in)
+  void size_arrays() {
+    S.reset(new BatchStore());
+    S->lrb.push_back(0); S->motif_off.push_back(0); S->set_begin.push_back(0);
+    S->contig_off.push_back(0); S->id_off.push_back(0); S->struc_off.push_back(0);
+    at.assign((size_t)nl + 1, BatchAt());
+    for (int64_t li = 0; li < nl; ++li) {
+      CatalogLocus& l = loci[(size_t)li];
+      S->lf_off.push_back(S->flank.size()); S->lf_len.push_back((uint32_t)l.lf.size()); S->flank += l.lf;
+      S->rf_off.push_back(S->flank.size()); S->rf_len.push_back((uint32_t)l.rf.size()); S->flank += l.rf;
+      S->tr_off.push_back(S->tr.size()); S->tr_len.push_back((uint32_t)l.tr.size()); S->tr += l.tr;
+      for (auto& m : l.motifs) { S->motifs += m; S->motif_off.push_back((uint32_t)S->motifs.size()); }
+      S->set_begin.push_back((uint32_t)S->motif_off.size() - 1);
+      S->ploidy.push_back((uint8_t)p->default_ploidy); S->genotyper.push_back((uint8_t)p->genotyper);
+      S->contigs += l.contig; S->contig_off.push_back(S->contigs.size()); S->ids += l.id; S->id_off.push_back(S->ids.size());
+      S->strucs += l.struc; S->struc_off.push_back(S->strucs.size());
+      S->region_start.push_back(l.start); S->region_end.push_back(l.end);
+      S->n_filtered.push_back(from_device ? dev.out.n_filt[li] : l.n_filt); S->n_seen.push_back(from_device ? dev.out.n_seen[li] : l.n_seen);
+      BatchAt n = at[(size_t)li];
+      for (auto& r : l.reads) {
+        ++n.read; n.bytes += r.bases.size(); n.name += r.id.size(); n.snp += r.mismatch_offsets.size(); n.meth += r.has_meth ? r.meth.size() : 0;
+        n.cig += r.cigar.size(); n.bam4 += (r.bases.size() + 1) / 2;
+      }
+      at[(size_t)li + 1] = n;
+      S->lrb.push_back(from_device ? dev.out.lrb[li + 1] : n.read);
+    }
+    tot = at[(size_t)nl];
+    const size_t nr = (size_t)tot.read;
+    S->read_off.resize(nr); S->read_len.resize(nr); S->reads.resize((size_t)tot.bytes); S->quals.resize((size_t)tot.bytes);
+    S->names.resize((size_t)tot.name); S->name_off.assign(nr + 1, 0); S->rq.resize(nr); S->is_reverse.resize(nr); S->mapq.resize(nr); S->hp.resize(nr);
+    S->start_offset.resize(nr); S->end_offset.resize(nr); S->snp.resize((size_t)tot.snp); S->snp_off.assign(nr + 1, 0);
+    S->meth.resize((size_t)tot.meth); S->moff.assign(nr + 1, 0); S->has_meth.resize(nr);
+    S->cig.resize((size_t)tot.cig); S->cig_off.assign(nr + 1, 0); S->cig_ref_pos.resize(nr);
+    if (p->keep_bam4) { S->bam4.assign((size_t)tot.bam4 + 1, 0); S->bam4_off.assign(nr + 1, 0); }  // the reads once more, two bases per byte (half the bytes to move to the GPU)
+  }
+  // the reads of locus li into their places; false: the 4-bit form does not have the size it was given
+  bool fill_locus(int64_t li) {
+    BatchAt n = at[(size_t)li];
+    const size_t r0 = (size_t)n.read;
+    for (auto& r : loci[(size_t)li].reads) {
+      const size_t k = (size_t)n.read;
+      S->read_off[k] = n.bytes; S->read_len[k] = (uint32_t)r.bases.size();
+      std::memcpy(&S->reads[0] + n.bytes, r.bases.data(), r.bases.size());
+      std::memcpy(&S->quals[0] + n.bytes, r.quals.data(), std::min(r.quals.size(), r.bases.size()));
+      std::memcpy(&S->names[0] + n.name, r.id.data(), r.id.size());
+      S->rq[k] = r.rq; S->is_reverse[k] = r.is_reverse ? 1 : 0; S->mapq[k] = r.mapq; S->hp[k] = (int16_t)r.hp;
+      S->start_offset[k] = r.start_offset; S->end_offset[k] = r.end_offset;
+      std::copy(r.mismatch_offsets.begin(), r.mismatch_offsets.end(), S->snp.begin() + (ptrdiff_t)n.snp);
+      S->has_meth[k] = r.has_meth ? 1 : 0;
+      if (r.has_meth) std::copy(r.meth.begin(), r.meth.end(), S->meth.begin() + (ptrdiff_t)n.meth);
+      std::copy(r.cigar.begin(), r.cigar.end(), S->cig.begin() + (ptrdiff_t)n.cig); S->cig_ref_pos[k] = r.ref_pos;
+      ++n.read; n.bytes += r.bases.size(); n.name += r.id.size(); n.snp += r.mismatch_offsets.size(); n.meth += r.has_meth ? r.meth.size() : 0; n.cig += r.cigar.size();
+      S->name_off[k + 1] = n.name; S->snp_off[k + 1] = n.snp; S->moff[k + 1] = n.meth; S->cig_off[k + 1] = n.cig;
+    }
+    bool ok = true;
+    if (p->keep_bam4 && n.read > r0) {
+      const uint64_t base = at[(size_t)li].bam4;
+      const int64_t got = trgt_reads_pack_bam4((const uint8_t*)S->reads.data(), (int64_t)(n.read - r0), S->read_off.data() + r0, S->read_len.data() + r0, S->bam4.data() + base, S->bam4_off.data() + r0);
+      ok = got == (int64_t)(at[(size_t)li + 1].bam4 - base);
+      for (size_t k = r0; k < (size_t)n.read; ++k) S->bam4_off[k] += base;
+    }
+    std::vector<Read>().swap(loci[(size_t)li].reads);  // (freed by the worker, not by the caller's thread at the end)
+    return ok;
+  }
+  int fill_arrays() {
+    std::atomic<int64_t> next_fill{0};
+    std::atomic<int> fill_failed{0};
+    auto fill = [&]() {
+      try {
+        for (;;) {
+          const int64_t l0 = next_fill.fetch_add(16);
+          if (l0 >= nl) break;
+          for (int64_t li = l0; li < std::min(nl, l0 + 16); ++li) if (!fill_locus(li)) fill_failed = 1;
+        }
+      } catch (const std::exception&) { fill_failed = 1; }
+    };
+    run_on_threads(nthr, fill);
+    return fill_failed ? bad("trgt_ingest: assembling the batch failed") : TRGT_OK;
+  }
+  // the per-read arrays the host path assembled, as the view the device path returns
+  trgt::ingd::HostOut host_view() {
+    if (S->reads.empty()) S->reads.push_back('\0');
+    auto u8 = [](const std::string& s) { return (const uint8_t*)s.data(); };
+    trgt::ingd::HostOut V;
+    V.n_reads = (int64_t)S->read_off.size(); V.read_bytes = S->reads.size();
+    V.read_off = S->read_off.data(); V.read_len = S->read_len.data(); V.reads = u8(S->reads); V.quals = u8(S->quals); V.names = S->names.data(); V.name_off = S->name_off.data();
+    V.rq = S->rq.data(); V.is_reverse = S->is_reverse.data(); V.mapq = S->mapq.data(); V.hp = S->hp.data(); V.start_offset = S->start_offset.data(); V.end_offset = S->end_offset.data();
+    V.snp = S->snp.data(); V.snp_off = S->snp_off.data(); V.meth = S->meth.data(); V.meth_off = S->moff.data(); V.has_meth = S->has_meth.data();
+    V.cig = S->cig.data(); V.cig_off = S->cig_off.data(); V.cig_ref_pos = S->cig_ref_pos.data();
+    if (p->keep_bam4) { V.bam4 = S->bam4.data(); V.bam4_off = S->bam4_off.data(); V.bam4_bytes = tot.bam4; }
+    return V;
+  }
+  // the one place a per-read pointer of the public struct is set (an empty blob is handed out as one NUL byte: read_bytes >= 1)
+  void publish_reads(trgt_ingest_batch& B, const trgt::ingd::HostOut& V) const {
+    B.n_reads = V.n_reads; B.read_bytes = std::max<uint64_t>(1, V.read_bytes);
+    B.read_blob = V.reads; B.read_off = V.read_off; B.read_len = V.read_len; B.read_qual = V.rq;
+    B.qual_blob = V.quals; B.name_blob = V.names; B.name_off = V.name_off;
+    B.is_reverse = V.is_reverse; B.mapq = V.mapq; B.hp_tag = V.hp; B.has_meth = V.has_meth;
+    B.start_offset = V.start_offset; B.end_offset = V.end_offset;
+    B.mismatch_offsets = V.snp; B.mismatch_off = V.snp_off; B.meth = V.meth; B.meth_off = V.meth_off;
+    B.cigar = V.cig; B.cigar_off = V.cig_off; B.cigar_ref_pos = V.cig_ref_pos;
+    if (p->keep_bam4) { B.read_bam4 = V.bam4; B.read_bam4_off = V.bam4_off; B.read_bam4_bytes = V.bam4_bytes; }
+    B.read_blob_dev = V.dev_reads; B.read_blob_device = V.dev_reads ? p->ingest_device : -1;
+  }
+  int publish(trgt_ingest_batch** out) {
+    trgt_ingest_batch& B = S->pub;
+    std::memset(&B, 0, sizeof B);
+    auto u8 = [](const std::string& s) { return (const uint8_t*)s.data(); };
+    if (S->flank.empty()) S->flank.push_back('\0');
+    if (S->tr.empty()) S->tr.push_back('\0');
+    B.n_loci = nl; B.n_motifs = (int64_t)S->motif_off.size() - 1;
+    B.flank_bytes = S->flank.size(); B.tr_bytes = S->tr.size(); B.motif_bytes = S->motifs.size();
+    B.flank_blob = u8(S->flank); B.lf_off = S->lf_off.data(); B.lf_len = S->lf_len.data(); B.rf_off = S->rf_off.data(); B.rf_len = S->rf_len.data();
+    B.tr_blob = u8(S->tr); B.tr_off = S->tr_off.data(); B.tr_len = S->tr_len.data();
+    B.motif_blob = u8(S->motifs); B.motif_off = S->motif_off.data(); B.set_motif_begin = S->set_begin.data();
+    B.ploidy = S->ploidy.data(); B.genotyper = S->genotyper.data(); B.locus_read_begin = S->lrb.data();
+    B.n_quality_filtered = S->n_filtered.data(); B.n_reads_seen = S->n_seen.data();
+    B.contig_blob = S->contigs.data(); B.contig_off = S->contig_off.data(); B.id_blob = S->ids.data(); B.id_off = S->id_off.data();
+    B.struc_blob = S->strucs.data(); B.struc_off = S->struc_off.data(); B.region_start = S->region_start.data(); B.region_end = S->region_end.data();
+    S->skipped_off.push_back(0);
+    for (auto& m : skipped) { S->skipped += m; S->skipped_off.push_back(S->skipped.size()); }
+    B.n_skipped = (int64_t)skipped.size(); B.skipped_blob = S->skipped.data(); B.skipped_off = S->skipped_off.data();
+    // device: the per-read arrays are pieces of the slab the kernels filled (pinned mirror), and the ASCII reads stay in HBM as well
+    if (from_device) S->lease = std::move(dev.lease);
+    publish_reads(B, from_device ? dev.out : host_view());
+    if (trace) std::fprintf(stderr, "[ingest] %lld loci, %d threads (runs of %lld): catalog+genome %.1f ms, reads %.1f ms (%s; %llu blocks inflated by the workers, %llu found in their caches), arrays %.1f ms\n", (long long)nl, nthr, (long long)run, t1 - t0, t2 - t1, from_device ? "on the device" : "host workers", (unsigned long long)n_inflated.load(), (unsigned long long)n_cache_hits.load(), trgt::ingd::now_ms() - t2);
+    B.owner = S.release();
+    *out = &reinterpret_cast<BatchStore*>(B.owner)->pub;
+    return TRGT_OK;
+  }
+};
+
+static int ingest_batch_impl(trgt_ingest* h, const trgt_ingest_params* p, const char* bed_path, int64_t first_locus, int64_t max_loci,
+                             trgt_ingest_batch** out) {
+  if (!h || !p || !bed_path || !out) return TRGT_ERR_INVALID;
+  *out = nullptr;
+  BatchCall c{h, p};
+  if (const int rc = c.read_catalog(bed_path, first_locus, max_loci)) return rc;
+  if (const int rc = c.device_attempt()) return rc;
+  c.size_workers();
+  if (!c.from_device) if (const int rc = c.host_reads()) return rc;
+  c.t2 = trgt::ingd::now_ms();
+  c.size_arrays();
+  if (!c.from_device) if (const int rc = c.fill_arrays()) return rc;
+  return c.publish(out);
 }
 
 // exceptions (std::bad_alloc on a corrupt size field, ...) never cross the C ABI

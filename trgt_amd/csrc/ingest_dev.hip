@@ -17,7 +17,6 @@
 // call back to the host path of ingest.hip, which then produces the data or the error message.
 #include <zlib.h>
 
-#include <chrono>
 #include <cstring>
 
 #include "common.hpp"
@@ -787,150 +786,188 @@ uint8_t* slot_src(Slot* s, size_t bytes, std::string& err) {
   } while (0)
 #define ING_NEED(buf, bytes) do { if (!(buf).need(bytes)) { err = "trgt_ingest (device): out of device memory"; return TRGT_ERR_NOMEM; } } while (0)
 
-int slot_run(Slot* s, const RunIn& in, SlabPool& pool, RunOut& out, std::string& err) {
-  auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  out = RunOut();
-  ING_TRY(hipSetDevice(s->device));
-  hipStream_t st = s->stream;
-  const double t0 = now();
-  const uint32_t nb = (uint32_t)in.n_blocks, nl = (uint32_t)in.n_loci;
-  if (!s->tab_ready) {
+// One run of a slot: the stages of slot_run in the order of run().  A stage returns TRGT_OK or a TRGT_ERR_* code (with `err`); one that sets
+// out.fallback ends the run with TRGT_OK.  Everything goes to the slot's stream in this order; `out` owns the slab from take_slab on.
+struct SlotRun {
+  Slot* s; const RunIn& in; const std::shared_ptr<SlabPool>& pool; RunOut& out; std::string& err;
+  hipStream_t st = nullptr;
+  uint32_t nb = 0, nl = 0;
+  uint8_t *h_blocks = nullptr, *h_crc = nullptr, *h_loci = nullptr, *h_chunks = nullptr, *h_status = nullptr;  // pieces of small_pin
+  WalkOut* h_walk = nullptr; uint64_t* h_first = nullptr; Counters* h_counters = nullptr;
+  uint64_t n_pre = 0;                       // reads the walk kept: one wave each from read_sizes_kernel on
+  SlabLayout a{}; uint8_t* D = nullptr; uint8_t* H = nullptr;  // the batch's slab: layout, device copy, pinned mirror
+  double t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0;
+
+  int crc_tables_once() {
+    ING_TRY(hipSetDevice(s->device));
+    st = s->stream;
+    t0 = now_ms();
+    nb = (uint32_t)in.n_blocks; nl = (uint32_t)in.n_loci;
+    if (s->tab_ready) return TRGT_OK;
     ING_NEED(s->d_tab, sizeof(CrcTables));
     CrcTables T; make_crc_tables(T);
     ING_TRY(hipMemcpy(s->d_tab.p, &T, sizeof T, hipMemcpyHostToDevice));
     s->tab_ready = true;
+    return TRGT_OK;
   }
-  // ---- upload: compressed bytes (staged by the caller in slot_src()), block table, footer CRCs, locus and chunk tables
-  ING_NEED(s->d_src, in.src_bytes + 64); ING_NEED(s->d_blocks, (size_t)nb * sizeof(infl::BlockDesc) + 64); ING_NEED(s->d_crc, (size_t)nb * 4 + 64);
-  ING_NEED(s->d_infl, in.infl_bytes + 256); ING_NEED(s->d_status, (size_t)nb + 64); ING_NEED(s->d_counter, 64);
-  ING_NEED(s->d_loci, (size_t)nl * sizeof(LocusDesc) + 64); ING_NEED(s->d_chunks, (size_t)in.n_chunks * sizeof(ChunkDesc) + 64);
-  ING_NEED(s->d_list, (size_t)nl * in.reservoir * 8 + 64); ING_NEED(s->d_walk, (size_t)nl * sizeof(WalkOut) + 64); ING_NEED(s->d_first, ((size_t)nl + 1) * 8 + 64);
-  ING_NEED(s->d_counters, sizeof(Counters)); ING_NEED(s->d_lrb, ((size_t)nl + 1) * 8 + 64);
-  const size_t small_bytes = (size_t)nb * (sizeof(infl::BlockDesc) + 4 + 1) + (size_t)nl * (sizeof(LocusDesc) + sizeof(WalkOut) + 16) + (size_t)in.n_chunks * sizeof(ChunkDesc) + sizeof(Counters) + 1024;
-  if (!s->small_pin.need(small_bytes)) { err = "trgt_ingest (device): no pinned memory"; return TRGT_ERR_NOMEM; }
-  uint8_t* sp = (uint8_t*)s->small_pin.p;
-  auto carve = [&](size_t bytes) { uint8_t* p = sp; sp += (bytes + 63) & ~(size_t)63; return p; };
-  uint8_t* h_blocks = carve((size_t)nb * sizeof(infl::BlockDesc)); uint8_t* h_crc = carve((size_t)nb * 4); uint8_t* h_loci = carve((size_t)nl * sizeof(LocusDesc));
-  uint8_t* h_chunks = carve((size_t)in.n_chunks * sizeof(ChunkDesc)); uint8_t* h_status = carve(nb); WalkOut* h_walk = (WalkOut*)carve((size_t)nl * sizeof(WalkOut));
-  uint64_t* h_first = (uint64_t*)carve(((size_t)nl + 1) * 8); Counters* h_counters = (Counters*)carve(sizeof(Counters));
-  std::memcpy(h_blocks, in.blocks, (size_t)nb * sizeof(infl::BlockDesc)); std::memcpy(h_crc, in.crc, (size_t)nb * 4);
-  std::memcpy(h_loci, in.loci, (size_t)nl * sizeof(LocusDesc)); std::memcpy(h_chunks, in.chunks, (size_t)in.n_chunks * sizeof(ChunkDesc));
-  ING_TRY(hipMemcpyAsync(s->d_src.p, s->src_pin.p, in.src_bytes, hipMemcpyHostToDevice, st));
-  ING_TRY(hipMemcpyAsync(s->d_blocks.p, h_blocks, (size_t)nb * sizeof(infl::BlockDesc), hipMemcpyHostToDevice, st));
-  ING_TRY(hipMemcpyAsync(s->d_crc.p, h_crc, (size_t)nb * 4, hipMemcpyHostToDevice, st));
-  ING_TRY(hipMemcpyAsync(s->d_loci.p, h_loci, (size_t)nl * sizeof(LocusDesc), hipMemcpyHostToDevice, st));
-  ING_TRY(hipMemcpyAsync(s->d_chunks.p, h_chunks, (size_t)in.n_chunks * sizeof(ChunkDesc), hipMemcpyHostToDevice, st));
-  ING_TRY(hipMemsetAsync(s->d_counter.p, 0, 64, st));
-  ING_TRY(hipMemsetAsync(s->d_counters.p, 0, sizeof(Counters), st));
-  ING_TRY(hipMemsetAsync(s->d_status.p, 0, (size_t)nb + 64, st));
-  // ---- inflate + CRC-32
-  const unsigned waves_per_cu = in.waves_per_cu > 0 ? (unsigned)std::min(in.waves_per_cu, 16) : 12u;
-  int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
-  trgt::inflate_launch((void*)st, (const uint8_t*)s->d_src.p, (const infl::BlockDesc*)s->d_blocks.p, nb, (uint8_t*)s->d_infl.p, (uint8_t*)s->d_status.p, (unsigned*)s->d_counter.p,
-                       (unsigned)cus * waves_per_cu);
-  if (nb) hipLaunchKernelGGL(crc32_blocks_kernel, dim3(nb), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const infl::BlockDesc*)s->d_blocks.p, (const uint32_t*)s->d_crc.p, nb,
-                             (const CrcTables*)s->d_tab.p, (uint8_t*)s->d_status.p, (uint32_t*)nullptr);
-  ING_TRY(hipGetLastError());
-  ING_TRY(hipMemcpyAsync(h_status, s->d_status.p, nb, hipMemcpyDeviceToHost, st));
-  ING_TRY(slot_wait(s));
-  const double t1 = now();
+  // compressed bytes (staged by the caller in slot_src()), block table, footer CRCs, locus and chunk tables
+  int size_and_upload() {
+    ING_NEED(s->d_src, in.src_bytes + 64); ING_NEED(s->d_blocks, (size_t)nb * sizeof(infl::BlockDesc) + 64); ING_NEED(s->d_crc, (size_t)nb * 4 + 64);
+    ING_NEED(s->d_infl, in.infl_bytes + 256); ING_NEED(s->d_status, (size_t)nb + 64); ING_NEED(s->d_counter, 64);
+    ING_NEED(s->d_loci, (size_t)nl * sizeof(LocusDesc) + 64); ING_NEED(s->d_chunks, (size_t)in.n_chunks * sizeof(ChunkDesc) + 64);
+    ING_NEED(s->d_list, (size_t)nl * in.reservoir * 8 + 64); ING_NEED(s->d_walk, (size_t)nl * sizeof(WalkOut) + 64); ING_NEED(s->d_first, ((size_t)nl + 1) * 8 + 64);
+    ING_NEED(s->d_counters, sizeof(Counters)); ING_NEED(s->d_lrb, ((size_t)nl + 1) * 8 + 64);
+    const size_t small_bytes = (size_t)nb * (sizeof(infl::BlockDesc) + 4 + 1) + (size_t)nl * (sizeof(LocusDesc) + sizeof(WalkOut) + 16) + (size_t)in.n_chunks * sizeof(ChunkDesc) + sizeof(Counters) + 1024;
+    if (!s->small_pin.need(small_bytes)) { err = "trgt_ingest (device): no pinned memory"; return TRGT_ERR_NOMEM; }
+    uint8_t* sp = (uint8_t*)s->small_pin.p;
+    auto carve = [&](size_t bytes) { uint8_t* p = sp; sp += (bytes + 63) & ~(size_t)63; return p; };
+    h_blocks = carve((size_t)nb * sizeof(infl::BlockDesc)); h_crc = carve((size_t)nb * 4); h_loci = carve((size_t)nl * sizeof(LocusDesc));
+    h_chunks = carve((size_t)in.n_chunks * sizeof(ChunkDesc)); h_status = carve(nb); h_walk = (WalkOut*)carve((size_t)nl * sizeof(WalkOut));
+    h_first = (uint64_t*)carve(((size_t)nl + 1) * 8); h_counters = (Counters*)carve(sizeof(Counters));
+    std::memcpy(h_blocks, in.blocks, (size_t)nb * sizeof(infl::BlockDesc)); std::memcpy(h_crc, in.crc, (size_t)nb * 4);
+    std::memcpy(h_loci, in.loci, (size_t)nl * sizeof(LocusDesc)); std::memcpy(h_chunks, in.chunks, (size_t)in.n_chunks * sizeof(ChunkDesc));
+    ING_TRY(hipMemcpyAsync(s->d_src.p, s->src_pin.p, in.src_bytes, hipMemcpyHostToDevice, st));
+    ING_TRY(hipMemcpyAsync(s->d_blocks.p, h_blocks, (size_t)nb * sizeof(infl::BlockDesc), hipMemcpyHostToDevice, st));
+    ING_TRY(hipMemcpyAsync(s->d_crc.p, h_crc, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+    ING_TRY(hipMemcpyAsync(s->d_loci.p, h_loci, (size_t)nl * sizeof(LocusDesc), hipMemcpyHostToDevice, st));
+    ING_TRY(hipMemcpyAsync(s->d_chunks.p, h_chunks, (size_t)in.n_chunks * sizeof(ChunkDesc), hipMemcpyHostToDevice, st));
+    ING_TRY(hipMemsetAsync(s->d_counter.p, 0, 64, st));
+    ING_TRY(hipMemsetAsync(s->d_counters.p, 0, sizeof(Counters), st));
+    ING_TRY(hipMemsetAsync(s->d_status.p, 0, (size_t)nb + 64, st));
+    return TRGT_OK;
+  }
+  int inflate_and_crc() {
+    const unsigned waves_per_cu = in.waves_per_cu > 0 ? (unsigned)std::min(in.waves_per_cu, 16) : 12u;
+    int cus = 256; (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, s->device);
+    trgt::inflate_launch((void*)st, (const uint8_t*)s->d_src.p, (const infl::BlockDesc*)s->d_blocks.p, nb, (uint8_t*)s->d_infl.p, (uint8_t*)s->d_status.p, (unsigned*)s->d_counter.p,
+                         (unsigned)cus * waves_per_cu);
+    if (nb) hipLaunchKernelGGL(crc32_blocks_kernel, dim3(nb), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const infl::BlockDesc*)s->d_blocks.p, (const uint32_t*)s->d_crc.p, nb,
+                               (const CrcTables*)s->d_tab.p, (uint8_t*)s->d_status.p, (uint32_t*)nullptr);
+    ING_TRY(hipGetLastError());
+    ING_TRY(hipMemcpyAsync(h_status, s->d_status.p, nb, hipMemcpyDeviceToHost, st));
+    ING_TRY(slot_wait(s));
+    t1 = now_ms();
+    return TRGT_OK;
+  }
   // a block the device declined goes through zlib here (rare: the kernel takes every stream zlib level 1-9 writes); a block that does not
   // inflate to its ISIZE or whose CRC-32 differs sends the call to the host path, which reports it
-  for (uint32_t b = 0; b < nb; ++b) {
-    if (h_status[b] == 1) continue;
-    if (h_status[b] == 2) { out.fallback = FB_BLOCK; return TRGT_OK; }
-    const infl::BlockDesc& bd = in.blocks[b];
-    std::vector<uint8_t> tmp(bd.dst_len);
-    z_stream zs; std::memset(&zs, 0, sizeof zs);
-    if (inflateInit2(&zs, -15) != Z_OK) { out.fallback = FB_BLOCK; return TRGT_OK; }
-    zs.next_in = (Bytef*)s->src_pin.p + bd.src_off; zs.avail_in = bd.src_len; zs.next_out = tmp.data(); zs.avail_out = bd.dst_len;
-    const int rc = inflate(&zs, Z_FINISH);
-    const bool good = rc == Z_STREAM_END && zs.avail_out == 0 && trgt::crc32_fast(tmp.data(), bd.dst_len) == in.crc[b];
-    inflateEnd(&zs);
-    if (!good) { out.fallback = FB_BLOCK; return TRGT_OK; }
-    ING_TRY(hipMemcpyAsync((uint8_t*)s->d_infl.p + bd.dst_off, tmp.data(), bd.dst_len, hipMemcpyHostToDevice, st));
+  int rescue_declined_blocks() {
+    for (uint32_t b = 0; b < nb; ++b) {
+      if (h_status[b] == 1) continue;
+      if (h_status[b] == 2) { out.fallback = FB_BLOCK; return TRGT_OK; }
+      const infl::BlockDesc& bd = in.blocks[b];
+      std::vector<uint8_t> tmp(bd.dst_len);
+      z_stream zs; std::memset(&zs, 0, sizeof zs);
+      if (inflateInit2(&zs, -15) != Z_OK) { out.fallback = FB_BLOCK; return TRGT_OK; }
+      zs.next_in = (Bytef*)s->src_pin.p + bd.src_off; zs.avail_in = bd.src_len; zs.next_out = tmp.data(); zs.avail_out = bd.dst_len;
+      const int rc = inflate(&zs, Z_FINISH);
+      const bool good = rc == Z_STREAM_END && zs.avail_out == 0 && trgt::crc32_fast(tmp.data(), bd.dst_len) == in.crc[b];
+      inflateEnd(&zs);
+      if (!good) { out.fallback = FB_BLOCK; return TRGT_OK; }
+      ING_TRY(hipMemcpyAsync((uint8_t*)s->d_infl.p + bd.dst_off, tmp.data(), bd.dst_len, hipMemcpyHostToDevice, st));
+      ING_TRY(slot_wait(s));
+      ++out.blocks_host_inflated;
+    }
+    return TRGT_OK;
+  }
+  int record_walk() {
+    if (nl) hipLaunchKernelGGL(walk_kernel, dim3(nl), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const LocusDesc*)s->d_loci.p, (const ChunkDesc*)s->d_chunks.p, nl, in.reservoir, in.min_rq,
+                               (uint64_t*)s->d_list.p, (WalkOut*)s->d_walk.p);
+    ING_TRY(hipGetLastError());
+    ING_TRY(hipMemcpyAsync(h_walk, s->d_walk.p, (size_t)nl * sizeof(WalkOut), hipMemcpyDeviceToHost, st));
     ING_TRY(slot_wait(s));
-    ++out.blocks_host_inflated;
+    t2 = now_ms();
+    for (uint32_t l = 0; l < nl; ++l) {
+      if (h_walk[l].status == WS_ERROR) { out.fallback = FB_WALK; return TRGT_OK; }
+      h_first[l] = n_pre; n_pre += std::min(h_walk[l].n_kept, in.reservoir);  // (n_kept counts every read that passed the filters: beyond the reservoir they replaced others)
+    }
+    h_first[nl] = n_pre;
+    if (n_pre >= (1ull << 31)) out.fallback = FB_WALK;
+    return TRGT_OK;
   }
-  // ---- the record walk
-  if (nl) hipLaunchKernelGGL(walk_kernel, dim3(nl), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const LocusDesc*)s->d_loci.p, (const ChunkDesc*)s->d_chunks.p, nl, in.reservoir, in.min_rq,
-                             (uint64_t*)s->d_list.p, (WalkOut*)s->d_walk.p);
-  ING_TRY(hipGetLastError());
-  ING_TRY(hipMemcpyAsync(h_walk, s->d_walk.p, (size_t)nl * sizeof(WalkOut), hipMemcpyDeviceToHost, st));
-  ING_TRY(slot_wait(s));
-  const double t2 = now();
-  uint64_t n_pre = 0;
-  for (uint32_t l = 0; l < nl; ++l) {
-    if (h_walk[l].status == WS_ERROR) { out.fallback = FB_WALK; return TRGT_OK; }
-    h_first[l] = n_pre; n_pre += std::min(h_walk[l].n_kept, in.reservoir);  // (n_kept counts every read that passed the filters: beyond the reservoir they replaced others)
-  }
-  h_first[nl] = n_pre;
-  if (n_pre >= (1ull << 31)) { out.fallback = FB_WALK; return TRGT_OK; }
-  ING_NEED(s->d_info, (size_t)(n_pre + 1) * sizeof(ReadInfo)); ING_NEED(s->d_off, (size_t)(n_pre + 1) * sizeof(ReadOff));
-  ING_TRY(hipMemcpyAsync(s->d_first.p, h_first, ((size_t)nl + 1) * 8, hipMemcpyHostToDevice, st));
-  if (n_pre) hipLaunchKernelGGL(read_sizes_kernel, dim3((unsigned)n_pre), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const LocusDesc*)s->d_loci.p, nl, (const uint64_t*)s->d_first.p, in.reservoir,
-                                (const uint64_t*)s->d_list.p, n_pre, (ReadInfo*)s->d_info.p, (Counters*)s->d_counters.p);
-  auto scan = [&]() {
+  void scan() {
     hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, st, (const ReadInfo*)s->d_info.p, n_pre, (ReadOff*)s->d_off.p, (const uint64_t*)s->d_first.p, nl, (uint64_t*)s->d_lrb.p, (Counters*)s->d_counters.p);
-  };
-  scan();
-  ING_TRY(hipGetLastError());
-  ING_TRY(hipMemcpyAsync(h_counters, s->d_counters.p, sizeof(Counters), hipMemcpyDeviceToHost, st));
-  ING_TRY(slot_wait(s));
-  if (h_counters->n_tagged) {  // reads with MM + ML: get_meth, then the sizes once more
-    ING_NEED(s->d_scratch, (size_t)h_counters->meth_scratch + 64);
-    hipLaunchKernelGGL(read_meth_kernel, dim3((unsigned)n_pre), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, n_pre, (ReadInfo*)s->d_info.p, (uint8_t*)s->d_scratch.p, (Counters*)s->d_counters.p);
+  }
+  int read_sizes_and_scan() {
+    ING_NEED(s->d_info, (size_t)(n_pre + 1) * sizeof(ReadInfo)); ING_NEED(s->d_off, (size_t)(n_pre + 1) * sizeof(ReadOff));
+    ING_TRY(hipMemcpyAsync(s->d_first.p, h_first, ((size_t)nl + 1) * 8, hipMemcpyHostToDevice, st));
+    if (n_pre) hipLaunchKernelGGL(read_sizes_kernel, dim3((unsigned)n_pre), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const LocusDesc*)s->d_loci.p, nl, (const uint64_t*)s->d_first.p, in.reservoir,
+                                  (const uint64_t*)s->d_list.p, n_pre, (ReadInfo*)s->d_info.p, (Counters*)s->d_counters.p);
     scan();
     ING_TRY(hipGetLastError());
     ING_TRY(hipMemcpyAsync(h_counters, s->d_counters.p, sizeof(Counters), hipMemcpyDeviceToHost, st));
     ING_TRY(slot_wait(s));
-    if (h_counters->meth_flag) { out.fallback = FB_METH; return TRGT_OK; }
+    return TRGT_OK;
   }
-  const double t3 = now();
-  // ---- the slab of the batch: every per-read array a 64-byte aligned piece, device copy + pinned mirror
-  const uint64_t nr = h_counters->tot[0], n_bytes = h_counters->tot[1], n_name = h_counters->tot[2], n_snp = h_counters->tot[3], n_meth = h_counters->tot[4], n_cig = h_counters->tot[5],
-                 n_bam4 = in.keep_bam4 ? h_counters->tot[6] : 0;
-  size_t at = 0;
-  auto piece = [&](size_t bytes) { const size_t a = at; at += (bytes + 63) & ~(size_t)63; return a; };
-  const size_t a_lrb = piece(((size_t)nl + 1) * 8), a_nfilt = piece((size_t)nl * 4), a_nseen = piece((size_t)nl * 8), a_roff = piece((nr + 1) * 8), a_rlen = piece((nr + 1) * 4),
-               a_reads = piece(n_bytes + 1), a_quals = piece(n_bytes + 1), a_names = piece(n_name + 1), a_noff = piece((nr + 1) * 8), a_rq = piece((nr + 1) * 8), a_rev = piece(nr + 1), a_mapq = piece(nr + 1),
-               a_hp = piece((nr + 1) * 2), a_so = piece((nr + 1) * 4), a_eo = piece((nr + 1) * 4), a_snp = piece((n_snp + 1) * 4), a_soff = piece((nr + 1) * 8), a_meth = piece(n_meth + 1),
-               a_moff = piece((nr + 1) * 8), a_hm = piece(nr + 1), a_cig = piece((n_cig + 1) * 4), a_coff = piece((nr + 1) * 8), a_cpos = piece((nr + 1) * 8),
-               a_b4 = piece(in.keep_bam4 ? n_bam4 + 1 : 0), a_b4off = piece(in.keep_bam4 ? (nr + 1) * 8 : 0);
-  if (!pool.take(s->device, at + 64, out.slab)) { err = "trgt_ingest (device): no memory for the batch's arrays"; return TRGT_ERR_NOMEM; }
-  uint8_t* D = (uint8_t*)out.slab.dev; uint8_t* H = (uint8_t*)out.slab.pin;
-  OutPtrs o;
-  o.read_off = (uint64_t*)(D + a_roff); o.read_len = (uint32_t*)(D + a_rlen); o.reads = D + a_reads; o.quals = D + a_quals; o.names = (char*)(D + a_names); o.name_off = (uint64_t*)(D + a_noff);
-  o.rq = (double*)(D + a_rq); o.is_reverse = D + a_rev; o.mapq = D + a_mapq; o.hp = (int16_t*)(D + a_hp); o.start_offset = (int32_t*)(D + a_so); o.end_offset = (int32_t*)(D + a_eo);
-  o.snp = (int32_t*)(D + a_snp); o.snp_off = (uint64_t*)(D + a_soff); o.meth = D + a_meth; o.meth_off = (uint64_t*)(D + a_moff); o.has_meth = D + a_hm; o.cig = (uint32_t*)(D + a_cig);
-  o.cig_off = (uint64_t*)(D + a_coff); o.cig_ref_pos = (int64_t*)(D + a_cpos); o.bam4 = in.keep_bam4 ? D + a_b4 : nullptr; o.bam4_off = in.keep_bam4 ? (uint64_t*)(D + a_b4off) : nullptr;
-  if (n_bytes == 0) ING_TRY(hipMemsetAsync(D + a_reads, 0, 64, st));  // (an empty blob is handed out as one NUL byte, like the host path's)
-  if (nr == 0) ING_TRY(hipMemsetAsync(D + a_noff, 0, 64, st));  // (the [n_reads + 1] offset arrays hold a 0 at least)
-  if (nr == 0) { ING_TRY(hipMemsetAsync(D + a_soff, 0, 64, st)); ING_TRY(hipMemsetAsync(D + a_moff, 0, 64, st)); ING_TRY(hipMemsetAsync(D + a_coff, 0, 64, st)); }
-  if (n_pre) hipLaunchKernelGGL(read_fill_kernel, dim3((unsigned)n_pre), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const LocusDesc*)s->d_loci.p, (const ReadInfo*)s->d_info.p, (const ReadOff*)s->d_off.p, n_pre,
-                                (const uint8_t*)s->d_scratch.p, o);
-  ING_TRY(hipGetLastError());
-  ING_TRY(hipMemcpyAsync(D + a_lrb, s->d_lrb.p, ((size_t)nl + 1) * 8, hipMemcpyDeviceToDevice, st));
-  const double t4 = now();
-  ING_TRY(hipMemcpyAsync(H, D, at, hipMemcpyDeviceToHost, st));
-  ING_TRY(slot_wait(s));
-  {  // per locus counters: known to the host since the walk
-    int32_t* nf = (int32_t*)(H + a_nfilt); int64_t* ns = (int64_t*)(H + a_nseen);
-    for (uint32_t l = 0; l < nl; ++l) { nf[l] = (int32_t)h_walk[l].n_filt; ns[l] = (int64_t)h_walk[l].n_kept; }
+  // reads with MM + ML: get_meth, then the sizes once more
+  int methylation_pass() {
+    if (h_counters->n_tagged) {
+      ING_NEED(s->d_scratch, (size_t)h_counters->meth_scratch + 64);
+      hipLaunchKernelGGL(read_meth_kernel, dim3((unsigned)n_pre), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, n_pre, (ReadInfo*)s->d_info.p, (uint8_t*)s->d_scratch.p, (Counters*)s->d_counters.p);
+      scan();
+      ING_TRY(hipGetLastError());
+      ING_TRY(hipMemcpyAsync(h_counters, s->d_counters.p, sizeof(Counters), hipMemcpyDeviceToHost, st));
+      ING_TRY(slot_wait(s));
+      if (h_counters->meth_flag) { out.fallback = FB_METH; return TRGT_OK; }
+    }
+    t3 = now_ms();
+    return TRGT_OK;
   }
-  HostOut& R = out.out;
-  R.n_reads = (int64_t)nr; R.read_bytes = n_bytes; R.name_bytes = n_name; R.snp_n = n_snp; R.meth_n = n_meth; R.cig_n = n_cig; R.bam4_bytes = n_bam4;
-  R.lrb = (const uint64_t*)(H + a_lrb); R.n_filt = (const int32_t*)(H + a_nfilt); R.n_seen = (const int64_t*)(H + a_nseen);
-  R.read_off = (const uint64_t*)(H + a_roff); R.read_len = (const uint32_t*)(H + a_rlen); R.reads = H + a_reads; R.quals = H + a_quals; R.names = (const char*)(H + a_names);
-  R.name_off = (const uint64_t*)(H + a_noff); R.rq = (const double*)(H + a_rq); R.is_reverse = H + a_rev; R.mapq = H + a_mapq; R.hp = (const int16_t*)(H + a_hp);
-  R.start_offset = (const int32_t*)(H + a_so); R.end_offset = (const int32_t*)(H + a_eo); R.snp = (const int32_t*)(H + a_snp); R.snp_off = (const uint64_t*)(H + a_soff);
-  R.meth = H + a_meth; R.meth_off = (const uint64_t*)(H + a_moff); R.has_meth = H + a_hm; R.cig = (const uint32_t*)(H + a_cig); R.cig_off = (const uint64_t*)(H + a_coff);
-  R.cig_ref_pos = (const int64_t*)(H + a_cpos);
-  if (in.keep_bam4) { R.bam4 = H + a_b4; R.bam4_off = (const uint64_t*)(H + a_b4off); }
-  R.dev_reads = D + a_reads;
-  const double t5 = now();
-  out.ms_upload = t4 - t3; out.ms_inflate = t1 - t0; out.ms_walk = t2 - t1; out.ms_reads = t3 - t2; out.ms_download = t5 - t4;
-  return TRGT_OK;
+  // the slab of the batch: every per-read array a piece of it (slab_layout), device copy + pinned mirror
+  int take_slab() {
+    a = slab_layout(nl, h_counters->tot, in.keep_bam4);
+    Slab slab;
+    if (!pool->take(s->device, a.total + 64, slab)) { err = "trgt_ingest (device): no memory for the batch's arrays"; return TRGT_ERR_NOMEM; }
+    out.lease = SlabLease(slab, pool);
+    D = (uint8_t*)slab.dev; H = (uint8_t*)slab.pin;
+    return TRGT_OK;
+  }
+  int fill_and_download() {
+    const uint64_t nr = h_counters->tot[0], n_bytes = h_counters->tot[1];
+    OutPtrs o;
+    slab_view(o, D, a, in.keep_bam4);
+    if (n_bytes == 0) ING_TRY(hipMemsetAsync(D + a.reads, 0, 64, st));  // (an empty blob is handed out as one NUL byte, like the host path's)
+    if (nr == 0) ING_TRY(hipMemsetAsync(D + a.name_off, 0, 64, st));  // (the [n_reads + 1] offset arrays hold a 0 at least)
+    if (nr == 0) { ING_TRY(hipMemsetAsync(D + a.snp_off, 0, 64, st)); ING_TRY(hipMemsetAsync(D + a.meth_off, 0, 64, st)); ING_TRY(hipMemsetAsync(D + a.cig_off, 0, 64, st)); }
+    // (keep_bam4 without a 4-bit byte / without a read: the one byte and the one offset the host path hands out are 0, not what the slab held before)
+    if (in.keep_bam4 && h_counters->tot[6] == 0) ING_TRY(hipMemsetAsync(D + a.bam4, 0, 64, st));
+    if (in.keep_bam4 && nr == 0) ING_TRY(hipMemsetAsync(D + a.bam4_off, 0, 64, st));
+    if (n_pre) hipLaunchKernelGGL(read_fill_kernel, dim3((unsigned)n_pre), dim3(64), 0, st, (const uint8_t*)s->d_infl.p, (const LocusDesc*)s->d_loci.p, (const ReadInfo*)s->d_info.p, (const ReadOff*)s->d_off.p, n_pre,
+                                  (const uint8_t*)s->d_scratch.p, o);
+    ING_TRY(hipGetLastError());
+    ING_TRY(hipMemcpyAsync(D + a.lrb, s->d_lrb.p, ((size_t)nl + 1) * 8, hipMemcpyDeviceToDevice, st));
+    t4 = now_ms();
+    ING_TRY(hipMemcpyAsync(H, D, a.total, hipMemcpyDeviceToHost, st));
+    ING_TRY(slot_wait(s));
+    return TRGT_OK;
+  }
+  int publish() {
+    {  // per locus counters: known to the host since the walk
+      int32_t* nf = (int32_t*)(H + a.n_filt); int64_t* ns = (int64_t*)(H + a.n_seen);
+      for (uint32_t l = 0; l < nl; ++l) { nf[l] = (int32_t)h_walk[l].n_filt; ns[l] = (int64_t)h_walk[l].n_kept; }
+    }
+    const uint64_t* tot = h_counters->tot;
+    HostOut& R = out.out;
+    R.n_reads = (int64_t)tot[0]; R.read_bytes = tot[1]; R.name_bytes = tot[2]; R.snp_n = tot[3]; R.meth_n = tot[4]; R.cig_n = tot[5]; R.bam4_bytes = in.keep_bam4 ? tot[6] : 0;
+    R.lrb = (const uint64_t*)(H + a.lrb); R.n_filt = (const int32_t*)(H + a.n_filt); R.n_seen = (const int64_t*)(H + a.n_seen);
+    slab_view(R, H, a, in.keep_bam4);
+    R.dev_reads = D + a.reads;
+    const double t5 = now_ms();
+    out.ms_upload = t4 - t3; out.ms_inflate = t1 - t0; out.ms_walk = t2 - t1; out.ms_reads = t3 - t2; out.ms_download = t5 - t4;
+    return TRGT_OK;
+  }
+  int run() {
+    using Stage = int (SlotRun::*)();
+    static constexpr Stage stages[] = {&SlotRun::crc_tables_once, &SlotRun::size_and_upload, &SlotRun::inflate_and_crc, &SlotRun::rescue_declined_blocks, &SlotRun::record_walk,
+                                       &SlotRun::read_sizes_and_scan, &SlotRun::methylation_pass, &SlotRun::take_slab, &SlotRun::fill_and_download, &SlotRun::publish};
+    for (const Stage stage : stages) { const int rc = (this->*stage)(); if (rc || out.fallback) return rc; }
+    return TRGT_OK;
+  }
+};
+
+int slot_run(Slot* s, const RunIn& in, const std::shared_ptr<SlabPool>& pool, RunOut& out, std::string& err) {
+  out = RunOut();
+  return SlotRun{s, in, pool, out, err}.run();
 }
 
 #ifdef TRGT_DEV_BUILD
