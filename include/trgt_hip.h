@@ -394,6 +394,15 @@ int trgt_locus_meth_batch(trgt_hip_ctx* ctx, const trgt_locus_batch_in* in, cons
  * out[0] tr_meth_kernel, out[1] allele_meth_kernel (tools/locus_meth_timing.py). */
 int trgt_locus_meth_kernel_ms(const trgt_hip_ctx* ctx, double out[2]);
 
+/* ------------------------------------------------------------------ plot */
+/* The consumer of the spanning BAM: what `trgt plot` computes per locus before it draws (src/trvz/).  One call aligns the alleles of an
+ * allele plot (get_allele_align, trvz/align_allele.rs:7-14) or the reads of a waterfall plot (align, trvz/waterfall_plot.rs:42-123,
+ * with the sort and longest_read of :28-37) for a whole batch of panels and returns typed run-length segments, projected CpG
+ * positions, scores and the drawing order.  The two structures and the three prototypes -- trgt_plot_align_batch(ctx, in, out),
+ * trgt_plot_seg_capacity(mode, ref_len, read_len), trgt_plot_kernel_ms(ctx, out[2]) -- are declared and documented in
+ * trgt_hip_plot.h, which this header includes: every program that includes trgt_hip.h has them. */
+#include "trgt_hip_plot.h"
+
 /* Host helper for callers that hold ASCII reads and want TRGT_READS_BAM4 (a BAM reader has the codes already: trgt_ingest_params.
  * keep_bam4): packs read r (ascii + read_off[r], read_len[r] bases) to packed + packed_off[r], where packed_off[r] is written as the
  * running sum of ceil(read_len / 2).  Letters outside "=ACMGRSVTWYHKDBN" become N, as in htslib.  packed needs

@@ -93,6 +93,9 @@ CLUSTER_SNV_EXPORTS = ["trgt_hip_set_snv_cluster_device", "trgt_hip_snv_cluster_
 CLUSTER_DEEP_FLANK_EXPORTS = ["trgt_hip_set_flank_cluster_deep_device", "trgt_hip_flank_cluster_deep_stats"]
 # ... and the two of the SNV branch behind the deep chain (the SNV forms of the same header), checked the same way
 CLUSTER_DEEP_SNV_EXPORTS = ["trgt_hip_set_snv_cluster_deep_device", "trgt_hip_snv_cluster_deep_stats"]
+# The three entry points of the plot path (include/trgt_hip_plot.h, csrc/plot_align.hip; mirrored by trgt_amd/plot.py), a list of its own
+# checked the same way: tests/test_abi_exports.py holds EXPORTS to the names include/trgt_hip.h itself declares.
+PLOT_EXPORTS = ["trgt_plot_align_batch", "trgt_plot_seg_capacity", "trgt_plot_kernel_ms"]
 
 # The opt-in device routes of genotype_flank (FlankRoute, csrc/common.hpp): (name, C setter, C statistics call, its width, docstring of
 # Context.set_<name>_device, docstring of Context.<statistics name without trgt_hip_>).  Context gets the two methods of every row below.
@@ -188,6 +191,7 @@ def lib():
         L = C.CDLL(_SO)
         missing = [n for n in EXPORTS + CLUSTER_FLANK_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_SNV_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_DEEP_FLANK_EXPORTS if not hasattr(L, n)]
         missing += [n for n in CLUSTER_DEEP_SNV_EXPORTS if not hasattr(L, n)]
+        missing += [n for n in PLOT_EXPORTS if not hasattr(L, n)]
         if missing:
             raise TrgtHipError("%s does not export %s (stale build?)" % (_SO, ", ".join(missing)))
         L.trgt_hip_last_error.restype = C.c_char_p
@@ -220,6 +224,10 @@ def lib():
         L.trgt_locus_batch.argtypes = [_VP, _VP, _VP, _VP]
         L.trgt_locus_meth_batch.argtypes = [_VP] * 9
         L.trgt_locus_meth_kernel_ms.argtypes = [_VP, C.POINTER(C.c_double)]
+        L.trgt_plot_align_batch.argtypes = [_VP, _VP, _VP]
+        L.trgt_plot_seg_capacity.argtypes = [C.c_int32, C.c_uint32, C.c_uint32]
+        L.trgt_plot_seg_capacity.restype = C.c_uint64
+        L.trgt_plot_kernel_ms.argtypes = [_VP, C.POINTER(C.c_double)]
         L.trgt_reads_pack_bam4.argtypes = [_VP, C.c_int64, _VP, _VP, _VP, _VP]
         L.trgt_reads_pack_bam4.restype = C.c_int64
         L.trgt_locus_batch_submit.argtypes = [_VP, _VP, _VP, _VP, C.POINTER(C.c_int64)]

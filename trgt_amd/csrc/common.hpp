@@ -137,6 +137,7 @@ struct trgt_hip_ctx {
   int64_t size_deep_stats[4] = {0, 0, 0, 0};  // trgt_hip_size_deep_stats: the deep size loci of the last trgt_locus_batch (genotyped on the device, repaired among them, handed to the host, reserved)
   FlankRouteState route[FR_N];  // the opt-in device routes of genotype_flank, indexed by FlankRoute (above)
   double meth_ms[2] = {0, 0};   // trgt_locus_meth_kernel_ms: tr_meth_kernel and allele_meth_kernel of the last timed trgt_locus_meth_batch
+  double plot_ms[2] = {0, 0};   // trgt_plot_kernel_ms: plot_motif_segs_kernel and plot_read_segs_kernel of the last timed trgt_plot_align_batch
   int num_cus = 256;
   int band_occ = 0;  // resident workgroups per CU of wfa_band_kernel (wfa_band.hip), asked at its first launch (0: not yet)
   // cached device buffers, indexed by slot
@@ -307,6 +308,7 @@ enum Slot {
   S_FS_SETTLED, S_FS_FILTERJOBS,  // flank location: the marks of what the seed search's shortcuts settled, and the pre-filter's list behind the settled-sibling rule (spans.hip)
   S_FS_BANDFALL, S_LW_BANDFALL,  // flank location: the banded jobs the one-wave forward kernel leaves to the LDS launch (wfa_band.hip), short and long reads
   S_METH_READS, S_METH_CALLS, S_METH_JOBS, S_METH_LOCI, S_METH_LEVEL, S_METH_LEN, S_METH_FLAG, S_METH_OUT, S_METH_NREADS, S_METH_PERREAD,  // trgt_locus_meth_batch (locus_meth.hip)
+  S_PLOT_IN, S_PLOT_PATH, S_PLOT_HMMOUT, S_PLOT_WORK, S_PLOT_WFAOUT, S_PLOT_PSEG, S_PLOT_NPSEG, S_PLOT_RSEG, S_PLOT_NRSEG, S_PLOT_BPROJ, S_PLOT_SCORE, S_PLOT_POFF, S_PLOT_PACKED,  // trgt_plot_align_batch (plot_align.hip)
   S_COUNT
 };
 // pinned host buffer slots
