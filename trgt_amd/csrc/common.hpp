@@ -57,6 +57,8 @@ struct trgt_knobs {
   bool no_early = false;        // TRGT_WFA_NO_EARLY: the flank pre-filter runs every alignment to its end
   bool stage_lock = false;      // TRGT_STAGE_LOCK: only one context per device in its flank-location stage at a time
   bool host_hmm_lists = false;  // TRGT_HOST_HMM_LISTS: stage C job lists built by the host after the genotyper (not resolved on the device)
+  bool gt_serial = false;    // TRGT_GT_SERIAL (DEV): the size genotyper (locus_gt.hpp) takes every section read by read, as before its lane-parallel sections
+  bool gt_weak_hash = false; // TRGT_GT_WEAK_HASH (DEV): its sequence hash is the length alone: distinct sequences collide, the comparison and the plain insertion run
   bool debug = false;        // TRGT_WFA_DEBUG: launch plans on stderr (synchronises)
   bool hmm_resolve_one_wg = false;   // TRGT_HMM_RESOLVE_ONE_WG: the stage-C job list by the one-workgroup kernel, class after class
   bool wfa_no_wave_variant = false;  // TRGT_WFA_NO_WAVE_VARIANT: one-wave batches of the generic kernel take the 168-register build (three waves per SIMD)
@@ -363,6 +365,36 @@ inline int pin_get(trgt_hip_ctx* c, int slot, size_t bytes, void** out) {
   }
   *out = b.p;
   return TRGT_OK;
+}
+
+// ---- exclusive prefix sum of n 32-bit counts into 64-bit offsets by one workgroup of 1 024 threads; off[n] = the total.  Each of the 16
+// waves owns a contiguous piece of whole 64-element tiles and reads it coalesced, twice: for the piece's sum, and -- behind one LDS hop
+// over the 16 sums -- four tiles at a time, each scanned across the lanes, with the running offset carried along.
+static __device__ __forceinline__ void block_prefix_u32(const uint32_t* __restrict__ v, uint64_t* __restrict__ off, uint64_t n) {
+  typedef unsigned long long u64;
+  __shared__ u64 wave_total[16];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const uint64_t per = ((n + 63) / 64 + 15) / 16 * 64;  // elements per wave
+  const uint64_t b = (uint64_t)wave * per < n ? (uint64_t)wave * per : n, e = b + per < n ? b + per : n;
+  u64 s = 0;
+  for (uint64_t i = b + lane; i < e; i += 64) s += v[i];
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) wave_total[wave] = s;
+  __syncthreads();
+  u64 run = 0;
+  for (uint32_t w = 0; w < wave; ++w) run += wave_total[w];
+  if (threadIdx.x == 1023) off[n] = run + s;
+  for (uint64_t base = b; base < e; base += 256) {
+    u64 x[4], inc[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const uint64_t i = base + 64 * k + lane; x[k] = i < e ? v[i] : 0; inc[k] = x[k]; }
+    for (int o = 1; o < 64; o <<= 1) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { const u64 y = __shfl_up(inc[k], o); if (lane >= (uint32_t)o) inc[k] += y; }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const uint64_t i = base + 64 * k + lane; if (i < e) off[i] = run + inc[k] - x[k]; run += __shfl(inc[k], 63); }
+  }
 }
 
 // ---- zero arena.  zero_begin (start of trgt_locus_batch, on the call's stream) clears what the call before handed out; zero_take

@@ -1626,17 +1626,7 @@ __global__ void hmm_pack_spans_kernel(const int32_t* __restrict__ spans3, const 
 
 // exclusive prefix of the span counts (one workgroup): where every job's spans go in the packed array; off[n] = their total
 __global__ void __launch_bounds__(1024) hmm_span_prefix_kernel(const uint32_t* __restrict__ n_spans, uint64_t* __restrict__ off, uint64_t n) {
-  __shared__ uint64_t part[1024];
-  const uint32_t t = threadIdx.x;
-  const uint64_t per = (n + 1023) / 1024, b = t * per < n ? t * per : n, e = b + per < n ? b + per : n;
-  uint64_t sum = 0;
-  for (uint64_t i = b; i < e; ++i) sum += n_spans[i];
-  part[t] = sum;
-  __syncthreads();
-  if (t == 0) { uint64_t run = 0; for (int i = 0; i < 1024; ++i) { const uint64_t v = part[i]; part[i] = run; run += v; } off[n] = run; }
-  __syncthreads();
-  uint64_t run = part[t];
-  for (uint64_t i = b; i < e; ++i) { off[i] = run; run += n_spans[i]; }
+  block_prefix_u32(n_spans, off, n);
 }
 
 

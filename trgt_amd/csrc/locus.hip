@@ -506,20 +506,11 @@ HostPool* host_pool(trgt_hip_ctx* c, int threads) {
 //  source: zeros -- which were a D2D copy or a fill each)
 struct CountCopy { const uint32_t* src1; uint32_t* dst1; uint32_t n1; const uint32_t* src2; uint32_t* dst2; uint32_t n2; const uint32_t* src3; uint32_t* dst3; uint32_t n3; };
 __global__ void __launch_bounds__(1024) allele_prefix_kernel(const uint32_t* __restrict__ len, uint64_t* __restrict__ off, int64_t n, const CountCopy cc) {
-  __shared__ uint64_t part[1024];
   const int t = threadIdx.x;
   if ((uint32_t)t < cc.n1) cc.dst1[t] = cc.src1 ? __hip_atomic_load(cc.src1 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   if ((uint32_t)t < cc.n2) cc.dst2[t] = cc.src2 ? __hip_atomic_load(cc.src2 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
   if ((uint32_t)t < cc.n3) cc.dst3[t] = cc.src3 ? __hip_atomic_load(cc.src3 + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-  const int64_t per = (n + 1023) / 1024, b = t * per, e = b + per < n ? b + per : n;
-  uint64_t sum = 0;
-  for (int64_t i = b; i < e; ++i) sum += len[i];
-  part[t] = sum;
-  __syncthreads();
-  if (t == 0) { uint64_t run = 0; for (int i = 0; i < 1024; ++i) { const uint64_t v = part[i]; part[i] = run; run += v; } off[n] = run; }
-  __syncthreads();
-  uint64_t run = part[t];
-  for (int64_t i = b; i < e; ++i) { off[i] = run; run += len[i]; }
+  block_prefix_u32(len, off, (uint64_t)n);
 }
 __global__ void allele_pack_kernel(const uint8_t* __restrict__ blob, const uint64_t* __restrict__ src_off, const uint32_t* __restrict__ len,
                                    const uint64_t* __restrict__ dst_off, uint8_t* __restrict__ packed, int64_t n) {
@@ -809,6 +800,7 @@ struct LocusCall {
   enum class GtForm { PLAIN, FLANK, SNV };
   GtForm gt_form() const { return fits[FR_SIZE_SNV] ? GtForm::SNV : fits[FR_SIZE_TAG] ? GtForm::FLANK : GtForm::PLAIN; }
   void launch_genotype_kernels(), launch_finish_kernels(const gt::FinishArgs& fa);
+  int gt_prof_readback();
   void tally_route(FlankRoute r, const std::vector<uint32_t>* list, uint8_t snv, const uint8_t* fdone, const uint8_t* need);
   // ga as it stands, with what the FLANK forms read beyond it
   gt::GtFlankArgs flank_args() const { gt::GtFlankArgs fa; static_cast<gt::GtArgs&>(fa) = ga; fa.hp_tag = g.hp; fa.flank_done = (uint8_t*)slab.d(o_fdone); return fa; }
@@ -1305,9 +1297,29 @@ void LocusCall::launch_finish_kernels(const gt::FinishArgs& fa) {
       break;
   }
 }
+// make GTPROF=1: the clocks lane 0 of every locus left in the genotyper's profile symbol, as shares per section, read and cleared
+// (synchronises; a TRGT_WFA_DEBUG call only)
+int LocusCall::gt_prof_readback() {
+#ifdef TRGT_GT_PROF
+  if (!c->knobs.debug) return TRGT_OK;
+  unsigned long long h[gt::GTP_WORDS], z[gt::GTP_WORDS] = {0};
+  TRGT_HIP_TRY(c, trgt::stream_wait(c, c->stream));
+  TRGT_HIP_TRY(c, hipMemcpyFromSymbol(h, HIP_SYMBOL(gt::g_gt_prof), sizeof h));
+  TRGT_HIP_TRY(c, hipMemcpyToSymbol(HIP_SYMBOL(gt::g_gt_prof), z, sizeof h));
+  double tot = 1e-9;
+  for (int i = 0; i <= gt::GTP_OUT; ++i) tot += (double)h[i];
+  fprintf(stderr, "[gt prof] %lld loci, %s reads | front %.1f%% staging %.1f%% lengths %.1f%% candidates %.1f%% sequences %.1f%% routes %.1f%% picks %.1f%% classification %.1f%% outputs %.1f%% | kcycles per locus %.1f\n",
+          (long long)nl, small_gt ? "<= 64" : "<= 256", 100 * h[gt::GTP_FRONT] / tot, 100 * h[gt::GTP_STAGE] / tot, 100 * h[gt::GTP_LENS] / tot, 100 * h[gt::GTP_CAND] / tot, 100 * h[gt::GTP_SEQ] / tot,
+          100 * h[gt::GTP_ROUTE] / tot, 100 * h[gt::GTP_PICK] / tot, 100 * h[gt::GTP_CLASS] / tot, 100 * h[gt::GTP_OUT] / tot, tot / 1e3 / (double)std::max<int64_t>(1, nl));
+#endif
+  return TRGT_OK;
+}
 int LocusCall::size_genotyper() {
   if (!dev_gt) return TRGT_OK;
+  // (the one-wave genotyper reads its developer switches -- TRGT_GT_SERIAL, TRGT_GT_WEAK_HASH -- from the field the finish kernels read later)
+  ga.finish_clears_need = (c->knobs.gt_serial ? gt::GT_DEV_SERIAL : 0) | (c->knobs.gt_weak_hash ? gt::GT_DEV_WEAK_HASH : 0);
   launch_genotype_kernels();
+  if (int prc = gt_prof_readback()) return prc;
   ran[FR_SIZE_TAG] = fits[FR_SIZE_TAG]; ran[FR_SIZE_SNV] = fits[FR_SIZE_SNV];  // (the size routes run with the genotyper itself)
   TRGT_HIP_TRY(c, hipGetLastError());
   tl_mark(c, "genotyper launched");
@@ -1358,16 +1370,18 @@ int LocusCall::repair_chain() {
   LR.pat_base = d_reads; LR.txt_base = d_reads;
   LR.max_plen = rp.max_seg; LR.max_tlen = rp.max_seg; LR.max_sum = 2 * (int64_t)rp.max_seg;
   LR.cigar = (uint32_t*)rb.cig; LR.cigar_len = (uint32_t*)rb.clen; LR.buffer_set = 2; LR.ws_budget = 512ull << 20; LR.refused = rp.counts + gt::RC_REFUSED;
-  auto dbg_sync = [&](const char* what) -> int {  // TRGT_WFA_DEBUG: which kernel of the chain a device fault belongs to
+  auto dbg_sync = [&](const char* what, bool size_gt = false) -> int {  // TRGT_WFA_DEBUG: which kernel of the chain a device fault belongs to
     if (!c->knobs.debug) return TRGT_OK;
     const hipError_t e = trgt::stream_wait(c, c->stream);
     uint32_t h[gt::RC_WORDS]; std::memset(h, 0, sizeof h);
     if (e == hipSuccess) (void)hipMemcpy(h, rp.counts, sizeof h, hipMemcpyDeviceToHost);
     fprintf(stderr, "[repair] %s: %s (groups %u jobs %u loci %u failed %u cigar words %llu)\n", what, hipGetErrorString(e), h[gt::RC_GROUPS], h[gt::RC_JOBS], h[gt::RC_LOCI], h[gt::RC_FAILED],
             (unsigned long long)h[gt::RC_CIGAR] | ((unsigned long long)h[gt::RC_CIGAR + 1] << 32));
+    // (the size genotyper's tally: loci of this call that left one of its lane-parallel sections, by reason)
+    if (size_gt) fprintf(stderr, "[size gt] of %lld loci: unsorted %u, not staged %u, hash collision %u\n", (long long)nl, h[gt::RC_GT_UNSORTED], h[gt::RC_GT_NOFIT], h[gt::RC_GT_COLLISION]);
     return e == hipSuccess ? TRGT_OK : fail(c, TRGT_ERR_HIP, "%s failed: %s", what, hipGetErrorString(e));
   };
-  if ((rc = dbg_sync("genotyper"))) return rc;
+  if ((rc = dbg_sync("genotyper", true))) return rc;
   if (uint32_t* trace_host = repair_trace_buf()) { std::memset(trace_host, 0, 4096); hipLaunchKernelGGL(repair_trace_kernel, dim3(1), dim3(64), 0, c->stream, rp, trace_host); }
   static const bool repair_check = TRGT_DEV_ENV("TRGT_REPAIR_CHECK") != nullptr;
   if (repair_check) {

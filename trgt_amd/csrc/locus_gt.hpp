@@ -54,6 +54,10 @@ constexpr int SNV_OFFS_PER_READ = 8;    // in-region mismatch offsets of a locus
 // the per-read byte of a locus the SNV branch left waiting for the repair chain (SnvArgs::snv_read): assignment, membership of either group
 enum { SR_ASSIGN = 1, SR_IN0 = 2, SR_IN1 = 4 };
 
+// GtArgs::finish_clears_need as locus_genotype_kernel reads it.  GT_DEV_SERIAL (TRGT_GT_SERIAL, developer build): every section of the size
+// genotyper as one lane, or the whole wave in step, takes it read by read; GT_DEV_WEAK_HASH (TRGT_GT_WEAK_HASH): gt_equal_reads tells
+// sequences apart by length alone
+enum { GT_DEV_SERIAL = 2, GT_DEV_WEAK_HASH = 4 };
 struct GtArgs {
   const uint8_t* reads; const uint64_t* read_off; const uint32_t* read_len; const uint64_t* locus_read_begin;
   const int32_t* span_start; const int32_t* span_end;
@@ -66,7 +70,8 @@ struct GtArgs {
   int32_t* gt_size;  // [2 n_loci] TrSize::size of the genotype behind every allele (optional)
   const uint8_t* genotyper;  // optional [n_loci]: 1 = Genotyper::Cluster, a locus the host genotypes (need_host = 1 at once)
   uint8_t* skip_b;   // [n_loci] 0 for the loci repair_finish_kernel completed (their HMM batch runs behind it), else 1
-  int32_t finish_clears_need;  // 1: repair_finish_kernel also sets need_host = 0 (nothing reads it concurrently: one HMM batch behind the repair)
+  int32_t finish_clears_need;  // the finish kernels: 1 = repair_finish_kernel also sets need_host = 0 (nothing reads it concurrently: one HMM batch behind the repair);
+                               // locus_genotype_kernel, launched before that is decided: its developer switches (GT_DEV_*; the struct must not grow)
   RepairBufs rp;
   // calls with filter_impure_trs on (locus_purity.hpp), read by the PRESEL instantiations only: the kept reads of locus l, already selected,
   // ordered and filtered, in slots [locus_read_begin[l], + n_sel[l]) -- read (index inside the locus), span start, span length
@@ -643,6 +648,166 @@ __device__ __forceinline__ bool snv_route(SH& sh, const A& a, int64_t l, uint64_
   } else return END::split(sh, a, l, lane, cnt, hap);
 }
 
+// ---- the lane-parallel sections of locus_genotype_kernel.  Elements (kept reads, unique lengths, unique sequences) are spread over the
+// wave as lane, lane + 64, ...: R = MAXR / 64 per lane.  Uniform arguments; every function is called by the whole wave.
+__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) { for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o); return v; }
+__device__ __forceinline__ uint32_t wave_incl_sum_u(uint32_t v, int lane) {
+  for (int o = 1; o < 64; o <<= 1) { const uint32_t w = (uint32_t)__shfl_up((int)v, o); if (lane >= o) v += w; }
+  return v;
+}
+// how many loci of a call left the lane-parallel sections, and why (RC_GT_* of repair_queue.hpp; calls with the device-side repair)
+__device__ __forceinline__ void gt_tally(const RepairBufs& rp, int word, int lane) { if (lane == 0 && rp.counts) atomicAdd(rp.counts + word, 1u); }
+
+// LDS layout of the n repeat segments (4-aligned, in kept order) and of the reference repeat behind them: a prefix sum over the
+// aligned lengths.  sh.fits = 0 when the sum passes SEG at any segment, or with the reference repeat behind the last one.
+template <int MAXR, int SEG, class SH>
+__device__ __forceinline__ void gt_layout(SH& sh, int n, uint32_t refn, int lane) {
+  uint32_t carry = 0; bool over = false;
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    const uint32_t v = i < n ? (sh.s_len[i] + 3u) & ~3u : 0u;
+    const uint32_t inc = wave_incl_sum_u(v, lane);
+    if (i < n) sh.s_loff[i] = (uint16_t)(carry + inc - v);
+    over = over || __ballot(i < n && carry + inc > (uint32_t)SEG) != 0ull;
+    carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+  }
+  if (lane == 0) { sh.ref_off = carry; if (over || carry + ((refn + 3u) & ~3u) > (uint32_t)SEG) sh.fits = 0; }
+}
+
+// The segments of the n kept reads and, as item n, the reference repeat from global memory into their places in sh.bytes.  A group of
+// 16 lanes takes K items at a time and has the first 256 bytes and the tail bytes of all K in flight before it stores any of them:
+// the copy is bound by the latency of these loads, not by their number (longer items finish 256 bytes per round, as copy16 does).
+template <int K, class SH>
+__device__ __forceinline__ void gt_stage(SH& sh, const GtArgs& a, int n, uint32_t refn, uint64_t refo, int lane) {
+  const int grp = lane >> 4, sub = lane & 15;
+  for (int j0 = grp * K; j0 <= n; j0 += 4 * K) {
+    const uint8_t* src[K]; uint8_t* dst[K]; uint32_t len[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const int j = j0 + k;
+      src[k] = a.tr_blob + refo; dst[k] = sh.bytes + sh.ref_off; len[k] = j == n ? refn : 0u;
+      if (j < n) { src[k] = a.reads + sh.r_off[sh.s_read[j]] + sh.s_start[j]; dst[k] = sh.bytes + sh.s_loff[j]; len[k] = sh.s_len[j]; }
+    }
+    uint4 v[K]; uint8_t tl[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const uint32_t full = len[k] >> 4, tb = full * 16 + (uint32_t)sub;
+      if ((uint32_t)sub < full) __builtin_memcpy(&v[k], src[k] + 16 * sub, 16);
+      if (tb < len[k]) tl[k] = src[k][tb];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const uint32_t full = len[k] >> 4, tb = full * 16 + (uint32_t)sub;
+      if ((uint32_t)sub < full) { uint32_t* d = reinterpret_cast<uint32_t*>(dst[k]) + 4 * sub; d[0] = v[k].x; d[1] = v[k].y; d[2] = v[k].z; d[3] = v[k].w; }
+      if (tb < len[k]) dst[k][tb] = tl[k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      for (uint32_t w = 16 + (uint32_t)sub; w < (len[k] >> 4); w += 16) {
+        uint4 x; __builtin_memcpy(&x, src[k] + 16 * w, 16);
+        uint32_t* d = reinterpret_cast<uint32_t*>(dst[k]) + 4 * w;
+        d[0] = x.x; d[1] = x.y; d[2] = x.z; d[3] = x.w;
+      }
+  }
+}
+
+// Unique lengths ascending with their multiplicities (sh.ulen, sh.ucnt, sh.n_sizes) of a kept list that is sorted by length: the runs.
+// A lane per read marks where a run begins, the begins before it give the run its slot, the next begin its length.  false: the list
+// is not sorted (the downsample moved reads) and the caller builds the histogram read by read.
+template <int MAXR, class SH>
+__device__ __forceinline__ bool gt_len_runs(SH& sh, int n, int lane) {
+  int u = 0; bool sorted = true;
+  for (int base = 0; base < n; base += 64) {
+    const int i = base + lane;
+    const uint32_t cur = i < n ? sh.s_len[i] : 0u, prev = i > 0 && i < n ? sh.s_len[i - 1] : 0u;
+    sorted = sorted && __ballot(i > 0 && i < n && prev > cur) == 0ull;
+    const bool begin = i < n && (i == 0 || prev != cur);
+    const unsigned long long bb = __ballot(begin);
+    if (begin) { const int s = u + __popcll(bb & ((1ull << lane) - 1ull)); sh.ulen[s] = cur; sh.ucnt[s] = (uint32_t)i; }
+    u += __popcll(bb);
+  }
+  if (!sorted) return false;
+  __syncthreads();
+  uint32_t at[MAXR / 64], next[MAXR / 64];
+#pragma unroll
+  for (int t = 0; t < MAXR / 64; ++t) { const int s = lane + 64 * t; if (s < u) { at[t] = sh.ucnt[s]; next[t] = s + 1 < u ? sh.ucnt[s + 1] : (uint32_t)n; } }
+  __syncthreads();
+#pragma unroll
+  for (int t = 0; t < MAXR / 64; ++t) { const int s = lane + 64 * t; if (s < u) sh.ucnt[s] = next[t] - at[t]; }
+  if (lane == 0) sh.n_sizes = u;
+  return true;
+}
+
+// Which of the n kept reads carry the same sequence (segments staged in sh.bytes): fr[t] = the first kept read with the sequence of read
+// lane + 64 t (-1 beyond n).  Every lane hashes its own segments (independent LDS loads), the first read of the same length and hash
+// is found by passing the reads round the wave in kept order, and every read is then compared with that first read dword by dword
+// (the tail mask of cmp_lds).  false: a comparison failed -- two sequences share length and hash -- and the caller takes every read
+// singly.  weak: the hash is left out (developer switch: every pair of distinct sequences of one length collides).
+template <int R, class SH>
+__device__ __forceinline__ bool gt_equal_reads(SH& sh, int n, int lane, bool weak, int (&fr)[R]) {
+  uint32_t ln[R], h1[R], h2[R];
+#pragma unroll
+  for (int t = 0; t < R; ++t) {
+    const int i = lane + 64 * t;
+    ln[t] = 0; h1[t] = 0x811C9DC5u; h2[t] = 0x9E3779B9u; fr[t] = -1;
+    if (i >= n) continue;
+    ln[t] = sh.s_len[i];
+    if (weak) continue;
+    const uint32_t* W = reinterpret_cast<const uint32_t*>(sh.bytes + sh.s_loff[i]);
+    const uint32_t nw = (ln[t] + 3u) >> 2, tail = (ln[t] & 3u) ? (1u << (8 * (ln[t] & 3u))) - 1u : 0xFFFFFFFFu;
+    for (uint32_t w = 0; w < nw; w += 4) {  // (words beyond the segment count as 0: the same for every segment of this length)
+      uint32_t x[4];
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) { x[k] = w + k < nw ? W[w + k] : 0u; if (w + k == nw - 1) x[k] &= tail; }
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) {
+        h1[t] = (h1[t] ^ x[k]) * 0x9E3779B1u; h1[t] = (h1[t] << 13) | (h1[t] >> 19);
+        h2[t] = (h2[t] + x[k]) * 0x85EBCA6Bu; h2[t] ^= h2[t] >> 15;
+      }
+    }
+  }
+#pragma unroll
+  for (int tj = 0; tj < R; ++tj)
+    for (int jl = 0; jl < 64 && 64 * tj + jl < n; ++jl) {
+      const uint32_t lj = (uint32_t)__builtin_amdgcn_readlane((int)ln[tj], jl), a1 = (uint32_t)__builtin_amdgcn_readlane((int)h1[tj], jl),
+                     a2 = (uint32_t)__builtin_amdgcn_readlane((int)h2[tj], jl);
+#pragma unroll
+      for (int t = 0; t < R; ++t)
+        if (fr[t] < 0 && lane + 64 * t < n && ln[t] == lj && h1[t] == a1 && h2[t] == a2) fr[t] = 64 * tj + jl;
+    }
+  bool differ = false;
+#pragma unroll
+  for (int t = 0; t < R; ++t) {
+    const int i = lane + 64 * t;
+    if (i >= n || fr[t] == i) continue;
+    const uint32_t* A = reinterpret_cast<const uint32_t*>(sh.bytes + sh.s_loff[i]);
+    const uint32_t* B = reinterpret_cast<const uint32_t*>(sh.bytes + sh.s_loff[fr[t]]);
+    const uint32_t nw = (ln[t] + 3u) >> 2, tail = (ln[t] & 3u) ? (1u << (8 * (ln[t] & 3u))) - 1u : 0xFFFFFFFFu;
+    for (uint32_t w = 0; w < nw; w += 4) {
+#pragma unroll
+      for (uint32_t k = 0; k < 4; ++k) {
+        if (w + k >= nw) break;
+        uint32_t x = A[w + k] ^ B[w + k];
+        if (w + k == nw - 1) x &= tail;
+        differ = differ || x != 0u;
+      }
+    }
+  }
+  return __ballot(differ) == 0ull;
+}
+
+// make GTPROF=1 (developer build): lane 0 of every locus splits its shader-clock time over the sections of the kernel; the sums leave the
+// kernel through a symbol of their own (locus.hip prints and clears it behind the launch of a TRGT_WFA_DEBUG call)
+enum { GTP_FRONT = 0, GTP_STAGE, GTP_LENS, GTP_CAND, GTP_SEQ, GTP_ROUTE, GTP_PICK, GTP_CLASS, GTP_OUT, GTP_WORDS = 16 };
+#ifdef TRGT_GT_PROF
+__device__ unsigned long long g_gt_prof[GTP_WORDS];
+#define GTP_DECL unsigned long long gtp_t = clock64()
+#define GTP_MARK(i) do { const unsigned long long n_ = clock64(); if (threadIdx.x == 0) atomicAdd(&g_gt_prof[i], n_ - gtp_t); gtp_t = n_; } while (0)
+#else
+#define GTP_DECL
+#define GTP_MARK(i)
+#endif
+
 template <int MAXR, int SEG, bool PRESEL = false, bool FLANK = false, bool SNV = false>
 __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK, SNV> a) {  // exactly one wave per locus: the lane-0 sections and the ballots rely on it
   static_assert(FLANK || !SNV, "the SNV forms are FLANK forms: they share the tail of the route and its LDS");
@@ -650,8 +815,15 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
   const int64_t l = blockIdx.x;
   if (l >= a.n_loci) return;
   const int lane = threadIdx.x;
+  constexpr int R = MAXR / 64;  // elements per lane: lane owns lane, lane + 64, ...
+  const bool serial = (a.finish_clears_need & GT_DEV_SERIAL) != 0, weak_hash = (a.finish_clears_need & GT_DEV_WEAK_HASH) != 0;
   const uint64_t r0 = a.locus_read_begin[l], r1 = a.locus_read_begin[l + 1];
   const int nr = (int)(r1 - r0);
+  // (what the locus needs from global memory beside its reads, asked for here: each of these loads is a round trip of its own further down)
+  const uint8_t ploidy_l = a.ploidy[l];
+  const uint32_t refn = a.tr_len[l], allele_cap_l = a.allele_cap[l];
+  const uint64_t refo = a.tr_off[l], allele_at[2] = {a.allele_off[2 * l], a.allele_off[2 * l + 1]};
+  GTP_DECL;
   if (lane == 0) {
     sh.n = 0; sh.bail = 0; sh.fits = 1; sh.res_n_gt = 0;
     if (a.gt_size) a.gt_size[2 * l] = a.gt_size[2 * l + 1] = 0;
@@ -661,42 +833,47 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
     if constexpr (FLANK) a.flank_done[l] = 0;
   }
   const bool cluster = a.genotyper && a.genotyper[l] == 1;
-  if (a.ploidy[l] == 0 || nr == 0 || nr > MAXR || cluster) {  // Ploidy::Zero -> LocusResult::empty (tr.rs:29-31); oversized, cluster genotyper -> host
+  if (ploidy_l == 0 || nr == 0 || nr > MAXR || cluster) {  // Ploidy::Zero -> LocusResult::empty (tr.rs:29-31); oversized, cluster genotyper -> host
     for (int i = lane; i < nr; i += 64) { a.classification[r0 + i] = -1; a.read_rank[r0 + i] = -1; }
-    if (lane == 0 && (nr > MAXR || cluster) && a.ploidy[l] != 0 && nr != 0) a.need_host[l] = 1;
+    if (lane == 0 && (nr > MAXR || cluster) && ploidy_l != 0 && nr != 0) a.need_host[l] = 1;
     return;
   }
   gt_selected<MAXR, PRESEL>(sh, a, l, r0, nr, lane);
-  const uint32_t refn = a.tr_len[l];
-  const uint64_t refo = a.tr_off[l];
   int n = sh.n;
+  GTP_MARK(GTP_FRONT);
   if (n > 0) {
-    if (lane == 0) {
-      // ---- LDS layout of the repeat segments (4-aligned) and of the reference repeat behind them
+    // ---- LDS layout of the repeat segments (4-aligned) and of the reference repeat behind them
+    //      (segments that do not fit are compared where they lie, in the read blob: sh.fits = 0)
+    if (!serial) gt_layout<MAXR, SEG>(sh, n, refn, lane);
+    else if (lane == 0) {
       uint32_t o = 0;
-      const int nn = sh.n;
-      //      (segments that do not fit are compared where they lie, in the read blob: sh.fits = 0)
-      for (int i = 0; i < nn; ++i) { sh.s_loff[i] = (uint16_t)o; o += (sh.s_len[i] + 3u) & ~3u; if (o > (uint32_t)SEG) { sh.fits = 0; break; } }
+      for (int i = 0; i < n; ++i) { sh.s_loff[i] = (uint16_t)o; o += (sh.s_len[i] + 3u) & ~3u; if (o > (uint32_t)SEG) { sh.fits = 0; break; } }
       sh.ref_off = o;
       if (o + ((refn + 3u) & ~3u) > (uint32_t)SEG) sh.fits = 0;
     }
     __syncthreads();
-    n = sh.n;
     if (sh.fits) {
-      const int grp = lane >> 4, sub = lane & 15;
-      for (int i = grp; i < n; i += 4) copy16(sh.bytes + sh.s_loff[i], a.reads + sh.r_off[sh.s_read[i]] + sh.s_start[i], sh.s_len[i], sub);
-      if (grp == 0) copy16(sh.bytes + sh.ref_off, a.tr_blob + refo, refn, sub);
+      if (!serial) gt_stage<4>(sh, a, n, refn, refo, lane);
+      else {
+        const int grp = lane >> 4, sub = lane & 15;
+        for (int i = grp; i < n; i += 4) copy16(sh.bytes + sh.s_loff[i], a.reads + sh.r_off[sh.s_read[i]] + sh.s_start[i], sh.s_len[i], sub);
+        if (grp == 0) copy16(sh.bytes + sh.ref_off, a.tr_blob + refo, refn, sub);
+      }
     }
     __syncthreads();
   }
   const bool fits = sh.fits != 0;
-  auto seg_glob = [&](int i) { return a.reads + sh.r_off[sh.s_read[i]] + sh.s_start[i]; };
+  GTP_MARK(GTP_STAGE);
+  auto seg_glob =[&](int i) { return a.reads + sh.r_off[sh.s_read[i]] + sh.s_start[i]; };
   auto cmp_seg = [&](int i, int j) {  // uniform arguments, uniform result
     return fits ? cmp_lds(sh.bytes + sh.s_loff[i], sh.s_len[i], sh.bytes + sh.s_loff[j], sh.s_len[j]) : cmp_bytes(seg_glob(i), sh.s_len[i], seg_glob(j), sh.s_len[j]);
   };
   if (n > 0 && !sh.bail) {
     // ---- unique lengths / counts ascending (sorted(lens) of genotype_size_front; after a downsample the list is not sorted)
-    if (lane == 0) {  // (one lane builds the histogram: read-modify-writes of LDS by 64 lanes at once only work by lockstep)
+    //      a sorted list -- every list that was not downsampled -- is cut into its runs by the whole wave
+    const bool runs = !serial && gt_len_runs<MAXR>(sh, n, lane);
+    if (!runs && !serial) gt_tally(a.rp, RC_GT_UNSORTED, lane);
+    if (!runs && lane == 0) {  // (one lane builds the histogram: read-modify-writes of LDS by 64 lanes at once only work by lockstep)
       int u = 0;
       for (int i = 0; i < n; ++i) {
         const uint32_t v = sh.s_len[i];
@@ -710,7 +887,8 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
     }
     __syncthreads();
     const int u = sh.n_sizes;
-    const int ploidy = a.ploidy[l] == 1 ? 1 : 2;
+    GTP_MARK(GTP_LENS);
+    const int ploidy = ploidy_l == 1 ? 1 : 2;
     // ---- diploid::genotype / haploid::genotype: candidates spread over the lanes, first minimum wins
     double best_pen = 0.0; int best_p = 0x7FFFFFFF; bool have = false;
     if (ploidy == 2) {
@@ -742,6 +920,7 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
       const double op = __shfl_xor(best_pen, o); const int oi = __shfl_xor(best_p, o); const int oh = __shfl_xor((int)have, o);
       if (oh && (!have || op < best_pen || (op == best_pen && oi < best_p))) { have = true; best_pen = op; best_p = oi; }
     }
+    GTP_MARK(GTP_CAND);
     // ---- the decisions are sequential and small: every lane takes them redundantly (uniform control flow, identical LDS
     //      writes), which lets the sequence comparisons use the whole wave
     {
@@ -771,25 +950,51 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
         civ[0] = sh.ulen[0]; civ[1] = sh.ulen[u - 1];
       }
       // ---- get_seq_hist: unique sequences in byte-lexicographic order (binary-search insertion into a sorted unique list)
-      int nu = 0;
-      for (int i = 0; i < n; ++i) {
-        int lo = 0, hi = nu, eq = -1;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          const int r = sh.u_rep[mid];
-          const int c = cmp_seg(i, r);
-          if (c == 0) { eq = mid; break; }
-          if (c < 0) hi = mid; else lo = mid + 1;
-        }
-        // (the list is written by lane 0 only; the comparisons of the next round read it back in program order: one wave, one LDS queue)
-        if (eq >= 0) { if (lane == 0) { sh.u_cnt[eq] += 1; if constexpr (FLANK) sh.f_uidx[i] = sh.u_rep[eq]; } continue; }
-        if (lane == 0) {
-          for (int q = nu; q > lo; --q) { sh.u_rep[q] = sh.u_rep[q - 1]; sh.u_cnt[q] = sh.u_cnt[q - 1]; }
-          sh.u_rep[lo] = (uint16_t)i; sh.u_cnt[lo] = 1;
-          if constexpr (FLANK) sh.f_uidx[i] = (uint16_t)i;
-        }
-        ++nu;
+      //      Which reads are equal is settled first, a lane per read (gt_equal_reads: fr[t] = the first kept read with the sequence of
+      //      read lane + 64 t); the insertion then runs over those first reads only and adds each one's multiplicity.  Segments that are
+      //      not staged, a hash collision and TRGT_GT_SERIAL leave every read its own first read, and the loop is the plain insertion of
+      //      all n reads, which finds the equal ones itself (eq below).
+      GTP_MARK(GTP_CAND);
+      int fr[R];
+      bool grouped = fits && !serial;
+      if (grouped) { grouped = gt_equal_reads<R>(sh, n, lane, weak_hash, fr); if (!grouped) gt_tally(a.rp, RC_GT_COLLISION, lane); }
+      else if (!serial) gt_tally(a.rp, RC_GT_NOFIT, lane);
+      unsigned long long first[R];  // uniform: the reads to insert
+#pragma unroll
+      for (int t = 0; t < R; ++t) {
+        const int i = lane + 64 * t;
+        if (!grouped) fr[t] = i < n ? i : -1;
+        first[t] = __ballot(i < n && fr[t] == i);
+        if constexpr (FLANK) { if (i < n) sh.f_uidx[i] = (uint16_t)fr[t]; }
       }
+      __syncthreads();
+      int nu = 0;
+#pragma unroll
+      for (int t = 0; t < R; ++t) {
+        for (unsigned long long m = first[t]; m; m &= m - 1ull) {
+          const int i = 64 * t + __ffsll((long long)m) - 1;
+          int mult = 0;
+#pragma unroll
+          for (int tt = 0; tt < R; ++tt) mult += __popcll(__ballot(fr[tt] == i));
+          int lo = 0, hi = nu, eq = -1;
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            const int r = sh.u_rep[mid];
+            const int c = cmp_seg(i, r);
+            if (c == 0) { eq = mid; break; }
+            if (c < 0) hi = mid; else lo = mid + 1;
+          }
+          // (the list is written by lane 0 only; the comparisons of the next round read it back in program order: one wave, one LDS queue)
+          if (eq >= 0) { if (lane == 0) { sh.u_cnt[eq] += (uint16_t)mult; if constexpr (FLANK) sh.f_uidx[i] = sh.u_rep[eq]; } continue; }
+          if (lane == 0) {
+            for (int q = nu; q > lo; --q) { sh.u_rep[q] = sh.u_rep[q - 1]; sh.u_cnt[q] = sh.u_cnt[q - 1]; }
+            sh.u_rep[lo] = (uint16_t)i; sh.u_cnt[lo] = (uint16_t)mult;
+          }
+          ++nu;
+        }
+      }
+      __syncthreads();
+      GTP_MARK(GTP_SEQ);
       // ---- FLANK: two sizes at most 10 apart (tr.rs:69-75) and tags that split the reads replace everything below; the size
       //      genotyper's own repair is not queued for such a locus
       bool by_tags = false;
@@ -805,26 +1010,70 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
         if (a.hp_tag && n_gt == 2 && adiff_u(size[0], size[1]) <= 10) by_tags = flank_route(sh, a, l, r0, n, nu, lane, fits, refn, refo);
       }
       auto ulen_of = [&](int q) { return sh.s_len[sh.u_rep[q]]; };
-      auto closest = [&](uint32_t target) { uint32_t c = ulen_of(0); for (int q = 0; q < nu; ++q) if (adiff_u(c, target) > adiff_u(ulen_of(q), target)) c = ulen_of(q); return c; };
-      auto most_frequent = [&](uint32_t len) { int best = -1; for (int q = 0; q < nu; ++q) if (ulen_of(q) == len && (best < 0 || sh.u_cnt[q] >= sh.u_cnt[best])) best = q; return best; };
+      GTP_MARK(GTP_ROUTE);
+      // ---- the picks: lane q holds the length and the multiplicity of unique sequence q (q + 64 t), the loops over the list are
+      //      ballots and reductions.  closest: the first minimum in u_rep order; most_frequent: the last maximum (>=).
+      uint32_t ql[R], qc[R];
+#pragma unroll
+      for (int t = 0; t < R; ++t) { const int q = lane + 64 * t; ql[t] = q < nu ? ulen_of(q) : 0u; qc[t] = q < nu ? sh.u_cnt[q] : 0u; }
+      auto len_in_group = [&](uint32_t len, int al) {
+        if (n_gt == 1) return true;
+        const uint32_t d1 = adiff_u(len, size[0]), d2 = adiff_u(len, size[1]);
+        return al == 0 ? d1 <= d2 : d2 < d1;
+      };
+      auto in_group = [&](int q, int al) { return len_in_group(ulen_of(q), al); };
+      auto closest = [&](uint32_t target) {
+        if (serial) { uint32_t c = ulen_of(0); for (int q = 0; q < nu; ++q) if (adiff_u(c, target) > adiff_u(ulen_of(q), target)) c = ulen_of(q); return c; }
+        uint32_t d[R], best = 0xFFFFFFFFu;
+#pragma unroll
+        for (int t = 0; t < R; ++t) { d[t] = lane + 64 * t < nu ? adiff_u(ql[t], target) : 0xFFFFFFFFu; best = d[t] < best ? d[t] : best; }
+        best = wave_min_u(best);
+        uint32_t c = 0;
+#pragma unroll
+        for (int t = R - 1; t >= 0; --t) {
+          const unsigned long long bal = __ballot(lane + 64 * t < nu && d[t] == best);
+          if (bal) c = (uint32_t)__builtin_amdgcn_readlane((int)ql[t], __ffsll((long long)bal) - 1);
+        }
+        return c;
+      };
+      auto most_frequent = [&](uint32_t len) {
+        if (serial) { int best = -1; for (int q = 0; q < nu; ++q) if (ulen_of(q) == len && (best < 0 || sh.u_cnt[q] >= sh.u_cnt[best])) best = q; return best; }
+        uint32_t mx = 0;
+#pragma unroll
+        for (int t = 0; t < R; ++t) if (lane + 64 * t < nu && ql[t] == len && qc[t] > mx) mx = qc[t];
+        mx = wave_max_u(mx);
+        int best = -1;
+#pragma unroll
+        for (int t = 0; t < R; ++t) {
+          const unsigned long long bal = __ballot(lane + 64 * t < nu && ql[t] == len && qc[t] == mx);
+          if (bal) best = 64 * t + 63 - __clzll((long long)bal);
+        }
+        return best;
+      };
       int pick[2] = {most_frequent(closest(size[0])), -1};
       int n_pick = 1;
       if (n_gt != 1 && size[0] != size[1]) { pick[1] = most_frequent(closest(size[1])); n_pick = 2; }
       bool majority = true, lacks[2] = {false, false};
-      auto in_group = [&](int q, int al) {
-        if (n_gt == 1) return true;
-        const uint32_t d1 = adiff_u(ulen_of(q), size[0]), d2 = adiff_u(ulen_of(q), size[1]);
-        return al == 0 ? d1 <= d2 : d2 < d1;
-      };
       for (int al = 0; al < n_pick; ++al) {  // split(): majority support of the pick inside its group, else stage B is needed
         uint64_t coverage = 0, ref_count = 0;
-        for (int q = 0; q < nu; ++q) {
-          if (!in_group(q, al)) continue;
-          coverage += sh.u_cnt[q];
-          if (q == pick[al]) ref_count = sh.u_cnt[q];
+        if (serial) {
+          for (int q = 0; q < nu; ++q) {
+            if (!in_group(q, al)) continue;
+            coverage += sh.u_cnt[q];
+            if (q == pick[al]) ref_count = sh.u_cnt[q];
+          }
+        } else {
+          uint32_t cov = 0, ref = 0;
+#pragma unroll
+          for (int t = 0; t < R; ++t) {
+            const int q = lane + 64 * t;
+            if (q < nu && len_in_group(ql[t], al)) { cov += qc[t]; if (q == pick[al]) ref = qc[t]; }
+          }
+          coverage = wave_sum_u(cov); ref_count = wave_sum_u(ref);
         }
         if (!(2 * ref_count >= coverage)) { majority = false; lacks[al] = true; }
       }
+      GTP_MARK(GTP_PICK);
       if (by_tags) {}
       else if (!majority) {
         // ---- stage B on the device: one vote group per allele without majority support, one alignment job per unique sequence of
@@ -874,14 +1123,34 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
         for (int al = 0; al < n_pick; ++al) { rep[al] = sh.u_rep[pick[al]]; aln[al] = sh.s_len[rep[al]]; }
         int n_al = n_pick;
         if (ploidy == 2 && n_al == 1) { rep[1] = rep[0]; aln[1] = aln[0]; n_al = 2; }
-        int by_hap[2] = {0, 0}, tie = 1;
-        for (int i = 0; i < n; ++i) {
-          int cc = 0;
-          if (n_al == 2) {
-            const uint32_t d1 = adiff_u(sh.s_len[i], aln[0]), d2 = adiff_u(sh.s_len[i], aln[1]);
-            if (d1 < d2) cc = 0; else if (d1 > d2) cc = 1; else { tie = (tie + 1) % 2; cc = tie; }
+        int by_hap[2] = {0, 0};
+        if (serial) {
+          int tie = 1;
+          for (int i = 0; i < n; ++i) {
+            int cc = 0;
+            if (n_al == 2) {
+              const uint32_t d1 = adiff_u(sh.s_len[i], aln[0]), d2 = adiff_u(sh.s_len[i], aln[1]);
+              if (d1 < d2) cc = 0; else if (d1 > d2) cc = 1; else { tie = (tie + 1) % 2; cc = tie; }
+            }
+            sh.cls[i] = (int8_t)cc; by_hap[cc] += 1;
           }
-          sh.cls[i] = (int8_t)cc; by_hap[cc] += 1;
+        } else {
+          // a lane per read; the k-th tied read, k from 0, gets k % 2 (the tie toggle starts at 1 and is advanced before use)
+          int ties = 0;
+          for (int base = 0; base < n; base += 64) {
+            const int i = base + lane;
+            int cc = 0; bool tied = false;
+            if (n_al == 2 && i < n) {
+              const uint32_t d1 = adiff_u(sh.s_len[i], aln[0]), d2 = adiff_u(sh.s_len[i], aln[1]);
+              cc = d1 > d2 ? 1 : 0; tied = d1 == d2;
+            }
+            const unsigned long long tb = __ballot(tied);
+            if (tied) cc = (ties + __popcll(tb & ((1ull << lane) - 1ull))) & 1;
+            if (i < n) sh.cls[i] = (int8_t)cc;
+            const int ones = __popcll(__ballot(i < n && cc == 1));
+            by_hap[1] += ones; by_hap[0] += (n - base < 64 ? n - base : 64) - ones;
+            ties += __popcll(tb);
+          }
         }
         auto eq_ref = [&](int al) {
           return fits ? cmp_lds(sh.bytes + sh.s_loff[rep[al]], aln[al], sh.bytes + sh.ref_off, refn) == 0 : cmp_bytes(seg_glob(rep[al]), aln[al], a.tr_blob + refo, refn) == 0;
@@ -889,7 +1158,7 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
         int order[2] = {0, 1}; int flip = 0;
         if (n_gt != 1 && !eq_ref(0) && eq_ref(1)) { order[0] = 1; order[1] = 0; flip = 1; }
         for (int oi = 0; oi < n_gt; ++oi)
-          if (aln[order[oi]] > a.allele_cap[l]) sh.bail = 1;  // the host path reports the error
+          if (aln[order[oi]] > allele_cap_l) sh.bail = 1;  // the host path reports the error
         sh.res_n_gt = n_gt; sh.res_flip = flip;
         for (int oi = 0; oi < n_gt; ++oi) {
           const int al = order[oi];
@@ -898,19 +1167,38 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
       }
     }
     __syncthreads();
+    GTP_MARK(GTP_CLASS);
   }
   // ---- outputs, by the whole wave
   const bool done = n > 0 && !sh.bail;
-  for (int i = lane; i < nr; i += 64) { a.classification[r0 + i] = -1; a.read_rank[r0 + i] = -1; }
-  if (n > 0 && sh.bail) { if (lane == 0) a.need_host[l] = (uint8_t)(sh.bail == 2 ? 2 : 1); return; }
-  if (!done) return;
-  __syncthreads();  // the -1 defaults above are ordered before the entries of the kept reads (same wave, same addresses)
+  if (serial) {
+    for (int i = lane; i < nr; i += 64) { a.classification[r0 + i] = -1; a.read_rank[r0 + i] = -1; }
+    if (n > 0 && sh.bail) { if (lane == 0) a.need_host[l] = (uint8_t)(sh.bail == 2 ? 2 : 1); return; }
+    if (!done) return;
+    __syncthreads();  // the -1 defaults above are ordered before the entries of the kept reads (same wave, same addresses)
+  } else {
+    // every read's entries are written once: its rank among the kept reads (-1: not kept, or no genotype) is collected in LDS first
+    // (r_len is done with behind the selection), so that no store waits for an earlier one to the same address
+    int32_t* rank = reinterpret_cast<int32_t*>(sh.r_len);
+    for (int i = lane; i < nr; i += 64) rank[i] = -1;
+    __syncthreads();
+    if (done) for (int i = lane; i < n; i += 64) if (sh.s_read[i] < (uint32_t)nr) rank[sh.s_read[i]] = i;
+    __syncthreads();
+    const int flip_all = done ? sh.res_flip : 0;
+    for (int i = lane; i < nr; i += 64) {
+      const int rk = rank[i];
+      a.classification[r0 + i] = rk < 0 ? -1 : (flip_all ? 1 - sh.cls[rk] : sh.cls[rk]);
+      a.read_rank[r0 + i] = rk;
+    }
+    if (n > 0 && sh.bail) { if (lane == 0) a.need_host[l] = (uint8_t)(sh.bail == 2 ? 2 : 1); return; }
+    if (!done) return;
+  }
   const int n_gt = sh.res_n_gt;
   for (int oi = 0; oi < n_gt; ++oi) {
     const int rep = sh.res_rep[oi];
     const uint32_t len = sh.s_len[rep];
     const uint8_t* src = fits ? sh.bytes + sh.s_loff[rep] : seg_glob(rep);
-    uint8_t* dst = a.allele_blob + a.allele_off[2 * l + oi];
+    uint8_t* dst = a.allele_blob + allele_at[oi];
     for (uint32_t b = lane; b < len; b += 64) dst[b] = src[b];
     if (lane == 0) {
       a.allele_len[2 * l + oi] = len;
@@ -919,11 +1207,13 @@ __global__ void __launch_bounds__(64) locus_genotype_kernel(const GtArgsOf<FLANK
       if (a.gt_size) a.gt_size[2 * l + oi] = (int32_t)len;  // (a pick with majority support has the genotype's size)
     }
   }
-  for (int i = lane; i < n; i += 64) {
-    a.classification[r0 + sh.s_read[i]] = sh.res_flip ? 1 - sh.cls[i] : sh.cls[i];
-    a.read_rank[r0 + sh.s_read[i]] = i;
-  }
+  if (serial)
+    for (int i = lane; i < n; i += 64) {
+      a.classification[r0 + sh.s_read[i]] = sh.res_flip ? 1 - sh.cls[i] : sh.cls[i];
+      a.read_rank[r0 + sh.s_read[i]] = i;
+    }
   if (lane == 0) { a.n_alleles[l] = n_gt; a.n_spanning_reads[l] = (uint32_t)n; a.flipped[l] = (uint8_t)sh.res_flip; }
+  GTP_MARK(GTP_OUT);
 }
 
 // ---- behind the consensus alignments and the column voting of the loci that waited for a repair: the rest of genotype_size::genotype
