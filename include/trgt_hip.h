@@ -403,6 +403,14 @@ int trgt_locus_meth_kernel_ms(const trgt_hip_ctx* ctx, double out[2]);
  * trgt_hip_plot.h, which this header includes: every program that includes trgt_hip.h has them. */
 #include "trgt_hip_plot.h"
 
+/* ------------------------------------------------------------------ merge */
+/* The consumer of the VCF: what `trgt merge` computes per site between reading N records and writing one, merge_exact
+ * (src/merge/strategy/exact.rs:6-88) -- the distinct ALT sequences of all entries ordered by (length, bytes) behind the one REF, and
+ * every GT index rewritten -- for a whole batch of sites.  The two structures and the five prototypes -- trgt_merge_exact_batch(ctx,
+ * in, out), its host twin trgt_merge_exact_host(in, out), trgt_merge_site_alleles_limit(), trgt_merge_stats(ctx, out[4]),
+ * trgt_merge_kernel_ms(ctx, out[2]) -- are declared and documented in trgt_hip_merge.h, which this header includes. */
+#include "trgt_hip_merge.h"
+
 /* Host helper for callers that hold ASCII reads and want TRGT_READS_BAM4 (a BAM reader has the codes already: trgt_ingest_params.
  * keep_bam4): packs read r (ascii + read_off[r], read_len[r] bases) to packed + packed_off[r], where packed_off[r] is written as the
  * running sum of ceil(read_len / 2).  Letters outside "=ACMGRSVTWYHKDBN" become N, as in htslib.  packed needs

@@ -59,6 +59,8 @@ struct trgt_knobs {
   bool host_hmm_lists = false;  // TRGT_HOST_HMM_LISTS: stage C job lists built by the host after the genotyper (not resolved on the device)
   bool gt_serial = false;    // TRGT_GT_SERIAL (DEV): the size genotyper (locus_gt.hpp) takes every section read by read, as before its lane-parallel sections
   bool gt_weak_hash = false; // TRGT_GT_WEAK_HASH (DEV): its sequence hash is the length alone: distinct sequences collide, the comparison and the plain insertion run
+  int merge_hash_bits = 64;  // TRGT_MERGE_HASH_BITS (DEV): merge_hash_kernel (merge_exact.hip) keeps this many bits of its sequence hash: with 4 nearly every pair collides and the bytes decide
+  int merge_lane_max = 256;  // TRGT_MERGE_LANE_MAX (DEV): alleles of up to this many bytes are hashed one per lane, longer ones one per wave (profiles/merge_exact_timing.txt)
   bool debug = false;        // TRGT_WFA_DEBUG: launch plans on stderr (synchronises)
   bool hmm_resolve_one_wg = false;   // TRGT_HMM_RESOLVE_ONE_WG: the stage-C job list by the one-workgroup kernel, class after class
   bool wfa_no_wave_variant = false;  // TRGT_WFA_NO_WAVE_VARIANT: one-wave batches of the generic kernel take the 168-register build (three waves per SIMD)
@@ -140,6 +142,8 @@ struct trgt_hip_ctx {
   FlankRouteState route[FR_N];  // the opt-in device routes of genotype_flank, indexed by FlankRoute (above)
   double meth_ms[2] = {0, 0};   // trgt_locus_meth_kernel_ms: tr_meth_kernel and allele_meth_kernel of the last timed trgt_locus_meth_batch
   double plot_ms[2] = {0, 0};   // trgt_plot_kernel_ms: plot_motif_segs_kernel and plot_read_segs_kernel of the last timed trgt_plot_align_batch
+  int64_t merge_stats[4] = {0, 0, 0, 0};  // trgt_merge_stats: the last trgt_merge_exact_batch (sites on the device, by the host twin, with a status, HBM byte comparisons)
+  double merge_ms[2] = {0, 0};  // trgt_merge_kernel_ms: merge_hash_kernel and merge_site_kernel of the last timed trgt_merge_exact_batch
   int num_cus = 256;
   int band_occ = 0;  // resident workgroups per CU of wfa_band_kernel (wfa_band.hip), asked at its first launch (0: not yet)
   // cached device buffers, indexed by slot
@@ -311,6 +315,8 @@ enum Slot {
   S_FS_BANDFALL, S_LW_BANDFALL,  // flank location: the banded jobs the one-wave forward kernel leaves to the LDS launch (wfa_band.hip), short and long reads
   S_METH_READS, S_METH_CALLS, S_METH_JOBS, S_METH_LOCI, S_METH_LEVEL, S_METH_LEN, S_METH_FLAG, S_METH_OUT, S_METH_NREADS, S_METH_PERREAD,  // trgt_locus_meth_batch (locus_meth.hip)
   S_PLOT_IN, S_PLOT_PATH, S_PLOT_HMMOUT, S_PLOT_WORK, S_PLOT_WFAOUT, S_PLOT_PSEG, S_PLOT_NPSEG, S_PLOT_RSEG, S_PLOT_NRSEG, S_PLOT_BPROJ, S_PLOT_SCORE, S_PLOT_POFF, S_PLOT_PACKED,  // trgt_plot_align_batch (plot_align.hip)
+  S_MERGE_BLOB, S_MERGE_OFF, S_MERGE_LEN, S_MERGE_SEB, S_MERGE_EAB, S_MERGE_EGB, S_MERGE_GT, S_MERGE_HASH, S_MERGE_KEY, S_MERGE_LIST, S_MERGE_SLOT, S_MERGE_STATUS, S_MERGE_NOUT,
+  S_MERGE_SRC, S_MERGE_MAP, S_MERGE_GTOUT, S_MERGE_CNT,  // trgt_merge_exact_batch (merge_exact.hip)
   S_COUNT
 };
 // pinned host buffer slots
@@ -666,6 +672,7 @@ hipError_t make_stream(trgt_hip_ctx* c, hipStream_t* s);
 hipError_t make_side_stream(trgt_hip_ctx* c, hipStream_t* s);
 void ctx_next_stream_priority(int p);
 void ctx_next_in_pool(bool on);
+void ctx_free_error(const char* msg);  // sets the context-free error string, what trgt_hip_last_error(NULL) returns
 
 inline void resolve_timing(trgt_hip_ctx* c) {
   for (auto& p : c->pending) {

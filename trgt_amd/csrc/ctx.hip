@@ -34,6 +34,7 @@ static thread_local int g_next_stream_priority = 0;
 static thread_local bool g_next_in_pool = false;
 void ctx_next_stream_priority(int p) { g_next_stream_priority = p; }
 void ctx_next_in_pool(bool on) { g_next_in_pool = on; }
+void ctx_free_error(const char* msg) { g_create_err = msg; }
 hipError_t make_stream(trgt_hip_ctx* c, hipStream_t* s) {
   return c->stream_priority ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, c->stream_priority) : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 }
@@ -97,6 +98,7 @@ int trgt_hip_create(int device, trgt_hip_ctx** out) {
     k.flank_threads = DEV_NUM("TRGT_FLANK_THREADS", k.flank_threads); k.heavy_threads = DEV_NUM("TRGT_HEAVY_THREADS", 0); k.heavy_band = std::max(0, std::min(num("TRGT_HEAVY_BAND", k.heavy_band), 256));
     k.win_threads = DEV_NUM("TRGT_WIN_THREADS", k.win_threads); { const int bt = DEV_NUM("TRGT_BAND_THREADS", k.band_threads); k.band_threads = bt == 128 || bt == 256 ? bt : 64; } k.win_segments = DEV_NUM("TRGT_WIN_SEGMENTS", k.win_segments); k.win_lds = DEV_FLAG("TRGT_WIN_LDS"); k.band_lds = DEV_FLAG("TRGT_BAND_LDS");
     k.gt_serial = DEV_FLAG("TRGT_GT_SERIAL"); k.gt_weak_hash = DEV_FLAG("TRGT_GT_WEAK_HASH");
+    k.merge_hash_bits = std::max(1, std::min(DEV_NUM("TRGT_MERGE_HASH_BITS", k.merge_hash_bits), 64)); k.merge_lane_max = std::max(0, DEV_NUM("TRGT_MERGE_LANE_MAX", k.merge_lane_max));
     k.grid_per_cu = DEV_NUM("TRGT_WFA_GRID_PER_CU", 0); k.filter_per_cu = DEV_NUM("TRGT_FILTER_PER_CU", 0);
     k.one_launch = DEV_FLAG("TRGT_WFA_ONE_LAUNCH"); k.no_spec = DEV_FLAG("TRGT_WFA_NO_SPEC"); k.no_window = flag("TRGT_WFA_NO_WINDOW"); k.no_hamming = flag("TRGT_NO_HAMMING"); k.no_indel_shortcut = flag("TRGT_NO_INDEL_SHORTCUT"); k.no_heavy_window = DEV_FLAG("TRGT_NO_HEAVY_WINDOW"); k.no_sibling_rule = DEV_FLAG("TRGT_NO_SIBLING_RULE"); k.no_settled_sibling_rule = DEV_FLAG("TRGT_NO_SETTLED_SIBLING_RULE"); k.no_lcs_rule = DEV_FLAG("TRGT_NO_LCS_RULE"); { const char* e = TRGT_DEV_ENV("TRGT_EARLY_ADAPTIVE"); if (e && *e) k.early_adaptive = std::strcmp(e, "0") != 0; }
     k.no_filter = flag("TRGT_WFA_NO_FILTER"); k.one_stream = DEV_FLAG("TRGT_FLANK_ONE_STREAM"); k.host_genotyper = flag("TRGT_HOST_GENOTYPER"); k.host_hmm_lists = DEV_FLAG("TRGT_HOST_HMM_LISTS"); k.no_early = flag("TRGT_WFA_NO_EARLY"); k.stage_lock = flag("TRGT_STAGE_LOCK"); k.no_long_filter = flag("TRGT_NO_LONG_FILTER"); k.no_long_window = DEV_FLAG("TRGT_NO_LONG_WINDOW"); k.filter_force = DEV_NUM("TRGT_FILTER_FORCE", 0); k.filter_one_launch = DEV_FLAG("TRGT_FILTER_ONE_LAUNCH"); k.filter_serial = DEV_FLAG("TRGT_FILTER_SERIAL"); k.filter_side = DEV_FLAG("TRGT_FILTER_SIDE"); k.wfa_no_stage = DEV_FLAG("TRGT_WFA_NO_STAGE"); k.wfa_no_wave_variant = DEV_FLAG("TRGT_WFA_NO_WAVE_VARIANT"); k.hmm_resolve_one_wg = DEV_FLAG("TRGT_HMM_RESOLVE_ONE_WG"); k.debug = flag("TRGT_WFA_DEBUG");
