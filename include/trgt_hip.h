@@ -410,6 +410,10 @@ int trgt_locus_meth_kernel_ms(const trgt_hip_ctx* ctx, double out[2]);
  * in, out), its host twin trgt_merge_exact_host(in, out), trgt_merge_site_alleles_limit(), trgt_merge_stats(ctx, out[4]),
  * trgt_merge_kernel_ms(ctx, out[2]) -- are declared and documented in trgt_hip_merge.h, which this header includes. */
 #include "trgt_hip_merge.h"
+/* ... and what merge_variants / merge_variant (src/merge/vcf_processor.rs) compute in front of it for one contig: the sites (the heap
+ * over positions), the padding base of pre-1.0 files, the concatenated entries with their dense FORMAT rows, the template records: a
+ * ready trgt_merge_in.  Two more structures and four prototypes, declared and documented in trgt_hip_merge_sites.h. */
+#include "trgt_hip_merge_sites.h"
 
 /* Host helper for callers that hold ASCII reads and want TRGT_READS_BAM4 (a BAM reader has the codes already: trgt_ingest_params.
  * keep_bam4): packs read r (ascii + read_off[r], read_len[r] bases) to packed + packed_off[r], where packed_off[r] is written as the

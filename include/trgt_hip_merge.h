@@ -6,8 +6,9 @@
  *   - every GT index rewritten into the new list.
  *
  * Part of include/trgt_hip.h, which includes this file inside its extern "C" block; not meant to be included on its own.  Additions to
- * ABI 11.  Reading the VCFs, the heap over positions, the padding of pre-1.0 files, header merging, the FORMAT concatenation of
- * process_format_fields (vcf_processor.rs) and writing stay with the caller.
+ * ABI 11.  The heap over positions, the padding of pre-1.0 files and the FORMAT concatenation of process_format_fields
+ * (vcf_processor.rs) are trgt_merge_sites_batch (trgt_hip_merge_sites.h), which leaves a ready trgt_merge_in; reading the VCFs, header
+ * merging, the FORMAT strings themselves, skip_n / process_n and writing stay with the caller.
  *
  * Input.  An ENTRY is one input VCF's record at a site; an entry with zero alleles stands for a file that has no record there
  * (process_missing_record).  Site s owns entries [site_entry_begin[s], site_entry_begin[s + 1]); entry e owns alleles

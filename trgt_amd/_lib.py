@@ -99,6 +99,8 @@ PLOT_EXPORTS = ["trgt_plot_align_batch", "trgt_plot_seg_capacity", "trgt_plot_ke
 # The five entry points of the merge path (include/trgt_hip_merge.h, csrc/merge_exact.hip; mirrored by trgt_amd/merge.py), a list of its own
 # checked the same way
 MERGE_EXPORTS = ["trgt_merge_exact_batch", "trgt_merge_exact_host", "trgt_merge_site_alleles_limit", "trgt_merge_stats", "trgt_merge_kernel_ms"]
+# ... and the four in front of them (include/trgt_hip_merge_sites.h, csrc/merge_sites.hip): sites, padding and FORMAT rows of one contig
+MERGE_SITES_EXPORTS = ["trgt_merge_sites_batch", "trgt_merge_sites_host", "trgt_merge_sites_stats", "trgt_merge_sites_kernel_ms"]
 
 # The opt-in device routes of genotype_flank (FlankRoute, csrc/common.hpp): (name, C setter, C statistics call, its width, docstring of
 # Context.set_<name>_device, docstring of Context.<statistics name without trgt_hip_>).  Context gets the two methods of every row below.
@@ -195,7 +197,7 @@ def lib():
         missing = [n for n in EXPORTS + CLUSTER_FLANK_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_SNV_EXPORTS if not hasattr(L, n)] + [n for n in CLUSTER_DEEP_FLANK_EXPORTS if not hasattr(L, n)]
         missing += [n for n in CLUSTER_DEEP_SNV_EXPORTS if not hasattr(L, n)]
         missing += [n for n in PLOT_EXPORTS if not hasattr(L, n)]
-        missing += [n for n in MERGE_EXPORTS if not hasattr(L, n)]
+        missing += [n for n in MERGE_EXPORTS + MERGE_SITES_EXPORTS if not hasattr(L, n)]
         if missing:
             raise TrgtHipError("%s does not export %s (stale build?)" % (_SO, ", ".join(missing)))
         L.trgt_hip_last_error.restype = C.c_char_p
@@ -238,6 +240,10 @@ def lib():
         L.trgt_merge_site_alleles_limit.restype = C.c_int32
         L.trgt_merge_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
         L.trgt_merge_kernel_ms.argtypes = [_VP, C.POINTER(C.c_double)]
+        L.trgt_merge_sites_batch.argtypes = [_VP, _VP, _VP]
+        L.trgt_merge_sites_host.argtypes = [_VP, _VP]
+        L.trgt_merge_sites_stats.argtypes = [_VP, C.POINTER(C.c_int64)]
+        L.trgt_merge_sites_kernel_ms.argtypes = [_VP, C.POINTER(C.c_double)]
         L.trgt_reads_pack_bam4.argtypes = [_VP, C.c_int64, _VP, _VP, _VP, _VP]
         L.trgt_reads_pack_bam4.restype = C.c_int64
         L.trgt_locus_batch_submit.argtypes = [_VP, _VP, _VP, _VP, C.POINTER(C.c_int64)]
@@ -300,6 +306,13 @@ class Context:
         status != 0, byte comparisons that went to HBM)."""
         out = (C.c_int64 * 4)()
         self.check(lib().trgt_merge_stats(self.handle, out))
+        return tuple(int(v) for v in out)
+
+    def merge_sites_stats(self):
+        """trgt_merge_sites_stats of the context's last trgt_merge_sites_batch: (sites, sites with a stage status, padded records, blob
+        bytes written)."""
+        out = (C.c_int64 * 4)()
+        self.check(lib().trgt_merge_sites_stats(self.handle, out))
         return tuple(int(v) for v in out)
 
     def timing_enable(self, on=True):

@@ -143,6 +143,8 @@ struct trgt_hip_ctx {
   double meth_ms[2] = {0, 0};   // trgt_locus_meth_kernel_ms: tr_meth_kernel and allele_meth_kernel of the last timed trgt_locus_meth_batch
   double plot_ms[2] = {0, 0};   // trgt_plot_kernel_ms: plot_motif_segs_kernel and plot_read_segs_kernel of the last timed trgt_plot_align_batch
   int64_t merge_stats[4] = {0, 0, 0, 0};  // trgt_merge_stats: the last trgt_merge_exact_batch (sites on the device, by the host twin, with a status, HBM byte comparisons)
+  int64_t merge_sites_stats[4] = {0, 0, 0, 0};  // trgt_merge_sites_stats: the last trgt_merge_sites_batch (sites, with a stage status, padded records, blob bytes written)
+  double merge_sites_ms[3] = {0, 0, 0};  // trgt_merge_sites_kernel_ms: grouping, fill and blob copy of the last timed trgt_merge_sites_batch
   double merge_ms[2] = {0, 0};  // trgt_merge_kernel_ms: merge_hash_kernel and merge_site_kernel of the last timed trgt_merge_exact_batch
   int num_cus = 256;
   int band_occ = 0;  // resident workgroups per CU of wfa_band_kernel (wfa_band.hip), asked at its first launch (0: not yet)
@@ -317,6 +319,7 @@ enum Slot {
   S_PLOT_IN, S_PLOT_PATH, S_PLOT_HMMOUT, S_PLOT_WORK, S_PLOT_WFAOUT, S_PLOT_PSEG, S_PLOT_NPSEG, S_PLOT_RSEG, S_PLOT_NRSEG, S_PLOT_BPROJ, S_PLOT_SCORE, S_PLOT_POFF, S_PLOT_PACKED,  // trgt_plot_align_batch (plot_align.hip)
   S_MERGE_BLOB, S_MERGE_OFF, S_MERGE_LEN, S_MERGE_SEB, S_MERGE_EAB, S_MERGE_EGB, S_MERGE_GT, S_MERGE_HASH, S_MERGE_KEY, S_MERGE_LIST, S_MERGE_SLOT, S_MERGE_STATUS, S_MERGE_NOUT,
   S_MERGE_SRC, S_MERGE_MAP, S_MERGE_GTOUT, S_MERGE_CNT,  // trgt_merge_exact_batch (merge_exact.hip)
+  S_MSITES_0, S_MSITES_LAST = S_MSITES_0 + 59,  // trgt_merge_sites_batch (merge_sites.hip): its 60 inputs, work arrays and staged outputs, numbered and counted there
   S_COUNT
 };
 // pinned host buffer slots
